@@ -9,19 +9,22 @@ guppy5_stats penalties, max_b_rows=20000.
 With --gpus N every rank runs the same-sized, different batch (weak scaling,
 reads dealt by index); the only collective is the final max/sum reduction.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Order of business (one JSON line on rank 0 at the end):
+Order of business (one JSON line on rank 0 at the end).  A plain run does 1 and 3 only; the items marked
+[full] run with --full and fill the fields of the line that a plain run leaves null:
   1. synthetic reads of this rank                                   (host, before anything touches HIP)
-  2. CPU baseline: oracle/ (plain-C port of the reference DP) on one core and on the host's cores -- forked
+  2. [full] CPU baseline: oracle/ (plain-C port of the reference DP) on one core and on the host's cores -- forked
      worker pools, so this also runs BEFORE the GPU runtime is initialised; N=1 only
-  3. W warm-up steps, then EXACTLY K timed steps, device-resident    -> value, ms_per_step, roofline
-  4. the same batch through the host-buffer entry point (pinned host memory in and out) -> value_pcie_inclusive
-  5. a sustained leg: device-resident steps for >= --sustain seconds -> sustained (the GPU is busy long enough
+  3. W warm-up steps, then EXACTLY K timed steps, device-resident    -> value, ms_per_step
+     (--dump-outputs DIR: rank 0 then writes what the last timed step returned, see dump_outputs)
+  3a. [full] every output string with a committed oracle digest checked -> parity; the fill kernel alone -> roofline
+  4. [full] the same batch through the host-buffer entry point (pinned host memory in and out) -> value_pcie_inclusive
+  5. [full] a sustained leg: device-resident steps for >= --sustain seconds -> sustained (the GPU is busy long enough
      for an outside sampler to see it; not part of `value`), and `production_default`: one second of the tool's
      default band (r=30) on 4 000 reads, whole path pipelined -- the number a user of realign.py sees per GPU
-  6. every CPU string compared with the GPU's.
+  6. [full] every CPU string compared with the GPU's.
 """
 import argparse
 import ctypes as C
@@ -171,6 +174,28 @@ def digest_parity(key, read_index, out_host, oo, out_len):
     return compared, bad
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(path, out, ln, st, oo):
+    """--dump-outputs: the arrays one call of the timed path hands back (string buffer, lengths, statuses), as floats.
+    lengths.npy / status.npy (float64): per read, the length of its string and its status.  alignments.npy (float32):
+    the character codes of the strings of the reads listed in alignment_reads.npy (float64, ascending), concatenated in
+    that order -- every read when they fit into DUMP_BYTES, else the longest prefix of a fixed seeded permutation of
+    the reads that does.  Equal outputs give equal files."""
+    os.makedirs(path, exist_ok=True)
+    out_len, status, buf = ln.cpu().numpy(), st.cpu().numpy(), out.cpu().numpy()
+    n = len(out_len)
+    budget = DUMP_BYTES - 3 * 8 * n - 4 * 128                  # (lengths, status, read list, .npy headers)
+    order = np.random.default_rng(0).permutation(n)
+    take = np.sort(order[np.cumsum(4 * out_len[order]) <= budget])
+    strings = np.concatenate([buf[oo[k]:oo[k] + out_len[k]] for k in take] + [np.zeros(0, np.uint8)])
+    np.save(os.path.join(path, "lengths.npy"), out_len.astype(np.float64))
+    np.save(os.path.join(path, "status.npy"), status.astype(np.float64))
+    np.save(os.path.join(path, "alignment_reads.npy"), take.astype(np.float64))
+    np.save(os.path.join(path, "alignments.npy"), strings.astype(np.float32))
+
+
 def cpu_baseline(args, refs, seqs, cigs, sub, nps):
     """The oracle (plain-C port of the reference's align(), proven equal to the Cython build in the build
     container) on the GPU box's host cores: one core on a sample, then a process pool over reads -- the
@@ -281,6 +306,11 @@ def main():
     ap.add_argument("--inflight", type=int, default=1,
                     help="batches in flight per GPU: each has its own context (stream + work buffers) and host thread, "
                          "so one batch's traceback / gather and the next one's preparation run beside a fill kernel")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the digest parity check, the fill kernel alone (roofline), the PCIe-inclusive, "
+                         "sustained and production legs; the options above that configure them act only with --full")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -302,13 +332,13 @@ def main():
         refs = [refs[k] for k in rep]; seqs = [seqs[k] for k in rep]; cigs = [cigs[k] for k in rep]
     sub, nps, _, _ = aln.load_default_tables()
     prod_reads = None
-    if args.production > 0:
+    if args.full and args.production > 0:
         prod_reads = make_reads(synth, args, args.production_reads, rank, world, ref_len=10_000, mixed=False, base_seed=2)
     t_generate = time.perf_counter() - t_setup0          # host-side input generation of this rank: BEFORE the timed region
 
     # ---- 2. CPU baseline (forked pools: before the HIP runtime exists in this process)
     cpu, cpu_want = None, {}
-    if rank == 0 and world == 1 and not args.no_cpu:      # reported at N=1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:      # reported at N=1 only
         cpu, cpu_want = cpu_baseline(args, refs, seqs, cigs, sub, nps)
 
     import torch
@@ -427,8 +457,9 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     assert len(stage) == args.steps
-    for o in outs[1:min(n_ctx, args.steps + warmup)]:             # every batch in flight produced the same strings
-        assert torch.equal(o[0], outs[0][0]) and torch.equal(o[1], outs[0][1])
+    if args.full:
+        for o in outs[1:min(n_ctx, args.steps + warmup)]:             # every batch in flight produced the same strings
+            assert torch.equal(o[0], outs[0][0]) and torch.equal(o[1], outs[0][1])
     fill_ms, tb_ms, prep_ms = ([x[i] for x in stage] for i in range(3))
     # the only collective of the job: sum of counters, max of the elapsed time
     from npore_amd.dist import reduce_counters
@@ -441,6 +472,44 @@ def main():
     total_reads = int(sums["reads"])
     assert total_reads == n * world * args.steps
     value = total_reads / elapsed
+    if args.dump_outputs and rank == 0:
+        o, ln, st_ = outs[(args.steps - 1) % n_ctx]               # the context that ran the last timed step
+        dump_outputs(args.dump_outputs, o, ln, st_, oo)
+    line = {
+        "metric": "realigned reads/sec (10 kb ONT-like)", "value": round(value, 1), "unit": "reads/s",
+        "n_gpus": world, "steps": args.steps, "warmup": warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{n} synthetic {args.ref_len // 1000} kb reads per GPU, r={args.r} "
+                               f"(band={args.r}), max_b_rows={args.max_b_rows}, guppy5_stats penalties "
+                               f"(SURVEY 8d generator{', mixed p_np' if args.mixed else ''}, base_seed={args.base_seed}"
+                               f"{f', {n_uniq} distinct reads repeated' if n_uniq < n else ''})",
+                   "reads_per_gpu": n, "ref_len": args.ref_len, "r": args.r, "max_b_rows": args.max_b_rows,
+                   "base_seed": args.base_seed, "mixed": bool(args.mixed), "parallelism": f"reads x{world}",
+                   "batches_in_flight": n_ctx, "pipelined": pipelined, "devices_visible": n_dev,
+                   "value_excludes": "H2D/D2H: inputs and outputs stay in HBM across the timed region (the bench contract of "
+                                     "`value`); the same batch through page-locked host buffers is `value_pcie_inclusive`",
+                   "survey_8d_metric": "SURVEY.md 8(d) words the metric with H2D/D2H INCLUDED: that figure is "
+                                       "`value_pcie_inclusive.value` (host buffers in, strings out), reported beside `value`",
+                   "reduction_backend": {"nccl": "rccl", "gloo": "gloo (ranks share a device)", None: "none"}[backend],
+                   "host_setup": {"generate_s_max_over_ranks": round(maxes["generate"], 2),
+                                  "start_to_timed_region_s_max_over_ranks": round(maxes["until_timed"], 2),
+                                  "note": "every rank generates its own reads before the first barrier: outside the timed region"},
+                   "full": bool(args.full)},
+        "roofline": None, "cpu_baseline": None, "value_pcie_inclusive": None, "sustained": None, "production_default": None,
+        "stage_ms": None, "bad_reads": n_bad, "parity": None,
+    }
+
+    def close():
+        if use_dist:
+            dist.destroy_process_group()
+        for c in ctxs:
+            c.close()
+    if not args.full:            # a plain run: the headline figure only (the fields above left null need --full)
+        if rank == 0:
+            print(json.dumps(line))
+        close()
+        return
     out_len = d_len.cpu().numpy()
     out_host = d_out.cpu().numpy()
     # ---- 3a. EVERY rank proves its strings: each output whose (seed, index, r, max_b_rows) has a committed digest of
@@ -720,39 +789,17 @@ def main():
         cpu["gpu_speedup"] = sp
 
     if rank == 0:
-        line = {
-            "metric": "realigned reads/sec (10 kb ONT-like)", "value": round(value, 1), "unit": "reads/s",
-            "n_gpus": world, "steps": args.steps, "warmup": warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{n} synthetic {args.ref_len // 1000} kb reads per GPU, r={args.r} "
-                                   f"(band={args.r}), max_b_rows={args.max_b_rows}, guppy5_stats penalties "
-                                   f"(SURVEY 8d generator{', mixed p_np' if args.mixed else ''}, base_seed={args.base_seed}"
-                                   f"{f', {n_uniq} distinct reads repeated' if n_uniq < n else ''})",
-                       "reads_per_gpu": n, "ref_len": args.ref_len, "r": args.r, "max_b_rows": args.max_b_rows,
-                       "base_seed": args.base_seed, "mixed": bool(args.mixed), "parallelism": f"reads x{world}",
-                       "batches_in_flight": n_ctx, "pipelined": pipelined, "devices_visible": n_dev,
-                       "value_excludes": "H2D/D2H: inputs and outputs stay in HBM across the timed region (the bench contract of "
-                                         "`value`); the same batch through page-locked host buffers is `value_pcie_inclusive`",
-                       "survey_8d_metric": "SURVEY.md 8(d) words the metric with H2D/D2H INCLUDED: that figure is "
-                                           "`value_pcie_inclusive.value` (host buffers in, strings out), reported beside `value`",
-                       "reduction_backend": {"nccl": "rccl", "gloo": "gloo (ranks share a device)", None: "none"}[backend],
-                       "host_setup": {"generate_s_max_over_ranks": round(maxes["generate"], 2),
-                                      "start_to_timed_region_s_max_over_ranks": round(maxes["until_timed"], 2),
-                                      "note": "every rank generates its own reads before the first barrier: outside the timed region"}},
+        line.update({
             "roofline": roofline, "cpu_baseline": cpu,
             "value_pcie_inclusive": pcie, "sustained": sustained, "production_default": production,
             "stage_ms": {"fill_alone": round(fill_avg_ms, 2), "fill_event_to_event_overlapped": round(fill_region_ms, 2),
                          "traceback_gather": round(float(np.mean(tb_ms)), 2), "prep": round(float(np.mean(prep_ms)), 2),
                          "note": "fill_alone: the kernel with the GPU to itself (what the roofline is priced with); the other "
                                  "three are HIP-event times inside the timed region, where consecutive steps' stages overlap"},
-            "bad_reads": n_bad, "parity": parity,
-        }
+            "parity": parity,
+        })
         print(json.dumps(line))
-    if use_dist:
-        dist.destroy_process_group()
-    for c in ctxs:
-        c.close()
+    close()
     if parity["strings_bad"]:
         print(f"bench.py: {parity['strings_bad']} of {parity['strings_compared']} strings differ from the pinned oracle's digests",
               file=sys.stderr)

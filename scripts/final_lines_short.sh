@@ -3,9 +3,9 @@
 tag=${1:-r03}
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 o=gpurun_out/$tag; mkdir -p $o
-python bench.py --steps 20 --warmup 5 > $o/bench.log 2>&1 || exit 1
+python bench.py --full --steps 20 --warmup 5 > $o/bench.log 2>&1 || exit 1
 grep -h '^{"metric' $o/bench.log | tail -n 1 > $o/bench_line.json
-X="--no-cpu --pcie-steps 0 --sustain 0 --production 0"
+X="--full --no-cpu --pcie-steps 0 --sustain 0 --production 0"
 : > $o/config_lines.jsonl
 python bench.py --reads 1000 --band 30 --steps 20 --warmup 5 $X > $o/c2r30.log 2>&1 && grep -h '^{"metric' $o/c2r30.log | tail -n 1 >> $o/config_lines.jsonl
 python bench.py --reads 4000 --band 30 --steps 20 --warmup 5 $X > $o/r30x4000.log 2>&1 && grep -h '^{"metric' $o/r30x4000.log | tail -n 1 >> $o/config_lines.jsonl

@@ -15,10 +15,10 @@ base=
 for n in 1 2 4 8; do
   [ "$n" -gt "$ngpu" ] && break
   if [ "$n" -eq 1 ]; then
-    line=$(python3 bench.py --gpus 1 --no-cpu --sustain 0 --pcie-steps 0 "$@" | tail -1)
+    line=$(python3 bench.py --gpus 1 --full --no-cpu --sustain 0 --pcie-steps 0 "$@" | tail -1)
   else
     line=$(python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-           bench.py --gpus "$n" --no-cpu --sustain 0 --pcie-steps 0 "$@" 2>/dev/null | grep '^{' | tail -1)
+           bench.py --gpus "$n" --full --no-cpu --sustain 0 --pcie-steps 0 "$@" 2>/dev/null | grep '^{' | tail -1)
   fi
   python3 - "$n" "$line" "${base:-0}" <<'PY'
 import json, sys

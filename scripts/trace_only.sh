@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/trace_$tag
 rm -rf $out; mkdir -p $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/t -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu --pcie-steps 0 --sustain 0 --production 0 "$@" > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/t -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu --pcie-steps 0 --sustain 0 --production 0 "$@" > $out/bench.log 2>&1
 rc=$?
 f=$(find $out/t -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cut -d, -f1-4 $f | grep -v "at::native\|rocclr" > $out/kernel_stats.csv

@@ -3,6 +3,7 @@ process has not touched the GPU yet when it launches them:
 
   * bench.py under torch.distributed.run with 2 ranks on this box's one GPU -- the N > 1 path (reads dealt
     by index, per-rank contexts, counter reduction, rank-0 JSON line) executed once under the driver;
+  * a plain bench.py run on one GPU with --dump-outputs (the headline only, the dumped strings against the oracle);
   * aln.get_np_info() as the very first call of a fresh process (no align(), no Context, no tables) on a
     5 Mbp sequence, as the reference's callers use it (src/bed.py:62, src/bam.pyx:381).
 """
@@ -24,7 +25,7 @@ def test_bench_two_ranks_on_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--reads", "96", "--ref-len", "3000", "--band", "30", "--steps", "2", "--warmup", "1",
-           "--sustain", "0", "--pcie-steps", "1", "--no-cpu", "--production", "0.05", "--production-reads", "64"]
+           "--sustain", "0", "--pcie-steps", "1", "--no-cpu", "--production", "0.05", "--production-reads", "64", "--full"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -54,7 +55,7 @@ def test_bench_four_ranks_every_rank_proves_its_strings():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
            "--gpus", "4", "--reads", "250", "--steps", "2", "--warmup", "1", "--sustain", "0", "--pcie-steps", "0",
-           "--no-cpu", "--production", "0.05", "--production-reads", "100", "--solo-steps", "1"]
+           "--no-cpu", "--production", "0.05", "--production-reads", "100", "--solo-steps", "1", "--full"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -62,6 +63,36 @@ def test_bench_four_ranks_every_rank_proves_its_strings():
     assert line["parity"]["main"] == {"strings_compared": 1000, "strings_bad": 0}
     assert line["parity"]["production_default"] == {"strings_compared": 400, "strings_bad": 0}
     assert line["parity"]["strings_compared"] == 1400 and line["parity"]["strings_bad"] == 0
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` (no --full): exactly --steps timed steps, the headline fields, the --full fields null,
+    and --dump-outputs: the strings of the last timed step as float arrays, equal to the oracle's read for read."""
+    import numpy as np
+    import oracle
+    from npore_amd import aln, synth
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--reads", "40", "--ref-len", "3000", "--band", "30",
+           "--steps", "3", "--warmup", "1", "--dump-outputs", str(dump)]
+    out = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["bad_reads"] == 0 and line["config"]["full"] is False
+    assert line["unit"] == "reads/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert abs(40 / line["value"] * 1e3 - line["ms_per_step"]) < 0.006          # (ms_per_step is rounded to 0.01 ms)
+    for key in ("roofline", "cpu_baseline", "value_pcie_inclusive", "sustained", "production_default", "stage_ms", "parity"):
+        assert line[key] is None, key
+    got = {f: np.load(dump / (f + ".npy")) for f in ("lengths", "status", "alignment_reads", "alignments")}
+    assert got["lengths"].dtype == got["status"].dtype == got["alignment_reads"].dtype == np.float64
+    assert got["alignments"].dtype == np.float32
+    assert not got["status"].any() and got["alignment_reads"].tolist() == list(range(40))      # 40 short reads: all fit
+    sub, nps, _, _ = aln.load_default_tables()
+    refs, seqs, cigs = synth.make_batch(2, 40, ref_len=3000)
+    want = [oracle.align(refs[k], seqs[k], cigs[k], sub, nps, r=30, max_b_rows=20000) for k in range(40)]
+    assert got["lengths"].tolist() == [len(w) for w in want]
+    assert got["alignments"].astype(np.uint8).tobytes().decode() == "".join(want)
 
 
 def test_bench_two_ranks_production_shape_bookkeeping():
@@ -73,7 +104,7 @@ def test_bench_two_ranks_production_shape_bookkeeping():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--reads", "4000", "--band", "30", "--steps", "3", "--warmup", "1",
-           "--sustain", "0", "--pcie-steps", "0", "--no-cpu", "--production", "0", "--solo-steps", "1"]
+           "--sustain", "0", "--pcie-steps", "0", "--no-cpu", "--production", "0", "--solo-steps", "1", "--full"]
     out = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

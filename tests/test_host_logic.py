@@ -301,6 +301,41 @@ def test_bench_digest_parity_every_rank(tables):
         assert bench.digest_parity((9, False, 10_000, 100, 20000), idx, buf, oo, ln) == (0, 0)     # no table
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on host tensors laid out as the timed path leaves them (one slot per read, the string at
+    its start): lengths / statuses of every read, the strings of every read while they fit, else of a fixed seeded
+    sample that stays within the byte budget."""
+    import torch
+    import bench
+    rng = np.random.default_rng(5)
+    n = 50
+    strings = ["".join(rng.choice(list("=XID"), int(rng.integers(0, 40)))) for _ in range(n)]
+    oo = np.zeros(n + 1, np.int64)
+    oo[1:] = np.cumsum([len(s) + 7 for s in strings])                   # slots larger than the strings, as in bench.py
+    buf = np.full(int(oo[-1]) + 64, ord("?"), np.uint8)
+    for k, s in enumerate(strings):
+        buf[oo[k]:oo[k] + len(s)] = np.frombuffer(s.encode(), np.uint8)
+    ln = torch.tensor([len(s) for s in strings], dtype=torch.int64)
+    st = torch.zeros(n, dtype=torch.int32)
+    st[3] = 2
+
+    def dump(d):
+        bench.dump_outputs(str(d), torch.from_numpy(buf), ln, st, oo)
+        z = {f: np.load(d / (f + ".npy")) for f in ("lengths", "status", "alignment_reads", "alignments")}
+        assert z["lengths"].dtype == z["status"].dtype == z["alignment_reads"].dtype == np.float64
+        assert z["alignments"].dtype == np.float32
+        assert z["lengths"].tolist() == [len(s) for s in strings] and z["status"].tolist() == [2 if k == 3 else 0 for k in range(n)]
+        reads = z["alignment_reads"].astype(np.int64)
+        assert z["alignments"].astype(np.uint8).tobytes().decode() == "".join(strings[k] for k in reads)
+        assert sum(os.path.getsize(d / (f + ".npy")) for f in z) <= bench.DUMP_BYTES
+        return reads
+    assert dump(tmp_path / "all").tolist() == list(range(n))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 8 * n + 4 * 128 + 4 * sum(len(s) for s in strings) // 3)
+    some = dump(tmp_path / "some")
+    assert 0 < len(some) < n and list(some) == sorted(some)
+    assert dump(tmp_path / "again").tolist() == some.tolist()           # the same sample every time
+
+
 def _parts_worker(rank, world_size, port, prefix, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world_size),
                       LOCAL_RANK=str(rank))

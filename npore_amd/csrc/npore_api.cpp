@@ -6,11 +6,13 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <condition_variable>
 #include <deque>
 #include <future>
+#include <limits>
 #include <mutex>
 #include <memory>
 #include <numeric>
@@ -755,6 +757,8 @@ int run_core(npore_ctx *ctx, const AlignArgs &a, const OutTarget &ot, hipStream_
     if (a.n_reads < 0) return fail(NPORE_E_INVALID, "n_reads < 0");
     if (!ctx->d_sub || !ctx->d_np) return fail(NPORE_E_INVALID, "this context was created without penalty tables (annotation only)");
     if (a.r < 1) return fail(NPORE_E_INVALID, "r must be >= 1");
+    if (!std::isfinite(a.indel_start) || !std::isfinite(a.indel_extend))
+        return fail(NPORE_E_INVALID, "indel_start and indel_extend must be finite");
     if (a.max_b_rows < 2) return fail(NPORE_E_INVALID, "max_b_rows must be >= 2");
     if (a.max_b_rows > 60000)
         return fail(NPORE_E_UNSUPPORTED, "max_b_rows > 60000: run lengths are kept in 16 bits");
@@ -871,6 +875,20 @@ try {
     if ((!tables && (sub_scores || np_scores)) || max_n < 1 || max_n > MAX_PERIOD || max_l < 2 || max_l > 127) {   // repeat counts travel in 7-bit fields (layout.hpp, annotate planes)
         fail(NPORE_E_INVALID, "npore_ctx_create: need both tables (or neither: annotation-only context), 1 <= max_n <= 6, 2 <= max_l <= 127");
         return nullptr;
+    }
+    if (tables) {
+        // a NaN breaks the MIN3 form of the MAT choice (cell.hpp Env::MIN3), and a -inf meets the +inf history
+        // sentinels (inf - inf): either gives strings that silently differ from the reference's, so both are refused
+        const size_t np_n = (size_t)max_n * (max_l + 1) * (max_l + 1);
+        for (size_t i = 0; i < 25 + np_n; i++) {
+            const float v = i < 25 ? sub_scores[i] : np_scores[i - 25];
+            if (v != v || v == -std::numeric_limits<float>::infinity()) {
+                fail(NPORE_E_INVALID, std::string("npore_ctx_create: ") + (i < 25 ? "sub_scores" : "np_scores") + "[" +
+                                          std::to_string(i < 25 ? i : i - 25) + "] is " + (v != v ? "NaN" : "-inf") +
+                                          ": penalty tables must hold no NaN and no -inf entries");
+                return nullptr;
+            }
+        }
     }
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0 || device_id < 0 || device_id >= n) {
@@ -2233,6 +2251,9 @@ template <class Acquire, class OnStatus>
 int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, float indel_start, float indel_extend,
                   int max_b_rows, int r, int threads, FILE *fh, bool serial_acquire, Acquire acquire, OnStatus on_status)
 {
+    // (run_core refuses them too, but on a worker thread: refuse here, before a batch is read or a record written)
+    if (!std::isfinite(indel_start) || !std::isfinite(indel_extend))
+        return fail(NPORE_E_INVALID, "indel_start and indel_extend must be finite");
     for (auto &sp : ctx->slots)
         if (!sp) sp = new npore_batch_slot();
     const auto wall0 = std::chrono::steady_clock::now();

@@ -977,3 +977,19 @@ def test_bam_shares_begin_at_record_starts(tmp_path):
         g.set_share(1, 2, bai=bai)                               # another file's index: its offsets are not block starts here
     g.close()
     h.close()
+
+
+def test_non_finite_tables_refused(tables):
+    """npore_ctx_create refuses a NaN or -inf table entry loudly (NPORE_E_INVALID, which entry): a NaN breaks the MIN3 form
+    of the MAT choice and a -inf meets the +inf history sentinels, either giving silently different strings.  The tables
+    are checked before any device is looked for, so the refusal is the same with and without a GPU."""
+    sub, nps = tables
+    for where, bad, msg in (("sub", np.nan, r"sub_scores\[7\] is NaN"), ("np", np.nan, r"np_scores\[1234\] is NaN"),
+                            ("np", -np.inf, r"np_scores\[1234\] is -inf"), ("sub", -np.inf, r"sub_scores\[7\] is -inf")):
+        s, t = sub.copy(), nps.copy()
+        if where == "sub":
+            s.reshape(-1)[7] = bad
+        else:
+            t.reshape(-1)[1234] = bad
+        with pytest.raises(aln.NporeError, match=msg):
+            aln.Context(s, t, max_n=6, max_l=100)

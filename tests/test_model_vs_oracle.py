@@ -1,6 +1,7 @@
 """CPU: the product's cell recurrence (npore_amd/csrc/cell.hpp) and packing
 (prep.hpp), executed cell by cell by tests/model, against the oracle."""
 import numpy as np
+import pytest
 
 import oracle
 from model import model
@@ -226,3 +227,24 @@ def test_segments_with_warm_up_equal_the_whole_sequence():
                 g0 = s0 - warm
                 part = oracle.get_np_info(s[g0:], max_n=max_n, max_l=max_l)
                 assert np.array_equal(part[s0 - g0:s0 - g0 + 1500], full[s0:s0 + 1500]), (max_n, max_l, trial, s0)
+
+
+def _table_sets():
+    import table_families as tf
+    return list(tf.TABLE_SETS)
+
+
+@pytest.mark.parametrize("name", _table_sets())
+def test_table_families(name):
+    """The cell recurrence under every G8 table set (tests/table_families.py) on the GPU test's input set: a GPU-only
+    mismatch under these tables then points at the generated assembly or the device environment, not at cell.hpp."""
+    import table_families as tf
+    sub, nps, ist, iex, max_n, max_l = tf.load(name)
+    reads = tf.input_set(max_l, int(tf.g8()["input/seed"][0]))
+    for r, mbr in ((1, 20000), (5, 7), (30, 333), (100, 20000), (230, 7)):
+        for k, (ref, seq, cig, _) in enumerate(reads):
+            a, sa = oracle.align(ref, seq, cig, sub, nps, indel_start=ist, indel_extend=iex, max_b_rows=mbr, r=r,
+                                 max_n=max_n, max_l=max_l, return_status=True)
+            b, sb = model.align(ref, seq, cig, sub, nps, indel_start=ist, indel_extend=iex, max_b_rows=mbr, r=r,
+                                max_n=max_n, max_l=max_l)
+            assert a == b and sa == sb, (name, r, mbr, k)

@@ -106,3 +106,85 @@ def test_fullsize_digests_are_the_oracles(tables):
         s = oracle.align(ref, seq, cig, sub, nps, r=r)
         k = int(np.nonzero(z[name + "_idx"] == i)[0][0])
         assert len(s) == z[name + "_len"][k] and int(hashlib.sha256(s.encode()).hexdigest()[:16], 16) == int(z[name + "_dig"][k])
+
+
+# ---- G8 (tests/golden/make_golden_tables.py): score tables other than the shipped ones
+
+def _g8_sets():
+    import table_families as tf
+    return list(tf.TABLE_SETS)
+
+
+@pytest.mark.parametrize("name", _g8_sets())
+def test_oracle_vs_reference_table_families(name):
+    """oracle == the reference's compiled align() under every G8 table set (random entries with N scored, grids of ties,
+    all-equal, calc_score_matrices of sparse counts, G1 moved by ulps with signed zeros / denormals / +inf entries,
+    penalties at the reference's INF = 100, other max_n / max_l), on the input set of the GPU test."""
+    import table_families as tf
+    sub, nps, ist, iex, max_n, max_l = tf.load(name)
+    reads = tf.input_set(max_l, int(tf.g8()["input/seed"][0]))
+    n = 0
+    for r, mbr in tf.g8()["input/configs"].tolist():
+        got = [oracle.align(ref, seq, cig, sub, nps, indel_start=ist, indel_extend=iex, max_b_rows=mbr, r=r,
+                            max_n=max_n, max_l=max_l) for ref, seq, cig, _ in reads]
+        n += tf.g8_check(name, got, r, mbr)
+    assert n >= 7 * (len(reads) - 4)
+
+
+def test_calc_score_matrices_sparse_counts():
+    """aln.calc_score_matrices == the reference's, bit for bit, on the sparse counts of cms.json (what --recalc_cms over a
+    small region hands the kernel: mostly eps plus fix_matrix_properties' ramps); G1 pins only the shipped counts."""
+    import table_families as tf
+    from npore_amd import aln
+    z = tf.g8()
+    sub, nps, ins, dels = aln.calc_score_matrices(*tf.cms_counts(6, 100))
+    for got, key in ((sub, "recalc/sub"), (nps, "recalc/np"), (ins, "recalc/ins"), (dels, "recalc/del")):
+        want = z[key]
+        assert got.dtype == np.float32 and got.shape == want.shape, key
+        assert got.tobytes() == want.tobytes(), (key, np.argwhere(got != want)[:4])
+
+
+SENSITIVITY_MIN = 3
+
+
+def test_table_inputs_are_sensitive():
+    """What makes tests/test_gpu_tables.py fail on a subtly wrong kernel: on its input set, under the `random` table set,
+    every table lookup a mis-indexed kernel could get wrong changes the strings of at least SENSITIVITY_MIN reads (so no
+    single tie-breaking read carries a lookup) -- in at least one of the two band widths the GPU test runs them at.
+    Under G1 (the shipped tables) zeroing the N row or column changes nothing: they are 0 already, the value the device's
+    LDS table puts in its unused slots."""
+    import table_families as tf
+    sub, nps, ist, iex, max_n, max_l = tf.load("random")
+    reads = [x for x in tf.input_set(max_l, int(tf.g8()["input/seed"][0]))]
+
+    def run(s, t, a=ist, b=iex, r=30, mbr=333):
+        return [oracle.align(ref, seq, cig, s, t, indel_start=a, indel_extend=b, max_b_rows=mbr, r=r, max_n=max_n,
+                             max_l=max_l) for ref, seq, cig, _ in reads]
+
+    base = {r: run(sub, nps, r=r) for r in (5, 30)}
+
+    def changed(s=sub, t=nps, a=ist, b=iex):
+        return max(sum(x != y for x, y in zip(base[r], run(s, t, a, b, r=r))) for r in (5, 30))
+
+    def with_np(fn):
+        t = nps.copy(); fn(t); return t
+
+    def with_sub(fn):
+        s = sub.copy(); fn(s); return s
+
+    big = np.zeros(nps.shape, bool)
+    big[:, 32:, :] = True; big[:, :, 32:] = True
+    shifted = np.concatenate([nps[:, :, 1:], nps[:, :, -1:]], axis=2)
+    corruptions = {
+        "sub transposed": changed(s=np.ascontiguousarray(sub.T)),
+        "sub N row zeroed": changed(s=with_sub(lambda s: s.__setitem__(0, 0))),
+        "sub N column zeroed": changed(s=with_sub(lambda s: s.__setitem__((slice(None), 0), 0))),
+        "np call index + 1": changed(t=with_np(lambda t: t.__setitem__((slice(None), slice(None), slice(0, -1)), nps[:, :, 1:]))),
+        "np L index + 1": changed(t=with_np(lambda t: t.__setitem__((slice(None), slice(0, -1)), nps[:, 1:]))),
+        "np period rolled": changed(t=np.ascontiguousarray(np.roll(nps, 1, axis=0))),
+        "np L or call >= 32 shifted": changed(t=np.where(big, shifted, nps).astype(np.float32)),
+        "np clamp row max_l - 1 = its neighbour": changed(t=with_np(lambda t: t.__setitem__((slice(None), max_l - 1), nps[:, max_l - 2]))),
+        "indel_start and indel_extend swapped": changed(a=iex, b=ist),
+    }
+    weak = {k: v for k, v in corruptions.items() if v < SENSITIVITY_MIN}
+    assert not weak, (weak, corruptions)

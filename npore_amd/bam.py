@@ -9,7 +9,7 @@ get_reference_sequence() reconstructs from the MD tag.
 
 Two implementations of the same logic live here:
   * NativeBam / NativeFasta / realign_native: thin ctypes wrappers of the library's
-    C++ host I/O (csrc/hostio.hpp: parallel BGZF inflate, batch packing, SAM
+    C++ host I/O (csrc/hostio.hpp, csrc/bam_reader.hpp: parallel BGZF inflate, batch packing, SAM
     formatting) -- what realign.py runs;
   * BamFile / read_fasta / get_read_data / realign_reads: the pure-Python
     restatement, record by record as the reference does it -- what the tests
@@ -283,7 +283,7 @@ def sam_line(rd, final):
 
 
 # ---------------------------------------------------------------------------
-# native host I/O (libnpore_amd.so, csrc/hostio.hpp)
+# native host I/O (libnpore_amd.so, csrc/hostio.hpp + csrc/bam_reader.hpp)
 class NativeFasta:
     """Contig names / lengths of a FASTA held by the library; behaves like {name: sized} for get_bam_regions."""
 

@@ -1,0 +1,846 @@
+// bam_reader.hpp -- the BAM reader and the SAM writer of the BAM -> SAM pipeline, host side: opening a BAM (resident,
+// streamed, header only), the record index and selection by region, the .bai share cuts, the one-pass window reader,
+// record packing, SAM text.  Everything here parses untrusted files and none of it touches the GPU: this header and
+// what it includes (hostio.hpp) compile with any C++17 compiler, no HIP header in reach.  The C ABI's entry points
+// (npore_api.cpp) are thin wrappers around these bodies.
+#pragma once
+#include "../../include/npore_amd.h"
+#include "hostio.hpp"
+
+#include <condition_variable>
+#include <deque>
+#if defined(__x86_64__)
+#include <immintrin.h>
+#endif
+
+namespace npore {
+
+// header of a BAM stream at d[0 .. N): text, references; *hdr_end = offset of the first record.  -1: more bytes needed
+// (streamed mode reads on), 0: corrupt, 1: ok
+inline int bam_parse_header(npore_bam *b, const uint8_t *d, size_t N, size_t *hdr_end)
+{
+    if (N < 12) return -1;
+    if (std::memcmp(d, "BAM\1", 4) != 0) return 0;
+    size_t p = 4;
+    const int64_t l_text = rdi32(&d[p]);
+    p += 4;
+    if (l_text < 0) return 0;
+    if (p + (size_t)l_text + 4 > N) return -1;
+    b->text.assign(reinterpret_cast<const char *>(&d[p]), (size_t)l_text);
+    while (!b->text.empty() && b->text.back() == '\0') b->text.pop_back();
+    p += (size_t)l_text;
+    const int32_t n_ref = rdi32(&d[p]);
+    p += 4;
+    if (n_ref < 0) return 0;
+    b->ref_names.clear();
+    b->ref_lens.clear();
+    for (int32_t k = 0; k < n_ref; k++) {
+        if (p + 4 > N) return -1;
+        const int32_t l_name = rdi32(&d[p]);
+        if (l_name < 1) return 0;
+        if (p + 8 + (size_t)l_name > N) return -1;
+        b->ref_names.emplace_back(reinterpret_cast<const char *>(&d[p + 4]), (size_t)l_name - 1);
+        b->ref_lens.push_back(rdi32(&d[p + 4 + (size_t)l_name]));
+        p += 8 + (size_t)l_name;
+    }
+    *hdr_end = p;
+    return 1;
+}
+
+// the variable-length parts the record accessors will walk lie inside the record
+inline bool record_is_sound(const uint8_t *q)
+{
+    const int32_t bs = rdi32(q);
+    const uint8_t *f = q + 4;
+    const int64_t l_rn = f[8], n_cig = rd16(f + 12), l_seq = rdi32(f + 16);
+    return !(l_rn < 1 || l_seq < 0 || 32 + l_rn + 4 * n_cig + (l_seq + 1) / 2 + l_seq > bs || f[32 + l_rn - 1] != 0);
+}
+
+// The framing step of every walk over a record stream: is the record whose block_size field lies at d[p] whole within
+// the N bytes at hand?  WHOLE: yes, the next record begins at `next`; MORE: its end (or its block_size field) lies
+// beyond d[N) -- what that means is the caller's business (the end of a resident stream, a tail to carry into the next
+// window); CORRUPT: a block_size smaller than the fixed fields.
+enum class Frame { WHOLE, MORE, CORRUPT };
+inline Frame frame_record(const uint8_t *d, size_t N, size_t p, size_t &next)
+{
+    if (p + 4 > N) return Frame::MORE;
+    const int32_t bs = rdi32(d + p);
+    if (bs < 32) return Frame::CORRUPT;
+    if (p + 4 + (size_t)bs > N) return Frame::MORE;
+    next = p + 4 + (size_t)bs;
+    return Frame::WHOLE;
+}
+
+// what selection needs of the records in d[first record .. ): validation + metadata on all cores.  `offs` = offsets of
+// the records' block_size fields relative to d; the metadata is appended to the handle's arrays.
+inline bool bam_index_records(npore_bam *b, const uint8_t *d, const std::vector<int64_t> &offs, int64_t global_base, int threads)
+{
+    const int64_t n = (int64_t)offs.size(), at = (int64_t)b->rec_off.size();
+    b->rec_off.resize((size_t)(at + n));
+    b->m_ref.resize((size_t)(at + n));
+    b->m_pos.resize((size_t)(at + n));
+    b->m_span.resize((size_t)(at + n));
+    b->m_flag.resize((size_t)(at + n));
+    std::atomic<int> corrupt{0};
+    const int64_t per = 256;
+    parallel_for((n + per - 1) / per, threads, [&](int64_t blk) {
+        for (int64_t i = blk * per; i < std::min(n, (blk + 1) * per); i++) {
+            const uint8_t *q = d + offs[(size_t)i];
+            if (!record_is_sound(q)) { corrupt++; return; }
+            const RecView r = rec_view(q);
+            const int64_t span = rec_ref_len(r);
+            b->rec_off[(size_t)(at + i)] = global_base + offs[(size_t)i];
+            b->m_ref[(size_t)(at + i)] = r.ref_id();
+            b->m_pos[(size_t)(at + i)] = r.pos();
+            b->m_span[(size_t)(at + i)] = (int32_t)std::min<int64_t>(span, INT32_MAX);
+            b->m_flag[(size_t)(at + i)] = (uint16_t)r.flag();
+        }
+    });
+    return corrupt == 0;
+}
+
+// per-reference record lists and the shortcuts of npore_bam_select, from the per-record metadata
+inline void bam_finish_index(npore_bam *b)
+{
+    const int32_t n_ref = (int32_t)b->ref_names.size();
+    b->ref_has_reads.assign((size_t)n_ref, 0);
+    b->by_ref.assign((size_t)n_ref, {});
+    b->ref_sorted.assign((size_t)n_ref, 1);
+    b->ref_max_len.assign((size_t)n_ref, 0);
+    std::vector<int64_t> last_pos((size_t)n_ref, -1);
+    const int64_t n_rec = (int64_t)b->rec_off.size();
+    for (int64_t i = 0; i < n_rec; i++) {
+        const int32_t rid = b->m_ref[(size_t)i];
+        if (rid >= 0 && rid < n_ref) {
+            const int64_t pos = b->m_pos[(size_t)i];
+            b->ref_has_reads[(size_t)rid] = 1;
+            b->by_ref[(size_t)rid].push_back(i);
+            if (pos < last_pos[(size_t)rid]) b->ref_sorted[(size_t)rid] = 0;
+            last_pos[(size_t)rid] = pos;
+            b->ref_max_len[(size_t)rid] = std::max<int64_t>(b->ref_max_len[(size_t)rid], b->m_span[(size_t)i]);
+        }
+    }
+}
+
+// STREAMED open: block table, then the stream in windows of `win_blocks` BGZF blocks (inflated on all cores, walked,
+// dropped); a record that straddles two windows is carried over.  Resident: one window + 22 bytes per record.
+inline npore_bam *bam_open_streamed(const char *path, int threads, std::unique_ptr<PreadFile> file, const char *index_path)
+{
+    std::unique_ptr<npore_bam> hold(new npore_bam());
+    npore_bam *b = hold.get();
+    b->streamed = true;
+    b->file = std::move(file);
+    uint64_t total = 0;
+    if (!bgzf_scan(*b->file, b->blocks, total)) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BGZF file"); return nullptr; }
+    b->data_size = (size_t)total;
+    if (index_path && *index_path) {        // another process of this node has made the record index already
+        MappedFile ix;
+        const uint8_t *q = nullptr;
+        if (ix.open(index_path) && ix.n >= 32 && std::memcmp(ix.p, "NPOREIX1", 8) == 0) q = ix.p;
+        if (q) {
+            uint64_t n_rec, hdr_len, tot;
+            std::memcpy(&n_rec, q + 8, 8); std::memcpy(&hdr_len, q + 16, 8); std::memcpy(&tot, q + 24, 8);
+            size_t hdr_end = 0;
+            const size_t need = 32 + hdr_len + n_rec * 22;
+            if (tot == total && ix.n >= need && bam_parse_header(b, q + 32, (size_t)hdr_len, &hdr_end) == 1) {
+                const uint8_t *a = q + 32 + hdr_len;
+                b->rec_off.resize(n_rec); b->m_ref.resize(n_rec); b->m_pos.resize(n_rec); b->m_span.resize(n_rec); b->m_flag.resize(n_rec);
+                std::memcpy(b->rec_off.data(), a, n_rec * 8); a += n_rec * 8;
+                std::memcpy(b->m_ref.data(), a, n_rec * 4); a += n_rec * 4;
+                std::memcpy(b->m_pos.data(), a, n_rec * 4); a += n_rec * 4;
+                std::memcpy(b->m_span.data(), a, n_rec * 4); a += n_rec * 4;
+                std::memcpy(b->m_flag.data(), a, n_rec * 2);
+                bam_finish_index(b);
+                return hold.release();
+            }
+        }
+        // (an unusable index file: fall through and index the file here)
+    }
+    size_t win_blocks = 4096;               // <= 256 MB of inflated stream per window
+    if (const char *e = std::getenv("NPORE_BAM_WINDOW_BLOCKS")) win_blocks = (size_t)std::max(1, std::atoi(e));
+    RawBuf win;
+    std::vector<uint8_t> carry;             // the incomplete tail of the previous window
+    uint64_t carry_at = 0;                  // stream offset of carry[0]
+    bool have_header = false;
+    std::vector<int64_t> offs;
+    for (size_t b0 = 0; b0 < b->blocks.size();) {
+        const size_t b1 = std::min(b->blocks.size(), b0 + win_blocks);
+        const uint64_t w0 = b->blocks[b0].out_off, w1 = b->blocks[b1 - 1].out_off + b->blocks[b1 - 1].out_len;
+        if (!win.ensure(carry.size() + (size_t)(w1 - w0) + 8)) { fail(NPORE_E_NOMEM, "BAM window"); return nullptr; }
+        uint8_t *d = reinterpret_cast<uint8_t *>(win.p);
+        if (!carry.empty()) std::memcpy(d, carry.data(), carry.size());
+        if (!bgzf_inflate_range(*b->file, b->blocks, b0, b1, d + carry.size(), threads)) {
+            fail(NPORE_E_INVALID, std::string("'") + path + "': corrupt BGZF block");
+            return nullptr;
+        }
+        const uint64_t base = carry.empty() ? w0 : carry_at;      // stream offset of d[0]
+        const size_t N = carry.size() + (size_t)(w1 - w0);
+        size_t p = 0;
+        if (!have_header) {
+            size_t hdr_end = 0;
+            const int rc = bam_parse_header(b, d, N, &hdr_end);
+            if (rc == 0) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file"); return nullptr; }
+            if (rc < 0) {                                         // the header does not end in this window: read on
+                if (b1 == b->blocks.size()) { fail(NPORE_E_INVALID, "truncated BAM header"); return nullptr; }
+                carry.assign(d, d + N);
+                carry_at = base;
+                b0 = b1;
+                continue;
+            }
+            have_header = true;
+            p = hdr_end;
+        }
+        offs.clear();
+        for (size_t nx = 0;; p = nx) {
+            const Frame f = frame_record(d, N, p, nx);
+            if (f == Frame::CORRUPT) { fail(NPORE_E_INVALID, "truncated BAM record"); return nullptr; }
+            if (f == Frame::MORE) break;                          // the tail is carried into the next window
+            offs.push_back((int64_t)p);
+        }
+        if (!bam_index_records(b, d, offs, (int64_t)base, threads)) { fail(NPORE_E_INVALID, "corrupt BAM record"); return nullptr; }
+        carry.assign(d + p, d + N);
+        carry_at = base + p;
+        b0 = b1;
+    }
+    if (!have_header) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file"); return nullptr; }
+    if (!carry.empty()) { fail(NPORE_E_INVALID, "truncated BAM record"); return nullptr; }
+    bam_finish_index(b);
+    return hold.release();
+}
+
+// ONE-PASS open (mode 3): the BGZF block table and the BAM header, nothing else -- no record is looked at until
+// npore_bam_realign_sequential walks the stream.  Such a handle has no record index: npore_bam_select finds nothing.
+inline npore_bam *bam_open_header_only(const char *path, int threads, std::unique_ptr<PreadFile> file)
+{
+    std::unique_ptr<npore_bam> hold(new npore_bam());
+    npore_bam *b = hold.get();
+    b->streamed = true;
+    b->file = std::move(file);
+    uint64_t total = 0;
+    if (!bgzf_scan(*b->file, b->blocks, total)) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BGZF file"); return nullptr; }
+    b->data_size = (size_t)total;
+    RawBuf head;
+    for (size_t b1 = std::min<size_t>(b->blocks.size(), 16);; b1 = std::min(b->blocks.size(), b1 * 4)) {
+        if (b1 == 0) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file"); return nullptr; }
+        const size_t n = (size_t)(b->blocks[b1 - 1].out_off + b->blocks[b1 - 1].out_len);
+        if (!head.ensure(n + 8) || !bgzf_inflate_range(*b->file, b->blocks, 0, b1, reinterpret_cast<uint8_t *>(head.p), threads)) {
+            fail(NPORE_E_INVALID, std::string("'") + path + "': corrupt BGZF block");
+            return nullptr;
+        }
+        size_t hdr_end = 0;
+        const int rc = bam_parse_header(b, reinterpret_cast<const uint8_t *>(head.p), n, &hdr_end);
+        if (rc == 1) break;
+        if (rc == 0 || b1 == b->blocks.size()) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file"); return nullptr; }
+    }
+    bam_finish_index(b);                                 // (empty per-reference lists)
+    // which contigs have reads (get_bam_regions' default keeps only those, src/util.py:16-93 with bam.count() > 0): from
+    // the file's .bai when there is one (a reference with bins or linear-index entries has records) -- otherwise unknown
+    // without a pass over the records: every contig is assumed to have some
+    b->ref_has_reads.assign(b->ref_names.size(), 1);
+    {
+        const std::string p0 = std::string(path) + ".bai";
+        std::string p1 = path;
+        const size_t dot = p1.rfind('.');
+        if (dot != std::string::npos) p1 = p1.substr(0, dot) + ".bai";
+        std::vector<uint64_t> offs;
+        std::vector<uint8_t> has;
+        for (const std::string &cand : {p0, p1})
+            if (bai_linear_offsets(cand.c_str(), offs, &has) && has.size() == b->ref_names.size()) { b->ref_has_reads = has; break; }
+    }
+    return hold.release();
+}
+
+// mode 0: automatic (streamed when the file is BGZF and larger than NPORE_BAM_STREAM_MB, default 1024 MB), 1: whole file
+// resident, 2: streamed, 3: one-pass (header only; the reads through npore_bam_realign_sequential).  index_path (may be NULL): a record index saved by npore_bam_save_index for this very file --
+// a streamed handle then skips its indexing pass (one process of a node indexes, the others load).
+inline npore_bam *bam_open(const char *path, int threads, int mode, const char *index_path)
+{
+    if (!path) { fail(NPORE_E_INVALID, "null path"); return nullptr; }
+    if (mode != 1) {
+        std::unique_ptr<PreadFile> pf(new PreadFile());
+        if (!pf->open(path)) { fail(NPORE_E_INVALID, std::string("BAM file '") + path + "' not found"); return nullptr; }
+        uint8_t magic[4] = {0, 0, 0, 0};
+        const bool gz = pf->size >= 28 && pf->read(0, magic, 4) && magic[0] == 31 && magic[1] == 139;
+        uint64_t limit_mb = 1024;
+        if (const char *e = std::getenv("NPORE_BAM_STREAM_MB")) limit_mb = (uint64_t)std::max(0ll, std::atoll(e));
+        if (gz && mode == 3) return bam_open_header_only(path, threads, std::move(pf));
+        if (mode == 3) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BGZF file (one-pass mode)"); return nullptr; }
+        if (gz && (mode == 2 || pf->size > limit_mb * 1048576ull)) return bam_open_streamed(path, threads, std::move(pf), index_path);
+        if (mode == 2) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BGZF file (streamed mode)"); return nullptr; }
+    }
+    std::unique_ptr<MappedFile> mfp(new MappedFile());
+    MappedFile &mf = *mfp;
+    if (!mf.open(path)) { fail(NPORE_E_INVALID, std::string("BAM file '") + path + "' not found"); return nullptr; }
+    const ByteSpan raw{mf.p, mf.n};
+    std::unique_ptr<npore_bam> hold(new npore_bam());
+    npore_bam *b = hold.get();
+    std::string err;
+    if (mf.n >= 12 && std::memcmp(mf.p, "BAM\1", 4) == 0) {
+        // an inflated BAM stream (npore_bam_dump_inflated: one rank of a node inflates, the others map its copy)
+        b->data = mf.p;
+        b->data_size = mf.n;
+        b->raw_map = std::move(mfp);
+    } else {
+        if (!bgzf_inflate(raw, threads, b->data_buf, b->data_size, err) || b->data_size < 12 || std::memcmp(b->data_buf.p, "BAM\1", 4) != 0) {
+            fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file" + (err.empty() ? "" : " (" + err + ")"));
+            return nullptr;
+        }
+        b->data = reinterpret_cast<const uint8_t *>(b->data_buf.p);
+    }
+    const uint8_t *d = b->data;
+    const size_t N = b->data_size;
+    size_t p = 0;
+    if (bam_parse_header(b, d, N, &p) != 1) { fail(NPORE_E_INVALID, "truncated BAM header"); return nullptr; }
+    // records: offsets (one hop per record), then validation + metadata on all cores, then the per-reference lists
+    std::vector<int64_t> offs;
+    while (p + 4 <= N) {                                          // (fewer than four bytes behind the last record are let be)
+        size_t nx = 0;
+        if (frame_record(d, N, p, nx) != Frame::WHOLE) { fail(NPORE_E_INVALID, "truncated BAM record"); return nullptr; }
+        offs.push_back((int64_t)p);
+        p = nx;
+    }
+    if (!bam_index_records(b, d, offs, 0, threads)) { fail(NPORE_E_INVALID, "corrupt BAM record"); return nullptr; }
+    bam_finish_index(b);
+    return hold.release();
+}
+
+// The record index of a handle (header + per-record offsets and metadata: 22 bytes per record), complete or not there
+// at all, for npore_bam_open_mode(..., index_path) in the other processes of a node.
+inline int bam_save_index(const npore_bam *b, const char *path)
+{
+    if (!b || !path) return fail(NPORE_E_INVALID, "null argument");
+    // the header as a BAM stream prefix, so that the loader parses it with the same code
+    std::string hdr("BAM\1", 4);
+    auto put32 = [&](int32_t v) { hdr.append(reinterpret_cast<const char *>(&v), 4); };
+    put32((int32_t)b->text.size());
+    hdr += b->text;
+    put32((int32_t)b->ref_names.size());
+    for (size_t k = 0; k < b->ref_names.size(); k++) {
+        put32((int32_t)b->ref_names[k].size() + 1);
+        hdr.append(b->ref_names[k].c_str(), b->ref_names[k].size() + 1);
+        put32((int32_t)b->ref_lens[k]);
+    }
+    const std::string tmp = std::string(path) + ".tmp" + std::to_string((long long)::getpid());
+    FILE *fh = std::fopen(tmp.c_str(), "wb");
+    if (!fh) return fail(NPORE_E_INVALID, "cannot create '" + tmp + "'");
+    const uint64_t n_rec = b->rec_off.size(), hdr_len = hdr.size(), tot = b->data_size;
+    bool ok = std::fwrite("NPOREIX1", 1, 8, fh) == 8 && std::fwrite(&n_rec, 8, 1, fh) == 1 && std::fwrite(&hdr_len, 8, 1, fh) == 1 &&
+              std::fwrite(&tot, 8, 1, fh) == 1 && std::fwrite(hdr.data(), 1, hdr.size(), fh) == hdr.size();
+    auto put = [&](const void *p, size_t bytes) { if (ok && bytes) ok = std::fwrite(p, 1, bytes, fh) == bytes; };
+    put(b->rec_off.data(), n_rec * 8); put(b->m_ref.data(), n_rec * 4); put(b->m_pos.data(), n_rec * 4);
+    put(b->m_span.data(), n_rec * 4); put(b->m_flag.data(), n_rec * 2);
+    if (std::fclose(fh) != 0 || !ok || std::rename(tmp.c_str(), path) != 0) {
+        std::remove(tmp.c_str());
+        return fail(NPORE_E_INVALID, std::string("cannot write '") + path + "'");
+    }
+    return NPORE_OK;
+}
+
+inline int bam_dump_inflated(const npore_bam *b, const char *path)
+{
+    if (!b || !path) return fail(NPORE_E_INVALID, "null argument");
+    if (b->streamed) return fail(NPORE_E_UNSUPPORTED, "a streamed BAM handle holds no inflated stream (share its index: npore_bam_save_index)");
+    const std::string tmp = std::string(path) + ".tmp" + std::to_string((long long)::getpid());
+    FILE *fh = std::fopen(tmp.c_str(), "wb");
+    if (!fh) return fail(NPORE_E_INVALID, "cannot create '" + tmp + "'");
+    const bool ok = std::fwrite(b->data, 1, b->data_size, fh) == b->data_size;
+    if (std::fclose(fh) != 0 || !ok || std::rename(tmp.c_str(), path) != 0) {       // complete, or not there at all
+        std::remove(tmp.c_str());
+        return fail(NPORE_E_INVALID, std::string("cannot write '") + path + "'");
+    }
+    return NPORE_OK;
+}
+
+inline int64_t bam_select(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
+                          int64_t max_reads, int64_t *out_idx, int64_t cap)
+{
+    if (!b || (n_regions > 0 && (!ref_id || !start || !stop)) || (cap > 0 && !out_idx)) return fail(NPORE_E_INVALID, "null argument");
+    int64_t kept = 0;
+    for (int g = 0; g < n_regions; g++) {
+        if (ref_id[g] < 0 || ref_id[g] >= (int32_t)b->by_ref.size()) continue;
+        const std::vector<int64_t> &recs = b->by_ref[(size_t)ref_id[g]];     // file order
+        size_t first = 0;
+        if (b->ref_sorted[(size_t)ref_id[g]]) {
+            // coordinate-sorted (the usual case): skip everything that ends before the region can start
+            const int64_t lo = start[g] - b->ref_max_len[(size_t)ref_id[g]];
+            first = (size_t)(std::lower_bound(recs.begin(), recs.end(), lo,
+                                              [&](int64_t i, int64_t v) { return (int64_t)b->m_pos[(size_t)i] < v; }) - recs.begin());
+        }
+        for (size_t q = first; q < recs.size(); q++) {
+            const int64_t i = recs[q];
+            const int64_t pos = b->m_pos[(size_t)i], rl = b->m_span[(size_t)i];
+            if (b->ref_sorted[(size_t)ref_id[g]] && pos >= stop[g]) break;
+            if (!(pos < stop[g] && pos + rl > start[g])) continue;                 // overlaps [start, stop)
+            if (max_reads > 0 && kept >= max_reads) return kept;                   // src/bam.pyx:29-30
+            if (b->m_flag[(size_t)i] & (0x100 | 0x800 | 0x4)) continue;           // secondary / supplementary / unmapped, :31-32
+            if (kept < cap) out_idx[kept] = i;
+            kept++;
+        }
+    }
+    return kept;
+}
+
+// ONE-PASS handle, several processes: the stretch of the record stream that `rank` of `world` walks (npore_bam.share_*)
+inline int bam_set_share(npore_bam *b, int rank, int world, const char *bai_path)
+{
+    if (!b || world < 1 || rank < 0 || rank >= world) return fail(NPORE_E_INVALID, "bad argument");
+    if (!b->file || b->blocks.empty()) return fail(NPORE_E_INVALID, "a share needs a handle opened on a BGZF file (modes 2 and 3)");
+    b->has_share = false;
+    b->share_begin = 0;
+    b->share_end = UINT64_MAX;
+    b->share_block = 0;
+    if (world == 1) return NPORE_OK;
+    std::vector<uint64_t> cuts;
+    if (!bai_path || !bai_linear_offsets(bai_path, cuts) || cuts.empty())
+        return fail(NPORE_E_UNSUPPORTED, "no usable .bai linear index: the record stream cannot be dealt without a pass over it");
+    // the first record of the stretch whose compressed offset lies at or behind k / world of the file
+    const uint64_t c0 = b->blocks.front().in_off, c1 = b->blocks.back().in_off + b->blocks.back().in_len;
+    auto cut_of = [&](int k) -> uint64_t {
+        if (k <= 0) return 0;
+        if (k >= world) return UINT64_MAX;
+        const uint64_t target = c0 + (uint64_t)((long double)(c1 - c0) * k / world);
+        auto it = std::lower_bound(cuts.begin(), cuts.end(), target << 16);
+        return it == cuts.end() ? UINT64_MAX : *it;
+    };
+    // virtual offset -> block of the table and offset in the inflated stream (false: the index is not this file's)
+    auto locate = [&](uint64_t v, size_t &blk, uint64_t &abs) -> bool {
+        const uint64_t coff = v >> 16, uoff = v & 0xFFFFu;
+        // a block's payload begins a gzip header's length behind the block: the block that starts at `coff` is the first
+        // one whose payload offset lies behind it
+        size_t lo = 0, hi = b->blocks.size();
+        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (b->blocks[mid].in_off > coff) hi = mid; else lo = mid + 1; }
+        if (lo == b->blocks.size() || b->blocks[lo].in_off - coff > 4096 || uoff >= b->blocks[lo].out_len) return false;
+        blk = lo;
+        abs = b->blocks[lo].out_off + uoff;
+        return true;
+    };
+    const uint64_t v0 = cut_of(rank), v1 = cut_of(rank + 1);
+    if (v0 == UINT64_MAX) { b->share_begin = b->share_end = UINT64_MAX; }       // nothing left for this rank
+    else if (v0 != 0) {
+        if (!locate(v0, b->share_block, b->share_begin)) return fail(NPORE_E_UNSUPPORTED, "the .bai index does not belong to this BAM file");
+    }
+    if (v1 != UINT64_MAX && v0 != UINT64_MAX) {
+        size_t blk;
+        if (!locate(v1, blk, b->share_end)) return fail(NPORE_E_UNSUPPORTED, "the .bai index does not belong to this BAM file");
+    }
+    b->has_share = true;
+    return NPORE_OK;
+}
+
+inline bool pack_args_ok(const npore_bam *b, const int64_t *idx, int64_t n)
+{
+    if (!b || n < 0 || (n > 0 && !idx)) return false;
+    for (int64_t k = 0; k < n; k++)
+        if (idx[k] < 0 || idx[k] >= (int64_t)b->rec_off.size()) return false;
+    return true;
+}
+
+inline int fetch_records(const npore_bam *b, const int64_t *idx, int64_t n, int threads, RecFetch &rf)
+{
+    std::string err;
+    if (!bam_fetch(*b, idx, n, threads, rf, err)) return fail(NPORE_E_INVALID, "BAM records: " + err);
+    return NPORE_OK;
+}
+inline void pack_sizes_of(const RecFetch &rf, int64_t n, int64_t *ref_off, int64_t *seq_off, int64_t *cig_off, int threads = 0)
+{
+    // per read (a 10 kb read has thousands of CIGAR operations: all cores), then the prefix sums
+    ref_off[0] = seq_off[0] = cig_off[0] = 0;
+    const int64_t per = 64;
+    parallel_for((n + per - 1) / per, threads, [&](int64_t t) {
+        for (int64_t k = t * per; k < std::min(n, (t + 1) * per); k++) {
+            const RecView r = rec_of(rf, k);
+            int64_t lead, trail, ops = 0, rl = 0;
+            rec_clips(r, lead, trail);
+            const int nc = r.n_cigar();
+            for (int c = 0; c < nc; c++) {
+                const uint32_t w = r.cig(c), op = w & 15u, len = w >> 4;
+                if (op != 4 && op != 5) ops += len;
+                if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += len;      // (rec_ref_len: M D N = X)
+            }
+            ref_off[k + 1] = rl;
+            seq_off[k + 1] = std::max<int64_t>(0, (int64_t)r.l_seq() - lead - trail);
+            cig_off[k + 1] = ops;
+        }
+    });
+    for (int64_t k = 0; k < n; k++) { ref_off[k + 1] += ref_off[k]; seq_off[k + 1] += seq_off[k]; cig_off[k + 1] += cig_off[k]; }
+}
+
+inline int pack_records(const npore_bam *b, const RecFetch &rf, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n,
+                 uint8_t *refs, const int64_t *ref_off, uint8_t *seqs, const int64_t *seq_off, char *cigs,
+                 const int64_t *cig_off, int threads, bool for_upload = false)
+{
+    std::atomic<int> bad{0};
+    parallel_for(n, threads, [&](int64_t k) {
+        const RecView r = rec_of(rf, k);
+        const int32_t rid = r.ref_id();
+        const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
+        if (fi < 0 || fi >= (int)fa->names.size()) { bad++; return; }
+        // reference bases: FASTA slice [pos, pos + reference_length), what pysam rebuilds from MD (src/bam.pyx:45)
+        const char *ctg = fa->seq((size_t)fi);
+        const int64_t ctg_len = fa->len((size_t)fi);
+        const int64_t rl = ref_off[k + 1] - ref_off[k], pos = r.pos();
+        uint8_t *ro = refs + ref_off[k];
+        {
+            const int64_t q0 = std::min(rl, std::max<int64_t>(0, -pos)), q1 = std::max(q0, std::min(rl, ctg_len - pos));
+            std::memset(ro, 0, (size_t)q0);
+            base_codes(ctg + pos + q0, ro + q0, q1 - q0);
+            std::memset(ro + q1, 0, (size_t)(rl - q1));
+        }
+        // query bases without the soft clips (src/bam.pyx:42)
+        int64_t lead, trail;
+        rec_clips(r, lead, trail);
+        uint8_t *so = seqs + seq_off[k];
+        const int64_t sl = seq_off[k + 1] - seq_off[k];
+        nibble_codes(r.seq(), lead, so, sl);
+        // expanded CIGAR without S and H (src/bam.pyx:59)
+        char *co = cigs + cig_off[k];
+        const int nc = r.n_cigar();
+        for (int c = 0; c < nc; c++) {
+            const uint32_t w = r.cig(c), op = w & 15u, len = w >> 4;
+            if (op == 4 || op == 5) continue;
+            const char ch = op < 10 ? CIGOPS[op] : '?';
+            if (len <= 8) { for (uint32_t q = 0; q < len; q++) co[q] = ch; }      // (most runs are a few ops long)
+            else std::memset(co, ch, len);
+            co += len;
+        }
+        if (for_upload) {       // page-locked staging about to cross PCIe: out of this core's cache first (hostio.hpp)
+            cache_writeback(ro, (size_t)rl);
+            cache_writeback(so, (size_t)sl);
+            cache_writeback(cigs + cig_off[k], (size_t)(cig_off[k + 1] - cig_off[k]));
+        }
+    });
+    return bad ? fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA") : NPORE_OK;
+}
+
+#if defined(__x86_64__)
+// "=ACMGRSVTWYHKDBN"[nibble] for 16 packed bytes at a time (high nibble first); returns the packed bytes done (a multiple of 16)
+__attribute__((target("ssse3"))) inline int64_t nibbles_to_text_ssse3(const uint8_t *src, char *dst, int64_t n_bytes)
+{
+    const __m128i lut = _mm_loadu_si128(reinterpret_cast<const __m128i *>(SEQ16));
+    const __m128i low = _mm_set1_epi8(0x0F);
+    int64_t j = 0;
+    for (; j + 16 <= n_bytes; j += 16) {
+        const __m128i v = _mm_loadu_si128(reinterpret_cast<const __m128i *>(src + j));
+        const __m128i hi = _mm_shuffle_epi8(lut, _mm_and_si128(_mm_srli_epi16(v, 4), low));
+        const __m128i lo = _mm_shuffle_epi8(lut, _mm_and_si128(v, low));
+        _mm_storeu_si128(reinterpret_cast<__m128i *>(dst + 2 * j), _mm_unpacklo_epi8(hi, lo));
+        _mm_storeu_si128(reinterpret_cast<__m128i *>(dst + 2 * j + 16), _mm_unpackhi_epi8(hi, lo));
+    }
+    return j;
+}
+#endif
+
+inline int format_sam_into(const npore_bam *b, const RecFetch &rf, int64_t n, const char *finals, const int64_t *final_off,
+                    const int64_t *final_len, const int32_t *status, int threads, RawBuf &out, int64_t *sam_len)
+{
+    if (!b || n < 0 || !sam_len || (n > 0 && (!finals || !final_off || !final_len || !status)))
+        return fail(NPORE_E_INVALID, "bad argument");
+    // pass 1: line sizes; pass 2: fill (both parallel over reads)
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    // decimal text of v at dst (dst == nullptr: only the length), no terminator
+    auto put_int = [](char *dst, long long v) -> int {
+        char tmp[24];
+        int nd = 0;
+        unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
+        do { tmp[nd++] = (char)('0' + u % 10); u /= 10; } while (u);
+        const int neg = v < 0;
+        if (dst) {
+            if (neg) *dst++ = '-';
+            for (int q = 0; q < nd; q++) dst[q] = tmp[nd - 1 - q];
+        }
+        return nd + neg;
+    };
+#if defined(__x86_64__)
+    static const bool have_ssse3 = __builtin_cpu_supports("ssse3");
+#endif
+    static const struct PairTab {      // two bases of the 4-bit packed sequence per lookup
+        uint16_t pair[256];
+        PairTab() { for (int v = 0; v < 256; v++) pair[v] = (uint16_t)((uint8_t)SEQ16[v >> 4] | ((uint8_t)SEQ16[v & 15] << 8)); }
+    } seqtab;
+    auto line = [&](int64_t k, char *dst) -> int64_t {    // returns the length; writes when dst != nullptr
+        if (status[k] & NPORE_ST_BAD_INPUT) return 0;    // refused reads are not written
+        const RecView r = rec_of(rf, k);
+        int64_t lead, trail;
+        rec_clips(r, lead, trail);
+        const int64_t sl = std::max<int64_t>(0, (int64_t)r.l_seq() - lead - trail);
+        const int32_t rid = r.ref_id();
+        const std::string &rn = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? b->ref_names[(size_t)rid] : std::string("*");
+        const bool noq = r.l_seq() == 0 || r.qual()[0] == 0xFF;
+        const size_t nl = std::strlen(r.name());
+        const long long flag = r.flag(), pos1 = (long long)r.pos() + 1, mapq = r.mapq(), hp = (long long)rec_hp(r),
+                        reflen = (long long)rec_ref_len(r);
+        if (!dst)       // name \t flag \t rname \t pos \t mapq \t cigar \t * \t 0 \t tlen \t seq \t qual \t HP:i:n \n
+            return (int64_t)nl + 1 + put_int(nullptr, flag) + 1 + (int64_t)rn.size() + 1 + put_int(nullptr, pos1) + 1 +
+                   put_int(nullptr, mapq) + 1 + final_len[k] + 5 + put_int(nullptr, reflen) + 1 + sl + 1 + (noq ? 1 : sl) + 6 +
+                   put_int(nullptr, hp) + 1;
+        char *o = dst;
+        std::memcpy(o, r.name(), nl); o += nl;
+        *o++ = '\t'; o += put_int(o, flag); *o++ = '\t';
+        std::memcpy(o, rn.data(), rn.size()); o += rn.size();
+        *o++ = '\t'; o += put_int(o, pos1); *o++ = '\t'; o += put_int(o, mapq); *o++ = '\t';
+        std::memcpy(o, finals + final_off[k], (size_t)final_len[k]); o += final_len[k];
+        std::memcpy(o, "\t*\t0\t", 5); o += 5;
+        o += put_int(o, reflen); *o++ = '\t';
+        {
+            const uint8_t *sq = r.seq();
+            int64_t q = 0, t = lead;
+            if (q < sl && (t & 1)) { o[q++] = SEQ16[sq[t >> 1] & 15]; t++; }
+            const uint8_t *src = sq + (t >> 1);
+            const int64_t pairs = (sl - q) >> 1;
+            char *po = o + q;
+            int64_t j = 0;
+#if defined(__x86_64__)
+            if (have_ssse3) j = nibbles_to_text_ssse3(src, po, pairs);          // 16 packed bytes -> 32 letters per step
+#endif
+            for (; j < pairs; j++) { const uint16_t v = seqtab.pair[src[j]]; std::memcpy(po + 2 * j, &v, 2); }
+            q += 2 * pairs;
+            if (q < sl) { o[q] = SEQ16[src[pairs] >> 4]; q++; }
+            o += sl;
+        }
+        *o++ = '\t';
+        if (noq) *o++ = '*';
+        else {
+            const uint8_t *__restrict ql = r.qual() + lead;
+            char *__restrict qo = o;
+            for (int64_t q = 0; q < sl; q++) qo[q] = (char)(33 + ql[q]);
+            o += sl;
+        }
+        std::memcpy(o, "\tHP:i:", 6); o += 6;
+        o += put_int(o, hp); *o++ = '\n';
+        return (int64_t)(o - dst);
+    };
+    parallel_for(n, threads, [&](int64_t k) { off[(size_t)k + 1] = line(k, nullptr); });
+    for (int64_t k = 0; k < n; k++) off[(size_t)k + 1] += off[(size_t)k];
+    if (!out.ensure((size_t)off[(size_t)n] + 1)) return fail(NPORE_E_NOMEM, "SAM text buffer");
+    parallel_for(n, threads, [&](int64_t k) { if (off[(size_t)k + 1] > off[(size_t)k]) line(k, out.p + off[(size_t)k]); });
+    *sam_len = off[(size_t)n];
+    return NPORE_OK;
+}
+
+// ---- the one-pass reader: the record stream walked once, front to back, no record index ------------------------
+// A stretch of the inflated stream in one buffer: d[0 .. n) lies at offset abs0 of the stream.  The buffer lives as
+// long as somebody points into it (a batch's records).
+struct BamWindow {
+    std::shared_ptr<RawBuf> buf;
+    const uint8_t *d = nullptr;
+    size_t n = 0;
+    uint64_t abs0 = 0;
+};
+
+// The inflated stream of a BGZF file from one block on, in windows of NPORE_BAM_WINDOW_BLOCKS consecutive blocks (1024:
+// <= 64 MB of stream), each inflated ONCE.  ONE inflater thread takes the windows in file order, each on all cores
+// (bgzf_inflate_range; NPORE_INFLATE_THREADS: how many it may take at once), and keeps up to NPORE_BAM_WINDOWS_AHEAD (3)
+// of them ready -- the inflation then runs whenever CPUs are free instead of one window ahead of the walk (the
+// acquisitions of consecutive batches took 12 ... 72 ms that way, the long ones waiting for a window that the SAM text
+// and packing threads had slowed down).  A window is inflated behind HEAD bytes of room, where next() puts the tail the
+// reader carries over from the window before; so every record lies in one buffer.  The thread starts with the first
+// next() and is stopped and joined by the destructor: a reader that ends early (the end of its share, max_reads, a
+// failure) leaves at most that many windows inflated for nothing.
+class BamWindowSource {
+public:
+    static constexpr size_t HEAD = 4u << 20;
+    BamWindowSource(const npore_bam *b, int threads) : b_(b), inflate_threads_(threads)
+    {
+        if (const char *e = std::getenv("NPORE_BAM_WINDOW_BLOCKS")) win_blocks_ = (size_t)std::max(1, std::atoi(e));
+        if (const char *e = std::getenv("NPORE_BAM_WINDOWS_AHEAD")) depth_ = std::max(1, std::atoi(e));
+        if (const char *e = std::getenv("NPORE_INFLATE_THREADS")) inflate_threads_ = std::max(1, std::atoi(e));
+    }
+    BamWindowSource(const BamWindowSource &) = delete;
+    BamWindowSource &operator=(const BamWindowSource &) = delete;
+    ~BamWindowSource()
+    {
+        { std::lock_guard<std::mutex> lk(m_); stop_ = true; }
+        cv_.notify_all();
+        if (thread_.joinable()) thread_.join();
+    }
+    void start_at(size_t block) { next_block_ = block; }         // (before the first next(): a share that begins mid-file)
+    // Replaces w by the next window, the unread tail w.d[from .. w.n) carried in front of it.  1: in place; 0: no block
+    // is left (w stays as it is); -1: failure (fail() called)
+    int next(BamWindow &w, size_t from)
+    {
+        if (next_block_ >= b_->blocks.size()) return 0;
+        if (!thread_.joinable()) thread_ = std::thread([this, first = next_block_] { inflate_ahead(first); });
+        const size_t c = (w.buf && from < w.n) ? w.n - from : 0;
+        const uint64_t win_off = b_->blocks[next_block_].out_off;
+        Pending pd;
+        {
+            std::unique_lock<std::mutex> lk(m_);
+            cv_.wait(lk, [&] { return !ready_.empty() || ended_; });
+            if (ready_.empty()) { fail(NPORE_E_INVALID, "BAM window reader ended early"); return -1; }
+            pd = std::move(ready_.front());
+            ready_.pop_front();
+        }
+        cv_.notify_all();
+        if (!pd.ok || pd.b0 != next_block_) { fail(NPORE_E_INVALID, "corrupt BGZF block (or out of memory)"); return -1; }
+        std::shared_ptr<RawBuf> nw = pd.buf;
+        uint8_t *d0 = reinterpret_cast<uint8_t *>(nw->p) + HEAD;
+        if (c > HEAD) {                                          // a record longer than the room in front: copy once
+            auto big = std::make_shared<RawBuf>();
+            if (!big->ensure(c + pd.bytes + 8)) { fail(NPORE_E_NOMEM, "BAM window"); return -1; }
+            std::memcpy(big->p + c, d0, pd.bytes);
+            nw = big;
+            d0 = reinterpret_cast<uint8_t *>(nw->p) + c;
+        }
+        if (c) std::memcpy(d0 - c, w.d + from, c);
+        w.buf = nw;
+        w.d = d0 - c;
+        w.abs0 = win_off - c;
+        w.n = c + pd.bytes;
+        next_block_ = pd.b1;
+        return 1;
+    }
+
+private:
+    struct Pending { std::shared_ptr<RawBuf> buf; size_t bytes = 0, b0 = 0, b1 = 0; bool ok = false; };
+    void inflate_ahead(size_t b0)                                // the inflater thread
+    {
+        const size_t end = b_->blocks.size();
+        for (;;) {
+            {
+                std::unique_lock<std::mutex> lk(m_);
+                cv_.wait(lk, [&] { return stop_ || (int)ready_.size() < depth_; });
+                if (stop_ || b0 >= end) { ended_ = true; cv_.notify_all(); return; }
+            }
+            Pending pd;
+            pd.b0 = b0;
+            pd.b1 = std::min(end, b0 + win_blocks_);
+            const uint64_t w0 = b_->blocks[b0].out_off, w1 = b_->blocks[pd.b1 - 1].out_off + b_->blocks[pd.b1 - 1].out_len;
+            pd.bytes = (size_t)(w1 - w0);
+            try {                                                // (no exception may leave a thread: next() sees ok == false)
+                pd.buf = std::make_shared<RawBuf>();
+                pd.ok = pd.buf->ensure(HEAD + pd.bytes + 8) &&
+                        bgzf_inflate_range(*b_->file, b_->blocks, b0, pd.b1, reinterpret_cast<uint8_t *>(pd.buf->p) + HEAD, inflate_threads_);
+            } catch (...) {
+                pd.ok = false;
+            }
+            b0 = pd.b1;
+            {
+                std::lock_guard<std::mutex> lk(m_);
+                ready_.push_back(std::move(pd));
+            }
+            cv_.notify_all();
+        }
+    }
+    const npore_bam *b_;
+    size_t win_blocks_ = 1024;
+    int depth_ = 3, inflate_threads_;
+    size_t next_block_ = 0;                  // the block the next window begins with (the walking thread's)
+    std::mutex m_;                           // guards ready_, stop_, ended_
+    std::condition_variable cv_;
+    std::deque<Pending> ready_;
+    bool stop_ = false, ended_ = false;
+    std::thread thread_;
+};
+
+// what a one-pass walk refuses before it begins
+inline int one_pass_args_check(const npore_bam *b, int n_regions, const int32_t *ref_id, int64_t max_reads)
+{
+    if (!b->file || b->blocks.empty()) return fail(NPORE_E_INVALID, "one-pass ingest needs a handle opened on a BGZF file (modes 2 and 3)");
+    for (int g = 0; g < n_regions; g++)
+        if (ref_id[g] < 0 || ref_id[g] >= (int32_t)b->ref_names.size() || (g > 0 && ref_id[g] <= ref_id[g - 1]))
+            return fail(NPORE_E_UNSUPPORTED, "one-pass ingest takes at most one region per contig, in the order of the BAM header");
+    if (b->has_share && max_reads > 0)
+        return fail(NPORE_E_UNSUPPORTED, "one-pass ingest: max_reads needs one process (the ranks cannot know how many reads the others keep)");
+    return NPORE_OK;
+}
+
+// The records of a coordinate-sorted BAM that npore_bam_select would keep for the same regions (at most one per contig,
+// in header order), max_reads and flag filter, found by ONE walk over the stream, batch by batch.  Several processes on
+// one file (npore_bam_set_share): this one keeps the records that START in [share_begin, share_end) of the inflated
+// stream -- a stretch that begins at a record; the header was read when the handle was opened.
+// next_batch() is called by one thread at a time (whichever packing thread holds the file pipeline's `acquired` gate):
+// the walker's state needs no lock, the window source's queue has its own.
+class BamRecordWalker {
+public:
+    BamRecordWalker(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
+                    int64_t max_reads, int threads)
+        : b_(b), src_(b, threads), n_regions_(n_regions), ref_id_(ref_id), start_(start), stop_(stop), max_reads_(max_reads),
+          done_(n_regions == 0)
+    {
+        if (!b->has_share) return;
+        if (b->share_begin == UINT64_MAX) done_ = true;          // nothing left for this rank
+        else if (b->share_begin > 0) { src_.start_at(b->share_block); have_header_ = seek_share_ = true; }
+    }
+    // The next (up to) batch_reads kept records: pointers to them in rf.ptr, the windows they lie in added to `keep`.
+    // Returns their number, 0 at the end of the walk, a negative code after fail().
+    int64_t next_batch(RecFetch &rf, std::vector<std::shared_ptr<RawBuf>> &keep, int64_t batch_reads)
+    {
+        rf.ptr.clear();
+        while ((int64_t)rf.ptr.size() < batch_reads && !done_) {
+            if (!have_header_) {
+                npore_bam scratch;
+                size_t hdr_end = 0;
+                const int hrc = win_.buf ? bam_parse_header(&scratch, win_.d, win_.n, &hdr_end) : -1;
+                if (hrc == 0) return fail(NPORE_E_INVALID, "not a BAM file");
+                if (hrc < 0) {                                   // the header does not end in what is inflated so far
+                    p_ = 0;
+                    if (load_window() != 1) return -1;           // (the blocks running out here is a failure too)
+                    continue;
+                }
+                have_header_ = true;
+                p_ = hdr_end;
+                continue;
+            }
+            size_t nx = 0;
+            const Frame f = frame_record(win_.d, win_.n, p_, nx);
+            if (f == Frame::CORRUPT) return fail(NPORE_E_INVALID, "truncated BAM record");
+            if (f == Frame::MORE) {
+                const int lw = load_window();
+                if (lw < 0) return lw;
+                if (lw == 0) done_ = true;
+                continue;
+            }
+            if (win_.abs0 + p_ >= b_->share_end) { done_ = true; break; }        // the next process's stretch begins here
+            const uint8_t *q = win_.d + p_;
+            p_ = nx;
+            if (!record_is_sound(q)) return fail(NPORE_E_INVALID, "corrupt BAM record");
+            const RecView rv = rec_view(q);
+            const int32_t rid = rv.ref_id();
+            if (rid < 0) continue;                               // unplaced
+            if (rid < last_rid_) return fail(NPORE_E_UNSUPPORTED, "the BAM is not sorted by reference: one-pass ingest needs a coordinate-sorted file");
+            last_rid_ = rid;
+            while (g_ < n_regions_ && ref_id_[g_] < rid) g_++;
+            if (g_ == n_regions_) { done_ = true; break; }
+            if (ref_id_[g_] != rid) continue;
+            const int64_t pos = rv.pos(), rl = rec_ref_len(rv);
+            if (!(pos < stop_[g_] && pos + rl > start_[g_])) continue;           // overlaps [start, stop)
+            if (max_reads_ > 0 && kept_ >= max_reads_) { done_ = true; break; }  // src/bam.pyx:29-30
+            if (rv.flag() & (0x100 | 0x800 | 0x4)) continue;                     // secondary / supplementary / unmapped, :31-32
+            rf.ptr.push_back(q);
+            if (keep.empty() || keep.back() != win_.buf) keep.push_back(win_.buf);
+            kept_++;
+        }
+        return (int64_t)rf.ptr.size();
+    }
+
+private:
+    // the next window behind what has been walked, the unread tail in front.  1: in place; 0: the blocks have run out
+    // at a record's end; -1: failure (fail() called) -- they ran out inside a record, or before the header's end
+    int load_window()
+    {
+        const int rc = src_.next(win_, p_);
+        if (rc == 0 && (!have_header_ || (win_.buf && p_ < win_.n))) {
+            fail(NPORE_E_INVALID, have_header_ ? "truncated BAM record" : "not a BAM file");
+            return -1;
+        }
+        if (rc != 1) return rc;
+        p_ = 0;
+        if (seek_share_) { p_ = (size_t)(b_->share_begin - win_.abs0); seek_share_ = false; }   // (the first window of a share that begins mid-file)
+        return 1;
+    }
+    const npore_bam *b_;
+    BamWindowSource src_;
+    BamWindow win_;                          // the window being walked
+    size_t p_ = 0;                           // ... and the offset of the next record in it
+    bool have_header_ = false, seek_share_ = false;
+    const int n_regions_;
+    const int32_t *const ref_id_;            // the regions, ascending in ref_id
+    const int64_t *const start_, *const stop_;
+    int g_ = 0;                              // the region the walk has reached
+    const int64_t max_reads_;
+    int64_t kept_ = 0;
+    int32_t last_rid_ = -1;                  // (the sorted-by-reference check)
+    bool done_;
+};
+
+}  // namespace npore

@@ -10,8 +10,10 @@
 // BAM = BGZF (independent deflate blocks of <= 64 KiB, each announcing its compressed size in a
 // gzip extra field and its inflated size in its trailer) around a simple binary record stream,
 // so the blocks are located with one pass over the file and inflated in parallel.
+//
+// This header holds the pieces (BGZF, FASTA, record accessors, the handles); bam_reader.hpp the readers built from
+// them.  Neither includes a HIP header: both compile for a CPU alone (tests/model/bam_walk.cpp does).
 #pragma once
-#include <hip/hip_runtime.h>
 #include <fcntl.h>
 #include <sched.h>
 #include <sys/mman.h>
@@ -74,6 +76,14 @@ inline int host_threads(int threads)
     return threads > 0 ? threads : std::min(64, usable_cpus());
 }
 
+// the calling thread's last failure (npore_last_error); fail() notes it and hands the code back
+inline thread_local std::string g_err;
+inline int fail(int code, const std::string &msg)
+{
+    g_err = msg;
+    return code;
+}
+
 // uninitialised byte buffer (a std::vector would zero hundreds of megabytes per batch)
 // NPORE_ALLOC_TRACE=1: one line on stderr per device / page-locked allocation (what a cold run pays once)
 inline bool alloc_trace_on() { static const bool on = std::getenv("NPORE_ALLOC_TRACE") != nullptr; return on; }
@@ -93,17 +103,13 @@ struct AllocTrace {
 struct RawBuf {
     char *p = nullptr;
     size_t cap = 0;
-    bool pinned = false;       // page-locked (hipHostMalloc): buffers that cross PCIe every batch
     RawBuf() = default;
-    explicit RawBuf(bool pin) : pinned(pin) {}
     RawBuf(const RawBuf &) = delete;
     RawBuf &operator=(const RawBuf &) = delete;
     ~RawBuf() { release(); }
     void release()
     {
-        if (!p) return;
-        if (pinned) (void)hipHostFree(p);
-        else std::free(p);
+        std::free(p);
         p = nullptr;
         cap = 0;
     }
@@ -112,29 +118,22 @@ struct RawBuf {
         if (n <= cap) return true;
         release();
         n += n / 4;            // head-room: batches of a run differ a little in size
-        if (pinned) {
-            void *q = nullptr;
-            AllocTrace tr("hipHostMalloc", n);
-            if (hipHostMalloc(&q, n, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                pinned = false;
-                if (std::getenv("NPORE_DEBUG")) std::fprintf(stderr, "npore: hipHostMalloc(%zu) failed, pageable staging buffer\n", n);
-            }
-            else p = static_cast<char *>(q);
-        }
-        if (!pinned) {
-            p = static_cast<char *>(std::malloc(n));
-            // a large buffer is touched for the first time by all threads at once (the FASTA's bases, an inflated window,
-            // a batch's SAM text): with 2 MB pages that is one page fault per 2 MB instead of 512 (where the kernel
-            // offers transparent huge pages on request; a no-op elsewhere)
-            if (p && n >= (size_t)32 << 20 && std::getenv("NPORE_NO_THP") == nullptr) {
-                const uintptr_t a = ((uintptr_t)p + ((size_t)2 << 20) - 1) & ~(uintptr_t)(((size_t)2 << 20) - 1);
-                const uintptr_t e = ((uintptr_t)p + n) & ~(uintptr_t)(((size_t)2 << 20) - 1);
-                if (e > a) (void)::madvise(reinterpret_cast<void *>(a), e - a, MADV_HUGEPAGE);
-            }
-        }
+        p = alloc(n);
         cap = p ? n : 0;
         return p != nullptr;
+    }
+    static char *alloc(size_t n)
+    {
+        char *q = static_cast<char *>(std::malloc(n));
+        // a large buffer is touched for the first time by all threads at once (the FASTA's bases, an inflated window,
+        // a batch's SAM text): with 2 MB pages that is one page fault per 2 MB instead of 512 (where the kernel
+        // offers transparent huge pages on request; a no-op elsewhere)
+        if (q && n >= (size_t)32 << 20 && std::getenv("NPORE_NO_THP") == nullptr) {
+            const uintptr_t a = ((uintptr_t)q + ((size_t)2 << 20) - 1) & ~(uintptr_t)(((size_t)2 << 20) - 1);
+            const uintptr_t e = ((uintptr_t)q + n) & ~(uintptr_t)(((size_t)2 << 20) - 1);
+            if (e > a) (void)::madvise(reinterpret_cast<void *>(a), e - a, MADV_HUGEPAGE);
+        }
+        return q;
     }
 };
 

@@ -1,6 +1,7 @@
 // npore_api.cpp -- C ABI (include/npore_amd.h) and host orchestration.
 // Compiled with hipcc for gfx950 only.  There is no CPU execution path for the
-// DP here: without a gfx950 device npore_ctx_create fails.
+// DP here: without a gfx950 device npore_ctx_create fails.  What reads BAM / FASTA
+// files and writes SAM text needs no device and lives in bam_reader.hpp / hostio.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,15 +21,11 @@
 #include <thread>
 #include <vector>
 
-#include <unistd.h>
-#if defined(__x86_64__)
-#include <immintrin.h>
-#endif
-
 #include "../../include/npore_amd.h"
 #include "confusion.hpp"
 #include "glue.hpp"
 #include "hostio.hpp"
+#include "bam_reader.hpp"
 #include "kernels.hpp"
 #include "prep_kernels.hpp"
 #include "annot_wave.hpp"
@@ -38,12 +35,6 @@ using namespace npore;
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string &msg)
-{
-    g_err = msg;
-    return code;
-}
 // No C++ exception may cross the C ABI: the entry points that allocate are function-try-blocks ending in one of these.
 #define NPORE_CATCH_INT                                                                             \
     catch (const std::bad_alloc &) { return fail(NPORE_E_NOMEM, "out of host memory"); }           \
@@ -125,6 +116,45 @@ struct HostBuf {   // pinned staging
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// Page-locked staging (hipHostMalloc) of the BAM -> SAM pipeline: the buffers of a batch that cross PCIe.  Unlike HostBuf
+// it does not fail where the runtime has no page-locked memory left: the buffer is pageable from then on.
+struct PinnedBuf {
+    char *p = nullptr;
+    size_t cap = 0;
+    bool pinned = true;        // false once hipHostMalloc has failed: pageable (RawBuf::alloc) for the rest of its life
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+    void release()
+    {
+        if (!p) return;
+        if (pinned) (void)hipHostFree(p);
+        else std::free(p);
+        p = nullptr;
+        cap = 0;
+    }
+    bool ensure(size_t n)
+    {
+        if (n <= cap) return true;
+        release();
+        n += n / 4;            // head-room: batches of a run differ a little in size
+        if (pinned) {
+            void *q = nullptr;
+            AllocTrace tr("hipHostMalloc", n);
+            if (hipHostMalloc(&q, n, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                pinned = false;
+                if (std::getenv("NPORE_DEBUG")) std::fprintf(stderr, "npore: hipHostMalloc(%zu) failed, pageable staging buffer\n", n);
+            }
+            else p = static_cast<char *>(q);
+        }
+        if (!pinned) p = RawBuf::alloc(n);
+        cap = p ? n : 0;
+        return p != nullptr;
+    }
+};
+
 }  // namespace
 
 // One batch on its way through the BAM -> SAM pipeline: host staging (page-locked where it crosses PCIe) and offsets.
@@ -140,15 +170,16 @@ struct TextCompact {
 };
 
 struct npore_batch_slot {
-    RawBuf refs{true}, seqs{true}, cigs{true}, alns{true}, finals, sam;
-    RawBuf raw{true};            // device pack: the heads of the batch's records (fixed fields ... 4-bit bases), one after the other
+    PinnedBuf refs, seqs, cigs, alns;
+    RawBuf finals, sam;
+    PinnedBuf raw;               // device pack: the heads of the batch's records (fixed fields ... 4-bit bases), one after the other
     std::vector<int64_t> rawo;   // ... and where each starts
     // device glue: the batch's texts compacted on the device (unpack_kernels.hpp compact_texts_kernel) -- the compact buffer
     // and its cursor there, the copied front of it and the reads' offsets here (page-locked)
     DevBuf d_ctext, d_cursor;
-    RawBuf ctext_pin{true}, coff_pin{true};
+    PinnedBuf ctext_pin, coff_pin;
     int64_t ctext_copied = 0;              // bytes of the compact buffer the batch's last group sent behind its kernels
-    RawBuf olen_pin{true}, st_pin{true};   // lengths / status bits of an ASYNCHRONOUS batch land here (page-locked: a copy into
+    PinnedBuf olen_pin, st_pin;            // lengths / status bits of an ASYNCHRONOUS batch land here (page-locked: a copy into
                                            // pageable memory would make the enqueueing call wait for the whole batch)
     hipEvent_t done = nullptr;             // ... behind which this event is recorded (npore_bam_realign_file)
     std::vector<std::shared_ptr<RawBuf>> keep;   // one-pass ingest: the inflated windows the batch's records lie in
@@ -213,7 +244,6 @@ struct npore_ctx {
     // three non-blocking streams: preparation (also every copy), fill kernels, traceback + gather; events order
     // the stages of a group, the streams let stages of neighbouring groups run side by side
     hipStream_t stream = nullptr, s_fill[2] = {nullptr, nullptr}, s_post = nullptr;
-    const TextCompact *pending_compact = nullptr;      // file pipeline: the next align_batch_raw / _host call compacts its texts
     int next_fill = 0;           // the fill stream the next group's fill kernel goes to
     int fill_streams = 2;        // 1: every fill kernel on one stream (npore_ctx_set "fill_streams")
     hipEvent_t ev[8] = {};       // [4..7] H2D / D2H of the host-buffer entry point, [0] the caller's stream
@@ -841,6 +871,37 @@ int run_core(npore_ctx *ctx, const AlignArgs &a, const OutTarget &ot, hipStream_
     return NPORE_OK;
 }
 
+// A batch in host buffers (a.h_*: filled by the caller, the three public entry points and the file pipeline): what all
+// of them refuse, then run_core.  Every group of reads uploads its own slice and downloads its own results (run_group):
+// the copies of one group run beside the kernels of its neighbours, and the caller's arrays are used as they are.
+// With a.h_raw, align()'s inputs are still inside BAM records: `h_raw` holds the heads of the records (fixed fields ...
+// 4-bit bases) one after the other, h_raw_off[n + 1] where each starts, and the three offset arrays are the sizes
+// pack_sizes_of found; every group unpacks its slice on the device (unpack_kernels.hpp) against the context's device
+// copy of the FASTA (device_fasta).
+int align_batch(npore_ctx *ctx, const AlignArgs &a, bool sync)
+{
+    if (!ctx) return fail(NPORE_E_INVALID, "null context");
+    if (a.n_reads < 0) return fail(NPORE_E_INVALID, "n_reads < 0");
+    if (a.n_reads == 0) return NPORE_OK;
+    const bool inputs = a.h_raw ? a.h_raw_off && a.d_ctg : a.h_refs && a.h_seqs && a.h_cigs;
+    if (!inputs || !a.h_out || !a.h_ref_off || !a.h_seq_off || !a.h_cig_off || !a.h_out_off || !a.h_out_len || !a.h_status)
+        return fail(NPORE_E_INVALID, "null argument");
+    if (!a.h_raw && a.h_out_off[a.n_reads] < a.h_out_off[0]) return fail(NPORE_E_INVALID, "out_off not ascending");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (ctx->deferred_rc) return quiesce(ctx);   // a group of an earlier asynchronous call failed
+    return run_core(ctx, a, OutTarget{nullptr, nullptr, nullptr, nullptr}, nullptr, sync);
+}
+
+// AlignArgs of a batch whose offset arrays and output slots are the caller's (the inputs: h_refs ... or h_raw, by the caller)
+AlignArgs host_batch_args(int64_t n_reads, const int64_t *ref_off, const int64_t *seq_off, const int64_t *cig_off, float indel_start,
+                          float indel_extend, int max_b_rows, int r, char *out, const int64_t *out_off, int64_t *out_len, int32_t *status)
+{
+    AlignArgs a{n_reads, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ref_off, seq_off, cig_off,
+                indel_start, indel_extend, max_b_rows, r};
+    a.h_out = out; a.h_out_off = out_off; a.h_out_len = out_len; a.h_status = status;
+    return a;
+}
+
 }  // namespace
 
 extern "C" {
@@ -965,55 +1026,6 @@ void npore_ctx_destroy(npore_ctx *ctx)
     delete ctx;
 }
 
-static int align_batch_host(npore_ctx *ctx, int64_t n_reads, const uint8_t *refs, const int64_t *ref_off,
-                            const uint8_t *seqs, const int64_t *seq_off, const char *cigars, const int64_t *cig_off,
-                            float indel_start, float indel_extend, int max_b_rows, int r, char *out,
-                            const int64_t *out_off, int64_t *out_len, int32_t *status, bool sync, bool final_text = false)
-{
-    if (!ctx) return fail(NPORE_E_INVALID, "null context");
-    if (n_reads < 0) return fail(NPORE_E_INVALID, "n_reads < 0");
-    if (n_reads == 0) return NPORE_OK;
-    if (!refs || !seqs || !cigars || !out || !ref_off || !seq_off || !cig_off || !out_off || !out_len || !status)
-        return fail(NPORE_E_INVALID, "null argument");
-    if (out_off[n_reads] < out_off[0]) return fail(NPORE_E_INVALID, "out_off not ascending");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->deferred_rc) return quiesce(ctx);   // a group of an earlier asynchronous call failed
-    // every group of reads uploads its own slice and downloads its own results (run_group): the copies of one
-    // group run beside the kernels of its neighbours, and the caller's arrays are used as they are
-    AlignArgs a{n_reads, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ref_off, seq_off, cig_off,
-                indel_start, indel_extend, max_b_rows, r};
-    a.h_refs = refs; a.h_seqs = seqs; a.h_cigs = cigars;
-    a.h_out = out; a.h_out_off = out_off; a.h_out_len = out_len; a.h_status = status;
-    a.final_text = final_text;
-    if (final_text) { a.compact = ctx->pending_compact; ctx->pending_compact = nullptr; }
-    return run_core(ctx, a, OutTarget{nullptr, nullptr, nullptr, nullptr}, nullptr, sync);
-}
-
-// The same with align()'s inputs still inside BAM records: `raw` holds the heads of the records (fixed fields ... 4-bit
-// bases) one after the other, raw_off[n + 1] where each starts; the three offset arrays are the sizes pack_sizes_of
-// found.  Every group uploads its slice of `raw` and unpacks it on the device (unpack_kernels.hpp); the contigs are the
-// context's device copy of the FASTA (device_fasta).  Asynchronous, final CIGAR text out: the file pipeline's call.
-static int align_batch_raw(npore_ctx *ctx, int64_t n_reads, const uint8_t *raw, const int64_t *raw_off, const int64_t *ref_off,
-                           const int64_t *seq_off, const int64_t *cig_off, float indel_start, float indel_extend, int max_b_rows,
-                           int r, char *out, const int64_t *out_off, int64_t *out_len, int32_t *status)
-{
-    if (!ctx) return fail(NPORE_E_INVALID, "null context");
-    if (n_reads <= 0) return n_reads < 0 ? fail(NPORE_E_INVALID, "n_reads < 0") : NPORE_OK;
-    if (!raw || !raw_off || !out || !ref_off || !seq_off || !cig_off || !out_off || !out_len || !status || !ctx->d_ctg.p)
-        return fail(NPORE_E_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->deferred_rc) return quiesce(ctx);
-    AlignArgs a{n_reads, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ref_off, seq_off, cig_off,
-                indel_start, indel_extend, max_b_rows, r};
-    a.h_raw = raw; a.h_raw_off = raw_off;
-    a.d_ctg = ctx->d_ctg.as<CtgEntry>(); a.n_ctg = ctx->n_ctg;
-    a.h_out = out; a.h_out_off = out_off; a.h_out_len = out_len; a.h_status = status;
-    a.final_text = true;
-    a.compact = ctx->pending_compact;
-    ctx->pending_compact = nullptr;
-    return run_core(ctx, a, OutTarget{nullptr, nullptr, nullptr, nullptr}, nullptr, false);
-}
-
 // The FASTA on the device (once per FASTA and context) and, per BAM reference, where its contig lies there.
 static int device_fasta(npore_ctx *ctx, const npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref)
 {
@@ -1043,8 +1055,9 @@ int npore_align_batch(npore_ctx *ctx, int64_t n_reads, const uint8_t *refs, cons
                       float indel_start, float indel_extend, int max_b_rows, int r, char *out,
                       const int64_t *out_off, int64_t *out_len, int32_t *status)
 try {
-    return align_batch_host(ctx, n_reads, refs, ref_off, seqs, seq_off, cigars, cig_off, indel_start, indel_extend,
-                            max_b_rows, r, out, out_off, out_len, status, true);
+    AlignArgs a = host_batch_args(n_reads, ref_off, seq_off, cig_off, indel_start, indel_extend, max_b_rows, r, out, out_off, out_len, status);
+    a.h_refs = refs; a.h_seqs = seqs; a.h_cigs = cigars;
+    return align_batch(ctx, a, true);
 }
 NPORE_CATCH_INT
 
@@ -1053,8 +1066,9 @@ int npore_align_batch_async(npore_ctx *ctx, int64_t n_reads, const uint8_t *refs
                             float indel_start, float indel_extend, int max_b_rows, int r, char *out,
                             const int64_t *out_off, int64_t *out_len, int32_t *status)
 try {
-    return align_batch_host(ctx, n_reads, refs, ref_off, seqs, seq_off, cigars, cig_off, indel_start, indel_extend,
-                            max_b_rows, r, out, out_off, out_len, status, false);
+    AlignArgs a = host_batch_args(n_reads, ref_off, seq_off, cig_off, indel_start, indel_extend, max_b_rows, r, out, out_off, out_len, status);
+    a.h_refs = refs; a.h_seqs = seqs; a.h_cigs = cigars;
+    return align_batch(ctx, a, false);
 }
 NPORE_CATCH_INT
 
@@ -1063,8 +1077,10 @@ int npore_align_batch_cigars(npore_ctx *ctx, int64_t n_reads, const uint8_t *ref
                              float indel_start, float indel_extend, int max_b_rows, int r, char *out,
                              const int64_t *out_off, int64_t *out_len, int32_t *status)
 try {
-    return align_batch_host(ctx, n_reads, refs, ref_off, seqs, seq_off, cigars, cig_off, indel_start, indel_extend,
-                            max_b_rows, r, out, out_off, out_len, status, true, true);
+    AlignArgs a = host_batch_args(n_reads, ref_off, seq_off, cig_off, indel_start, indel_extend, max_b_rows, r, out, out_off, out_len, status);
+    a.h_refs = refs; a.h_seqs = seqs; a.h_cigs = cigars;
+    a.final_text = true;                 // (no a.compact: the text of every read into the caller's slot)
+    return align_batch(ctx, a, true);
 }
 NPORE_CATCH_INT
 
@@ -1481,277 +1497,13 @@ int npore_debug_fetch_tb(npore_ctx *ctx, int64_t offset, void *dst, int64_t byte
 }
 
 
-// ---- BAM ingest / SAM emit (hostio.hpp) ---------------------------------------------------------
-namespace {
-// header of a BAM stream at d[0 .. N): text, references; *hdr_end = offset of the first record.  -1: more bytes needed
-// (streamed mode reads on), 0: corrupt, 1: ok
-int bam_parse_header(npore_bam *b, const uint8_t *d, size_t N, size_t *hdr_end)
-{
-    if (N < 12) return -1;
-    if (std::memcmp(d, "BAM\1", 4) != 0) return 0;
-    size_t p = 4;
-    const int64_t l_text = rdi32(&d[p]);
-    p += 4;
-    if (l_text < 0) return 0;
-    if (p + (size_t)l_text + 4 > N) return -1;
-    b->text.assign(reinterpret_cast<const char *>(&d[p]), (size_t)l_text);
-    while (!b->text.empty() && b->text.back() == '\0') b->text.pop_back();
-    p += (size_t)l_text;
-    const int32_t n_ref = rdi32(&d[p]);
-    p += 4;
-    if (n_ref < 0) return 0;
-    b->ref_names.clear();
-    b->ref_lens.clear();
-    for (int32_t k = 0; k < n_ref; k++) {
-        if (p + 4 > N) return -1;
-        const int32_t l_name = rdi32(&d[p]);
-        if (l_name < 1) return 0;
-        if (p + 8 + (size_t)l_name > N) return -1;
-        b->ref_names.emplace_back(reinterpret_cast<const char *>(&d[p + 4]), (size_t)l_name - 1);
-        b->ref_lens.push_back(rdi32(&d[p + 4 + (size_t)l_name]));
-        p += 8 + (size_t)l_name;
-    }
-    *hdr_end = p;
-    return 1;
-}
-
-// what selection needs of the records in d[first record .. ): validation + metadata on all cores.  `offs` = offsets of
-// the records' block_size fields relative to d; the metadata is appended to the handle's arrays.
-bool bam_index_records(npore_bam *b, const uint8_t *d, const std::vector<int64_t> &offs, int64_t global_base, int threads)
-{
-    const int64_t n = (int64_t)offs.size(), at = (int64_t)b->rec_off.size();
-    b->rec_off.resize((size_t)(at + n));
-    b->m_ref.resize((size_t)(at + n));
-    b->m_pos.resize((size_t)(at + n));
-    b->m_span.resize((size_t)(at + n));
-    b->m_flag.resize((size_t)(at + n));
-    std::atomic<int> corrupt{0};
-    const int64_t per = 256;
-    parallel_for((n + per - 1) / per, threads, [&](int64_t blk) {
-        for (int64_t i = blk * per; i < std::min(n, (blk + 1) * per); i++) {
-            // the variable-length parts the accessors will walk must lie inside the record
-            const uint8_t *q = d + offs[(size_t)i];
-            const int32_t bs = rdi32(q);
-            const uint8_t *f = q + 4;
-            const int64_t l_rn = f[8], n_cig = rd16(f + 12), l_seq = rdi32(f + 16);
-            if (l_rn < 1 || l_seq < 0 || 32 + l_rn + 4 * n_cig + (l_seq + 1) / 2 + l_seq > bs || f[32 + l_rn - 1] != 0) { corrupt++; return; }
-            const RecView r = rec_view(q);
-            const int64_t span = rec_ref_len(r);
-            b->rec_off[(size_t)(at + i)] = global_base + offs[(size_t)i];
-            b->m_ref[(size_t)(at + i)] = r.ref_id();
-            b->m_pos[(size_t)(at + i)] = r.pos();
-            b->m_span[(size_t)(at + i)] = (int32_t)std::min<int64_t>(span, INT32_MAX);
-            b->m_flag[(size_t)(at + i)] = (uint16_t)r.flag();
-        }
-    });
-    return corrupt == 0;
-}
-
-// per-reference record lists and the shortcuts of npore_bam_select, from the per-record metadata
-void bam_finish_index(npore_bam *b)
-{
-    const int32_t n_ref = (int32_t)b->ref_names.size();
-    b->ref_has_reads.assign((size_t)n_ref, 0);
-    b->by_ref.assign((size_t)n_ref, {});
-    b->ref_sorted.assign((size_t)n_ref, 1);
-    b->ref_max_len.assign((size_t)n_ref, 0);
-    std::vector<int64_t> last_pos((size_t)n_ref, -1);
-    const int64_t n_rec = (int64_t)b->rec_off.size();
-    for (int64_t i = 0; i < n_rec; i++) {
-        const int32_t rid = b->m_ref[(size_t)i];
-        if (rid >= 0 && rid < n_ref) {
-            const int64_t pos = b->m_pos[(size_t)i];
-            b->ref_has_reads[(size_t)rid] = 1;
-            b->by_ref[(size_t)rid].push_back(i);
-            if (pos < last_pos[(size_t)rid]) b->ref_sorted[(size_t)rid] = 0;
-            last_pos[(size_t)rid] = pos;
-            b->ref_max_len[(size_t)rid] = std::max<int64_t>(b->ref_max_len[(size_t)rid], b->m_span[(size_t)i]);
-        }
-    }
-}
-
-// STREAMED open: block table, then the stream in windows of `win_blocks` BGZF blocks (inflated on all cores, walked,
-// dropped); a record that straddles two windows is carried over.  Resident: one window + 22 bytes per record.
-npore_bam *bam_open_streamed(const char *path, int threads, std::unique_ptr<PreadFile> file, const char *index_path)
-{
-    std::unique_ptr<npore_bam> hold(new npore_bam());
-    npore_bam *b = hold.get();
-    b->streamed = true;
-    b->file = std::move(file);
-    uint64_t total = 0;
-    if (!bgzf_scan(*b->file, b->blocks, total)) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BGZF file"); return nullptr; }
-    b->data_size = (size_t)total;
-    if (index_path && *index_path) {        // another process of this node has made the record index already
-        MappedFile ix;
-        const uint8_t *q = nullptr;
-        if (ix.open(index_path) && ix.n >= 32 && std::memcmp(ix.p, "NPOREIX1", 8) == 0) q = ix.p;
-        if (q) {
-            uint64_t n_rec, hdr_len, tot;
-            std::memcpy(&n_rec, q + 8, 8); std::memcpy(&hdr_len, q + 16, 8); std::memcpy(&tot, q + 24, 8);
-            size_t hdr_end = 0;
-            const size_t need = 32 + hdr_len + n_rec * 22;
-            if (tot == total && ix.n >= need && bam_parse_header(b, q + 32, (size_t)hdr_len, &hdr_end) == 1) {
-                const uint8_t *a = q + 32 + hdr_len;
-                b->rec_off.resize(n_rec); b->m_ref.resize(n_rec); b->m_pos.resize(n_rec); b->m_span.resize(n_rec); b->m_flag.resize(n_rec);
-                std::memcpy(b->rec_off.data(), a, n_rec * 8); a += n_rec * 8;
-                std::memcpy(b->m_ref.data(), a, n_rec * 4); a += n_rec * 4;
-                std::memcpy(b->m_pos.data(), a, n_rec * 4); a += n_rec * 4;
-                std::memcpy(b->m_span.data(), a, n_rec * 4); a += n_rec * 4;
-                std::memcpy(b->m_flag.data(), a, n_rec * 2);
-                bam_finish_index(b);
-                return hold.release();
-            }
-        }
-        // (an unusable index file: fall through and index the file here)
-    }
-    size_t win_blocks = 4096;               // <= 256 MB of inflated stream per window
-    if (const char *e = std::getenv("NPORE_BAM_WINDOW_BLOCKS")) win_blocks = (size_t)std::max(1, std::atoi(e));
-    RawBuf win;
-    std::vector<uint8_t> carry;             // the incomplete tail of the previous window
-    uint64_t carry_at = 0;                  // stream offset of carry[0]
-    bool have_header = false;
-    std::vector<int64_t> offs;
-    for (size_t b0 = 0; b0 < b->blocks.size();) {
-        const size_t b1 = std::min(b->blocks.size(), b0 + win_blocks);
-        const uint64_t w0 = b->blocks[b0].out_off, w1 = b->blocks[b1 - 1].out_off + b->blocks[b1 - 1].out_len;
-        if (!win.ensure(carry.size() + (size_t)(w1 - w0) + 8)) { fail(NPORE_E_NOMEM, "BAM window"); return nullptr; }
-        uint8_t *d = reinterpret_cast<uint8_t *>(win.p);
-        if (!carry.empty()) std::memcpy(d, carry.data(), carry.size());
-        if (!bgzf_inflate_range(*b->file, b->blocks, b0, b1, d + carry.size(), threads)) {
-            fail(NPORE_E_INVALID, std::string("'") + path + "': corrupt BGZF block");
-            return nullptr;
-        }
-        const uint64_t base = carry.empty() ? w0 : carry_at;      // stream offset of d[0]
-        const size_t N = carry.size() + (size_t)(w1 - w0);
-        size_t p = 0;
-        if (!have_header) {
-            size_t hdr_end = 0;
-            const int rc = bam_parse_header(b, d, N, &hdr_end);
-            if (rc == 0) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file"); return nullptr; }
-            if (rc < 0) {                                         // the header does not end in this window: read on
-                if (b1 == b->blocks.size()) { fail(NPORE_E_INVALID, "truncated BAM header"); return nullptr; }
-                carry.assign(d, d + N);
-                carry_at = base;
-                b0 = b1;
-                continue;
-            }
-            have_header = true;
-            p = hdr_end;
-        }
-        offs.clear();
-        while (p + 4 <= N) {
-            const int32_t bs = rdi32(&d[p]);
-            if (bs < 32) { fail(NPORE_E_INVALID, "truncated BAM record"); return nullptr; }
-            if (p + 4 + (size_t)bs > N) break;
-            offs.push_back((int64_t)p);
-            p += 4 + (size_t)bs;
-        }
-        if (!bam_index_records(b, d, offs, (int64_t)base, threads)) { fail(NPORE_E_INVALID, "corrupt BAM record"); return nullptr; }
-        carry.assign(d + p, d + N);
-        carry_at = base + p;
-        b0 = b1;
-    }
-    if (!have_header) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file"); return nullptr; }
-    if (!carry.empty()) { fail(NPORE_E_INVALID, "truncated BAM record"); return nullptr; }
-    bam_finish_index(b);
-    return hold.release();
-}
-}  // namespace
-
-// ONE-PASS open (mode 3): the BGZF block table and the BAM header, nothing else -- no record is looked at until
-// npore_bam_realign_sequential walks the stream.  Such a handle has no record index: npore_bam_select finds nothing.
-npore_bam *bam_open_header_only(const char *path, int threads, std::unique_ptr<PreadFile> file)
-{
-    std::unique_ptr<npore_bam> hold(new npore_bam());
-    npore_bam *b = hold.get();
-    b->streamed = true;
-    b->file = std::move(file);
-    uint64_t total = 0;
-    if (!bgzf_scan(*b->file, b->blocks, total)) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BGZF file"); return nullptr; }
-    b->data_size = (size_t)total;
-    RawBuf head;
-    for (size_t b1 = std::min<size_t>(b->blocks.size(), 16);; b1 = std::min(b->blocks.size(), b1 * 4)) {
-        if (b1 == 0) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file"); return nullptr; }
-        const size_t n = (size_t)(b->blocks[b1 - 1].out_off + b->blocks[b1 - 1].out_len);
-        if (!head.ensure(n + 8) || !bgzf_inflate_range(*b->file, b->blocks, 0, b1, reinterpret_cast<uint8_t *>(head.p), threads)) {
-            fail(NPORE_E_INVALID, std::string("'") + path + "': corrupt BGZF block");
-            return nullptr;
-        }
-        size_t hdr_end = 0;
-        const int rc = bam_parse_header(b, reinterpret_cast<const uint8_t *>(head.p), n, &hdr_end);
-        if (rc == 1) break;
-        if (rc == 0 || b1 == b->blocks.size()) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file"); return nullptr; }
-    }
-    bam_finish_index(b);                                 // (empty per-reference lists)
-    // which contigs have reads (get_bam_regions' default keeps only those, src/util.py:16-93 with bam.count() > 0): from
-    // the file's .bai when there is one (a reference with bins or linear-index entries has records) -- otherwise unknown
-    // without a pass over the records: every contig is assumed to have some
-    b->ref_has_reads.assign(b->ref_names.size(), 1);
-    {
-        const std::string p0 = std::string(path) + ".bai";
-        std::string p1 = path;
-        const size_t dot = p1.rfind('.');
-        if (dot != std::string::npos) p1 = p1.substr(0, dot) + ".bai";
-        std::vector<uint64_t> offs;
-        std::vector<uint8_t> has;
-        for (const std::string &cand : {p0, p1})
-            if (bai_linear_offsets(cand.c_str(), offs, &has) && has.size() == b->ref_names.size()) { b->ref_has_reads = has; break; }
-    }
-    return hold.release();
-}
-
+// ---- BAM ingest / SAM emit (bam_reader.hpp) -----------------------------------------------------
 // mode 0: automatic (streamed when the file is BGZF and larger than NPORE_BAM_STREAM_MB, default 1024 MB), 1: whole file
 // resident, 2: streamed, 3: one-pass (header only; the reads through npore_bam_realign_sequential).  index_path (may be NULL): a record index saved by npore_bam_save_index for this very file --
 // a streamed handle then skips its indexing pass (one process of a node indexes, the others load).
 npore_bam *npore_bam_open_mode(const char *path, int threads, int mode, const char *index_path)
 try {
-    if (!path) { fail(NPORE_E_INVALID, "null path"); return nullptr; }
-    if (mode != 1) {
-        std::unique_ptr<PreadFile> pf(new PreadFile());
-        if (!pf->open(path)) { fail(NPORE_E_INVALID, std::string("BAM file '") + path + "' not found"); return nullptr; }
-        uint8_t magic[4] = {0, 0, 0, 0};
-        const bool gz = pf->size >= 28 && pf->read(0, magic, 4) && magic[0] == 31 && magic[1] == 139;
-        uint64_t limit_mb = 1024;
-        if (const char *e = std::getenv("NPORE_BAM_STREAM_MB")) limit_mb = (uint64_t)std::max(0ll, std::atoll(e));
-        if (gz && mode == 3) return bam_open_header_only(path, threads, std::move(pf));
-        if (mode == 3) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BGZF file (one-pass mode)"); return nullptr; }
-        if (gz && (mode == 2 || pf->size > limit_mb * 1048576ull)) return bam_open_streamed(path, threads, std::move(pf), index_path);
-        if (mode == 2) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BGZF file (streamed mode)"); return nullptr; }
-    }
-    std::unique_ptr<MappedFile> mfp(new MappedFile());
-    MappedFile &mf = *mfp;
-    if (!mf.open(path)) { fail(NPORE_E_INVALID, std::string("BAM file '") + path + "' not found"); return nullptr; }
-    const ByteSpan raw{mf.p, mf.n};
-    std::unique_ptr<npore_bam> hold(new npore_bam());
-    npore_bam *b = hold.get();
-    std::string err;
-    if (mf.n >= 12 && std::memcmp(mf.p, "BAM\1", 4) == 0) {
-        // an inflated BAM stream (npore_bam_dump_inflated: one rank of a node inflates, the others map its copy)
-        b->data = mf.p;
-        b->data_size = mf.n;
-        b->raw_map = std::move(mfp);
-    } else {
-        if (!bgzf_inflate(raw, threads, b->data_buf, b->data_size, err) || b->data_size < 12 || std::memcmp(b->data_buf.p, "BAM\1", 4) != 0) {
-            fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file" + (err.empty() ? "" : " (" + err + ")"));
-            return nullptr;
-        }
-        b->data = reinterpret_cast<const uint8_t *>(b->data_buf.p);
-    }
-    const uint8_t *d = b->data;
-    const size_t N = b->data_size;
-    size_t p = 0;
-    if (bam_parse_header(b, d, N, &p) != 1) { fail(NPORE_E_INVALID, "truncated BAM header"); return nullptr; }
-    // records: offsets (one hop per record), then validation + metadata on all cores, then the per-reference lists
-    std::vector<int64_t> offs;
-    while (p + 4 <= N) {
-        const int32_t bs = rdi32(&d[p]);
-        if (bs < 32 || p + 4 + (size_t)bs > N) { fail(NPORE_E_INVALID, "truncated BAM record"); return nullptr; }
-        offs.push_back((int64_t)p);
-        p += 4 + (size_t)bs;
-    }
-    if (!bam_index_records(b, d, offs, 0, threads)) { fail(NPORE_E_INVALID, "corrupt BAM record"); return nullptr; }
-    bam_finish_index(b);
-    return hold.release();
+    return bam_open(path, threads, mode, index_path);
 }
 NPORE_CATCH_PTR
 npore_bam *npore_bam_open(const char *path, int threads) { return npore_bam_open_mode(path, threads, 0, nullptr); }
@@ -1761,32 +1513,7 @@ int npore_bam_is_streamed(const npore_bam *b) { return b && b->streamed ? 1 : 0;
 // at all, for npore_bam_open_mode(..., index_path) in the other processes of a node.
 int npore_bam_save_index(const npore_bam *b, const char *path)
 try {
-    if (!b || !path) return fail(NPORE_E_INVALID, "null argument");
-    // the header as a BAM stream prefix, so that the loader parses it with the same code
-    std::string hdr("BAM\1", 4);
-    auto put32 = [&](int32_t v) { hdr.append(reinterpret_cast<const char *>(&v), 4); };
-    put32((int32_t)b->text.size());
-    hdr += b->text;
-    put32((int32_t)b->ref_names.size());
-    for (size_t k = 0; k < b->ref_names.size(); k++) {
-        put32((int32_t)b->ref_names[k].size() + 1);
-        hdr.append(b->ref_names[k].c_str(), b->ref_names[k].size() + 1);
-        put32((int32_t)b->ref_lens[k]);
-    }
-    const std::string tmp = std::string(path) + ".tmp" + std::to_string((long long)::getpid());
-    FILE *fh = std::fopen(tmp.c_str(), "wb");
-    if (!fh) return fail(NPORE_E_INVALID, "cannot create '" + tmp + "'");
-    const uint64_t n_rec = b->rec_off.size(), hdr_len = hdr.size(), tot = b->data_size;
-    bool ok = std::fwrite("NPOREIX1", 1, 8, fh) == 8 && std::fwrite(&n_rec, 8, 1, fh) == 1 && std::fwrite(&hdr_len, 8, 1, fh) == 1 &&
-              std::fwrite(&tot, 8, 1, fh) == 1 && std::fwrite(hdr.data(), 1, hdr.size(), fh) == hdr.size();
-    auto put = [&](const void *p, size_t bytes) { if (ok && bytes) ok = std::fwrite(p, 1, bytes, fh) == bytes; };
-    put(b->rec_off.data(), n_rec * 8); put(b->m_ref.data(), n_rec * 4); put(b->m_pos.data(), n_rec * 4);
-    put(b->m_span.data(), n_rec * 4); put(b->m_flag.data(), n_rec * 2);
-    if (std::fclose(fh) != 0 || !ok || std::rename(tmp.c_str(), path) != 0) {
-        std::remove(tmp.c_str());
-        return fail(NPORE_E_INVALID, std::string("cannot write '") + path + "'");
-    }
-    return NPORE_OK;
+    return bam_save_index(b, path);
 }
 NPORE_CATCH_INT
 void npore_bam_close(npore_bam *b) { delete b; }
@@ -1795,17 +1522,7 @@ int64_t npore_bam_inflated_size(const npore_bam *b) { return b ? (int64_t)b->dat
 
 int npore_bam_dump_inflated(const npore_bam *b, const char *path)
 try {
-    if (!b || !path) return fail(NPORE_E_INVALID, "null argument");
-    if (b->streamed) return fail(NPORE_E_UNSUPPORTED, "a streamed BAM handle holds no inflated stream (share its index: npore_bam_save_index)");
-    const std::string tmp = std::string(path) + ".tmp" + std::to_string((long long)::getpid());
-    FILE *fh = std::fopen(tmp.c_str(), "wb");
-    if (!fh) return fail(NPORE_E_INVALID, "cannot create '" + tmp + "'");
-    const bool ok = std::fwrite(b->data, 1, b->data_size, fh) == b->data_size;
-    if (std::fclose(fh) != 0 || !ok || std::rename(tmp.c_str(), path) != 0) {       // complete, or not there at all
-        std::remove(tmp.c_str());
-        return fail(NPORE_E_INVALID, std::string("cannot write '") + path + "'");
-    }
-    return NPORE_OK;
+    return bam_dump_inflated(b, path);
 }
 NPORE_CATCH_INT
 int64_t npore_bam_n_records(const npore_bam *b) { return b ? (int64_t)b->rec_off.size() : 0; }
@@ -1817,30 +1534,7 @@ int npore_bam_ref_has_reads(const npore_bam *b, int i) { return (b && i >= 0 && 
 int64_t npore_bam_select(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
                          int64_t max_reads, int64_t *out_idx, int64_t cap)
 {
-    if (!b || (n_regions > 0 && (!ref_id || !start || !stop)) || (cap > 0 && !out_idx)) return fail(NPORE_E_INVALID, "null argument");
-    int64_t kept = 0;
-    for (int g = 0; g < n_regions; g++) {
-        if (ref_id[g] < 0 || ref_id[g] >= (int32_t)b->by_ref.size()) continue;
-        const std::vector<int64_t> &recs = b->by_ref[(size_t)ref_id[g]];     // file order
-        size_t first = 0;
-        if (b->ref_sorted[(size_t)ref_id[g]]) {
-            // coordinate-sorted (the usual case): skip everything that ends before the region can start
-            const int64_t lo = start[g] - b->ref_max_len[(size_t)ref_id[g]];
-            first = (size_t)(std::lower_bound(recs.begin(), recs.end(), lo,
-                                              [&](int64_t i, int64_t v) { return (int64_t)b->m_pos[(size_t)i] < v; }) - recs.begin());
-        }
-        for (size_t q = first; q < recs.size(); q++) {
-            const int64_t i = recs[q];
-            const int64_t pos = b->m_pos[(size_t)i], rl = b->m_span[(size_t)i];
-            if (b->ref_sorted[(size_t)ref_id[g]] && pos >= stop[g]) break;
-            if (!(pos < stop[g] && pos + rl > start[g])) continue;                 // overlaps [start, stop)
-            if (max_reads > 0 && kept >= max_reads) return kept;                   // src/bam.pyx:29-30
-            if (b->m_flag[(size_t)i] & (0x100 | 0x800 | 0x4)) continue;           // secondary / supplementary / unmapped, :31-32
-            if (kept < cap) out_idx[kept] = i;
-            kept++;
-        }
-    }
-    return kept;
+    return bam_select(b, n_regions, ref_id, start, stop, max_reads, out_idx, cap);
 }
 
 npore_fasta *npore_fasta_open(const char *path)
@@ -1862,48 +1556,6 @@ const char *npore_fasta_name(const npore_fasta *f, int i) { return (f && i >= 0 
 const char *npore_fasta_seq(const npore_fasta *f, int i) { return (f && i >= 0 && i < (int)f->names.size()) ? f->seq((size_t)i) : nullptr; }
 int64_t npore_fasta_len(const npore_fasta *f, int i) { return (f && i >= 0 && i < (int)f->names.size()) ? f->len((size_t)i) : -1; }
 
-namespace {
-bool pack_args_ok(const npore_bam *b, const int64_t *idx, int64_t n)
-{
-    if (!b || n < 0 || (n > 0 && !idx)) return false;
-    for (int64_t k = 0; k < n; k++)
-        if (idx[k] < 0 || idx[k] >= (int64_t)b->rec_off.size()) return false;
-    return true;
-}
-}  // namespace
-
-namespace {
-int fetch_records(const npore_bam *b, const int64_t *idx, int64_t n, int threads, RecFetch &rf)
-{
-    std::string err;
-    if (!bam_fetch(*b, idx, n, threads, rf, err)) return fail(NPORE_E_INVALID, "BAM records: " + err);
-    return NPORE_OK;
-}
-void pack_sizes_of(const RecFetch &rf, int64_t n, int64_t *ref_off, int64_t *seq_off, int64_t *cig_off, int threads = 0)
-{
-    // per read (a 10 kb read has thousands of CIGAR operations: all cores), then the prefix sums
-    ref_off[0] = seq_off[0] = cig_off[0] = 0;
-    const int64_t per = 64;
-    parallel_for((n + per - 1) / per, threads, [&](int64_t t) {
-        for (int64_t k = t * per; k < std::min(n, (t + 1) * per); k++) {
-            const RecView r = rec_of(rf, k);
-            int64_t lead, trail, ops = 0, rl = 0;
-            rec_clips(r, lead, trail);
-            const int nc = r.n_cigar();
-            for (int c = 0; c < nc; c++) {
-                const uint32_t w = r.cig(c), op = w & 15u, len = w >> 4;
-                if (op != 4 && op != 5) ops += len;
-                if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += len;      // (rec_ref_len: M D N = X)
-            }
-            ref_off[k + 1] = rl;
-            seq_off[k + 1] = std::max<int64_t>(0, (int64_t)r.l_seq() - lead - trail);
-            cig_off[k + 1] = ops;
-        }
-    });
-    for (int64_t k = 0; k < n; k++) { ref_off[k + 1] += ref_off[k]; seq_off[k + 1] += seq_off[k]; cig_off[k + 1] += cig_off[k]; }
-}
-}  // namespace
-
 int npore_bam_pack_sizes(const npore_bam *b, const int64_t *idx, int64_t n, int64_t *ref_off, int64_t *seq_off, int64_t *cig_off)
 try {
     if (!pack_args_ok(b, idx, n) || !ref_off || !seq_off || !cig_off) return fail(NPORE_E_INVALID, "bad argument");
@@ -1914,11 +1566,6 @@ try {
 }
 NPORE_CATCH_INT
 
-namespace {
-int pack_records(const npore_bam *b, const RecFetch &rf, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n,
-                 uint8_t *refs, const int64_t *ref_off, uint8_t *seqs, const int64_t *seq_off, char *cigs,
-                 const int64_t *cig_off, int threads, bool for_upload = false);
-}
 int npore_bam_pack(const npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
                    uint8_t *refs, const int64_t *ref_off, uint8_t *seqs, const int64_t *seq_off, char *cigs,
                    const int64_t *cig_off, int threads)
@@ -1931,160 +1578,6 @@ try {
     return pack_records(b, rf, fa, fasta_of_ref, n, refs, ref_off, seqs, seq_off, cigs, cig_off, threads);
 }
 NPORE_CATCH_INT
-
-namespace {
-int pack_records(const npore_bam *b, const RecFetch &rf, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n,
-                 uint8_t *refs, const int64_t *ref_off, uint8_t *seqs, const int64_t *seq_off, char *cigs,
-                 const int64_t *cig_off, int threads, bool for_upload)
-{
-    std::atomic<int> bad{0};
-    parallel_for(n, threads, [&](int64_t k) {
-        const RecView r = rec_of(rf, k);
-        const int32_t rid = r.ref_id();
-        const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
-        if (fi < 0 || fi >= (int)fa->names.size()) { bad++; return; }
-        // reference bases: FASTA slice [pos, pos + reference_length), what pysam rebuilds from MD (src/bam.pyx:45)
-        const char *ctg = fa->seq((size_t)fi);
-        const int64_t ctg_len = fa->len((size_t)fi);
-        const int64_t rl = ref_off[k + 1] - ref_off[k], pos = r.pos();
-        uint8_t *ro = refs + ref_off[k];
-        {
-            const int64_t q0 = std::min(rl, std::max<int64_t>(0, -pos)), q1 = std::max(q0, std::min(rl, ctg_len - pos));
-            std::memset(ro, 0, (size_t)q0);
-            base_codes(ctg + pos + q0, ro + q0, q1 - q0);
-            std::memset(ro + q1, 0, (size_t)(rl - q1));
-        }
-        // query bases without the soft clips (src/bam.pyx:42)
-        int64_t lead, trail;
-        rec_clips(r, lead, trail);
-        uint8_t *so = seqs + seq_off[k];
-        const int64_t sl = seq_off[k + 1] - seq_off[k];
-        nibble_codes(r.seq(), lead, so, sl);
-        // expanded CIGAR without S and H (src/bam.pyx:59)
-        char *co = cigs + cig_off[k];
-        const int nc = r.n_cigar();
-        for (int c = 0; c < nc; c++) {
-            const uint32_t w = r.cig(c), op = w & 15u, len = w >> 4;
-            if (op == 4 || op == 5) continue;
-            const char ch = op < 10 ? CIGOPS[op] : '?';
-            if (len <= 8) { for (uint32_t q = 0; q < len; q++) co[q] = ch; }      // (most runs are a few ops long)
-            else std::memset(co, ch, len);
-            co += len;
-        }
-        if (for_upload) {       // page-locked staging about to cross PCIe: out of this core's cache first (hostio.hpp)
-            cache_writeback(ro, (size_t)rl);
-            cache_writeback(so, (size_t)sl);
-            cache_writeback(cigs + cig_off[k], (size_t)(cig_off[k + 1] - cig_off[k]));
-        }
-    });
-    return bad ? fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA") : NPORE_OK;
-}
-
-#if defined(__x86_64__)
-// "=ACMGRSVTWYHKDBN"[nibble] for 16 packed bytes at a time (high nibble first); returns the packed bytes done (a multiple of 16)
-__attribute__((target("ssse3"))) static int64_t nibbles_to_text_ssse3(const uint8_t *src, char *dst, int64_t n_bytes)
-{
-    const __m128i lut = _mm_loadu_si128(reinterpret_cast<const __m128i *>(SEQ16));
-    const __m128i low = _mm_set1_epi8(0x0F);
-    int64_t j = 0;
-    for (; j + 16 <= n_bytes; j += 16) {
-        const __m128i v = _mm_loadu_si128(reinterpret_cast<const __m128i *>(src + j));
-        const __m128i hi = _mm_shuffle_epi8(lut, _mm_and_si128(_mm_srli_epi16(v, 4), low));
-        const __m128i lo = _mm_shuffle_epi8(lut, _mm_and_si128(v, low));
-        _mm_storeu_si128(reinterpret_cast<__m128i *>(dst + 2 * j), _mm_unpacklo_epi8(hi, lo));
-        _mm_storeu_si128(reinterpret_cast<__m128i *>(dst + 2 * j + 16), _mm_unpackhi_epi8(hi, lo));
-    }
-    return j;
-}
-#endif
-
-int format_sam_into(const npore_bam *b, const RecFetch &rf, int64_t n, const char *finals, const int64_t *final_off,
-                    const int64_t *final_len, const int32_t *status, int threads, RawBuf &out, int64_t *sam_len)
-{
-    if (!b || n < 0 || !sam_len || (n > 0 && (!finals || !final_off || !final_len || !status)))
-        return fail(NPORE_E_INVALID, "bad argument");
-    // pass 1: line sizes; pass 2: fill (both parallel over reads)
-    std::vector<int64_t> off((size_t)n + 1, 0);
-    // decimal text of v at dst (dst == nullptr: only the length), no terminator
-    auto put_int = [](char *dst, long long v) -> int {
-        char tmp[24];
-        int nd = 0;
-        unsigned long long u = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
-        do { tmp[nd++] = (char)('0' + u % 10); u /= 10; } while (u);
-        const int neg = v < 0;
-        if (dst) {
-            if (neg) *dst++ = '-';
-            for (int q = 0; q < nd; q++) dst[q] = tmp[nd - 1 - q];
-        }
-        return nd + neg;
-    };
-#if defined(__x86_64__)
-    static const bool have_ssse3 = __builtin_cpu_supports("ssse3");
-#endif
-    static const struct PairTab {      // two bases of the 4-bit packed sequence per lookup
-        uint16_t pair[256];
-        PairTab() { for (int v = 0; v < 256; v++) pair[v] = (uint16_t)((uint8_t)SEQ16[v >> 4] | ((uint8_t)SEQ16[v & 15] << 8)); }
-    } seqtab;
-    auto line = [&](int64_t k, char *dst) -> int64_t {    // returns the length; writes when dst != nullptr
-        if (status[k] & NPORE_ST_BAD_INPUT) return 0;    // refused reads are not written
-        const RecView r = rec_of(rf, k);
-        int64_t lead, trail;
-        rec_clips(r, lead, trail);
-        const int64_t sl = std::max<int64_t>(0, (int64_t)r.l_seq() - lead - trail);
-        const int32_t rid = r.ref_id();
-        const std::string &rn = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? b->ref_names[(size_t)rid] : std::string("*");
-        const bool noq = r.l_seq() == 0 || r.qual()[0] == 0xFF;
-        const size_t nl = std::strlen(r.name());
-        const long long flag = r.flag(), pos1 = (long long)r.pos() + 1, mapq = r.mapq(), hp = (long long)rec_hp(r),
-                        reflen = (long long)rec_ref_len(r);
-        if (!dst)       // name \t flag \t rname \t pos \t mapq \t cigar \t * \t 0 \t tlen \t seq \t qual \t HP:i:n \n
-            return (int64_t)nl + 1 + put_int(nullptr, flag) + 1 + (int64_t)rn.size() + 1 + put_int(nullptr, pos1) + 1 +
-                   put_int(nullptr, mapq) + 1 + final_len[k] + 5 + put_int(nullptr, reflen) + 1 + sl + 1 + (noq ? 1 : sl) + 6 +
-                   put_int(nullptr, hp) + 1;
-        char *o = dst;
-        std::memcpy(o, r.name(), nl); o += nl;
-        *o++ = '\t'; o += put_int(o, flag); *o++ = '\t';
-        std::memcpy(o, rn.data(), rn.size()); o += rn.size();
-        *o++ = '\t'; o += put_int(o, pos1); *o++ = '\t'; o += put_int(o, mapq); *o++ = '\t';
-        std::memcpy(o, finals + final_off[k], (size_t)final_len[k]); o += final_len[k];
-        std::memcpy(o, "\t*\t0\t", 5); o += 5;
-        o += put_int(o, reflen); *o++ = '\t';
-        {
-            const uint8_t *sq = r.seq();
-            int64_t q = 0, t = lead;
-            if (q < sl && (t & 1)) { o[q++] = SEQ16[sq[t >> 1] & 15]; t++; }
-            const uint8_t *src = sq + (t >> 1);
-            const int64_t pairs = (sl - q) >> 1;
-            char *po = o + q;
-            int64_t j = 0;
-#if defined(__x86_64__)
-            if (have_ssse3) j = nibbles_to_text_ssse3(src, po, pairs);          // 16 packed bytes -> 32 letters per step
-#endif
-            for (; j < pairs; j++) { const uint16_t v = seqtab.pair[src[j]]; std::memcpy(po + 2 * j, &v, 2); }
-            q += 2 * pairs;
-            if (q < sl) { o[q] = SEQ16[src[pairs] >> 4]; q++; }
-            o += sl;
-        }
-        *o++ = '\t';
-        if (noq) *o++ = '*';
-        else {
-            const uint8_t *__restrict ql = r.qual() + lead;
-            char *__restrict qo = o;
-            for (int64_t q = 0; q < sl; q++) qo[q] = (char)(33 + ql[q]);
-            o += sl;
-        }
-        std::memcpy(o, "\tHP:i:", 6); o += 6;
-        o += put_int(o, hp); *o++ = '\n';
-        return (int64_t)(o - dst);
-    };
-    parallel_for(n, threads, [&](int64_t k) { off[(size_t)k + 1] = line(k, nullptr); });
-    for (int64_t k = 0; k < n; k++) off[(size_t)k + 1] += off[(size_t)k];
-    if (!out.ensure((size_t)off[(size_t)n] + 1)) return fail(NPORE_E_NOMEM, "SAM text buffer");
-    parallel_for(n, threads, [&](int64_t k) { if (off[(size_t)k + 1] > off[(size_t)k]) line(k, out.p + off[(size_t)k]); });
-    *sam_len = off[(size_t)n];
-    return NPORE_OK;
-}
-}  // namespace
 
 int npore_bam_format_sam(npore_bam *b, const int64_t *idx, int64_t n, const char *finals, const int64_t *final_off,
                          const int64_t *final_len, const int32_t *status, int threads, const char **sam, int64_t *sam_len)
@@ -2389,17 +1882,19 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             cmp = TextCompact{s.d_ctext.as<uint8_t>(), s.d_cursor.as<unsigned long long>(), slots,
                               reinterpret_cast<int64_t *>(s.coff_pin.p), s.ctext_pin.p, bound};
             s.ctext_copied = bound;
-            ctx->pending_compact = &cmp;
         }
         char *const out_host = glue ? s.ctext_pin.p : s.alns.p;      // (with the compaction nothing is copied there)
-        if (dpack)
-            s.rc = align_batch_raw(ctx, m, reinterpret_cast<uint8_t *>(s.raw.p), s.rawo.data(), s.ro.data(), s.so.data(), s.co.data(),
-                                   indel_start, indel_extend, max_b_rows, r, out_host, s.oo.data(),
-                                   reinterpret_cast<int64_t *>(s.olen_pin.p), reinterpret_cast<int32_t *>(s.st_pin.p));
-        else
-            s.rc = align_batch_host(ctx, m, reinterpret_cast<uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<uint8_t *>(s.seqs.p),
-                                    s.so.data(), s.cigs.p, s.co.data(), indel_start, indel_extend, max_b_rows, r, out_host,
-                                    s.oo.data(), reinterpret_cast<int64_t *>(s.olen_pin.p), reinterpret_cast<int32_t *>(s.st_pin.p), false, glue);
+        AlignArgs a = host_batch_args(m, s.ro.data(), s.so.data(), s.co.data(), indel_start, indel_extend, max_b_rows, r, out_host,
+                                      s.oo.data(), reinterpret_cast<int64_t *>(s.olen_pin.p), reinterpret_cast<int32_t *>(s.st_pin.p));
+        if (dpack) {
+            a.h_raw = reinterpret_cast<uint8_t *>(s.raw.p); a.h_raw_off = s.rawo.data();
+            a.d_ctg = ctx->d_ctg.as<CtgEntry>(); a.n_ctg = ctx->n_ctg;
+        } else {
+            a.h_refs = reinterpret_cast<uint8_t *>(s.refs.p); a.h_seqs = reinterpret_cast<uint8_t *>(s.seqs.p); a.h_cigs = s.cigs.p;
+        }
+        a.final_text = glue;
+        if (glue) a.compact = &cmp;                                  // (read while the groups are enqueued, not behind the call)
+        s.rc = align_batch(ctx, a, false);
         if (s.rc) { rc = s.rc; err = npore_last_error(); s.err = err; break; }
         if (hipEventRecord(s.done, ctx->s_post) != hipSuccess) { rc = NPORE_E_HIP; err = "hipEventRecord"; s.rc = rc; s.err = err; break; }
         mark("enqueued", k);
@@ -2425,63 +1920,13 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
     b->file_ms[7] = ctx->totals[3] + ctx->totals[4] - ctx->file_mark[1];                     // H2D + D2H): SUMS over groups that run beside each other
     return rc == NPORE_OK ? NPORE_OK : fail(rc, err);
 }
-
-// the variable-length parts the record accessors will walk lie inside the record
-bool record_is_sound(const uint8_t *q)
-{
-    const int32_t bs = rdi32(q);
-    const uint8_t *f = q + 4;
-    const int64_t l_rn = f[8], n_cig = rd16(f + 12), l_seq = rdi32(f + 16);
-    return !(l_rn < 1 || l_seq < 0 || 32 + l_rn + 4 * n_cig + (l_seq + 1) / 2 + l_seq > bs || f[32 + l_rn - 1] != 0);
-}
 }  // namespace
 
 extern "C" {
 
 int npore_bam_set_share(npore_bam *b, int rank, int world, const char *bai_path)
 try {
-    if (!b || world < 1 || rank < 0 || rank >= world) return fail(NPORE_E_INVALID, "bad argument");
-    if (!b->file || b->blocks.empty()) return fail(NPORE_E_INVALID, "a share needs a handle opened on a BGZF file (modes 2 and 3)");
-    b->has_share = false;
-    b->share_begin = 0;
-    b->share_end = UINT64_MAX;
-    b->share_block = 0;
-    if (world == 1) return NPORE_OK;
-    std::vector<uint64_t> cuts;
-    if (!bai_path || !bai_linear_offsets(bai_path, cuts) || cuts.empty())
-        return fail(NPORE_E_UNSUPPORTED, "no usable .bai linear index: the record stream cannot be dealt without a pass over it");
-    // the first record of the stretch whose compressed offset lies at or behind k / world of the file
-    const uint64_t c0 = b->blocks.front().in_off, c1 = b->blocks.back().in_off + b->blocks.back().in_len;
-    auto cut_of = [&](int k) -> uint64_t {
-        if (k <= 0) return 0;
-        if (k >= world) return UINT64_MAX;
-        const uint64_t target = c0 + (uint64_t)((long double)(c1 - c0) * k / world);
-        auto it = std::lower_bound(cuts.begin(), cuts.end(), target << 16);
-        return it == cuts.end() ? UINT64_MAX : *it;
-    };
-    // virtual offset -> block of the table and offset in the inflated stream (false: the index is not this file's)
-    auto locate = [&](uint64_t v, size_t &blk, uint64_t &abs) -> bool {
-        const uint64_t coff = v >> 16, uoff = v & 0xFFFFu;
-        // a block's payload begins a gzip header's length behind the block: the block that starts at `coff` is the first
-        // one whose payload offset lies behind it
-        size_t lo = 0, hi = b->blocks.size();
-        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (b->blocks[mid].in_off > coff) hi = mid; else lo = mid + 1; }
-        if (lo == b->blocks.size() || b->blocks[lo].in_off - coff > 4096 || uoff >= b->blocks[lo].out_len) return false;
-        blk = lo;
-        abs = b->blocks[lo].out_off + uoff;
-        return true;
-    };
-    const uint64_t v0 = cut_of(rank), v1 = cut_of(rank + 1);
-    if (v0 == UINT64_MAX) { b->share_begin = b->share_end = UINT64_MAX; }       // nothing left for this rank
-    else if (v0 != 0) {
-        if (!locate(v0, b->share_block, b->share_begin)) return fail(NPORE_E_UNSUPPORTED, "the .bai index does not belong to this BAM file");
-    }
-    if (v1 != UINT64_MAX && v0 != UINT64_MAX) {
-        size_t blk;
-        if (!locate(v1, blk, b->share_end)) return fail(NPORE_E_UNSUPPORTED, "the .bai index does not belong to this BAM file");
-    }
-    b->has_share = true;
-    return NPORE_OK;
+    return bam_set_share(b, rank, world, bai_path);
 }
 NPORE_CATCH_INT
 
@@ -2501,9 +1946,9 @@ int npore_bam_realign_file(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, 
 try {
     if (!ctx || !b || !fa || !fasta_of_ref || !out_path || (n > 0 && (!idx || !status)) || batch_reads < 1) return fail(NPORE_E_INVALID, "bad argument");
     if (!pack_args_ok(b, idx, n)) return fail(NPORE_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(ctx->device));
     FILE *fh = std::fopen(out_path, "ab");
     if (!fh) return fail(NPORE_E_INVALID, std::string("cannot open '") + out_path + "' for appending");
-    HIP_TRY(hipSetDevice(ctx->device));
     const int64_t nb = (n + batch_reads - 1) / batch_reads;
     int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, fh, false,
                            [&](int64_t k, npore_batch_slot &s) -> int64_t {
@@ -2526,183 +1971,13 @@ try {
     if (!ctx || !b || !fa || !fasta_of_ref || !out_path || !counts || batch_reads < 1 || n_regions < 0 ||
         (n_regions > 0 && (!ref_id || !start || !stop)) || (bad_cap > 0 && (!bad_ord || !bad_status)))
         return fail(NPORE_E_INVALID, "bad argument");
-    if (!b->file || b->blocks.empty()) return fail(NPORE_E_INVALID, "one-pass ingest needs a handle opened on a BGZF file (modes 2 and 3)");
-    for (int g = 0; g < n_regions; g++)
-        if (ref_id[g] < 0 || ref_id[g] >= (int32_t)b->ref_names.size() || (g > 0 && ref_id[g] <= ref_id[g - 1]))
-            return fail(NPORE_E_UNSUPPORTED, "one-pass ingest takes at most one region per contig, in the order of the BAM header");
+    if (int rc = one_pass_args_check(b, n_regions, ref_id, max_reads)) return rc;
     counts[0] = counts[1] = counts[2] = 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    BamRecordWalker walker(b, n_regions, ref_id, start, stop, max_reads, threads);
     FILE *fh = std::fopen(out_path, "ab");
     if (!fh) return fail(NPORE_E_INVALID, std::string("cannot open '") + out_path + "' for appending");
-    HIP_TRY(hipSetDevice(ctx->device));
-    // the reader: the stream in windows of consecutive BGZF blocks, each inflated ONCE on all cores; a record that
-    // straddles two windows is carried to the front of the next one, so every record lies in one window buffer, which
-    // lives as long as a batch points into it
-    size_t win_blocks = 1024;                // <= 64 MB of inflated stream per window
-    if (const char *e = std::getenv("NPORE_BAM_WINDOW_BLOCKS")) win_blocks = (size_t)std::max(1, std::atoi(e));
-    std::shared_ptr<RawBuf> win;
-    const uint8_t *wd = nullptr;             // the window's first byte (the carried tail sits in front of the inflated blocks)
-    size_t next_block = 0, N = 0, p = 0;
-    bool have_header = false, done = n_regions == 0;
-    // several processes on one file (npore_bam_set_share): this one walks the records that START in [share_begin,
-    // share_end) of the inflated stream -- a stretch that begins at a record (a virtual offset of the .bai linear index);
-    // the header was read when the handle was opened
-    uint64_t abs0 = 0;                       // offset of the window's first byte in the inflated stream
-    bool seek_share = false;
-    if (b->has_share) {
-        if (max_reads > 0) { std::fclose(fh); return fail(NPORE_E_UNSUPPORTED, "one-pass ingest: max_reads needs one process (the ranks cannot know how many reads the others keep)"); }
-        if (b->share_begin == UINT64_MAX) done = true;
-        else if (b->share_begin > 0) { next_block = b->share_block; have_header = true; seek_share = true; }
-    }
-    int g = 0;
-    int64_t kept = 0, n_bad = 0, ordinal0 = 0;
-    int32_t last_rid = -1;
-    // the next window is inflated (on all cores) while the records of the current one are walked and packed: into its
-    // buffer behind HEAD bytes of room, where the carried tail of the current window is put once the walk has reached it
-    constexpr size_t HEAD = 4u << 20;
-    struct Pending { std::shared_ptr<RawBuf> buf; size_t bytes = 0, b0 = 0, b1 = 0; bool ok = false; };
-    // The inflater: ONE thread that takes the windows in file order, each on all cores (bgzf_inflate_range), and keeps up to
-    // `depth` of them ready -- the inflation then runs whenever CPUs are free instead of one window ahead of the walk (rounds
-    // 4 - 5a: the acquisitions of consecutive batches took 12 ... 72 ms, the long ones waiting for a window that the SAM text
-    // and packing threads had slowed down, with 12 of the lease's 16 CPUs busy on average).
-    // (a process that walks only its stretch of the file stops taking windows where the stretch ends; the inflater is at most
-    // `depth` windows further on then -- the last record of a stretch may run on into any number of blocks, so it is not
-    // cut off by block count)
-    const size_t pf_end = b->blocks.size();
-    int pf_depth = 3;
-    if (const char *e = std::getenv("NPORE_BAM_WINDOWS_AHEAD")) pf_depth = std::max(1, std::atoi(e));
-    int inflate_threads = threads;                     // (experiments: how many of the lease's CPUs the inflater may take at once)
-    if (const char *e = std::getenv("NPORE_INFLATE_THREADS")) inflate_threads = std::max(1, std::atoi(e));
-    std::mutex pf_m;
-    std::condition_variable pf_cv;
-    std::deque<Pending> pf_ready;
-    bool pf_stop = false, pf_done = false, pf_started = false;
-    std::thread pf_thread;
-    auto pf_start = [&](size_t first_block) {
-        pf_started = true;
-        pf_thread = std::thread([&, first_block] {
-            size_t b0 = first_block;
-            for (;;) {
-                {
-                    std::unique_lock<std::mutex> lk(pf_m);
-                    pf_cv.wait(lk, [&] { return pf_stop || (int)pf_ready.size() < pf_depth; });
-                    if (pf_stop || b0 >= pf_end) { pf_done = true; pf_cv.notify_all(); return; }
-                }
-                Pending pd;
-                pd.b0 = b0;
-                pd.b1 = std::min(pf_end, b0 + win_blocks);
-                const uint64_t w0 = b->blocks[b0].out_off, w1 = b->blocks[pd.b1 - 1].out_off + b->blocks[pd.b1 - 1].out_len;
-                pd.bytes = (size_t)(w1 - w0);
-                try {                                       // (no exception may leave a thread: the walk sees ok == false)
-                    pd.buf = std::make_shared<RawBuf>();
-                    pd.ok = pd.buf->ensure(HEAD + pd.bytes + 8) &&
-                            bgzf_inflate_range(*b->file, b->blocks, b0, pd.b1, reinterpret_cast<uint8_t *>(pd.buf->p) + HEAD, inflate_threads);
-                } catch (...) {
-                    pd.ok = false;
-                }
-                b0 = pd.b1;
-                {
-                    std::lock_guard<std::mutex> lk(pf_m);
-                    pf_ready.push_back(std::move(pd));
-                }
-                pf_cv.notify_all();
-            }
-        });
-    };
-    auto pf_finish = [&] {
-        if (!pf_started) return;
-        { std::lock_guard<std::mutex> lk(pf_m); pf_stop = true; }
-        pf_cv.notify_all();
-        if (pf_thread.joinable()) pf_thread.join();
-    };
-    struct PfGuard { decltype(pf_finish) &f; ~PfGuard() { f(); } } pf_guard{pf_finish};
-    // -1: failure (fail() called); 0: end of the stream; 1: a new window is in place
-    auto load_window = [&]() -> int {
-        const size_t c = (win && p < N) ? N - p : 0;             // carried tail of the current window
-        if (next_block >= pf_end) {
-            if (c || !have_header) { fail(NPORE_E_INVALID, have_header ? "truncated BAM record" : "not a BAM file"); return -1; }
-            return 0;
-        }
-        if (!pf_started) pf_start(next_block);
-        const uint64_t win_off = b->blocks[next_block].out_off;
-        Pending pd;
-        {
-            std::unique_lock<std::mutex> lk(pf_m);
-            pf_cv.wait(lk, [&] { return !pf_ready.empty() || pf_done; });
-            if (pf_ready.empty()) { fail(NPORE_E_INVALID, "BAM window reader ended early"); return -1; }
-            pd = std::move(pf_ready.front());
-            pf_ready.pop_front();
-        }
-        pf_cv.notify_all();
-        if (!pd.ok || pd.b0 != next_block) { fail(NPORE_E_INVALID, "corrupt BGZF block (or out of memory)"); return -1; }
-        std::shared_ptr<RawBuf> nw = pd.buf;
-        uint8_t *d0 = reinterpret_cast<uint8_t *>(nw->p) + HEAD;
-        if (c > HEAD) {                                          // a record longer than the room in front: copy once
-            auto big = std::make_shared<RawBuf>();
-            if (!big->ensure(c + pd.bytes + 8)) { fail(NPORE_E_NOMEM, "BAM window"); return -1; }
-            std::memcpy(big->p + c, d0, pd.bytes);
-            nw = big;
-            d0 = reinterpret_cast<uint8_t *>(nw->p) + c;
-        }
-        if (c) std::memcpy(d0 - c, wd + p, c);
-        win = nw;
-        wd = d0 - c;
-        abs0 = win_off - c;
-        N = c + pd.bytes;
-        p = 0;
-        if (seek_share) { p = (size_t)(b->share_begin - abs0); seek_share = false; }      // (the first window of a share that begins mid-file)
-        next_block = pd.b1;
-        return 1;
-    };
-    auto acquire = [&](int64_t, npore_batch_slot &s) -> int64_t {
-        s.rf.ptr.clear();
-        while ((int64_t)s.rf.ptr.size() < batch_reads && !done) {
-            const uint8_t *d = wd;
-            if (!have_header) {
-                npore_bam scratch;
-                size_t hdr_end = 0;
-                const int hrc = win ? bam_parse_header(&scratch, d, N, &hdr_end) : -1;
-                if (hrc == 0) return fail(NPORE_E_INVALID, "not a BAM file");
-                if (hrc < 0) {                                   // the header does not end in what is inflated so far
-                    p = 0;
-                    const int lw = load_window();
-                    if (lw < 0) return lw;
-                    if (lw == 0) return fail(NPORE_E_INVALID, "truncated BAM header");
-                    continue;
-                }
-                have_header = true;
-                p = hdr_end;
-                continue;
-            }
-            int32_t bs = 0;
-            if (p + 4 > N || (bs = rdi32(d + p)) < 32 || p + 4 + (size_t)bs > N) {
-                if (p + 4 <= N && bs < 32) return fail(NPORE_E_INVALID, "truncated BAM record");
-                const int lw = load_window();
-                if (lw < 0) return lw;
-                if (lw == 0) done = true;
-                continue;
-            }
-            if (abs0 + p >= b->share_end) { done = true; break; }                // the next process's stretch begins here
-            const uint8_t *q = d + p;
-            p += 4 + (size_t)bs;
-            if (!record_is_sound(q)) return fail(NPORE_E_INVALID, "corrupt BAM record");
-            const RecView rv = rec_view(q);
-            const int32_t rid = rv.ref_id();
-            if (rid < 0) continue;                               // unplaced
-            if (rid < last_rid) return fail(NPORE_E_UNSUPPORTED, "the BAM is not sorted by reference: one-pass ingest needs a coordinate-sorted file");
-            last_rid = rid;
-            while (g < n_regions && ref_id[g] < rid) g++;
-            if (g == n_regions) { done = true; break; }
-            if (ref_id[g] != rid) continue;
-            const int64_t pos = rv.pos(), rl = rec_ref_len(rv);
-            if (!(pos < stop[g] && pos + rl > start[g])) continue;               // overlaps [start, stop)
-            if (max_reads > 0 && kept >= max_reads) { done = true; break; }      // src/bam.pyx:29-30
-            if (rv.flag() & (0x100 | 0x800 | 0x4)) continue;                     // secondary / supplementary / unmapped, :31-32
-            s.rf.ptr.push_back(q);
-            if (s.keep.empty() || s.keep.back() != win) s.keep.push_back(win);
-            kept++;
-        }
-        return (int64_t)s.rf.ptr.size();
-    };
+    int64_t n_bad = 0, ordinal0 = 0;
     auto on_status = [&](int64_t, int64_t m, const int32_t *st) {
         for (int64_t i = 0; i < m; i++)
             if (st[i]) {
@@ -2712,8 +1987,8 @@ try {
             }
         ordinal0 += m;
     };
-    int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, fh, true, acquire, on_status);
-    pf_finish();                                                 // (windows inflated ahead of a stream that ended early)
+    int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, fh, true,
+                           [&](int64_t, npore_batch_slot &s) { return walker.next_batch(s.rf, s.keep, batch_reads); }, on_status);
     counts[0] = ordinal0;
     if (std::fclose(fh) != 0 && rc == NPORE_OK) rc = fail(NPORE_E_INVALID, "close failed");
     return rc;

@@ -3,7 +3,7 @@
 // realign_read (reference src/bam.pyx:51-61) hands align() three things per read: the reference bases under the
 // alignment (`get_reference_sequence`, :45 -- here: a slice of the FASTA contig), the query bases without the soft
 // clips (:42) and the expanded CIGAR without S and H (:59), bases as codes 'NACGT-' -> 0..5 (src/cig.pyx:212-229).
-// The host twin is pack_records (npore_api.cpp: base_codes / nibble_codes of hostio.hpp + the op loop); the file
+// The host twin is pack_records (bam_reader.hpp: base_codes / nibble_codes of hostio.hpp + the op loop); the file
 // pipeline used to run it on the host for every batch -- 18 us per 10 kb read and core, 40 KB per read across PCIe.
 // Here the pipeline uploads the HEAD of every record as it lies in the BAM stream (fixed fields, name, CIGAR words,
 // 4-bit bases: ~11 KB per 10 kb read; qualities and tags stay on the host) and the FASTA once per run; one workgroup per

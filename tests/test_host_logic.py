@@ -366,7 +366,7 @@ def test_realign_part_files_gloo_world2(tmp_path):
     assert not os.path.exists(prefix + ".part0.sam") and not os.path.exists(prefix + ".part1.sam")
 
 
-# ---- native host I/O (csrc/hostio.hpp) against the pure-Python restatement in npore_amd/bam.py ----
+# ---- native host I/O (csrc/hostio.hpp, csrc/bam_reader.hpp) against the pure-Python restatement in npore_amd/bam.py ----
 def _native_vs_python(bam_path, fasta_path, regions, max_reads=0, stream=None):
     import argparse
     from npore_amd import bam, cfg
@@ -792,13 +792,9 @@ def test_append_file_copy_file_range(tmp_path):
         assert sum(calls) == 100_004        # every byte went through the in-kernel copy
 
 
-def test_streamed_bam_equals_resident(tmp_path, monkeypatch):
-    """STREAMED ingest (npore_bam_open_mode 2: block table + 22 bytes per record, the records of a batch inflated from
-    the BGZF blocks they lie in) against the resident mode and the Python reader: a BAM of ~120 BGZF blocks indexed in
-    windows of 2 blocks (records straddle blocks and windows, the header straddles the first window), selection by
-    region, packed bases / CIGARs, SAM text, all through tiny scattered batches; the saved record index reopens the
-    file without a second pass; a file that is not BGZF is refused in that mode."""
-    from npore_amd import bam
+def _many_window_bam(tmp_path):
+    """900 records of 30 ... 9 000 bases on three contigs, sorted, in ~120 BGZF blocks; 2 500 read-less contigs more in the
+    header.  Returns (BAM path, FASTA path, names of the three contigs)."""
     rng = np.random.default_rng(12)
     contigs = {f"c{k}_{'x' * 40}": "".join(rng.choice(list("ACGT"), 60_000)) for k in range(3)}
     fa = tmp_path / "r.fa"
@@ -822,6 +818,17 @@ def test_streamed_bam_equals_resident(tmp_path, monkeypatch):
     # (+ 2 500 read-less contigs in the header: ~300 KB, so the header itself spans several windows)
     bam.write_bam(bp, [(n, len(s_)) for n, s_ in contigs.items()] + [(f"unplaced_scaffold_{k:05d}_{'y' * 30}", 1000 + k) for k in range(2500)],
                   recs, level=1)
+    return bp, fa, names
+
+
+def test_streamed_bam_equals_resident(tmp_path, monkeypatch):
+    """STREAMED ingest (npore_bam_open_mode 2: block table + 22 bytes per record, the records of a batch inflated from
+    the BGZF blocks they lie in) against the resident mode and the Python reader: a BAM of ~120 BGZF blocks indexed in
+    windows of 2 blocks (records straddle blocks and windows, the header straddles the first window), selection by
+    region, packed bases / CIGARs, SAM text, all through tiny scattered batches; the saved record index reopens the
+    file without a second pass; a file that is not BGZF is refused in that mode."""
+    from npore_amd import bam
+    bp, fa, names = _many_window_bam(tmp_path)
     monkeypatch.setenv("NPORE_BAM_WINDOW_BLOCKS", "2")
     regions = [(names[0], 0, 59_999), (names[2], 10_000, 30_000), (names[1], 0, 59_999)]
     n1 = _native_vs_python(bp, str(fa), regions, stream=True)
@@ -910,11 +917,8 @@ def test_fill_step_asm_is_generated_and_counter_clean(tmp_path):
     assert any(rule == "R3" for rule, _, _, _ in chk.findings(1, [ln for ln in G.gen_role(1)][:-1]))
 
 
-def test_bam_shares_begin_at_record_starts(tmp_path):
-    """npore_bam_set_share (several ranks, each one pass over its stretch of the file): the cut points come from the .bai
-    LINEAR index and are record starts; the stretches of the ranks tile the record stream; a .bai of another file, no
-    .bai, a handle that is not on a BGZF file: refused.  (Host logic only; the walk itself is a GPU test.)"""
-    import struct
+def _share_test_bam(tmp_path):
+    """400 records of 200 ... 900 bases on two contigs (300 + 100), sorted.  Returns (BAM path, records)."""
     recs, pos = [], 0
     rng = np.random.default_rng(3)
     for k in range(400):
@@ -926,6 +930,16 @@ def test_bam_shares_begin_at_record_starts(tmp_path):
             pos = 0
     path = str(tmp_path / "s.bam")
     bam.write_bam(path, [("a", 300_000), ("b", 300_000)], recs, level=1)
+    return path, recs
+
+
+def test_bam_shares_begin_at_record_starts(tmp_path):
+    """npore_bam_set_share (several ranks, each one pass over its stretch of the file): the cut points come from the .bai
+    LINEAR index and are record starts; the stretches of the ranks tile the record stream; a .bai of another file, no
+    .bai, a handle that is not on a BGZF file: refused.  (The cuts only; the walk over them: test_one_pass_walk_equals_indexed_selection,
+    and with the device behind it the GPU tests.)"""
+    import struct
+    path, recs = _share_test_bam(tmp_path)
     h = bam.NativeBam(path, one_pass=True, share=False)
     with pytest.raises(bam.OnePassUnsupported):
         h.set_share(0, 2)
@@ -977,6 +991,96 @@ def test_bam_shares_begin_at_record_starts(tmp_path):
         g.set_share(1, 2, bai=bai)                               # another file's index: its offsets are not block starts here
     g.close()
     h.close()
+
+
+def test_one_pass_walk_equals_indexed_selection(tmp_path, monkeypatch):
+    """The one-pass record walker (csrc/bam_reader.hpp BamRecordWalker over BamWindowSource: what npore_bam_realign_sequential
+    takes its batches from) keeps exactly the records npore_bam_select keeps on an indexed, resident handle of the same
+    file -- compared as offsets into the inflated stream, by tests/model/bam_walk.cpp, which is the reader built with plain
+    g++ (no GPU, no HIP header).  Windows of 1, 2 and the default number of BGZF blocks (records and the header straddle
+    windows), max_reads 0 and 17, and for 1, 2, 3, 7 and 16 ranks the kept lists of the ranks, one after the other, are
+    the whole file's.  A stream that ends inside a record, or inside the header, is an error in the one-pass walk too."""
+    import struct, zlib
+    from model import bam_walk
+    golden = os.path.join(GOLDEN, "data", "reads.bam")
+    g = bam.NativeBam(golden, stream=False)
+    golden_regions = [(k, 0, 1 << 40) for k in range(len(g.references))]
+    g.close()
+    big, _, _ = _many_window_bam(tmp_path)
+    shares, _ = _share_test_bam(tmp_path)
+    files = [(golden, bam.NativeBam.bai_path(golden), [golden_regions]),
+             (big, bam.write_bai(big), [[(0, 0, 59_999), (1, 10_000, 30_000), (2, 0, 59_999)], [(1, 0, 59_999)]]),
+             (shares, bam.write_bai(shares), [[(0, 0, 300_000), (1, 0, 300_000)], [(0, 50_000, 120_000), (1, 1_000, 90_000)]])]
+    n_kept = []
+    for win in ("1", "2", None):
+        if win is None:
+            monkeypatch.delenv("NPORE_BAM_WINDOW_BLOCKS", raising=False)
+        else:
+            monkeypatch.setenv("NPORE_BAM_WINDOW_BLOCKS", win)
+        for path, bai, region_lists in files:
+            for regions in region_lists:
+                whole = bam_walk.select(path, regions)
+                n_kept.append(len(whole))
+                for max_reads in (0, 17):
+                    want = bam_walk.select(path, regions, max_reads)
+                    assert len(want) == (min(17, len(whole)) if max_reads else len(whole))
+                    for batch_reads in (7, 4000):
+                        assert np.array_equal(bam_walk.one_pass(path, regions, max_reads, batch_reads=batch_reads), want), (path, win, max_reads)
+                for world in (1, 2, 3, 7, 16):
+                    parts = [bam_walk.one_pass(path, regions, 0, rank, world, bai) for rank in range(world)]
+                    assert np.array_equal(np.concatenate(parts), whole), (path, win, world)
+                    if world > 1 and path != golden and regions is region_lists[0]:      # (all contigs: the cuts do deal the file)
+                        assert sum(len(q) > 0 for q in parts) > 1
+    assert n_kept[0] == 10 and min(n_kept) > 0 and max(n_kept) > 300
+    with pytest.raises(bam_walk.WalkError, match="max_reads needs one process"):
+        bam_walk.one_pass(shares, [(0, 0, 300_000)], 17, 0, 2, files[2][1])
+    with pytest.raises(bam_walk.WalkError, match="one region per contig"):
+        bam_walk.one_pass(shares, [(1, 0, 300_000), (0, 0, 300_000)])
+
+    def bgzf(payload):
+        out = b""
+        for q in range(0, len(payload), 0xFF00):
+            chunk = payload[q:q + 0xFF00]
+            c = zlib.compressobj(6, zlib.DEFLATED, -15)
+            data = c.compress(chunk) + c.flush()
+            out += struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 0xFF, 6, 66, 67, 2, len(data) + 25) + data + \
+                struct.pack("<II", zlib.crc32(chunk), len(chunk))
+        return out
+
+    def first_record(raw):
+        l_text, = struct.unpack_from("<i", raw, 4)
+        q = 8 + l_text
+        n_ref, = struct.unpack_from("<i", raw, q); q += 4
+        for _ in range(n_ref):
+            l_name, = struct.unpack_from("<i", raw, q); q += 8 + l_name
+        return q
+
+    raw = bam._bgzf_decompress(golden)
+    p0 = first_record(raw)
+    raw_s = bam._bgzf_decompress(shares)
+    ends = [first_record(raw_s)]
+    while ends[-1] + 4 <= len(raw_s):
+        ends.append(ends[-1] + 4 + struct.unpack_from("<i", raw_s, ends[-1])[0])
+    assert ends[-1] == len(raw_s) and len(ends) == 401
+    cases = {"short.bam": (bgzf(raw[:p0 + 40]), golden_regions, "truncated BAM record"),           # (test_native_bam_rejects_corrupt_files')
+             "late.bam": (bgzf(raw_s[:ends[350] + 100]), files[2][2][0], "truncated BAM record"),    # ... many windows into the walk
+             "late2.bam": (bgzf(raw_s[:ends[350] + 2]), files[2][2][0], "truncated BAM record"),      # ... inside a block_size field
+             "whole.bam": (bgzf(raw_s[:ends[350]]), files[2][2][0], None),
+             "header.bam": (bgzf(raw[:p0 - 7]), golden_regions, "BAM"),
+             "header2.bam": (bgzf(raw[:10]), golden_regions, "BAM")}
+    for win in ("1", None):
+        if win is None:
+            monkeypatch.delenv("NPORE_BAM_WINDOW_BLOCKS", raising=False)
+        else:
+            monkeypatch.setenv("NPORE_BAM_WINDOW_BLOCKS", win)
+        for name, (content, regions, msg) in cases.items():
+            (tmp_path / name).write_bytes(content)
+            if msg is None:
+                assert len(bam_walk.one_pass(str(tmp_path / name), regions)) == 350
+                continue
+            with pytest.raises(bam_walk.WalkError, match=msg) as ei:
+                bam_walk.one_pass(str(tmp_path / name), regions)
+            assert len(str(ei.value)) > 5, name                  # (a message, not just a code)
 
 
 def test_non_finite_tables_refused(tables):

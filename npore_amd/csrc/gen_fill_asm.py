@@ -44,7 +44,8 @@ SMR = SF      # the descriptor's summary bits (rc0 & 0xbc) from the head of a st
               # registers v108 ... v111, which the previous step's ds_write_b128 may still be reading there
 SCRATCH = ["v%d" % k for k in range(87, 112)]
 
-LDS_SUB_BASE = 6 * 32 * 33 * 4      # kernels.hpp LDS_SUB_BASE
+NP_CT = 34                          # layout.hpp: words per row of the LDS score table
+LDS_SUB_BASE = 6 * 32 * NP_CT * 4   # kernels.hpp LDS_SUB_BASE
 XCH_WORDS = 12                      # kernels.hpp
 
 
@@ -103,8 +104,8 @@ def shr_hist(t):
 
 def sub_read(t):
     t(f"""
-        v_alignbit_b32 {SUBV}, {O('refx')}, {O('seqw')}, 25
-        v_and_b32 {SUBV}, 0x3fc, {SUBV}
+        v_alignbit_b32 {SUBV}, {O('refx')}, {O('seqw')}, 27
+        v_and_b32 {SUBV}, 0xfc, {SUBV}
         ds_read_b32 {SUBV}, {SUBV} offset:{LDS_SUB_BASE}
     """)
 
@@ -333,7 +334,7 @@ def len_pass(t, mid, sfx, mode, first, last, multi):
         v_or_b32 {SE}, {SD}, {P1}
         v_cmp_lt_u32 vcc, 31, {SE}
         v_lshl_or_b32 {SE}, {X4}, 5, {SD}
-        v_mul_u32_u24 {SE}, 33, {SE}
+        v_mul_u32_u24 {SE}, {NP_CT}, {SE}
         v_sub_u32 {SE}, {SE}, {P1}
         v_add_u32 {SE}, 31, {SE}
         v_lshlrev_b32 {SE}, 2, {SE}

@@ -154,7 +154,7 @@ struct DevEnv {
         asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
         return r;
     }
-    const char *lds_sub;      // [ref 8][seq 8][4] copy of sub_scores (layout.hpp SUBT_*)
+    const char *lds_sub;      // [ref 8][seq 8] copy of sub_scores (layout.hpp SUBT_*)
     const char *lds_np;       // [6][NP_LT][NP_CT] floats (layout.hpp)
     const float *g_np;        // full table in global memory
     const uint8_t *win;       // LDS window of reference L bytes, 8 per position
@@ -207,8 +207,8 @@ struct DevEnv {
     __device__ __forceinline__ uint32_t mer_mask(const Tab &, uint32_t n4) const { return lane_table(n4, t_mmask); }
     __device__ __forceinline__ float sub(uint32_t seqw, uint32_t refx) const
     {
-        // bits 2-9 of {refx, seqw} >> 25: ref[j-1] (3 bits) | seq[i-1] (3 bits) | 2 bits of seq[i-2] (don't care)
-        return lds_abs_f32(LDS_SUB_BASE + (__builtin_amdgcn_alignbit(refx, seqw, 25) & 0x3FCu));
+        // bits 2-7 of {refx, seqw} >> 27: ref[j-1] (3 bits) | seq[i-1] (3 bits)
+        return lds_abs_f32(LDS_SUB_BASE + (__builtin_amdgcn_alignbit(refx, seqw, 27) & 0xFCu));
     }
     __device__ __forceinline__ float np_small(uint32_t dsc, int q) const
     {
@@ -362,8 +362,8 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
     int *slotbox = prog + MAX_WAVES_PER_CHUNK;                                // [SLOT_RING] + generation word
 
     // workgroup-shared tables.  A score row is stored with the call length DEcreasing, so that "q more copies
-    // deleted" is q entries UP from the address a column descriptor holds, and ends in one guard entry holding
-    // the constant 100 for negative call lengths (layout.hpp)
+    // deleted" is q entries UP from the address a column descriptor holds, and ends in a guard entry holding
+    // the constant 100 for negative call lengths and a pad entry that keeps the rows off each other's banks (layout.hpp)
     const int np_dim = p.max_l + 1;
     for (int idx = threadIdx.x; idx < MAX_PERIOD * NP_LT * NP_CT; idx += blockDim.x) {
         const int n = idx / (NP_LT * NP_CT), a = (idx / NP_CT) % NP_LT, b = NP_LT - 1 - idx % NP_CT;
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
         __syncthreads();
     }
     for (int idx = threadIdx.x; idx < SUBT_ENTRIES; idx += blockDim.x) {
-        const int rb = idx >> 5, sb = (idx >> 2) & 7;
+        const int rb = idx >> 3, sb = idx & 7;
         lds_sub[idx] = (rb < 5 && sb < 5) ? p.sub_scores[sb * 5 + rb] : 0.0f;
     }
     const int r = p.r;

@@ -21,8 +21,8 @@
 //                 (code 6 = past the chunk slice)
 //     bits  8-13  bit n-1: reference position j starts an n-polymer (L != 0 && L_IDX == 0)
 //     bits  0-2   the cell's own reference base ref[j-1]
-//                 (v_alignbit(refw.x, seqw, 25) & 0x3FC is then the byte offset of
-//                 sub_scores[seq[i-1]][ref[j-1]] in a [ref][seq][4] LDS table, see SUBT_*)
+//                 (v_alignbit(refw.x, seqw, 27) & 0xFC is then the byte offset of
+//                 sub_scores[seq[i-1]][ref[j-1]] in a [ref 8][seq 8] LDS table, see SUBT_*)
 //   refw[j].y
 //     bits  0-5   bit n-1: reference position j-n lies in an n-polymer (L != 0)
 //     bits  6-11  bit n-1: ... and is its first copy                  (L_IDX == 0)
@@ -34,7 +34,7 @@
 //                .y and the L window); .z: bit 6 of either word or bit 7 of .w is set ("rare column")
 //     bits 8-14  L of reference position j-n for that period
 //     bits 15-30 byte address, inside the LDS score table, of the entry for "call length L-1":
-//                (((n-1)*32 + min(L, max_l-1))*33 + 32 - L)*4; a deletion of q more copies reads 4q bytes higher
+//                (((n-1)*32 + min(L, max_l-1))*34 + 32 - L)*4; a deletion of q more copies reads 4q bytes higher
 //     bit  31    "first copy": start a deletion rather than continue one
 //   refl[j]  8 bytes: byte n-1 = L of reference position j for period n (0..max_l)
 //
@@ -68,8 +68,11 @@ NPORE_HD int tb_run(uint32_t w) { return (int)(w & TB_RUN_MASK); }
 constexpr int MER_SHIFT = 14, FLAG_SHIFT = 8;  // positions of the 18-bit base field and of the 6 "in an n-polymer" flags
 constexpr uint32_t SEQW_SENTINEL = 0x3FFFFu << MER_SHIFT;  // six code-7 bases, no flags
 constexpr uint32_t REFW_SENTINEL = 0x36DB6u << MER_SHIFT;  // six code-6 bases, no flags, own base 0
-// substitution-score table as the kernel indexes it: entry (ref << 5 | seq << 2 | g), g = 2 don't-care bits
-constexpr int SUBT_ENTRIES = 256;
+// substitution-score table as the kernel indexes it: entry (ref << 3 | seq).  The LDS bank of an entry is
+// (ref & 3) << 3 | seq: the 16 pairs of the base codes 1 ... 4 lie on 16 different banks, so a wave's read is free of
+// bank conflicts whatever its bases are.  (An index with don't-care bits BELOW seq -- ref << 5 | seq << 2 | g, 256
+// entries -- puts the four reference bases of one seq on ONE bank: 7.6 LDS cycles per wave read instead of 2.)
+constexpr int SUBT_ENTRIES = 64;
 constexpr int MAX_PERIOD = 6;                  // kernels are specialised for max_n <= 6
 constexpr float INF_F = 100.0f;                // reference src/aln.pyx:428
 constexpr int HIST_PAD = 6;                    // never-written history records either side of a row (cell.hpp)
@@ -79,11 +82,16 @@ constexpr uint32_t DSC_N4 = 0x1Cu, DSC_BIGL = 1u << 6, DSC_MORE = 1u << 7, DSC_S
 // column needs the generic path (L >= NP_LT in either candidate, or more than two candidates)
 constexpr uint32_t DSC_HAS2 = 1u << 5, DSC_RARE = 1u << 7;
 // LDS score table: [MAX_PERIOD][NP_LT][NP_CT] floats; a row holds np_scores[n][L][call] with the call length
-// DEcreasing -- entry NP_LT - 1 - call for call = NP_LT-1 ... 0 -- followed by one guard entry (NP_C0) holding INF_F
-// for call < 0 (np_score's "call < 0 -> 100"), which a candidate reaches by clamping "copies deleted so far" at the
-// row's own L (byte 1 of its descriptor): deleting q more copies is q entries up from the descriptor's address
-// (one shift-add).  25 KB; the odd row length also spreads the rows over the LDS banks.
-constexpr int NP_LT = 32, NP_CT = 33, NP_C0 = 1;
+// DEcreasing -- entry NP_LT - 1 - call for call = NP_LT-1 ... 0 -- followed by NP_C0 entries holding INF_F: the first
+// is the guard entry for call < 0 (np_score's "call < 0 -> 100"), which a candidate reaches by clamping "copies deleted
+// so far" at the row's own L (byte 1 of its descriptor): deleting q more copies is q entries up from the descriptor's
+// address (one shift-add); the second is padding that nothing reads.  25.5 KB.
+// Why the padding: the entry a descriptor holds is row L, column NP_LT - L, that is word (n-1)*NP_LT*NP_CT +
+// (NP_CT - 1)*L + NP_LT (+ q), and the LDS bank of a word is its index mod 32.  With a row of 33 words the -L cancels
+// the odd stride and EVERY candidate of a wave -- and the empty descriptor's entry 0 -- reads bank q: as many LDS
+// cycles as the half-wave has distinct (period, L) pairs (7 per wave read on 10 kb reads).  With 34 the bank is
+// (L + q) mod 32: different lengths on different banks, the empty descriptor alone on bank 0 (2.2 cycles).
+constexpr int NP_LT = 32, NP_CT = 34, NP_C0 = 2;
 // max_l: np_score clamps the table ROW to max_l - 1 (src/aln.pyx:257-274 as called); L itself is capped at max_l, so
 // the call length L - 1 - q never needs the clamp
 // A period n > max_l never scores: np_score returns its constant 100 (`n > max_n` with max_l passed as max_n,

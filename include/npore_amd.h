@@ -220,7 +220,7 @@ int npore_total_timing(npore_ctx *ctx, double *ms, int n);
  * The BAM -> SAM pipeline (npore_bam_realign_file / _sequential): "device_glue" (default 1): realign_read's glue
  * (src/bam.pyx:65-78) on the device, 0 = on the host from the op strings; "device_pack" (default 1, with the device
  * glue): align()'s inputs (src/bam.pyx:42, 45, 59-61) unpacked from the BAM records on the device, 0 = packed on the
- * host and uploaded. */
+ * host and uploaded.  "cms_batch_reads" (default 4000): records per batch of npore_bam_confusion. */
 int npore_ctx_set(npore_ctx *ctx, const char *key, int64_t value);
 
 /* Batch sizing.  The DP of a chunk (at most max_b_rows anti-diagonals of a read; reference src/aln.pyx:344-358,
@@ -367,6 +367,27 @@ int npore_confusion_counts(const char *lines, const int64_t *line_off, int64_t n
                            int64_t n_ref, const char *ref_text, int64_t ref_text_len, const int32_t *np_info,
                            int64_t np_len, int max_n, int max_l, int64_t *subs, int64_t *nps, int64_t *inss,
                            int64_t *dels, int64_t *bad_lines, int threads);
+
+/*
+ * The same four count matrices straight from the BAM records, on the device: no pileup text, no samtools
+ * (csrc/confusion_rec.hpp states the rule, csrc/confusion_kernels.hpp counts: one workgroup per record).
+ *   bam: a handle of any mode -- a one-pass handle (mode 3) is walked once (NPORE_E_UNSUPPORTED when the file is not
+ *     sorted by reference: open it indexed), any other is read through its record index;
+ *   fa / fasta_of_ref: as for npore_bam_realign_file; ranges (ref_id, start, stop)[n_ranges]: BAM reference id and
+ *     [start, stop) of get_ranges(regions, chunk_width); a position is annotated within the slice of its range, like
+ *     calc_confusion_matrices does, and counts once per range that holds it;
+ *   min_bq: base entries below it are dropped (mpileup's -Q, 13; quality 0xFF = missing passes); exclude_flags: records
+ *     with one of these flag bits are left out (mpileup's default 0x704).
+ * max_n / max_l are the context's (an annotation-only context will do).  The counts are ADDED to subs[5][5],
+ * nps[max_n][max_l+1][max_l+1], inss[max_l+1], dels[max_l+1] and tallies[16] (int64) on success only: [0] records walked,
+ * [1] dropped by flags, [2] with N / P in the CIGAR, [3] with a CIGAR that disagrees with l_seq, [4] I / D operations
+ * without a base to sit on (not counted), [5] entries with a letter outside ACGTN, [6] entries below min_bq, [7] entries
+ * counted, [8] batches, [9] nanoseconds of the counting kernels alone (events).  Batch size: npore_ctx_set
+ * "cms_batch_reads" (default 4000).  Integer counters: the result does not depend on batching or on the reader.
+ */
+int npore_bam_confusion(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n_ranges,
+                        const int32_t *ref_id, const int64_t *start, const int64_t *stop, int min_bq, uint32_t exclude_flags,
+                        int64_t *subs, int64_t *nps, int64_t *inss, int64_t *dels, int64_t *tallies);
 
 /* Debug / tests: one raw DEFLATE stream (a BGZF block's payload; the BAM reader's inner loop, pysam / htslib in the
  * reference) of in_len bytes that must inflate to exactly out_len bytes.  force: 0 = as the readers do it (this

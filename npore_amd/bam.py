@@ -795,6 +795,66 @@ def calc_confusion_matrices(range_tuple, pileups=None, refs=None, np_info=None, 
     return subs, nps, inss, dels
 
 
+CMS_TALLIES = ("records", "records_flagged", "records_refskip", "records_malformed", "adjacent_indels", "entries_ambiguous",
+               "entries_lowq", "entries_counted", "batches", "kernel_ns")
+
+
+def confusion_from_bam(ctx, bam, fasta, ranges, min_bq=13, exclude_flags=0x704):
+    """The four count matrices of calc_confusion_matrices straight from the BAM records, counted on the GPU
+    (npore_bam_confusion; the rule: csrc/confusion_rec.hpp) -- no pileup text, no samtools.
+    ctx: an aln.Context (an annotation-only one will do; max_n / max_l are its own); bam: a path or a NativeBam; fasta: a
+    path or a NativeFasta; ranges: [(contig, start, stop)] as bed.get_ranges(cfg.args.regions, chunk_width) makes them.
+    A path is read in ONE PASS where the reader's rules allow it (a BGZF file sorted by reference), else through the
+    record index.  min_bq / exclude_flags: the defaults of `samtools mpileup` (-Q 13; UNMAP, SECONDARY, QCFAIL, DUP).
+    Position-true: a position nobody covers adds nothing (the text route shifts behind a coverage gap); no depth cap
+    (mpileup -d) and no handling of overlapping mates.  Returns (subs, nps, inss, dels, tallies): int64 matrices
+    and a dict of CMS_TALLIES -- `adjacent_indels` counts the I / D operations that follow another I / D (or lead a read)
+    and are not counted, because pileup programs place their markers differently."""
+    from . import _lib
+    lib = _lib.load()
+    own_fa = not isinstance(fasta, NativeFasta)
+    fa = NativeFasta(fasta) if own_fa else fasta
+    max_n, max_l = ctx.max_n, ctx.max_l
+
+    def run(b):
+        ids = {n: i for i, n in enumerate(b.references)}
+        rid = np.array([ids.get(c, -1) for c, _, _ in ranges], np.int32)
+        beg = np.array([s for _, s, _ in ranges], np.int64)
+        end = np.array([e for _, _, e in ranges], np.int64)
+        subs = np.zeros((cfg.nbases, cfg.nbases), np.int64)
+        nps = np.zeros((max_n, max_l + 1, max_l + 1), np.int64)
+        inss, dels, tallies = np.zeros(max_l + 1, np.int64), np.zeros(max_l + 1, np.int64), np.zeros(16, np.int64)
+        fmap = b.fasta_map(fa)
+        rc = lib.npore_bam_confusion(ctx.handle, b.handle, fa.handle, fmap.ctypes.data, len(ranges), rid.ctypes.data, beg.ctypes.data,
+                                     end.ctypes.data, int(min_bq), int(exclude_flags), subs.ctypes.data, nps.ctypes.data,
+                                     inss.ctypes.data, dels.ctypes.data, tallies.ctypes.data)
+        if rc == -5 and b.one_pass:
+            raise OnePassUnsupported(_lib.last_error())
+        if rc:
+            raise RuntimeError(f"libnpore_amd: {rc} {_lib.last_error()}")
+        return subs, nps, inss, dels, dict(zip(CMS_TALLIES, tallies.tolist()))
+
+    try:
+        if isinstance(bam, NativeBam):
+            return run(bam)
+        if NativeBam.is_bgzf(bam) and os.environ.get("NPORE_BAM_ONE_PASS", "1") != "0":
+            b = NativeBam(bam, one_pass=True)
+            try:
+                return run(b)
+            except OnePassUnsupported:
+                pass                             # (not sorted by reference: nothing was added, the indexed reader counts)
+            finally:
+                b.close()
+        b = NativeBam(bam, share=False)
+        try:
+            return run(b)
+        finally:
+            b.close()
+    finally:
+        if own_fa:
+            fa.close()
+
+
 def get_confusion_matrices():
     """Reference src/bam.pyx:166-200: the cached count matrices of --stats_dir, or (--recalc_cms) counted from the
     BAM range by range (cfg.args.regions cut into --chunk_width pieces), summed and cached there.
@@ -818,6 +878,21 @@ def get_confusion_matrices():
         from .bed import get_ranges
         total = None
         ranges = get_ranges(cfg.args.regions, cfg.args.chunk_width)
+        if getattr(cfg.args, "cms_source", "mpileup") == "bam" and ranges:
+            # straight from the records, on the GPU (confusion_from_bam): an annotation-only context of its own
+            from . import aln
+            ctx = aln.Context(None, None, device=int(getattr(cfg.args, "device", 0)) % max(aln.device_count(), 1))
+            try:
+                *total, tallies = confusion_from_bam(ctx, cfg.args.bam, cfg.args.ref, ranges, min_bq=cfg.args.cms_min_bq,
+                                                     exclude_flags=cfg.args.cms_exclude_flags)
+            finally:
+                ctx.close()
+            total = tuple(total)
+            print(f"    {tallies['records']} records, {tallies['entries_counted']} bases counted in {len(ranges)} chunks; left out: "
+                  f"{tallies['entries_lowq']} bases below the quality bound, {tallies['entries_ambiguous']} ambiguous letters, "
+                  f"{tallies['adjacent_indels']} adjacent INDELs, {tallies['records_flagged']} records by flags, "
+                  f"{tallies['records_refskip']} with N / P, {tallies['records_malformed']} malformed.")
+            ranges = []
         for k, rg in enumerate(ranges):
             res = calc_confusion_matrices(rg)
             total = res if total is None else tuple(a + b for a, b in zip(total, res))

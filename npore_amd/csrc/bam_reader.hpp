@@ -352,7 +352,7 @@ inline int bam_dump_inflated(const npore_bam *b, const char *path)
 }
 
 inline int64_t bam_select(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
-                          int64_t max_reads, int64_t *out_idx, int64_t cap)
+                          int64_t max_reads, int64_t *out_idx, int64_t cap, uint32_t drop_flags = 0x100 | 0x800 | 0x4)
 {
     if (!b || (n_regions > 0 && (!ref_id || !start || !stop)) || (cap > 0 && !out_idx)) return fail(NPORE_E_INVALID, "null argument");
     int64_t kept = 0;
@@ -372,7 +372,7 @@ inline int64_t bam_select(const npore_bam *b, int n_regions, const int32_t *ref_
             if (b->ref_sorted[(size_t)ref_id[g]] && pos >= stop[g]) break;
             if (!(pos < stop[g] && pos + rl > start[g])) continue;                 // overlaps [start, stop)
             if (max_reads > 0 && kept >= max_reads) return kept;                   // src/bam.pyx:29-30
-            if (b->m_flag[(size_t)i] & (0x100 | 0x800 | 0x4)) continue;           // secondary / supplementary / unmapped, :31-32
+            if (b->m_flag[(size_t)i] & drop_flags) continue;                      // secondary / supplementary / unmapped, :31-32
             if (kept < cap) out_idx[kept] = i;
             kept++;
         }
@@ -753,9 +753,9 @@ inline int one_pass_args_check(const npore_bam *b, int n_regions, const int32_t 
 class BamRecordWalker {
 public:
     BamRecordWalker(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
-                    int64_t max_reads, int threads)
+                    int64_t max_reads, int threads, uint32_t drop_flags = 0x100 | 0x800 | 0x4)
         : b_(b), src_(b, threads), n_regions_(n_regions), ref_id_(ref_id), start_(start), stop_(stop), max_reads_(max_reads),
-          done_(n_regions == 0)
+          drop_flags_(drop_flags), done_(n_regions == 0)
     {
         if (!b->has_share) return;
         if (b->share_begin == UINT64_MAX) done_ = true;          // nothing left for this rank
@@ -805,7 +805,7 @@ public:
             const int64_t pos = rv.pos(), rl = rec_ref_len(rv);
             if (!(pos < stop_[g_] && pos + rl > start_[g_])) continue;           // overlaps [start, stop)
             if (max_reads_ > 0 && kept_ >= max_reads_) { done_ = true; break; }  // src/bam.pyx:29-30
-            if (rv.flag() & (0x100 | 0x800 | 0x4)) continue;                     // secondary / supplementary / unmapped, :31-32
+            if ((uint32_t)rv.flag() & drop_flags_) continue;                     // secondary / supplementary / unmapped, :31-32
             rf.ptr.push_back(q);
             if (keep.empty() || keep.back() != win_.buf) keep.push_back(win_.buf);
             kept_++;
@@ -838,6 +838,7 @@ private:
     const int64_t *const start_, *const stop_;
     int g_ = 0;                              // the region the walk has reached
     const int64_t max_reads_;
+    const uint32_t drop_flags_;              // (the realigner's; the recount of the confusion matrices filters for itself)
     int64_t kept_ = 0;
     int32_t last_rid_ = -1;                  // (the sorted-by-reference check)
     bool done_;

@@ -30,6 +30,7 @@
 #include "prep_kernels.hpp"
 #include "annot_wave.hpp"
 #include "unpack_kernels.hpp"
+#include "confusion_kernels.hpp"
 
 using namespace npore;
 
@@ -263,6 +264,10 @@ struct npore_ctx {
     int device_pack = 1;        // BAM -> SAM pipeline with the glue on the device: align()'s inputs unpacked from the records on the device
     // device pack: the FASTA of the current run on the device (uploaded once per FASTA), the contig of every BAM reference
     DevBuf d_fasta, d_ctg;
+    // recount of the confusion matrices from BAM records (npore_bam_confusion): the batch's record heads and their offsets,
+    // the current contig's ranges, the counters
+    DevBuf cms_raw, cms_off, cms_ranges, cms_counts;
+    int64_t cms_batch_reads = 4000;
     uint64_t d_fasta_serial = 0;
     size_t d_fasta_bytes = 0;
     int n_ctg = 0;
@@ -1004,7 +1009,7 @@ void npore_ctx_destroy(npore_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();       // nothing of this context may still be running
     for (DevBuf *b : {&ctx->in_refs, &ctx->in_seqs, &ctx->in_cigs, &ctx->in_off, &ctx->out, &ctx->out_off, &ctx->out_len, &ctx->status,
-                      &ctx->d_fasta, &ctx->d_ctg})
+                      &ctx->d_fasta, &ctx->d_ctg, &ctx->cms_raw, &ctx->cms_off, &ctx->cms_ranges, &ctx->cms_counts})
         b->release();
     for (auto &w : ctx->ws) {
         for (DevBuf *b : w.all) b->release();
@@ -1291,6 +1296,7 @@ try {
     else if (k == "coresident") ctx->coresident = value != 0;
     else if (k == "device_glue") ctx->device_glue = value != 0;
     else if (k == "device_pack") ctx->device_pack = value != 0;
+    else if (k == "cms_batch_reads") { if (value < 1) return fail(NPORE_E_INVALID, "cms_batch_reads: at least 1"); ctx->cms_batch_reads = value; }
     else if (k == "fill_streams") { if (value < 1 || value > 2) return fail(NPORE_E_INVALID, "fill_streams: 1 or 2"); ctx->fill_streams = (int)value; }
     else return fail(NPORE_E_INVALID, "unknown key " + k);
     return NPORE_OK;
@@ -1392,6 +1398,231 @@ try {
         nbad += bad[(size_t)t];
     }
     if (bad_lines) *bad_lines = nbad;
+    return NPORE_OK;
+}
+NPORE_CATCH_INT
+
+// ---- confusion matrices from BAM records (confusion_rec.hpp, confusion_kernels.hpp) ------------------------------
+namespace {
+struct CmsContig {
+    std::vector<CmsRange> ranges;        // layer after layer
+    std::vector<int32_t> layer_off;
+    int64_t bases = 0;                   // of all slices
+    int64_t lo = 0, hi = 0;              // hull of the ranges: what the reader selects by
+};
+
+// the caller's ranges of one contig (clipped to it) in layers of ascending, disjoint ranges, their slices laid out back to back
+void cms_layers(std::vector<CmsRange> rs, int max_n, CmsContig &c)
+{
+    std::sort(rs.begin(), rs.end(), [](const CmsRange &a, const CmsRange &b) { return a.st != b.st ? a.st < b.st : a.en < b.en; });
+    std::vector<std::vector<CmsRange>> layers;
+    int64_t off = 0;
+    c.lo = rs.front().st;
+    c.hi = 0;
+    for (CmsRange r : rs) {
+        r.ann = off * max_n;
+        off += r.slen;
+        c.hi = std::max(c.hi, r.en);
+        size_t y = 0;
+        while (y < layers.size() && layers[y].back().en > r.st) y++;
+        if (y == layers.size()) layers.emplace_back();
+        layers[y].push_back(r);
+    }
+    c.bases = off;
+    c.layer_off.assign(1, 0);
+    for (auto &l : layers) {
+        c.ranges.insert(c.ranges.end(), l.begin(), l.end());
+        c.layer_off.push_back((int32_t)c.ranges.size());
+    }
+}
+
+struct CmsHostTally {
+    int64_t t[CMS_N_TALLIES] = {};
+};
+}  // namespace
+
+// the planes of a contig's range slices (ws[0].seql) and its range table (cms_ranges) on the device
+static int cms_contig_planes(npore_ctx *ctx, const CmsContig &c, const char *d_contig, hipStream_t s)
+{
+    const int mn = ctx->max_n;
+    const size_t n = c.ranges.size(), rbytes = n * sizeof(CmsRange), lbytes = c.layer_off.size() * 4;
+    if (int rc = ctx->in_seqs.ensure((size_t)c.bases + 16)) return rc;
+    if (int rc = ctx->ws[0].seql.ensure((size_t)c.bases * mn + 64)) return rc;
+    if (int rc = ctx->cms_ranges.ensure(rbytes + lbytes + 16)) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->cms_ranges.p, c.ranges.data(), rbytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ctx->cms_ranges.as<char>() + rbytes, c.layer_off.data(), lbytes, hipMemcpyHostToDevice, s));
+    SliceCodesParams sp{d_contig, ctx->cms_ranges.as<CmsRange>(), (int)n, mn, ctx->in_seqs.as<uint8_t>()};
+    hipLaunchKernelGGL(slice_codes_kernel, dim3((unsigned)n), dim3(256), 0, s, sp);
+    HIP_TRY(hipGetLastError());
+    std::vector<int64_t> off(n + 1);
+    for (size_t k = 0; k < n; k++) off[k] = c.ranges[k].ann / mn;
+    off[n] = c.bases;
+    std::sort(off.begin(), off.end());               // (the table is in layer order, the slices lie in the order of their starts)
+    return launch_np_info(ctx, s, off.data(), (int64_t)n, nullptr, ctx->ws[0].seql.as<uint8_t>());
+}
+
+int npore_bam_confusion(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n_ranges,
+                        const int32_t *ref_id, const int64_t *start, const int64_t *stop, int min_bq, uint32_t exclude_flags,
+                        int64_t *subs, int64_t *nps, int64_t *inss, int64_t *dels, int64_t *tallies)
+try {
+    if (!ctx || !b || !fa || !fasta_of_ref || n_ranges < 0 || (n_ranges > 0 && (!ref_id || !start || !stop)) || !subs || !nps || !inss ||
+        !dels || !tallies)
+        return fail(NPORE_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = quiesce(ctx)) return rc;
+    const int mn = ctx->max_n, dim = ctx->max_l + 1;
+    const size_t n_nps = (size_t)mn * dim * dim, n_counts = 25 + n_nps + 2 * (size_t)dim + CMS_N_TALLIES;
+    const size_t n_refs = b->ref_names.size();
+    // the ranges by contig
+    std::vector<CmsContig> contigs(n_refs);
+    {
+        std::vector<std::vector<CmsRange>> by(n_refs);
+        for (int64_t k = 0; k < n_ranges; k++) {
+            if (ref_id[k] < 0 || ref_id[k] >= (int32_t)n_refs) continue;      // (a contig the BAM does not know has no records)
+            const int fi = fasta_of_ref[ref_id[k]];
+            if (fi < 0 || fi >= (int)fa->names.size()) return fail(NPORE_E_INVALID, "a range lies on a contig that is not in the FASTA");
+            const int64_t clen = fa->len((size_t)fi);
+            if (clen >= (1ll << 30)) return fail(NPORE_E_UNSUPPORTED, "contig too long");
+            CmsRange r;
+            if (cms_clip(start[k], stop[k], clen, r)) by[(size_t)ref_id[k]].push_back(r);
+        }
+        for (size_t r = 0; r < n_refs; r++)
+            if (!by[r].empty()) cms_layers(std::move(by[r]), mn, contigs[r]);
+    }
+    std::vector<int32_t> h_rid;
+    std::vector<int64_t> h_lo, h_hi;
+    for (size_t r = 0; r < n_refs; r++)
+        if (!contigs[r].ranges.empty()) { h_rid.push_back((int32_t)r); h_lo.push_back(contigs[r].lo); h_hi.push_back(contigs[r].hi); }
+    if (int rc = device_fasta(ctx, b, fa, fasta_of_ref)) return rc;
+    std::vector<CtgEntry> ctg(std::max<size_t>(1, n_refs), CtgEntry{nullptr, 0});
+    for (size_t k = 0; k < n_refs; k++) {
+        const int fi = fasta_of_ref[k];
+        if (fi >= 0 && fi < (int)fa->names.size()) ctg[k] = CtgEntry{ctx->d_fasta.as<char>() + fa->off[(size_t)fi], fa->len((size_t)fi)};
+    }
+    hipStream_t s = ctx->stream;
+    if (int rc = ctx->cms_counts.ensure(n_counts * 8)) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->cms_counts.p, 0, n_counts * 8, s));
+
+    // the reader: one pass where the handle allows it (mode 3: no record index), else selection on the index; the flags
+    // are this function's business (drop_flags = 0), unplaced records never arrive
+    const bool one_pass = b->file && !b->blocks.empty() && b->rec_off.empty();
+    const int threads = 0;
+    const int64_t batch_reads = ctx->cms_batch_reads;
+    std::unique_ptr<BamRecordWalker> walker;
+    std::vector<int64_t> idx;
+    int64_t idx_at = 0;
+    if (one_pass) {
+        if (int rc = one_pass_args_check(b, (int)h_rid.size(), h_rid.data(), 0)) return rc;
+        walker.reset(new BamRecordWalker(b, (int)h_rid.size(), h_rid.data(), h_lo.data(), h_hi.data(), 0, threads, 0u));
+    } else {
+        const int64_t k = bam_select(b, (int)h_rid.size(), h_rid.data(), h_lo.data(), h_hi.data(), 0, nullptr, 0, 0u);
+        if (k < 0) return (int)k;
+        idx.assign((size_t)k + 1, 0);
+        if (bam_select(b, (int)h_rid.size(), h_rid.data(), h_lo.data(), h_hi.data(), 0, idx.data(), k, 0u) != k) return fail(NPORE_E_INVALID, "select is not repeatable");
+        idx.resize((size_t)k);
+    }
+    RecFetch rf;
+    std::vector<std::shared_ptr<RawBuf>> keep;
+    PinnedBuf raw, rawo_pin;
+    std::vector<int32_t> gate;
+    std::vector<int64_t> rawo;
+    std::vector<int32_t> kept_rid;
+    CmsHostTally ht;
+    double kernel_ms = 0.0;
+    int32_t cur_rid = -1;
+    for (;;) {
+        keep.clear();
+        int64_t m;
+        if (one_pass) m = walker->next_batch(rf, keep, batch_reads);
+        else {
+            m = std::min<int64_t>(batch_reads, (int64_t)idx.size() - idx_at);
+            if (m > 0) { if (int rc = fetch_records(b, idx.data() + idx_at, m, threads, rf)) return rc; }
+            idx_at += std::max<int64_t>(m, 0);
+        }
+        if (m < 0) return (int)m;
+        if (m == 0) break;
+        // the gate (confusion_rec.hpp cms_gate), on all cores
+        gate.assign((size_t)m, -1);
+        const int64_t per = 64;
+        parallel_for((m + per - 1) / per, threads, [&](int64_t tix) {
+            for (int64_t k = tix * per; k < std::min(m, (tix + 1) * per); k++) {
+                const RecView r = rec_of(rf, k);
+                const int32_t rid = r.ref_id();
+                if (rid < 0 || rid >= (int32_t)n_refs || contigs[(size_t)rid].ranges.empty()) continue;
+                const CmsContig &c = contigs[(size_t)rid];
+                gate[(size_t)k] = cms_gate((uint32_t)r.flag(), r.pos(), r.l_seq(), r.cigar(), r.n_cigar(), exclude_flags, c.ranges.data(),
+                                           c.layer_off.data(), (int)c.layer_off.size() - 1);
+            }
+        });
+        rawo.assign(1, 0);
+        kept_rid.clear();
+        std::vector<int64_t> kept;
+        for (int64_t k = 0; k < m; k++) {
+            const int g = gate[(size_t)k];
+            if (g > 0) ht.t[g]++;
+            if (g != 0) continue;
+            const RecView r = rec_of(rf, k);
+            kept.push_back(k);
+            kept_rid.push_back(r.ref_id());
+            rawo.push_back(rawo.back() + (((int64_t)(r.aux() - r.p) + 4 + 7) & ~7ll));
+        }
+        ht.t[CMS_T_BATCHES]++;
+        const int64_t n = (int64_t)kept.size();
+        if (n == 0) continue;
+        if (!raw.ensure((size_t)rawo[(size_t)n] + 64) || !rawo_pin.ensure((size_t)(n + 1) * 8)) return fail(NPORE_E_NOMEM, "batch buffers");
+        std::memcpy(rawo_pin.p, rawo.data(), (size_t)(n + 1) * 8);
+        parallel_for((n + per - 1) / per, threads, [&](int64_t tix) {
+            for (int64_t k = tix * per; k < std::min(n, (tix + 1) * per); k++) {
+                const RecView r = rec_of(rf, kept[(size_t)k]);
+                std::memcpy(raw.p + rawo[(size_t)k], rf.ptr[(size_t)kept[(size_t)k]], (size_t)(r.aux() - r.p) + 4);
+            }
+        });
+        if (int rc = ctx->cms_raw.ensure((size_t)rawo[(size_t)n] + 64)) return rc;
+        if (int rc = ctx->cms_off.ensure((size_t)(n + 1) * 8)) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->cms_raw.p, raw.p, (size_t)rawo[(size_t)n], hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ctx->cms_off.p, rawo_pin.p, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        for (int64_t k0 = 0; k0 < n;) {
+            int64_t k1 = k0 + 1;
+            while (k1 < n && kept_rid[(size_t)k1] == kept_rid[(size_t)k0]) k1++;
+            const int32_t rid = kept_rid[(size_t)k0];
+            const CmsContig &c = contigs[(size_t)rid];
+            if (rid != cur_rid) {                    // one contig's planes at a time
+                if (int rc = cms_contig_planes(ctx, c, ctg[(size_t)rid].bases, s)) return rc;
+                cur_rid = rid;
+            }
+            CmsParams cp;
+            cp.raw = ctx->cms_raw.as<uint8_t>();
+            cp.raw_off = ctx->cms_off.as<int64_t>() + k0;
+            cp.n_reads = k1 - k0;
+            cp.contig = ctg[(size_t)rid].bases;
+            cp.clen = ctg[(size_t)rid].len;
+            cp.ranges = ctx->cms_ranges.as<CmsRange>();
+            cp.layer_off = reinterpret_cast<const int32_t *>(ctx->cms_ranges.as<char>() + c.ranges.size() * sizeof(CmsRange));
+            cp.n_layers = (int)c.layer_off.size() - 1;
+            cp.planes = ctx->ws[0].seql.as<uint8_t>();
+            cp.max_n = mn;
+            cp.max_l = ctx->max_l;
+            cp.min_bq = min_bq;
+            cp.counts = ctx->cms_counts.as<unsigned long long>();
+            HIP_TRY(hipEventRecord(ctx->ev[1], s));
+            hipLaunchKernelGGL(confusion_records_kernel, dim3((unsigned)(k1 - k0)), dim3(256), 0, s, cp);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(ctx->ev[2], s));
+            HIP_TRY(hipStreamSynchronize(s));        // (the staging buffers and the planes are free again)
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
+            kernel_ms += ms;
+            k0 = k1;
+        }
+    }
+    std::vector<unsigned long long> h(n_counts);
+    HIP_TRY(hipMemcpyAsync(h.data(), ctx->cms_counts.p, n_counts * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t k = 0; k < 25; k++) subs[k] += (int64_t)h[k];
+    for (size_t k = 0; k < n_nps; k++) nps[k] += (int64_t)h[25 + k];
+    for (int k = 0; k < dim; k++) { inss[k] += (int64_t)h[25 + n_nps + k]; dels[k] += (int64_t)h[25 + n_nps + dim + k]; }
+    for (int k = 0; k < CMS_N_TALLIES; k++) tallies[k] += (int64_t)h[25 + n_nps + 2 * dim + k] + ht.t[k];
+    tallies[CMS_T_KERNEL_NS] += (int64_t)(kernel_ms * 1e6);
     return NPORE_OK;
 }
 NPORE_CATCH_INT

@@ -10,7 +10,8 @@ it in batches instead of one align() call per pool worker
 `python -m torch.distributed.run --nproc-per-node N -m npore_amd.realign ...`;
 rank k realigns reads k, k+N, ... into its own part file and rank 0 appends
 the parts to the SAM (record order is arbitrary in the reference too).
---recalc_cms recounts the confusion matrices with `samtools mpileup` like the reference (bam.get_confusion_matrices); --plot is out of scope.
+--recalc_cms recounts the confusion matrices with `samtools mpileup` like the reference (bam.get_confusion_matrices), or with
+--cms_source bam straight from the BAM records on the GPU (bam.confusion_from_bam); --plot is out of scope.
 """
 import argparse
 import os
@@ -41,8 +42,16 @@ def argparser():
                              "recounted matrices are written here, default ./stats as in the reference).")
     parser.add_argument("--plot", action="store_true", help="(not supported in this build)")
     parser.add_argument("--recalc_cms", action="store_true",
-                        help="Recount the confusion matrices from the BAM (needs `samtools mpileup`) instead of loading them.")
+                        help="Recount the confusion matrices from the BAM instead of loading them (--cms_source: `samtools mpileup`, or the records themselves).")
     parser.add_argument("--recalc_exit", action="store_true", help="Exit after --recalc_cms.")
+    parser.add_argument("--cms_source", choices=("mpileup", "bam"), default="mpileup",
+                        help="--recalc_cms: `mpileup` reads the text of `samtools mpileup` like the reference; `bam` counts straight "
+                             "from the BAM records on the GPU, without samtools.  `bam` is position-true (a position nobody covers "
+                             "adds nothing, where the text route shifts), has no depth cap (mpileup -d) and no handling of "
+                             "overlapping mates, and leaves out INDELs that follow another INDEL.")
+    parser.add_argument("--cms_min_bq", type=int, default=13, help="--cms_source bam: bases below this quality are not counted (mpileup -Q).")
+    parser.add_argument("--cms_exclude_flags", type=int, default=0x704,
+                        help="--cms_source bam: records with one of these flag bits are left out (mpileup's UNMAP, SECONDARY, QCFAIL, DUP).")
     # additions
     parser.add_argument("--batch_reads", type=int, default=4000, help="Reads per GPU batch (4 000 reads of 10 kb fill the GPU once at the default band, Context.round_chunks; file to file 6 000 - 8 000 measured 5 - 7 %% faster at twice the device memory: 49 GB of traceback words per batch in flight, three in flight).")
     parser.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")), help="HIP device.")

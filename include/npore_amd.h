@@ -307,6 +307,39 @@ int npore_bam_format_sam(npore_bam *bam, const int64_t *idx, int64_t n, const ch
                          const int64_t *final_len, const int32_t *status, int threads, const char **sam,
                          int64_t *sam_len);
 
+/* The same reads as BAM records (csrc/bam_reader.hpp states the record: the SAM line's fields in binary, the final CIGAR
+ * as `len << 4 | op` words, bases and qualities without the soft clips, next_refID = next_pos = -1, tlen = the reference
+ * length, the HP tag in the smallest integer type), one after the other, each with its block_size word.
+ * NPORE_E_UNSUPPORTED: a final CIGAR of more than 65 535 operations.  *recs points into storage owned by `bam`. */
+int npore_bam_format_bam(npore_bam *bam, const int64_t *idx, int64_t n, const char *finals, const int64_t *final_off,
+                         const int64_t *final_len, const int32_t *status, int threads, const uint8_t **recs,
+                         int64_t *recs_len);
+/* What the NEXT npore_bam_realign_file / _sequential / npore_bam_write_file on the handle appends to its out_path
+ * (the setting holds for that one run): NPORE_OUT_SAM, the text, or NPORE_OUT_BAM, the records of npore_bam_format_bam in
+ * BGZF members with STORED deflate blocks -- the record stream cut every 65 280 bytes counted from the run's first
+ * record, whatever the batches are, so the file does not depend on batch_reads or on the reader.  The run appends at
+ * the file's end (the caller has written the header's members there, or nothing: a rank's part) and ends the file with
+ * the 28-byte EOF member if flags has NPORE_OUT_EOF.  bai_path (NULL / "": none): the .bai of the run's records -- bins
+ * with their chunks and the 16 kb linear index, virtual offsets counted from where the run began to append -- written
+ * when the records went out in coordinate order, and not at all otherwise (npore_bam_output_info says which). */
+#define NPORE_OUT_SAM 0
+#define NPORE_OUT_BAM 1
+#define NPORE_OUT_EOF 1
+/* flags: the run writes one rank's PART of a file (no header in front, no EOF member): the offsets of its index count from
+ * a nominal first member at NPORE_PART_BASE instead of from the file's size -- none of them is 0, which a .bai takes for
+ * "no record in this window" -- and whoever appends the part to the file shifts them (npore_amd/dist.py). */
+#define NPORE_OUT_PART 2
+#define NPORE_PART_BASE 65536
+int npore_bam_set_output(npore_bam *bam, int format, const char *bai_path, int flags);
+/* Of the last BAM-mode run on the handle: out4[0] records written, [1] bytes of the record stream, [2] 1 = the index was
+ * written, 0 = none was asked for, -1 = the records were not in coordinate order (no index), [3] size of the file. */
+int npore_bam_output_info(const npore_bam *bam, int64_t *out4);
+/* The host's part of a BAM-mode run alone (no GPU): the selected reads with their final CIGARs, record bytes made in
+ * batches of batch_reads and appended to out_path as npore_bam_set_output says. */
+int npore_bam_write_file(npore_bam *bam, const int64_t *idx, int64_t n, int64_t batch_reads, const char *finals,
+                         const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
+                         const char *out_path);
+
 /* realign_read for a batch: pack -> npore_align_batch -> npore_standardize_batch -> SAM text. */
 int npore_bam_realign_batch(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref,
                             const int64_t *idx, int64_t n, float indel_start, float indel_extend, int max_b_rows,

@@ -221,19 +221,136 @@ def get_read_data(bam, ref_seqs):
                    0 if r.hp is None else int(r.hp))
 
 
+def header_text(bam):
+    """The header the reference writes through pysam (src/bam.pyx:127-145)."""
+    return ("@HD\tVN:1.6\tSO:coordinate\n" + "".join(f"@SQ\tSN:{name}\tLN:{l}\n" for name, l in zip(bam.references, bam.lengths)) +
+            f"@PG\tPN:realigner\tID:realigner\tVN:{cfg.__version__}\tCL:{' '.join(sys.argv)}\n")
+
+
 def create_header(outfile, bam):
     """SAM header as the reference writes it through pysam (src/bam.pyx:127-145); truncates."""
     if os.path.dirname(outfile):
         os.makedirs(os.path.dirname(outfile), exist_ok=True)
     with open(outfile, "w") as fh:
-        fh.write("@HD\tVN:1.6\tSO:coordinate\n")
-        for name, l in zip(bam.references, bam.lengths):
-            fh.write(f"@SQ\tSN:{name}\tLN:{l}\n")
-        fh.write(f"@PG\tPN:realigner\tID:realigner\tVN:{cfg.__version__}\tCL:{' '.join(sys.argv)}\n")
+        fh.write(header_text(bam))
 
 
-def realign_reads(ctx, read_data, out_sam, r=30, max_b_rows=20000):
-    """Batched realign_read (src/bam.pyx:51-84): align on the GPU, standardise, append SAM lines.
+# ---- BAM out (--out_format bam): the pure-Python statement of csrc/bam_reader.hpp's RECORD / FILE / INDEX rules ----
+BGZF_STORED_PAYLOAD = 0xFF00         # payload bytes of a member; a stored member is its payload + 31 bytes
+PART_BASE = 65536                    # where the index sidecar of a rank's part takes the part to begin (NPORE_PART_BASE)
+BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+
+
+def reg2bin(beg, end):
+    """SAM specification 5.3: the bin of [beg, end)."""
+    end -= 1
+    for shift, first in ((14, 4681), (17, 585), (20, 73), (23, 9), (26, 1)):
+        if beg >> shift == end >> shift:
+            return first + (beg >> shift)
+    return 0
+
+
+def hp_tag(hp):
+    """The HP tag in the smallest integer type that holds it, htslib's order: C, S, I from 0 up, c, s, i below."""
+    hp = int(hp)
+    if hp >= 0:
+        typ, fmt = ("C", "<B") if hp <= 0xFF else ("S", "<H") if hp <= 0xFFFF else ("I", "<I")
+    else:
+        typ, fmt = ("c", "<b") if hp >= -128 else ("s", "<h") if hp >= -32768 else ("i", "<i")
+    return b"HP" + typ.encode() + struct.pack(fmt, hp)
+
+
+def bam_record(rd, final, references=None):
+    """BAM record (with its block_size word) of one get_read_data tuple with its final CIGAR: what sam_line says, in
+    binary -- the statement npore_bam_format_bam and the device path are tested against.  references: the header's
+    contig names (refID = the contig's place among them; 0 without)."""
+    import re
+    read_id, flag, ref_name, start, mapq, _cig, stop, sseq, quals, _ref, hap = rd
+    ref_id = list(references).index(ref_name) if references is not None else 0
+    reflen = stop - start
+    name = read_id.encode() + b"\0"
+    cig = [(int(n), "MIDNSHP=X".index(op)) for n, op in re.findall(r"(\d+)([MIDNSHP=X])", final)]
+    code = {c: i for i, c in enumerate(_SEQ16)}
+    nib = [code[c] for c in sseq] + ([0] if len(sseq) & 1 else [])
+    packed = bytes((nib[k] << 4) | nib[k + 1] for k in range(0, len(nib), 2))
+    qual = bytes([0xFF]) * len(sseq) if quals == "*" else bytes(ord(c) - 33 for c in quals)
+    body = (struct.pack("<iiBBHHHiiii", ref_id, start, len(name), mapq, reg2bin(start, start + max(1, reflen)), len(cig), flag,
+                        len(sseq), -1, -1, reflen) + name + b"".join(struct.pack("<I", (n << 4) | op) for n, op in cig) +
+            packed + qual + hp_tag(hap))
+    return struct.pack("<i", len(body)) + body
+
+
+def bgzf_stored(data):
+    """`data` as BGZF members with stored deflate blocks, cut every BGZF_STORED_PAYLOAD bytes."""
+    out = []
+    for p in range(0, len(data), BGZF_STORED_PAYLOAD):
+        chunk = bytes(data[p:p + BGZF_STORED_PAYLOAD])
+        n = len(chunk)
+        out.append(struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 0xFF, 6, 66, 67, 2, n + 30) +
+                   struct.pack("<BHH", 1, n, n ^ 0xFFFF) + chunk + struct.pack("<II", zlib.crc32(chunk), n))
+    return b"".join(out)
+
+
+def bam_header_bytes(text, references, lengths):
+    out = bytearray(b"BAM\1" + struct.pack("<i", len(text.encode())) + text.encode() + struct.pack("<i", len(references)))
+    for n, l in zip(references, lengths):
+        out += struct.pack("<i", len(n) + 1) + n.encode() + b"\0" + struct.pack("<i", l)
+    return bytes(out)
+
+
+def create_bam_header(outfile, bam):
+    """create_header for a BAM: the same text and the binary reference list, in BGZF members of their own; truncates."""
+    if os.path.dirname(outfile):
+        os.makedirs(os.path.dirname(outfile), exist_ok=True)
+    with open(outfile, "wb") as fh:
+        fh.write(bgzf_stored(bam_header_bytes(header_text(bam), bam.references, bam.lengths)))
+
+
+NOT_SORTED_MSG = "    (the records did not go out in coordinate order: no .bai index is written)"
+
+
+class BamRecordWriter:
+    """Pure-Python twin of the library's BgzfStoredWriter: record bytes appended to `path` behind what lies there (the
+    header's members), the stream cut every BGZF_STORED_PAYLOAD bytes whatever the batches were; close() writes the last
+    member, the EOF member and -- when the records came in coordinate order -- `bai` (write_bai with its bins).  Whole
+    files only: --python_io runs in one process."""
+
+    def __init__(self, path, bai=None):
+        self.path, self.bai = path, bai
+        self.fh = open(path, "ab")
+        self.carry = b""
+        self.sorted, self.last = True, (-1, -1)
+        self.n_records = 0
+
+    def add(self, records):
+        for rec in records:
+            key = struct.unpack_from("<ii", rec, 4)
+            if key < self.last:
+                self.sorted = False
+            self.last = key
+            self.n_records += 1
+        data = self.carry + b"".join(records)
+        whole = len(data) - len(data) % BGZF_STORED_PAYLOAD
+        self.fh.write(bgzf_stored(data[:whole]))
+        self.carry = data[whole:]
+
+    def close(self):
+        """Returns True when the index was written (or none was asked for)."""
+        self.fh.write(bgzf_stored(self.carry))
+        self.fh.write(BGZF_EOF)
+        self.fh.close()
+        if self.bai and self.sorted:
+            write_bai(self.path, self.bai, bins=True)
+        elif self.bai:
+            if os.path.exists(self.bai):
+                os.remove(self.bai)
+            print(NOT_SORTED_MSG)
+        return self.sorted or not self.bai
+
+
+def realign_reads(ctx, read_data, out_sam, r=30, max_b_rows=20000, bam_writer=None, references=None):
+    """Batched realign_read (src/bam.pyx:51-84): align on the GPU, standardise, append SAM lines -- or, with a
+    BamRecordWriter, hand it the reads' BAM records (out_sam is not touched then).
     Returns the number of reads written."""
     read_data = list(read_data)
     if not read_data:
@@ -245,15 +362,20 @@ def realign_reads(ctx, read_data, out_sam, r=30, max_b_rows=20000):
         seqs.append(bases_to_int(rd[7]))
     alns, status = ctx.align_batch(refs, seqs, cigs, r=r, max_b_rows=max_b_rows, return_status=True)
     finals = standardize_batch(alns, refs, seqs)          # src/bam.pyx:65-78, C++ glue in the library
-    with open(out_sam, "a") as fh:
-        for rd, final, st in zip(read_data, finals, status):
-            read_id, flag, ref_name, start, mapq, _cig, stop, sseq, quals, _ref, hap = rd
-            if st & 32:
-                print(f"\nERROR: read '{read_id}': CIGAR does not match sequence lengths; skipped.")
-                continue
-            if st:
-                print(f"\nERROR: inconsistent traceback for read '{read_id}' (status {int(st)})")   # src/aln.pyx:689-716
-            fh.write(sam_line(rd, final))
+    lines = []
+    for rd, final, st in zip(read_data, finals, status):
+        read_id = rd[0]
+        if st & 32:
+            print(f"\nERROR: read '{read_id}': CIGAR does not match sequence lengths; skipped.")
+            continue
+        if st:
+            print(f"\nERROR: inconsistent traceback for read '{read_id}' (status {int(st)})")   # src/aln.pyx:689-716
+        lines.append(sam_line(rd, final) if bam_writer is None else bam_record(rd, final, references))
+    if bam_writer is not None:
+        bam_writer.add(lines)
+    else:
+        with open(out_sam, "a") as fh:
+            fh.write("".join(lines))
     return len(read_data)
 
 
@@ -596,6 +718,59 @@ class NativeBam:
                                                    fl.ctypes.data, st.ctypes.data, threads, C.byref(sam), C.byref(sam_len)))
         return C.string_at(sam.value, sam_len.value).decode() if sam_len.value else ""
 
+    def format_bam(self, idx, finals, status, threads=0):
+        """BAM records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam)."""
+        import ctypes as C
+        idx = np.ascontiguousarray(idx, np.int64)
+        n = len(idx)
+        fb = [f.encode() for f in finals]
+        fo = np.zeros(n + 1, np.int64)
+        np.cumsum([len(f) for f in fb], out=fo[1:])
+        fl = np.diff(fo)
+        buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
+        st = np.ascontiguousarray(status, np.int32)
+        recs, recs_len = C.c_void_p(), C.c_int64()
+        self._check(self._lib.npore_bam_format_bam(self.handle, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data,
+                                                   fl.ctypes.data, st.ctypes.data, threads, C.byref(recs), C.byref(recs_len)))
+        return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
+
+    def set_output(self, out_format="sam", bai=None, eof=True):
+        """What the NEXT realign_file / realign_sequential / write_file on this handle appends to its output path
+        (npore_bam_set_output; the setting holds for that one run): "sam", or "bam" -- records in stored BGZF members behind
+        what lies in the file (the header's members: create_bam_header) and `bai` written when the records went out in
+        coordinate order.  eof: the run ends the file (the EOF member); False: it writes one rank's PART -- no EOF member,
+        and `bai` is a sidecar whose offsets count from PART_BASE (dist.gather_bam_parts shifts and merges them)."""
+        flags = 0 if out_format != "bam" else 1 if eof else 2       # NPORE_OUT_EOF / NPORE_OUT_PART
+        self._check(self._lib.npore_bam_set_output(self.handle, {"sam": 0, "bam": 1}[out_format], os.fsencode(bai) if bai else None, flags))
+
+    def output_info(self):
+        """Of the last BAM-mode run: records written, bytes of the record stream, index (1 written, 0 none asked for, -1 the
+        records were not in coordinate order), size of the file."""
+        info = np.zeros(4, np.int64)
+        self._check(self._lib.npore_bam_output_info(self.handle, info.ctypes.data))
+        return dict(zip(("records", "stream_bytes", "indexed", "file_bytes"), (int(x) for x in info)))
+
+    def _after_bam_run(self, out_format):
+        if out_format == "bam" and self.output_info()["indexed"] < 0:
+            print(NOT_SORTED_MSG)
+
+    def write_file(self, idx, finals, status, out_path, batch_reads=4000, threads=0, bai=None, eof=True):
+        """The host's part of a BAM-mode run alone (npore_bam_write_file, no GPU): the selected reads with their final
+        CIGARs as records, made in batches of batch_reads and appended to out_path."""
+        idx = np.ascontiguousarray(idx, np.int64)
+        n = len(idx)
+        fb = [f.encode() for f in finals]
+        fo = np.zeros(n + 1, np.int64)
+        np.cumsum([len(f) for f in fb], out=fo[1:])
+        fl = np.ascontiguousarray(np.diff(fo))
+        buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
+        st = np.ascontiguousarray(status, np.int32)
+        self.set_output("bam", bai, eof)
+        self._check(self._lib.npore_bam_write_file(self.handle, idx.ctypes.data, n, int(batch_reads), buf.ctypes.data, fo.ctypes.data,
+                                                   fl.ctypes.data, st.ctypes.data, threads, os.fsencode(out_path)))
+        self._after_bam_run("bam")
+        return self.output_info()
+
     @staticmethod
     def bai_path(path):
         """the file's .bai index (`x.bam.bai`, or `x.bai` beside `x.bam`), or None"""
@@ -620,11 +795,12 @@ class NativeBam:
         return tuple(int(x) for x in info)
 
     def realign_sequential(self, ctx, fasta, regions, out_path, batch_reads=4000, max_reads=0, r=30, max_b_rows=20000,
-                           indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000):
+                           indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, out_format="sam", bai=None, eof=True):
         """ONE PASS over the file: inflate, filter by `regions` [(contig, start, stop)] (at most one per contig, in header
         order), batch, realign, write -- npore_bam_realign_sequential.  Returns (reads selected, [(ordinal, status)] of
         the first bad reads, (refused, inconsistent)); raises OnePassUnsupported when the regions or the file's
-        order rule the one-pass run out (the caller truncates the output and takes the indexed path)."""
+        order rule the one-pass run out (the caller truncates the output and takes the indexed path).
+        out_format / bai / eof: set_output for this run ("bam": records instead of text)."""
         ids = {n: i for i, n in enumerate(self.references)}
         rid = np.array([ids.get(c, -2) for c, _, _ in regions], np.int32)
         beg = np.array([s for _, s, _ in regions], np.int64)
@@ -634,6 +810,7 @@ class NativeBam:
         counts = np.zeros(3, np.int64)
         bad_ord, bad_st = np.zeros(max(bad_cap, 1), np.int64), np.zeros(max(bad_cap, 1), np.int32)
         fmap = self.fasta_map(fasta)
+        self.set_output(out_format, bai, eof)
         rc = self._lib.npore_bam_realign_sequential(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, len(regions), rid.ctypes.data,
                                                     beg.ctypes.data, end.ctypes.data, int(max_reads or 0), int(batch_reads), indel_start,
                                                     indel_extend, max_b_rows, r, threads, os.fsencode(out_path), counts.ctypes.data,
@@ -646,6 +823,7 @@ class NativeBam:
             if "one-pass ingest" in msg or "not sorted by reference" in msg:
                 raise OnePassUnsupported(msg)
         self._check(rc)
+        self._after_bam_run(out_format)
         nb = int(min(bad_cap, counts[1] + counts[2]))
         return int(counts[0]), list(zip(bad_ord[:nb].tolist(), bad_st[:nb].tolist())), (int(counts[1]), int(counts[2]))
 
@@ -664,15 +842,18 @@ class NativeBam:
         return (memoryview((C.c_char * sam_len.value).from_address(sam.value)) if sam_len.value else memoryview(b"")), st[:n]
 
     def realign_file(self, ctx, fasta, idx, out_sam, batch_reads=4000, r=30, max_b_rows=20000, indel_start=5.0,
-                     indel_extend=1.0, threads=0):
+                     indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True):
         """All selected reads, batch by batch, appended to out_sam by the library with packing, GPU work and
-        formatting/writing of neighbouring batches overlapped.  Returns status[n]."""
+        formatting/writing of neighbouring batches overlapped.  Returns status[n].
+        out_format / bai / eof: set_output for this run ("bam": records instead of text)."""
         idx = np.ascontiguousarray(idx, np.int64)
         st = np.zeros(max(len(idx), 1), np.int32)
         fmap = self.fasta_map(fasta)
+        self.set_output(out_format, bai, eof)
         self._check(self._lib.npore_bam_realign_file(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data,
                                                      len(idx), int(batch_reads), indel_start, indel_extend, max_b_rows, r,
                                                      threads, os.fsencode(out_sam), st.ctypes.data))
+        self._after_bam_run(out_format)
         return st[:len(idx)]
 
     def timing(self):
@@ -714,15 +895,19 @@ class NativeBam:
             atexit.register(lambda f=skip: os.path.exists(f) and os.remove(f))
 
 
-def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0):
+def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0, out_format="sam", bai=None,
+                   eof=True):
     """realign_reads() through the library; returns the number of reads handed in.  batch_reads > 0: the whole
     index list in overlapped batches written by the library itself; 0: one batch, text written here.
-    threads: host threads of the parallel host stages (0 = all cores; one process per GPU: dist.host_threads_per_rank)."""
-    if len(idx) == 0:
+    threads: host threads of the parallel host stages (0 = all cores; one process per GPU: dist.host_threads_per_rank).
+    out_format "bam" (with bai / eof: NativeBam.set_output) needs batch_reads > 0: the library writes the file."""
+    if out_format == "bam" and batch_reads <= 0:
+        raise ValueError("BAM output is written by the library's file pipeline: batch_reads must be positive")
+    if len(idx) == 0 and out_format != "bam":
         return 0
     if batch_reads > 0:
         text, status = None, bam.realign_file(ctx, fasta, idx, out_sam, batch_reads=batch_reads, r=r, max_b_rows=max_b_rows,
-                                              threads=threads)
+                                              threads=threads, out_format=out_format, bai=bai, eof=eof)
     else:
         text, status = bam.realign_batch(ctx, fasta, idx, r=r, max_b_rows=max_b_rows, threads=threads)
     bad = np.nonzero(status)[0]
@@ -918,10 +1103,11 @@ def get_confusion_matrices():
     return total
 
 
-def write_bai(bam_path, bai_path=None):
-    """A .bai for a BAM file (tests / benchmarks; `samtools index` makes the real ones): the LINEAR index only -- per
+def write_bai(bam_path, bai_path=None, bins=False):
+    """A .bai for a BAM file (tests / benchmarks; `samtools index` makes the real ones): the LINEAR index -- per
     reference and 16 kb window the virtual offset (block offset << 16 | offset in the block) of the first record that
-    overlaps the window, SAM specification 5.2 -- with no bins, which is all npore_bam_set_share reads."""
+    overlaps the window, SAM specification 5.2 -- which is all npore_bam_set_share reads; no bins unless `bins`: then
+    every bin with its chunks, neighbouring records of a bin merged into one (the --python_io BAM writer)."""
     raw = open(bam_path, "rb").read()
     blocks, p, u = [], 0, 0                      # (compressed offset, inflated offset) of every BGZF block
     parts = []
@@ -942,6 +1128,15 @@ def write_bai(bam_path, bai_path=None):
     for _ in range(n_ref):
         l_name, = struct.unpack_from("<i", data, q); q += 8 + l_name
     lin = [dict() for _ in range(n_ref)]
+    binned = [dict() for _ in range(n_ref)]
+    sizes = [len(x) for x in parts]
+
+    def voff_end(e):
+        """where a record ends: in the member that holds its last byte, or (that member being full) at the next one's start"""
+        k = int(np.searchsorted(starts, e - 1, side="right")) - 1
+        if e - int(starts[k]) == sizes[k] == 0xFF00 and k + 1 < len(blocks):
+            return int(coffs[k + 1]) << 16
+        return (int(coffs[k]) << 16) | (e - int(starts[k]))
     ref_len_of_op = (1, 0, 1, 1, 0, 0, 0, 1, 1)  # MIDNSHP=X consume the reference?
     while q + 4 <= len(data):
         bs, = struct.unpack_from("<i", data, q)
@@ -955,10 +1150,21 @@ def write_bai(bam_path, bai_path=None):
             end = pos + max(1, sum((c >> 4) * ref_len_of_op[c & 15] for c in cig))
             for w in range(pos >> 14, ((end - 1) >> 14) + 1):
                 lin[rid].setdefault(w, v)
+            if bins:
+                chunks = binned[rid].setdefault(reg2bin(pos, end), [])
+                ve = voff_end(q + 4 + bs)
+                if chunks and chunks[-1][1] == v:
+                    chunks[-1][1] = ve
+                else:
+                    chunks.append([v, ve])
         q += 4 + bs
     out = bytearray(b"BAI\1" + struct.pack("<i", n_ref))
-    for d in lin:
-        out += struct.pack("<i", 0)                                  # no bins
+    for d, bn in zip(lin, binned):
+        out += struct.pack("<i", len(bn))                            # (no bins unless asked for)
+        for b_id in sorted(bn):
+            out += struct.pack("<Ii", b_id, len(bn[b_id]))
+            for c0, c1 in bn[b_id]:
+                out += struct.pack("<QQ", c0, c1)
         n_intv = (max(d) + 1) if d else 0
         out += struct.pack("<i", n_intv)
         last = 0
@@ -969,6 +1175,69 @@ def write_bai(bam_path, bai_path=None):
     with open(bai_path, "wb") as fh:
         fh.write(bytes(out))
     return bai_path
+
+
+def read_bai(path):
+    """[(bins {bin: [(chunk_beg, chunk_end)]}, linear [ioffset])] per reference of a .bai file."""
+    raw = open(path, "rb").read()
+    if raw[:4] != b"BAI\1":
+        raise ValueError(f"'{path}' is not a .bai file")
+    n_ref, = struct.unpack_from("<i", raw, 4)
+    q, out = 8, []
+    for _ in range(n_ref):
+        n_bin, = struct.unpack_from("<i", raw, q); q += 4
+        bins = {}
+        for _ in range(n_bin):
+            b_id, n_chunk = struct.unpack_from("<Ii", raw, q); q += 8
+            v = struct.unpack_from(f"<{2 * n_chunk}Q", raw, q); q += 16 * n_chunk
+            bins[b_id] = list(zip(v[0::2], v[1::2]))
+        n_intv, = struct.unpack_from("<i", raw, q); q += 4
+        out.append((bins, list(struct.unpack_from(f"<{n_intv}Q", raw, q)))); q += 8 * n_intv
+    return out
+
+
+def pack_bai(refs):
+    """read_bai's list as the bytes of a .bai file."""
+    out = bytearray(b"BAI\1" + struct.pack("<i", len(refs)))
+    for bins, lin in refs:
+        out += struct.pack("<i", len(bins))
+        for b_id in sorted(bins):
+            out += struct.pack("<Ii", b_id, len(bins[b_id]))
+            for c0, c1 in bins[b_id]:
+                out += struct.pack("<QQ", c0, c1)
+        out += struct.pack("<i", len(lin)) + struct.pack(f"<{len(lin)}Q", *lin)
+    return bytes(out)
+
+
+def merge_bai_parts(parts):
+    """One index from the index sidecars of the parts of a file, [(read_bai list, where the part begins in the file)] in
+    file order: compressed offsets shifted (a sidecar counts from PART_BASE), a bin's chunk lists joined, per linear window the first
+    entry (a part's windows in front of its first record hold 0; those it filled forward lie in front of every later
+    part's records), empty windows filled forward again.  None when the parts are not in coordinate order (a later part
+    has records on an earlier reference than the part before)."""
+    n_ref = max((len(p) for p, _ in parts), default=0)
+    merged = [({}, []) for _ in range(n_ref)]
+    last_ref = -1
+    for refs, shift in parts:
+        shift -= PART_BASE
+        used = [k for k, (bins, lin) in enumerate(refs) if bins or any(lin)]
+        if used and used[0] < last_ref:
+            return None
+        if used:
+            last_ref = used[-1]
+        for k, (bins, lin) in enumerate(refs):
+            mb, ml = merged[k]
+            for b_id, chunks in bins.items():
+                mb.setdefault(b_id, []).extend((c0 + (shift << 16), c1 + (shift << 16)) for c0, c1 in chunks)
+            ml.extend([0] * (len(lin) - len(ml)))
+            for w, v in enumerate(lin):
+                if v and not ml[w]:
+                    ml[w] = v + (shift << 16)
+    for _, ml in merged:
+        last = 0
+        for w, v in enumerate(ml):
+            last = ml[w] = v or last
+    return merged
 
 
 def write_bam(path, references, records, level=6):

@@ -1,0 +1,186 @@
+// bam_emit_kernels.hpp -- the realigned reads as BAM records, built on the device (the file pipeline's BAM mode).
+//
+// bam_reader.hpp states the record and holds the host twin (bam_record_into).  Almost everything a record needs is on
+// the device already: the input record up to the end of its qualities (what unpack_records_kernel reads, uploaded a
+// little further in this mode), and the final CIGAR, which standardize_words_kernel (kernels.hpp) leaves as
+// `len << 4 | op` words in the read's slot.  Two kernels per group of reads, behind its standardisation, on the
+// traceback stream:
+//   place_bam_records_kernel  one workgroup: every kept read's size, 36 + l_read_name + 4 * n_cigar + (l_seq + 1) / 2 +
+//                             l_seq + tag, and a scan over the sizes -- the group's records lie one after the other, in
+//                             input order, behind those of the batch's groups before it (a cursor that the groups, which
+//                             follow each other on one stream, hand on);
+//   emit_bam_records_kernel   one wavefront per read: fixed fields, name, CIGAR words, the 4-bit bases from the leading
+//                             soft clip on (an odd clip moves every nibble), the quality slice, the HP tag.
+// The host then takes the batch's bytes as they lie (BgzfStoredWriter) and the records' lengths for its index.
+// Both run beside the next batch's fill kernel and keep to what the other light kernels keep to: at most
+// 64 vector registers; the placement's 2 KB of LDS are less than a fill workgroup leaves free, the assembly has none.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "unpack_kernels.hpp"
+
+namespace npore {
+
+struct BamEmitParams {
+    const uint8_t *raw;            // the group's records, block_size word first, up to the end of the qualities
+    const int64_t *raw_off;        // [n_reads + 1]
+    const int64_t *ref_off;        // [n_reads + 1]: reference length of read k = ref_off[k + 1] - ref_off[k]
+    const int64_t *seq_off;        // [n_reads + 1]: bases without the soft clips
+    const int64_t *hp;             // [n_reads] the HP tag's value (0: none)
+    const uint8_t *words;          // the slots: the final CIGAR as words (standardize_words_kernel)
+    const int64_t *words_off;      // [reads of the target + 1]
+    const int64_t *words_len;      // bytes of words per read (<= 0: none)
+    const int32_t *status;
+    int64_t read_base, n_reads;    // this group's reads within words_off / words_len / status
+    uint8_t *recs;                 // the batch's record buffer
+    int64_t cap;
+    unsigned long long *cursor;    // bytes of it in use
+    int64_t *rec_off;              // [n_reads] of this group: where the read's record begins
+    int64_t *rec_len;              // [n_reads]: its bytes (0: the read is not written; -1: no room)
+};
+
+__device__ __forceinline__ int bam_hp_bytes(int64_t hp)
+{
+    if (hp >= 0) return hp <= 0xFF ? 1 : hp <= 0xFFFF ? 2 : 4;
+    return hp >= -128 ? 1 : hp >= -32768 ? 2 : 4;
+}
+
+__device__ __forceinline__ uint32_t bam_reg2bin_dev(int64_t beg, int64_t end)      // SAM specification 5.3
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t)(4681 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t)(585 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t)(73 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t)(9 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t)(1 + (beg >> 26));
+    return 0;
+}
+
+// size of read k's record (0: not written -- NPORE_ST_BAD_INPUT, as format_sam_into leaves the line out)
+__device__ __forceinline__ int64_t bam_record_size(const BamEmitParams &p, int64_t k)
+{
+    const int64_t g = p.read_base + k;
+    if (p.status[g] & 32) return 0;
+    const uint8_t *f = p.raw + p.raw_off[k] + 4;
+    const int64_t sl = p.seq_off[k + 1] - p.seq_off[k], wl = p.words_len[g] > 0 ? p.words_len[g] : 0;
+    return 36 + (int64_t)f[8] + wl + (sl + 1) / 2 + sl + 3 + bam_hp_bytes(p.hp[k]);
+}
+
+// one workgroup of 256: every thread sizes a contiguous share of the reads; their places follow from the sums of the shares
+__global__ __launch_bounds__(256) void place_bam_records_kernel(BamEmitParams p)
+{
+    __shared__ int64_t s_sum[257];
+    const int t = threadIdx.x;
+    const int64_t n = p.n_reads, seg = (n + 255) / 256;
+    const int64_t k0 = min(n, t * seg), k1 = min(n, k0 + seg);
+    int64_t mine = 0;
+    for (int64_t k = k0; k < k1; k++) mine += bam_record_size(p, k);
+    s_sum[t + 1] = mine;
+    __syncthreads();
+    if (t == 0) {
+        s_sum[0] = (int64_t)*p.cursor;
+        for (int q = 1; q <= 256; q++) s_sum[q] += s_sum[q - 1];
+        *p.cursor = (unsigned long long)s_sum[256];
+    }
+    __syncthreads();
+    int64_t at = s_sum[t];
+    for (int64_t k = k0; k < k1; k++) {
+        const int64_t sz = bam_record_size(p, k);
+        p.rec_off[k] = at;
+        p.rec_len[k] = at + sz <= p.cap ? sz : -1;
+        at += sz;
+    }
+}
+
+// dst[j] = src[j] (NIB == 0) or the bytes one nibble further on, src[j] << 4 | src[j + 1] >> 4 (NIB == 1), j in [0, n),
+// by the 64 lanes of a wavefront: four bytes per store where dst is aligned, each from two aligned words of the source;
+// bytes in front of the first aligned word and behind the last whole one singly.  NIB == 1 reads src[n]; both sides read
+// whole words around [src, src + n + NIB): the buffers they lie in end 64 bytes behind their last record.
+// clear_low: the low nibble of the last byte is 0 (an odd number of bases).
+template <int NIB>
+__device__ __forceinline__ void wave_copy(uint8_t *dst, const uint8_t *src, int64_t n, bool clear_low, int lane)
+{
+    auto one = [&](int64_t j) {
+        uint32_t v = NIB ? ((uint32_t)src[j] << 4 | (uint32_t)src[j + 1] >> 4) : src[j];
+        if (clear_low && j == n - 1) v &= 0xF0u;
+        dst[j] = (uint8_t)v;
+    };
+    const int64_t head = min(n, (int64_t)((4 - ((uintptr_t)dst & 3)) & 3));
+    const int64_t n_words = (n - head) >> 2, tail = head + 4 * n_words;
+    if (lane < head) one(lane);
+    if (lane >= 60 && tail + (lane - 60) < n) one(tail + (lane - 60));
+    const uint8_t *s0 = src + head;
+    const int sa = (int)((uintptr_t)s0 & 3);
+    const uint32_t *sw = reinterpret_cast<const uint32_t *>(s0 - sa);
+    uint32_t *dw = reinterpret_cast<uint32_t *>(dst + head);
+    for (int64_t w = lane; w < n_words; w += 64) {
+        const uint64_t v = ((uint64_t)sw[w + 1] << 32 | sw[w]) >> (8 * sa);        // bytes 4w ... 4w + 4 of s0
+        uint32_t o;
+        if (NIB) o = ((uint32_t)v & 0x0F0F0F0Fu) << 4 | ((uint32_t)(v >> 8) >> 4 & 0x0F0F0F0Fu);
+        else o = (uint32_t)v;
+        if (clear_low && head + 4 * w + 4 == n) o &= 0xF0FFFFFFu;
+        dw[w] = o;
+    }
+}
+
+// one wavefront per read
+__global__ __launch_bounds__(64) void emit_bam_records_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    const int64_t size = p.rec_len[k];
+    if (size <= 0) return;
+    const int64_t g = p.read_base + k;
+    const uint8_t *f = p.raw + p.raw_off[k] + 4;                 // the fixed fields (hostio.hpp RecView)
+    const int32_t pos = (int32_t)ld32(f + 4);
+    const int l_rn = f[8], nc = (int)ld16(f + 12);
+    const int64_t l_seq = (int32_t)ld32(f + 16);
+    const uint8_t *cg = f + 32 + l_rn, *sq = cg + 4 * (size_t)nc, *ql = sq + (l_seq + 1) / 2;
+    auto op_of = [&](int c) { return ld32(cg + 4 * (size_t)c); };
+    int64_t lead = 0;                                            // (hostio.hpp rec_clips)
+    if (nc >= 1 && (op_of(0) & 15u) == 4) lead = op_of(0) >> 4;
+    if (nc > 1 && (op_of(0) & 15u) == 5 && (op_of(1) & 15u) == 4) lead = op_of(1) >> 4;
+    const int64_t sl = p.seq_off[k + 1] - p.seq_off[k], reflen = p.ref_off[k + 1] - p.ref_off[k];
+    const int64_t wl = p.words_len[g] > 0 ? p.words_len[g] : 0, nb = (sl + 1) / 2;
+    const int64_t hp = p.hp[k];
+    const int hb = bam_hp_bytes(hp);
+    uint8_t *o = p.recs + p.rec_off[k];
+    if (lane < 9) {                                              // block_size and the fixed fields, a word per lane
+        uint32_t w = 0xFFFFFFFFu;                                // (next_refID, next_pos)
+        switch (lane) {
+            case 0: w = (uint32_t)(size - 4); break;
+            case 1: w = ld32(f); break;
+            case 2: w = (uint32_t)pos; break;
+            case 3: w = (uint32_t)l_rn | (uint32_t)f[9] << 8 | bam_reg2bin_dev(pos, (int64_t)pos + max((int64_t)1, reflen)) << 16; break;
+            case 4: w = (uint32_t)(wl >> 2) | ld16(f + 14) << 16; break;
+            case 5: w = (uint32_t)sl; break;
+            case 8: w = (uint32_t)reflen; break;
+            default: break;
+        }
+        uint8_t *q = o + 4 * lane;
+        q[0] = (uint8_t)w; q[1] = (uint8_t)(w >> 8); q[2] = (uint8_t)(w >> 16); q[3] = (uint8_t)(w >> 24);
+    }
+    o += 36;
+    for (int j = lane; j < l_rn; j += 64) o[j] = f[32 + j];
+    o += l_rn;
+    wave_copy<0>(o, p.words + p.words_off[g], wl, false, lane);
+    o += wl;
+    if (sl > 0) {
+        if (lead & 1) wave_copy<1>(o, sq + (lead >> 1), nb, (sl & 1) != 0, lane);
+        else wave_copy<0>(o, sq + (lead >> 1), nb, (sl & 1) != 0, lane);
+        o += nb;
+        if (ql[0] == 0xFF) for (int64_t j = lane; j < sl; j += 64) o[j] = 0xFF;
+        else wave_copy<0>(o, ql + lead, sl, false, lane);
+        o += sl;
+    }
+    if (lane == 0) {
+        o[0] = 'H'; o[1] = 'P';
+        o[2] = (uint8_t)(hp >= 0 ? (hb == 1 ? 'C' : hb == 2 ? 'S' : 'I') : (hb == 1 ? 'c' : hb == 2 ? 's' : 'i'));
+        const uint32_t v = (uint32_t)(int32_t)hp;
+        for (int q = 0; q < hb; q++) o[3 + q] = (uint8_t)(v >> (8 * q));
+    }
+}
+
+}  // namespace npore

@@ -7,8 +7,12 @@
 #include "../../include/npore_amd.h"
 #include "hostio.hpp"
 
+#include <sys/uio.h>
+
+#include <cerrno>
 #include <condition_variable>
 #include <deque>
+#include <map>
 #if defined(__x86_64__)
 #include <immintrin.h>
 #endif
@@ -616,6 +620,341 @@ inline int format_sam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     *sam_len = off[(size_t)n];
     return NPORE_OK;
 }
+
+// ---- BAM out: records and file, stated once -----------------------------------------------------------------------
+// RECORD.  One per read that format_sam_into would write (reads with NPORE_ST_BAD_INPUT are left out), carrying what
+// the SAM line of src/bam.pyx:83 carries:
+//   block_size | refID, pos, l_read_name, mapq, bin, n_cigar_op, flag, l_seq, next_refID, next_pos, tlen | read_name\0 |
+//   CIGAR words | 4-bit bases | qualities | the HP tag
+//   - refID, pos, mapq, flag and the name are the input record's; bin = reg2bin(pos, pos + max(1, reflen)), reflen the
+//     input record's reference length;
+//   - the CIGAR words `len << 4 | op` are the final standardised CIGAR (M / I / D, no clips);
+//   - l_seq counts the bases without the soft clips; the 4-bit bases are the input's from the leading clip on (an odd
+//     clip moves every nibble), the low nibble of an odd last byte is 0; the qualities are the same slice, a read
+//     without qualities (first byte 0xFF) gets 0xFF x l_seq;
+//   - next_refID = next_pos = -1 (SAM's `*` and `0`), tlen = reflen (SAM's `stop - start`);
+//   - one tag, HP, as the smallest integer type that holds it in htslib's order: C, S, I from 0 up, c, s, i below; 0 when
+//     the input has none.
+//   A record's size is 36 + l_read_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq + 3 + {1, 2, 4}.  More than 65 535 CIGAR
+//   operations would need the CG tag: refused (NPORE_E_UNSUPPORTED).
+// FILE.  BGZF with STORED deflate members (level 0, what `samtools view -u` writes): 18 bytes of gzip header with the BC
+//   field, one stored block (01 LEN NLEN), the payload, CRC-32 and ISIZE -- payload + 31 bytes.  The header (text +
+//   reference list) lies in members of its own; the record stream is cut every 65 280 payload bytes counted from the
+//   first record of the file (or of a rank's part), whatever the batches were; the 28-byte EOF member ends the file.
+// INDEX.  <out>.bam.bai from the same pass: per reference the bins with their chunks (neighbouring records of a bin
+//   merged into one chunk), and the 16 kb linear index with empty windows filled forward -- from (refID, pos, reflen,
+//   record bytes) and the virtual offsets the framing implies.  Written only when the records came in coordinate order.
+constexpr size_t BGZF_STORED_PAYLOAD = 0xFF00, BGZF_STORED_OVERHEAD = 31;
+static const uint8_t BGZF_EOF_MEMBER[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+inline uint32_t bam_reg2bin(int64_t beg, int64_t end)      // SAM specification 5.3
+{
+    --end;
+    if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+inline int bam_hp_tag_bytes(int64_t hp)      // the value's bytes (type letter: bam_record_into)
+{
+    if (hp >= 0) return hp <= 0xFF ? 1 : hp <= 0xFFFF ? 2 : 4;
+    return hp >= -128 ? 1 : hp >= -32768 ? 2 : 4;
+}
+// operations of a collapsed CIGAR text ("12M3I..."); -1: not such a text
+inline int64_t cigar_text_ops(const char *t, int64_t n)
+{
+    int64_t ops = 0;
+    bool digits = false;
+    for (int64_t q = 0; q < n; q++) {
+        if (t[q] >= '0' && t[q] <= '9') digits = true;
+        else { if (!digits) return -1; digits = false; ops++; }
+    }
+    return digits ? -1 : ops;
+}
+// The BAM record of read `r` with its final CIGAR text: its size (dst == nullptr) or its bytes at dst; 0 = the read is
+// not written, < 0 = it cannot be (a final text that is no CIGAR, too many operations).  `meta`: what the index needs.
+inline int64_t bam_record_into(const RecView &r, const char *final_text, int64_t final_len, int32_t status, uint8_t *dst,
+                               BamRecMeta *meta = nullptr)
+{
+    if (status & NPORE_ST_BAD_INPUT) return 0;
+    int64_t lead, trail;
+    rec_clips(r, lead, trail);
+    const int64_t sl = std::max<int64_t>(0, (int64_t)r.l_seq() - lead - trail);
+    const int64_t n_cig = cigar_text_ops(final_text, final_len);
+    if (n_cig < 0 || n_cig > 0xFFFF) return -1;
+    const int64_t hp = rec_hp(r);
+    const int l_rn = r.l_read_name(), hb = bam_hp_tag_bytes(hp);
+    const int64_t size = 36 + l_rn + 4 * n_cig + (sl + 1) / 2 + sl + 3 + hb;
+    if (!dst) return size;
+    const int64_t reflen = rec_ref_len(r);
+    auto w32 = [](uint8_t *o, uint32_t v) { std::memcpy(o, &v, 4); };
+    auto w16 = [](uint8_t *o, uint16_t v) { std::memcpy(o, &v, 2); };
+    uint8_t *o = dst;
+    w32(o, (uint32_t)(size - 4));
+    w32(o + 4, (uint32_t)r.ref_id());
+    w32(o + 8, (uint32_t)r.pos());
+    o[12] = (uint8_t)l_rn;
+    o[13] = (uint8_t)r.mapq();
+    w16(o + 14, (uint16_t)bam_reg2bin(r.pos(), (int64_t)r.pos() + std::max<int64_t>(1, reflen)));
+    w16(o + 16, (uint16_t)n_cig);
+    w16(o + 18, (uint16_t)r.flag());
+    w32(o + 20, (uint32_t)sl);
+    w32(o + 24, 0xFFFFFFFFu);
+    w32(o + 28, 0xFFFFFFFFu);
+    w32(o + 32, (uint32_t)reflen);
+    o += 36;
+    std::memcpy(o, r.name(), (size_t)l_rn);
+    o += l_rn;
+    {
+        uint32_t len = 0;
+        for (int64_t q = 0; q < final_len; q++) {
+            const char c = final_text[q];
+            if (c >= '0' && c <= '9') { len = len * 10 + (uint32_t)(c - '0'); continue; }
+            const uint32_t op = c == 'M' ? 0 : c == 'I' ? 1 : c == 'D' ? 2 : c == 'N' ? 3 : c == 'S' ? 4 : c == 'H' ? 5 : c == 'P' ? 6 : c == '=' ? 7 : 8;
+            w32(o, len << 4 | op);
+            o += 4;
+            len = 0;
+        }
+    }
+    {
+        const uint8_t *sq = r.seq() + (lead >> 1);
+        const int64_t nb = (sl + 1) / 2;
+        if (!(lead & 1)) std::memcpy(o, sq, (size_t)nb);
+        else for (int64_t j = 0; j < nb; j++) o[j] = (uint8_t)(sq[j] << 4 | sq[j + 1] >> 4);      // (sq[nb] is a byte of the record: the trailing clip or the qualities)
+        if (sl & 1) o[nb - 1] &= 0xF0;
+        o += nb;
+    }
+    if (r.l_seq() == 0 || r.qual()[0] == 0xFF) std::memset(o, 0xFF, (size_t)sl);
+    else std::memcpy(o, r.qual() + lead, (size_t)sl);
+    o += sl;
+    o[0] = 'H'; o[1] = 'P';
+    o[2] = (uint8_t)(hp >= 0 ? (hb == 1 ? 'C' : hb == 2 ? 'S' : 'I') : (hb == 1 ? 'c' : hb == 2 ? 's' : 'i'));
+    { const uint32_t v = (uint32_t)(int32_t)hp; std::memcpy(o + 3, &v, (size_t)hb); }
+    if (meta) *meta = BamRecMeta{r.ref_id(), r.pos(), reflen, size};
+    return size;
+}
+
+// format_sam_into's twin for BAM records: the kept reads' records one after the other in `out`, *out_len bytes;
+// meta (may be null): one entry per WRITTEN record, in order
+inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, const char *finals, const int64_t *final_off,
+                           const int64_t *final_len, const int32_t *status, int threads, RawBuf &out, int64_t *out_len,
+                           std::vector<BamRecMeta> *meta)
+{
+    if (!b || n < 0 || !out_len || (n > 0 && (!finals || !final_off || !final_len || !status)))
+        return fail(NPORE_E_INVALID, "bad argument");
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    std::atomic<int> bad{0};
+    parallel_for(n, threads, [&](int64_t k) {
+        const int64_t sz = bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], nullptr);
+        if (sz < 0) bad++;
+        off[(size_t)k + 1] = std::max<int64_t>(sz, 0);
+    });
+    if (bad) return fail(NPORE_E_UNSUPPORTED, "a final CIGAR is no CIGAR text or has more than 65535 operations (BAM output)");
+    for (int64_t k = 0; k < n; k++) off[(size_t)k + 1] += off[(size_t)k];
+    if (!out.ensure((size_t)off[(size_t)n] + 8)) return fail(NPORE_E_NOMEM, "BAM record buffer");
+    std::vector<BamRecMeta> all;
+    if (meta) all.resize((size_t)n);
+    parallel_for(n, threads, [&](int64_t k) {
+        if (off[(size_t)k + 1] > off[(size_t)k])
+            bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], reinterpret_cast<uint8_t *>(out.p) + off[(size_t)k],
+                            meta ? &all[(size_t)k] : nullptr);
+    });
+    if (meta) {
+        meta->clear();
+        for (int64_t k = 0; k < n; k++)
+            if (off[(size_t)k + 1] > off[(size_t)k]) meta->push_back(all[(size_t)k]);
+    }
+    *out_len = off[(size_t)n];
+    return NPORE_OK;
+}
+
+// The BAM index of a record stream written in stored members of BGZF_STORED_PAYLOAD bytes: every member but the last
+// has the same size, so a record's virtual offset follows from its offset in the stream and where the first member lies.
+class BaiBuilder {
+public:
+    void reset(size_t n_ref, uint64_t base) { refs_.assign(n_ref, Ref{}); base_ = base; sorted_ = true; last_ref_ = -1; last_pos_ = INT64_MIN; }
+    uint64_t voffset(uint64_t u) const
+    {
+        return (base_ + (u / BGZF_STORED_PAYLOAD) * (BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD)) << 16 | (u % BGZF_STORED_PAYLOAD);
+    }
+    void add(const BamRecMeta &m, uint64_t u)         // the record at stream offset u
+    {
+        if (m.ref < last_ref_ || (m.ref == last_ref_ && m.pos < last_pos_)) sorted_ = false;
+        last_ref_ = m.ref;
+        last_pos_ = m.pos;
+        if (m.ref < 0 || (size_t)m.ref >= refs_.size() || !sorted_) return;
+        Ref &r = refs_[(size_t)m.ref];
+        const uint64_t v0 = voffset(u), v1 = voffset(u + (uint64_t)m.bytes);
+        const int64_t end = (int64_t)m.pos + std::max<int64_t>(1, m.span);
+        auto &chunks = r.bins[bam_reg2bin(m.pos, end)];
+        if (!chunks.empty() && chunks.back().second == v0) chunks.back().second = v1;
+        else chunks.emplace_back(v0, v1);
+        const size_t w0 = (size_t)(std::max<int64_t>(0, m.pos) >> 14), w1 = (size_t)(std::max<int64_t>(0, end - 1) >> 14);
+        if (r.lin.size() <= w1) r.lin.resize(w1 + 1, 0);
+        for (size_t w = w0; w <= w1; w++)
+            if (!r.lin[w]) r.lin[w] = v0;
+    }
+    bool sorted() const { return sorted_; }
+    bool write(const char *path) const                // complete, or not there at all
+    {
+        std::string out("BAI\1", 4);
+        auto p32 = [&](uint32_t v) { out.append(reinterpret_cast<const char *>(&v), 4); };
+        auto p64 = [&](uint64_t v) { out.append(reinterpret_cast<const char *>(&v), 8); };
+        p32((uint32_t)refs_.size());
+        for (const Ref &r : refs_) {
+            p32((uint32_t)r.bins.size());
+            for (const auto &bn : r.bins) {
+                p32(bn.first);
+                p32((uint32_t)bn.second.size());
+                for (const auto &c : bn.second) { p64(c.first); p64(c.second); }
+            }
+            p32((uint32_t)r.lin.size());
+            uint64_t last = 0;
+            for (uint64_t v : r.lin) { if (v) last = v; p64(last); }       // (windows without a record: the entry before)
+        }
+        const std::string tmp = std::string(path) + ".tmp" + std::to_string((long long)::getpid());
+        FILE *fh = std::fopen(tmp.c_str(), "wb");
+        if (!fh) return false;
+        const bool ok = std::fwrite(out.data(), 1, out.size(), fh) == out.size();
+        if (std::fclose(fh) != 0 || !ok || std::rename(tmp.c_str(), path) != 0) { std::remove(tmp.c_str()); return false; }
+        return true;
+    }
+
+private:
+    struct Ref {
+        std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins;
+        std::vector<uint64_t> lin;
+    };
+    std::vector<Ref> refs_;
+    uint64_t base_ = 0;
+    bool sorted_ = true;
+    int32_t last_ref_ = -1;
+    int64_t last_pos_ = INT64_MIN;
+};
+
+// Appends a record stream to a file as stored BGZF members (the FILE rules above): add() takes a batch's record bytes as
+// they lie -- the members' payload goes out from the caller's buffer (writev), only the tail that does not fill a member
+// is kept for the next batch -- and does the index bookkeeping; finish() writes the last member, the EOF member if asked
+// for, and the index.  One thread at a time (the file pipeline's ordered write step).
+class BgzfStoredWriter {
+public:
+    BgzfStoredWriter() = default;
+    BgzfStoredWriter(const BgzfStoredWriter &) = delete;
+    BgzfStoredWriter &operator=(const BgzfStoredWriter &) = delete;
+    ~BgzfStoredWriter() { if (fd_ >= 0) ::close(fd_); }
+    // the file is appended to: what lies there already (the header's members) stays
+    // part: a rank's part of a file -- the index counts its offsets from a nominal first member at NPORE_PART_BASE, so
+    // that none is 0, which a .bai takes for "no record in this window"; whoever appends the part shifts them
+    int open(const char *path, size_t n_ref, const char *bai_path, bool eof_member, bool part = false)
+    {
+        fd_ = ::open(path, O_WRONLY | O_CREAT | O_APPEND, 0666);
+        if (fd_ < 0) return fail(NPORE_E_INVALID, std::string("cannot open '") + path + "' for appending");
+        struct stat st;
+        if (::fstat(fd_, &st) != 0) return fail(NPORE_E_INVALID, std::string("cannot stat '") + path + "'");
+        base_ = (uint64_t)st.st_size;
+        bai_path_ = bai_path ? bai_path : "";
+        eof_ = eof_member;
+        index_.reset(n_ref, part ? (uint64_t)NPORE_PART_BASE : base_);
+        carry_.reserve(BGZF_STORED_PAYLOAD);
+        return NPORE_OK;
+    }
+    int add(const uint8_t *bytes, int64_t len, const BamRecMeta *meta, int64_t n_rec)
+    {
+        uint64_t u = stream_;
+        for (int64_t k = 0; k < n_rec; k++) { index_.add(meta[k], u); u += (uint64_t)meta[k].bytes; }
+        if (u != stream_ + (uint64_t)len) return fail(NPORE_E_INVALID, "internal: record sizes do not add up to the batch's bytes");
+        n_rec_ += n_rec;
+        stream_ = u;
+        size_t at = 0;
+        const size_t N = (size_t)len;
+        heads_.clear();
+        iov_.clear();
+        if (!carry_.empty() && carry_.size() + N >= BGZF_STORED_PAYLOAD) {      // the member begun by the batch before
+            const size_t take = BGZF_STORED_PAYLOAD - carry_.size();
+            member(carry_.data(), carry_.size(), bytes, take);
+            at = take;
+        }
+        const bool carried = at > 0;
+        if (carry_.empty() || carried)
+            for (; N - at >= BGZF_STORED_PAYLOAD; at += BGZF_STORED_PAYLOAD) member(bytes + at, BGZF_STORED_PAYLOAD, nullptr, 0);
+        if (int rc = flush_iov()) return rc;
+        if (carried) carry_.clear();
+        carry_.insert(carry_.end(), bytes + at, bytes + N);
+        return NPORE_OK;
+    }
+    // info[4]: records, payload bytes, 1 = an index was written / 0 = none asked for / -1 = not in coordinate order, file size
+    int finish(int64_t *info)
+    {
+        heads_.clear();
+        iov_.clear();
+        if (!carry_.empty()) member(carry_.data(), carry_.size(), nullptr, 0);
+        if (eof_) { iov_.push_back(iovec{const_cast<uint8_t *>(BGZF_EOF_MEMBER), 28}); file_bytes_ += 28; }
+        if (int rc = flush_iov()) return rc;
+        carry_.clear();
+        const int rcc = ::close(fd_);
+        fd_ = -1;
+        if (rcc != 0) return fail(NPORE_E_INVALID, "close failed");
+        int indexed = 0;
+        if (!bai_path_.empty()) {
+            if (!index_.sorted()) { indexed = -1; std::remove(bai_path_.c_str()); }
+            else if (!index_.write(bai_path_.c_str())) return fail(NPORE_E_INVALID, "cannot write '" + bai_path_ + "'");
+            else indexed = 1;
+        }
+        if (info) { info[0] = n_rec_; info[1] = (int64_t)stream_; info[2] = indexed; info[3] = (int64_t)(base_ + file_bytes_); }
+        return NPORE_OK;
+    }
+
+private:
+    struct Head { uint8_t h[23], t[8]; };
+    // one member of a + b bytes (b may be empty) queued for the next writev
+    void member(const uint8_t *a, size_t na, const uint8_t *b, size_t nb)
+    {
+        const size_t n = na + nb, bsize = n + BGZF_STORED_OVERHEAD;
+        heads_.emplace_back();
+        Head &hd = heads_.back();
+        const uint8_t h[23] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, (uint8_t)((bsize - 1) & 0xFF), (uint8_t)((bsize - 1) >> 8),
+                               1, (uint8_t)(n & 0xFF), (uint8_t)(n >> 8), (uint8_t)(~n & 0xFF), (uint8_t)((~n >> 8) & 0xFF)};
+        std::memcpy(hd.h, h, 23);
+        uint32_t crc = crc32_fast(0, a, na);
+        if (nb) crc = crc32_fast(crc, b, nb);
+        const uint32_t isize = (uint32_t)n;
+        std::memcpy(hd.t, &crc, 4);
+        std::memcpy(hd.t + 4, &isize, 4);
+        // (heads_ is a deque: the addresses stay while members are added)
+        iov_.push_back(iovec{hd.h, 23});
+        iov_.push_back(iovec{const_cast<uint8_t *>(a), na});
+        if (nb) iov_.push_back(iovec{const_cast<uint8_t *>(b), nb});
+        iov_.push_back(iovec{hd.t, 8});
+        file_bytes_ += bsize;
+    }
+    int flush_iov()
+    {
+        size_t k = 0;
+        while (k < iov_.size()) {
+            const int cnt = (int)std::min<size_t>(iov_.size() - k, 512);
+            ssize_t w = ::writev(fd_, iov_.data() + k, cnt);
+            if (w < 0) { if (errno == EINTR) continue; return fail(NPORE_E_INVALID, "short write"); }
+            while (w > 0 && k < iov_.size()) {                  // (a partial write: go on behind it)
+                if ((size_t)w >= iov_[k].iov_len) { w -= (ssize_t)iov_[k].iov_len; k++; }
+                else { iov_[k].iov_base = static_cast<uint8_t *>(iov_[k].iov_base) + w; iov_[k].iov_len -= (size_t)w; w = 0; }
+            }
+            while (k < iov_.size() && iov_[k].iov_len == 0) k++;
+        }
+        iov_.clear();
+        return NPORE_OK;
+    }
+    int fd_ = -1;
+    uint64_t base_ = 0, stream_ = 0, file_bytes_ = 0;
+    int64_t n_rec_ = 0;
+    bool eof_ = false;
+    std::string bai_path_;
+    std::vector<uint8_t> carry_;             // the tail of the stream that does not fill a member yet (< 65 280 bytes)
+    std::deque<Head> heads_;
+    std::vector<iovec> iov_;
+    BaiBuilder index_;
+};
 
 // ---- the one-pass reader: the record stream walked once, front to back, no record index ------------------------
 // A stretch of the inflated stream in one buffer: d[0 .. n) lies at offset abs0 of the stream.  The buffer lives as

@@ -530,6 +530,12 @@ struct RecFetch {
     RawBuf buf;
     std::vector<const uint8_t *> ptr;
 };
+// what the BAM writer's index bookkeeping needs of one written record (bam_reader.hpp BgzfStoredWriter)
+struct BamRecMeta {
+    int32_t ref, pos;
+    int64_t span;                         // reference length
+    int64_t bytes;                        // the record with its block_size word
+};
 }  // namespace npore
 
 // ---- handles ---------------------------------------------------------------------------------
@@ -563,6 +569,12 @@ struct npore_bam {
     bool has_share = false;
     uint64_t share_begin = 0, share_end = UINT64_MAX;
     size_t share_block = 0;               // the BGZF block share_begin lies in
+    // npore_bam_set_output: what the NEXT file run on the handle writes (0 = SAM text, 1 = BAM records in stored BGZF
+    // members), where its .bai goes ("" = none), NPORE_OUT_* flags; out_info: what that run wrote (npore_bam_output_info)
+    int out_format = 0, out_flags = 0;
+    std::string out_bai;
+    int64_t out_info[4] = {0, 0, 0, 0};
+    npore::RawBuf recs;                   // record bytes of the last npore_bam_format_bam
     double stage_ms[4] = {0, 0, 0, 0};    // last npore_bam_realign_batch: pack, align, standardise, format
     double file_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last npore_bam_realign_file (npore_bam_file_timing)
 };

@@ -1413,6 +1413,20 @@ struct CigarTextSink {
     }
 };
 
+// The same runs as BAM CIGAR words `len << 4 | op` (M = 0, I = 1, D = 2: SOP_* are BAM's codes), four bytes per run in the
+// read's slot (the file pipeline's BAM mode sizes the slots for it: 4 bytes per op + 16) -- what emit_bam_records_kernel
+// (bam_emit_kernels.hpp) copies into the record.  The slots lie at multiples of 4.
+struct CigarWordSink {
+    uint8_t *o, *end;
+    bool overflow;
+    __device__ __forceinline__ void operator()(uint32_t op, int32_t n)
+    {
+        if (o + 4 > end) { overflow = true; return; }
+        if (threadIdx.x == 0) *reinterpret_cast<uint32_t *>(o) = (uint32_t)n << 4 | op;
+        o += 4;
+    }
+};
+
 // std_stream.hpp's probe by the 64 lanes of a wavefront: positions p - 1 - t, t = s + lane, 64 at a time (two coalesced
 // byte loads per lane and one ballot per round); every lane returns the same count
 struct WaveProbe {
@@ -1435,7 +1449,8 @@ struct WaveProbe {
 
 // Held to 64 vector registers: what the fill kernel's four waves leave on a SIMD (fill_kernel) -- with more it would wait
 // for a fill workgroup to leave its CU, i.e. for the end of the launch it is meant to run beside.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(32))) void standardize_kernel(StdKParams p)
+template <class Sink>
+__device__ __forceinline__ void standardize_read(const StdKParams &p)
 {
     const int64_t rd = (int64_t)blockIdx.x;
     if (rd >= p.n_reads) return;
@@ -1443,9 +1458,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(32))) void stand
     const int64_t grd = p.read_base + rd;
     if (p.out_len[grd] < 0) { if (lane == 0) p.out_len[grd] = 0; return; }
     uint8_t *start = p.out + p.out_off[grd];
-    CigarTextSink sink{start, p.out + p.out_off[grd + 1], false};
+    Sink sink{start, p.out + p.out_off[grd + 1], false};
     // (32-bit lengths and positions: a read has fewer than 2^31 ops -- run_core refuses longer ones)
-    StdStream<CigarTextSink, int32_t, WaveProbe> st(sink, p.refs + p.ref_off[rd], (int32_t)(p.ref_off[rd + 1] - p.ref_off[rd]),
+    StdStream<Sink, int32_t, WaveProbe> st(sink, p.refs + p.ref_off[rd], (int32_t)(p.ref_off[rd + 1] - p.ref_off[rd]),
                                                     p.seqs + p.seq_off[rd], (int32_t)(p.seq_off[rd + 1] - p.seq_off[rd]));
     const int c0 = uni(p.read_first_chunk[rd]), c1 = uni(p.read_first_chunk[rd + 1]);
     // the read's runs in read order (a chunk's last-recorded run first), 64 per load: lane l holds run `hi - l` of the
@@ -1487,6 +1502,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(32))) void stand
             p.out_len[grd] = (int64_t)(sink.o - start);
         }
     }
+}
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(32))) void standardize_kernel(StdKParams p)
+{
+    standardize_read<CigarTextSink>(p);
+}
+// (BAM mode of the file pipeline: out_len = 4 * the number of CIGAR operations)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(32))) void standardize_words_kernel(StdKParams p)
+{
+    standardize_read<CigarWordSink>(p);
 }
 
 // exhaustive check of div_recip on its domain: counts violations of its contract

@@ -30,6 +30,7 @@
 #include "prep_kernels.hpp"
 #include "annot_wave.hpp"
 #include "unpack_kernels.hpp"
+#include "bam_emit_kernels.hpp"
 #include "confusion_kernels.hpp"
 
 using namespace npore;
@@ -170,6 +171,17 @@ struct TextCompact {
     int64_t h_bytes;             // how much of the compact buffer's front to send with the batch's last group
 };
 
+// The file pipeline's BAM mode with the records built on the device (bam_emit_kernels.hpp): what a batch's align call needs
+// to know about it
+struct BamEmit {
+    uint8_t *d_recs;             // the batch's record buffer
+    int64_t cap;
+    unsigned long long *d_cursor;
+    const int64_t *h_hp;         // [n_reads] page-locked: the reads' HP values
+    int64_t *h_rec_len;          // [n_reads] page-locked: bytes of every read's record (0: not written)
+    unsigned long long *h_total; // page-locked: bytes of the batch's records
+};
+
 struct npore_batch_slot {
     PinnedBuf refs, seqs, cigs, alns;
     RawBuf finals, sam;
@@ -179,6 +191,11 @@ struct npore_batch_slot {
     // and its cursor there, the copied front of it and the reads' offsets here (page-locked)
     DevBuf d_ctext, d_cursor;
     PinnedBuf ctext_pin, coff_pin;
+    // BAM mode, records built on the device: the batch's record buffer there (the cursor is d_cursor) and its upper bound,
+    // the reads' HP values, and what comes back: the records' lengths, their total, the bytes
+    DevBuf d_recs;
+    int64_t rec_cap = 0;
+    PinnedBuf hp_pin, reclen_pin, total_pin, recs_pin;
     int64_t ctext_copied = 0;              // bytes of the compact buffer the batch's last group sent behind its kernels
     PinnedBuf olen_pin, st_pin;            // lengths / status bits of an ASYNCHRONOUS batch land here (page-locked: a copy into
                                            // pageable memory would make the enqueueing call wait for the whole batch)
@@ -188,6 +205,7 @@ struct npore_batch_slot {
     RecFetch rf;                 // the batch's BAM records (streamed handles: inflated for the batch)
     double t_ms[6] = {0, 0, 0, 0, 0, 0};   // npore_bam_realign_file: fetch + pack, align call, standardise, format, write, (spare)
     std::vector<int64_t> ro, so, co, oo, fo, olen, flen;
+    std::vector<BamRecMeta> meta;  // BAM output: what the index needs of every record written (sam then holds record bytes)
     int64_t sam_len = 0;
     int64_t m = 0;               // reads of the batch
     int rc = 0;
@@ -209,6 +227,7 @@ struct WorkSet {
     DevBuf in_refs, in_seqs, in_cigs, in_off, out, out_len, status;
     DevBuf in_raw;               // device pack (unpack_kernels.hpp): the group's record heads
     DevBuf coff;                 // compacted texts: where each read of the group begins in the batch's compact buffer
+    DevBuf in_hp, rec_off, rec_len;   // BAM records built on the device: the group's HP values, its records' places and sizes
     HostBuf h_off;
     hipEvent_t evc[4] = {};      // H2D start / end, D2H start / end of a staged group
     bool staged = false;
@@ -223,13 +242,14 @@ struct WorkSet {
                                         &WorkSet::hist, &WorkSet::counters, &WorkSet::tiles, &WorkSet::cwoff, &WorkSet::seqw, &WorkSet::refw,
                                         &WorkSet::refl, &WorkSet::seql, &WorkSet::tb, &WorkSet::cout_, &WorkSet::clen, &WorkSet::cstat,
                                         &WorkSet::cnruns, &WorkSet::in_refs, &WorkSet::in_seqs, &WorkSet::in_cigs, &WorkSet::in_off,
-                                        &WorkSet::out, &WorkSet::out_len, &WorkSet::status, &WorkSet::in_raw, &WorkSet::coff};
+                                        &WorkSet::out, &WorkSet::out_len, &WorkSet::status, &WorkSet::in_raw, &WorkSet::coff,
+                                        &WorkSet::in_hp, &WorkSet::rec_off, &WorkSet::rec_len};
         for (auto m : all) (this->*m).match(o.*m);
     }
     int64_t cells = 0, call_id = 0;
-    DevBuf *all[28] = {&rd_i32, &rd_i64, &steps, &inss, &descs, &sched, &hist, &counters, &tiles, &cwoff,
+    DevBuf *all[31] = {&rd_i32, &rd_i64, &steps, &inss, &descs, &sched, &hist, &counters, &tiles, &cwoff,
                        &seqw, &refw, &refl, &seql, &tb, &cout_, &clen, &cstat, &cnruns,
-                       &in_refs, &in_seqs, &in_cigs, &in_off, &out, &out_len, &status, &in_raw, &coff};
+                       &in_refs, &in_seqs, &in_cigs, &in_off, &out, &out_len, &status, &in_raw, &coff, &in_hp, &rec_off, &rec_len};
 };
 
 // Work sets of a context: group k + 1 is prepared while group k is in the fill kernel and group k - 1 in its traceback;
@@ -424,6 +444,9 @@ struct AlignArgs {
     // the file pipeline with the device glue: the texts compacted on the device, the used front of the compact buffer and
     // the reads' offsets copied instead of the slots (nullptr: the slots, as the public entry points promise)
     const TextCompact *compact = nullptr;
+    // BAM mode of the file pipeline (device pack + device glue): the final CIGARs stay on the device as words and the
+    // records are assembled there; neither the slots nor a compact buffer are copied
+    const BamEmit *bam = nullptr;
     bool staged() const { return h_out != nullptr; }
 };
 
@@ -531,6 +554,10 @@ int run_group(npore_ctx *ctx, WorkSet *w, const AlignArgs &a, int64_t g0, int64_
             HIP_TRY(hipMemcpyAsync(w->in_cigs.p, a.h_cigs + a.h_cig_off[g0], (size_t)cig_bytes, hipMemcpyHostToDevice, s));
         }
         HIP_TRY(hipMemcpyAsync(w->in_off.p, ho, (size_t)5 * (nr + 1) * 8, hipMemcpyHostToDevice, s));
+        if (a.bam) {
+            if (int rc = w->in_hp.ensure((size_t)nr * 8 + 64)) return rc;
+            HIP_TRY(hipMemcpyAsync(w->in_hp.p, a.bam->h_hp + g0, (size_t)nr * 8, hipMemcpyHostToDevice, s));
+        }
         HIP_TRY(hipEventRecord(w->evc[1], s));
         const int64_t *d_off = w->in_off.as<int64_t>();
         if (a.h_raw) {          // align()'s three inputs from the record heads (unpack_kernels.hpp), where the copies above would have put them
@@ -689,8 +716,25 @@ int run_group(npore_ctx *ctx, WorkSet *w, const AlignArgs &a, int64_t g0, int64_
         sp.status = got.d_status;
         sp.read_base = out_read_base;
         sp.n_reads = nr;
-        hipLaunchKernelGGL(standardize_kernel, dim3((unsigned)nr), dim3(64), 0, s, sp);      // one wavefront per read
-        if (a.compact) {        // the texts to the front of the batch's compact buffer (unpack_kernels.hpp)
+        if (a.bam) hipLaunchKernelGGL(standardize_words_kernel, dim3((unsigned)nr), dim3(64), 0, s, sp);
+        else hipLaunchKernelGGL(standardize_kernel, dim3((unsigned)nr), dim3(64), 0, s, sp);      // one wavefront per read
+        if (a.bam) {            // the group's records behind those of the groups before it (bam_emit_kernels.hpp)
+            if (!a.h_raw || !a.staged()) return fail(NPORE_E_INVALID, "internal: BAM records on the device need the device pack");
+            if (int rc = w->rec_off.ensure((size_t)nr * 8 + 64)) return rc;
+            if (int rc = w->rec_len.ensure((size_t)nr * 8 + 64)) return rc;
+            if (g0 == 0) HIP_TRY(hipMemsetAsync(a.bam->d_cursor, 0, 8, s));
+            const int64_t *d_off = w->in_off.as<int64_t>();
+            BamEmitParams bp;
+            bp.raw = w->in_raw.as<uint8_t>(); bp.raw_off = d_off + 4 * (nr + 1);
+            bp.ref_off = d_off; bp.seq_off = d_off + (nr + 1);
+            bp.hp = w->in_hp.as<int64_t>();
+            bp.words = got.d_out; bp.words_off = got.d_out_off; bp.words_len = got.d_out_len; bp.status = got.d_status;
+            bp.read_base = out_read_base; bp.n_reads = nr;
+            bp.recs = a.bam->d_recs; bp.cap = a.bam->cap; bp.cursor = a.bam->d_cursor;
+            bp.rec_off = w->rec_off.as<int64_t>(); bp.rec_len = w->rec_len.as<int64_t>();
+            hipLaunchKernelGGL(place_bam_records_kernel, dim3(1), dim3(256), 0, s, bp);
+            hipLaunchKernelGGL(emit_bam_records_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
+        } else if (a.compact) {        // the texts to the front of the batch's compact buffer (unpack_kernels.hpp)
             if (int rc = w->coff.ensure((size_t)nr * 8 + 64)) return rc;
             if (g0 == 0) HIP_TRY(hipMemsetAsync(a.compact->d_cursor, 0, 8, s));
             CompactParams cp;
@@ -723,7 +767,10 @@ int run_group(npore_ctx *ctx, WorkSet *w, const AlignArgs &a, int64_t g0, int64_
     HIP_TRY(hipGetLastError());
     if (a.staged()) {                   // download the group's slice of the results behind its gather
         HIP_TRY(hipEventRecord(w->evc[2], s));
-        if (a.final_text && a.compact) {
+        if (a.final_text && a.bam) {
+            HIP_TRY(hipMemcpyAsync(a.bam->h_rec_len + g0, w->rec_len.p, (size_t)nr * 8, hipMemcpyDeviceToHost, s));
+            if (g1 == a.n_reads) HIP_TRY(hipMemcpyAsync(a.bam->h_total, a.bam->d_cursor, 8, hipMemcpyDeviceToHost, s));
+        } else if (a.final_text && a.compact) {
             HIP_TRY(hipMemcpyAsync(a.compact->h_coff + g0, w->coff.p, (size_t)nr * 8, hipMemcpyDeviceToHost, s));
             if (g1 == a.n_reads && a.compact->h_bytes > 0)       // the batch's last group: the front of the compact buffer
                 HIP_TRY(hipMemcpyAsync(a.compact->h_ctext, a.compact->d_ctext, (size_t)a.compact->h_bytes, hipMemcpyDeviceToHost, s));
@@ -1821,6 +1868,59 @@ try {
 }
 NPORE_CATCH_INT
 
+int npore_bam_format_bam(npore_bam *b, const int64_t *idx, int64_t n, const char *finals, const int64_t *final_off,
+                         const int64_t *final_len, const int32_t *status, int threads, const uint8_t **recs, int64_t *recs_len)
+try {
+    if (!pack_args_ok(b, idx, n) || !recs) return fail(NPORE_E_INVALID, "bad argument");
+    if (int rc = fetch_records(b, idx, n, threads, b->api_fetch)) return rc;
+    const int rc = format_bam_into(b, b->api_fetch, n, finals, final_off, final_len, status, threads, b->recs, recs_len, nullptr);
+    *recs = reinterpret_cast<const uint8_t *>(b->recs.p);
+    return rc;
+}
+NPORE_CATCH_INT
+
+int npore_bam_set_output(npore_bam *b, int format, const char *bai_path, int flags)
+{
+    if (!b || (format != NPORE_OUT_SAM && format != NPORE_OUT_BAM) || (flags & ~(NPORE_OUT_EOF | NPORE_OUT_PART))) return fail(NPORE_E_INVALID, "bad argument");
+    b->out_format = format;
+    b->out_bai = (format == NPORE_OUT_BAM && bai_path) ? bai_path : "";
+    b->out_flags = flags;
+    return NPORE_OK;
+}
+
+int npore_bam_output_info(const npore_bam *b, int64_t *out4)
+{
+    if (!b || !out4) return fail(NPORE_E_INVALID, "null argument");
+    for (int k = 0; k < 4; k++) out4[k] = b->out_info[k];
+    return NPORE_OK;
+}
+
+int npore_bam_write_file(npore_bam *b, const int64_t *idx, int64_t n, int64_t batch_reads, const char *finals, const int64_t *final_off,
+                         const int64_t *final_len, const int32_t *status, int threads, const char *out_path)
+try {
+    if (!pack_args_ok(b, idx, n) || !out_path || batch_reads < 1 || (n > 0 && (!finals || !final_off || !final_len || !status)))
+        return fail(NPORE_E_INVALID, "bad argument");
+    if (b->out_format != NPORE_OUT_BAM) return fail(NPORE_E_INVALID, "npore_bam_write_file writes BAM: npore_bam_set_output first");
+    BgzfStoredWriter w;
+    const std::string bai = b->out_bai;
+    const int flags = b->out_flags;
+    b->out_format = NPORE_OUT_SAM;                   // (the setting holds for one run)
+    b->out_bai.clear();
+    b->out_flags = 0;
+    std::fill(b->out_info, b->out_info + 4, 0);
+    if (int rc = w.open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0)) return rc;
+    std::vector<BamRecMeta> meta;
+    for (int64_t k0 = 0; k0 < n; k0 += batch_reads) {
+        const int64_t m = std::min(batch_reads, n - k0);
+        if (int rc = fetch_records(b, idx + k0, m, threads, b->api_fetch)) return rc;
+        int64_t len = 0;
+        if (int rc = format_bam_into(b, b->api_fetch, m, finals, final_off + k0, final_len + k0, status + k0, threads, b->recs, &len, &meta)) return rc;
+        if (int rc = w.add(reinterpret_cast<const uint8_t *>(b->recs.p), len, meta.data(), (int64_t)meta.size())) return rc;
+    }
+    return w.finish(b->out_info);
+}
+NPORE_CATCH_INT
+
 namespace {
 // pack the selected records into the slot (inputs of npore_align_batch) and size its output buffers
 // (the records are in s.rf already)
@@ -1852,8 +1952,13 @@ int slot_pack_records(const npore_bam *b, const npore_fasta *fa, const int32_t *
 // name, CIGAR words, 4-bit bases -- about half of a record; qualities and tags are not needed on the device) copied one
 // after the other into the slot's page-locked buffer; unpack_kernels.hpp does the rest per group.  Device glue only
 // (the host glue reads the base arrays).
-int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, int64_t n, int threads, npore_batch_slot &s, bool compact = false)
+// as_bam (BAM mode): each record up to the end of its QUALITIES (the tags stay on the host), the reads' HP values, slots of
+// 4 bytes per op + 16 (CIGAR words instead of text), and the bound of the batch's record bytes.
+int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, int64_t n, int threads, npore_batch_slot &s, bool compact = false,
+                  bool as_bam = false)
 {
+    if (as_bam && !s.hp_pin.ensure((size_t)n * 8 + 64)) return fail(NPORE_E_NOMEM, "batch buffers");
+    s.rec_cap = 0;
     for (auto *v : {&s.ro, &s.so, &s.co, &s.oo, &s.fo}) v->assign((size_t)n + 1, 0);
     s.rawo.assign((size_t)n + 1, 0);
     s.olen.assign((size_t)n, 0);
@@ -1864,9 +1969,14 @@ int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, 
         const int32_t rid = r.ref_id();
         const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
         if (fi < 0 || fi >= n_fasta) return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
-        s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + (int64_t)(r.qual() - r.p) + 4;
+        s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + (int64_t)((as_bam ? r.aux() : r.qual()) - r.p) + 4;
         const int64_t cap = (s.ro[(size_t)k + 1] - s.ro[(size_t)k]) + (s.so[(size_t)k + 1] - s.so[(size_t)k]);
-        s.oo[(size_t)k + 1] = s.oo[(size_t)k] + 2 * cap + 16;
+        s.oo[(size_t)k + 1] = s.oo[(size_t)k] + (as_bam ? 4 : 2) * cap + 16;
+        if (as_bam) {
+            const int64_t sl = s.so[(size_t)k + 1] - s.so[(size_t)k];
+            reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = rec_hp(r);
+            s.rec_cap += 36 + r.l_read_name() + 4 * cap + 16 + (sl + 1) / 2 + sl + 7;
+        }
     }
     if (!s.raw.ensure((size_t)s.rawo[(size_t)n] + 64) || (!compact && !s.alns.ensure((size_t)s.oo[(size_t)n] + 64))) return fail(NPORE_E_NOMEM, "batch buffers");
     const int64_t per = 16;
@@ -1896,8 +2006,13 @@ int slot_align(npore_ctx *ctx, int64_t n, float indel_start, float indel_extend,
 }
 // realign_read's glue (src/bam.pyx:65-78) and the SAM lines; reads refused by align() have no string and get an empty CIGAR
 int slot_post(const npore_bam *b, const int64_t *idx, int64_t n, const int32_t *status, int threads, npore_batch_slot &s,
-              double *ms_std = nullptr, bool device_glue = false)
+              double *ms_std = nullptr, bool device_glue = false, bool as_bam = false)
 {
+    // SAM text, or (a BAM-mode file run) the same reads' records
+    auto format_into = [&](const char *finals, const int64_t *final_off) {
+        return as_bam ? format_bam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len, &s.meta)
+                      : format_sam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len);
+    };
     if (device_glue) {          // the slots hold the final CIGAR text already (standardize_kernel)
         if (ms_std) *ms_std = 0.0;
         for (int64_t k = 0; k < n; k++) s.flen[(size_t)k] = s.olen[(size_t)k] > 0 ? s.olen[(size_t)k] : 0;
@@ -1913,9 +2028,9 @@ int slot_post(const npore_bam *b, const int64_t *idx, int64_t n, const int32_t *
                 HIP_TRY(hipMemcpy(s.ctext_pin.p, s.d_ctext.p, (size_t)extent, hipMemcpyDeviceToHost));
                 s.ctext_copied = extent;
             }
-            return format_sam_into(b, s.rf, n, s.ctext_pin.p, coff, s.flen.data(), status, threads, s.sam, &s.sam_len);
+            return format_into(s.ctext_pin.p, coff);
         }
-        return format_sam_into(b, s.rf, n, s.alns.p, s.oo.data(), s.flen.data(), status, threads, s.sam, &s.sam_len);
+        return format_into(s.alns.p, s.oo.data());
     }
     const auto t0 = std::chrono::steady_clock::now();
     const uint8_t *refs = reinterpret_cast<const uint8_t *>(s.refs.p), *seqs = reinterpret_cast<const uint8_t *>(s.seqs.p);
@@ -1927,7 +2042,31 @@ int slot_post(const npore_bam *b, const int64_t *idx, int64_t n, const int32_t *
     });
     if (ms_std) *ms_std = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     (void)idx;
-    return format_sam_into(b, s.rf, n, s.finals.p, s.fo.data(), s.flen.data(), status, threads, s.sam, &s.sam_len);
+    return format_into(s.finals.p, s.fo.data());
+}
+// BAM mode, records built on the device: nothing is formatted here -- the batch's bytes as they lie there, into page-locked
+// memory, and from the records' lengths what the writer's index needs (reference, position and span are the input record's)
+int slot_fetch_records(int64_t n, const int32_t *status, npore_batch_slot &s)
+{
+    const int64_t total = (int64_t)*reinterpret_cast<const unsigned long long *>(s.total_pin.p);
+    const int64_t *len = reinterpret_cast<const int64_t *>(s.reclen_pin.p);
+    if (total < 0 || total > s.rec_cap) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
+    s.meta.clear();
+    int64_t sum = 0;
+    for (int64_t k = 0; k < n; k++) {
+        if (len[k] < 0) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
+        if (s.olen[(size_t)k] > 4 * 0xFFFF) return fail(NPORE_E_UNSUPPORTED, "a final CIGAR has more than 65535 operations (BAM output)");
+        if ((len[k] == 0) != ((status[k] & NPORE_ST_BAD_INPUT) != 0)) return fail(NPORE_E_HIP, "internal: BAM records and status bits disagree");
+        if (len[k] == 0) continue;
+        const RecView r = rec_of(s.rf, k);
+        s.meta.push_back(BamRecMeta{r.ref_id(), r.pos(), s.ro[(size_t)k + 1] - s.ro[(size_t)k], len[k]});
+        sum += len[k];
+    }
+    if (sum != total) return fail(NPORE_E_HIP, "internal: BAM record sizes do not add up");
+    if (!s.recs_pin.ensure((size_t)total + 64)) return fail(NPORE_E_NOMEM, "batch buffers");
+    if (total > 0) HIP_TRY(hipMemcpy(s.recs_pin.p, s.d_recs.p, (size_t)total, hipMemcpyDeviceToHost));
+    s.sam_len = total;
+    return NPORE_OK;
 }
 }  // namespace
 
@@ -1971,9 +2110,42 @@ namespace {
 //   acquire(k, slot) -> the records of batch k in slot.rf: their number, 0 = no further batch, < 0 = failure (fail() called);
 //     serial_acquire: called in batch order (the one-pass reader), else from the packing threads as they come;
 //   on_status(k, m, status bits): in batch order, in front of the batch's text.
+// Where a file run's output goes: the SAM text's FILE, or (npore_bam_set_output, which holds for one run) the BAM writer
+struct RunOutput {
+    FILE *fh = nullptr;
+    std::unique_ptr<BgzfStoredWriter> bw;
+    npore_bam *b = nullptr;
+    int open(npore_bam *bam, const char *out_path)
+    {
+        b = bam;
+        const int format = b->out_format, flags = b->out_flags;
+        const std::string bai = b->out_bai;
+        b->out_format = NPORE_OUT_SAM;
+        b->out_flags = 0;
+        b->out_bai.clear();
+        std::fill(b->out_info, b->out_info + 4, 0);
+        if (format == NPORE_OUT_BAM) {
+            bw.reset(new BgzfStoredWriter());
+            return bw->open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0);
+        }
+        fh = std::fopen(out_path, "ab");
+        return fh ? NPORE_OK : fail(NPORE_E_INVALID, std::string("cannot open '") + out_path + "' for appending");
+    }
+    int close(int rc)
+    {
+        if (fh && std::fclose(fh) != 0 && rc == NPORE_OK) rc = fail(NPORE_E_INVALID, "close failed");
+        fh = nullptr;
+        if (bw && rc == NPORE_OK) rc = bw->finish(b->out_info);
+        bw.reset();
+        return rc;
+    }
+    ~RunOutput() { if (fh) std::fclose(fh); }
+};
+
 template <class Acquire, class OnStatus>
 int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, float indel_start, float indel_extend,
-                  int max_b_rows, int r, int threads, FILE *fh, bool serial_acquire, Acquire acquire, OnStatus on_status)
+                  int max_b_rows, int r, int threads, FILE *fh, bool serial_acquire, Acquire acquire, OnStatus on_status,
+                  BgzfStoredWriter *bw = nullptr)
 {
     // (run_core refuses them too, but on a worker thread: refuse here, before a batch is read or a record written)
     if (!std::isfinite(indel_start) || !std::isfinite(indel_extend))
@@ -1998,6 +2170,9 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
     if (dpack)
         if (int rc = device_fasta(ctx, b, fa, fasta_of_ref)) return rc;
     const int n_fasta = (int)fa->names.size();
+    // BAM mode: the records are built on the device where the default pipeline runs (device pack + device glue:
+    // bam_emit_kernels.hpp); with the host glue or the host pack the host twin makes them (format_bam_into)
+    const bool dev_bam = bw != nullptr && dpack;
     // NPORE_PIPE_TRACE=1: one line per batch and stage boundary on stderr (ms since the call began)
     const bool trace = std::getenv("NPORE_PIPE_TRACE") != nullptr;
     std::mutex trace_m;
@@ -2038,7 +2213,7 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
                 if (serial_acquire) { bump(acquired); bumped = true; }
                 s.m = m > 0 ? m : 0;
                 if (m < 0) s.rc = (int)m;
-                else if (m > 0) s.rc = dpack ? slot_pack_raw(b, fasta_of_ref, n_fasta, m, pack_threads, s, glue)
+                else if (m > 0) s.rc = dpack ? slot_pack_raw(b, fasta_of_ref, n_fasta, m, pack_threads, s, glue, dev_bam)
                                              : slot_pack_records(b, fa, fasta_of_ref, m, pack_threads, s, glue, glue);
                 if (s.rc) s.err = npore_last_error();
             } catch (const std::exception &e) {
@@ -2067,7 +2242,7 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             t0 = std::chrono::steady_clock::now();
             double ms_std = 0.0;
             try {
-                t.rc = slot_post(b, nullptr, m, st, post_threads, t, &ms_std, glue);
+                t.rc = dev_bam ? slot_fetch_records(m, st, t) : slot_post(b, nullptr, m, st, post_threads, t, &ms_std, glue, bw != nullptr);
             } catch (const std::exception &e) {
                 fail(NPORE_E_NOMEM, std::string("SAM text of a batch: ") + e.what());
                 t.rc = NPORE_E_NOMEM;
@@ -2080,7 +2255,10 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             wait_for(written, k);                              // records in input order
             on_status(k, m, st);
             t0 = std::chrono::steady_clock::now();
-            if (std::fwrite(t.sam.p, 1, (size_t)t.sam_len, fh) != (size_t)t.sam_len) { t.rc = NPORE_E_INVALID; t.err = "short write"; }
+            if (bw) {
+                const char *bytes = dev_bam ? t.recs_pin.p : t.sam.p;
+                if (bw->add(reinterpret_cast<const uint8_t *>(bytes), t.sam_len, t.meta.data(), (int64_t)t.meta.size())) { t.rc = NPORE_E_INVALID; t.err = npore_last_error(); }
+            } else if (std::fwrite(t.sam.p, 1, (size_t)t.sam_len, fh) != (size_t)t.sam_len) { t.rc = NPORE_E_INVALID; t.err = "short write"; }
             t.t_ms[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             mark("written", k);
             t.keep.clear();
@@ -2104,8 +2282,14 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
         // device glue: the texts come back compacted -- the front of the batch's compact buffer (0.5 bytes per base are
         // sent with the batch's last group; what usual reads need is a quarter of that) and the reads' offsets
         TextCompact cmp{};
+        BamEmit emit{};
         s.ctext_copied = 0;
-        if (glue) {
+        if (dev_bam) {
+            if (s.d_recs.ensure((size_t)s.rec_cap + 64) || s.d_cursor.ensure(64) || !s.ctext_pin.ensure(64) || !s.reclen_pin.ensure((size_t)m * 8 + 64) ||
+                !s.total_pin.ensure(64)) { rc = NPORE_E_NOMEM; err = "batch buffers"; break; }
+            emit = BamEmit{s.d_recs.as<uint8_t>(), s.rec_cap, s.d_cursor.as<unsigned long long>(), reinterpret_cast<const int64_t *>(s.hp_pin.p),
+                           reinterpret_cast<int64_t *>(s.reclen_pin.p), reinterpret_cast<unsigned long long *>(s.total_pin.p)};
+        } else if (glue) {
             // (a text takes whole 16-byte granules of the compact buffer: at most 15 bytes more than its slot)
             const int64_t slots = s.oo[(size_t)m] + 16 * m, bound = std::min(slots, slots / 4 + 4096);
             if (s.d_ctext.ensure((size_t)slots + 64) || s.d_cursor.ensure(64) || !s.ctext_pin.ensure((size_t)bound + 64) ||
@@ -2124,7 +2308,8 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             a.h_refs = reinterpret_cast<uint8_t *>(s.refs.p); a.h_seqs = reinterpret_cast<uint8_t *>(s.seqs.p); a.h_cigs = s.cigs.p;
         }
         a.final_text = glue;
-        if (glue) a.compact = &cmp;                                  // (read while the groups are enqueued, not behind the call)
+        if (dev_bam) a.bam = &emit;
+        else if (glue) a.compact = &cmp;                             // (read while the groups are enqueued, not behind the call)
         s.rc = align_batch(ctx, a, false);
         if (s.rc) { rc = s.rc; err = npore_last_error(); s.err = err; break; }
         if (hipEventRecord(s.done, ctx->s_post) != hipSuccess) { rc = NPORE_E_HIP; err = "hipEventRecord"; s.rc = rc; s.err = err; break; }
@@ -2178,19 +2363,19 @@ try {
     if (!ctx || !b || !fa || !fasta_of_ref || !out_path || (n > 0 && (!idx || !status)) || batch_reads < 1) return fail(NPORE_E_INVALID, "bad argument");
     if (!pack_args_ok(b, idx, n)) return fail(NPORE_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(ctx->device));
-    FILE *fh = std::fopen(out_path, "ab");
-    if (!fh) return fail(NPORE_E_INVALID, std::string("cannot open '") + out_path + "' for appending");
+    RunOutput out;
+    if (int rco = out.open(b, out_path)) return rco;
     const int64_t nb = (n + batch_reads - 1) / batch_reads;
-    int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, fh, false,
+    int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, out.fh, false,
                            [&](int64_t k, npore_batch_slot &s) -> int64_t {
                                if (k >= nb) return 0;
                                const int64_t m = std::min(batch_reads, n - k * batch_reads);
                                const int rcf = fetch_records(b, idx + k * batch_reads, m, threads, s.rf);
                                return rcf ? (int64_t)rcf : m;
                            },
-                           [&](int64_t k, int64_t m, const int32_t *st) { std::memcpy(status + k * batch_reads, st, (size_t)m * 4); });
-    if (std::fclose(fh) != 0 && rc == NPORE_OK) rc = fail(NPORE_E_INVALID, "close failed");
-    return rc;
+                           [&](int64_t k, int64_t m, const int32_t *st) { std::memcpy(status + k * batch_reads, st, (size_t)m * 4); },
+                           out.bw.get());
+    return out.close(rc);
 }
 NPORE_CATCH_INT
 
@@ -2206,8 +2391,8 @@ try {
     counts[0] = counts[1] = counts[2] = 0;
     HIP_TRY(hipSetDevice(ctx->device));
     BamRecordWalker walker(b, n_regions, ref_id, start, stop, max_reads, threads);
-    FILE *fh = std::fopen(out_path, "ab");
-    if (!fh) return fail(NPORE_E_INVALID, std::string("cannot open '") + out_path + "' for appending");
+    RunOutput out;
+    if (int rco = out.open(b, out_path)) return rco;
     int64_t n_bad = 0, ordinal0 = 0;
     auto on_status = [&](int64_t, int64_t m, const int32_t *st) {
         for (int64_t i = 0; i < m; i++)
@@ -2218,11 +2403,11 @@ try {
             }
         ordinal0 += m;
     };
-    int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, fh, true,
-                           [&](int64_t, npore_batch_slot &s) { return walker.next_batch(s.rf, s.keep, batch_reads); }, on_status);
+    int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, out.fh, true,
+                           [&](int64_t, npore_batch_slot &s) { return walker.next_batch(s.rf, s.keep, batch_reads); }, on_status,
+                           out.bw.get());
     counts[0] = ordinal0;
-    if (std::fclose(fh) != 0 && rc == NPORE_OK) rc = fail(NPORE_E_INVALID, "close failed");
-    return rc;
+    return out.close(rc);
 }
 NPORE_CATCH_INT
 

@@ -154,3 +154,52 @@ def gather_parts(final_path, out_prefix, n_local):
     if own_group:
         dist.destroy_process_group()
     return int(t.item())
+
+
+def gather_bam_parts(final_path, out_prefix, n_local):
+    """gather_parts for --out_format bam.  Every rank has written `prefix.part{k}.bam` -- its records in stored BGZF members
+    from a member boundary on, no header, no EOF member -- and, when they went out in coordinate order, the sidecar
+    `prefix.part{k}.bam.bai`: a .bai whose offsets count from the part's first byte.  Rank 0 appends the parts in rank order
+    behind the header that lies in final_path, then the EOF member, and merges the sidecars into `final_path.bai`
+    (bam.merge_bai_parts); a missing sidecar, or parts that are not in order: one line saying so, and the BAM alone.
+    Returns the total number of reads (on every rank)."""
+    import torch
+    import torch.distributed as dist
+    from . import bam as bam_mod
+    rank, world_size, _ = world()
+    own_group = not dist.is_initialized()
+    if own_group:
+        dist.init_process_group("gloo")
+    t = torch.tensor([float(n_local)], dtype=torch.float64)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)        # also the barrier: every part is complete
+    if rank == 0:
+        parts = []
+        with open(final_path, "r+b") as out:
+            out.seek(0, os.SEEK_END)
+            for k in range(world_size):
+                part = f"{out_prefix}.part{k}.bam"
+                shift = out.tell()
+                with open(part, "rb") as fh:
+                    _append_file(out, fh)
+                os.remove(part)
+                if parts is not None and os.path.exists(part + ".bai"):
+                    parts.append((bam_mod.read_bai(part + ".bai"), shift))
+                elif out.tell() > shift:             # (a part without records needs no index)
+                    parts = None
+                if os.path.exists(part + ".bai"):
+                    os.remove(part + ".bai")
+            out.write(bam_mod.BGZF_EOF)
+        merged = bam_mod.merge_bai_parts(parts) if parts is not None else None
+        if merged is None:
+            if os.path.exists(final_path + ".bai"):
+                os.remove(final_path + ".bai")
+            print(bam_mod.NOT_SORTED_MSG)
+        else:
+            tmp = f"{final_path}.bai.tmp{os.getpid()}"
+            with open(tmp, "wb") as fh:
+                fh.write(bam_mod.pack_bai(merged))
+            os.replace(tmp, final_path + ".bai")
+    dist.barrier()
+    if own_group:
+        dist.destroy_process_group()
+    return int(t.item())

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""realign.py -- BAM in, SAM out, same flags as reference src/realign.py:15-71.
+"""realign.py -- BAM in, SAM (or, --out_format bam, indexed BAM) out, same flags as reference src/realign.py:15-71.
 
     python -m npore_amd.realign --bam reads.bam --ref ref.fasta --out_prefix out \\
                                 [--stats_dir DIR] [--contig ...] [--max_reads N] ...
@@ -55,6 +55,10 @@ def argparser():
     # additions
     parser.add_argument("--batch_reads", type=int, default=4000, help="Reads per GPU batch (4 000 reads of 10 kb fill the GPU once at the default band, Context.round_chunks; file to file 6 000 - 8 000 measured 5 - 7 %% faster at twice the device memory: 49 GB of traceback words per batch in flight, three in flight).")
     parser.add_argument("--device", type=int, default=int(os.environ.get("LOCAL_RANK", "0")), help="HIP device.")
+    parser.add_argument("--out_format", choices=("sam", "bam"), default="sam",
+                        help="`sam`: the text, OUT_PREFIX.sam.  `bam`: OUT_PREFIX.bam, the same records in binary (built on the GPU in "
+                             "the default pipeline) in uncompressed BGZF members, with OUT_PREFIX.bam.bai when they go out in "
+                             "coordinate order -- what `samtools view -u` and `samtools index` would make of the SAM.")
     parser.add_argument("--python_io", action="store_true",
                         help="Use the pure-Python BAM reader / SAM writer (the restatement the native one is tested against).")
     return parser
@@ -111,13 +115,22 @@ def main():
     if world > 1 and not native:
         print("\nERROR: --python_io runs on one GPU only.")
         sys.exit(1)
-    print("> creating output SAM")
-    final_sam = f"{cfg.args.out_prefix}.sam"
-    out_sam = final_sam if world == 1 else f"{cfg.args.out_prefix}.part{rank}.sam"
+    fmt = getattr(cfg.args, "out_format", "sam")
+    as_bam = fmt == "bam"
+    if as_bam and native and cfg.args.batch_reads <= 0:
+        print("\nERROR: --out_format bam is written by the library's file pipeline: --batch_reads must be positive.")
+        sys.exit(1)
+    print(f"> creating output {fmt.upper()}")
+    final_sam = f"{cfg.args.out_prefix}.{fmt}"
+    out_sam = final_sam if world == 1 else f"{cfg.args.out_prefix}.part{rank}.{fmt}"
     if rank == 0:
-        bam_mod.create_header(final_sam, bam)
+        (bam_mod.create_bam_header if as_bam else bam_mod.create_header)(final_sam, bam)
     if world > 1:
         open(out_sam, "w").close()
+    # BAM: the index beside the file (a rank's part: a sidecar with part-relative offsets, merged by dist.gather_bam_parts);
+    # the EOF member ends the whole file, not a part
+    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1) if as_bam else {}
+    gather = dist_mod.gather_bam_parts if as_bam else dist_mod.gather_parts
 
     print("> extracting read data from BAM")
     start = perf_counter()
@@ -130,7 +143,7 @@ def main():
         header_bytes = os.path.getsize(out_sam)
         try:
             n, bad, _ = bam.realign_sequential(ctx, ref_seqs, cfg.args.regions, out_sam, batch_reads=cfg.args.batch_reads,
-                                               max_reads=cfg.args.max_reads, threads=threads)
+                                               max_reads=cfg.args.max_reads, threads=threads, **out_kw)
             for k, st in bad:
                 print(f"\nERROR: read #{k} of the selected reads: " +
                       ("CIGAR does not match sequence lengths; skipped." if st & 32 else f"inconsistent traceback (status {st})"))
@@ -150,32 +163,37 @@ def main():
         bam.close()
         ref_seqs.close()
         if world > 1:
-            n = dist_mod.gather_parts(final_sam, cfg.args.out_prefix, n)
+            n = gather(final_sam, cfg.args.out_prefix, n)
     elif native:
         idx = bam.select(cfg.args.regions, cfg.args.max_reads)
         # reads are independent: dealt by index, no data-path collective.  A resident BAM is dealt round-robin; a
         # STREAMED one in contiguous shares, so that a rank only ever inflates the blocks that hold its own reads
-        if bam.streamed and world > 1:
+        # (BAM output: contiguous shares always -- the parts in rank order are then in file order, sorted and indexable)
+        if (bam.streamed or as_bam) and world > 1:
             per = (len(idx) + world - 1) // world
             idx = idx[rank * per:(rank + 1) * per]
         else:
             idx = idx[rank::world]
         print("> computing individual read realignments")
-        n += bam_mod.realign_native(ctx, bam, ref_seqs, idx, out_sam, batch_reads=cfg.args.batch_reads, threads=threads)
+        n += bam_mod.realign_native(ctx, bam, ref_seqs, idx, out_sam, batch_reads=cfg.args.batch_reads, threads=threads, **out_kw)
         bam.close()
         ref_seqs.close()
         if world > 1:
-            n = dist_mod.gather_parts(final_sam, cfg.args.out_prefix, n)
+            n = gather(final_sam, cfg.args.out_prefix, n)
     else:
         read_data = bam_mod.get_read_data(bam, ref_seqs)
         print("> computing individual read realignments")
         batch = []
+        writer = bam_mod.BamRecordWriter(out_sam, bai=out_sam + ".bai") if as_bam else None
+        py_kw = dict(bam_writer=writer, references=bam.references) if as_bam else {}
         for rd in read_data:
             batch.append(rd)
             if len(batch) >= cfg.args.batch_reads:
-                n += bam_mod.realign_reads(ctx, batch, out_sam)
+                n += bam_mod.realign_reads(ctx, batch, out_sam, **py_kw)
                 batch = []
-        n += bam_mod.realign_reads(ctx, batch, out_sam)
+        n += bam_mod.realign_reads(ctx, batch, out_sam, **py_kw)
+        if writer is not None:
+            writer.close()
     ctx.close()
     print(f"    {n} reads, runtime: {perf_counter() - start:.2f}s")
 

@@ -120,7 +120,7 @@ __device__ __forceinline__ uint32_t lane_table(uint32_t addr4, uint32_t tab)
 
 // LDS reads of the workgroup-shared score tables by ABSOLUTE LDS byte address.  The kernels here use dynamic LDS only,
 // so the `lds` array starts at LDS address 0 (checked once per launch configuration on the host:
-// hipFuncGetAttributes().sharedSizeBytes == 0, npore_api.cpp); going through the array symbol instead costs one
+// hipFuncGetAttributes().sharedSizeBytes == 0, align_engine.hpp); going through the array symbol instead costs one
 // `v_add_u32 v, <lds>, v` per lookup, because the symbol's value is only known at link time.
 typedef const __attribute__((address_space(3))) float lds_cfloat;
 __device__ __forceinline__ float lds_abs_f32(uint32_t byte_addr)
@@ -301,7 +301,7 @@ constexpr int SLOT_RING = 8;    // chunk slots published by a group's first wave
 // workgroups as the GPU keeps resident, and every group of NW waves pulls its next chunk from a device-wide queue
 // (the schedule lists the chunks largest first) the moment it has finished one, until the queue is empty -- no
 // group waits for a sibling of its workgroup, no workgroup waits for a "round" to drain.
-// Registers: four of these waves share a SIMD with whatever the NEXT batch runs beside them (npore_api.cpp: its
+// Registers: four of these waves share a SIMD with whatever the NEXT batch runs beside them (align_engine.hpp: its
 // preparation, the previous one's traceback), so the kernel is held to 112 of the SIMD's 512 / 4 = 128 vector
 // registers -- amdgpu_num_vgpr counts in halves on this target (arch + acc registers) -- which leaves 64 for one
 // light wave per SIMD (this round's annotate_wave_kernel is held to those 64).  The cap costs spills (NW >= 2: 59 vector

@@ -1,7 +1,7 @@
-// npore_api.cpp -- C ABI (include/npore_amd.h) and host orchestration.
+// npore_api.cpp -- C ABI (include/npore_amd.h), the batch slots and the file pipeline; the only translation unit.
 // Compiled with hipcc for gfx950 only.  There is no CPU execution path for the
-// DP here: without a gfx950 device npore_ctx_create fails.  What reads BAM / FASTA
-// files and writes SAM text needs no device and lives in bam_reader.hpp / hostio.hpp.
+// DP here: without a gfx950 device npore_ctx_create fails.  The device path of a batch of reads lives in align_engine.hpp;
+// what reads BAM / FASTA files and writes SAM text needs no device and lives in bam_reader.hpp / hostio.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,12 +11,10 @@
 #include <cstdio>
 #include <cstring>
 #include <condition_variable>
-#include <deque>
 #include <future>
 #include <limits>
 #include <mutex>
 #include <memory>
-#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -32,10 +30,7 @@
 #include "unpack_kernels.hpp"
 #include "bam_emit_kernels.hpp"
 #include "confusion_kernels.hpp"
-
-using namespace npore;
-
-namespace {
+#include "align_engine.hpp"
 
 // No C++ exception may cross the C ABI: the entry points that allocate are function-try-blocks ending in one of these.
 #define NPORE_CATCH_INT                                                                             \
@@ -44,144 +39,8 @@ namespace {
 #define NPORE_CATCH_PTR                                                                             \
     catch (const std::bad_alloc &) { fail(NPORE_E_NOMEM, "out of host memory"); return nullptr; }  \
     catch (const std::exception &e) { fail(NPORE_E_INVALID, std::string("internal: ") + e.what()); return nullptr; }
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(NPORE_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    } while (0)
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return NPORE_OK;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        AllocTrace tr("hipMalloc", want);
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(NPORE_E_NOMEM, "hipMalloc(" + std::to_string(want) + "): " + hipGetErrorString(e));
-        }
-        cap = want;
-        return NPORE_OK;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    // best effort, no head-room: another buffer of the same role already has this capacity (presize_like)
-    void match(const DevBuf &o)
-    {
-        if (o.cap <= cap) return;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        AllocTrace tr("hipMalloc like", o.cap);
-        if (hipMalloc(&p, o.cap) == hipSuccess) cap = o.cap;
-        else { p = nullptr; (void)hipGetLastError(); }
-    }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-struct HostBuf {   // pinned staging
-    void *p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes)
-    {
-        if (bytes <= cap) return NPORE_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        AllocTrace tr("hipHostMalloc", want);
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) {
-            p = nullptr;
-            return fail(NPORE_E_NOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-        }
-        cap = want;
-        return NPORE_OK;
-    }
-    void release()
-    {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
-
-// Page-locked staging (hipHostMalloc) of the BAM -> SAM pipeline: the buffers of a batch that cross PCIe.  Unlike HostBuf
-// it does not fail where the runtime has no page-locked memory left: the buffer is pageable from then on.
-struct PinnedBuf {
-    char *p = nullptr;
-    size_t cap = 0;
-    bool pinned = true;        // false once hipHostMalloc has failed: pageable (RawBuf::alloc) for the rest of its life
-    PinnedBuf() = default;
-    PinnedBuf(const PinnedBuf &) = delete;
-    PinnedBuf &operator=(const PinnedBuf &) = delete;
-    ~PinnedBuf() { release(); }
-    void release()
-    {
-        if (!p) return;
-        if (pinned) (void)hipHostFree(p);
-        else std::free(p);
-        p = nullptr;
-        cap = 0;
-    }
-    bool ensure(size_t n)
-    {
-        if (n <= cap) return true;
-        release();
-        n += n / 4;            // head-room: batches of a run differ a little in size
-        if (pinned) {
-            void *q = nullptr;
-            AllocTrace tr("hipHostMalloc", n);
-            if (hipHostMalloc(&q, n, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                pinned = false;
-                if (std::getenv("NPORE_DEBUG")) std::fprintf(stderr, "npore: hipHostMalloc(%zu) failed, pageable staging buffer\n", n);
-            }
-            else p = static_cast<char *>(q);
-        }
-        if (!pinned) p = RawBuf::alloc(n);
-        cap = p ? n : 0;
-        return p != nullptr;
-    }
-};
-
-}  // namespace
 
 // One batch on its way through the BAM -> SAM pipeline: host staging (page-locked where it crosses PCIe) and offsets.
-// The file pipeline's texts compacted on the device (unpack_kernels.hpp compact_texts_kernel): what a batch's align call needs
-// to know about it
-struct TextCompact {
-    uint8_t *d_ctext;
-    unsigned long long *d_cursor;
-    int64_t cap;                 // bytes of d_ctext (all slots: it cannot overflow)
-    int64_t *h_coff;             // [n_reads] page-locked
-    char *h_ctext;               // page-locked
-    int64_t h_bytes;             // how much of the compact buffer's front to send with the batch's last group
-};
-
-// The file pipeline's BAM mode with the records built on the device (bam_emit_kernels.hpp): what a batch's align call needs
-// to know about it
-struct BamEmit {
-    uint8_t *d_recs;             // the batch's record buffer
-    int64_t cap;
-    unsigned long long *d_cursor;
-    const int64_t *h_hp;         // [n_reads] page-locked: the reads' HP values
-    int64_t *h_rec_len;          // [n_reads] page-locked: bytes of every read's record (0: not written)
-    unsigned long long *h_total; // page-locked: bytes of the batch's records
-};
-
 struct npore_batch_slot {
     PinnedBuf refs, seqs, cigs, alns;
     RawBuf finals, sam;
@@ -211,750 +70,6 @@ struct npore_batch_slot {
     int rc = 0;
     std::string err;
 };
-
-// Work buffers of one group of reads on its way through the device stages (grow-only, reused).  A context has
-// N_SETS of them: while the fill kernel works on one group, the next group is prepared in another set and the previous
-// group's traceback / gather drains from a third (run_core).
-struct WorkSet {
-    DevBuf rd_i32, rd_i64, steps, inss, descs, sched, hist, counters; // path + chunks
-    DevBuf tiles, cwoff;                                             // CIGAR tiles; chunk positions in the output
-    DevBuf seqw, refw, refl, seql;                                   // annotation
-    DevBuf tb, cout_, clen, cstat, cnruns;                           // fill / traceback (cout_: uint32 runs)
-    DevBuf dbg;                                                      // experiments build: MAT.VAL per cell (NPORE_DBGMAT=1)
-    HostBuf h_cnt;                                                   // counters read back with the group
-    // host-buffer entry points: the group's slice of the caller's inputs / outputs on the device, its offset
-    // arrays rebased to the slice (page-locked copy for the upload)
-    DevBuf in_refs, in_seqs, in_cigs, in_off, out, out_len, status;
-    DevBuf in_raw;               // device pack (unpack_kernels.hpp): the group's record heads
-    DevBuf coff;                 // compacted texts: where each read of the group begins in the batch's compact buffer
-    DevBuf in_hp, rec_off, rec_len;   // BAM records built on the device: the group's HP values, its records' places and sizes
-    HostBuf h_off;
-    hipEvent_t evc[4] = {};      // H2D start / end, D2H start / end of a staged group
-    bool staged = false;
-    hipEvent_t ev[6] = {};       // prep start / end, fill start / end, traceback + gather start / end (= group done)
-    bool busy = false;           // enqueued, not collected yet
-    // An idle set takes the capacities of one that has just been given a group: the groups of a run are alike, so its
-    // own first group then finds its buffers in place instead of allocating tens of GB in front of its kernels (with
-    // three sets that was the THIRD step of a run -- 0.4 s in a timed region that had two warm-up steps)
-    void presize_like(const WorkSet &o)
-    {
-        DevBuf WorkSet::*const all[] = {&WorkSet::rd_i32, &WorkSet::rd_i64, &WorkSet::steps, &WorkSet::inss, &WorkSet::descs, &WorkSet::sched,
-                                        &WorkSet::hist, &WorkSet::counters, &WorkSet::tiles, &WorkSet::cwoff, &WorkSet::seqw, &WorkSet::refw,
-                                        &WorkSet::refl, &WorkSet::seql, &WorkSet::tb, &WorkSet::cout_, &WorkSet::clen, &WorkSet::cstat,
-                                        &WorkSet::cnruns, &WorkSet::in_refs, &WorkSet::in_seqs, &WorkSet::in_cigs, &WorkSet::in_off,
-                                        &WorkSet::out, &WorkSet::out_len, &WorkSet::status, &WorkSet::in_raw, &WorkSet::coff,
-                                        &WorkSet::in_hp, &WorkSet::rec_off, &WorkSet::rec_len};
-        for (auto m : all) (this->*m).match(o.*m);
-    }
-    int64_t cells = 0, call_id = 0;
-    DevBuf *all[31] = {&rd_i32, &rd_i64, &steps, &inss, &descs, &sched, &hist, &counters, &tiles, &cwoff,
-                       &seqw, &refw, &refl, &seql, &tb, &cout_, &clen, &cstat, &cnruns,
-                       &in_refs, &in_seqs, &in_cigs, &in_off, &out, &out_len, &status, &in_raw, &coff, &in_hp, &rec_off, &rec_len};
-};
-
-// Work sets of a context: group k + 1 is prepared while group k is in the fill kernel and group k - 1 in its traceback;
-// the third set lets the host enqueue group k + 1's preparation without waiting for group k - 1's traceback to end
-// (with two, that wait sits between every pair of groups; measured equal within 1 % either way on this hardware --
-// what binds the pipelined r = 30 case is the preparation's own duration beside a running fill kernel, LABNOTES.md).
-constexpr int N_SETS = 3;
-
-struct npore_ctx {
-    int device = 0;
-    int n_cus = 256;
-    int max_n = 6, max_l = 100;
-    // three non-blocking streams: preparation (also every copy), fill kernels, traceback + gather; events order
-    // the stages of a group, the streams let stages of neighbouring groups run side by side
-    hipStream_t stream = nullptr, s_fill[2] = {nullptr, nullptr}, s_post = nullptr;
-    int next_fill = 0;           // the fill stream the next group's fill kernel goes to
-    int fill_streams = 2;        // 1: every fill kernel on one stream (npore_ctx_set "fill_streams")
-    hipEvent_t ev[8] = {};       // [4..7] H2D / D2H of the host-buffer entry point, [0] the caller's stream
-    float *d_sub = nullptr, *d_np = nullptr;   // NULL in an annotation-only context (created without tables)
-    WorkSet ws[N_SETS];
-    int next_ws = 0;             // set the next group goes into (the oldest of them)
-    WorkSet *last_ws = nullptr;  // set of the group enqueued last (npore_debug_fetch)
-    int64_t call_id = 0, timing_call = -1;
-    int deferred_rc = 0;         // failure found while collecting a group of an asynchronous call
-    std::string deferred_err;
-    double totals[8] = {};       // like timing[], summed over every group since the context was made
-    // tunables
-    int64_t tb_budget_mb = 0;   // 0 = auto
-    int force_chunks = 0;
-    int device_glue = 1;        // BAM -> SAM pipeline: realign_read's glue on the device (0: on the host, from the op strings)
-    int coresident = 1;         // kernel shapes that fit beside a fill kernel for a group that overlaps another one's
-    int device_pack = 1;        // BAM -> SAM pipeline with the glue on the device: align()'s inputs unpacked from the records on the device
-    // device pack: the FASTA of the current run on the device (uploaded once per FASTA), the contig of every BAM reference
-    DevBuf d_fasta, d_ctg;
-    // recount of the confusion matrices from BAM records (npore_bam_confusion): the batch's record heads and their offsets,
-    // the current contig's ranges, the counters
-    DevBuf cms_raw, cms_off, cms_ranges, cms_counts;
-    int64_t cms_batch_reads = 4000;
-    uint64_t d_fasta_serial = 0;
-    size_t d_fasta_bytes = 0;
-    int n_ctg = 0;
-    bool fill_has_room = false; // the last fill launch left LDS for such kernels on its CUs
-    HostBuf h_offs;             // offset arrays of a device-resident batch (npore_align_batch_device)
-    // device buffers (grow-only, reused across calls)
-    DevBuf in_refs, in_seqs, in_cigs, in_off;                       // raw inputs (host-buffer entry point)
-    std::vector<int32_t> regions;                                    // npore_np_regions: positions, then repeat counts
-    DevBuf out, out_off, out_len, status;                            // outputs (host-buffer entry point)
-    // host staging of the BAM -> SAM pipeline (npore_bam_realign_batch / _file): grow-only, reused across batches and files
-    double file_mark[2] = {0, 0};      // totals at the start of npore_bam_realign_file (kernels, PCIe)
-    static constexpr int N_SLOTS = 6;
-    npore_batch_slot *slots[N_SLOTS] = {};
-    // second context of the file pipeline (its own stream and work buffers), so that the transfers, preparation and
-    // traceback of one batch run beside the fill kernel of its neighbour; made on first use from the host copy of the tables
-    std::vector<float> h_sub, h_np;
-    npore_ctx *peer = nullptr;
-    double timing[8] = {};
-};
-
-namespace {
-
-std::atomic<int> g_live_ctx[16];   // contexts alive per device (they share its memory: run_core's budget)
-
-// waves per chunk: the smallest count whose 64 * nw lanes cover the band (the kernel relies on band
-// column 2r lying in the last wave); 0 if the band is too wide
-int pick_shape(int r)
-{
-    const int nw = (2 * r + 1 + 63) / 64;
-    return nw <= MAX_WAVES_PER_CHUNK ? nw : 0;
-}
-
-int pow2_at_least(int x)
-{
-    int p = 64;
-    while (p < x) p <<= 1;
-    return p;
-}
-
-// Geometry of a fill launch for band half-width r: LDS sizes, chunks per workgroup and how many workgroups the
-// GPU holds at a time.
-struct FillGeom {
-    int nw = 0, hw = 0, rwin = 0, cmax = 0;
-};
-bool fill_geometry(int r, FillGeom &g)
-{
-    g.nw = pick_shape(r);
-    if (!g.nw) return false;
-    g.hw = 2 * r + 1 + HIST_PAD;
-    // reference-L window: the band (2r+1), 96 positions of read-ahead and the 6 positions below the band that the
-    // generic SHR path looks back on -- plus 16 of margin, because the first wave of a chunk may run NW - 2
-    // anti-diagonals behind the last one, which refills the window
-    // (a chunk of ONE wave refills for itself, 32 positions at a time with 8 of slack: kernels.hpp WIN_STEP / WIN_SLACK;
-    // r <= 31 then needs 2r + 6 + 8 + 32 <= 128 entries, which leaves the CU 16 KB of LDS at r = 30 -- room for the
-    // kernels of the neighbouring batches beside 16 chunks)
-    g.rwin = g.nw == 1 ? pow2_at_least(2 * r + 6 + 8 + 32) : pow2_at_least(2 * r + 101 + 16);
-    const size_t lds_cap = 160 * 1024 / sizeof(float);
-    if (fill_lds_floats(g.nw, 1, g.hw, g.rwin) > lds_cap) return false;
-    g.cmax = 1;
-    while ((g.cmax + 1) * g.nw * 64 <= 1024 && fill_lds_floats(g.nw, g.cmax + 1, g.hw, g.rwin) <= lds_cap) g.cmax++;
-    return true;
-}
-// workgroups of `chunks` chunks that are resident together: the size of a persistent fill launch
-int fill_round_workgroups(const FillGeom &g, int chunks, int n_cus)
-{
-    const size_t lds = fill_lds_floats(g.nw, chunks, g.hw, g.rwin) * sizeof(float);
-    const int wg_per_cu = std::max(1, std::min((int)((160 * 1024) / std::max<size_t>(lds, 1)), 2048 / (64 * g.nw * chunks)));
-    return std::max(1, n_cus) * wg_per_cu;
-}
-
-// NW waves per chunk, `chunks` chunks per workgroup (they share the LDS score table).
-// leave_room: groups of reads overlap on the device (run_core), so the next group's preparation and this one's
-// gather will look for room BESIDE fill workgroups: where the fill would take (nearly) all of a CU's LDS -- r = 30:
-// 16 chunks = 159.75 KB -- a workgroup takes one chunk less (measured at r = 30, 8 000 reads per batch: 154 k
-// instead of 144 k reads/s; the scans and the gather need ~3.5 KB of LDS).
-// (NWT = 0: the instantiation that takes its wave count from the launch -- bands of 9 ... 16 waves, one chunk per workgroup)
-template <int NWT>
-hipError_t launch_fill(KParams kp, int max_chunks, int force_chunks, int n_cus, hipStream_t s, bool leave_room, bool *has_room)
-{
-    constexpr int MAXT = 1024;
-    FillGeom g;
-    if (!fill_geometry(kp.r, g) || (NWT ? g.nw != NWT : g.nw <= 8)) return hipErrorInvalidValue;
-    const int NW = g.nw;
-    kp.hw = g.hw;
-    kp.rwin = g.rwin;
-    const int cmax = g.cmax;
-    // few chunks: spread them over the CUs; many: pack workgroups so that the table is amortised
-    int chunks = std::min(cmax, std::max(1, (max_chunks + 255) / 256));
-    if (leave_room && chunks > 1 && fill_lds_floats(NW, chunks, kp.hw, kp.rwin) * sizeof(float) + 4096 > 160 * 1024) {
-        // ... unless exactly that chunk per workgroup decides whether the batch's full-size chunks (about half of
-        // the upper bound: a read's last chunk is a short tail) are resident all at once (r = 30, 4 000 reads per
-        // batch: 142 k reads/s with 16 chunks per workgroup, 127 k with 15)
-        const int64_t big = (max_chunks + 1) / 2, wgs = fill_round_workgroups(g, chunks, n_cus);
-        if (!(big <= wgs * chunks && big > wgs * (chunks - 1))) chunks--;
-    }
-    if (force_chunks > 0) chunks = std::min(cmax, force_chunks);
-    const size_t lds = fill_lds_floats(NW, chunks, kp.hw, kp.rwin) * sizeof(float);
-    *has_room = lds + 4096 <= 160 * 1024;      // other kernels' light workgroups fit beside this launch's
-    // the kernel addresses its score tables by absolute LDS address (kernels.hpp: lds_abs_f32): it must not
-    // own any static LDS, so that the dynamic array starts at address 0
-    static const hipError_t no_static_lds = [] {
-        hipFuncAttributes at;
-        const hipError_t e0 = hipFuncGetAttributes(&at, reinterpret_cast<const void *>(&fill_kernel<NWT, MAXT>));
-        return e0 != hipSuccess ? e0 : (at.sharedSizeBytes == 0 ? hipSuccess : hipErrorInvalidDeviceFunction);
-    }();
-    if (no_static_lds != hipSuccess) return no_static_lds;
-    // A persistent launch: as many workgroups as the GPU keeps resident (or fewer, if the batch is small); their
-    // groups of NW waves pull the chunks of the schedule (largest first) from a device-side queue (kernels.hpp)
-    const int resident = fill_round_workgroups(g, chunks, n_cus);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&fill_kernel<NWT, MAXT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((fill_kernel<NWT, MAXT>), dim3(std::min((max_chunks + chunks - 1) / chunks, resident)),
-                       dim3(64 * NW * chunks), lds, s, kp);
-    return hipGetLastError();
-}
-
-struct OutTarget {
-    uint8_t *d_out;
-    const int64_t *d_out_off;
-    int64_t *d_out_len;
-    int32_t *d_status;
-};
-
-// device pointers to the raw batch + host copies of the three offset arrays
-struct AlignArgs {
-    int64_t n_reads;
-    const uint8_t *d_refs;
-    const int64_t *d_ref_off;
-    const uint8_t *d_seqs;
-    const int64_t *d_seq_off;
-    const char *d_cigs;
-    const int64_t *d_cig_off;
-    const int64_t *h_ref_off, *h_seq_off, *h_cig_off;
-    float indel_start, indel_extend;
-    int max_b_rows, r;
-    // host-buffer entry points (d_* above are NULL then): every group uploads its slice of these, and downloads
-    // its slice of the results, around its own kernels -- the copies of one group overlap the kernels of its neighbours
-    const uint8_t *h_refs = nullptr, *h_seqs = nullptr;
-    const char *h_cigs = nullptr;
-    char *h_out = nullptr;
-    const int64_t *h_out_off = nullptr;
-    int64_t *h_out_len = nullptr;
-    int32_t *h_status = nullptr;
-    // the output is the collapsed, standardised CIGAR text (realign_read's glue on the device, kernels.hpp
-    // standardize_kernel) instead of the op string; out_len = bytes of text
-    bool final_text = false;
-    // device pack: instead of h_refs / h_seqs / h_cigs the heads of the BAM records; every group uploads its slice and
-    // unpacks it on the device (unpack_kernels.hpp)
-    const uint8_t *h_raw = nullptr;
-    const int64_t *h_raw_off = nullptr;
-    const CtgEntry *d_ctg = nullptr;
-    int n_ctg = 0;
-    // the file pipeline with the device glue: the texts compacted on the device, the used front of the compact buffer and
-    // the reads' offsets copied instead of the slots (nullptr: the slots, as the public entry points promise)
-    const TextCompact *compact = nullptr;
-    // BAM mode of the file pipeline (device pack + device glue): the final CIGARs stay on the device as words and the
-    // records are assembled there; neither the slots nor a compact buffer are copied
-    const BamEmit *bam = nullptr;
-    bool staged() const { return h_out != nullptr; }
-};
-
-
-int64_t chunk_bound(int64_t cig_len, int max_b_rows)
-{
-    const int64_t cm1 = max_b_rows - 1;
-    return std::max<int64_t>(1, (2 * cig_len + cm1 - 1) / cm1);
-}
-
-// Reads [g0,g1): everything from the raw bytes to the gathered output, on stream s,
-// without host synchronisation.
-int run_group(npore_ctx *ctx, WorkSet *w, const AlignArgs &a, int64_t g0, int64_t g1, const OutTarget &ot, int shape,
-              bool overlapping)
-{
-    // overlapping: another group of this context is on the device.  beside_fill: ... and the fill launch it belongs to
-    // left room on its CUs (launch_fill), so kernels of light shapes can run beside it.
-    const bool beside_fill = overlapping && ctx->fill_has_room;
-    // beside_fill: another group of this context is on the device, most likely in its fill kernel, whose persistent
-    // workgroups hold nearly all the LDS and most of the vector registers of every CU until they have emptied their
-    // queue.  The preparation and gather kernels of THIS group then run in shapes that find room beside a fill
-    // workgroup instead of waiting for it to leave: 256-thread scans (one wave per SIMD), the LDS-free annotation
-    // (prep_kernels.hpp) and the gather without its LDS tile (kernels.hpp).
-    const unsigned scan_threads = beside_fill ? 256 : 1024;
-    hipStream_t s = ctx->stream;      // preparation; the fill and traceback stages go to their own streams below
-    const int64_t nr = g1 - g0;
-    const int r = a.r;
-    const int tbs = tb_stride(r);
-    const int64_t cig_bytes = a.h_cig_off[g1] - a.h_cig_off[g0];
-    const int64_t S_tot = a.h_seq_off[g1] - a.h_seq_off[g0], R_tot = a.h_ref_off[g1] - a.h_ref_off[g0];
-    // longest chunk slice of the group: a slice never exceeds its sequence, nor max_b_rows + 1 bases
-    int64_t max_len = 0;
-    for (int64_t i = g0; i < g1; i++)
-        max_len = std::max({max_len, a.h_seq_off[i + 1] - a.h_seq_off[i], a.h_ref_off[i + 1] - a.h_ref_off[i]});
-    int64_t max_chunks = 0;
-    for (int64_t k = g0; k < g1; k++) max_chunks += chunk_bound(a.h_cig_off[k + 1] - a.h_cig_off[k], a.max_b_rows);
-    if (max_chunks > (1ll << 30)) return fail(NPORE_E_UNSUPPORTED, "too many chunks in one group");
-    const int64_t steps_cap = 2 * cig_bytes + 512;
-    const int64_t tb_words = (2 * cig_bytes + max_chunks) * tbs;
-
-    // CIGAR tiles (prep_kernels.hpp): every read has at least one
-    int64_t max_tiles = 0;
-    for (int64_t k = g0; k < g1; k++)
-        max_tiles += std::max<int64_t>(1, (a.h_cig_off[k + 1] - a.h_cig_off[k] + CIGAR_TILE - 1) / CIGAR_TILE);
-    if (max_tiles > (1ll << 30)) return fail(NPORE_E_UNSUPPORTED, "too many CIGAR tiles in one group");
-    if (int rc = w->rd_i32.ensure((size_t)(5 * nr + 16) * 4)) return rc;
-    if (int rc = w->tiles.ensure((size_t)max_tiles * 24 + 64)) return rc;
-    if (int rc = w->cwoff.ensure((size_t)max_chunks * 8 + 64)) return rc;
-    if (int rc = w->rd_i64.ensure((size_t)(nr + 2) * 8)) return rc;
-    if (int rc = w->steps.ensure(steps_cap)) return rc;
-    if (int rc = w->inss.ensure((size_t)(2 * cig_bytes + nr + 16) * 4)) return rc;
-    if (int rc = w->descs.ensure((size_t)max_chunks * sizeof(ChunkDesc))) return rc;
-    if (int rc = w->sched.ensure((size_t)max_chunks * 4)) return rc;
-    if (int rc = w->hist.ensure((size_t)(a.max_b_rows + 2) * 4)) return rc;
-    if (int rc = w->counters.ensure(64)) return rc;
-    if (int rc = w->seqw.ensure((size_t)(S_tot + max_chunks + 16) * 4)) return rc;
-    if (int rc = w->refw.ensure((size_t)(R_tot + max_chunks + 16) * 16)) return rc;
-    if (int rc = w->refl.ensure((size_t)(R_tot + max_chunks + 16) * 8)) return rc;
-    if (int rc = w->tb.ensure((size_t)tb_words * 4 + 64)) return rc;
-#if defined(NPORE_EXPERIMENTS)
-    if (std::getenv("NPORE_DBGMAT") && w->dbg.p) (void)hipMemsetAsync(w->dbg.p, 0, w->dbg.cap, ctx->stream);     // (steps of the compiled path leave zeros)
-    if (std::getenv("NPORE_DBGMAT")) { if (int rc = w->dbg.ensure((size_t)tb_words * 4 * (size_t)std::max(1, std::atoi(std::getenv("NPORE_DBGMAT"))) + 64)) return rc; }
-#endif
-    if (int rc = w->cout_.ensure(((size_t)(S_tot + R_tot) + 64) * 4)) return rc;
-    if (int rc = w->cnruns.ensure((size_t)max_chunks * 4 + 64)) return rc;
-    if (int rc = w->clen.ensure((size_t)max_chunks * 4 + 64)) return rc;
-    if (int rc = w->cstat.ensure((size_t)max_chunks * 4 + 64)) return rc;
-
-    PrepParams pp;
-    pp.n_reads = nr;
-    pp.refs = a.d_refs; pp.ref_off = a.d_ref_off + g0;
-    pp.seqs = a.d_seqs; pp.seq_off = a.d_seq_off + g0;
-    pp.cigs = a.d_cigs; pp.cig_off = a.d_cig_off + g0;
-    OutTarget got = ot;                  // where the gather writes, and the index of this group's first read in it
-    int64_t out_read_base = g0;
-    w->staged = a.staged();
-    if (a.staged()) {
-        // upload the group's slice: bases + CIGAR ops as they lie, the four offset arrays rebased to the slice
-        const int64_t out_bytes = a.h_out_off[g1] - a.h_out_off[g0];
-        if (int rc = w->h_off.ensure((size_t)5 * (nr + 1) * 8)) return rc;
-        if (int rc = w->in_refs.ensure((size_t)R_tot + 64)) return rc;
-        if (int rc = w->in_seqs.ensure((size_t)S_tot + 64)) return rc;
-        if (int rc = w->in_cigs.ensure((size_t)cig_bytes + 64)) return rc;
-        if (int rc = w->in_off.ensure((size_t)5 * (nr + 1) * 8)) return rc;
-        if (int rc = w->out.ensure((size_t)out_bytes + 64)) return rc;
-        if (int rc = w->out_len.ensure((size_t)nr * 8)) return rc;
-        if (int rc = w->status.ensure((size_t)nr * 4)) return rc;
-        int64_t *ho = w->h_off.as<int64_t>(), *hro = ho, *hso = ho + (nr + 1), *hco = ho + 2 * (nr + 1), *hoo = ho + 3 * (nr + 1);
-        for (int64_t i = 0; i <= nr; i++) {
-            hro[i] = a.h_ref_off[g0 + i] - a.h_ref_off[g0]; hso[i] = a.h_seq_off[g0 + i] - a.h_seq_off[g0];
-            hco[i] = a.h_cig_off[g0 + i] - a.h_cig_off[g0]; hoo[i] = a.h_out_off[g0 + i] - a.h_out_off[g0];
-        }
-        const int64_t raw_bytes = a.h_raw ? a.h_raw_off[g1] - a.h_raw_off[g0] : 0;
-        if (a.h_raw) {
-            int64_t *hwo = ho + 4 * (nr + 1);
-            for (int64_t i = 0; i <= nr; i++) hwo[i] = a.h_raw_off[g0 + i] - a.h_raw_off[g0];
-            if (int rc = w->in_raw.ensure((size_t)raw_bytes + 64)) return rc;
-        }
-        HIP_TRY(hipEventRecord(w->evc[0], s));
-        if (a.h_raw) {
-            HIP_TRY(hipMemcpyAsync(w->in_raw.p, a.h_raw + a.h_raw_off[g0], (size_t)raw_bytes, hipMemcpyHostToDevice, s));
-        } else {
-            HIP_TRY(hipMemcpyAsync(w->in_refs.p, a.h_refs + a.h_ref_off[g0], (size_t)R_tot, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(w->in_seqs.p, a.h_seqs + a.h_seq_off[g0], (size_t)S_tot, hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpyAsync(w->in_cigs.p, a.h_cigs + a.h_cig_off[g0], (size_t)cig_bytes, hipMemcpyHostToDevice, s));
-        }
-        HIP_TRY(hipMemcpyAsync(w->in_off.p, ho, (size_t)5 * (nr + 1) * 8, hipMemcpyHostToDevice, s));
-        if (a.bam) {
-            if (int rc = w->in_hp.ensure((size_t)nr * 8 + 64)) return rc;
-            HIP_TRY(hipMemcpyAsync(w->in_hp.p, a.bam->h_hp + g0, (size_t)nr * 8, hipMemcpyHostToDevice, s));
-        }
-        HIP_TRY(hipEventRecord(w->evc[1], s));
-        const int64_t *d_off = w->in_off.as<int64_t>();
-        if (a.h_raw) {          // align()'s three inputs from the record heads (unpack_kernels.hpp), where the copies above would have put them
-            UnpackParams up;
-            up.raw = w->in_raw.as<uint8_t>(); up.raw_off = d_off + 4 * (nr + 1);
-            up.ctg = a.d_ctg; up.n_ctg = a.n_ctg;
-            up.refs = w->in_refs.as<uint8_t>(); up.ref_off = d_off;
-            up.seqs = w->in_seqs.as<uint8_t>(); up.seq_off = d_off + (nr + 1);
-            up.cigs = w->in_cigs.as<char>(); up.cig_off = d_off + 2 * (nr + 1);
-            up.n_reads = nr;
-            hipLaunchKernelGGL(unpack_records_kernel, dim3((unsigned)nr), dim3(256), 0, s, up);
-            HIP_TRY(hipGetLastError());
-        }
-        pp.refs = w->in_refs.as<uint8_t>(); pp.ref_off = d_off;
-        pp.seqs = w->in_seqs.as<uint8_t>(); pp.seq_off = d_off + (nr + 1);
-        pp.cigs = w->in_cigs.as<char>(); pp.cig_off = d_off + 2 * (nr + 1);
-        got = OutTarget{w->out.as<uint8_t>(), d_off + 3 * (nr + 1), w->out_len.as<int64_t>(), w->status.as<int32_t>()};
-        out_read_base = 0;
-    }
-    pp.max_b_rows = a.max_b_rows; pp.r = r; pp.tbstride = tbs; pp.max_n = ctx->max_n; pp.max_l = ctx->max_l;
-    pp.max_chunks = (int)max_chunks;
-    int32_t *i32 = w->rd_i32.as<int32_t>();
-    pp.rd_nsteps = i32;
-    pp.rd_nchunks = i32 + nr;
-    pp.rd_status = i32 + 2 * nr;
-    pp.rd_chunk_first = i32 + 3 * nr;   // nr + 1 entries
-    pp.rd_tile_first = i32 + 4 * nr + 4;   // nr + 1 entries
-    pp.tile_cnt = w->tiles.as<int4>();
-    pp.tile_base = reinterpret_cast<int2 *>(w->tiles.as<char>() + (size_t)max_tiles * 16);
-    pp.rd_steps_off = w->rd_i64.as<int64_t>();
-    pp.steps = w->steps.as<uint8_t>();
-    pp.inss = w->inss.as<int32_t>();
-    pp.descs = w->descs.as<ChunkDesc>();
-    pp.sched = w->sched.as<int32_t>();
-    pp.hist = w->hist.as<int32_t>();
-    pp.counters = w->counters.as<int32_t>();
-    pp.seqw = w->seqw.as<uint32_t>();
-    pp.refw = w->refw.as<uint4>();
-    pp.refl = w->refl.as<uint2>();
-
-    if (int rc = w->h_cnt.ensure(64)) return rc;
-    HIP_TRY(hipEventRecord(w->ev[0], s));
-    HIP_TRY(hipMemsetAsync(pp.hist, 0, (size_t)(a.max_b_rows + 2) * 4, s));
-    const unsigned rd_blocks = (unsigned)((nr + 3) / 4), ch_blocks = (unsigned)((max_chunks + 255) / 256);
-    const unsigned tile_blocks = (unsigned)((max_tiles + 3) / 4);
-    hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(scan_threads), 0, s, pp);
-    hipLaunchKernelGGL(cigar_tile_kernel, dim3(tile_blocks), dim3(256), 0, s, pp);
-    hipLaunchKernelGGL(cigar_scan_kernel, dim3(rd_blocks), dim3(256), 0, s, pp);
-    hipLaunchKernelGGL(read_scan_kernel, dim3(1), dim3(scan_threads), 0, s, pp);
-    hipLaunchKernelGGL(expand_path_kernel, dim3(tile_blocks), dim3(256), 0, s, pp);
-    hipLaunchKernelGGL(make_chunks_kernel, dim3(ch_blocks), dim3(256), 0, s, pp);
-    hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(scan_threads), 0, s, pp);
-    hipLaunchKernelGGL(sched_scatter_kernel, dim3(ch_blocks), dim3(256), 0, s, pp);
-    // n-polymer annotation + word packing: one wave per (chunk, sequence), registers only (annot_wave.hpp) -- the same
-    // launch whether the GPU is empty or a fill kernel holds the CUs' LDS
-    if (ctx->max_n == MAX_PERIOD) hipLaunchKernelGGL(annotate_wave_kernel<true>, dim3((unsigned)(2 * max_chunks)), dim3(64), 0, s, pp);
-    else hipLaunchKernelGGL(annotate_wave_kernel<false>, dim3((unsigned)(2 * max_chunks)), dim3(64), 0, s, pp);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(w->ev[1], s));
-    // ---- fill: behind this group's preparation.  Consecutive groups alternate between two streams: their fill
-    // kernels share nothing, so the next one's persistent workgroups move onto the CUs that this one's leave as its
-    // last chunks run out -- the tail of one launch is filled by the head of the next (C2, steps back to back:
-    // 17.1 ms per step against the 18.0 ms one fill kernel takes alone; one stream: 18.1)
-    s = ctx->s_fill[ctx->next_fill];
-    if (ctx->fill_streams == 2) ctx->next_fill ^= 1;
-    HIP_TRY(hipStreamWaitEvent(s, w->ev[1], 0));
-    HIP_TRY(hipEventRecord(w->ev[2], s));
-
-    KParams kp;
-    kp.descs = pp.descs;
-    kp.sched = pp.sched;
-    kp.n_chunks = pp.counters;
-    kp.queue = pp.counters + 2;
-    kp.steps = pp.steps;
-    kp.inss = pp.inss;
-    kp.seqw = pp.seqw;
-    kp.refw = pp.refw;
-    kp.refl = pp.refl;
-    kp.tb = w->tb.as<uint32_t>();
-    kp.dbg = w->dbg.as<uint32_t>();
-    kp.sub_scores = ctx->d_sub;
-    kp.np_scores = ctx->d_np;
-    kp.max_n = ctx->max_n;
-    kp.max_l = ctx->max_l;
-    kp.r = r;
-    kp.tbstride = tbs;
-    kp.indel_start = a.indel_start;
-    kp.indel_extend = a.indel_extend;
-    hipError_t e = hipSuccess;
-    const int mc = (int)max_chunks;
-    switch (shape) {
-        case 1: e = launch_fill<1>(kp, mc, ctx->force_chunks, ctx->n_cus, s, overlapping, &ctx->fill_has_room); break;
-        case 2: e = launch_fill<2>(kp, mc, ctx->force_chunks, ctx->n_cus, s, overlapping, &ctx->fill_has_room); break;
-        case 3: e = launch_fill<3>(kp, mc, ctx->force_chunks, ctx->n_cus, s, overlapping, &ctx->fill_has_room); break;
-        case 4: e = launch_fill<4>(kp, mc, ctx->force_chunks, ctx->n_cus, s, overlapping, &ctx->fill_has_room); break;
-        case 5: e = launch_fill<5>(kp, mc, ctx->force_chunks, ctx->n_cus, s, overlapping, &ctx->fill_has_room); break;
-        case 6: e = launch_fill<6>(kp, mc, ctx->force_chunks, ctx->n_cus, s, overlapping, &ctx->fill_has_room); break;
-        case 7: e = launch_fill<7>(kp, mc, ctx->force_chunks, ctx->n_cus, s, overlapping, &ctx->fill_has_room); break;
-        case 8: e = launch_fill<8>(kp, mc, ctx->force_chunks, ctx->n_cus, s, overlapping, &ctx->fill_has_room); break;
-        case 9: case 10: case 11: case 12: case 13: case 14: case 15: case 16:
-            e = launch_fill<0>(kp, mc, ctx->force_chunks, ctx->n_cus, s, overlapping, &ctx->fill_has_room); break;
-        default: return fail(NPORE_E_UNSUPPORTED, "unsupported waves-per-chunk count");
-    }
-    if (e != hipSuccess) return fail(NPORE_E_HIP, std::string("fill launch: ") + hipGetErrorString(e));
-    HIP_TRY(hipEventRecord(w->ev[3], s));
-    // ---- traceback + gather: behind this group's fill, beside the next group's
-    s = ctx->s_post;
-    HIP_TRY(hipStreamWaitEvent(s, w->ev[3], 0));
-    HIP_TRY(hipEventRecord(w->ev[4], s));
-
-    TParams tp;
-    tp.descs = pp.descs;
-    tp.n_chunks = pp.counters;
-    tp.tb = kp.tb;
-    tp.inss = pp.inss;
-    tp.chunk_runs = w->cout_.as<uint32_t>();
-    tp.chunk_nruns = w->cnruns.as<int32_t>();
-    tp.chunk_len = w->clen.as<int32_t>();
-    tp.chunk_status = w->cstat.as<int32_t>();
-    tp.r = r;
-    tp.tbstride = tbs;
-    // (10 kb reads: 0.53 ms at 500 chunk slots, 0.83 ms at 8 000)
-    hipLaunchKernelGGL(traceback_rows_kernel, dim3((unsigned)max_chunks), dim3(64), 0, s, tp);
-    HIP_TRY(hipGetLastError());
-
-    GParams gp;
-    gp.descs = pp.descs;
-    gp.read_first_chunk = pp.rd_chunk_first;
-    gp.chunk_runs = tp.chunk_runs;
-    gp.chunk_nruns = tp.chunk_nruns;
-    gp.chunk_len = tp.chunk_len;
-    gp.chunk_status = tp.chunk_status;
-    gp.read_status_in = pp.rd_status;
-    gp.counters = pp.counters;
-    gp.seqs = pp.seqs;
-    gp.refs = pp.refs;
-    gp.out = got.d_out;
-    gp.out_off = got.d_out_off;
-    gp.out_len = got.d_out_len;
-    gp.status = got.d_status;
-    gp.read_base = out_read_base;
-    gp.n_reads = nr;
-    gp.chunk_woff = w->cwoff.as<int64_t>();
-    hipLaunchKernelGGL(gather_scan_kernel, dim3(rd_blocks), dim3(256), 0, s, gp);
-    if (a.final_text) {
-        StdKParams sp;
-        sp.descs = pp.descs;
-        sp.read_first_chunk = pp.rd_chunk_first;
-        sp.chunk_runs = tp.chunk_runs;
-        sp.chunk_nruns = tp.chunk_nruns;
-        sp.refs = pp.refs; sp.ref_off = pp.ref_off;
-        sp.seqs = pp.seqs; sp.seq_off = pp.seq_off;
-        sp.out = got.d_out;
-        sp.out_off = got.d_out_off;
-        sp.out_len = got.d_out_len;
-        sp.status = got.d_status;
-        sp.read_base = out_read_base;
-        sp.n_reads = nr;
-        if (a.bam) hipLaunchKernelGGL(standardize_words_kernel, dim3((unsigned)nr), dim3(64), 0, s, sp);
-        else hipLaunchKernelGGL(standardize_kernel, dim3((unsigned)nr), dim3(64), 0, s, sp);      // one wavefront per read
-        if (a.bam) {            // the group's records behind those of the groups before it (bam_emit_kernels.hpp)
-            if (!a.h_raw || !a.staged()) return fail(NPORE_E_INVALID, "internal: BAM records on the device need the device pack");
-            if (int rc = w->rec_off.ensure((size_t)nr * 8 + 64)) return rc;
-            if (int rc = w->rec_len.ensure((size_t)nr * 8 + 64)) return rc;
-            if (g0 == 0) HIP_TRY(hipMemsetAsync(a.bam->d_cursor, 0, 8, s));
-            const int64_t *d_off = w->in_off.as<int64_t>();
-            BamEmitParams bp;
-            bp.raw = w->in_raw.as<uint8_t>(); bp.raw_off = d_off + 4 * (nr + 1);
-            bp.ref_off = d_off; bp.seq_off = d_off + (nr + 1);
-            bp.hp = w->in_hp.as<int64_t>();
-            bp.words = got.d_out; bp.words_off = got.d_out_off; bp.words_len = got.d_out_len; bp.status = got.d_status;
-            bp.read_base = out_read_base; bp.n_reads = nr;
-            bp.recs = a.bam->d_recs; bp.cap = a.bam->cap; bp.cursor = a.bam->d_cursor;
-            bp.rec_off = w->rec_off.as<int64_t>(); bp.rec_len = w->rec_len.as<int64_t>();
-            hipLaunchKernelGGL(place_bam_records_kernel, dim3(1), dim3(256), 0, s, bp);
-            hipLaunchKernelGGL(emit_bam_records_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
-        } else if (a.compact) {        // the texts to the front of the batch's compact buffer (unpack_kernels.hpp)
-            if (int rc = w->coff.ensure((size_t)nr * 8 + 64)) return rc;
-            if (g0 == 0) HIP_TRY(hipMemsetAsync(a.compact->d_cursor, 0, 8, s));
-            CompactParams cp;
-            cp.out = got.d_out;
-            cp.out_off = got.d_out_off;
-            cp.out_len = got.d_out_len;
-            cp.read_base = out_read_base;
-            cp.n_reads = nr;
-            cp.ctext = a.compact->d_ctext;
-            cp.cursor = a.compact->d_cursor;
-            cp.coff = w->coff.as<int64_t>();
-            cp.cap = a.compact->cap;
-            hipLaunchKernelGGL(compact_texts_kernel, dim3((unsigned)nr), dim3(64), 0, s, cp);
-        }
-    } else
-    // LDS of gather_kernel: one tile of ops + (when a chunk's two base slices fit beside it) the slices
-    {
-        const int64_t rows_max = std::min<int64_t>(max_len, a.max_b_rows) + 1;    // longest slice of any chunk
-        if (beside_fill) {
-            gp.slice_cap = 0;
-            hipLaunchKernelGGL(gather_kernel<false>, dim3((unsigned)max_chunks), dim3(256), 0, s, gp);
-        } else {
-            gp.slice_cap = rows_max <= 24 * 1024 ? (int)((rows_max + 15) & ~(int64_t)15) : 0;
-            const size_t glds = (size_t)GATHER_TILE + 2 * (size_t)gp.slice_cap;
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(&gather_kernel<true>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds));
-            hipLaunchKernelGGL(gather_kernel<true>, dim3((unsigned)max_chunks), dim3(256), glds, s, gp);
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    if (a.staged()) {                   // download the group's slice of the results behind its gather
-        HIP_TRY(hipEventRecord(w->evc[2], s));
-        if (a.final_text && a.bam) {
-            HIP_TRY(hipMemcpyAsync(a.bam->h_rec_len + g0, w->rec_len.p, (size_t)nr * 8, hipMemcpyDeviceToHost, s));
-            if (g1 == a.n_reads) HIP_TRY(hipMemcpyAsync(a.bam->h_total, a.bam->d_cursor, 8, hipMemcpyDeviceToHost, s));
-        } else if (a.final_text && a.compact) {
-            HIP_TRY(hipMemcpyAsync(a.compact->h_coff + g0, w->coff.p, (size_t)nr * 8, hipMemcpyDeviceToHost, s));
-            if (g1 == a.n_reads && a.compact->h_bytes > 0)       // the batch's last group: the front of the compact buffer
-                HIP_TRY(hipMemcpyAsync(a.compact->h_ctext, a.compact->d_ctext, (size_t)a.compact->h_bytes, hipMemcpyDeviceToHost, s));
-        } else {
-            HIP_TRY(hipMemcpyAsync(a.h_out + a.h_out_off[g0], w->out.p, (size_t)(a.h_out_off[g1] - a.h_out_off[g0]), hipMemcpyDeviceToHost, s));
-        }
-        HIP_TRY(hipMemcpyAsync(a.h_out_len + g0, w->out_len.p, (size_t)nr * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(a.h_status + g0, w->status.p, (size_t)nr * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipEventRecord(w->evc[3], s));
-    }
-    HIP_TRY(hipMemcpyAsync(w->h_cnt.p, w->counters.p, 8, hipMemcpyDeviceToHost, s));    // chunk count, overflow flag
-    HIP_TRY(hipEventRecord(w->ev[5], s));
-    return NPORE_OK;
-}
-
-// Wait for a group that was enqueued into `w`, add its stage times to the context's timing and check its counters.
-int collect_group(npore_ctx *ctx, WorkSet *w)
-{
-    if (!w->busy) return NPORE_OK;
-    w->busy = false;
-    HIP_TRY(hipEventSynchronize(w->ev[5]));
-    if (w->call_id != ctx->timing_call) {       // first group of a newer call: npore_last_timing starts over
-        std::fill(ctx->timing, ctx->timing + 8, 0.0);
-        ctx->timing_call = w->call_id;
-    }
-    float ms = 0;
-    for (int k = 0; k < 3; k++) {
-        HIP_TRY(hipEventElapsedTime(&ms, w->ev[2 * k], w->ev[2 * k + 1]));
-        ctx->timing[k] += ms;
-        ctx->totals[k] += ms;
-    }
-    if (w->staged)
-        for (int k = 0; k < 2; k++) {
-            HIP_TRY(hipEventElapsedTime(&ms, w->evc[2 * k], w->evc[2 * k + 1]));
-            ctx->timing[3 + k] += ms;
-            ctx->totals[3 + k] += ms;
-        }
-    ctx->timing[6] += (double)w->cells; ctx->totals[6] += (double)w->cells;
-    ctx->timing[7] += 1; ctx->totals[7] += 1;
-    if (w->h_cnt.as<int32_t>()[1]) return fail(NPORE_E_HIP, "internal: chunk bound exceeded");
-    return NPORE_OK;
-}
-
-// Everything this context has in flight (asynchronous calls): collected oldest first.  Returns the first failure,
-// including one found earlier while a work set was being recycled.
-int quiesce(npore_ctx *ctx)
-{
-    int rc = ctx->deferred_rc;
-    std::string err = ctx->deferred_err;
-    for (int k = 0; k < N_SETS; k++) {
-        WorkSet *w = &ctx->ws[(ctx->next_ws + k) % N_SETS];
-        const int r2 = collect_group(ctx, w);
-        if (r2 && !rc) { rc = r2; err = g_err; }
-    }
-    ctx->deferred_rc = 0;
-    ctx->deferred_err.clear();
-    return rc ? fail(rc, err) : NPORE_OK;
-}
-
-// The batch, group by group, through the three-stage pipeline: the groups rotate through the N_SETS work sets, so
-// that group k+1 is prepared and group k-1 traced back while the fill kernel works on group k.  `user` (may be
-// NULL) is the caller's stream: the batch is ordered behind what it holds now.  sync = false returns once the
-// last group is enqueued (results complete when npore_ctx_wait returns, or for work put on `user` afterwards).
-int run_core(npore_ctx *ctx, const AlignArgs &a, const OutTarget &ot, hipStream_t user, bool sync)
-{
-    if (a.n_reads < 0) return fail(NPORE_E_INVALID, "n_reads < 0");
-    if (!ctx->d_sub || !ctx->d_np) return fail(NPORE_E_INVALID, "this context was created without penalty tables (annotation only)");
-    if (a.r < 1) return fail(NPORE_E_INVALID, "r must be >= 1");
-    if (!std::isfinite(a.indel_start) || !std::isfinite(a.indel_extend))
-        return fail(NPORE_E_INVALID, "indel_start and indel_extend must be finite");
-    if (a.max_b_rows < 2) return fail(NPORE_E_INVALID, "max_b_rows must be >= 2");
-    if (a.max_b_rows > 60000)
-        return fail(NPORE_E_UNSUPPORTED, "max_b_rows > 60000: run lengths are kept in 16 bits");
-    const int shape = pick_shape(a.r);
-    if (!shape) return fail(NPORE_E_UNSUPPORTED, "band half-width r > 511");
-    if (a.n_reads == 0) return NPORE_OK;
-    ctx->call_id++;
-    if (user) {
-        HIP_TRY(hipEventRecord(ctx->ev[0], user));
-        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev[0], 0));
-    }
-
-    // groups of consecutive reads whose traceback words fit the budget.  The automatic budget is this context's
-    // share of the device (contexts of one device run side by side: the file pipeline's peer, bench --inflight),
-    // divided by its N_SETS work sets: 60 % of the memory divided by the live contexts, and never more than what is
-    // free now plus what the context already holds.
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    const int live = std::max(1, g_live_ctx[ctx->device & 15].load());
-    size_t held = 0;
-    for (const auto &w0 : ctx->ws) held += w0.tb.cap;
-    const int64_t budget = ctx->tb_budget_mb > 0
-                               ? ctx->tb_budget_mb * (int64_t)1048576
-                               : (int64_t)(std::min(0.6 * (double)total_b / live, 0.9 * (double)(free_b + held)) / N_SETS);
-    const int tbs = tb_stride(a.r);
-    int64_t g0 = 0;
-    int64_t max_group = a.n_reads;       // halved when a group's buffers do not fit after all
-    WorkSet *last = nullptr;
-    while (g0 < a.n_reads) {
-        int64_t g1 = g0, acc = 0, cells = 0;
-        while (g1 < a.n_reads && g1 - g0 < max_group) {
-            const int64_t cl = a.h_cig_off[g1 + 1] - a.h_cig_off[g1];
-            // traceback words + the per-step / per-base side arrays (steps, inss, refw, refl, seqw, runs: < 48 B per op)
-            const int64_t need = (2 * cl + chunk_bound(cl, a.max_b_rows)) * tbs * 4 + 48 * cl;
-            if (g1 > g0 && acc + need > budget) break;
-            acc += need;
-            g1++;
-        }
-        // a group that is not the last one holds a whole number of launch-fulls of full-size chunks (about one per
-        // read): its fill kernel then ends on full chains instead of a sparse tail
-        if (g1 < a.n_reads) {
-            FillGeom fg;
-            if (fill_geometry(a.r, fg)) {
-                const int64_t full = (int64_t)fill_round_workgroups(fg, fg.cmax, ctx->n_cus) * fg.cmax;
-                if (g1 - g0 > full) g1 = g0 + (g1 - g0) / full * full;
-            }
-        }
-        cells = (a.h_seq_off[g1] - a.h_seq_off[g0] + a.h_ref_off[g1] - a.h_ref_off[g0] + (g1 - g0)) * (2 * a.r + 1);
-        WorkSet *w = &ctx->ws[ctx->next_ws];
-        if (int rc = collect_group(ctx, w)) {        // the set's previous group (N_SETS groups back) has to be through
-            if (!ctx->deferred_rc) { ctx->deferred_rc = rc; ctx->deferred_err = g_err; }
-        }
-        // (the other work set still busy: its group is in the fill or traceback stage while this one is prepared,
-        // and this group's gather will most likely run while the next one's fill is on the GPU)
-        bool beside = false;
-        for (int k = 1; k < N_SETS; k++) beside |= ctx->coresident && ctx->ws[(ctx->next_ws + k) % N_SETS].busy;
-        if (int rc = run_group(ctx, w, a, g0, g1, ot, shape, beside)) {
-            // drain what is in flight; a failure found there (an earlier group of this call, or of a previous
-            // sync = 0 call) is the older one and must not be lost: it stays deferred / is what the call returns
-            const std::string this_err = g_err;
-            const int older = quiesce(ctx);
-            if (rc == NPORE_E_NOMEM && g1 - g0 > 1) {          // another context got there first: smaller groups
-                if (older) { ctx->deferred_rc = older; ctx->deferred_err = g_err; }
-                max_group = (g1 - g0) / 2;
-                continue;
-            }
-            return older ? older : fail(rc, this_err);
-        }
-        for (auto &o : ctx->ws)
-            if (&o != w && !o.busy && o.tb.cap < w->tb.cap) o.presize_like(*w);
-        w->busy = true;
-        w->cells = cells;
-        w->call_id = ctx->call_id;
-        ctx->last_ws = last = w;
-        ctx->next_ws = (ctx->next_ws + 1) % N_SETS;
-        g0 = g1;
-    }
-    if (sync) return quiesce(ctx);
-    if (user && last) HIP_TRY(hipStreamWaitEvent(user, last->ev[5], 0));
-    return NPORE_OK;
-}
-
-// A batch in host buffers (a.h_*: filled by the caller, the three public entry points and the file pipeline): what all
-// of them refuse, then run_core.  Every group of reads uploads its own slice and downloads its own results (run_group):
-// the copies of one group run beside the kernels of its neighbours, and the caller's arrays are used as they are.
-// With a.h_raw, align()'s inputs are still inside BAM records: `h_raw` holds the heads of the records (fixed fields ...
-// 4-bit bases) one after the other, h_raw_off[n + 1] where each starts, and the three offset arrays are the sizes
-// pack_sizes_of found; every group unpacks its slice on the device (unpack_kernels.hpp) against the context's device
-// copy of the FASTA (device_fasta).
-int align_batch(npore_ctx *ctx, const AlignArgs &a, bool sync)
-{
-    if (!ctx) return fail(NPORE_E_INVALID, "null context");
-    if (a.n_reads < 0) return fail(NPORE_E_INVALID, "n_reads < 0");
-    if (a.n_reads == 0) return NPORE_OK;
-    const bool inputs = a.h_raw ? a.h_raw_off && a.d_ctg : a.h_refs && a.h_seqs && a.h_cigs;
-    if (!inputs || !a.h_out || !a.h_ref_off || !a.h_seq_off || !a.h_cig_off || !a.h_out_off || !a.h_out_len || !a.h_status)
-        return fail(NPORE_E_INVALID, "null argument");
-    if (!a.h_raw && a.h_out_off[a.n_reads] < a.h_out_off[0]) return fail(NPORE_E_INVALID, "out_off not ascending");
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (ctx->deferred_rc) return quiesce(ctx);   // a group of an earlier asynchronous call failed
-    return run_core(ctx, a, OutTarget{nullptr, nullptr, nullptr, nullptr}, nullptr, sync);
-}
-
-// AlignArgs of a batch whose offset arrays and output slots are the caller's (the inputs: h_refs ... or h_raw, by the caller)
-AlignArgs host_batch_args(int64_t n_reads, const int64_t *ref_off, const int64_t *seq_off, const int64_t *cig_off, float indel_start,
-                          float indel_extend, int max_b_rows, int r, char *out, const int64_t *out_off, int64_t *out_len, int32_t *status)
-{
-    AlignArgs a{n_reads, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ref_off, seq_off, cig_off,
-                indel_start, indel_extend, max_b_rows, r};
-    a.h_out = out; a.h_out_off = out_off; a.h_out_len = out_len; a.h_status = status;
-    return a;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -1026,15 +141,12 @@ try {
               hipStreamCreateWithFlags(&ctx->s_fill[0], hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&ctx->s_fill[1], hipStreamNonBlocking) == hipSuccess &&
               hipStreamCreateWithFlags(&ctx->s_post, hipStreamNonBlocking) == hipSuccess;
-    if (tables) {
-        ctx->h_sub.assign(sub_scores, sub_scores + 25);
-        ctx->h_np.assign(np_scores, np_scores + np_elems);
+    if (tables)
         ok = ok && hipMalloc((void **)&ctx->d_sub, 25 * sizeof(float)) == hipSuccess &&
              hipMalloc((void **)&ctx->d_np, np_elems * sizeof(float)) == hipSuccess &&
              hipMemcpy(ctx->d_sub, sub_scores, 25 * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
              hipMemcpy(ctx->d_np, np_scores, np_elems * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-    }
-    for (auto &e : ctx->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+    for (hipEvent_t *e : {&ctx->ev_user, &ctx->ev_cms[0], &ctx->ev_cms[1]}) ok = ok && hipEventCreate(e) == hipSuccess;
     for (auto &w : ctx->ws) {
         for (auto &e : w.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
         for (auto &e : w.evc) ok = ok && hipEventCreate(&e) == hipSuccess;
@@ -1052,28 +164,8 @@ void npore_ctx_destroy(npore_ctx *ctx)
 {
     if (!ctx) return;
     g_live_ctx[ctx->device & 15]--;
-    npore_ctx_destroy(ctx->peer);
     (void)hipSetDevice(ctx->device);
-    (void)hipDeviceSynchronize();       // nothing of this context may still be running
-    for (DevBuf *b : {&ctx->in_refs, &ctx->in_seqs, &ctx->in_cigs, &ctx->in_off, &ctx->out, &ctx->out_off, &ctx->out_len, &ctx->status,
-                      &ctx->d_fasta, &ctx->d_ctg, &ctx->cms_raw, &ctx->cms_off, &ctx->cms_ranges, &ctx->cms_counts})
-        b->release();
-    for (auto &w : ctx->ws) {
-        for (DevBuf *b : w.all) b->release();
-        w.h_cnt.release();
-        w.h_off.release();
-        for (auto &e : w.ev)
-            if (e) (void)hipEventDestroy(e);
-        for (auto &e : w.evc)
-            if (e) (void)hipEventDestroy(e);
-    }
-    ctx->h_offs.release();
-    if (ctx->d_sub) (void)hipFree(ctx->d_sub);
-    if (ctx->d_np) (void)hipFree(ctx->d_np);
-    for (auto &e : ctx->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipStream_t st : {ctx->stream, ctx->s_fill[0], ctx->s_fill[1], ctx->s_post})
-        if (st) (void)hipStreamDestroy(st);
+    (void)hipDeviceSynchronize();       // nothing of this context may still be running: only then do its members die
     for (auto *sp : ctx->slots) delete sp;
     delete ctx;
 }
@@ -1159,9 +251,13 @@ try {
     HIP_TRY(hipMemcpyAsync(offs + (n + 1), d_seq_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(offs + 2 * (n + 1), d_cig_off, (n + 1) * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    AlignArgs a{n, d_refs, d_ref_off, d_seqs, d_seq_off, d_cigars, d_cig_off,
-                offs, offs + (n + 1), offs + 2 * (n + 1),
-                indel_start, indel_extend, max_b_rows, r};
+    AlignArgs a;
+    a.n_reads = n;
+    a.d_refs = d_refs; a.d_ref_off = d_ref_off;
+    a.d_seqs = d_seqs; a.d_seq_off = d_seq_off;
+    a.d_cigs = d_cigars; a.d_cig_off = d_cig_off;
+    a.h_ref_off = offs; a.h_seq_off = offs + (n + 1); a.h_cig_off = offs + 2 * (n + 1);
+    a.indel_start = indel_start; a.indel_extend = indel_extend; a.max_b_rows = max_b_rows; a.r = r;
     OutTarget ot{reinterpret_cast<uint8_t *>(d_out), d_out_off, d_out_len, d_status};
     return run_core(ctx, a, ot, (hipStream_t)stream, sync != 0);
 }
@@ -1616,7 +712,8 @@ try {
         ht.t[CMS_T_BATCHES]++;
         const int64_t n = (int64_t)kept.size();
         if (n == 0) continue;
-        if (!raw.ensure((size_t)rawo[(size_t)n] + 64) || !rawo_pin.ensure((size_t)(n + 1) * 8)) return fail(NPORE_E_NOMEM, "batch buffers");
+        if (int rc = raw.ensure((size_t)rawo[(size_t)n] + 64)) return rc;
+        if (int rc = rawo_pin.ensure((size_t)(n + 1) * 8)) return rc;
         std::memcpy(rawo_pin.p, rawo.data(), (size_t)(n + 1) * 8);
         parallel_for((n + per - 1) / per, threads, [&](int64_t tix) {
             for (int64_t k = tix * per; k < std::min(n, (tix + 1) * per); k++) {
@@ -1651,13 +748,13 @@ try {
             cp.max_l = ctx->max_l;
             cp.min_bq = min_bq;
             cp.counts = ctx->cms_counts.as<unsigned long long>();
-            HIP_TRY(hipEventRecord(ctx->ev[1], s));
+            HIP_TRY(hipEventRecord(ctx->ev_cms[0], s));
             hipLaunchKernelGGL(confusion_records_kernel, dim3((unsigned)(k1 - k0)), dim3(256), 0, s, cp);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(ctx->ev[2], s));
+            HIP_TRY(hipEventRecord(ctx->ev_cms[1], s));
             HIP_TRY(hipStreamSynchronize(s));        // (the staging buffers and the planes are free again)
             float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[1], ctx->ev[2]));
+            HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_cms[0], ctx->ev_cms[1]));
             kernel_ms += ms;
             k0 = k1;
         }
@@ -1713,24 +810,23 @@ int64_t npore_debug_crc32(const uint8_t *p, int64_t n, uint32_t crc)
 
 int npore_debug_dpp(uint32_t *out128)
 {
-    uint32_t *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, 128 * 4));
-    hipLaunchKernelGGL(dpp_selftest_kernel, dim3(1), dim3(64), 0, 0, d);
+    DevBuf d;
+    if (int rc = d.ensure(128 * 4)) return rc;
+    hipLaunchKernelGGL(dpp_selftest_kernel, dim3(1), dim3(64), 0, 0, d.as<uint32_t>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out128, d, 128 * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d));
+    HIP_TRY(hipMemcpy(out128, d.p, 128 * 4, hipMemcpyDeviceToHost));
     return NPORE_OK;
 }
 
 int npore_debug_divcheck(int64_t *mismatches)
 {
-    unsigned long long *d = nullptr, h = 0;
-    HIP_TRY(hipMalloc((void **)&d, 8));
-    HIP_TRY(hipMemset(d, 0, 8));
-    hipLaunchKernelGGL(divcheck_kernel, dim3(256), dim3(256), 0, 0, d);
+    DevBuf d;
+    unsigned long long h = 0;
+    if (int rc = d.ensure(8)) return rc;
+    HIP_TRY(hipMemset(d.p, 0, 8));
+    hipLaunchKernelGGL(divcheck_kernel, dim3(256), dim3(256), 0, 0, d.as<unsigned long long>());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(&h, d, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipFree(d));
+    HIP_TRY(hipMemcpy(&h, d.p, 8, hipMemcpyDeviceToHost));
     *mismatches = (int64_t)h;
     return NPORE_OK;
 }
@@ -1931,8 +1027,9 @@ int slot_pack_records(const npore_bam *b, const npore_fasta *fa, const int32_t *
     s.olen.assign((size_t)n, 0);
     s.flen.assign((size_t)n, 0);
     pack_sizes_of(s.rf, n, s.ro.data(), s.so.data(), s.co.data(), threads);
-    if (!s.refs.ensure((size_t)s.ro[(size_t)n] + 64) || !s.seqs.ensure((size_t)s.so[(size_t)n] + 64) || !s.cigs.ensure((size_t)s.co[(size_t)n] + 64))
-        return fail(NPORE_E_NOMEM, "batch buffers");
+    if (int rc = s.refs.ensure((size_t)s.ro[(size_t)n] + 64)) return rc;
+    if (int rc = s.seqs.ensure((size_t)s.so[(size_t)n] + 64)) return rc;
+    if (int rc = s.cigs.ensure((size_t)s.co[(size_t)n] + 64)) return rc;
     if (!fa || !fasta_of_ref) return fail(NPORE_E_INVALID, "bad argument");
     if (int rc = pack_records(b, s.rf, fa, fasta_of_ref, n, reinterpret_cast<uint8_t *>(s.refs.p), s.ro.data(),
                               reinterpret_cast<uint8_t *>(s.seqs.p), s.so.data(), s.cigs.p, s.co.data(), threads, true))
@@ -1944,8 +1041,9 @@ int slot_pack_records(const npore_bam *b, const npore_fasta *fa, const int32_t *
         s.fo[(size_t)k + 1] = s.fo[(size_t)k] + 2 * cap + 16;
     }
     // (compact: the texts come back compacted -- file_pipeline --, no page-locked copy of the slots is needed)
-    if ((!compact && !s.alns.ensure((size_t)s.oo[(size_t)n] + 64)) || (!device_glue && !s.finals.ensure((size_t)s.fo[(size_t)n] + 64)))
-        return fail(NPORE_E_NOMEM, "batch buffers");
+    if (!compact)
+        if (int rc = s.alns.ensure((size_t)s.oo[(size_t)n] + 64)) return rc;
+    if (!device_glue && !s.finals.ensure((size_t)s.fo[(size_t)n] + 64)) return fail(NPORE_E_NOMEM, "batch buffers");     // (a RawBuf: hostio.hpp)
     return NPORE_OK;
 }
 // device pack: the sizes as above, and instead of the three arrays the HEADS of the records (block_size word, fixed fields,
@@ -1957,7 +1055,8 @@ int slot_pack_records(const npore_bam *b, const npore_fasta *fa, const int32_t *
 int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, int64_t n, int threads, npore_batch_slot &s, bool compact = false,
                   bool as_bam = false)
 {
-    if (as_bam && !s.hp_pin.ensure((size_t)n * 8 + 64)) return fail(NPORE_E_NOMEM, "batch buffers");
+    if (as_bam)
+        if (int rc = s.hp_pin.ensure((size_t)n * 8 + 64)) return rc;
     s.rec_cap = 0;
     for (auto *v : {&s.ro, &s.so, &s.co, &s.oo, &s.fo}) v->assign((size_t)n + 1, 0);
     s.rawo.assign((size_t)n + 1, 0);
@@ -1978,7 +1077,9 @@ int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, 
             s.rec_cap += 36 + r.l_read_name() + 4 * cap + 16 + (sl + 1) / 2 + sl + 7;
         }
     }
-    if (!s.raw.ensure((size_t)s.rawo[(size_t)n] + 64) || (!compact && !s.alns.ensure((size_t)s.oo[(size_t)n] + 64))) return fail(NPORE_E_NOMEM, "batch buffers");
+    if (int rc = s.raw.ensure((size_t)s.rawo[(size_t)n] + 64)) return rc;
+    if (!compact)
+        if (int rc = s.alns.ensure((size_t)s.oo[(size_t)n] + 64)) return rc;
     const int64_t per = 16;
     parallel_for((n + per - 1) / per, threads, [&](int64_t t) {
         for (int64_t k = t * per; k < std::min(n, (t + 1) * per); k++) {
@@ -2005,8 +1106,8 @@ int slot_align(npore_ctx *ctx, int64_t n, float indel_start, float indel_extend,
                              s.olen.data(), status);
 }
 // realign_read's glue (src/bam.pyx:65-78) and the SAM lines; reads refused by align() have no string and get an empty CIGAR
-int slot_post(const npore_bam *b, const int64_t *idx, int64_t n, const int32_t *status, int threads, npore_batch_slot &s,
-              double *ms_std = nullptr, bool device_glue = false, bool as_bam = false)
+int slot_post(const npore_bam *b, int64_t n, const int32_t *status, int threads, npore_batch_slot &s, double *ms_std = nullptr,
+              bool device_glue = false, bool as_bam = false)
 {
     // SAM text, or (a BAM-mode file run) the same reads' records
     auto format_into = [&](const char *finals, const int64_t *final_off) {
@@ -2024,7 +1125,7 @@ int slot_post(const npore_bam *b, const int64_t *idx, int64_t n, const int32_t *
                 if (s.flen[(size_t)k] > 0) extent = std::max(extent, coff[k] + s.flen[(size_t)k]);
             }
             if (extent > s.ctext_copied) {        // (texts far longer than usual: 0.5 bytes per base were sent with the batch)
-                if (!s.ctext_pin.ensure((size_t)extent + 64)) return fail(NPORE_E_NOMEM, "batch buffers");
+                if (int rc = s.ctext_pin.ensure((size_t)extent + 64)) return rc;
                 HIP_TRY(hipMemcpy(s.ctext_pin.p, s.d_ctext.p, (size_t)extent, hipMemcpyDeviceToHost));
                 s.ctext_copied = extent;
             }
@@ -2041,7 +1142,6 @@ int slot_post(const npore_bam *b, const int64_t *idx, int64_t n, const int32_t *
                                                        s.so[(size_t)k + 1] - s.so[(size_t)k], s.finals.p + s.fo[(size_t)k]);
     });
     if (ms_std) *ms_std = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    (void)idx;
     return format_into(s.finals.p, s.fo.data());
 }
 // BAM mode, records built on the device: nothing is formatted here -- the batch's bytes as they lie there, into page-locked
@@ -2063,7 +1163,7 @@ int slot_fetch_records(int64_t n, const int32_t *status, npore_batch_slot &s)
         sum += len[k];
     }
     if (sum != total) return fail(NPORE_E_HIP, "internal: BAM record sizes do not add up");
-    if (!s.recs_pin.ensure((size_t)total + 64)) return fail(NPORE_E_NOMEM, "batch buffers");
+    if (int rc = s.recs_pin.ensure((size_t)total + 64)) return rc;
     if (total > 0) HIP_TRY(hipMemcpy(s.recs_pin.p, s.d_recs.p, (size_t)total, hipMemcpyDeviceToHost));
     s.sam_len = total;
     return NPORE_OK;
@@ -2089,7 +1189,7 @@ try {
     b->stage_ms[1] = ms_since(t0);
     t0 = clk::now();
     double ms_std = 0.0;
-    const int rc = slot_post(b, idx, n, status, threads, s, &ms_std);
+    const int rc = slot_post(b, n, status, threads, s, &ms_std);
     b->stage_ms[2] = ms_std;
     b->stage_ms[3] = ms_since(t0) - ms_std;
     *sam = s.sam.p;
@@ -2242,7 +1342,7 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             t0 = std::chrono::steady_clock::now();
             double ms_std = 0.0;
             try {
-                t.rc = dev_bam ? slot_fetch_records(m, st, t) : slot_post(b, nullptr, m, st, post_threads, t, &ms_std, glue, bw != nullptr);
+                t.rc = dev_bam ? slot_fetch_records(m, st, t) : slot_post(b, m, st, post_threads, t, &ms_std, glue, bw != nullptr);
             } catch (const std::exception &e) {
                 fail(NPORE_E_NOMEM, std::string("SAM text of a batch: ") + e.what());
                 t.rc = NPORE_E_NOMEM;
@@ -2275,7 +1375,7 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
         if (s.m == 0) break;                                   // the source is exhausted
         start_pack(k + 2);
         const int64_t m = s.m;
-        if (!s.olen_pin.ensure((size_t)m * 8 + 64) || !s.st_pin.ensure((size_t)m * 4 + 64)) { rc = NPORE_E_NOMEM; err = "batch buffers"; break; }
+        if ((rc = s.olen_pin.ensure((size_t)m * 8 + 64)) || (rc = s.st_pin.ensure((size_t)m * 4 + 64))) { err = "batch buffers"; break; }
         if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) { rc = NPORE_E_HIP; err = "hipEventCreate"; break; }
         // (returns once the batch's groups are enqueued; waits only when all work sets of the context are still busy)
         mark("enqueue begins", k);
@@ -2285,15 +1385,15 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
         BamEmit emit{};
         s.ctext_copied = 0;
         if (dev_bam) {
-            if (s.d_recs.ensure((size_t)s.rec_cap + 64) || s.d_cursor.ensure(64) || !s.ctext_pin.ensure(64) || !s.reclen_pin.ensure((size_t)m * 8 + 64) ||
-                !s.total_pin.ensure(64)) { rc = NPORE_E_NOMEM; err = "batch buffers"; break; }
+            if ((rc = s.d_recs.ensure((size_t)s.rec_cap + 64)) || (rc = s.d_cursor.ensure(64)) || (rc = s.ctext_pin.ensure(64)) ||
+                (rc = s.reclen_pin.ensure((size_t)m * 8 + 64)) || (rc = s.total_pin.ensure(64))) { err = "batch buffers"; break; }
             emit = BamEmit{s.d_recs.as<uint8_t>(), s.rec_cap, s.d_cursor.as<unsigned long long>(), reinterpret_cast<const int64_t *>(s.hp_pin.p),
                            reinterpret_cast<int64_t *>(s.reclen_pin.p), reinterpret_cast<unsigned long long *>(s.total_pin.p)};
         } else if (glue) {
             // (a text takes whole 16-byte granules of the compact buffer: at most 15 bytes more than its slot)
             const int64_t slots = s.oo[(size_t)m] + 16 * m, bound = std::min(slots, slots / 4 + 4096);
-            if (s.d_ctext.ensure((size_t)slots + 64) || s.d_cursor.ensure(64) || !s.ctext_pin.ensure((size_t)bound + 64) ||
-                !s.coff_pin.ensure((size_t)m * 8 + 64)) { rc = NPORE_E_NOMEM; err = "batch buffers"; break; }
+            if ((rc = s.d_ctext.ensure((size_t)slots + 64)) || (rc = s.d_cursor.ensure(64)) || (rc = s.ctext_pin.ensure((size_t)bound + 64)) ||
+                (rc = s.coff_pin.ensure((size_t)m * 8 + 64))) { err = "batch buffers"; break; }
             cmp = TextCompact{s.d_ctext.as<uint8_t>(), s.d_cursor.as<unsigned long long>(), slots,
                               reinterpret_cast<int64_t *>(s.coff_pin.p), s.ctext_pin.p, bound};
             s.ctext_copied = bound;

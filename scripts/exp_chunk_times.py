@@ -4,7 +4,7 @@ Needs a THROWAWAY build of the library (LABNOTES round 5, "Why 8 000 reads per l
   kernels.hpp, fill_body: `const unsigned long long x_t0 = __builtin_amdgcn_s_memrealtime();` behind the chunk's slot is known, and
   behind `pbase += d.nrows;`: lane 0 of the chunk's first wave stores {x_t0, s_memrealtime(), s_getreg(HW_ID), s_getreg(XCC_ID),
   d.nrows, blockIdx.x} as eight 32-bit words at p.dbg + 8 * slot_id;
-  npore_api.cpp: `w->dbg.ensure(max_chunks * 32 + 64)` + a memset beside the other buffers of a group, and &w->dbg as selector 8
+  align_engine.hpp: `w->dbg.ensure(max_chunks * 32 + 64)` + a memset beside the other buffers of a group, and &w->dbg as selector 8
   of npore_debug_fetch.
     python scripts/exp_chunk_times.py ab_libs/libnpore_chunktime.so [reads=4000] [r=30]"""
 import os

@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 FAMILY_SETS = ["random", "grid", "equal", "recalc", "ulp", "inf_boundary"]
 SHAPE_SETS = ["random_6_100", "random_6_127", "random_4_20", "random_6_5", "random_3_31"]
 # the r of test_kernel_shapes and test_bands_of_nine_to_sixteen_waves plus 1, 5, 330, 360 and 470: a chunk of
-# ceil((2r + 1) / 64) waves (npore_api.cpp pick_shape) = 1 1 1 2 3 3 4 4 5 6 7 8 9 10 11 12 13 14 15 16, every count
+# ceil((2r + 1) / 64) waves (align_engine.hpp pick_shape) = 1 1 1 2 3 3 4 4 5 6 7 8 9 10 11 12 13 14 15 16, every count
 BANDS = [1, 5, 30, 40, 70, 95, 96, 100, 140, 170, 200, 230, 256, 300, 330, 360, 384, 447, 470, 511]
 MBRS = (20000, 333, 7)
 

@@ -330,6 +330,12 @@ int npore_bam_format_bam(npore_bam *bam, const int64_t *idx, int64_t n, const ch
  * "no record in this window" -- and whoever appends the part to the file shifts them (npore_amd/dist.py). */
 #define NPORE_OUT_PART 2
 #define NPORE_PART_BASE 65536
+/* flags: every member of the record stream is ONE dynamic-Huffman DEFLATE block of literals (no match search), or the
+ * stored block where that would not be smaller -- the rule of csrc/deflate_code.hpp.  The cuts, CRC-32, ISIZE and the
+ * header's members are as without the flag; members differ in size, and the index follows a table of their places.  The
+ * default file pipeline codes the whole members inside a batch on the device (csrc/bam_deflate_kernels.hpp), the host
+ * twin the rest.  NPORE_OUT_BAM only. */
+#define NPORE_OUT_DEFLATE 4
 int npore_bam_set_output(npore_bam *bam, int format, const char *bai_path, int flags);
 /* Of the last BAM-mode run on the handle: out4[0] records written, [1] bytes of the record stream, [2] 1 = the index was
  * written, 0 = none was asked for, -1 = the records were not in coordinate order (no index), [3] size of the file. */
@@ -436,6 +442,18 @@ int npore_debug_inflate_pair(const uint8_t *in_a, int64_t in_len_a, uint8_t *out
  * multiplication where the CPU has it): crc32(crc, p, n) of zlib, `crc` = the value so far (0 at the start).  Returns the
  * new value (0 ... 2^32 - 1) or a negative NPORE_E_* code.  Host code, no GPU. */
 int64_t npore_debug_crc32(const uint8_t *p, int64_t n, uint32_t crc);
+/* The host twin of NPORE_OUT_DEFLATE: the n <= 65 280 bytes at `in` as one whole BGZF member at `out` (cap >= n + 31
+ * always suffices).  Returns the member's size or a negative NPORE_E_* code.  Host code, no GPU. */
+int64_t npore_debug_deflate_member(const uint8_t *in, int64_t n, uint8_t *out, int64_t cap);
+/* The device side of NPORE_OUT_DEFLATE on a caller's buffer: the n bytes at `bytes` taken as a batch's records whose first
+ * byte lies at offset `phase` of the record stream (the first cut is (65 280 - phase % 65 280) % 65 280 bytes in), through
+ * the planning, placing and emitting kernels.  members / members_cap: the whole members inside the buffer, one after the
+ * other; sizes[k], k < sizes_cap: member k's bytes; head / tail (room for 65 280 bytes each): the raw bytes in front of the
+ * first cut and behind the last, as the post stage fetches them; info[5]: members, their bytes in all, head bytes, tail
+ * bytes, the device's stream position behind the call. */
+int npore_debug_deflate_device(npore_ctx *ctx, const uint8_t *bytes, int64_t n, int64_t phase, uint8_t *members,
+                               int64_t members_cap, uint32_t *sizes, int64_t sizes_cap, uint8_t *head, uint8_t *tail,
+                               int64_t *info);
 
 /* Debug self-test: out128[l] = value lane l receives from lane l-1 (l>0),
  * out128[64+l] = value from lane l+1 (l<63); checks the DPP wave-shift

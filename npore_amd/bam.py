@@ -291,6 +291,172 @@ def bgzf_stored(data):
     return b"".join(out)
 
 
+# ---- --bam_compress huffman: the Python statement of csrc/deflate_code.hpp (read the rule there) ---------------------
+_CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+_CL_EXTRA = {16: 2, 17: 3, 18: 7}
+
+
+def huffman_lengths(freq, limit):
+    """Code lengths (at most `limit` bits) of the symbols with freq > 0: Huffman's algorithm on the symbols in ascending
+    (freq, symbol) order with two queues -- a leaf before an internal node of equal weight --, the Kraft-sum repair for
+    trees deeper than `limit`, the longest lengths to the rarest symbols."""
+    order = sorted((f, s) for s, f in enumerate(freq) if f)
+    lens = [0] * len(freq)
+    m = len(order)
+    if m == 0:
+        return lens
+    if m == 1:
+        lens[order[0][1]] = 1
+        return lens
+    weight = [f for f, _ in order]              # leaves 0 .. m-1, then the internal nodes in order of creation
+    parent = [0] * (2 * m - 1)
+    leaf, node = 0, m
+    for new in range(m, 2 * m - 1):
+        w = 0
+        for _ in range(2):
+            if leaf < m and (node >= new or weight[leaf] <= weight[node]):
+                pick, leaf = leaf, leaf + 1
+            else:
+                pick, node = node, node + 1
+            parent[pick] = new
+            w += weight[pick]
+        weight.append(w)
+    depth = [0] * (2 * m - 1)
+    for k in range(2 * m - 3, -1, -1):
+        depth[k] = depth[parent[k]] + 1
+    count = [0] * (limit + 1)
+    for k in range(m):
+        count[min(depth[k], limit)] += 1
+    total = sum(count[l] << (limit - l) for l in range(1, limit + 1))
+    while total != 1 << limit:
+        count[limit] -= 1
+        for l in range(limit - 1, 0, -1):
+            if count[l]:
+                count[l] -= 1
+                count[l + 1] += 2
+                break
+        total -= 1
+    k = 0
+    for l in range(limit, 0, -1):
+        for _ in range(count[l]):
+            lens[order[k][1]] = l
+            k += 1
+    return lens
+
+
+def canonical_codes(lens):
+    """(length, code bit-reversed for an LSB-first stream) per symbol: RFC 1951 3.2.2."""
+    count = [0] * 17
+    for l in lens:
+        count[l] += 1
+    count[0] = 0
+    nxt, c = [0] * 17, 0
+    for l in range(1, 16):
+        c = (c + count[l - 1]) << 1
+        nxt[l] = c
+    out = []
+    for l in lens:
+        if not l:
+            out.append((0, 0))
+            continue
+        v, nxt[l] = nxt[l], nxt[l] + 1
+        out.append((l, int(format(v, "0%db" % l)[::-1], 2)))
+    return out
+
+
+def deflate_block(payload):
+    """(block bytes or None when it would not be smaller than the stored block, header bits, data bits) of the payload as
+    one final dynamic-Huffman block of literals."""
+    freq = np.bincount(np.frombuffer(payload, np.uint8), minlength=257).tolist()
+    freq[256] = 1
+    lens = huffman_lengths(freq, 15)
+    codes = canonical_codes(lens)
+    seq, cl_freq = [], [0] * 19
+    allv = lens + [0]                            # ... and the one distance code, of length 0
+    i = 0
+    while i < len(allv):
+        v, r = allv[i], 1
+        while i + r < len(allv) and allv[i + r] == v:
+            r += 1
+        i += r
+        if v == 0:
+            while r >= 11:
+                t = min(r, 138)
+                seq.append((18, t - 11))
+                r -= t
+            if r >= 3:
+                seq.append((17, r - 3))
+                r = 0
+        else:
+            seq.append((v, 0))
+            r -= 1
+            while r >= 3:
+                t = min(r, 6)
+                seq.append((16, t - 3))
+                r -= t
+        seq += [(v, 0)] * r
+    for s, _ in seq:
+        cl_freq[s] += 1
+    cl_lens = huffman_lengths(cl_freq, 7)
+    cl_codes = canonical_codes(cl_lens)
+    hclen = max([4] + [k + 1 for k in range(19) if cl_lens[_CL_ORDER[k]]])
+    acc, nbits = 0, 0
+
+    def put(v, n):
+        nonlocal acc, nbits
+        acc |= v << nbits
+        nbits += n
+    put(1, 1), put(2, 2), put(0, 5), put(0, 5), put(hclen - 4, 4)
+    for k in range(hclen):
+        put(cl_lens[_CL_ORDER[k]], 3)
+    for s, extra in seq:
+        put(cl_codes[s][1], cl_codes[s][0])
+        if s >= 16:
+            put(extra, _CL_EXTRA[s])
+    header_bits = nbits
+    data_bits = sum(f * l for f, l in zip(freq, lens))
+    n_bytes = (header_bits + data_bits + 7) // 8
+    if n_bytes >= len(payload) + 5:
+        return None, header_bits, data_bits
+    # the data bits with numpy: every code at its bit offset
+    sym = np.concatenate([np.frombuffer(payload, np.uint8).astype(np.int64), [256]])
+    ln = np.array([c[0] for c in codes], np.int64)[sym]
+    cd = np.array([c[1] for c in codes], np.int64)[sym]
+    at = header_bits + np.concatenate([[0], np.cumsum(ln)[:-1]])
+    bits = np.zeros(n_bytes * 8, np.uint8)
+    hb = np.array([(acc >> k) & 1 for k in range(header_bits)], np.uint8)
+    bits[:header_bits] = hb
+    for b in range(15):
+        use = ln > b
+        bits[at[use] + b] = (cd[use] >> b) & 1
+    return np.packbits(bits, bitorder="little").tobytes(), header_bits, data_bits
+
+
+def deflate_member(payload):
+    """One BGZF member (at most BGZF_STORED_PAYLOAD bytes of payload) in --bam_compress huffman: one dynamic-Huffman block
+    of literals, or the stored member where that is not smaller (and for an empty payload)."""
+    payload = bytes(payload)
+    n = len(payload)
+    block = deflate_block(payload)[0] if n else None
+    if block is None:
+        return _stored_member(payload)
+    return (struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 0xFF, 6, 66, 67, 2, len(block) + 25) + block +
+            struct.pack("<II", zlib.crc32(payload), n))
+
+
+def _stored_member(chunk):
+    n = len(chunk)
+    return (struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 0xFF, 6, 66, 67, 2, n + 30) +
+            struct.pack("<BHH", 1, n, n ^ 0xFFFF) + chunk + struct.pack("<II", zlib.crc32(chunk), n))
+
+
+def bgzf_members(data, compress="none"):
+    """`data` cut every BGZF_STORED_PAYLOAD bytes, each piece a member of the mode."""
+    if compress == "none":
+        return bgzf_stored(data)
+    return b"".join(deflate_member(data[p:p + BGZF_STORED_PAYLOAD]) for p in range(0, len(data), BGZF_STORED_PAYLOAD))
+
+
 def bam_header_bytes(text, references, lengths):
     out = bytearray(b"BAM\1" + struct.pack("<i", len(text.encode())) + text.encode() + struct.pack("<i", len(references)))
     for n, l in zip(references, lengths):
@@ -315,8 +481,8 @@ class BamRecordWriter:
     member, the EOF member and -- when the records came in coordinate order -- `bai` (write_bai with its bins).  Whole
     files only: --python_io runs in one process."""
 
-    def __init__(self, path, bai=None):
-        self.path, self.bai = path, bai
+    def __init__(self, path, bai=None, compress="none"):
+        self.path, self.bai, self.compress = path, bai, compress
         self.fh = open(path, "ab")
         self.carry = b""
         self.sorted, self.last = True, (-1, -1)
@@ -331,12 +497,12 @@ class BamRecordWriter:
             self.n_records += 1
         data = self.carry + b"".join(records)
         whole = len(data) - len(data) % BGZF_STORED_PAYLOAD
-        self.fh.write(bgzf_stored(data[:whole]))
+        self.fh.write(bgzf_members(data[:whole], self.compress))
         self.carry = data[whole:]
 
     def close(self):
         """Returns True when the index was written (or none was asked for)."""
-        self.fh.write(bgzf_stored(self.carry))
+        self.fh.write(bgzf_members(self.carry, self.compress))
         self.fh.write(BGZF_EOF)
         self.fh.close()
         if self.bai and self.sorted:
@@ -734,13 +900,20 @@ class NativeBam:
                                                    fl.ctypes.data, st.ctypes.data, threads, C.byref(recs), C.byref(recs_len)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def set_output(self, out_format="sam", bai=None, eof=True):
+    def set_output(self, out_format="sam", bai=None, eof=True, compress="none"):
         """What the NEXT realign_file / realign_sequential / write_file on this handle appends to its output path
         (npore_bam_set_output; the setting holds for that one run): "sam", or "bam" -- records in stored BGZF members behind
         what lies in the file (the header's members: create_bam_header) and `bai` written when the records went out in
         coordinate order.  eof: the run ends the file (the EOF member); False: it writes one rank's PART -- no EOF member,
-        and `bai` is a sidecar whose offsets count from PART_BASE (dist.gather_bam_parts shifts and merges them)."""
+        and `bai` is a sidecar whose offsets count from PART_BASE (dist.gather_bam_parts shifts and merges them).
+        compress: "none", stored members, or "huffman", every member one dynamic-Huffman block of literals
+        (NPORE_OUT_DEFLATE; "bam" only)."""
+        if compress not in ("none", "huffman"):
+            raise ValueError("compress must be 'none' or 'huffman'")
+        if compress != "none" and out_format != "bam":
+            raise ValueError("compress needs out_format 'bam'")
         flags = 0 if out_format != "bam" else 1 if eof else 2       # NPORE_OUT_EOF / NPORE_OUT_PART
+        flags |= 4 if compress == "huffman" else 0                  # NPORE_OUT_DEFLATE
         self._check(self._lib.npore_bam_set_output(self.handle, {"sam": 0, "bam": 1}[out_format], os.fsencode(bai) if bai else None, flags))
 
     def output_info(self):
@@ -754,7 +927,7 @@ class NativeBam:
         if out_format == "bam" and self.output_info()["indexed"] < 0:
             print(NOT_SORTED_MSG)
 
-    def write_file(self, idx, finals, status, out_path, batch_reads=4000, threads=0, bai=None, eof=True):
+    def write_file(self, idx, finals, status, out_path, batch_reads=4000, threads=0, bai=None, eof=True, compress="none"):
         """The host's part of a BAM-mode run alone (npore_bam_write_file, no GPU): the selected reads with their final
         CIGARs as records, made in batches of batch_reads and appended to out_path."""
         idx = np.ascontiguousarray(idx, np.int64)
@@ -765,7 +938,7 @@ class NativeBam:
         fl = np.ascontiguousarray(np.diff(fo))
         buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
         st = np.ascontiguousarray(status, np.int32)
-        self.set_output("bam", bai, eof)
+        self.set_output("bam", bai, eof, compress)
         self._check(self._lib.npore_bam_write_file(self.handle, idx.ctypes.data, n, int(batch_reads), buf.ctypes.data, fo.ctypes.data,
                                                    fl.ctypes.data, st.ctypes.data, threads, os.fsencode(out_path)))
         self._after_bam_run("bam")
@@ -795,7 +968,8 @@ class NativeBam:
         return tuple(int(x) for x in info)
 
     def realign_sequential(self, ctx, fasta, regions, out_path, batch_reads=4000, max_reads=0, r=30, max_b_rows=20000,
-                           indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, out_format="sam", bai=None, eof=True):
+                           indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, out_format="sam", bai=None, eof=True,
+                           compress="none"):
         """ONE PASS over the file: inflate, filter by `regions` [(contig, start, stop)] (at most one per contig, in header
         order), batch, realign, write -- npore_bam_realign_sequential.  Returns (reads selected, [(ordinal, status)] of
         the first bad reads, (refused, inconsistent)); raises OnePassUnsupported when the regions or the file's
@@ -810,7 +984,7 @@ class NativeBam:
         counts = np.zeros(3, np.int64)
         bad_ord, bad_st = np.zeros(max(bad_cap, 1), np.int64), np.zeros(max(bad_cap, 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof)
+        self.set_output(out_format, bai, eof, compress)
         rc = self._lib.npore_bam_realign_sequential(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, len(regions), rid.ctypes.data,
                                                     beg.ctypes.data, end.ctypes.data, int(max_reads or 0), int(batch_reads), indel_start,
                                                     indel_extend, max_b_rows, r, threads, os.fsencode(out_path), counts.ctypes.data,
@@ -842,14 +1016,14 @@ class NativeBam:
         return (memoryview((C.c_char * sam_len.value).from_address(sam.value)) if sam_len.value else memoryview(b"")), st[:n]
 
     def realign_file(self, ctx, fasta, idx, out_sam, batch_reads=4000, r=30, max_b_rows=20000, indel_start=5.0,
-                     indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True):
+                     indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none"):
         """All selected reads, batch by batch, appended to out_sam by the library with packing, GPU work and
         formatting/writing of neighbouring batches overlapped.  Returns status[n].
         out_format / bai / eof: set_output for this run ("bam": records instead of text)."""
         idx = np.ascontiguousarray(idx, np.int64)
         st = np.zeros(max(len(idx), 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof)
+        self.set_output(out_format, bai, eof, compress)
         self._check(self._lib.npore_bam_realign_file(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data,
                                                      len(idx), int(batch_reads), indel_start, indel_extend, max_b_rows, r,
                                                      threads, os.fsencode(out_sam), st.ctypes.data))
@@ -896,7 +1070,7 @@ class NativeBam:
 
 
 def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0, out_format="sam", bai=None,
-                   eof=True):
+                   eof=True, compress="none"):
     """realign_reads() through the library; returns the number of reads handed in.  batch_reads > 0: the whole
     index list in overlapped batches written by the library itself; 0: one batch, text written here.
     threads: host threads of the parallel host stages (0 = all cores; one process per GPU: dist.host_threads_per_rank).
@@ -907,7 +1081,7 @@ def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_
         return 0
     if batch_reads > 0:
         text, status = None, bam.realign_file(ctx, fasta, idx, out_sam, batch_reads=batch_reads, r=r, max_b_rows=max_b_rows,
-                                              threads=threads, out_format=out_format, bai=bai, eof=eof)
+                                              threads=threads, out_format=out_format, bai=bai, eof=eof, compress=compress)
     else:
         text, status = bam.realign_batch(ctx, fasta, idx, r=r, max_b_rows=max_b_rows, threads=threads)
     bad = np.nonzero(status)[0]

@@ -11,6 +11,7 @@
 #include "annot_wave.hpp"
 #include "unpack_kernels.hpp"
 #include "bam_emit_kernels.hpp"
+#include "bam_deflate_kernels.hpp"
 
 using namespace npore;
 
@@ -34,6 +35,12 @@ struct BamEmit {
     const int64_t *h_hp;         // [n_reads] page-locked: the reads' HP values
     int64_t *h_rec_len;          // [n_reads] page-locked: bytes of every read's record (0: not written)
     unsigned long long *h_total; // page-locked: bytes of the batch's records
+    // NPORE_OUT_DEFLATE (bam_deflate_kernels.hpp; deflate false: stored members, nothing more on the device): the three
+    // kernels' arguments, and where the member-size table and the batch's four numbers come down with the last group
+    bool deflate = false;
+    DeflateParams dfl{};
+    uint32_t *h_sizes = nullptr; // [dfl.max_members] page-locked
+    int64_t *h_info = nullptr;   // [4] page-locked: DeflateParams::info
 };
 
 struct npore_batch_slot;        // a batch of the BAM -> SAM pipeline (npore_api.cpp)
@@ -113,6 +120,7 @@ struct npore_ctx {
     int device_pack = 1;        // BAM -> SAM pipeline with the glue on the device: align()'s inputs unpacked from the records on the device
     // device pack: the FASTA of the current run on the device (uploaded once per FASTA), the contig of every BAM reference
     DevBuf d_fasta, d_ctg;
+    DevBuf d_stream_pos;        // BAM out, NPORE_OUT_DEFLATE: where the next batch's records begin in the run's record stream (8 bytes)
     // recount of the confusion matrices from BAM records (npore_bam_confusion): the batch's record heads and their offsets,
     // the current contig's ranges, the counters
     DevBuf cms_raw, cms_off, cms_ranges, cms_counts;
@@ -514,6 +522,16 @@ int fill_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs &
     return NPORE_OK;
 }
 
+// NPORE_OUT_DEFLATE: the whole members inside a batch's record bytes, coded (bam_deflate_kernels.hpp).  The grids cover the
+// most members the record buffer can hold; the kernels find on the device how many there are.
+inline void launch_deflate(const DeflateParams &dp, hipStream_t s)
+{
+    if (dp.max_members <= 0) return;
+    hipLaunchKernelGGL(plan_deflate_kernel, dim3((unsigned)dp.max_members), dim3(64), 0, s, dp);
+    hipLaunchKernelGGL(place_deflate_kernel, dim3(1), dim3(256), 0, s, dp);
+    hipLaunchKernelGGL(emit_deflate_kernel, dim3((unsigned)dp.max_members + 2), dim3(64), 0, s, dp);      // (+ 2: the fragments)
+}
+
 // Traceback + output, behind this group's fill and beside the next group's; the tail is chosen by the plan's OutMode
 int post_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs &a, const PrepParams &pp, const OutTarget &out, bool beside_fill)
 {
@@ -578,6 +596,7 @@ int post_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs &
         bp.rec_off = w->rec_off.as<int64_t>(); bp.rec_len = w->rec_len.as<int64_t>();
         hipLaunchKernelGGL(place_bam_records_kernel, dim3(1), dim3(256), 0, s, bp);
         hipLaunchKernelGGL(emit_bam_records_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
+        if (a.bam->deflate && p.g1 == a.n_reads) launch_deflate(a.bam->dfl, s);      // the batch's records are complete
     } else if (p.mode == OutMode::CompactText) {  // the texts to the front of the batch's compact buffer (unpack_kernels.hpp)
         if (p.g0 == 0) HIP_TRY(hipMemsetAsync(a.compact->d_cursor, 0, 8, s));
         CompactParams cp;
@@ -601,6 +620,10 @@ int download_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignAr
         if (p.mode == OutMode::BamRecords) {
             HIP_TRY(hipMemcpyAsync(a.bam->h_rec_len + g0, w->rec_len.p, (size_t)nr * 8, hipMemcpyDeviceToHost, s));
             if (p.g1 == a.n_reads) HIP_TRY(hipMemcpyAsync(a.bam->h_total, a.bam->d_cursor, 8, hipMemcpyDeviceToHost, s));
+            if (p.g1 == a.n_reads && a.bam->deflate) {
+                HIP_TRY(hipMemcpyAsync(a.bam->h_info, a.bam->dfl.info, 32, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(a.bam->h_sizes, a.bam->dfl.sizes, (size_t)a.bam->dfl.max_members * 4, hipMemcpyDeviceToHost, s));
+            }
         } else if (p.mode == OutMode::CompactText) {
             HIP_TRY(hipMemcpyAsync(a.compact->h_coff + g0, w->coff.p, (size_t)nr * 8, hipMemcpyDeviceToHost, s));
             if (p.g1 == a.n_reads && a.compact->h_bytes > 0)       // the batch's last group: the front of the compact buffer

@@ -6,6 +6,7 @@
 #pragma once
 #include "../../include/npore_amd.h"
 #include "hostio.hpp"
+#include "deflate_code.hpp"
 
 #include <sys/uio.h>
 
@@ -770,14 +771,27 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     return NPORE_OK;
 }
 
-// The BAM index of a record stream written in stored members of BGZF_STORED_PAYLOAD bytes: every member but the last
-// has the same size, so a record's virtual offset follows from its offset in the stream and where the first member lies.
+// The BAM index of a record stream cut into members every BGZF_STORED_PAYLOAD bytes: a record's virtual offset follows
+// from its offset u in the stream and the file offset of member u / BGZF_STORED_PAYLOAD.  The members may differ in size
+// (stored or Huffman-coded), so the builder keeps stream offsets and a table of the members' places, which the writer
+// fills as it writes them (member_at); write() maps the one to the other.  An offset on a cut is the next member's first
+// byte; behind the last member that is where the writer says the next one would lie (end_at: finish()).
 class BaiBuilder {
 public:
-    void reset(size_t n_ref, uint64_t base) { refs_.assign(n_ref, Ref{}); base_ = base; sorted_ = true; last_ref_ = -1; last_pos_ = INT64_MIN; }
+    void reset(size_t n_ref, uint64_t base)
+    {
+        refs_.assign(n_ref, Ref{});
+        base_ = end_ = base;
+        member_off_.clear();
+        sorted_ = true; last_ref_ = -1; last_pos_ = INT64_MIN;
+    }
+    uint64_t base() const { return base_; }
+    void member_at(uint64_t off) { member_off_.push_back(off); }      // in the index's coordinates (base() + bytes written)
+    void end_at(uint64_t off) { end_ = off; }
     uint64_t voffset(uint64_t u) const
     {
-        return (base_ + (u / BGZF_STORED_PAYLOAD) * (BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD)) << 16 | (u % BGZF_STORED_PAYLOAD);
+        const size_t k = (size_t)(u / BGZF_STORED_PAYLOAD);
+        return (k < member_off_.size() ? member_off_[k] : end_) << 16 | (u % BGZF_STORED_PAYLOAD);
     }
     void add(const BamRecMeta &m, uint64_t u)         // the record at stream offset u
     {
@@ -786,7 +800,7 @@ public:
         last_pos_ = m.pos;
         if (m.ref < 0 || (size_t)m.ref >= refs_.size() || !sorted_) return;
         Ref &r = refs_[(size_t)m.ref];
-        const uint64_t v0 = voffset(u), v1 = voffset(u + (uint64_t)m.bytes);
+        const uint64_t v0 = u, v1 = u + (uint64_t)m.bytes;           // (stream offsets: write() maps them)
         const int64_t end = (int64_t)m.pos + std::max<int64_t>(1, m.span);
         auto &chunks = r.bins[bam_reg2bin(m.pos, end)];
         if (!chunks.empty() && chunks.back().second == v0) chunks.back().second = v1;
@@ -794,7 +808,7 @@ public:
         const size_t w0 = (size_t)(std::max<int64_t>(0, m.pos) >> 14), w1 = (size_t)(std::max<int64_t>(0, end - 1) >> 14);
         if (r.lin.size() <= w1) r.lin.resize(w1 + 1, 0);
         for (size_t w = w0; w <= w1; w++)
-            if (!r.lin[w]) r.lin[w] = v0;
+            if (!r.lin[w]) r.lin[w] = v0 + 1;                        // (0: no record in this window)
     }
     bool sorted() const { return sorted_; }
     bool write(const char *path) const                // complete, or not there at all
@@ -808,11 +822,11 @@ public:
             for (const auto &bn : r.bins) {
                 p32(bn.first);
                 p32((uint32_t)bn.second.size());
-                for (const auto &c : bn.second) { p64(c.first); p64(c.second); }
+                for (const auto &c : bn.second) { p64(voffset(c.first)); p64(voffset(c.second)); }
             }
             p32((uint32_t)r.lin.size());
             uint64_t last = 0;
-            for (uint64_t v : r.lin) { if (v) last = v; p64(last); }       // (windows without a record: the entry before)
+            for (uint64_t v : r.lin) { if (v) last = voffset(v - 1); p64(last); }       // (windows without a record: the entry before)
         }
         const std::string tmp = std::string(path) + ".tmp" + std::to_string((long long)::getpid());
         FILE *fh = std::fopen(tmp.c_str(), "wb");
@@ -828,16 +842,20 @@ private:
         std::vector<uint64_t> lin;
     };
     std::vector<Ref> refs_;
-    uint64_t base_ = 0;
+    uint64_t base_ = 0, end_ = 0;
+    std::vector<uint64_t> member_off_;       // where member k of the record stream lies
     bool sorted_ = true;
     int32_t last_ref_ = -1;
     int64_t last_pos_ = INT64_MIN;
 };
 
-// Appends a record stream to a file as stored BGZF members (the FILE rules above): add() takes a batch's record bytes as
-// they lie -- the members' payload goes out from the caller's buffer (writev), only the tail that does not fill a member
-// is kept for the next batch -- and does the index bookkeeping; finish() writes the last member, the EOF member if asked
-// for, and the index.  One thread at a time (the file pipeline's ordered write step).
+// Appends a record stream to a file as BGZF members (the FILE rules above): add() takes a batch's record bytes as
+// they lie -- stored members' payload goes out from the caller's buffer (writev), only the tail that does not fill a
+// member is kept for the next batch -- and does the index bookkeeping; finish() writes the last member, the EOF member if
+// asked for, and the index.  deflate (NPORE_OUT_DEFLATE): every member is coded by deflate_code.hpp's host twin, on
+// `threads` threads -- or comes ready-made from the device (add_coded), which codes the whole members that lie inside a
+// batch; the one member that straddles two batches is joined and coded here.  One thread at a time (the file pipeline's
+// ordered write step).
 class BgzfStoredWriter {
 public:
     BgzfStoredWriter() = default;
@@ -847,7 +865,7 @@ public:
     // the file is appended to: what lies there already (the header's members) stays
     // part: a rank's part of a file -- the index counts its offsets from a nominal first member at NPORE_PART_BASE, so
     // that none is 0, which a .bai takes for "no record in this window"; whoever appends the part shifts them
-    int open(const char *path, size_t n_ref, const char *bai_path, bool eof_member, bool part = false)
+    int open(const char *path, size_t n_ref, const char *bai_path, bool eof_member, bool part = false, bool deflate = false, int threads = 1)
     {
         fd_ = ::open(path, O_WRONLY | O_CREAT | O_APPEND, 0666);
         if (fd_ < 0) return fail(NPORE_E_INVALID, std::string("cannot open '") + path + "' for appending");
@@ -856,21 +874,20 @@ public:
         base_ = (uint64_t)st.st_size;
         bai_path_ = bai_path ? bai_path : "";
         eof_ = eof_member;
+        deflate_ = deflate;
+        threads_ = threads;
         index_.reset(n_ref, part ? (uint64_t)NPORE_PART_BASE : base_);
         carry_.reserve(BGZF_STORED_PAYLOAD);
         return NPORE_OK;
     }
+    bool deflate() const { return deflate_; }
+    uint64_t stream_bytes() const { return stream_; }
     int add(const uint8_t *bytes, int64_t len, const BamRecMeta *meta, int64_t n_rec)
     {
-        uint64_t u = stream_;
-        for (int64_t k = 0; k < n_rec; k++) { index_.add(meta[k], u); u += (uint64_t)meta[k].bytes; }
-        if (u != stream_ + (uint64_t)len) return fail(NPORE_E_INVALID, "internal: record sizes do not add up to the batch's bytes");
-        n_rec_ += n_rec;
-        stream_ = u;
+        if (int rc = index_records(len, meta, n_rec)) return rc;
         size_t at = 0;
         const size_t N = (size_t)len;
-        heads_.clear();
-        iov_.clear();
+        begin_members();
         if (!carry_.empty() && carry_.size() + N >= BGZF_STORED_PAYLOAD) {      // the member begun by the batch before
             const size_t take = BGZF_STORED_PAYLOAD - carry_.size();
             member(carry_.data(), carry_.size(), bytes, take);
@@ -879,19 +896,49 @@ public:
         const bool carried = at > 0;
         if (carry_.empty() || carried)
             for (; N - at >= BGZF_STORED_PAYLOAD; at += BGZF_STORED_PAYLOAD) member(bytes + at, BGZF_STORED_PAYLOAD, nullptr, 0);
-        if (int rc = flush_iov()) return rc;
+        if (int rc = flush_members()) return rc;
         if (carried) carry_.clear();
         carry_.insert(carry_.end(), bytes + at, bytes + N);
+        return NPORE_OK;
+    }
+    // A batch from the device (deflate mode): the bytes in front of the stream's first cut inside the batch (head: they
+    // end the member begun by the batches before, or are all the batch has), the whole members behind it ready-made, one
+    // after the other, member k of sizes[k] bytes, and the bytes behind the last cut (tail).
+    int add_coded(const uint8_t *head, int64_t head_len, const uint8_t *members, const uint32_t *sizes, int64_t n_members,
+                  const uint8_t *tail, int64_t tail_len, const BamRecMeta *meta, int64_t n_rec)
+    {
+        const size_t want = (BGZF_STORED_PAYLOAD - carry_.size() % BGZF_STORED_PAYLOAD) % BGZF_STORED_PAYLOAD;
+        if (head_len < 0 || tail_len < 0 || n_members < 0 || tail_len >= (int64_t)BGZF_STORED_PAYLOAD ||
+            ((n_members > 0 || tail_len > 0) ? (size_t)head_len != want : (size_t)head_len > want) )
+            return fail(NPORE_E_INVALID, "internal: a batch's coded members do not fit the stream's cuts");
+        if (int rc = index_records(head_len + n_members * (int64_t)BGZF_STORED_PAYLOAD + tail_len, meta, n_rec)) return rc;
+        begin_members();
+        carry_.insert(carry_.end(), head, head + head_len);
+        const bool joined = carry_.size() == BGZF_STORED_PAYLOAD;
+        if (joined) member(carry_.data(), carry_.size(), nullptr, 0);
+        size_t at = 0;
+        for (int64_t k = 0; k < n_members; k++) {
+            if (sizes[k] < 28 || sizes[k] > BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD) return fail(NPORE_E_INVALID, "internal: bad size of a coded member");
+            jobs_.push_back(Job{nullptr, 0, nullptr, 0, members + at, sizes[k]});
+            at += sizes[k];
+        }
+        if (int rc = flush_members()) return rc;
+        if (joined) carry_.clear();
+        carry_.insert(carry_.end(), tail, tail + tail_len);
         return NPORE_OK;
     }
     // info[4]: records, payload bytes, 1 = an index was written / 0 = none asked for / -1 = not in coordinate order, file size
     int finish(int64_t *info)
     {
-        heads_.clear();
-        iov_.clear();
+        begin_members();
         if (!carry_.empty()) member(carry_.data(), carry_.size(), nullptr, 0);
-        if (eof_) { iov_.push_back(iovec{const_cast<uint8_t *>(BGZF_EOF_MEMBER), 28}); file_bytes_ += 28; }
-        if (int rc = flush_iov()) return rc;
+        if (int rc = flush_members()) return rc;
+        index_.end_at(index_.base() + file_bytes_);
+        if (eof_) {
+            iov_.push_back(iovec{const_cast<uint8_t *>(BGZF_EOF_MEMBER), 28});
+            file_bytes_ += 28;
+            if (int rc = flush_iov()) return rc;
+        }
         carry_.clear();
         const int rcc = ::close(fd_);
         fd_ = -1;
@@ -908,8 +955,60 @@ public:
 
 private:
     struct Head { uint8_t h[23], t[8]; };
-    // one member of a + b bytes (b may be empty) queued for the next writev
-    void member(const uint8_t *a, size_t na, const uint8_t *b, size_t nb)
+    // a member to be written: the payload a + b (b may be empty), or (ready != null) a member as it is
+    struct Job { const uint8_t *a; size_t na; const uint8_t *b; size_t nb; const uint8_t *ready; size_t n_ready; };
+    int index_records(int64_t len, const BamRecMeta *meta, int64_t n_rec)
+    {
+        uint64_t u = stream_;
+        for (int64_t k = 0; k < n_rec; k++) { index_.add(meta[k], u); u += (uint64_t)meta[k].bytes; }
+        if (u != stream_ + (uint64_t)len) return fail(NPORE_E_INVALID, "internal: record sizes do not add up to the batch's bytes");
+        n_rec_ += n_rec;
+        stream_ = u;
+        return NPORE_OK;
+    }
+    void begin_members() { heads_.clear(); iov_.clear(); jobs_.clear(); }
+    void member(const uint8_t *a, size_t na, const uint8_t *b, size_t nb) { jobs_.push_back(Job{a, na, b, nb, nullptr, 0}); }
+    // the queued members, in order, to the file; their places to the index
+    int flush_members()
+    {
+        if (deflate_) {                                 // code the payloads (a ready-made member needs nothing)
+            const size_t slot = BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD + BGZF_STORED_PAYLOAD;     // member, and a joined payload behind it
+            slot_of_.assign(jobs_.size(), 0);           // (only what is coded here takes a slot: a device batch has one such member at most)
+            size_t n_coded = 0;
+            for (size_t k = 0; k < jobs_.size(); k++)
+                if (!jobs_[k].ready) slot_of_[k] = n_coded++;
+            if (coded_.size() < n_coded * slot) coded_.resize(n_coded * slot);
+            coded_len_.assign(jobs_.size(), 0);
+            parallel_for((int64_t)jobs_.size(), n_coded > 1 ? threads_ : 1, [&](int64_t k) {
+                const Job &j = jobs_[(size_t)k];
+                if (j.ready) return;
+                uint8_t *out = coded_.data() + slot_of_[(size_t)k] * slot;
+                const uint8_t *in = j.a;
+                if (j.nb) {
+                    uint8_t *joined = out + BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD;
+                    std::memcpy(joined, j.a, j.na);
+                    std::memcpy(joined + j.na, j.b, j.nb);
+                    in = joined;
+                }
+                coded_len_[(size_t)k] = deflate_member_host(in, j.na + j.nb, crc32_fast(0, in, j.na + j.nb), out);
+            });
+            for (size_t k = 0; k < jobs_.size(); k++) {
+                const Job &j = jobs_[k];
+                index_.member_at(index_.base() + file_bytes_);
+                if (j.ready) { iov_.push_back(iovec{const_cast<uint8_t *>(j.ready), j.n_ready}); file_bytes_ += j.n_ready; }
+                else { iov_.push_back(iovec{coded_.data() + slot_of_[k] * slot, coded_len_[k]}); file_bytes_ += coded_len_[k]; }
+            }
+            return flush_iov();
+        }
+        for (const Job &j : jobs_) {
+            if (j.ready) return fail(NPORE_E_INVALID, "internal: a coded member for a stored file");
+            index_.member_at(index_.base() + file_bytes_);
+            stored_member(j.a, j.na, j.b, j.nb);
+        }
+        return flush_iov();
+    }
+    // one stored member of a + b bytes (b may be empty) queued for the next writev
+    void stored_member(const uint8_t *a, size_t na, const uint8_t *b, size_t nb)
     {
         const size_t n = na + nb, bsize = n + BGZF_STORED_OVERHEAD;
         heads_.emplace_back();
@@ -948,11 +1047,15 @@ private:
     int fd_ = -1;
     uint64_t base_ = 0, stream_ = 0, file_bytes_ = 0;
     int64_t n_rec_ = 0;
-    bool eof_ = false;
+    bool eof_ = false, deflate_ = false;
+    int threads_ = 1;
     std::string bai_path_;
     std::vector<uint8_t> carry_;             // the tail of the stream that does not fill a member yet (< 65 280 bytes)
     std::deque<Head> heads_;
     std::vector<iovec> iov_;
+    std::vector<Job> jobs_;
+    std::vector<uint8_t> coded_;             // deflate: the members coded here, a slot each
+    std::vector<size_t> coded_len_, slot_of_;
     BaiBuilder index_;
 };
 

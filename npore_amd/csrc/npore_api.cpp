@@ -55,6 +55,12 @@ struct npore_batch_slot {
     DevBuf d_recs;
     int64_t rec_cap = 0;
     PinnedBuf hp_pin, reclen_pin, total_pin, recs_pin;
+    // ... with NPORE_OUT_DEFLATE (bam_deflate_kernels.hpp): the members' plans, sizes and places, the coded members, the
+    // batch's four numbers; the size table and the numbers here; recs_pin then holds members | head fragment | tail fragment
+    DevBuf d_plans, d_sizes, d_moff, d_comp, d_info;
+    PinnedBuf sizes_pin, info_pin;
+    int64_t max_members = 0;
+    int64_t frag[4] = {0, 0, 0, 0};        // of the fetched batch: members, their bytes, head bytes, tail bytes
     int64_t ctext_copied = 0;              // bytes of the compact buffer the batch's last group sent behind its kernels
     PinnedBuf olen_pin, st_pin;            // lengths / status bits of an ASYNCHRONOUS batch land here (page-locked: a copy into
                                            // pageable memory would make the enqueueing call wait for the whole batch)
@@ -70,6 +76,33 @@ struct npore_batch_slot {
     int rc = 0;
     std::string err;
 };
+
+namespace {
+// NPORE_OUT_DEFLATE on the device: room for the most members `bytes` record bytes can hold
+int slot_deflate_buffers(npore_batch_slot &s, int64_t bytes)
+{
+    const int64_t mm = bytes / (int64_t)BGZF_STORED_PAYLOAD + 1;
+    s.max_members = mm;
+    if (int rc = s.d_plans.ensure((size_t)mm * sizeof(DeflateMemberPlan))) return rc;
+    if (int rc = s.d_sizes.ensure((size_t)mm * 4 + 64)) return rc;
+    if (int rc = s.d_moff.ensure((size_t)mm * 8 + 64)) return rc;
+    if (int rc = s.d_comp.ensure((size_t)mm * (BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD) + 2 * BGZF_STORED_PAYLOAD + 64)) return rc;      // (members, two fragments)
+    if (int rc = s.d_info.ensure(64)) return rc;
+    if (int rc = s.sizes_pin.ensure((size_t)mm * 4 + 64)) return rc;
+    return s.info_pin.ensure(64);
+}
+DeflateParams slot_deflate_params(npore_batch_slot &s, const uint8_t *d_recs, const unsigned long long *d_total, unsigned long long *d_stream_pos)
+{
+    DeflateParams dp{};
+    dp.recs = d_recs; dp.total = d_total; dp.stream_pos = d_stream_pos;
+    dp.plans = s.d_plans.as<DeflateMemberPlan>(); dp.sizes = s.d_sizes.as<uint32_t>(); dp.off = s.d_moff.as<int64_t>();
+    dp.comp = s.d_comp.as<uint8_t>();
+    dp.comp_cap = s.max_members * (int64_t)(BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD);
+    dp.max_members = s.max_members;
+    dp.info = s.d_info.as<int64_t>();
+    return dp;
+}
+}  // namespace
 
 extern "C" {
 
@@ -808,6 +841,51 @@ int64_t npore_debug_crc32(const uint8_t *p, int64_t n, uint32_t crc)
     return (int64_t)crc32_fast(crc, p, (size_t)n);
 }
 
+int64_t npore_debug_deflate_member(const uint8_t *in, int64_t n, uint8_t *out, int64_t cap)
+{
+    if ((!in && n > 0) || !out || n < 0 || n > (int64_t)BGZF_STORED_PAYLOAD || cap < n + (int64_t)BGZF_STORED_OVERHEAD) return fail(NPORE_E_INVALID, "bad argument");
+    return (int64_t)deflate_member_host(in, (size_t)n, crc32_fast(0, in, (size_t)n), out);
+}
+
+int npore_debug_deflate_device(npore_ctx *ctx, const uint8_t *bytes, int64_t n, int64_t phase, uint8_t *members, int64_t members_cap,
+                               uint32_t *sizes, int64_t sizes_cap, uint8_t *head, uint8_t *tail, int64_t *info)
+try {
+    if (!ctx || (!bytes && n > 0) || n < 0 || phase < 0 || !info || members_cap < 0 || sizes_cap < 0 || (members_cap > 0 && !members) ||
+        (sizes_cap > 0 && !sizes) || !head || !tail)
+        return fail(NPORE_E_INVALID, "bad argument");
+    if (int rc = quiesce(ctx)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    npore_batch_slot s;
+    DevBuf d_recs, d_total;
+    const unsigned long long total = (unsigned long long)n, pos = (unsigned long long)phase;
+    if (int rc = d_recs.ensure((size_t)n + 64)) return rc;
+    if (int rc = d_total.ensure(64)) return rc;
+    if (int rc = ctx->d_stream_pos.ensure(64)) return rc;
+    if (int rc = slot_deflate_buffers(s, n)) return rc;
+    if (n > 0) HIP_TRY(hipMemcpy(d_recs.p, bytes, (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_total.p, &total, 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ctx->d_stream_pos.p, &pos, 8, hipMemcpyHostToDevice));
+    const DeflateParams dp = slot_deflate_params(s, d_recs.as<uint8_t>(), d_total.as<unsigned long long>(), ctx->d_stream_pos.as<unsigned long long>());
+    launch_deflate(dp, ctx->s_post);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->s_post));
+    int64_t in4[4];
+    unsigned long long pos_after = 0;
+    HIP_TRY(hipMemcpy(in4, dp.info, 32, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&pos_after, ctx->d_stream_pos.p, 8, hipMemcpyDeviceToHost));
+    const int64_t nm = in4[0], comp = in4[1], hd = in4[2], tl = in4[3];
+    if (nm < 0 || nm > s.max_members || hd < 0 || tl < 0 || hd + nm * (int64_t)BGZF_STORED_PAYLOAD + tl != n || comp < 0 || comp > dp.comp_cap)
+        return fail(NPORE_E_HIP, "internal: the coded members do not add up to the buffer's bytes");
+    if (nm > sizes_cap || comp > members_cap) return fail(NPORE_E_INVALID, "the members need more room than the caller gave");
+    if (nm > 0) HIP_TRY(hipMemcpy(sizes, dp.sizes, (size_t)nm * 4, hipMemcpyDeviceToHost));
+    if (comp > 0) HIP_TRY(hipMemcpy(members, dp.comp, (size_t)comp, hipMemcpyDeviceToHost));
+    if (hd > 0) HIP_TRY(hipMemcpy(head, dp.comp + comp, (size_t)hd, hipMemcpyDeviceToHost));           // (where emit_deflate_kernel put them)
+    if (tl > 0) HIP_TRY(hipMemcpy(tail, dp.comp + comp + hd, (size_t)tl, hipMemcpyDeviceToHost));
+    info[0] = nm; info[1] = comp; info[2] = hd; info[3] = tl; info[4] = (int64_t)pos_after;
+    return NPORE_OK;
+}
+NPORE_CATCH_INT
+
 int npore_debug_dpp(uint32_t *out128)
 {
     DevBuf d;
@@ -977,7 +1055,9 @@ NPORE_CATCH_INT
 
 int npore_bam_set_output(npore_bam *b, int format, const char *bai_path, int flags)
 {
-    if (!b || (format != NPORE_OUT_SAM && format != NPORE_OUT_BAM) || (flags & ~(NPORE_OUT_EOF | NPORE_OUT_PART))) return fail(NPORE_E_INVALID, "bad argument");
+    if (!b || (format != NPORE_OUT_SAM && format != NPORE_OUT_BAM) || (flags & ~(NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE)) ||
+        ((flags & NPORE_OUT_DEFLATE) && format != NPORE_OUT_BAM))
+        return fail(NPORE_E_INVALID, "bad argument");
     b->out_format = format;
     b->out_bai = (format == NPORE_OUT_BAM && bai_path) ? bai_path : "";
     b->out_flags = flags;
@@ -1004,7 +1084,9 @@ try {
     b->out_bai.clear();
     b->out_flags = 0;
     std::fill(b->out_info, b->out_info + 4, 0);
-    if (int rc = w.open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0)) return rc;
+    if (int rc = w.open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0,
+                        (flags & NPORE_OUT_DEFLATE) != 0, host_threads(threads)))
+        return rc;
     std::vector<BamRecMeta> meta;
     for (int64_t k0 = 0; k0 < n; k0 += batch_reads) {
         const int64_t m = std::min(batch_reads, n - k0);
@@ -1146,7 +1228,7 @@ int slot_post(const npore_bam *b, int64_t n, const int32_t *status, int threads,
 }
 // BAM mode, records built on the device: nothing is formatted here -- the batch's bytes as they lie there, into page-locked
 // memory, and from the records' lengths what the writer's index needs (reference, position and span are the input record's)
-int slot_fetch_records(int64_t n, const int32_t *status, npore_batch_slot &s)
+int slot_fetch_records(int64_t n, const int32_t *status, npore_batch_slot &s, bool deflate)
 {
     const int64_t total = (int64_t)*reinterpret_cast<const unsigned long long *>(s.total_pin.p);
     const int64_t *len = reinterpret_cast<const int64_t *>(s.reclen_pin.p);
@@ -1163,6 +1245,19 @@ int slot_fetch_records(int64_t n, const int32_t *status, npore_batch_slot &s)
         sum += len[k];
     }
     if (sum != total) return fail(NPORE_E_HIP, "internal: BAM record sizes do not add up");
+    if (deflate) {          // exactly the coded members and the two raw fragments around them
+        const int64_t *info = reinterpret_cast<const int64_t *>(s.info_pin.p);
+        const int64_t nm = info[0], comp = info[1], head = info[2], tail = info[3];
+        if (nm < 0 || nm > s.max_members || head < 0 || tail < 0 || head + nm * (int64_t)BGZF_STORED_PAYLOAD + tail != total || comp < 0 ||
+            comp > nm * (int64_t)(BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD))
+            return fail(NPORE_E_HIP, "internal: the coded members do not add up to the batch's bytes");
+        // (one copy: the fragments lie behind the last member -- emit_deflate_kernel)
+        if (int rc = s.recs_pin.ensure((size_t)(comp + head + tail) + 64)) return rc;
+        if (comp + head + tail > 0) HIP_TRY(hipMemcpy(s.recs_pin.p, s.d_comp.p, (size_t)(comp + head + tail), hipMemcpyDeviceToHost));
+        std::copy(info, info + 4, s.frag);
+        s.sam_len = total;
+        return NPORE_OK;
+    }
     if (int rc = s.recs_pin.ensure((size_t)total + 64)) return rc;
     if (total > 0) HIP_TRY(hipMemcpy(s.recs_pin.p, s.d_recs.p, (size_t)total, hipMemcpyDeviceToHost));
     s.sam_len = total;
@@ -1215,7 +1310,7 @@ struct RunOutput {
     FILE *fh = nullptr;
     std::unique_ptr<BgzfStoredWriter> bw;
     npore_bam *b = nullptr;
-    int open(npore_bam *bam, const char *out_path)
+    int open(npore_bam *bam, const char *out_path, int threads)
     {
         b = bam;
         const int format = b->out_format, flags = b->out_flags;
@@ -1226,7 +1321,8 @@ struct RunOutput {
         std::fill(b->out_info, b->out_info + 4, 0);
         if (format == NPORE_OUT_BAM) {
             bw.reset(new BgzfStoredWriter());
-            return bw->open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0);
+            return bw->open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0,
+                            (flags & NPORE_OUT_DEFLATE) != 0, std::max(1, host_threads(threads) / 2));
         }
         fh = std::fopen(out_path, "ab");
         return fh ? NPORE_OK : fail(NPORE_E_INVALID, std::string("cannot open '") + out_path + "' for appending");
@@ -1273,6 +1369,13 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
     // BAM mode: the records are built on the device where the default pipeline runs (device pack + device glue:
     // bam_emit_kernels.hpp); with the host glue or the host pack the host twin makes them (format_bam_into)
     const bool dev_bam = bw != nullptr && dpack;
+    // ... and with NPORE_OUT_DEFLATE the whole members inside a batch are coded there too (bam_deflate_kernels.hpp); the
+    // run's stream position starts at 0
+    const bool dev_deflate = dev_bam && bw->deflate();
+    if (dev_deflate) {
+        if (int rc = ctx->d_stream_pos.ensure(64)) return rc;
+        HIP_TRY(hipMemset(ctx->d_stream_pos.p, 0, 8));
+    }
     // NPORE_PIPE_TRACE=1: one line per batch and stage boundary on stderr (ms since the call began)
     const bool trace = std::getenv("NPORE_PIPE_TRACE") != nullptr;
     std::mutex trace_m;
@@ -1342,7 +1445,7 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             t0 = std::chrono::steady_clock::now();
             double ms_std = 0.0;
             try {
-                t.rc = dev_bam ? slot_fetch_records(m, st, t) : slot_post(b, m, st, post_threads, t, &ms_std, glue, bw != nullptr);
+                t.rc = dev_bam ? slot_fetch_records(m, st, t, dev_deflate) : slot_post(b, m, st, post_threads, t, &ms_std, glue, bw != nullptr);
             } catch (const std::exception &e) {
                 fail(NPORE_E_NOMEM, std::string("SAM text of a batch: ") + e.what());
                 t.rc = NPORE_E_NOMEM;
@@ -1355,7 +1458,12 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             wait_for(written, k);                              // records in input order
             on_status(k, m, st);
             t0 = std::chrono::steady_clock::now();
-            if (bw) {
+            if (dev_deflate) {
+                const uint8_t *q = reinterpret_cast<const uint8_t *>(t.recs_pin.p);
+                // (recs_pin: members | head fragment | tail fragment)
+                if (bw->add_coded(q + t.frag[1], t.frag[2], q, reinterpret_cast<const uint32_t *>(t.sizes_pin.p), t.frag[0],
+                                  q + t.frag[1] + t.frag[2], t.frag[3], t.meta.data(), (int64_t)t.meta.size())) { t.rc = NPORE_E_INVALID; t.err = npore_last_error(); }
+            } else if (bw) {
                 const char *bytes = dev_bam ? t.recs_pin.p : t.sam.p;
                 if (bw->add(reinterpret_cast<const uint8_t *>(bytes), t.sam_len, t.meta.data(), (int64_t)t.meta.size())) { t.rc = NPORE_E_INVALID; t.err = npore_last_error(); }
             } else if (std::fwrite(t.sam.p, 1, (size_t)t.sam_len, fh) != (size_t)t.sam_len) { t.rc = NPORE_E_INVALID; t.err = "short write"; }
@@ -1389,6 +1497,13 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
                 (rc = s.reclen_pin.ensure((size_t)m * 8 + 64)) || (rc = s.total_pin.ensure(64))) { err = "batch buffers"; break; }
             emit = BamEmit{s.d_recs.as<uint8_t>(), s.rec_cap, s.d_cursor.as<unsigned long long>(), reinterpret_cast<const int64_t *>(s.hp_pin.p),
                            reinterpret_cast<int64_t *>(s.reclen_pin.p), reinterpret_cast<unsigned long long *>(s.total_pin.p)};
+            if (dev_deflate) {
+                if ((rc = slot_deflate_buffers(s, s.rec_cap))) { err = "batch buffers"; break; }
+                emit.deflate = true;
+                emit.dfl = slot_deflate_params(s, s.d_recs.as<uint8_t>(), s.d_cursor.as<unsigned long long>(), ctx->d_stream_pos.as<unsigned long long>());
+                emit.h_sizes = reinterpret_cast<uint32_t *>(s.sizes_pin.p);
+                emit.h_info = reinterpret_cast<int64_t *>(s.info_pin.p);
+            }
         } else if (glue) {
             // (a text takes whole 16-byte granules of the compact buffer: at most 15 bytes more than its slot)
             const int64_t slots = s.oo[(size_t)m] + 16 * m, bound = std::min(slots, slots / 4 + 4096);
@@ -1464,7 +1579,7 @@ try {
     if (!pack_args_ok(b, idx, n)) return fail(NPORE_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(ctx->device));
     RunOutput out;
-    if (int rco = out.open(b, out_path)) return rco;
+    if (int rco = out.open(b, out_path, threads)) return rco;
     const int64_t nb = (n + batch_reads - 1) / batch_reads;
     int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, out.fh, false,
                            [&](int64_t k, npore_batch_slot &s) -> int64_t {
@@ -1492,7 +1607,7 @@ try {
     HIP_TRY(hipSetDevice(ctx->device));
     BamRecordWalker walker(b, n_regions, ref_id, start, stop, max_reads, threads);
     RunOutput out;
-    if (int rco = out.open(b, out_path)) return rco;
+    if (int rco = out.open(b, out_path, threads)) return rco;
     int64_t n_bad = 0, ordinal0 = 0;
     auto on_status = [&](int64_t, int64_t m, const int32_t *st) {
         for (int64_t i = 0; i < m; i++)

@@ -59,6 +59,10 @@ def argparser():
                         help="`sam`: the text, OUT_PREFIX.sam.  `bam`: OUT_PREFIX.bam, the same records in binary (built on the GPU in "
                              "the default pipeline) in uncompressed BGZF members, with OUT_PREFIX.bam.bai when they go out in "
                              "coordinate order -- what `samtools view -u` and `samtools index` would make of the SAM.")
+    parser.add_argument("--bam_compress", choices=("none", "huffman"), default="none",
+                        help="--out_format bam: `none`, stored BGZF members; `huffman`, every member one dynamic-Huffman DEFLATE block "
+                             "of literals (no match search), coded on the GPU in the default pipeline.  The records, the cuts and "
+                             "the index's meaning are the same.")
     parser.add_argument("--python_io", action="store_true",
                         help="Use the pure-Python BAM reader / SAM writer (the restatement the native one is tested against).")
     return parser
@@ -117,6 +121,10 @@ def main():
         sys.exit(1)
     fmt = getattr(cfg.args, "out_format", "sam")
     as_bam = fmt == "bam"
+    compress = getattr(cfg.args, "bam_compress", "none")
+    if compress != "none" and not as_bam:
+        print("\nERROR: --bam_compress needs --out_format bam.")
+        sys.exit(1)
     if as_bam and native and cfg.args.batch_reads <= 0:
         print("\nERROR: --out_format bam is written by the library's file pipeline: --batch_reads must be positive.")
         sys.exit(1)
@@ -129,7 +137,7 @@ def main():
         open(out_sam, "w").close()
     # BAM: the index beside the file (a rank's part: a sidecar with part-relative offsets, merged by dist.gather_bam_parts);
     # the EOF member ends the whole file, not a part
-    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1) if as_bam else {}
+    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress) if as_bam else {}
     gather = dist_mod.gather_bam_parts if as_bam else dist_mod.gather_parts
 
     print("> extracting read data from BAM")
@@ -184,7 +192,7 @@ def main():
         read_data = bam_mod.get_read_data(bam, ref_seqs)
         print("> computing individual read realignments")
         batch = []
-        writer = bam_mod.BamRecordWriter(out_sam, bai=out_sam + ".bai") if as_bam else None
+        writer = bam_mod.BamRecordWriter(out_sam, bai=out_sam + ".bai", compress=compress) if as_bam else None
         py_kw = dict(bam_writer=writer, references=bam.references) if as_bam else {}
         for rd in read_data:
             batch.append(rd)

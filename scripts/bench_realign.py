@@ -131,7 +131,7 @@ def start_output(a, out, nb):
     """The header of the output file, and what the realign calls need to write behind it in a.out_format."""
     if a.out_format == "bam":
         bam.create_bam_header(out, nb)
-        return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai")
+        return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai", compress=a.bam_compress)
     bam.create_header(out, nb)
     return {}
 
@@ -249,8 +249,13 @@ def main():
     ap.add_argument("--out_format", choices=("sam", "bam"), default="sam",
                     help="what the timed legs write: SAM text, or (bam) the records built on the GPU in stored BGZF members with their .bai "
                          "(`sam_bytes` then counts the BAM's bytes; slot `format` of the stage sums is the record bytes' trip to the host)")
+    ap.add_argument("--bam_compress", choices=("none", "huffman"), default="none",
+                    help="--out_format bam: stored members, or every member one dynamic-Huffman block coded on the GPU; the line's "
+                         "`output_bytes` is the size of the one-pass leg's file")
     ap.add_argument("--gen-into", default=None, help=argparse.SUPPRESS)       # (internal: make the inputs in this directory and exit)
     a = ap.parse_args()
+    if a.bam_compress != "none" and a.out_format != "bam":
+        ap.error("--bam_compress needs --out_format bam")
     if a.gen_into:
         print(json.dumps(build_inputs(a.gen_into, a.reads, a.distinct, a.ref_len, a.seed, a.const_qual)))
         return
@@ -331,7 +336,8 @@ def main():
                 "one_pass": one_pass, "one_pass_output_identical": same_one_pass,
                 "reads": a.reads, "distinct_reads": a.reads if a.distinct <= 0 else min(a.distinct, a.reads),
                 "qualities": "constant 20" if a.const_qual else "uniform per base over phred 0 ... 93 (reference test/generate_bam.py:63,79)",
-                "ref_len": a.ref_len, "r": a.r, "batch": a.batch,
+                "ref_len": a.ref_len, "r": a.r, "batch": a.batch, "out_format": a.out_format, "bam_compress": a.bam_compress,
+                "output_bytes": os.path.getsize(out + ".o"),
                 "host_cpus": len(os.sched_getaffinity(0)), "bam_bytes": os.path.getsize(bp),
                 "resident": resident, "streamed": streamed, "streamed_output_identical": same,
                 "cold_start": cold,

@@ -220,7 +220,8 @@ int npore_total_timing(npore_ctx *ctx, double *ms, int n);
  * The BAM -> SAM pipeline (npore_bam_realign_file / _sequential): "device_glue" (default 1): realign_read's glue
  * (src/bam.pyx:65-78) on the device, 0 = on the host from the op strings; "device_pack" (default 1, with the device
  * glue): align()'s inputs (src/bam.pyx:42, 45, 59-61) unpacked from the BAM records on the device, 0 = packed on the
- * host and uploaded.  "cms_batch_reads" (default 4000): records per batch of npore_bam_confusion. */
+ * host and uploaded.  "cms_batch_reads" (default 4000): records per batch of npore_bam_confusion and
+ * npore_bam_purity.  "purity_window" (default 2^22, 64 .. 2^24): positions per counter window of npore_bam_purity. */
 int npore_ctx_set(npore_ctx *ctx, const char *key, int64_t value);
 
 /* Batch sizing.  The DP of a chunk (at most max_b_rows anti-diagonals of a read; reference src/aln.pyx:344-358,
@@ -427,6 +428,32 @@ int npore_confusion_counts(const char *lines, const int64_t *line_off, int64_t n
 int npore_bam_confusion(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n_ranges,
                         const int32_t *ref_id, const int64_t *start, const int64_t *stop, int min_bq, uint32_t exclude_flags,
                         int64_t *subs, int64_t *nps, int64_t *inss, int64_t *dels, int64_t *tallies);
+
+/* Gini purity of pileups straight from the BAM records, counted on the GPU -- what the reference's src/purity.py computes
+ * from `samtools mpileup` column 5, without a pileup and without samtools (the rule: csrc/purity_rec.hpp; the kernels:
+ * csrc/purity_kernels.hpp).  Per reference position of the ranges: n entries counted (A C G T and `*` for a deleted
+ * position), S_b = the sum of the squared symbol counts, t insertions, S_i = (n - t)^2 + the sum of the squared counts of
+ * the distinct inserted strings; the scores S_b / n^2 and S_i / n^2 are filed under bin (10^7 S - n^2) / (10^5 n^2) of
+ * 100, in integers (the reference's int(x * 100 - 0.00001)).
+ *   ranges (ref_id, start, stop)[n_ranges]: clipped to their contigs and merged per contig into a disjoint ascending
+ *     set -- a position is scored once; P = the merged positions, contigs in the order of the BAM header;
+ *   min_bq / exclude_flags: as for npore_bam_confusion; a `*` entry takes the quality of the read base consumed last
+ *     before the deletion;
+ *   pos_stats: NULL, or [P][4] rows (n, S_b, t, S_i) (pos_cap >= P rows of room): all zeros for an uncovered position; a
+ *     position of 2^20 entries or more is not binned and keeps n with -1 in the other three.
+ * Inserted strings longer than 14 letters are compared by a 56-bit hash (two different ones that collide at one position
+ * are merged).  An annotation-only context will do.  Both readers: ONE PASS over a coordinate-sorted file (a handle of
+ * mode 3; NPORE_E_UNSUPPORTED for an unsorted one) or selection on the record index, window by window.  The counters
+ * live on the device for a window of npore_ctx_set "purity_window" positions (default 2^22, 64 .. 2^24); batches are of
+ * "cms_batch_reads" records.  The histograms base_hist[100], ins_hist[100] and tallies[16] (int64) are ADDED to on
+ * success only: [0] records walked, [1] dropped by flags, [2] with N / P in the CIGAR, [3] with a CIGAR that disagrees with
+ * l_seq, [4] insertions without a base entry to sit on (not counted), [5] entries with a letter outside ACGT, [6] entries
+ * below min_bq, [7] entries counted, [8] `*` entries among them, [9] insertions counted, [10] insertions compared by
+ * hash, [11] positions covered, [12] positions too deep, [13] windows, [14] batches, [15] nanoseconds of the kernels
+ * alone (events).  Integer counters: the result does not depend on batching, on the window or on the reader. */
+int npore_bam_purity(npore_ctx *ctx, npore_bam *bam, int64_t n_ranges, const int32_t *ref_id, const int64_t *start,
+                     const int64_t *stop, int min_bq, uint32_t exclude_flags, int64_t *base_hist, int64_t *ins_hist,
+                     int64_t *pos_stats, int64_t pos_cap, int64_t *tallies);
 
 /* Debug / tests: one raw DEFLATE stream (a BGZF block's payload; the BAM reader's inner loop, pysam / htslib in the
  * reference) of in_len bytes that must inflate to exactly out_len bytes.  force: 0 = as the readers do it (this

@@ -45,6 +45,8 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_int]),
     "npore_bam_confusion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int, C.c_uint32] + [C.c_void_p] * 5),
+    "npore_bam_purity": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "npore_last_timing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "npore_ctx_set": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "npore_round_chunks": (C.c_int64, [C.c_void_p, C.c_int]),

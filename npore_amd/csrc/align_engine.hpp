@@ -125,6 +125,10 @@ struct npore_ctx {
     // the current contig's ranges, the counters
     DevBuf cms_raw, cms_off, cms_ranges, cms_counts;
     int64_t cms_batch_reads = 4000;
+    // Gini purity of pileups from BAM records (npore_bam_purity; staging: the cms_ buffers): the window's counter planes and
+    // sums of squares, the insertion events and their buckets, the scan's block sums, histograms | tallies | cursor, rows
+    DevBuf pur_cnt, pur_v2, pur_ev, pur_sorted, pur_bsum, pur_out, pur_rows;
+    int64_t purity_window = 1ll << 22;   // positions per counter window (npore_ctx_set "purity_window")
     uint64_t d_fasta_serial = 0;
     size_t d_fasta_bytes = 0;
     int n_ctg = 0;

@@ -30,6 +30,7 @@
 #include "unpack_kernels.hpp"
 #include "bam_emit_kernels.hpp"
 #include "confusion_kernels.hpp"
+#include "purity_kernels.hpp"
 #include "align_engine.hpp"
 
 // No C++ exception may cross the C ABI: the entry points that allocate are function-try-blocks ending in one of these.
@@ -473,6 +474,7 @@ try {
     else if (k == "device_glue") ctx->device_glue = value != 0;
     else if (k == "device_pack") ctx->device_pack = value != 0;
     else if (k == "cms_batch_reads") { if (value < 1) return fail(NPORE_E_INVALID, "cms_batch_reads: at least 1"); ctx->cms_batch_reads = value; }
+    else if (k == "purity_window") { if (value < 64 || value > (1ll << 24)) return fail(NPORE_E_INVALID, "purity_window: 64 .. 2^24"); ctx->purity_window = value; }
     else if (k == "fill_streams") { if (value < 1 || value > 2) return fail(NPORE_E_INVALID, "fill_streams: 1 or 2"); ctx->fill_streams = (int)value; }
     else return fail(NPORE_E_INVALID, "unknown key " + k);
     return NPORE_OK;
@@ -800,6 +802,414 @@ try {
     for (int k = 0; k < dim; k++) { inss[k] += (int64_t)h[25 + n_nps + k]; dels[k] += (int64_t)h[25 + n_nps + dim + k]; }
     for (int k = 0; k < CMS_N_TALLIES; k++) tallies[k] += (int64_t)h[25 + n_nps + 2 * dim + k] + ht.t[k];
     tallies[CMS_T_KERNEL_NS] += (int64_t)(kernel_ms * 1e6);
+    return NPORE_OK;
+}
+NPORE_CATCH_INT
+
+// ---- Gini purity of pileups from BAM records (purity_rec.hpp, purity_kernels.hpp) --------------------------------------
+namespace {
+struct PurContig {
+    std::vector<CmsRange> ranges;        // merged: ascending, disjoint, ann = dense index of the first position
+    int64_t P = 0, base = 0;             // positions; where its rows begin among all contigs'
+    int64_t lo = 0, hi = 0;              // hull
+};
+
+// the caller's ranges of one contig (clipped to it) merged into a disjoint ascending set
+void pur_merge(std::vector<CmsRange> rs, PurContig &c)
+{
+    std::sort(rs.begin(), rs.end(), [](const CmsRange &a, const CmsRange &b) { return a.st != b.st ? a.st < b.st : a.en < b.en; });
+    for (const CmsRange &r : rs) {
+        if (!c.ranges.empty() && r.st <= c.ranges.back().en) c.ranges.back().en = std::max(c.ranges.back().en, r.en);
+        else c.ranges.push_back(r);
+    }
+    int64_t off = 0;
+    for (CmsRange &r : c.ranges) {
+        r.ann = off;
+        r.slen = r.en - r.st;
+        off += r.slen;
+    }
+    c.P = off;
+    c.lo = c.ranges.front().st;
+    c.hi = c.ranges.back().en;
+}
+// the contig position of dense index d
+int64_t pur_ref_of_dense(const PurContig &c, int64_t d)
+{
+    size_t l = 0, h = c.ranges.size();   // last range with ann <= d
+    while (h - l > 1) {
+        const size_t mid = (l + h) / 2;
+        if (c.ranges[mid].ann <= d) l = mid; else h = mid;
+    }
+    return c.ranges[l].st + (d - c.ranges[l].ann);
+}
+
+// One run of npore_bam_purity: the device side of a window and the batch on its way to it.
+struct PurRun {
+    npore_ctx *ctx;
+    hipStream_t s;
+    int min_bq;
+    int64_t W, stride;                   // window size; plane stride (W, or fewer where no contig has as many positions)
+    int64_t batch_reads;
+    int64_t *pos_stats;
+    const PurContig *c = nullptr;        // the current contig, its window
+    int64_t w = 0, win_lo = 0, win_hi = 0, ref_lo = 0, ref_hi = 0;
+    bool dirty = false;
+    int64_t ev_bound = 0;                // no more events than this lie behind the cursor
+    std::vector<const uint8_t *> batch;
+    int64_t batch_ins = 0;
+    PinnedBuf raw, rawo_pin;
+    std::vector<int64_t> rawo;
+    double kernel_ms = 0.0;
+    int64_t windows = 0, batches = 0;
+
+    uint32_t *cnt() const { return ctx->pur_cnt.as<uint32_t>(); }
+    unsigned long long *hist() const { return ctx->pur_out.as<unsigned long long>(); }
+    unsigned long long *d_tallies() const { return hist() + 2 * PUR_BINS; }
+    uint32_t *cursor() const { return reinterpret_cast<uint32_t *>(d_tallies() + PUR_D_TALLIES); }
+    static size_t out_bytes() { return (2 * PUR_BINS + PUR_D_TALLIES + 1) * 8; }
+
+    int timed_begin() { HIP_TRY(hipEventRecord(ctx->ev_cms[0], s)); return NPORE_OK; }
+    int timed_end()
+    {
+        HIP_TRY(hipEventRecord(ctx->ev_cms[1], s));
+        HIP_TRY(hipStreamSynchronize(s));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_cms[0], ctx->ev_cms[1]));
+        kernel_ms += ms;
+        return NPORE_OK;
+    }
+    int set_contig(const PurContig &pc)
+    {
+        c = &pc;
+        const size_t bytes = pc.ranges.size() * sizeof(CmsRange);
+        if (int rc = ctx->cms_ranges.ensure(bytes + 16)) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->cms_ranges.p, pc.ranges.data(), bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        set_window(0);
+        return NPORE_OK;
+    }
+    void set_window(int64_t win)
+    {
+        w = win;
+        win_lo = win * W;
+        win_hi = std::min(c->P, win_lo + W);
+        ref_lo = pur_ref_of_dense(*c, win_lo);
+        ref_hi = pur_ref_of_dense(*c, win_hi - 1) + 1;
+    }
+    int64_t n_windows() const { return (c->P + W - 1) / W; }
+    int add(const uint8_t *q, int64_t ins_ops)
+    {
+        batch.push_back(q);
+        batch_ins += ins_ops;
+        return (int64_t)batch.size() >= batch_reads ? flush() : NPORE_OK;
+    }
+    // the batch through purity_records_kernel, into the current window
+    int flush()
+    {
+        const int64_t n = (int64_t)batch.size();
+        if (n == 0) return NPORE_OK;
+        rawo.assign(1, 0);
+        for (const uint8_t *q : batch) {
+            const RecView r = rec_view(q);
+            rawo.push_back(rawo.back() + (((int64_t)(r.aux() - r.p) + 4 + 7) & ~7ll));
+        }
+        if (int rc = raw.ensure((size_t)rawo[(size_t)n] + 64)) return rc;
+        if (int rc = rawo_pin.ensure((size_t)(n + 1) * 8)) return rc;
+        std::memcpy(rawo_pin.p, rawo.data(), (size_t)(n + 1) * 8);
+        const int64_t per = 64;
+        parallel_for((n + per - 1) / per, 0, [&](int64_t tix) {
+            for (int64_t k = tix * per; k < std::min(n, (tix + 1) * per); k++) {
+                const RecView r = rec_view(batch[(size_t)k]);
+                std::memcpy(raw.p + rawo[(size_t)k], batch[(size_t)k], (size_t)(r.aux() - r.p) + 4);
+            }
+        });
+        if (int rc = ctx->cms_raw.ensure((size_t)rawo[(size_t)n] + 64)) return rc;
+        if (int rc = ctx->cms_off.ensure((size_t)(n + 1) * 8)) return rc;
+        // the events of the window so far stay where they are when their buffer grows
+        const size_t ev_need = (size_t)(ev_bound + batch_ins + 1) * sizeof(PurEvent);
+        if (ev_need > ctx->pur_ev.cap) {
+            DevBuf nb;
+            if (int rc = nb.ensure(ev_need + ev_need / 2)) return rc;
+            if (ev_bound > 0) HIP_TRY(hipMemcpyAsync(nb.p, ctx->pur_ev.p, (size_t)ev_bound * sizeof(PurEvent), hipMemcpyDeviceToDevice, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            std::swap(nb.p, ctx->pur_ev.p);
+            std::swap(nb.cap, ctx->pur_ev.cap);
+        }
+        HIP_TRY(hipMemcpyAsync(ctx->cms_raw.p, raw.p, (size_t)rawo[(size_t)n], hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(ctx->cms_off.p, rawo_pin.p, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s));
+        PurParams p;
+        p.raw = ctx->cms_raw.as<uint8_t>();
+        p.raw_off = ctx->cms_off.as<int64_t>();
+        p.n_reads = n;
+        p.ranges = ctx->cms_ranges.as<CmsRange>();
+        p.n_ranges = (int)c->ranges.size();
+        p.win_lo = win_lo;
+        p.win_hi = win_hi;
+        p.ref_lo = ref_lo;
+        p.ref_hi = ref_hi;
+        p.W = stride;
+        p.min_bq = min_bq;
+        p.cnt = cnt();
+        p.events = ctx->pur_ev.as<PurEvent>();
+        p.cursor = cursor();
+        p.ev_cap = (uint32_t)std::min<int64_t>(ev_bound + batch_ins, UINT32_MAX);
+        p.tallies = d_tallies();
+        if (int rc = timed_begin()) return rc;
+        hipLaunchKernelGGL(purity_records_kernel, dim3((unsigned)n), dim3(256), 0, s, p);
+        HIP_TRY(hipGetLastError());
+        if (int rc = timed_end()) return rc;     // (the staging buffers are free again)
+        ev_bound += batch_ins;
+        batch.clear();
+        batch_ins = 0;
+        batches++;
+        dirty = true;
+        return NPORE_OK;
+    }
+    // the window's end: buckets, pair counts, scores; the window is zero afterwards
+    int finish_window()
+    {
+        if (int rc = flush()) return rc;
+        if (!dirty) return NPORE_OK;
+        const int64_t n = win_hi - win_lo;
+        if (ev_bound >= (int64_t)UINT32_MAX) return fail(NPORE_E_UNSUPPORTED, "more than 2^32 insertions in one window: choose a smaller purity_window");
+        const uint32_t cap = (uint32_t)ev_bound;
+        const unsigned n_blocks = (unsigned)((n + PUR_SCAN_PER_BLOCK - 1) / PUR_SCAN_PER_BLOCK);
+        if (cap > 0) {
+            if (int rc = ctx->pur_bsum.ensure((size_t)n_blocks * 4 + 16)) return rc;
+            if (int rc = ctx->pur_sorted.ensure((size_t)cap * sizeof(PurEvent))) return rc;
+        }
+        if (pos_stats)
+            if (int rc = ctx->pur_rows.ensure((size_t)n * 32)) return rc;
+        if (int rc = timed_begin()) return rc;
+        if (cap > 0) {
+            uint32_t *t_plane = cnt() + 5 * stride, *off = cnt() + 6 * stride;
+            hipLaunchKernelGGL(purity_scan_blocks_kernel, dim3(n_blocks), dim3(256), 0, s, t_plane, off, ctx->pur_bsum.as<uint32_t>(), n);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(purity_scan_top_kernel, dim3(1), dim3(256), 0, s, ctx->pur_bsum.as<uint32_t>(), (int)n_blocks);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(purity_scan_add_kernel, dim3(n_blocks), dim3(256), 0, s, off, ctx->pur_bsum.as<uint32_t>(), n);
+            HIP_TRY(hipGetLastError());
+            const unsigned eb = (cap + 255u) / 256u;
+            hipLaunchKernelGGL(purity_scatter_kernel, dim3(eb), dim3(256), 0, s, ctx->pur_ev.as<PurEvent>(), cursor(), cap, off, ctx->pur_sorted.as<PurEvent>());
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(purity_pairs_kernel, dim3(eb), dim3(256), 0, s, ctx->pur_sorted.as<PurEvent>(), cursor(), cap, t_plane, off,
+                               ctx->pur_v2.as<unsigned long long>());
+            HIP_TRY(hipGetLastError());
+        }
+        PurFinalParams fp{cnt(), ctx->pur_v2.as<unsigned long long>(), stride, n, hist(), d_tallies(), pos_stats ? ctx->pur_rows.as<int64_t>() : nullptr};
+        hipLaunchKernelGGL(purity_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, fp);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(cursor(), 0, 4, s));
+        if (int rc = timed_end()) return rc;
+        if (pos_stats) {
+            HIP_TRY(hipMemcpyAsync(pos_stats + 4 * (c->base + win_lo), ctx->pur_rows.p, (size_t)n * 32, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        windows++;
+        dirty = false;
+        ev_bound = 0;
+        return NPORE_OK;
+    }
+};
+}  // namespace
+
+int npore_bam_purity(npore_ctx *ctx, npore_bam *b, int64_t n_ranges, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
+                     int min_bq, uint32_t exclude_flags, int64_t *base_hist, int64_t *ins_hist, int64_t *pos_stats, int64_t pos_cap,
+                     int64_t *tallies)
+try {
+    if (!ctx || !b || n_ranges < 0 || (n_ranges > 0 && (!ref_id || !start || !stop)) || !base_hist || !ins_hist || !tallies || (pos_stats && pos_cap < 0))
+        return fail(NPORE_E_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = quiesce(ctx)) return rc;
+    const size_t n_refs = b->ref_names.size();
+    // the ranges by contig, merged; P = the positions of all of them, contigs in header order
+    std::vector<PurContig> contigs(n_refs);
+    int64_t P = 0, max_p = 0;
+    {
+        std::vector<std::vector<CmsRange>> by(n_refs);
+        for (int64_t k = 0; k < n_ranges; k++) {
+            if (ref_id[k] < 0 || ref_id[k] >= (int32_t)n_refs) continue;
+            const int64_t clen = b->ref_lens[(size_t)ref_id[k]];
+            if (clen >= (1ll << 31)) return fail(NPORE_E_UNSUPPORTED, "contig too long");
+            CmsRange r;
+            if (cms_clip(start[k], stop[k], clen, r)) by[(size_t)ref_id[k]].push_back(r);
+        }
+        for (size_t r = 0; r < n_refs; r++) {
+            if (by[r].empty()) continue;
+            pur_merge(std::move(by[r]), contigs[r]);
+            contigs[r].base = P;
+            P += contigs[r].P;
+            max_p = std::max(max_p, contigs[r].P);
+        }
+    }
+    if (pos_stats && P > pos_cap) return fail(NPORE_E_INVALID, "pos_stats holds fewer rows than the ranges have positions");
+    std::vector<int32_t> h_rid;
+    std::vector<int64_t> h_lo, h_hi;
+    for (size_t r = 0; r < n_refs; r++)
+        if (!contigs[r].ranges.empty()) { h_rid.push_back((int32_t)r); h_lo.push_back(contigs[r].lo); h_hi.push_back(contigs[r].hi); }
+
+    PurRun run;
+    run.ctx = ctx;
+    run.s = ctx->stream;
+    run.min_bq = min_bq;
+    run.W = ctx->purity_window;
+    run.stride = std::max<int64_t>(64, std::min(run.W, max_p));
+    run.batch_reads = ctx->cms_batch_reads;
+    run.pos_stats = pos_stats;
+    hipStream_t s = run.s;
+    if (int rc = ctx->pur_cnt.ensure((size_t)run.stride * PUR_PLANES * 4)) return rc;
+    if (int rc = ctx->pur_v2.ensure((size_t)run.stride * 8)) return rc;
+    if (int rc = ctx->pur_out.ensure(PurRun::out_bytes())) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->pur_cnt.p, 0, (size_t)run.stride * PUR_PLANES * 4, s));
+    HIP_TRY(hipMemsetAsync(ctx->pur_v2.p, 0, (size_t)run.stride * 8, s));
+    HIP_TRY(hipMemsetAsync(ctx->pur_out.p, 0, PurRun::out_bytes(), s));
+    if (pos_stats && P > 0) std::memset(pos_stats, 0, (size_t)P * 32);
+    int64_t ht[PUR_N_TALLIES] = {};
+
+    // What the host needs of every record of a reader's batch, found on all cores: the gate (cms_gate: 0 = walked, -1 = none
+    // of the ranges' records, else the tally it goes to), its I operations, the windows its positions lie in
+    struct RecInfo {
+        int gate;
+        int32_t no_entry, ins_ops;
+        int64_t w0, w1;
+    };
+    std::vector<RecInfo> info;
+    RecFetch rf;                         // the reader's batch
+    auto survey = [&](int64_t m) {
+        info.assign((size_t)m, RecInfo{-1, 0, 0, -1, -1});
+        const int64_t per = 64;
+        parallel_for((m + per - 1) / per, 0, [&](int64_t tix) {
+            for (int64_t k = tix * per; k < std::min(m, (tix + 1) * per); k++) {
+                const RecView r = rec_of(rf, k);
+                const int32_t rid = r.ref_id();
+                if (rid < 0 || rid >= (int32_t)n_refs || contigs[(size_t)rid].ranges.empty()) continue;
+                const PurContig &c = contigs[(size_t)rid];
+                const int32_t one_layer[2] = {0, (int32_t)c.ranges.size()};
+                RecInfo &ri = info[(size_t)k];
+                ri.gate = cms_gate((uint32_t)r.flag(), r.pos(), r.l_seq(), r.cigar(), r.n_cigar(), exclude_flags, c.ranges.data(), one_layer, 1);
+                if (ri.gate < 0) continue;
+                const int64_t end = r.pos() + cms_span(r.cigar(), r.n_cigar()).rl;
+                ri.w0 = pur_first_dense(c.ranges.data(), (int)c.ranges.size(), r.pos(), end) / run.W;
+                ri.w1 = pur_last_dense(c.ranges.data(), (int)c.ranges.size(), r.pos(), end) / run.W;
+                if (ri.gate != 0) continue;
+                ri.no_entry = pur_ins_no_entry(r.cigar(), r.n_cigar());
+                ri.ins_ops = pur_ins_ops(r.cigar(), r.n_cigar());
+            }
+        });
+    };
+    // true: walked.  first: count what is a matter of the record, not of a window
+    auto gate = [&](const RecInfo &ri, bool first) -> bool {
+        if (ri.gate > 0 && first) ht[ri.gate]++;
+        if (ri.gate != 0) return false;
+        if (first) {
+            ht[PUR_T_RECORDS]++;
+            ht[PUR_T_INS_NO_ENTRY] += ri.no_entry;
+        }
+        return true;
+    };
+
+    const bool one_pass = b->file && !b->blocks.empty() && b->rec_off.empty();
+    const int threads = 0;
+    if (one_pass) {
+        // ONE PASS over a coordinate-sorted file: the windows advance with the records; a record that reaches past the
+        // window's end is carried (a copy of its head) into the next one
+        if (int rc = one_pass_args_check(b, (int)h_rid.size(), h_rid.data(), 0)) return rc;
+        BamRecordWalker walker(b, (int)h_rid.size(), h_rid.data(), h_lo.data(), h_hi.data(), 0, threads, 0u);
+        std::vector<std::shared_ptr<RawBuf>> keep;
+        struct Carried { std::vector<uint8_t> bytes; int64_t w1, ins_ops; };
+        std::vector<Carried> carry;
+        // to window `target` of the current contig, through every window on the way that a carried record has positions in
+        auto advance_to = [&](int64_t target) -> int {
+            while (run.c && run.w < target) {
+                if (int rc = run.finish_window()) return rc;
+                std::vector<Carried> still;
+                for (Carried &cr : carry)
+                    if (cr.w1 > run.w) still.push_back(std::move(cr));
+                carry = std::move(still);
+                if (carry.empty()) {
+                    if (target < run.n_windows()) run.set_window(target);
+                    break;
+                }
+                run.set_window(run.w + 1);
+                for (const Carried &cr : carry)
+                    if (int rc = run.add(cr.bytes.data(), cr.ins_ops)) return rc;
+            }
+            return NPORE_OK;
+        };
+        int32_t cur_rid = -1;
+        int64_t last_pos = -1;
+        for (;;) {
+            keep.clear();
+            const int64_t m = walker.next_batch(rf, keep, run.batch_reads);
+            if (m < 0) return (int)m;
+            if (m == 0) break;
+            survey(m);
+            for (int64_t k = 0; k < m; k++) {
+                const RecView r = rec_of(rf, k);
+                const int32_t rid = r.ref_id();
+                if (rid < 0 || rid >= (int32_t)n_refs || contigs[(size_t)rid].ranges.empty()) continue;
+                if (rid == cur_rid && r.pos() < last_pos)
+                    return fail(NPORE_E_UNSUPPORTED, "the BAM is not sorted by position: one-pass purity needs a coordinate-sorted file");
+                if (rid != cur_rid) {
+                    if (int rc = advance_to(INT64_MAX)) return rc;
+                    if (int rc = run.finish_window()) return rc;
+                    carry.clear();
+                    if (int rc = run.set_contig(contigs[(size_t)rid])) return rc;
+                    cur_rid = rid;
+                }
+                last_pos = r.pos();
+                const RecInfo &ri = info[(size_t)k];
+                if (!gate(ri, true)) continue;
+                if (ri.w0 > run.w)
+                    if (int rc = advance_to(ri.w0)) return rc;
+                if (ri.w1 > run.w) {
+                    carry.push_back(Carried{std::vector<uint8_t>(rf.ptr[(size_t)k], r.aux()), ri.w1, ri.ins_ops});
+                    if (int rc = run.add(carry.back().bytes.data(), ri.ins_ops)) return rc;
+                } else if (int rc = run.add(rf.ptr[(size_t)k], ri.ins_ops)) return rc;
+            }
+            if (int rc = run.flush()) return rc;     // (the records' bytes go with the reader's next batch)
+        }
+        if (int rc = advance_to(INT64_MAX)) return rc;
+        if (int rc = run.finish_window()) return rc;
+    } else {
+        // INDEXED reader: select per window
+        std::vector<int64_t> idx;
+        for (size_t q = 0; q < h_rid.size(); q++) {
+            const int32_t rid = h_rid[q];
+            const PurContig &c = contigs[(size_t)rid];
+            if (int rc = run.set_contig(c)) return rc;
+            for (int64_t w = 0; w < run.n_windows(); w++) {
+                run.set_window(w);
+                const int64_t k = bam_select(b, 1, &rid, &run.ref_lo, &run.ref_hi, 0, nullptr, 0, 0u);
+                if (k < 0) return (int)k;
+                if (k == 0) continue;
+                idx.assign((size_t)k + 1, 0);
+                if (bam_select(b, 1, &rid, &run.ref_lo, &run.ref_hi, 0, idx.data(), k, 0u) != k) return fail(NPORE_E_INVALID, "select is not repeatable");
+                for (int64_t at = 0; at < k; at += run.batch_reads) {
+                    const int64_t m = std::min(run.batch_reads, k - at);
+                    if (int rc = fetch_records(b, idx.data() + at, m, threads, rf)) return rc;
+                    survey(m);
+                    for (int64_t i = 0; i < m; i++) {
+                        const RecInfo &ri = info[(size_t)i];
+                        if (ri.gate < 0 || w < ri.w0 || w > ri.w1) continue;      // (the window's hull holds positions of no range, too)
+                        if (!gate(ri, w == ri.w0)) continue;
+                        if (int rc = run.add(rf.ptr[(size_t)i], ri.ins_ops)) return rc;
+                    }
+                    if (int rc = run.flush()) return rc;
+                }
+                if (int rc = run.finish_window()) return rc;
+            }
+        }
+    }
+    std::vector<unsigned long long> h(PurRun::out_bytes() / 8);
+    HIP_TRY(hipMemcpyAsync(h.data(), ctx->pur_out.p, PurRun::out_bytes(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h[2 * PUR_BINS + PUR_D_OVERFLOW] != 0) return fail(NPORE_E_INVALID, "internal: the insertion event buffer was too small");
+    for (int k = 0; k < PUR_BINS; k++) { base_hist[k] += (int64_t)h[(size_t)k]; ins_hist[k] += (int64_t)h[(size_t)(PUR_BINS + k)]; }
+    for (int k = 0; k < PUR_N_TALLIES; k++) tallies[k] += (int64_t)h[(size_t)(2 * PUR_BINS + k)] + ht[k];
+    tallies[PUR_T_WINDOWS] += run.windows;
+    tallies[PUR_T_BATCHES] += run.batches;
+    tallies[PUR_T_KERNEL_NS] += (int64_t)(run.kernel_ms * 1e6);
     return NPORE_OK;
 }
 NPORE_CATCH_INT

@@ -310,8 +310,10 @@ int npore_bam_format_sam(npore_bam *bam, const int64_t *idx, int64_t n, const ch
 
 /* The same reads as BAM records (csrc/bam_reader.hpp states the record: the SAM line's fields in binary, the final CIGAR
  * as `len << 4 | op` words, bases and qualities without the soft clips, next_refID = next_pos = -1, tlen = the reference
- * length, the HP tag in the smallest integer type), one after the other, each with its block_size word.
- * NPORE_E_UNSUPPORTED: a final CIGAR of more than 65 535 operations.  *recs points into storage owned by `bam`. */
+ * length, the HP tag in the smallest integer type), one after the other, each with its block_size word.  A final
+ * CIGAR of more than 65 535 operations is written as htslib writes it: n_cigar_op = 2, the placeholder words
+ * `l_seq S`, `reflen N`, and the real words in a CG:B,I tag behind HP.  NPORE_E_UNSUPPORTED: a final text that is no
+ * CIGAR.  *recs points into storage owned by `bam`. */
 int npore_bam_format_bam(npore_bam *bam, const int64_t *idx, int64_t n, const char *finals, const int64_t *final_off,
                          const int64_t *final_len, const int32_t *status, int threads, const uint8_t **recs,
                          int64_t *recs_len);

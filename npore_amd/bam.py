@@ -72,8 +72,47 @@ class BamRecord:
     __slots__ = ("query_name", "flag", "ref_id", "reference_start", "mapping_quality", "cigar", "seq", "qual", "hp")
 
 
+MAX_CIGAR_OPS = 0xFFFF               # what n_cigar_op holds; more operations go into the CG tag
+
+
+def resolve_long_cigar(cigar, l_seq, ref_id, pos, aux):
+    """The real CIGAR of a record (SAM specification 4.2.2, the rule of csrc/hostio.hpp rec_cigar): `cigar` [(op, len)]
+    unless it begins with `<l_seq>S`, the record is placed and its tags `aux` hold CG:B,I (or B,i) with at least as many
+    words as `cigar` has operations (and fewer than 2^29), all inside the record -- then those words."""
+    if not cigar or cigar[0] != (4, l_seq) or l_seq >= 1 << 28 or ref_id < 0 or pos < 0:
+        return cigar
+    q, end = 0, len(aux)
+    while q + 3 <= end:
+        tag, typ = aux[q:q + 2], chr(aux[q + 2])
+        q += 3
+        if typ in "cCA":
+            w = 1
+        elif typ in "sS":
+            w = 2
+        elif typ in "iIf":
+            w = 4
+        elif typ in "ZH":
+            z = aux.find(b"\0", q)
+            w = (z if z >= 0 else end) - q + 1
+        elif typ == "B" and end - q >= 5 and chr(aux[q]) in "cCsSiIf":
+            w = 5 + struct.unpack_from("<I", aux, q + 1)[0] * {"c": 1, "C": 1, "s": 2, "S": 2}.get(chr(aux[q]), 4)
+        else:
+            return cigar
+        if w > end - q:
+            return cigar
+        if tag == b"CG":
+            if typ != "B" or chr(aux[q]) not in "Ii":
+                return cigar
+            n, = struct.unpack_from("<I", aux, q + 1)
+            if n < len(cigar) or n >= 1 << 29:
+                return cigar
+            return [(c & 15, c >> 4) for c in struct.unpack_from(f"<{n}I", aux, q + 5)]
+        q += w
+    return cigar
+
+
 class BamFile:
-    """Minimal reader: header text, reference names/lengths, all records."""
+    """Minimal reader: header text, reference names/lengths, all records (a long CIGAR resolved from its CG tag)."""
 
     def refs_with_reads(self):
         return {r.ref_id for r in self.records if r.ref_id >= 0}
@@ -118,6 +157,7 @@ class BamFile:
             q += l_seq
             r.hp = None
             end = p + 4 + block_size
+            r.cigar = resolve_long_cigar(r.cigar, l_seq, ref_id, pos, bytes(data[q:end]))
             while q + 3 <= end:      # optional fields: find HP
                 tag, typ = data[q:q + 2], chr(data[q + 2])
                 q += 3
@@ -270,13 +310,17 @@ def bam_record(rd, final, references=None):
     reflen = stop - start
     name = read_id.encode() + b"\0"
     cig = [(int(n), "MIDNSHP=X".index(op)) for n, op in re.findall(r"(\d+)([MIDNSHP=X])", final)]
+    words = b"".join(struct.pack("<I", (n << 4) | op) for n, op in cig)
+    tags = hp_tag(hap)
+    if len(cig) > MAX_CIGAR_OPS:         # as htslib writes it: the placeholder <l_seq>S<reflen>N, the words in CG:B,I behind HP
+        tags += b"CGBI" + struct.pack("<I", len(cig)) + words
+        words = struct.pack("<II", (len(sseq) << 4) | 4, (reflen << 4) | 3)
     code = {c: i for i, c in enumerate(_SEQ16)}
     nib = [code[c] for c in sseq] + ([0] if len(sseq) & 1 else [])
     packed = bytes((nib[k] << 4) | nib[k + 1] for k in range(0, len(nib), 2))
     qual = bytes([0xFF]) * len(sseq) if quals == "*" else bytes(ord(c) - 33 for c in quals)
-    body = (struct.pack("<iiBBHHHiiii", ref_id, start, len(name), mapq, reg2bin(start, start + max(1, reflen)), len(cig), flag,
-                        len(sseq), -1, -1, reflen) + name + b"".join(struct.pack("<I", (n << 4) | op) for n, op in cig) +
-            packed + qual + hp_tag(hap))
+    body = (struct.pack("<iiBBHHHiiii", ref_id, start, len(name), mapq, reg2bin(start, start + max(1, reflen)), len(words) // 4,
+                        flag, len(sseq), -1, -1, reflen) + name + words + packed + qual + tags)
     return struct.pack("<i", len(body)) + body
 
 
@@ -1417,7 +1461,10 @@ def merge_bai_parts(parts):
 def write_bam(path, references, records, level=6):
     """Write a BAM file (tests / benchmarks).  references: [(name, length)]; records: dicts with
     name, flag, ref_id, pos, mapq, cigar [(op, len)], seq (str over =ACMGRSVTWYHKDBN), qual (bytes or None),
-    hp (int or None)."""
+    hp (int or None); optional: tags (raw tag bytes written in front of HP), long_cigar (True: the CIGAR goes out as
+    the placeholder <l_seq>S<reflen>N with the real words in a CG:B,I tag behind HP, as for every record of more than
+    65 535 operations; "i": the same with subtype i; "front": the CG tag in front of `tags` and HP)."""
+    ref_len_of_op = (1, 0, 1, 1, 0, 0, 0, 1, 1)
     text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in references)
     out = bytearray(b"BAM\1" + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", len(references)))
     for n, l in references:
@@ -1430,9 +1477,15 @@ def write_bam(path, references, records, level=6):
         packed = ((nib[0::2] << 4) | nib[1::2]).astype(np.uint8).tobytes() if len(seq) else b""
         qual = r.get("qual")
         qual = bytes([0xFF]) * len(seq) if qual is None else bytes(qual)
-        cig = b"".join(struct.pack("<I", (ln << 4) | op) for op, ln in r["cigar"])
-        aux = b"" if r.get("hp") is None else b"HPC" + bytes([r["hp"]])
-        body = struct.pack("<iiBBHHHiiii", r["ref_id"], r["pos"], len(name), r.get("mapq", 60), 4680, len(r["cigar"]),
+        cig = np.array([(ln << 4) | op for op, ln in r["cigar"]], "<u4").tobytes()
+        aux = bytes(r.get("tags", b"")) + (b"" if r.get("hp") is None else b"HPC" + bytes([r["hp"]]))
+        long_cigar = r.get("long_cigar") or len(r["cigar"]) > MAX_CIGAR_OPS
+        if long_cigar:
+            cg = b"CGB" + (b"i" if long_cigar == "i" else b"I") + struct.pack("<I", len(r["cigar"])) + cig
+            aux = cg + aux if long_cigar == "front" else aux + cg
+            reflen = sum(ln * ref_len_of_op[op] for op, ln in r["cigar"])
+            cig = struct.pack("<II", (len(seq) << 4) | 4, (reflen << 4) | 3)
+        body = struct.pack("<iiBBHHHiiii", r["ref_id"], r["pos"], len(name), r.get("mapq", 60), 4680, len(cig) // 4,
                            r["flag"], len(seq), -1, -1, 0) + name + cig + packed + qual + aux
         out += struct.pack("<i", len(body)) + body
     with open(path, "wb") as fh:

@@ -11,6 +11,8 @@
 //                             follow each other on one stream, hand on);
 //   emit_bam_records_kernel   one wavefront per read: fixed fields, name, CIGAR words, the 4-bit bases from the leading
 //                             soft clip on (an odd clip moves every nibble), the quality slice, the HP tag.
+// A final CIGAR of more than 65 535 operations goes out as htslib writes it (bam_reader.hpp RECORD): two placeholder words
+// in the CIGAR's place, the real words in a CG:B,I tag behind HP -- 16 bytes more, in both kernels.
 // The host then takes the batch's bytes as they lie (BgzfStoredWriter) and the records' lengths for its index.
 // Both run beside the next batch's fill kernel and keep to what the other light kernels keep to: at most
 // 64 vector registers; the placement's 2 KB of LDS are less than a fill workgroup leaves free, the assembly has none.
@@ -23,7 +25,7 @@
 namespace npore {
 
 struct BamEmitParams {
-    const uint8_t *raw;            // the group's records, block_size word first, up to the end of the qualities
+    const uint8_t *raw;            // the group's staged heads (hostio.hpp stage_record_head), with the qualities
     const int64_t *raw_off;        // [n_reads + 1]
     const int64_t *ref_off;        // [n_reads + 1]: reference length of read k = ref_off[k + 1] - ref_off[k]
     const int64_t *seq_off;        // [n_reads + 1]: bases without the soft clips
@@ -57,6 +59,9 @@ __device__ __forceinline__ uint32_t bam_reg2bin_dev(int64_t beg, int64_t end)   
     return 0;
 }
 
+// more operations than n_cigar_op holds: placeholder + CG tag
+__device__ __forceinline__ bool bam_long_cigar(int64_t words_bytes) { return words_bytes > 4 * 0xFFFF; }
+
 // size of read k's record (0: not written -- NPORE_ST_BAD_INPUT, as format_sam_into leaves the line out)
 __device__ __forceinline__ int64_t bam_record_size(const BamEmitParams &p, int64_t k)
 {
@@ -64,7 +69,7 @@ __device__ __forceinline__ int64_t bam_record_size(const BamEmitParams &p, int64
     if (p.status[g] & 32) return 0;
     const uint8_t *f = p.raw + p.raw_off[k] + 4;
     const int64_t sl = p.seq_off[k + 1] - p.seq_off[k], wl = p.words_len[g] > 0 ? p.words_len[g] : 0;
-    return 36 + (int64_t)f[8] + wl + (sl + 1) / 2 + sl + 3 + bam_hp_bytes(p.hp[k]);
+    return 36 + (int64_t)f[8] + wl + (sl + 1) / 2 + sl + 3 + bam_hp_bytes(p.hp[k]) + (bam_long_cigar(wl) ? 16 : 0);
 }
 
 // one workgroup of 256: every thread sizes a contiguous share of the reads; their places follow from the sums of the shares
@@ -135,9 +140,12 @@ __global__ __launch_bounds__(64) void emit_bam_records_kernel(BamEmitParams p)
     const int64_t g = p.read_base + k;
     const uint8_t *f = p.raw + p.raw_off[k] + 4;                 // the fixed fields (hostio.hpp RecView)
     const int32_t pos = (int32_t)ld32(f + 4);
-    const int l_rn = f[8], nc = (int)ld16(f + 12);
+    const int l_rn = f[8];
     const int64_t l_seq = (int32_t)ld32(f + 16);
-    const uint8_t *cg = f + 32 + l_rn, *sq = cg + 4 * (size_t)nc, *ql = sq + (l_seq + 1) / 2;
+    const uint8_t *cg, *sq;
+    int nc;
+    staged_cigar(f, cg, nc, sq);
+    const uint8_t *ql = sq + (l_seq + 1) / 2;
     auto op_of = [&](int c) { return ld32(cg + 4 * (size_t)c); };
     int64_t lead = 0;                                            // (hostio.hpp rec_clips)
     if (nc >= 1 && (op_of(0) & 15u) == 4) lead = op_of(0) >> 4;
@@ -146,6 +154,7 @@ __global__ __launch_bounds__(64) void emit_bam_records_kernel(BamEmitParams p)
     const int64_t wl = p.words_len[g] > 0 ? p.words_len[g] : 0, nb = (sl + 1) / 2;
     const int64_t hp = p.hp[k];
     const int hb = bam_hp_bytes(hp);
+    const bool lng = bam_long_cigar(wl);
     uint8_t *o = p.recs + p.rec_off[k];
     if (lane < 9) {                                              // block_size and the fixed fields, a word per lane
         uint32_t w = 0xFFFFFFFFu;                                // (next_refID, next_pos)
@@ -154,7 +163,7 @@ __global__ __launch_bounds__(64) void emit_bam_records_kernel(BamEmitParams p)
             case 1: w = ld32(f); break;
             case 2: w = (uint32_t)pos; break;
             case 3: w = (uint32_t)l_rn | (uint32_t)f[9] << 8 | bam_reg2bin_dev(pos, (int64_t)pos + max((int64_t)1, reflen)) << 16; break;
-            case 4: w = (uint32_t)(wl >> 2) | ld16(f + 14) << 16; break;
+            case 4: w = (lng ? 2u : (uint32_t)(wl >> 2)) | ld16(f + 14) << 16; break;
             case 5: w = (uint32_t)sl; break;
             case 8: w = (uint32_t)reflen; break;
             default: break;
@@ -165,8 +174,17 @@ __global__ __launch_bounds__(64) void emit_bam_records_kernel(BamEmitParams p)
     o += 36;
     for (int j = lane; j < l_rn; j += 64) o[j] = f[32 + j];
     o += l_rn;
-    wave_copy<0>(o, p.words + p.words_off[g], wl, false, lane);
-    o += wl;
+    if (lng) {                                                   // the placeholder: <l_seq>S<reflen>N
+        if (lane < 2) {
+            const uint32_t w = lane == 0 ? ((uint32_t)sl << 4 | 4u) : ((uint32_t)reflen << 4 | 3u);
+            uint8_t *q = o + 4 * lane;
+            q[0] = (uint8_t)w; q[1] = (uint8_t)(w >> 8); q[2] = (uint8_t)(w >> 16); q[3] = (uint8_t)(w >> 24);
+        }
+        o += 8;
+    } else {
+        wave_copy<0>(o, p.words + p.words_off[g], wl, false, lane);
+        o += wl;
+    }
     if (sl > 0) {
         if (lead & 1) wave_copy<1>(o, sq + (lead >> 1), nb, (sl & 1) != 0, lane);
         else wave_copy<0>(o, sq + (lead >> 1), nb, (sl & 1) != 0, lane);
@@ -180,6 +198,12 @@ __global__ __launch_bounds__(64) void emit_bam_records_kernel(BamEmitParams p)
         o[2] = (uint8_t)(hp >= 0 ? (hb == 1 ? 'C' : hb == 2 ? 'S' : 'I') : (hb == 1 ? 'c' : hb == 2 ? 's' : 'i'));
         const uint32_t v = (uint32_t)(int32_t)hp;
         for (int q = 0; q < hb; q++) o[3 + q] = (uint8_t)(v >> (8 * q));
+    }
+    if (lng) {                                                   // CG:B,I behind HP: the count, then the words
+        o += 3 + hb;
+        if (lane < 4) o[lane] = (uint8_t)"CGBI"[lane];
+        else if (lane < 8) o[lane] = (uint8_t)((uint32_t)(wl >> 2) >> (8 * (lane - 4)));
+        wave_copy<0>(o + 8, p.words + p.words_off[g], wl, false, lane);
     }
 }
 

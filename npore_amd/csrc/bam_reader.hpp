@@ -454,11 +454,11 @@ inline void pack_sizes_of(const RecFetch &rf, int64_t n, int64_t *ref_off, int64
     parallel_for((n + per - 1) / per, threads, [&](int64_t t) {
         for (int64_t k = t * per; k < std::min(n, (t + 1) * per); k++) {
             const RecView r = rec_of(rf, k);
+            const RecCigar cg = rec_cigar(r);
             int64_t lead, trail, ops = 0, rl = 0;
-            rec_clips(r, lead, trail);
-            const int nc = r.n_cigar();
-            for (int c = 0; c < nc; c++) {
-                const uint32_t w = r.cig(c), op = w & 15u, len = w >> 4;
+            rec_clips(cg, lead, trail);
+            for (uint32_t c = 0; c < cg.n; c++) {
+                const uint32_t w = cg.op(c), op = w & 15u, len = w >> 4;
                 if (op != 4 && op != 5) ops += len;
                 if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += len;      // (rec_ref_len: M D N = X)
             }
@@ -492,16 +492,16 @@ inline int pack_records(const npore_bam *b, const RecFetch &rf, const npore_fast
             std::memset(ro + q1, 0, (size_t)(rl - q1));
         }
         // query bases without the soft clips (src/bam.pyx:42)
+        const RecCigar cg = rec_cigar(r);
         int64_t lead, trail;
-        rec_clips(r, lead, trail);
+        rec_clips(cg, lead, trail);
         uint8_t *so = seqs + seq_off[k];
         const int64_t sl = seq_off[k + 1] - seq_off[k];
         nibble_codes(r.seq(), lead, so, sl);
         // expanded CIGAR without S and H (src/bam.pyx:59)
         char *co = cigs + cig_off[k];
-        const int nc = r.n_cigar();
-        for (int c = 0; c < nc; c++) {
-            const uint32_t w = r.cig(c), op = w & 15u, len = w >> 4;
+        for (uint32_t c = 0; c < cg.n; c++) {
+            const uint32_t w = cg.op(c), op = w & 15u, len = w >> 4;
             if (op == 4 || op == 5) continue;
             const char ch = op < 10 ? CIGOPS[op] : '?';
             if (len <= 8) { for (uint32_t q = 0; q < len; q++) co[q] = ch; }      // (most runs are a few ops long)
@@ -565,15 +565,16 @@ inline int format_sam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     auto line = [&](int64_t k, char *dst) -> int64_t {    // returns the length; writes when dst != nullptr
         if (status[k] & NPORE_ST_BAD_INPUT) return 0;    // refused reads are not written
         const RecView r = rec_of(rf, k);
+        const RecCigar cg = rec_cigar(r);
         int64_t lead, trail;
-        rec_clips(r, lead, trail);
+        rec_clips(cg, lead, trail);
         const int64_t sl = std::max<int64_t>(0, (int64_t)r.l_seq() - lead - trail);
         const int32_t rid = r.ref_id();
         const std::string &rn = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? b->ref_names[(size_t)rid] : std::string("*");
         const bool noq = r.l_seq() == 0 || r.qual()[0] == 0xFF;
         const size_t nl = std::strlen(r.name());
         const long long flag = r.flag(), pos1 = (long long)r.pos() + 1, mapq = r.mapq(), hp = (long long)rec_hp(r),
-                        reflen = (long long)rec_ref_len(r);
+                        reflen = (long long)rec_ref_len(cg);
         if (!dst)       // name \t flag \t rname \t pos \t mapq \t cigar \t * \t 0 \t tlen \t seq \t qual \t HP:i:n \n
             return (int64_t)nl + 1 + put_int(nullptr, flag) + 1 + (int64_t)rn.size() + 1 + put_int(nullptr, pos1) + 1 +
                    put_int(nullptr, mapq) + 1 + final_len[k] + 5 + put_int(nullptr, reflen) + 1 + sl + 1 + (noq ? 1 : sl) + 6 +
@@ -636,8 +637,12 @@ inline int format_sam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
 //   - next_refID = next_pos = -1 (SAM's `*` and `0`), tlen = reflen (SAM's `stop - start`);
 //   - one tag, HP, as the smallest integer type that holds it in htslib's order: C, S, I from 0 up, c, s, i below; 0 when
 //     the input has none.
-//   A record's size is 36 + l_read_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq + 3 + {1, 2, 4}.  More than 65 535 CIGAR
-//   operations would need the CG tag: refused (NPORE_E_UNSUPPORTED).
+//   A record's size is 36 + l_read_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq + 3 + {1, 2, 4}.
+//   - a final CIGAR of n > 65 535 operations does not fit n_cigar_op; it is written as htslib writes it (SAM specification
+//     4.2.2): n_cigar_op = 2, the CIGAR field holds the placeholder `l_seq << 4 | 4`, `reflen << 4 | 3`, and a second tag
+//     BEHIND HP carries the words: 'C' 'G' 'B' 'I', the 32-bit count n, the n words.  Size: 36 + l_read_name + 8 +
+//     (l_seq + 1) / 2 + l_seq + 3 + {1, 2, 4} + 8 + 4 * n.  bin, tlen and the index entry come from the real reference
+//     length as always.  (The input side of the same rule: hostio.hpp rec_cigar.)
 // FILE.  BGZF with STORED deflate members (level 0, what `samtools view -u` writes): 18 bytes of gzip header with the BC
 //   field, one stored block (01 LEN NLEN), the payload, CRC-32 and ISIZE -- payload + 31 bytes.  The header (text +
 //   reference list) lies in members of its own; the record stream is cut every 65 280 payload bytes counted from the
@@ -675,21 +680,23 @@ inline int64_t cigar_text_ops(const char *t, int64_t n)
     return digits ? -1 : ops;
 }
 // The BAM record of read `r` with its final CIGAR text: its size (dst == nullptr) or its bytes at dst; 0 = the read is
-// not written, < 0 = it cannot be (a final text that is no CIGAR, too many operations).  `meta`: what the index needs.
+// not written, < 0 = it cannot be (a final text that is no CIGAR).  `meta`: what the index needs.
 inline int64_t bam_record_into(const RecView &r, const char *final_text, int64_t final_len, int32_t status, uint8_t *dst,
                                BamRecMeta *meta = nullptr)
 {
     if (status & NPORE_ST_BAD_INPUT) return 0;
+    const RecCigar in_cg = rec_cigar(r);
     int64_t lead, trail;
-    rec_clips(r, lead, trail);
+    rec_clips(in_cg, lead, trail);
     const int64_t sl = std::max<int64_t>(0, (int64_t)r.l_seq() - lead - trail);
     const int64_t n_cig = cigar_text_ops(final_text, final_len);
-    if (n_cig < 0 || n_cig > 0xFFFF) return -1;
+    if (n_cig < 0) return -1;
+    const bool lng = n_cig > 0xFFFF;                 // placeholder + CG tag
     const int64_t hp = rec_hp(r);
     const int l_rn = r.l_read_name(), hb = bam_hp_tag_bytes(hp);
-    const int64_t size = 36 + l_rn + 4 * n_cig + (sl + 1) / 2 + sl + 3 + hb;
+    const int64_t size = 36 + l_rn + 4 * n_cig + (sl + 1) / 2 + sl + 3 + hb + (lng ? 16 : 0);
     if (!dst) return size;
-    const int64_t reflen = rec_ref_len(r);
+    const int64_t reflen = rec_ref_len(in_cg);
     auto w32 = [](uint8_t *o, uint32_t v) { std::memcpy(o, &v, 4); };
     auto w16 = [](uint8_t *o, uint16_t v) { std::memcpy(o, &v, 2); };
     uint8_t *o = dst;
@@ -699,7 +706,7 @@ inline int64_t bam_record_into(const RecView &r, const char *final_text, int64_t
     o[12] = (uint8_t)l_rn;
     o[13] = (uint8_t)r.mapq();
     w16(o + 14, (uint16_t)bam_reg2bin(r.pos(), (int64_t)r.pos() + std::max<int64_t>(1, reflen)));
-    w16(o + 16, (uint16_t)n_cig);
+    w16(o + 16, (uint16_t)(lng ? 2 : n_cig));
     w16(o + 18, (uint16_t)r.flag());
     w32(o + 20, (uint32_t)sl);
     w32(o + 24, 0xFFFFFFFFu);
@@ -708,6 +715,15 @@ inline int64_t bam_record_into(const RecView &r, const char *final_text, int64_t
     o += 36;
     std::memcpy(o, r.name(), (size_t)l_rn);
     o += l_rn;
+    uint8_t *const seq_at = lng ? o + 8 : o + 4 * n_cig;
+    if (lng) {                                       // the words go behind HP
+        w32(o, (uint32_t)sl << 4 | 4u);
+        w32(o + 4, (uint32_t)reflen << 4 | 3u);
+        o = seq_at + (sl + 1) / 2 + sl + 3 + hb;
+        std::memcpy(o, "CGBI", 4);
+        w32(o + 4, (uint32_t)n_cig);
+        o += 8;
+    }
     {
         uint32_t len = 0;
         for (int64_t q = 0; q < final_len; q++) {
@@ -719,6 +735,7 @@ inline int64_t bam_record_into(const RecView &r, const char *final_text, int64_t
             len = 0;
         }
     }
+    o = seq_at;
     {
         const uint8_t *sq = r.seq() + (lead >> 1);
         const int64_t nb = (sl + 1) / 2;
@@ -752,7 +769,7 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
         if (sz < 0) bad++;
         off[(size_t)k + 1] = std::max<int64_t>(sz, 0);
     });
-    if (bad) return fail(NPORE_E_UNSUPPORTED, "a final CIGAR is no CIGAR text or has more than 65535 operations (BAM output)");
+    if (bad) return fail(NPORE_E_UNSUPPORTED, "a final CIGAR is no CIGAR text (BAM output)");
     for (int64_t k = 0; k < n; k++) off[(size_t)k + 1] += off[(size_t)k];
     if (!out.ensure((size_t)off[(size_t)n] + 8)) return fail(NPORE_E_NOMEM, "BAM record buffer");
     std::vector<BamRecMeta> all;

@@ -659,27 +659,120 @@ inline bool bam_fetch(const npore_bam &b, const int64_t *idx, int64_t n, int thr
     return true;
 }
 
+// ---- the real CIGAR of a record ------------------------------------------------------------------------------------
+// BAM keeps n_cigar_op in 16 bits; a read with more operations carries the placeholder CIGAR `<l_seq>S<reflen>N` and its
+// real CIGAR in the tag CG:B,I (SAM specification 4.2.2).  A record has such a LONG CIGAR when all of this holds (htslib
+// applies the same rule when it reads a record): n_cigar_op >= 1, refID >= 0, pos >= 0; the first operation is S with
+// length l_seq; the tags hold CG of type B with subtype I or i; its count n satisfies n_cigar_op <= n < 2^29; the array
+// lies inside the record.  Then the n words of the array are the record's CIGAR -- in every other case the record's own
+// stands.  Everything that walks a CIGAR for the MEANING of the alignment (clips, lengths, pack, recount, purity, the
+// writers) takes it from rec_cigar(); record_is_sound, the framing and seq() / qual() / aux() read the stored fields.
+// The tags are walked only behind a first operation `l_seq S`: ordinary records pay one compare.
+struct RecCigar {
+    const uint8_t *w;          // the words, little-endian, unaligned
+    uint32_t n;
+    uint32_t op(uint32_t k) const { return rd32(w + 4 * (size_t)k); }
+};
+
+// bytes of the value of a tag of type `typ` at q (behind the three bytes of tag and type); 0: unknown type or the value
+// leaves [q, end)
+inline size_t aux_value_bytes(const uint8_t *q, const uint8_t *end, char typ)
+{
+    size_t w = 0;
+    switch (typ) {
+        case 'c': case 'C': case 'A': w = 1; break;
+        case 's': case 'S': w = 2; break;
+        case 'i': case 'I': case 'f': w = 4; break;
+        case 'Z': case 'H': { const uint8_t *z = q; while (z < end && *z) z++; w = (size_t)(z - q) + 1; break; }
+        case 'B': {
+            if ((size_t)(end - q) < 5) return 0;
+            const char sub = (char)q[0];
+            const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+            if (!es) return 0;
+            w = 5 + (size_t)rd32(q + 1) * es;
+            break;
+        }
+        default: return 0;
+    }
+    return w <= (size_t)(end - q) ? w : 0;
+}
+
+inline RecCigar rec_cigar(const RecView &r)
+{
+    const RecCigar own{r.cigar(), (uint32_t)r.n_cigar()};
+    if (own.n < 1 || r.cig(0) != (((uint32_t)r.l_seq() << 4) | 4u) || r.l_seq() >= (1 << 28) || r.ref_id() < 0 || r.pos() < 0) return own;
+    const uint8_t *q = r.aux(), *end = r.end();
+    while (q + 3 <= end) {
+        const bool is_cg = q[0] == 'C' && q[1] == 'G';
+        const char typ = (char)q[2];
+        q += 3;
+        const size_t w = aux_value_bytes(q, end, typ);
+        if (!w) return own;                                // a tag that cannot be stepped over: nothing behind it is read
+        if (is_cg) {
+            if (typ != 'B' || (q[0] != 'I' && q[0] != 'i')) return own;
+            const uint32_t n = rd32(q + 1);
+            return (n >= own.n && n < (1u << 29)) ? RecCigar{q + 5, n} : own;
+        }
+        q += w;
+    }
+    return own;
+}
+
 // reference length consumed: M, D, N, =, X  (pysam reference_length)
-inline int64_t rec_ref_len(const RecView &r)
+inline int64_t rec_ref_len(const RecCigar &cg)
 {
     int64_t n = 0;
-    for (int k = 0; k < r.n_cigar(); k++) {
-        const uint32_t c = r.cig(k), op = c & 15u;
+    for (uint32_t k = 0; k < cg.n; k++) {
+        const uint32_t c = cg.op(k), op = c & 15u;
         if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) n += c >> 4;
     }
     return n;
 }
+inline int64_t rec_ref_len(const RecView &r) { return rec_ref_len(rec_cigar(r)); }
 
 // soft-clipped bases at either end (a hard clip may precede / follow them), src/bam.pyx:42-44 via
 // pysam query_alignment_sequence
-inline void rec_clips(const RecView &r, int64_t &lead, int64_t &trail)
+inline void rec_clips(const RecCigar &cg, int64_t &lead, int64_t &trail)
 {
-    const int nc = r.n_cigar();
+    const uint32_t nc = cg.n;
     lead = trail = 0;
-    if (nc >= 1 && (r.cig(0) & 15u) == 4) lead = r.cig(0) >> 4;
-    if (nc > 1 && (r.cig(0) & 15u) == 5 && (r.cig(1) & 15u) == 4) lead = r.cig(1) >> 4;
-    if (nc > 1 && (r.cig(nc - 1) & 15u) == 4) trail = r.cig(nc - 1) >> 4;
-    if (nc > 2 && (r.cig(nc - 1) & 15u) == 5 && (r.cig(nc - 2) & 15u) == 4) trail = r.cig(nc - 2) >> 4;
+    if (nc >= 1 && (cg.op(0) & 15u) == 4) lead = cg.op(0) >> 4;
+    if (nc > 1 && (cg.op(0) & 15u) == 5 && (cg.op(1) & 15u) == 4) lead = cg.op(1) >> 4;
+    if (nc > 1 && (cg.op(nc - 1) & 15u) == 4) trail = cg.op(nc - 1) >> 4;
+    if (nc > 2 && (cg.op(nc - 1) & 15u) == 5 && (cg.op(nc - 2) & 15u) == 4) trail = cg.op(nc - 2) >> 4;
+}
+inline void rec_clips(const RecView &r, int64_t &lead, int64_t &trail) { rec_clips(rec_cigar(r), lead, trail); }
+
+// ---- staged heads: what the device gets of a record ------------------------------------------------------------------
+// The kernels that read records (unpack, BAM emit, recount, purity) get each record's HEAD as it lies in the BAM stream
+// -- block_size word | 32 bytes of fixed fields | name | CIGAR words | 4-bit bases | (with_quals) qualities -- with ONE
+// difference: the CIGAR words are the record's real ones (rec_cigar: those of the CG tag for a long-CIGAR record, in the
+// place of the placeholder), and their count is 32-bit: its low half in the n_cigar_op field, its high half in the `bin`
+// field, which no kernel reads (the emit kernel recomputes the bin).  stage_record_head() writes both halves for every
+// record; staged_cigar() (staged_head.hpp) is the one reader, on the device and on the host.
+inline int64_t staged_head_bytes(const RecView &r, const RecCigar &cg, bool with_quals)
+{
+    return 4 + 32 + (int64_t)r.l_read_name() + 4 * (int64_t)cg.n + (int64_t)((with_quals ? r.aux() : r.qual()) - r.seq());
+}
+inline int64_t staged_head_bytes(const uint8_t *rec, bool with_quals)
+{
+    const RecView r = rec_view(rec);
+    return staged_head_bytes(r, rec_cigar(r), with_quals);
+}
+// rec: the record, block_size word first; dst: staged_head_bytes(rec, with_quals) bytes
+inline void stage_record_head(const uint8_t *rec, bool with_quals, uint8_t *dst)
+{
+    const RecView r = rec_view(rec);
+    const RecCigar cg = rec_cigar(r);
+    const size_t fixed = 4 + 32 + (size_t)r.l_read_name(), tail = (size_t)((with_quals ? r.aux() : r.qual()) - r.seq());
+    if (cg.w == r.cigar()) std::memcpy(dst, rec, fixed + 4 * (size_t)cg.n + tail);
+    else {
+        std::memcpy(dst, rec, fixed);
+        std::memcpy(dst + fixed, cg.w, 4 * (size_t)cg.n);
+        std::memcpy(dst + fixed + 4 * (size_t)cg.n, r.seq(), tail);
+    }
+    dst[4 + 10] = (uint8_t)(cg.n >> 16); dst[4 + 11] = (uint8_t)(cg.n >> 24);      // bin: the count's high half
+    dst[4 + 12] = (uint8_t)cg.n; dst[4 + 13] = (uint8_t)(cg.n >> 8);
 }
 
 // integer HP tag or 0 (src/bam.pyx:46)

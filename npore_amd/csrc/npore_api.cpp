@@ -728,7 +728,8 @@ try {
                 const int32_t rid = r.ref_id();
                 if (rid < 0 || rid >= (int32_t)n_refs || contigs[(size_t)rid].ranges.empty()) continue;
                 const CmsContig &c = contigs[(size_t)rid];
-                gate[(size_t)k] = cms_gate((uint32_t)r.flag(), r.pos(), r.l_seq(), r.cigar(), r.n_cigar(), exclude_flags, c.ranges.data(),
+                const RecCigar cg = rec_cigar(r);
+                gate[(size_t)k] = cms_gate((uint32_t)r.flag(), r.pos(), r.l_seq(), cg.w, (int)cg.n, exclude_flags, c.ranges.data(),
                                            c.layer_off.data(), (int)c.layer_off.size() - 1);
             }
         });
@@ -739,10 +740,9 @@ try {
             const int g = gate[(size_t)k];
             if (g > 0) ht.t[g]++;
             if (g != 0) continue;
-            const RecView r = rec_of(rf, k);
             kept.push_back(k);
-            kept_rid.push_back(r.ref_id());
-            rawo.push_back(rawo.back() + (((int64_t)(r.aux() - r.p) + 4 + 7) & ~7ll));
+            kept_rid.push_back(rec_of(rf, k).ref_id());
+            rawo.push_back(rawo.back() + ((staged_head_bytes(rf.ptr[(size_t)k], true) + 7) & ~7ll));
         }
         ht.t[CMS_T_BATCHES]++;
         const int64_t n = (int64_t)kept.size();
@@ -751,10 +751,8 @@ try {
         if (int rc = rawo_pin.ensure((size_t)(n + 1) * 8)) return rc;
         std::memcpy(rawo_pin.p, rawo.data(), (size_t)(n + 1) * 8);
         parallel_for((n + per - 1) / per, threads, [&](int64_t tix) {
-            for (int64_t k = tix * per; k < std::min(n, (tix + 1) * per); k++) {
-                const RecView r = rec_of(rf, kept[(size_t)k]);
-                std::memcpy(raw.p + rawo[(size_t)k], rf.ptr[(size_t)kept[(size_t)k]], (size_t)(r.aux() - r.p) + 4);
-            }
+            for (int64_t k = tix * per; k < std::min(n, (tix + 1) * per); k++)
+                stage_record_head(rf.ptr[(size_t)kept[(size_t)k]], true, reinterpret_cast<uint8_t *>(raw.p) + rawo[(size_t)k]);
         });
         if (int rc = ctx->cms_raw.ensure((size_t)rawo[(size_t)n] + 64)) return rc;
         if (int rc = ctx->cms_off.ensure((size_t)(n + 1) * 8)) return rc;
@@ -855,7 +853,8 @@ struct PurRun {
     int64_t w = 0, win_lo = 0, win_hi = 0, ref_lo = 0, ref_hi = 0;
     bool dirty = false;
     int64_t ev_bound = 0;                // no more events than this lie behind the cursor
-    std::vector<const uint8_t *> batch;
+    struct Item { const uint8_t *q; bool staged; };      // a record of the reader, or a carried staged head
+    std::vector<Item> batch;
     int64_t batch_ins = 0;
     PinnedBuf raw, rawo_pin;
     std::vector<int64_t> rawo;
@@ -897,9 +896,18 @@ struct PurRun {
         ref_hi = pur_ref_of_dense(*c, win_hi - 1) + 1;
     }
     int64_t n_windows() const { return (c->P + W - 1) / W; }
-    int add(const uint8_t *q, int64_t ins_ops)
+    // the bytes of a staged head with its qualities (staged_head.hpp)
+    static int64_t staged_bytes(const uint8_t *h)
     {
-        batch.push_back(q);
+        const uint8_t *cg, *sq;
+        int nc;
+        staged_cigar(h + 4, cg, nc, sq);
+        const int64_t l_seq = rdi32(h + 4 + 16);
+        return (int64_t)(sq - h) + (l_seq + 1) / 2 + l_seq;
+    }
+    int add(const uint8_t *q, int64_t ins_ops, bool staged = false)
+    {
+        batch.push_back(Item{q, staged});
         batch_ins += ins_ops;
         return (int64_t)batch.size() >= batch_reads ? flush() : NPORE_OK;
     }
@@ -909,18 +917,17 @@ struct PurRun {
         const int64_t n = (int64_t)batch.size();
         if (n == 0) return NPORE_OK;
         rawo.assign(1, 0);
-        for (const uint8_t *q : batch) {
-            const RecView r = rec_view(q);
-            rawo.push_back(rawo.back() + (((int64_t)(r.aux() - r.p) + 4 + 7) & ~7ll));
-        }
+        for (const Item &it : batch)
+            rawo.push_back(rawo.back() + (((it.staged ? staged_bytes(it.q) : staged_head_bytes(it.q, true)) + 7) & ~7ll));
         if (int rc = raw.ensure((size_t)rawo[(size_t)n] + 64)) return rc;
         if (int rc = rawo_pin.ensure((size_t)(n + 1) * 8)) return rc;
         std::memcpy(rawo_pin.p, rawo.data(), (size_t)(n + 1) * 8);
         const int64_t per = 64;
         parallel_for((n + per - 1) / per, 0, [&](int64_t tix) {
             for (int64_t k = tix * per; k < std::min(n, (tix + 1) * per); k++) {
-                const RecView r = rec_view(batch[(size_t)k]);
-                std::memcpy(raw.p + rawo[(size_t)k], batch[(size_t)k], (size_t)(r.aux() - r.p) + 4);
+                const Item &it = batch[(size_t)k];
+                if (it.staged) std::memcpy(raw.p + rawo[(size_t)k], it.q, (size_t)staged_bytes(it.q));
+                else stage_record_head(it.q, true, reinterpret_cast<uint8_t *>(raw.p) + rawo[(size_t)k]);
             }
         });
         if (int rc = ctx->cms_raw.ensure((size_t)rawo[(size_t)n] + 64)) return rc;
@@ -1086,14 +1093,15 @@ try {
                 const PurContig &c = contigs[(size_t)rid];
                 const int32_t one_layer[2] = {0, (int32_t)c.ranges.size()};
                 RecInfo &ri = info[(size_t)k];
-                ri.gate = cms_gate((uint32_t)r.flag(), r.pos(), r.l_seq(), r.cigar(), r.n_cigar(), exclude_flags, c.ranges.data(), one_layer, 1);
+                const RecCigar cg = rec_cigar(r);
+                ri.gate = cms_gate((uint32_t)r.flag(), r.pos(), r.l_seq(), cg.w, (int)cg.n, exclude_flags, c.ranges.data(), one_layer, 1);
                 if (ri.gate < 0) continue;
-                const int64_t end = r.pos() + cms_span(r.cigar(), r.n_cigar()).rl;
+                const int64_t end = r.pos() + cms_span(cg.w, (int)cg.n).rl;
                 ri.w0 = pur_first_dense(c.ranges.data(), (int)c.ranges.size(), r.pos(), end) / run.W;
                 ri.w1 = pur_last_dense(c.ranges.data(), (int)c.ranges.size(), r.pos(), end) / run.W;
                 if (ri.gate != 0) continue;
-                ri.no_entry = pur_ins_no_entry(r.cigar(), r.n_cigar());
-                ri.ins_ops = pur_ins_ops(r.cigar(), r.n_cigar());
+                ri.no_entry = pur_ins_no_entry(cg.w, (int)cg.n);
+                ri.ins_ops = pur_ins_ops(cg.w, (int)cg.n);
             }
         });
     };
@@ -1132,7 +1140,7 @@ try {
                 }
                 run.set_window(run.w + 1);
                 for (const Carried &cr : carry)
-                    if (int rc = run.add(cr.bytes.data(), cr.ins_ops)) return rc;
+                    if (int rc = run.add(cr.bytes.data(), cr.ins_ops, true)) return rc;
             }
             return NPORE_OK;
         };
@@ -1163,8 +1171,10 @@ try {
                 if (ri.w0 > run.w)
                     if (int rc = advance_to(ri.w0)) return rc;
                 if (ri.w1 > run.w) {
-                    carry.push_back(Carried{std::vector<uint8_t>(rf.ptr[(size_t)k], r.aux()), ri.w1, ri.ins_ops});
-                    if (int rc = run.add(carry.back().bytes.data(), ri.ins_ops)) return rc;
+                    // (carried as the staged head: its real CIGAR is resolved once)
+                    carry.push_back(Carried{std::vector<uint8_t>((size_t)staged_head_bytes(rf.ptr[(size_t)k], true)), ri.w1, ri.ins_ops});
+                    stage_record_head(rf.ptr[(size_t)k], true, carry.back().bytes.data());
+                    if (int rc = run.add(carry.back().bytes.data(), ri.ins_ops, true)) return rc;
                 } else if (int rc = run.add(rf.ptr[(size_t)k], ri.ins_ops)) return rc;
             }
             if (int rc = run.flush()) return rc;     // (the records' bytes go with the reader's next batch)
@@ -1560,13 +1570,13 @@ int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, 
         const int32_t rid = r.ref_id();
         const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
         if (fi < 0 || fi >= n_fasta) return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
-        s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + (int64_t)((as_bam ? r.aux() : r.qual()) - r.p) + 4;
+        s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_head_bytes(r, rec_cigar(r), as_bam);
         const int64_t cap = (s.ro[(size_t)k + 1] - s.ro[(size_t)k]) + (s.so[(size_t)k + 1] - s.so[(size_t)k]);
         s.oo[(size_t)k + 1] = s.oo[(size_t)k] + (as_bam ? 4 : 2) * cap + 16;
         if (as_bam) {
             const int64_t sl = s.so[(size_t)k + 1] - s.so[(size_t)k];
             reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = rec_hp(r);
-            s.rec_cap += 36 + r.l_read_name() + 4 * cap + 16 + (sl + 1) / 2 + sl + 7;
+            s.rec_cap += 36 + r.l_read_name() + 4 * cap + 16 + (sl + 1) / 2 + sl + 7 + 16;      // (+ 16: placeholder and CG tag head of a long final CIGAR)
         }
     }
     if (int rc = s.raw.ensure((size_t)s.rawo[(size_t)n] + 64)) return rc;
@@ -1577,7 +1587,7 @@ int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, 
         for (int64_t k = t * per; k < std::min(n, (t + 1) * per); k++) {
             char *dst = s.raw.p + s.rawo[(size_t)k];
             const size_t len = (size_t)(s.rawo[(size_t)k + 1] - s.rawo[(size_t)k]);
-            std::memcpy(dst, s.rf.ptr[(size_t)k], len);
+            stage_record_head(s.rf.ptr[(size_t)k], as_bam, reinterpret_cast<uint8_t *>(dst));
             cache_writeback(dst, len);         // page-locked staging about to cross PCIe: out of this core's cache first (hostio.hpp)
         }
     });
@@ -1647,7 +1657,6 @@ int slot_fetch_records(int64_t n, const int32_t *status, npore_batch_slot &s, bo
     int64_t sum = 0;
     for (int64_t k = 0; k < n; k++) {
         if (len[k] < 0) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
-        if (s.olen[(size_t)k] > 4 * 0xFFFF) return fail(NPORE_E_UNSUPPORTED, "a final CIGAR has more than 65535 operations (BAM output)");
         if ((len[k] == 0) != ((status[k] & NPORE_ST_BAD_INPUT) != 0)) return fail(NPORE_E_HIP, "internal: BAM records and status bits disagree");
         if (len[k] == 0) continue;
         const RecView r = rec_of(s.rf, k);

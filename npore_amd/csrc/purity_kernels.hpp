@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "purity_rec.hpp"
+#include "staged_head.hpp"
 
 namespace npore {
 
@@ -86,12 +87,10 @@ __global__ __launch_bounds__(256) void purity_records_kernel(PurParams p)
 
     const uint8_t *f = p.raw + p.raw_off[rec] + 4;                 // the fixed fields (hostio.hpp RecView)
     const int64_t pos = (int32_t)cms_ld32(f + 4);
-    const int l_rn = f[8], nc = (int)(cms_ld32(f + 12) & 0xFFFFu);
     const int64_t l_seq = (int32_t)cms_ld32(f + 16);
     PurView v;
-    v.cg = f + 32 + l_rn;
-    v.nc = nc;
-    v.sq = v.cg + 4 * (size_t)nc;
+    staged_cigar(f, v.cg, v.nc, v.sq);
+    const int nc = v.nc;
     v.ql = v.sq + (size_t)((l_seq + 1) / 2);
     v.l_seq = l_seq;
     v.ranges = p.ranges;

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "staged_head.hpp"
+
 namespace npore {
 
 struct CtgEntry {
@@ -21,7 +23,7 @@ struct CtgEntry {
 };
 
 struct UnpackParams {
-    const uint8_t *raw;          // record heads one after the other (block_size word first, as in the BAM stream)
+    const uint8_t *raw;          // staged record heads one after the other (hostio.hpp stage_record_head)
     const int64_t *raw_off;      // [n + 1]
     const CtgEntry *ctg;         // by BAM reference id
     int n_ctg;
@@ -42,8 +44,9 @@ __global__ __launch_bounds__(256) void unpack_records_kernel(UnpackParams p)
     const int t = threadIdx.x;
     const uint8_t *f = p.raw + p.raw_off[k] + 4;                 // the fixed fields (hostio.hpp RecView)
     const int32_t rid = (int32_t)ld32(f), pos = (int32_t)ld32(f + 4);
-    const int l_rn = f[8], nc = (int)ld16(f + 12);
-    const uint8_t *cg = f + 32 + l_rn, *sq = cg + 4 * (size_t)nc;
+    const uint8_t *cg, *sq;
+    int nc;
+    staged_cigar(f, cg, nc, sq);
 
     // ---- reference bases: contig[pos, pos + rl), zeros (N) where the slice leaves the contig
     {

@@ -339,6 +339,11 @@ int npore_bam_format_bam(npore_bam *bam, const int64_t *idx, int64_t n, const ch
  * default file pipeline codes the whole members inside a batch on the device (csrc/bam_deflate_kernels.hpp), the host
  * twin the rest.  NPORE_OUT_BAM only. */
 #define NPORE_OUT_DEFLATE 4
+/* flags, with NPORE_OUT_DEFLATE only (flags = 12): the members' blocks hold literals AND length / distance pairs -- a 15-bit
+ * hash of four bytes, the nearest earlier position of equal hash, matches of 4 ... 258 bytes at most 32 768 back, a greedy
+ * parse -- wherever that block is smaller than the literals-only one; otherwise the member is the one NPORE_OUT_DEFLATE
+ * alone writes.  The rule is csrc/deflate_code.hpp's; the device finds the matches too. */
+#define NPORE_OUT_MATCH 8
 int npore_bam_set_output(npore_bam *bam, int format, const char *bai_path, int flags);
 /* Of the last BAM-mode run on the handle: out4[0] records written, [1] bytes of the record stream, [2] 1 = the index was
  * written, 0 = none was asked for, -1 = the records were not in coordinate order (no index), [3] size of the file. */
@@ -474,6 +479,8 @@ int64_t npore_debug_crc32(const uint8_t *p, int64_t n, uint32_t crc);
 /* The host twin of NPORE_OUT_DEFLATE: the n <= 65 280 bytes at `in` as one whole BGZF member at `out` (cap >= n + 31
  * always suffices).  Returns the member's size or a negative NPORE_E_* code.  Host code, no GPU. */
 int64_t npore_debug_deflate_member(const uint8_t *in, int64_t n, uint8_t *out, int64_t cap);
+/* ... with the mode named: 1, literals only (the entry above), or 2, with matches (NPORE_OUT_MATCH). */
+int64_t npore_debug_deflate_member_mode(const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int mode);
 /* The device side of NPORE_OUT_DEFLATE on a caller's buffer: the n bytes at `bytes` taken as a batch's records whose first
  * byte lies at offset `phase` of the record stream (the first cut is (65 280 - phase % 65 280) % 65 280 bytes in), through
  * the planning, placing and emitting kernels.  members / members_cap: the whole members inside the buffer, one after the
@@ -483,6 +490,10 @@ int64_t npore_debug_deflate_member(const uint8_t *in, int64_t n, uint8_t *out, i
 int npore_debug_deflate_device(npore_ctx *ctx, const uint8_t *bytes, int64_t n, int64_t phase, uint8_t *members,
                                int64_t members_cap, uint32_t *sizes, int64_t sizes_cap, uint8_t *head, uint8_t *tail,
                                int64_t *info);
+/* ... with the mode named: 1, literals only (the entry above), or 2, with matches (NPORE_OUT_MATCH). */
+int npore_debug_deflate_device_mode(npore_ctx *ctx, const uint8_t *bytes, int64_t n, int64_t phase, uint8_t *members,
+                                    int64_t members_cap, uint32_t *sizes, int64_t sizes_cap, uint8_t *head, uint8_t *tail,
+                                    int64_t *info, int mode);
 
 /* Debug self-test: out128[l] = value lane l receives from lane l-1 (l>0),
  * out128[64+l] = value from lane l+1 (l<63); checks the DPP wave-shift

@@ -97,6 +97,9 @@ SIGNATURES = {
     "npore_debug_deflate_member": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "npore_debug_deflate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "npore_debug_deflate_member_mode": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int]),
+    "npore_debug_deflate_device_mode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "npore_debug_dpp": (C.c_int, [C.c_void_p]),
     "npore_debug_divcheck": (C.c_int, [C.c_void_p]),
     "npore_debug_fetch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]),

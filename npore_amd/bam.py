@@ -408,15 +408,11 @@ def canonical_codes(lens):
     return out
 
 
-def deflate_block(payload):
-    """(block bytes or None when it would not be smaller than the stored block, header bits, data bits) of the payload as
-    one final dynamic-Huffman block of literals."""
-    freq = np.bincount(np.frombuffer(payload, np.uint8), minlength=257).tolist()
-    freq[256] = 1
-    lens = huffman_lengths(freq, 15)
-    codes = canonical_codes(lens)
+def _code_length_header(ll_lens, d_lens):
+    """The block header (BFINAL ... the code-length sequence) as (bits as an integer, LSB first; how many): ll_lens the HLIT
+    literal / length lengths, d_lens the HDIST distance lengths, run-coded as ONE sequence."""
     seq, cl_freq = [], [0] * 19
-    allv = lens + [0]                            # ... and the one distance code, of length 0
+    allv = list(ll_lens) + list(d_lens)
     i = 0
     while i < len(allv):
         v, r = allv[i], 1
@@ -450,38 +446,144 @@ def deflate_block(payload):
         nonlocal acc, nbits
         acc |= v << nbits
         nbits += n
-    put(1, 1), put(2, 2), put(0, 5), put(0, 5), put(hclen - 4, 4)
+    put(1, 1), put(2, 2), put(len(ll_lens) - 257, 5), put(len(d_lens) - 1, 5), put(hclen - 4, 4)
     for k in range(hclen):
         put(cl_lens[_CL_ORDER[k]], 3)
     for s, extra in seq:
         put(cl_codes[s][1], cl_codes[s][0])
         if s >= 16:
             put(extra, _CL_EXTRA[s])
-    header_bits = nbits
+    return acc, nbits
+
+
+def _pack_fields(acc, header_bits, values, widths, n_bytes):
+    """The block's bytes: the header's bits, then field k's widths[k] low bits of values[k], LSB first, one after the other."""
+    values, widths = np.asarray(values, np.int64), np.asarray(widths, np.int64)
+    at = header_bits + np.concatenate([[0], np.cumsum(widths)[:-1]])
+    bits = np.zeros(n_bytes * 8, np.uint8)
+    bits[:header_bits] = np.array([(acc >> k) & 1 for k in range(header_bits)], np.uint8)
+    for b in range(int(widths.max()) if len(widths) else 0):
+        use = widths > b
+        bits[at[use] + b] = (values[use] >> b) & 1
+    return np.packbits(bits, bitorder="little").tobytes()
+
+
+def deflate_block(payload):
+    """(block bytes or None when it would not be smaller than the stored block, header bits, data bits) of the payload as
+    one final dynamic-Huffman block of literals."""
+    freq = np.bincount(np.frombuffer(payload, np.uint8), minlength=257).tolist()
+    freq[256] = 1
+    lens = huffman_lengths(freq, 15)
+    codes = canonical_codes(lens)
+    acc, header_bits = _code_length_header(lens, [0])       # ... and the one distance code, of length 0
     data_bits = sum(f * l for f, l in zip(freq, lens))
     n_bytes = (header_bits + data_bits + 7) // 8
     if n_bytes >= len(payload) + 5:
         return None, header_bits, data_bits
-    # the data bits with numpy: every code at its bit offset
     sym = np.concatenate([np.frombuffer(payload, np.uint8).astype(np.int64), [256]])
     ln = np.array([c[0] for c in codes], np.int64)[sym]
     cd = np.array([c[1] for c in codes], np.int64)[sym]
-    at = header_bits + np.concatenate([[0], np.cumsum(ln)[:-1]])
-    bits = np.zeros(n_bytes * 8, np.uint8)
-    hb = np.array([(acc >> k) & 1 for k in range(header_bits)], np.uint8)
-    bits[:header_bits] = hb
-    for b in range(15):
-        use = ln > b
-        bits[at[use] + b] = (cd[use] >> b) & 1
-    return np.packbits(bits, bitorder="little").tobytes(), header_bits, data_bits
+    return _pack_fields(acc, header_bits, cd, ln, n_bytes), header_bits, data_bits
 
 
-def deflate_member(payload):
-    """One BGZF member (at most BGZF_STORED_PAYLOAD bytes of payload) in --bam_compress huffman: one dynamic-Huffman block
-    of literals, or the stored member where that is not smaller (and for an empty payload)."""
+# ---- --bam_compress match: the rule's steps 1 to 6 (csrc/deflate_code.hpp, MATCHES), with the tables of RFC 1951 3.2.5 ---------
+_LEN_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
+_LEN_EXTRA = (0,) * 8 + (1,) * 4 + (2,) * 4 + (3,) * 4 + (4,) * 4 + (5,) * 4 + (0,)
+_DIST_BASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145,
+              8193, 12289, 16385, 24577)
+_DIST_EXTRA = (0, 0, 0, 0) + tuple(e for e in range(1, 14) for _ in range(2))
+MATCH_HASH_BITS, MATCH_MIN, MATCH_MAX, MATCH_MAX_DIST = 15, 4, 258, 32768
+
+
+def _len_symbol(length):
+    k = max(j for j in range(29) if _LEN_BASE[j] <= length)
+    return 257 + k, _LEN_EXTRA[k], length - _LEN_BASE[k]
+
+
+def _dist_symbol(dist):
+    k = max(j for j in range(30) if _DIST_BASE[j] <= dist)
+    return k, _DIST_EXTRA[k], dist - _DIST_BASE[k]
+
+
+def match_hashes(payload):
+    """H(i) for i <= n - 4: the four bytes at i little-endian, times 2654435761 modulo 2^32, the top 15 bits."""
+    p = np.frombuffer(payload, np.uint8).astype(np.uint64)
+    if len(p) < 4:
+        return np.zeros(0, np.int64)
+    word = p[:-3] | p[1:-2] << np.uint64(8) | p[2:-1] << np.uint64(16) | p[3:] << np.uint64(24)
+    return (((word * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) >> np.uint64(32 - MATCH_HASH_BITS)).astype(np.int64)
+
+
+def match_tokens(payload):
+    """The greedy parse: a list of literals (an int) and matches ((length, distance)).  The candidate of a position is the
+    nearest earlier position of equal HASH; a match has >= 4 equal bytes, at most 258 and not past the end, at most 32 768 back."""
     payload = bytes(payload)
     n = len(payload)
-    block = deflate_block(payload)[0] if n else None
+    hashes = match_hashes(payload).tolist()
+    cand, last = [], {}
+    for i, h in enumerate(hashes):
+        cand.append(last.get(h, -1))
+        last[h] = i
+    tokens, i = [], 0
+    while i < n:
+        c = cand[i] if i < len(cand) else -1
+        length = 0
+        if c >= 0 and i - c <= MATCH_MAX_DIST:
+            cap = min(MATCH_MAX, n - i)
+            a, b = payload[c:c + cap], payload[i:i + cap]
+            length = cap if a == b else next(k for k in range(cap) if a[k] != b[k])
+        if length >= MATCH_MIN:
+            tokens.append((length, i - c))
+            i += length
+        else:
+            tokens.append(payload[i])
+            i += 1
+    return tokens
+
+
+def deflate_match_block(payload, tokens=None):
+    """(block bytes, header bits, data bits) of the payload as one final dynamic-Huffman block of its tokens."""
+    tokens = match_tokens(payload) if tokens is None else tokens
+    ll_freq, d_freq = [0] * 286, [0] * 30
+    for t in tokens:
+        if isinstance(t, tuple):
+            ll_freq[_len_symbol(t[0])[0]] += 1
+            d_freq[_dist_symbol(t[1])[0]] += 1
+        else:
+            ll_freq[t] += 1
+    ll_freq[256] = 1
+    ll_lens, d_lens = huffman_lengths(ll_freq, 15), huffman_lengths(d_freq, 15)
+    hlit = max([257] + [s + 1 for s in range(286) if ll_freq[s]])
+    hdist = max([1] + [s + 1 for s in range(30) if d_freq[s]])
+    ll_codes, d_codes = canonical_codes(ll_lens), canonical_codes(d_lens)
+    acc, header_bits = _code_length_header(ll_lens[:hlit], d_lens[:hdist])
+    values, widths = [], []
+    for t in tokens + [256]:
+        if isinstance(t, tuple):
+            ls, le, lv = _len_symbol(t[0])
+            ds, de, dv = _dist_symbol(t[1])
+            values += [ll_codes[ls][1], lv, d_codes[ds][1], dv]
+            widths += [ll_codes[ls][0], le, d_codes[ds][0], de]
+        else:
+            values.append(ll_codes[t][1])
+            widths.append(ll_codes[t][0])
+    data_bits = sum(widths)
+    n_bytes = (header_bits + data_bits + 7) // 8
+    return _pack_fields(acc, header_bits, values, widths, n_bytes), header_bits, data_bits
+
+
+def deflate_member(payload, matches=False):
+    """One BGZF member (at most BGZF_STORED_PAYLOAD bytes of payload) in --bam_compress huffman: one dynamic-Huffman block
+    of literals, or the stored member where that is not smaller (and for an empty payload).  matches (--bam_compress match):
+    the block of literals and length / distance pairs where it is smaller than both, otherwise that same member."""
+    payload = bytes(payload)
+    n = len(payload)
+    block, hb, db = deflate_block(payload) if n else (None, 0, 0)
+    if matches and n:
+        h = (hb + db + 7) // 8
+        mblock = deflate_match_block(payload)[0]
+        if len(mblock) < h and len(mblock) < n + 5:
+            block = mblock
     if block is None:
         return _stored_member(payload)
     return (struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 0xFF, 6, 66, 67, 2, len(block) + 25) + block +
@@ -498,7 +600,9 @@ def bgzf_members(data, compress="none"):
     """`data` cut every BGZF_STORED_PAYLOAD bytes, each piece a member of the mode."""
     if compress == "none":
         return bgzf_stored(data)
-    return b"".join(deflate_member(data[p:p + BGZF_STORED_PAYLOAD]) for p in range(0, len(data), BGZF_STORED_PAYLOAD))
+    if compress not in ("huffman", "match"):
+        raise ValueError("compress must be 'none', 'huffman' or 'match'")
+    return b"".join(deflate_member(data[p:p + BGZF_STORED_PAYLOAD], compress == "match") for p in range(0, len(data), BGZF_STORED_PAYLOAD))
 
 
 def bam_header_bytes(text, references, lengths):
@@ -950,14 +1054,15 @@ class NativeBam:
         what lies in the file (the header's members: create_bam_header) and `bai` written when the records went out in
         coordinate order.  eof: the run ends the file (the EOF member); False: it writes one rank's PART -- no EOF member,
         and `bai` is a sidecar whose offsets count from PART_BASE (dist.gather_bam_parts shifts and merges them).
-        compress: "none", stored members, or "huffman", every member one dynamic-Huffman block of literals
+        compress: "none", stored members, "huffman", every member one dynamic-Huffman block of literals, or "match", of
+        literals and length / distance pairs where that is smaller
         (NPORE_OUT_DEFLATE; "bam" only)."""
-        if compress not in ("none", "huffman"):
-            raise ValueError("compress must be 'none' or 'huffman'")
+        if compress not in ("none", "huffman", "match"):
+            raise ValueError("compress must be 'none', 'huffman' or 'match'")
         if compress != "none" and out_format != "bam":
             raise ValueError("compress needs out_format 'bam'")
         flags = 0 if out_format != "bam" else 1 if eof else 2       # NPORE_OUT_EOF / NPORE_OUT_PART
-        flags |= 4 if compress == "huffman" else 0                  # NPORE_OUT_DEFLATE
+        flags |= {"none": 0, "huffman": 4, "match": 12}[compress]  # NPORE_OUT_DEFLATE, NPORE_OUT_MATCH
         self._check(self._lib.npore_bam_set_output(self.handle, {"sam": 0, "bam": 1}[out_format], os.fsencode(bai) if bai else None, flags))
 
     def output_info(self):

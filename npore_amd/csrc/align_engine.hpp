@@ -531,9 +531,10 @@ int fill_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs &
 inline void launch_deflate(const DeflateParams &dp, hipStream_t s)
 {
     if (dp.max_members <= 0) return;
-    hipLaunchKernelGGL(plan_deflate_kernel, dim3((unsigned)dp.max_members), dim3(64), 0, s, dp);
+    const bool match = dp.mode == DEFLATE_MODE_MATCH;           // (NPORE_OUT_MATCH: the planning and the emitting kernel with matches)
+    hipLaunchKernelGGL(match ? plan_match_kernel : plan_deflate_kernel, dim3((unsigned)dp.max_members), dim3(64), 0, s, dp);
     hipLaunchKernelGGL(place_deflate_kernel, dim3(1), dim3(256), 0, s, dp);
-    hipLaunchKernelGGL(emit_deflate_kernel, dim3((unsigned)dp.max_members + 2), dim3(64), 0, s, dp);      // (+ 2: the fragments)
+    hipLaunchKernelGGL(match ? emit_match_kernel : emit_deflate_kernel, dim3((unsigned)dp.max_members + 2), dim3(64), 0, s, dp);      // (+ 2: the fragments)
 }
 
 // Traceback + output, behind this group's fill and beside the next group's; the tail is chosen by the plan's OutMode

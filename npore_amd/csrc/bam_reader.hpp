@@ -869,7 +869,7 @@ private:
 // Appends a record stream to a file as BGZF members (the FILE rules above): add() takes a batch's record bytes as
 // they lie -- stored members' payload goes out from the caller's buffer (writev), only the tail that does not fill a
 // member is kept for the next batch -- and does the index bookkeeping; finish() writes the last member, the EOF member if
-// asked for, and the index.  deflate (NPORE_OUT_DEFLATE): every member is coded by deflate_code.hpp's host twin, on
+// asked for, and the index.  deflate (NPORE_OUT_DEFLATE, with NPORE_OUT_MATCH: the match mode): every member is coded by deflate_code.hpp's host twin, on
 // `threads` threads -- or comes ready-made from the device (add_coded), which codes the whole members that lie inside a
 // batch; the one member that straddles two batches is joined and coded here.  One thread at a time (the file pipeline's
 // ordered write step).
@@ -882,7 +882,7 @@ public:
     // the file is appended to: what lies there already (the header's members) stays
     // part: a rank's part of a file -- the index counts its offsets from a nominal first member at NPORE_PART_BASE, so
     // that none is 0, which a .bai takes for "no record in this window"; whoever appends the part shifts them
-    int open(const char *path, size_t n_ref, const char *bai_path, bool eof_member, bool part = false, bool deflate = false, int threads = 1)
+    int open(const char *path, size_t n_ref, const char *bai_path, bool eof_member, bool part = false, int deflate = 0, int threads = 1)
     {
         fd_ = ::open(path, O_WRONLY | O_CREAT | O_APPEND, 0666);
         if (fd_ < 0) return fail(NPORE_E_INVALID, std::string("cannot open '") + path + "' for appending");
@@ -897,7 +897,8 @@ public:
         carry_.reserve(BGZF_STORED_PAYLOAD);
         return NPORE_OK;
     }
-    bool deflate() const { return deflate_; }
+    bool deflate() const { return deflate_ != 0; }
+    int deflate_mode() const { return deflate_; }     // 0, DEFLATE_MODE_HUFFMAN or DEFLATE_MODE_MATCH
     uint64_t stream_bytes() const { return stream_; }
     int add(const uint8_t *bytes, int64_t len, const BamRecMeta *meta, int64_t n_rec)
     {
@@ -1007,7 +1008,7 @@ private:
                     std::memcpy(joined + j.na, j.b, j.nb);
                     in = joined;
                 }
-                coded_len_[(size_t)k] = deflate_member_host(in, j.na + j.nb, crc32_fast(0, in, j.na + j.nb), out);
+                coded_len_[(size_t)k] = deflate_member_host(in, j.na + j.nb, crc32_fast(0, in, j.na + j.nb), out, deflate_);
             });
             for (size_t k = 0; k < jobs_.size(); k++) {
                 const Job &j = jobs_[k];
@@ -1064,7 +1065,8 @@ private:
     int fd_ = -1;
     uint64_t base_ = 0, stream_ = 0, file_bytes_ = 0;
     int64_t n_rec_ = 0;
-    bool eof_ = false, deflate_ = false;
+    bool eof_ = false;
+    int deflate_ = 0;                        // 0: stored members; DEFLATE_MODE_HUFFMAN / DEFLATE_MODE_MATCH
     int threads_ = 1;
     std::string bai_path_;
     std::vector<uint8_t> carry_;             // the tail of the stream that does not fill a member yet (< 65 280 bytes)

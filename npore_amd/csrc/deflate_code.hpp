@@ -27,8 +27,30 @@
 //   symbol of RFC order that is used, at least 4.
 // From the histogram alone: header bits = 17 + 3 * HCLEN + sum over the sequence's symbols of (code length + extra
 // bits); data bits = sum f * length (end-of-block has f = 1); the block takes (header + data + 7) / 8 bytes.
+//
+// MATCHES (--bam_compress match; DEFLATE_MODE_MATCH).  The member's block holds literals AND length / distance pairs.  For a
+// payload p[0 .. n), n <= 65 280:
+//   1. HASH.  H(i), for i <= n - 4: the four bytes at i read little-endian as a 32-bit word, times 2654435761 modulo 2^32,
+//      the top 15 bits.
+//   2. CANDIDATE.  c(i): the greatest j < i with H(j) = H(i), or none -- the nearest earlier position of equal HASH, whatever
+//      its bytes: collisions are part of the rule, so a table that keeps the most recent position per bucket is exact.
+//   3. MATCH.  L(i): the number of equal bytes p[c(i) + k] = p[i + k], at most min(258, n - i); source and target may
+//      overlap.  A match iff L(i) >= 4 and i - c(i) <= 32 768.
+//   4. GREEDY PARSE from 0: at a position with a match the token (length L, distance i - c), on at i + L; otherwise a
+//      literal, on at i + 1.  No lazy evaluation.  End-of-block comes last.
+//   5. ALPHABETS.  Literal / length symbols 0 ... 285 and distance symbols 0 ... 29 with the bases and extra bits of RFC 1951
+//      3.2.5.  HLIT = max(257, highest used literal / length symbol + 1); HDIST = max(1, highest used distance symbol + 1).
+//      Code lengths of both by deflate_lengths, limit 15 (a single used distance symbol: the one 1-bit code); canonical
+//      codes; the code-length sequence and HCLEN by the run rule above on the HLIT + HDIST lengths as ONE sequence.  The
+//      literals-only block is the case HLIT = 257, HDIST = 1 with the distance length 0.
+//   6. CHOICE.  m: bytes of this block; h: bytes of the literals-only block.  The match block is written iff m < h and
+//      m < n + 5; otherwise exactly the member of the literals-only rule (its block, or the stored block if h >= n + 5).
+//      So size(match) <= size(huffman) <= n + 31 for every payload, and a payload without a match gives the literals-only
+//      member byte for byte.
 #pragma once
 #include <stdint.h>
+
+#include <vector>
 
 #if defined(__HIPCC__)
 #define NPORE_DFL_HD __host__ __device__ __forceinline__
@@ -39,7 +61,14 @@
 namespace npore {
 
 constexpr int DEFLATE_MEMBER_PAYLOAD = 0xFF00;     // (BGZF_STORED_PAYLOAD)
-constexpr int DEFLATE_NSYM = 257, DEFLATE_NSEQ = 258, DEFLATE_HDR_CAP = 240;
+constexpr int DEFLATE_NSYM = 257, DEFLATE_NSEQ = 258;       // the literals-only block: its alphabet, its code-length sequence
+constexpr int DEFLATE_NLL = 286, DEFLATE_NDIST = 30;        // the alphabets of a block with matches
+// the block header's bytes at the most: 17 + 3 * 19 bits, then at most 7 bits for each of the 286 + 30 lengths (a symbol with
+// extra bits stands for three lengths at the least)
+constexpr int DEFLATE_HDR_CAP = 296;
+constexpr int DEFLATE_MODE_HUFFMAN = 1, DEFLATE_MODE_MATCH = 2;
+constexpr int DEFLATE_HASH_BITS = 15, DEFLATE_MIN_MATCH = 4, DEFLATE_MAX_MATCH = 258, DEFLATE_MAX_DIST = 32768;
+constexpr uint32_t DEFLATE_NO_POS = 0xFFFFu;                // (a position is < 65 280)
 
 // ---- CRC-32 as polynomial arithmetic (reflected, as zlib's crc32_combine): what the device needs to join slices
 constexpr uint32_t CRC_POLY = 0xEDB88320u;
@@ -69,18 +98,40 @@ NPORE_DFL_HD uint32_t crc_byte(uint32_t c, uint32_t byte)
     return c;
 }
 
-// ---- the plan of one member: everything but the payload's bits.  3.6 KB: a workgroup's LDS on the device
+// ---- the plan of one member: everything but the payload's bits.  4.6 KB: a workgroup's LDS on the device
 struct DeflateWork {
-    uint32_t freq[DEFLATE_NSYM];       // in: the histogram, freq[256] = 1; out: code[s] = length << 16 | code, bit-reversed
-    uint32_t a[DEFLATE_NSYM];          // scratch: weights / depths by rank
-    uint16_t sym[DEFLATE_NSYM + 1];    // scratch: symbol by rank
-    uint8_t lens[DEFLATE_NSEQ + 2];    // lengths of the 257 symbols and the distance code
-    uint16_t seq[DEFLATE_NSEQ + 2];    // the code-length sequence: symbol | extra << 8
+    uint32_t freq[DEFLATE_NLL];        // in: the histogram, freq[256] = 1; out: code[s] = length << 16 | code, bit-reversed
+    uint32_t dfreq[DEFLATE_NDIST];     // the same of the distance symbols (matches only)
+    uint32_t a[DEFLATE_NLL];           // scratch: weights / depths by rank
+    uint16_t sym[DEFLATE_NLL + 2];     // scratch: symbol by rank
+    uint8_t lens[DEFLATE_NLL + DEFLATE_NDIST + 4];      // lengths of the HLIT symbols, behind them of the HDIST distance codes
+    uint8_t dlens[DEFLATE_NDIST + 2];
+    uint16_t seq[DEFLATE_NLL + DEFLATE_NDIST + 2];      // the code-length sequence: symbol | extra << 8
     uint32_t clfreq[19], clcode[19];
     uint8_t cllens[20];
     uint32_t count[17], next[17];
-    uint32_t n_seq, hclen, hdr_bits, data_bits;
+    uint32_t n_seq, hclen, hdr_bits, data_bits, hlit, hdist;
 };
+
+// ---- the rule's steps 1 to 3 and the symbols of step 5
+NPORE_DFL_HD uint32_t deflate_hash(uint32_t word) { return (word * 2654435761u) >> (32 - DEFLATE_HASH_BITS); }
+// length 3 ... 258 -> symbol | extra bits << 16 | their value << 24
+NPORE_DFL_HD uint32_t deflate_len_symbol(uint32_t len)
+{
+    const uint32_t l = len - 3;
+    if (l < 8) return 257 + l;
+    if (len == 258) return 285;
+    const uint32_t e = (uint32_t)(31 - __builtin_clz(l)) - 2;
+    return (261 + 4 * e + ((l >> e) & 3u)) | e << 16 | (l & ((1u << e) - 1)) << 24;
+}
+// distance 1 ... 32 768 -> symbol | extra bits << 8 | their value << 16
+NPORE_DFL_HD uint32_t deflate_dist_symbol(uint32_t dist)
+{
+    const uint32_t d = dist - 1;
+    if (d < 4) return d;
+    const uint32_t lg = (uint32_t)(31 - __builtin_clz(d)), e = lg - 1;
+    return (2 * lg + ((d >> e) & 1u)) | e << 8 | (d & ((1u << e) - 1)) << 16;
+}
 
 // step 1 for the symbols of freq[0 .. n): a[rank] = weight, sym[rank] = symbol; returns how many are used
 NPORE_DFL_HD int deflate_sort(const uint32_t *freq, int n, uint32_t *a, uint16_t *sym)
@@ -160,24 +211,48 @@ NPORE_DFL_HD int deflate_cl_order(int k)
 }
 NPORE_DFL_HD uint32_t deflate_cl_extra_bits(uint32_t s) { return s == 16 ? 2u : s == 17 ? 3u : s == 18 ? 7u : 0u; }
 
-// Everything behind step 1 of the literal alphabet: w.a / w.sym hold the m used symbols in order, w.freq the histogram.
-// Leaves the codes in w.freq, the sequence, its codes, HCLEN and the two bit counts.
-NPORE_DFL_HD void deflate_plan_sorted(DeflateWork &w, int m)
+// Everything behind step 1 of the literal (matches: literal / length) alphabet: w.a / w.sym hold the m used symbols in
+// order, w.freq the histogram (matches: w.dfreq that of the distance symbols).  Leaves the codes in w.freq (and w.dfreq), the
+// sequence, its codes, HLIT, HDIST, HCLEN and the two bit counts.
+NPORE_DFL_HD void deflate_plan_sorted(DeflateWork &w, int m, bool matches = false)
 {
-    for (int s = 0; s < DEFLATE_NSEQ + 2; s++) w.lens[s] = 0;
+    const int nll = matches ? DEFLATE_NLL : DEFLATE_NSYM;
+    for (int s = 0; s < DEFLATE_NLL + DEFLATE_NDIST + 4; s++) w.lens[s] = 0;
     deflate_lengths_sorted(w.a, w.sym, m, 15, w.count, w.lens);
     uint32_t bits = 0;
-    for (int s = 0; s < DEFLATE_NSYM; s++) bits += w.freq[s] * w.lens[s];
+    int hlit = DEFLATE_NSYM, hdist = 1;
+    for (int s = 0; s < nll; s++) {
+        bits += w.freq[s] * w.lens[s];
+        if (s >= DEFLATE_NSYM && w.freq[s]) {           // (a length symbol: its extra bits)
+            if (s >= 265 && s < 285) bits += w.freq[s] * (uint32_t)((s - 261) / 4);
+            hlit = s + 1;
+        }
+    }
+    deflate_codes(w.lens, nll, w.count, w.next, w.freq);
+    if (matches) {
+        for (int s = 0; s < DEFLATE_NDIST + 2; s++) w.dlens[s] = 0;
+        const int md = deflate_sort(w.dfreq, DEFLATE_NDIST, w.a, w.sym);
+        deflate_lengths_sorted(w.a, w.sym, md, 15, w.count, w.dlens);
+        for (int s = 0; s < DEFLATE_NDIST; s++) {
+            if (!w.dfreq[s]) continue;
+            bits += w.dfreq[s] * (w.dlens[s] + (s < 4 ? 0u : (uint32_t)(s / 2 - 1)));
+            hdist = s + 1;
+        }
+        deflate_codes(w.dlens, DEFLATE_NDIST, w.count, w.next, w.dfreq);
+        for (int s = 0; s < hdist; s++) w.lens[hlit + s] = w.dlens[s];
+    }
     w.data_bits = bits;
-    deflate_codes(w.lens, DEFLATE_NSYM, w.count, w.next, w.freq);
+    w.hlit = (uint32_t)hlit;
+    w.hdist = (uint32_t)hdist;
+    const int n_lens = hlit + hdist;
     // the code-length sequence
     for (int s = 0; s < 19; s++) w.clfreq[s] = 0;
     uint32_t n_seq = 0;
     auto put = [&](uint32_t s, uint32_t extra) { w.seq[n_seq++] = (uint16_t)(s | extra << 8); w.clfreq[s]++; };
-    for (int i = 0; i < DEFLATE_NSEQ;) {
+    for (int i = 0; i < n_lens;) {
         const uint32_t v = w.lens[i];
         int r = 1;
-        while (i + r < DEFLATE_NSEQ && w.lens[i + r] == v) r++;
+        while (i + r < n_lens && w.lens[i + r] == v) r++;
         i += r;
         if (v == 0) {
             while (r >= 11) { const int t = r < 138 ? r : 138; put(18, (uint32_t)(t - 11)); r -= t; }
@@ -227,8 +302,8 @@ NPORE_DFL_HD void deflate_header(const DeflateWork &w, uint8_t *hdr)
     DeflateBits b(hdr);
     b.put(1, 1);                       // BFINAL
     b.put(2, 2);                       // BTYPE: dynamic
-    b.put(0, 5);                       // HLIT: 257
-    b.put(0, 5);                       // HDIST: 1
+    b.put(w.hlit - 257, 5);            // HLIT (literals only: 257)
+    b.put(w.hdist - 1, 5);             // HDIST (literals only: 1)
     b.put(w.hclen - 4, 4);
     for (uint32_t k = 0; k < w.hclen; k++) b.put(w.cllens[deflate_cl_order((int)k)], 3);
     for (uint32_t k = 0; k < w.n_seq; k++) {
@@ -251,9 +326,34 @@ NPORE_DFL_HD void bgzf_member_header(uint8_t *h, uint32_t member_bytes)
     h[17] = (uint8_t)((member_bytes - 1) >> 8);
 }
 
+// Steps 1 to 4 of the match rule on the host: the tokens of in[0 .. n) -- length << 16 | distance, or the literal -- into
+// tok (room for n); head: 2^15 entries of scratch.  Returns how many there are.
+inline size_t deflate_tokens_host(const uint8_t *in, size_t n, uint32_t *tok, uint16_t *head)
+{
+    for (size_t h = 0; h < ((size_t)1 << DEFLATE_HASH_BITS); h++) head[h] = (uint16_t)DEFLATE_NO_POS;
+    size_t n_tok = 0, at = 0;                                   // at: where the parse stands
+    for (size_t i = 0; i < n; i++) {
+        uint32_t len = 0, dist = 0;
+        if (i + 4 <= n) {                                       // every position enters the table, parsed or skipped
+            const uint32_t word = (uint32_t)in[i] | (uint32_t)in[i + 1] << 8 | (uint32_t)in[i + 2] << 16 | (uint32_t)in[i + 3] << 24;
+            const uint32_t h = deflate_hash(word), c = head[h];
+            head[h] = (uint16_t)i;
+            if (i == at && c != DEFLATE_NO_POS && i - c <= (size_t)DEFLATE_MAX_DIST) {
+                const size_t cap = n - i < (size_t)DEFLATE_MAX_MATCH ? n - i : (size_t)DEFLATE_MAX_MATCH;
+                while (len < cap && in[c + len] == in[i + len]) len++;
+                dist = (uint32_t)(i - c);
+            }
+        }
+        if (i != at) continue;
+        if (len >= (uint32_t)DEFLATE_MIN_MATCH) { tok[n_tok++] = len << 16 | dist; at = i + len; }
+        else { tok[n_tok++] = in[i]; at = i + 1; }
+    }
+    return n_tok;
+}
+
 // The host twin: the member of in[0 .. n), n <= 65 280, into out (room for n + 31 bytes); returns its size.  crc: the
-// payload's CRC-32.
-inline size_t deflate_member_host(const uint8_t *in, size_t n, uint32_t crc, uint8_t *out)
+// payload's CRC-32.  mode: DEFLATE_MODE_HUFFMAN, literals only, or DEFLATE_MODE_MATCH.
+inline size_t deflate_member_host(const uint8_t *in, size_t n, uint32_t crc, uint8_t *out, int mode = DEFLATE_MODE_HUFFMAN)
 {
     auto trailer = [&](uint8_t *t) {
         for (int k = 0; k < 4; k++) { t[k] = (uint8_t)(crc >> (8 * k)); t[4 + k] = (uint8_t)((uint32_t)n >> (8 * k)); }
@@ -266,6 +366,42 @@ inline size_t deflate_member_host(const uint8_t *in, size_t n, uint32_t crc, uin
         w.freq[256] = 1;
         deflate_plan_sorted(w, deflate_sort(w.freq, DEFLATE_NSYM, w.a, w.sym));
         block = deflate_block_bytes(w);
+    }
+    if (n > 0 && mode == DEFLATE_MODE_MATCH) {                  // step 6: the match block only where it is the smallest
+        std::vector<uint32_t> tok(n);
+        std::vector<uint16_t> head((size_t)1 << DEFLATE_HASH_BITS);
+        const size_t n_tok = deflate_tokens_host(in, n, tok.data(), head.data());
+        DeflateWork wm;
+        for (int s = 0; s < DEFLATE_NLL; s++) wm.freq[s] = 0;
+        for (int s = 0; s < DEFLATE_NDIST; s++) wm.dfreq[s] = 0;
+        for (size_t k = 0; k < n_tok; k++) {
+            if (tok[k] >> 16) { wm.freq[deflate_len_symbol(tok[k] >> 16) & 0xFFFFu]++; wm.dfreq[deflate_dist_symbol(tok[k] & 0xFFFFu) & 0xFFu]++; }
+            else wm.freq[tok[k]]++;
+        }
+        wm.freq[256] = 1;
+        deflate_plan_sorted(wm, deflate_sort(wm.freq, DEFLATE_NLL, wm.a, wm.sym), true);
+        const uint32_t mblock = deflate_block_bytes(wm);
+        if (mblock < block && mblock < n + 5) {
+            bgzf_member_header(out, mblock + 26);
+            uint8_t hdr[DEFLATE_HDR_CAP];
+            deflate_header(wm, hdr);
+            const uint32_t hb = wm.hdr_bits >> 3;
+            for (uint32_t k = 0; k < hb; k++) out[18 + k] = hdr[k];
+            DeflateBits b(out + 18 + hb);
+            if (wm.hdr_bits & 7) b.put(hdr[hb], wm.hdr_bits & 7);
+            for (size_t k = 0; k < n_tok; k++) {
+                if (!(tok[k] >> 16)) { b.code(wm.freq[tok[k]]); continue; }
+                const uint32_t ls = deflate_len_symbol(tok[k] >> 16), ds = deflate_dist_symbol(tok[k] & 0xFFFFu);
+                b.code(wm.freq[ls & 0xFFFFu]);
+                b.put(ls >> 24, (ls >> 16) & 0xFFu);
+                b.code(wm.dfreq[ds & 0xFFu]);
+                b.put(ds >> 16, (ds >> 8) & 0xFFu);
+            }
+            b.code(wm.freq[256]);
+            if (b.n) *b.o = (uint8_t)b.acc;
+            trailer(out + 18 + mblock);
+            return (size_t)mblock + 26;
+        }
     }
     if (n == 0 || block >= n + 5) {
         bgzf_member_header(out, (uint32_t)n + 31);

@@ -59,6 +59,7 @@ struct npore_batch_slot {
     // ... with NPORE_OUT_DEFLATE (bam_deflate_kernels.hpp): the members' plans, sizes and places, the coded members, the
     // batch's four numbers; the size table and the numbers here; recs_pin then holds members | head fragment | tail fragment
     DevBuf d_plans, d_sizes, d_moff, d_comp, d_info;
+    DevBuf d_htab, d_tokens;               // NPORE_OUT_MATCH: per member the hash table (2^15 positions) and the tokens
     PinnedBuf sizes_pin, info_pin;
     int64_t max_members = 0;
     int64_t frag[4] = {0, 0, 0, 0};        // of the fetched batch: members, their bytes, head bytes, tail bytes
@@ -79,11 +80,16 @@ struct npore_batch_slot {
 };
 
 namespace {
+int out_deflate_mode(int flags) { return !(flags & NPORE_OUT_DEFLATE) ? 0 : (flags & NPORE_OUT_MATCH) ? DEFLATE_MODE_MATCH : DEFLATE_MODE_HUFFMAN; }
 // NPORE_OUT_DEFLATE on the device: room for the most members `bytes` record bytes can hold
-int slot_deflate_buffers(npore_batch_slot &s, int64_t bytes)
+int slot_deflate_buffers(npore_batch_slot &s, int64_t bytes, int mode)
 {
     const int64_t mm = bytes / (int64_t)BGZF_STORED_PAYLOAD + 1;
     s.max_members = mm;
+    if (mode == DEFLATE_MODE_MATCH) {       // a member's hash table and its tokens (a token per byte at the most)
+        if (int rc = s.d_htab.ensure((size_t)mm * sizeof(uint16_t) << DEFLATE_HASH_BITS)) return rc;
+        if (int rc = s.d_tokens.ensure((size_t)mm * BGZF_STORED_PAYLOAD * sizeof(uint32_t) + 64)) return rc;
+    }
     if (int rc = s.d_plans.ensure((size_t)mm * sizeof(DeflateMemberPlan))) return rc;
     if (int rc = s.d_sizes.ensure((size_t)mm * 4 + 64)) return rc;
     if (int rc = s.d_moff.ensure((size_t)mm * 8 + 64)) return rc;
@@ -92,9 +98,12 @@ int slot_deflate_buffers(npore_batch_slot &s, int64_t bytes)
     if (int rc = s.sizes_pin.ensure((size_t)mm * 4 + 64)) return rc;
     return s.info_pin.ensure(64);
 }
-DeflateParams slot_deflate_params(npore_batch_slot &s, const uint8_t *d_recs, const unsigned long long *d_total, unsigned long long *d_stream_pos)
+DeflateParams slot_deflate_params(npore_batch_slot &s, const uint8_t *d_recs, const unsigned long long *d_total, unsigned long long *d_stream_pos,
+                                  int mode)
 {
     DeflateParams dp{};
+    dp.mode = mode;
+    if (mode == DEFLATE_MODE_MATCH) { dp.htab = s.d_htab.as<uint16_t>(); dp.tokens = s.d_tokens.as<uint32_t>(); }
     dp.recs = d_recs; dp.total = d_total; dp.stream_pos = d_stream_pos;
     dp.plans = s.d_plans.as<DeflateMemberPlan>(); dp.sizes = s.d_sizes.as<uint32_t>(); dp.off = s.d_moff.as<int64_t>();
     dp.comp = s.d_comp.as<uint8_t>();
@@ -1261,16 +1270,30 @@ int64_t npore_debug_crc32(const uint8_t *p, int64_t n, uint32_t crc)
     return (int64_t)crc32_fast(crc, p, (size_t)n);
 }
 
+int64_t npore_debug_deflate_member_mode(const uint8_t *in, int64_t n, uint8_t *out, int64_t cap, int mode)
+try {
+    if ((!in && n > 0) || !out || n < 0 || n > (int64_t)BGZF_STORED_PAYLOAD || cap < n + (int64_t)BGZF_STORED_OVERHEAD ||
+        (mode != DEFLATE_MODE_HUFFMAN && mode != DEFLATE_MODE_MATCH))
+        return fail(NPORE_E_INVALID, "bad argument");
+    return (int64_t)deflate_member_host(in, (size_t)n, crc32_fast(0, in, (size_t)n), out, mode);
+}
+NPORE_CATCH_INT
+
 int64_t npore_debug_deflate_member(const uint8_t *in, int64_t n, uint8_t *out, int64_t cap)
 {
-    if ((!in && n > 0) || !out || n < 0 || n > (int64_t)BGZF_STORED_PAYLOAD || cap < n + (int64_t)BGZF_STORED_OVERHEAD) return fail(NPORE_E_INVALID, "bad argument");
-    return (int64_t)deflate_member_host(in, (size_t)n, crc32_fast(0, in, (size_t)n), out);
+    return npore_debug_deflate_member_mode(in, n, out, cap, DEFLATE_MODE_HUFFMAN);
 }
 
 int npore_debug_deflate_device(npore_ctx *ctx, const uint8_t *bytes, int64_t n, int64_t phase, uint8_t *members, int64_t members_cap,
                                uint32_t *sizes, int64_t sizes_cap, uint8_t *head, uint8_t *tail, int64_t *info)
+{
+    return npore_debug_deflate_device_mode(ctx, bytes, n, phase, members, members_cap, sizes, sizes_cap, head, tail, info, DEFLATE_MODE_HUFFMAN);
+}
+
+int npore_debug_deflate_device_mode(npore_ctx *ctx, const uint8_t *bytes, int64_t n, int64_t phase, uint8_t *members, int64_t members_cap,
+                                    uint32_t *sizes, int64_t sizes_cap, uint8_t *head, uint8_t *tail, int64_t *info, int mode)
 try {
-    if (!ctx || (!bytes && n > 0) || n < 0 || phase < 0 || !info || members_cap < 0 || sizes_cap < 0 || (members_cap > 0 && !members) ||
+    if (!ctx || (mode != DEFLATE_MODE_HUFFMAN && mode != DEFLATE_MODE_MATCH) || (!bytes && n > 0) || n < 0 || phase < 0 || !info || members_cap < 0 || sizes_cap < 0 || (members_cap > 0 && !members) ||
         (sizes_cap > 0 && !sizes) || !head || !tail)
         return fail(NPORE_E_INVALID, "bad argument");
     if (int rc = quiesce(ctx)) return rc;
@@ -1281,11 +1304,11 @@ try {
     if (int rc = d_recs.ensure((size_t)n + 64)) return rc;
     if (int rc = d_total.ensure(64)) return rc;
     if (int rc = ctx->d_stream_pos.ensure(64)) return rc;
-    if (int rc = slot_deflate_buffers(s, n)) return rc;
+    if (int rc = slot_deflate_buffers(s, n, mode)) return rc;
     if (n > 0) HIP_TRY(hipMemcpy(d_recs.p, bytes, (size_t)n, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_total.p, &total, 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(ctx->d_stream_pos.p, &pos, 8, hipMemcpyHostToDevice));
-    const DeflateParams dp = slot_deflate_params(s, d_recs.as<uint8_t>(), d_total.as<unsigned long long>(), ctx->d_stream_pos.as<unsigned long long>());
+    const DeflateParams dp = slot_deflate_params(s, d_recs.as<uint8_t>(), d_total.as<unsigned long long>(), ctx->d_stream_pos.as<unsigned long long>(), mode);
     launch_deflate(dp, ctx->s_post);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(ctx->s_post));
@@ -1475,8 +1498,8 @@ NPORE_CATCH_INT
 
 int npore_bam_set_output(npore_bam *b, int format, const char *bai_path, int flags)
 {
-    if (!b || (format != NPORE_OUT_SAM && format != NPORE_OUT_BAM) || (flags & ~(NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE)) ||
-        ((flags & NPORE_OUT_DEFLATE) && format != NPORE_OUT_BAM))
+    if (!b || (format != NPORE_OUT_SAM && format != NPORE_OUT_BAM) || (flags & ~(NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE | NPORE_OUT_MATCH)) ||
+        ((flags & NPORE_OUT_DEFLATE) && format != NPORE_OUT_BAM) || ((flags & NPORE_OUT_MATCH) && !(flags & NPORE_OUT_DEFLATE)))
         return fail(NPORE_E_INVALID, "bad argument");
     b->out_format = format;
     b->out_bai = (format == NPORE_OUT_BAM && bai_path) ? bai_path : "";
@@ -1505,7 +1528,7 @@ try {
     b->out_flags = 0;
     std::fill(b->out_info, b->out_info + 4, 0);
     if (int rc = w.open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0,
-                        (flags & NPORE_OUT_DEFLATE) != 0, host_threads(threads)))
+                        out_deflate_mode(flags), host_threads(threads)))
         return rc;
     std::vector<BamRecMeta> meta;
     for (int64_t k0 = 0; k0 < n; k0 += batch_reads) {
@@ -1741,7 +1764,7 @@ struct RunOutput {
         if (format == NPORE_OUT_BAM) {
             bw.reset(new BgzfStoredWriter());
             return bw->open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0,
-                            (flags & NPORE_OUT_DEFLATE) != 0, std::max(1, host_threads(threads) / 2));
+                            out_deflate_mode(flags), std::max(1, host_threads(threads) / 2));
         }
         fh = std::fopen(out_path, "ab");
         return fh ? NPORE_OK : fail(NPORE_E_INVALID, std::string("cannot open '") + out_path + "' for appending");
@@ -1917,9 +1940,10 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             emit = BamEmit{s.d_recs.as<uint8_t>(), s.rec_cap, s.d_cursor.as<unsigned long long>(), reinterpret_cast<const int64_t *>(s.hp_pin.p),
                            reinterpret_cast<int64_t *>(s.reclen_pin.p), reinterpret_cast<unsigned long long *>(s.total_pin.p)};
             if (dev_deflate) {
-                if ((rc = slot_deflate_buffers(s, s.rec_cap))) { err = "batch buffers"; break; }
+                if ((rc = slot_deflate_buffers(s, s.rec_cap, bw->deflate_mode()))) { err = "batch buffers"; break; }
                 emit.deflate = true;
-                emit.dfl = slot_deflate_params(s, s.d_recs.as<uint8_t>(), s.d_cursor.as<unsigned long long>(), ctx->d_stream_pos.as<unsigned long long>());
+                emit.dfl = slot_deflate_params(s, s.d_recs.as<uint8_t>(), s.d_cursor.as<unsigned long long>(), ctx->d_stream_pos.as<unsigned long long>(),
+                                               bw->deflate_mode());
                 emit.h_sizes = reinterpret_cast<uint32_t *>(s.sizes_pin.p);
                 emit.h_info = reinterpret_cast<int64_t *>(s.info_pin.p);
             }

@@ -59,10 +59,11 @@ def argparser():
                         help="`sam`: the text, OUT_PREFIX.sam.  `bam`: OUT_PREFIX.bam, the same records in binary (built on the GPU in "
                              "the default pipeline) in uncompressed BGZF members, with OUT_PREFIX.bam.bai when they go out in "
                              "coordinate order -- what `samtools view -u` and `samtools index` would make of the SAM.")
-    parser.add_argument("--bam_compress", choices=("none", "huffman"), default="none",
+    parser.add_argument("--bam_compress", choices=("none", "huffman", "match"), default="none",
                         help="--out_format bam: `none`, stored BGZF members; `huffman`, every member one dynamic-Huffman DEFLATE block "
-                             "of literals (no match search), coded on the GPU in the default pipeline.  The records, the cuts and "
-                             "the index's meaning are the same.")
+                             "of literals (no match search); `match`, of literals and length/distance pairs (a hash of four bytes, a "
+                             "greedy parse) wherever that is smaller.  Both are coded on the GPU in the default pipeline.  The records, "
+                             "the cuts and the index's meaning are the same.")
     parser.add_argument("--python_io", action="store_true",
                         help="Use the pure-Python BAM reader / SAM writer (the restatement the native one is tested against).")
     return parser

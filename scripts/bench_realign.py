@@ -249,8 +249,9 @@ def main():
     ap.add_argument("--out_format", choices=("sam", "bam"), default="sam",
                     help="what the timed legs write: SAM text, or (bam) the records built on the GPU in stored BGZF members with their .bai "
                          "(`sam_bytes` then counts the BAM's bytes; slot `format` of the stage sums is the record bytes' trip to the host)")
-    ap.add_argument("--bam_compress", choices=("none", "huffman"), default="none",
-                    help="--out_format bam: stored members, or every member one dynamic-Huffman block coded on the GPU; the line's "
+    ap.add_argument("--bam_compress", choices=("none", "huffman", "match"), default="none",
+                    help="--out_format bam: stored members, or every member one dynamic-Huffman block coded on the GPU, of literals "
+                         "(huffman) or of literals and matches (match); the line's "
                          "`output_bytes` is the size of the one-pass leg's file")
     ap.add_argument("--gen-into", default=None, help=argparse.SUPPRESS)       # (internal: make the inputs in this directory and exit)
     a = ap.parse_args()

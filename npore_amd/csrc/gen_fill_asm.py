@@ -10,10 +10,11 @@ step kinds update it in place, and the temporaries are fixed scratch registers (
 What the text does is exactly the `step` lambda of kernels.hpp for FASTSEL = true (cell.hpp cell_update<FAST>), for as
 many steps of a span as it can take, in BLOCKS (to the end of the 64-step window, of the span, or of what the word queues
 and the L window hold: `block_end`): it returns with status 1 in front of a step that needs the rare path (a column
-descriptor with DSC_RARE: tested once per entry and, in a 'D' step, on the descriptor that enters) -- nothing of that step
-is done yet -- or with status 2 behind the poll of a 'D' step whose entering descriptor (learnt from the wave above) is
-rare, and the caller runs that one step through the C++ body and comes back.
-Several waves per chunk: the hand-over writes only the exchange record the NEXT step reads (`finish`), the first look at
+descriptor with DSC_RARE: tested once per entry and, in a 'D' step, on the descriptor that enters, which every wave takes
+from its own queue of reference words) -- nothing of that step is done yet -- and the caller runs that one step through
+the C++ body and comes back.
+Several waves per chunk: the hand-over writes only the exchange record the NEXT step reads (`finish`: of a 'D' step
+the boundary CELL alone -- the reference words that move with it are static annotation and come from the queue), the first look at
 the neighbours' progress words and the read of the neighbour's boundary cell are issued at the head of the step
 (`poll_issue`), a wave that has to wait polls at issue priority 0 (`polls`).
 
@@ -27,9 +28,9 @@ import os
 import re
 
 # ---- scratch registers (clobbered) ---------------------------------------------------------------------------------
-# (X0 ... X3 are an aligned quad, X4 X5 an aligned pair: the exchange words of the neighbour waves arrive by ds_read_b128 / ds_read2_b32)
+# (X0 ... X3 are an aligned quad: the exchange words of the neighbour waves arrive by ds_read_b128)
 X0, X1, X2, X3, X4, X5 = "v92", "v93", "v94", "v95", "v96", "v97"      # neighbour cell / exchange words, then scratch
-XQ, X01, X23, X45 = "v[92:95]", "v[92:93]", "v[94:95]", "v[96:97]"
+XQ = "v[92:95]"
 SD, SE, SF = "v91", "v98", "v99"
 P0, P1, PP = "v100", "v101", "v[100:101]"
 SUBV, DRUN, NINSR, NDELR = "v102", "v103", "v87", "v88"
@@ -47,6 +48,7 @@ SCRATCH = ["v%d" % k for k in range(87, 112)]
 NP_CT = 34                          # layout.hpp: words per row of the LDS score table
 LDS_SUB_BASE = 6 * 32 * NP_CT * 4   # kernels.hpp LDS_SUB_BASE
 XCH_WORDS = 12                      # kernels.hpp
+XCH_D = 4                           # kernels.hpp: first word of the 'D' cell (MAT, INS, runs) in an exchange record, 16-byte aligned
 
 
 def O(name):
@@ -486,8 +488,7 @@ def next_step(t, mode):
 def finish(t, mode, first, last, multi, mid, len_variant):
     """behind MAT and the history record: band-edge cells, then (several waves per chunk) the hand-over and the next step.
     The exchange record a neighbour wave will read depends on the NEXT step's kind -- an 'I' step reads the last cell
-    of the wave below as its left neighbour, a 'D' step the first cell of the wave above (and the reference words that
-    move down with it) as its top neighbour -- and that kind is known here (the loop's own dispatch, done first): only
+    of the wave below as its left neighbour, a 'D' step the first cell of the wave above as its top neighbour -- and that kind is known here (the loop's own dispatch, done first): only
     that record is written.  At the end of a block of steps (the kind is in another mask word) both are.
     Release: the LDS unit serves the requests of one wave in order, so the record and the history row are in place
     before the progress word that follows them; the explicit lgkmcnt(0) in front of it (like the C++ body's workgroup
@@ -507,12 +508,11 @@ def finish(t, mode, first, last, multi, mid, len_variant):
             ds_write2_b32 {O('xown')}, {r2}, {O('seqw')} offset0:{2 * XCH_WORDS + 2} offset1:{2 * XCH_WORDS + 3}
         """)
 
-    def rec0():       # first lane's cell and its reference words, for the wave below (exec = lane 0)
-        b = 2 * XCH_WORDS + 5
+    def rec0():       # first lane's cell for the wave below (exec = lane 0)
+        b = 2 * XCH_WORDS + XCH_D
         t(f"""
             ds_write2_b32 {O('xown')}, {own_m}, {own_i} offset0:{b} offset1:{b + 1}
-            ds_write2_b32 {O('xown')}, {r1}, {O('refx')} offset0:{b + 2} offset1:{b + 3}
-            ds_write2_b32 {O('xown')}, {O('rc0')}, {O('rc1')} offset0:{b + 4} offset1:{b + 5}
+            ds_write_b32 {O('xown')}, {r1} offset:{4 * (b + 2)}
         """)
 
     def publish():    # (exec = lane 0) the progress word, then the other parity's exchange records
@@ -578,8 +578,8 @@ def tail(t, mode, first, last, multi):
 
 def block_end(t, first, last):
     """bl has reached bend, the end of a block of steps that needs no test but its own count: the 64-step window, the
-    span, and what the word queues (read words entering at column 0: first wave; reference words entering at the last
-    column: last wave) and the reference-L window (last wave) hold -- a block is at most as many steps, of either kind, as
+    span, and what the word queues (read words entering at column 0: first wave; reference words entering at the wave's
+    last lane: every wave) and the reference-L window (last wave) hold -- a block is at most as many steps, of either kind, as
     the emptiest of them has entries, so the steps themselves carry no queue tests; near a refill the blocks get short
     (halving), a dozen scalar instructions per block.
     At a window boundary the step window after the new one is fetched, 64 steps before it is needed (the wait also
@@ -618,16 +618,18 @@ def block_end(t, first, last):
             s_add_i32 {O('sx')}, {O('sx')}, 64
             s_min_i32 {O('bend')}, {O('bend')}, {O('sx')}
         """)
+    t(f"""
+        s_cmp_ge_i32 {O('rqidx')}, 64
+        s_cbranch_scc1 {L('fill_rq')}
+    """)
+    t.label("rq_ok")
+    t(f"""
+        s_sub_i32 {O('sx')}, {O('bl')}, {O('rqidx')}
+        s_add_i32 {O('sx')}, {O('sx')}, 64
+        s_min_i32 {O('bend')}, {O('bend')}, {O('sx')}
+    """)
     if last:
         t(f"""
-            s_cmp_ge_i32 {O('rqidx')}, 64
-            s_cbranch_scc1 {L('fill_rq')}
-        """)
-        t.label("rq_ok")
-        t(f"""
-            s_sub_i32 {O('sx')}, {O('bl')}, {O('rqidx')}
-            s_add_i32 {O('sx')}, {O('sx')}, 64
-            s_min_i32 {O('bend')}, {O('bend')}, {O('sx')}
             s_cmp_ge_i32 {O('sdel')}, {O('dlim')}
             s_cbranch_scc1 {L('fill_win')}
         """)
@@ -647,16 +649,12 @@ def block_end(t, first, last):
 def xch_reads(t, mode, first, last):
     """the neighbour wave's boundary cell of the previous anti-diagonal (its exchange record of the other parity): an 'I'
     step reads the last cell of the wave below (words 0-3: MAT, DEL, runs, read word), a 'D' step the first cell of the
-    wave above (words 5-10: MAT, INS, runs, reference word, the two column descriptors; the descriptors first)"""
+    wave above (words 4-6: MAT, INS, runs; word 7 comes along unused).  The reference words that move down with a 'D'
+    step are not handed over: every wave takes the one entering at its last lane from its own queue (mode_d)"""
     if mode == "I" and not first:
         t(f"ds_read_b128 {XQ}, {O('xoth')}")
     if mode == "D" and not last:
-        b = (4 * XCH_WORDS + 5)
-        t(f"""
-            ds_read2_b32 {X45}, {O('xoth')} offset0:{b + 4} offset1:{b + 5}
-            ds_read2_b32 {X01}, {O('xoth')} offset0:{b} offset1:{b + 1}
-            ds_read2_b32 {X23}, {O('xoth')} offset0:{b + 2} offset1:{b + 3}
-        """)
+        t(f"ds_read_b128 {XQ}, {O('xoth')} offset:{4 * (4 * XCH_WORDS + XCH_D)}")
 
 
 def poll_issue(t, mode, first, last):
@@ -763,7 +761,9 @@ def gen_role(role):
     if multi:
         poll_issue(t, "I", first, last)
     book(t, "I")
-    shr_tables(t, X3 if first else SD)          # (X3 is waiting for its exchange word)
+    # (every wave but the first: X0 ... X3 are waiting for the 'I' exchange record issued with the poll -- its read word
+    # lands in X3 -- so the scratch is SD; the first wave reads no 'I' record and X3 is free)
+    shr_tables(t, X3 if first else SD)
     t(f"v_add_u32_sdwa {DRUN}, {O('LMr')}, {O('one')} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD")
     ins_part(t, "I", X4, X5, O("sb"), (f"v_mov_b32 {O('TMv')}, {MATV}", f"v_mov_b32 {O('TMr')}, {O('R1')}"))
     if first:
@@ -800,16 +800,17 @@ def gen_role(role):
     len_pass(t, mid, "_I", "I", first, last, multi)
     tail(t, "I", first, last, multi)
     # ================= 'D' step: reference words (and the column descriptors) move one column down, "top" is the
-    # next lane.  Last wave of a chunk: the word entering at its last lane comes from its own queue and the next
-    # lane's cell is in its own registers, so all but the history reads sits in front of the poll; the other waves
-    # learn both from the wave above, behind the poll.
+    # next lane.  The word entering at the wave's last lane comes from the wave's own queue (static annotation: every
+    # wave keeps the 64 that will enter next, like the first wave its read words), so the rare test of the entering
+    # descriptor, the shifts, the summary bits and the lane-table reads sit in front of the poll.  Last wave: the next
+    # lane's cell is in its own registers too, and INS goes there as well; the other waves take the cell of the wave
+    # above's first lane from the exchange record, behind the poll.
     t.label("mode_d")
-    if last:
-        t(f"""
-            v_readlane_b32 {O('sx')}, {O('rqz')}, {O('rqidx')}
-            s_bitcmp1_b32 {O('sx')}, 7
-            s_cbranch_scc1 {L('exit')}
-        """)
+    t(f"""
+        v_readlane_b32 {O('sx')}, {O('rqz')}, {O('rqidx')}
+        s_bitcmp1_b32 {O('sx')}, 7
+        s_cbranch_scc1 {L('exit')}
+    """)
     if multi:
         poll_issue(t, "D", first, last)
     book(t, "D")
@@ -846,31 +847,41 @@ def gen_role(role):
         sub_read(t)
         t("s_waitcnt lgkmcnt(1)")
     else:
-        polls(t, "D", first, last, "_d")
+        # (X0 ... X3 are waiting for the exchange record, P0 P1 for the progress words: nothing in front of the poll
+        # touches them; the three shifts are interleaved so that each v_writelane finds its DPP move two slots back)
         t(f"""
-            v_and_b32 {SD}, 0x80, {X4}
-            v_cmp_ne_u32 vcc, 0, {SD}
-            s_cbranch_vccnz {L('exit2')}
-            v_mov_b32_dpp {X4}, {O('rc0')} wave_shl:1 row_mask:0xf bank_mask:0xf
-            v_mov_b32 {O('rc0')}, {X4}
-        """)
-        shr_tables(t, SD)          # (X3 holds its exchange word)
-        t(f"""
+            v_mov_b32_dpp {O('rc0')}, {O('rc0')} wave_shl:1 row_mask:0xf bank_mask:0xf
+            v_mov_b32_dpp {O('refx')}, {O('refx')} wave_shl:1 row_mask:0xf bank_mask:0xf
+            v_mov_b32_dpp {O('rc1')}, {O('rc1')} wave_shl:1 row_mask:0xf bank_mask:0xf
+            v_writelane_b32 {O('rc0')}, {O('sx')}, 63
+            v_readlane_b32 {O('sx')}, {O('rqx')}, {O('rqidx')}
             v_and_b32 {SMR}, {'0xbc' if mid else O('livebc')}, {O('rc0')}
-            v_mov_b32_dpp {X3}, {O('refx')} wave_shl:1 row_mask:0xf bank_mask:0xf
-            v_mov_b32_dpp {X5}, {O('rc1')} wave_shl:1 row_mask:0xf bank_mask:0xf
+        """)
+        shr_tables(t, X4)
+        t(f"""
+            v_writelane_b32 {O('refx')}, {O('sx')}, 63
+            v_readlane_b32 {O('sx')}, {O('rqw')}, {O('rqidx')}
+            s_add_i32 {O('rqidx')}, {O('rqidx')}, 1
+        """)
+        sub_addr = f"""
+            v_alignbit_b32 {SUBV}, {O('refx')}, {O('seqw')}, 27
+            v_and_b32 {SUBV}, 0xfc, {SUBV}
+        """
+        t(sub_addr)
+        t(f"v_writelane_b32 {O('rc1')}, {O('sx')}, 63")
+        polls(t, "D", first, last, "_d")
+        # behind the poll: the neighbour's cell (lane 63 keeps the exchange word: a DPP move without bound_ctrl leaves
+        # the lane without a source as it is), the candidate's source record, the score read, INS in their shadow
+        shr_hist(t)
+        t(f"""
+            ds_read_b32 {SUBV}, {SUBV} offset:{LDS_SUB_BASE}
             v_mov_b32_dpp {X0}, {MATV} wave_shl:1 row_mask:0xf bank_mask:0xf
             v_mov_b32_dpp {X1}, {O('insv')} wave_shl:1 row_mask:0xf bank_mask:0xf
             v_mov_b32_dpp {X2}, {O('R1')} wave_shl:1 row_mask:0xf bank_mask:0xf
-            v_mov_b32 {O('refx')}, {X3}
-            v_mov_b32 {O('rc1')}, {X5}
             v_mov_b32 {O('TMr')}, {X2}
         """)
-        sub_read(t)
-        ins_part(t, "D", X4, X5, O("sb"))      # (in the shadow of the lane-table reads)
+        ins_part(t, "D", X4, X5, O("sb"))
         t("s_waitcnt lgkmcnt(1)")
-        shr_hist(t)
-        t("s_waitcnt lgkmcnt(0)")
     shr_pass(t, mid, "_D", SMR, lambda: del_part(t, "D", X4, X5, O("sb")), lambda: del_part(t, "D", SD, P0, O("sb")), multi)
     len_pass(t, mid, "_D", "D", first, last, multi)
     tail(t, "D", first, last, multi)
@@ -893,29 +904,30 @@ def gen_role(role):
             s_mov_b64 exec, -1
             s_branch {L('sq_ok')}
         """)
+    # reference words entering at the wave's last lane: the next 64 (REFW_SENTINEL outside the chunk's columns).
+    # Every wave of a chunk counts the same 'D' steps from the same start, so they all refill at the same step
+    t.label("fill_rq")
+    t(f"""
+        s_sub_i32 {O('rqidx')}, {O('rqidx')}, 64
+        s_add_i32 {O('rqbase')}, {O('rqbase')}, 64
+        v_add_u32 {X5}, {O('rqbase')}, {O('laneid')}
+        v_mov_b32 {O('rqx')}, 0xdb6d8000
+        v_mov_b32 {O('rqz')}, 0
+        v_mov_b32 {O('rqw')}, 0
+        v_cmp_le_i32 vcc, 0, {X5}
+        v_cmp_ge_i32 {O('sa')}, {O('dcols')}, {X5}
+        v_lshlrev_b32 {X5}, 4, {X5}
+        s_and_b64 vcc, vcc, {O('sa')}
+        s_and_saveexec_b64 {O('sa')}, vcc
+        global_load_dwordx4 v[92:95], {X5}, {O('refwg')}
+        s_waitcnt vmcnt(0)
+        v_mov_b32 {O('rqx')}, v92
+        v_mov_b32 {O('rqz')}, v94
+        v_mov_b32 {O('rqw')}, v95
+        s_mov_b64 exec, -1
+        s_branch {L('rq_ok')}
+    """)
     if last:
-        # reference words entering at the last column: the next 64 (REFW_SENTINEL outside the chunk's columns)
-        t.label("fill_rq")
-        t(f"""
-            s_sub_i32 {O('rqidx')}, {O('rqidx')}, 64
-            s_add_i32 {O('rqbase')}, {O('rqbase')}, 64
-            v_add_u32 {X5}, {O('rqbase')}, {O('laneid')}
-            v_mov_b32 {O('rqx')}, 0xdb6d8000
-            v_mov_b32 {O('rqz')}, 0
-            v_mov_b32 {O('rqw')}, 0
-            v_cmp_le_i32 vcc, 0, {X5}
-            v_cmp_ge_i32 {O('sa')}, {O('dcols')}, {X5}
-            v_lshlrev_b32 {X5}, 4, {X5}
-            s_and_b64 vcc, vcc, {O('sa')}
-            s_and_saveexec_b64 {O('sa')}, vcc
-            global_load_dwordx4 v[92:95], {X5}, {O('refwg')}
-            s_waitcnt vmcnt(0)
-            v_mov_b32 {O('rqx')}, v92
-            v_mov_b32 {O('rqz')}, v94
-            v_mov_b32 {O('rqw')}, v95
-            s_mov_b64 exec, -1
-            s_branch {L('rq_ok')}
-        """)
         # reference-L window (LDS): the next WIN_STEP positions, ahead of the band
         ws = 32 if role == 0 else 64
         t.label("fill_win")
@@ -941,9 +953,6 @@ def gen_role(role):
             s_branch {L('win_ok')}
         """)
     block_end(t, first, last)
-    t.label("exit2")
-    t(f"s_mov_b32 {O('status')}, 2")
-    t(f"s_branch {L('end')}")
     t.label("exit")
     t(f"s_mov_b32 {O('status')}, 1")
     t(f"s_branch {L('end')}")
@@ -952,7 +961,7 @@ def gen_role(role):
     t.label("end")
     t(f"v_mov_b32 {O('matv')}, {MATV}")
     # nothing of this text may be in flight when the compiled code resumes: it reuses the scratch registers at once --
-    # loads still on their way into them (exit2: the exchange words), and the history record's ds_write_b128, which
+    # loads still on their way into them, and the history record's ds_write_b128, which
     # reads its four data registers for a few cycles after issue
     t("s_waitcnt lgkmcnt(0)")
     return fix_hazards(t.lines)
@@ -1061,9 +1070,9 @@ def operands(role):
         outs += [("prog", "+v", "prog_v"), ("xown", "+v", "xown"), ("xoth", "+v", "xoth")]
     if first:
         outs += [("sqidx", "+s", "a_sq"), ("sqbase", "+s", "a_sqb"), ("seqq", "+v", "seq_q")]
+    outs += [("rqidx", "+s", "a_rq"), ("rqbase", "+s", "a_rqb"), ("rqx", "+v", "ref_q.x"), ("rqz", "+v", "ref_q.z"), ("rqw", "+v", "ref_q.w")]
     if last:
-        outs += [("rqidx", "+s", "a_rq"), ("rqbase", "+s", "a_rqb"), ("rqx", "+v", "ref_q.x"), ("rqz", "+v", "ref_q.z"),
-                 ("rqw", "+v", "ref_q.w"), ("wfill", "+s", "a_wfill"), ("dlim", "+s", "a_dlim")]
+        outs += [("wfill", "+s", "a_wfill"), ("dlim", "+s", "a_dlim")]
     outs += [("sx", "=&s", "a_sx")]
     ins = [("stepsg", "s", "steps_g"), ("laneid", "v", "a_laneid"), ("b1", "s", "a_b1"), ("hw16", "s", "a_hw16"), ("ringb", "s", "ring_bytes"),
            ("tbs4", "s", "tbstride4"), ("n0", "s", "env.n0_lanes"), ("tbg", "s", "tb_g"), ("istart", "s", "a_istart"),
@@ -1082,6 +1091,8 @@ def operands(role):
         ins += [("ml0", "s", "a_ml0"), ("me", "s", "a_me")]
     if last:
         ins += [("medge", "s", "a_medge"), ("dcols", "s", "a_dcols"), ("refwg", "s", "refw_g"), ("reflg", "s", "refl_g")]
+    else:
+        ins += [("dcols", "s", "a_dcols"), ("refwg", "s", "refw_g")]
     if first:
         ins += [("drows", "s", "a_drows"), ("seqwg", "s", "seqw_g")]
     return outs, ins

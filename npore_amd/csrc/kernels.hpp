@@ -45,8 +45,11 @@ namespace npore {
 
 static_assert(NP_LT == NP_CT - NP_C0 && (NP_LT & (NP_LT - 1)) == 0, "np_full's range test");
 constexpr int MAX_WAVES_PER_CHUNK = 16;   // a workgroup of 1 024 threads: r <= 511
-constexpr int XCH_WORDS = 12;   // per wave, per parity: boundary cells handed to the neighbour waves
-                                // (words 0-3 last cell, 5-10 first cell)
+constexpr int XCH_WORDS = 12;   // per wave, per parity: boundary cells handed to the neighbour waves.  Words 0-3: the wave's
+                                // last cell for an 'I' step (MAT, DEL, runs, read word); words 4-6: its first cell for a
+                                // 'D' step; words 7-11 are unused (7 is read with the cell and ignored) and kept on
+                                // purpose, so that fill_lds_bytes and with it fill_shape(r) stay what they were
+constexpr int XCH_D = 4;        // first word of the 'D' cell (MAT, INS, runs) in a record: 16-byte aligned, one ds_read_b128
 
 // history ring rows.  One wave per chunk: row b overwrites row b-6 after this wave
 // has read it (LDS ops of a wave are in order).  Several waves per chunk: a wave may
@@ -490,9 +493,10 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
             rc0 = rw.z;
             rc1 = rw.w;
         }
-        // queues of words that will enter at column 0 (read; first wave) / column WPT-1 (reference; last wave)
+        // queues of words that will enter at column 0 (read; first wave) / at the wave's last lane (reference; every
+        // wave: the words are static annotation, so no wave takes them from the wave above through the hand-shake)
         int sq_base = r + 1;              // next read index entering at column 0 is ins_l + r
-        int rq_base = WPT - r;            // next reference index entering at column WPT-1 is del_l + WPT-1 - r
+        int rq_base = 64 * (cw + 1) - r;  // next reference index entering at lane 63 is del_l + 64 cw + 63 - r
         int sq_idx = 0, rq_idx = 0;       // lane of seq_q / ref_q that holds it
         uint32_t seq_q = SEQW_SENTINEL;
         uint4 ref_q = make_uint4(REFW_SENTINEL, 0u, 0u, 0u);
@@ -500,7 +504,7 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
             const int i = sq_base + lane;
             seq_q = (i <= d.drows) ? seqw_g[i] : SEQW_SENTINEL;
         }
-        if (cw == NW - 1) {
+        {
             const int j = rq_base + lane;
             ref_q = (j >= 0 && j <= d.dcols) ? refw_g[j] : make_uint4(REFW_SENTINEL, 0u, 0u, 0u);
         }
@@ -590,18 +594,15 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
         // instantiated per mode: the neighbour fetch then needs no selects.  (The compiler still places 14 + 5
         // register copies per step where the two bodies meet; ONE body with a short per-kind branch in front of a
         // common cell update has 5 inherent copies and measured 2.6 % slower at r = 100 -- DESIGN.md section 6.)
-        // book_tag = false: ring row, lane table of history offsets and traceback row of this anti-diagonal have been
-        // advanced already (a 'D' step that the assembly loop handed over behind its poll, plain_span below)
-        auto step4 = [&](auto mode_tag, auto role_tag, auto fast_tag, auto book_tag) __attribute__((always_inline)) {
+        auto step = [&](auto mode_tag, auto role_tag, auto fast_tag) __attribute__((always_inline)) {
             constexpr int MODE = decltype(mode_tag)::value;
-            constexpr bool BOOK = decltype(book_tag)::value;
             // ROLE: 0 = only wave of the chunk, 1 = first, 2 = middle, 3 = last (compile-time so that the
             // per-role code needs no joins inside the loop)
             constexpr int ROLE = decltype(role_tag)::value;
             constexpr bool IS_FIRST = (ROLE == 0 || ROLE == 1), IS_LAST = (ROLE == 0 || ROLE == 3);
             // FASTSEL: every band cell of this anti-diagonal is an ordinary one (cell.hpp step_is_plain)
             constexpr bool FASTSEL = decltype(fast_tag)::value;
-            if constexpr (MODE != 0 && BOOK) {
+            if constexpr (MODE != 0) {
                 // ring row of this anti-diagonal, then the lane table of history offsets: its entry n is entry n-1
                 // of the previous anti-diagonal's (same ring row), 16 bytes lower if the band has just moved (an
                 // 'I' step); entry 0 = this anti-diagonal's own row.  Nothing here depends on the neighbour waves,
@@ -697,38 +698,35 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
                 st.ins_l++;
             } else if constexpr (MODE == 2) {
                 float nm, ni;
-                uint32_t nr, nx, nc0, nc1;
+                uint32_t nr;
+                // reference word for col del_l + 64 cw + 63 - r enters at the wave's last lane, from the wave's own queue
+                if (rq_idx >= 64) {
+                    rq_idx -= 64;
+                    rq_base += 64;
+                    const int j = rq_base + lane;
+                    ref_q = (j >= 0 && j <= d.dcols) ? refw_g[j] : make_uint4(REFW_SENTINEL, 0u, 0u, 0u);
+                    asm volatile("" : "+v"(ref_q.x), "+v"(ref_q.z), "+v"(ref_q.w));   // wait inside the rare branch
+                }
+                const uint32_t inx = (uint32_t)__builtin_amdgcn_readlane((int)ref_q.x, rq_idx);
+                const uint32_t inz = (uint32_t)__builtin_amdgcn_readlane((int)ref_q.z, rq_idx);
+                const uint32_t inw = (uint32_t)__builtin_amdgcn_readlane((int)ref_q.w, rq_idx);
+                rq_idx++;
+                const uint32_t nx = lane_next_or(inx, refx);
+                const uint32_t nc0 = lane_next_or(inz, rc0);
+                const uint32_t nc1 = lane_next_or(inw, rc1);
                 if constexpr (IS_LAST) {
                     nm = lane_next(matv); ni = lane_next(insv); nr = lane_next(R1);
-                    // word for col del_l + WPT-1 - r enters at column WPT-1
-                    if (rq_idx >= 64) {
-                        rq_idx -= 64;
-                        rq_base += 64;
-                        const int j = rq_base + lane;
-                        ref_q = (j >= 0 && j <= d.dcols) ? refw_g[j] : make_uint4(REFW_SENTINEL, 0u, 0u, 0u);
-                        asm volatile("" : "+v"(ref_q.x), "+v"(ref_q.z), "+v"(ref_q.w));   // wait inside the rare branch
-                    }
-                    const uint32_t inx = (uint32_t)__builtin_amdgcn_readlane((int)ref_q.x, rq_idx);
-                    const uint32_t inz = (uint32_t)__builtin_amdgcn_readlane((int)ref_q.z, rq_idx);
-                    const uint32_t inw = (uint32_t)__builtin_amdgcn_readlane((int)ref_q.w, rq_idx);
-                    rq_idx++;
-                    nx = lane_next_or(inx, refx);
-                    nc0 = lane_next_or(inz, rc0);
-                    nc1 = lane_next_or(inw, rc1);
                 } else {
-                    // first cell of the wave above: record + 4 records, words 5-10
-                    uint32_t x0, x1, x2, x3, x4, x5;
-                    asm volatile("ds_read_b32 %0, %6 offset:212\n\tds_read_b32 %1, %6 offset:216\n\tds_read_b32 %2, %6 offset:220\n\t"
-                                 "ds_read_b32 %3, %6 offset:224\n\tds_read_b32 %4, %6 offset:228\n\tds_read_b32 %5, %6 offset:232\n\t"
+                    // first cell of the wave above: record + 4 records, words XCH_D ... XCH_D + 2
+                    uint32_t x0, x1, x2;
+                    asm volatile("ds_read_b32 %0, %3 offset:208\n\tds_read_b32 %1, %3 offset:212\n\tds_read_b32 %2, %3 offset:216\n\t"
                                  "s_waitcnt lgkmcnt(0)"
-                                 : "=&v"(x0), "=&v"(x1), "=&v"(x2), "=&v"(x3), "=&v"(x4), "=&v"(x5) : "v"(xoth) : "memory");
-                    static_assert((4 * XCH_WORDS + 5) * 4 == 212, "offsets in the asm above");
+                                 : "=&v"(x0), "=&v"(x1), "=&v"(x2) : "v"(xoth) : "memory");
+                    static_assert((4 * XCH_WORDS + XCH_D) * 4 == 208 && (XCH_WORDS * 4) % 16 == 0 && XCH_D % 4 == 0 && XCH_D >= 4 && XCH_D + 3 <= XCH_WORDS,
+                                  "offsets in the asm above and in gen_fill_asm.py (ds_read_b128: 16-byte aligned, clear of the 'I' cell)");
                     nm = lane_next_or(__uint_as_float(x0), matv);
                     ni = lane_next_or(__uint_as_float(x1), insv);
                     nr = lane_next_or(x2, R1);
-                    nx = lane_next_or(x3, refx);
-                    nc0 = lane_next_or(x4, rc0);
-                    nc1 = lane_next_or(x5, rc1);
                 }
                 st.del_l++;
                 if (st.del_l + r + WIN_SLACK >= wfill) {   // keep the L window ahead of the band
@@ -801,7 +799,7 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
             }
             if constexpr (MULTI) {
                 // boundary cells for the neighbour waves: the last lane's cell for the wave above (it reads
-                // it as a LEFT neighbour), the first lane's for the wave below (TOP neighbour + reference words);
+                // it as a LEFT neighbour), the first lane's for the wave below (TOP neighbour);
                 // then the progress word, after this step's LDS writes (workgroup release: LDS only, it does not
                 // wait for the traceback stores above, which must stay in flight)
                 lds_u32 *xout = reinterpret_cast<lds_u32 *>(xown) + 2 * XCH_WORDS;
@@ -816,12 +814,9 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
                 asm("v_add_u32 %0, 1, %0" : "+v"(prog_v));
                 if (lane == 0) {
                     if constexpr (!IS_FIRST) {
-                        xout[5] = __float_as_uint(matv);
-                        xout[6] = __float_as_uint(insv);
-                        xout[7] = R1;
-                        xout[8] = refx;
-                        xout[9] = rc0;
-                        xout[10] = rc1;
+                        xout[XCH_D] = __float_as_uint(matv);
+                        xout[XCH_D + 1] = __float_as_uint(insv);
+                        xout[XCH_D + 2] = R1;
                     }
                     NPORE_PUBLISH_FENCE();
                     __hip_atomic_store(&prog[cw], (int)prog_v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -830,10 +825,6 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
                 const uint32_t xs = xsum;      // (an asm operand alone does not make the lambda capture it)
                 asm("v_sub_u32 %0, %2, %0\n\tv_sub_u32 %1, %2, %1" : "+v"(xown), "+v"(xoth) : "s"(xs));
             }
-        };
-
-        auto step = [&](auto mode_tag, auto role_tag, auto fast_tag) __attribute__((always_inline)) {
-            step4(mode_tag, role_tag, fast_tag, std::true_type{});
         };
 
         // anti-diagonals [b0, b1) of one step window
@@ -917,15 +908,12 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
                 rq_idx = a_rq; rq_base = a_rqb;
                 if constexpr (ROLE == 0 || ROLE == 3) wfill = a_wfill;
                 // the scalar bookkeeping the text does not carry: local row / column of the input path
-                // 'I' steps = steps taken - 'D' steps taken (a 'D' step stopped behind its poll has counted itself already)
-                st.ins_l += (a_bl - bl_in) - (a_sdel - sdel_in - (a_status == 2 ? 1 : 0));
+                // 'I' steps = steps taken - 'D' steps taken
+                st.ins_l += (a_bl - bl_in) - (a_sdel - sdel_in);
                 st.del_l = a_sdel;
                 }
                 if (!a_status) break;
-                if (a_status == 2) {       // a 'D' step, stopped behind its poll: bookkeeping and column count already advanced
-                    st.del_l = a_sdel - 1;
-                    step4(std::integral_constant<int, 2>{}, role_tag, std::true_type{}, std::false_type{});
-                } else if ((stepmask >> (a_bl & 63)) & 1ull) step(std::integral_constant<int, 1>{}, role_tag, std::true_type{});
+                if ((stepmask >> (a_bl & 63)) & 1ull) step(std::integral_constant<int, 1>{}, role_tag, std::true_type{});
                 else step(std::integral_constant<int, 2>{}, role_tag, std::true_type{});
                 a_bl++;
                 a_sdel = uni(st.del_l);

@@ -82,19 +82,59 @@ def L(name):
     return name + "_%="
 
 
-# more scratch: lane-table results of the first SHR candidate, fetched before the hand-shake poll
+# more scratch: lane-table result of the first SHR candidate (where its source record lies), fetched before the
+# hand-shake poll; E1 is a temporary of the SHR / LEN passes
 E0, E1 = "v89", "v90"
+# ---- the column cache ------------------------------------------------------------------------------------------------
+# What a step derives from the column descriptor rc0 alone changes only when the descriptors move: in a 'D' step.  The
+# 'D' body (and the text's entry: the compiled step that ran before may have moved them) leaves it in operands of the
+# statement that nothing else in the text writes, and an 'I' step -- half of all steps -- reads it from there:
+#   cidx   rc0 & 28: the lane-table index of the first SHR candidate          cper   its period
+#   crcp   the lane's 1/n (trecip is a static table)                          cbase  its row of the LDS score table
+#   csf    (scalar pair) lanes whose candidate starts a run                   ctwo   lanes with a second candidate
+#   cnone  (first / last wave of several) lanes with any candidate
+# Early-clobber outputs: the compiler gives them registers of their own, apart from every input and from the scratch.
+CIDX, CRCP, CBASE, CPER = "%[cidx]", "%[crcp]", "%[cbase]", "%[cper]"
+CSF, CTWO, CNONE = "%[csf]", "%[ctwo]", "%[cnone]"
+PAD = {"valu": 0, "salu": 0, "bperm": 0}        # timing-only: --pad KIND:N extra instructions at the head of every step
 ABLATE = {"nopoll": False, "nolen": False}      # timing-only ablations (wrong strings): --nopoll / --nolen with --out FILE
 
 
-def shr_tables(t, tmp=X3):
-    """lane tables of the column's first SHR candidate (cell.hpp shr_small): where its source record lies, 1/n.
-    tmp: a register with NO load on its way (a VALU write to a register an LDS read is still going to fill races)"""
+def col_cache(t, mid, none_test, smr):
+    """the column cache from rc0 as it stands (the 'D' step: behind the shift and the v_writelane of the entering
+    descriptor; the text's entry); leaves the 1/n read in flight.  smr: scratch for the summary bits (rc0 & 0xbc of
+    the band-interior columns: the mask comes per lane, zero in the lanes of the band's edge columns and beyond; a
+    middle wave holds no such lanes) -- they live on only as the two wave-level decisions"""
     t(f"""
-        v_and_b32 {tmp}, 28, {O('rc0')}
-        ds_bpermute_b32 {E0}, {tmp}, {O('tab')}
-        ds_bpermute_b32 {E1}, {tmp}, {O('trecip')}
+        v_and_b32 {smr}, {'0xbc' if mid else O('livebc')}, {O('rc0')}
+        v_and_b32 {CIDX}, 28, {O('rc0')}
+        ds_bpermute_b32 {CRCP}, {CIDX}, {O('trecip')}
+        v_cmp_gt_i32 {CSF}, 0, {O('rc0')}
+        v_bfe_u32 {CBASE}, {O('rc0')}, 15, 16
+        v_cmp_lt_u32 {CTWO}, 28, {smr}
     """)
+    if not mid and none_test:
+        t(f"v_cmp_ne_u32 {CNONE}, 0, {smr}")
+    t(f"v_bfe_u32 {CPER}, {O('rc0')}, 2, 3")
+
+
+def shr_tables(t):
+    """where the source record of the column's first SHR candidate lies (cell.hpp shr_small): the one lane-table read
+    whose table changes every step"""
+    t(f"ds_bpermute_b32 {E0}, {CIDX}, {O('tab')}")
+
+
+def pads(t):
+    """timing-only (--pad): what one more instruction of a kind costs per step.  The strings stay the product's:
+    valu / bperm write SHRV, SHRRUN, LENV, LENRUN only, scratch that every step writes (SHR pass, LEN pass) before it
+    reads it, so dead at a step's head; salu moves a scalar onto itself (no value and no scc changes, whatever is
+    live).  A padded build is valid only if scripts/ab_fill.py prints the product's hashes for it."""
+    for k in range(PAD["valu"]):
+        t(f"v_add_u32 {SHRV if k & 1 else SHRRUN}, 1, {SHRV if k & 1 else SHRRUN}")
+    for k in range(PAD["salu"]):
+        t(f"s_mov_b32 {O('sx')}, {O('sx')}")
+    for k in range(PAD["bperm"]):
+        t(f"ds_bpermute_b32 {LENV if k & 1 else LENRUN}, {O('laneid')}, {O('laneid')}")
 
 
 def shr_hist(t):
@@ -158,9 +198,9 @@ def del_part(t, mode, A, B, msk):
     """)
 
 
-def shr_pass(t, mid, sfx, smr, shadow, shadow2, none_test=True):
-    """SHR candidates of the column (cell.hpp shr_small<FAST>).  On entry: the first candidate's lane-table results in
-    E0 (address of its source record) / E1 (1/n) and the record itself in SD (matv), P0 (shrstart), P1 (runs).
+def shr_pass(t, mid, sfx, shadow, shadow2, none_test=True):
+    """SHR candidates of the column (cell.hpp shr_small<FAST>).  On entry: the column cache, and the first candidate's
+    source record in HS (matv), HP0 (shrstart), HP1 (runs).  Nothing here writes the cache: products go to E0 E1 SE.
     shadow(): work issued in the shadow of the score read (free registers X4 X5 SF); shadow2(): the same for the
     two-candidate block (free registers SHRV SHRRUN).  Leaves X3 = refx & seqw (shadow's last act) for the LEN test.
     The single-candidate case falls through; "no candidate in the wave" and "two candidates" are out of line."""
@@ -169,8 +209,8 @@ def shr_pass(t, mid, sfx, smr, shadow, shadow2, none_test=True):
     # holds the empty descriptor, whose score is +infinity
     if not mid and none_test:
         t(f"""
-            v_cmp_ne_u32 vcc, 0, {smr}
-            s_cbranch_vccz {L('shr_none' + sfx)}
+            s_cmp_eq_u64 {CNONE}, 0
+            s_cbranch_scc1 {L('shr_none' + sfx)}
         """)
         t.rare()
         t.label("shr_none" + sfx)
@@ -183,21 +223,18 @@ def shr_pass(t, mid, sfx, smr, shadow, shadow2, none_test=True):
         t(f"s_branch {L('shr_done2' + sfx)}")
         t.common()
     t(f"""
-        v_cmp_lt_u32 vcc, 28, {smr}
-        s_cbranch_vccnz {L('shr_two' + sfx)}
+        s_cmp_lg_u64 {CTWO}, 0
+        s_cbranch_scc1 {L('shr_two' + sfx)}
     """)
     # ---- one candidate per column
     t(f"""
-        v_cmp_gt_i32 vcc, 0, {O('rc0')}
         v_lshrrev_b32 {HP1}, 16, {HP1}
-        v_bfe_u32 {SE}, {O('rc0')}, 15, 16
-        v_cndmask_b32 {HP1}, {HP1}, 0, vcc
-        v_cndmask_b32 {HS}, {HP0}, {HS}, vcc
-        v_mul_u32_u24 {E1}, {HP1}, {E1}
-        v_bfe_u32 {E0}, {O('rc0')}, 2, 3
+        v_cndmask_b32 {HS}, {HP0}, {HS}, {CSF}
+        v_cndmask_b32 {HP1}, {HP1}, 0, {CSF}
+        v_mul_u32_u24 {E1}, {HP1}, {CRCP}
         v_min_u32_sdwa {E1}, {E1}, {O('rc0')} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:BYTE_1
-        v_add3_u32 {HP1}, {HP1}, {E0}, {O('tagS')}
-        v_lshl_add_u32 {SE}, {E1}, 2, {SE}
+        v_add3_u32 {HP1}, {HP1}, {CPER}, {O('tagS')}
+        v_lshl_add_u32 {SE}, {E1}, 2, {CBASE}
         ds_read_b32 {SE}, {SE}
     """)
     shadow()
@@ -218,17 +255,14 @@ def shr_pass(t, mid, sfx, smr, shadow, shadow2, none_test=True):
         v_and_b32 {X3}, 28, {O('rc1')}
         ds_bpermute_b32 {X4}, {X3}, {O('tab')}
         ds_bpermute_b32 {X5}, {X3}, {O('trecip')}
-        v_cmp_gt_i32 vcc, 0, {O('rc0')}
         v_cmp_gt_i32 {O('sa')}, 0, {O('rc1')}
         v_lshrrev_b32 {HP1}, 16, {HP1}
-        v_bfe_u32 {SE}, {O('rc0')}, 15, 16
-        v_cndmask_b32 {HP1}, {HP1}, 0, vcc
-        v_cndmask_b32 {HS}, {HP0}, {HS}, vcc
-        v_mul_u32_u24 {E1}, {HP1}, {E1}
-        v_bfe_u32 {E0}, {O('rc0')}, 2, 3
+        v_cndmask_b32 {HS}, {HP0}, {HS}, {CSF}
+        v_cndmask_b32 {HP1}, {HP1}, 0, {CSF}
+        v_mul_u32_u24 {E1}, {HP1}, {CRCP}
         v_min_u32_sdwa {E1}, {E1}, {O('rc0')} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:BYTE_1
-        v_add3_u32 {HP1}, {HP1}, {E0}, {O('tagS')}
-        v_lshl_add_u32 {E0}, {E1}, 2, {SE}
+        v_add3_u32 {HP1}, {HP1}, {CPER}, {O('tagS')}
+        v_lshl_add_u32 {E0}, {E1}, 2, {CBASE}
         s_waitcnt lgkmcnt(0)
         v_add_u32 {X4}, {O('hca')}, {X4}
         ds_read_b32 {E1}, {X4}
@@ -749,21 +783,23 @@ def gen_role(role):
     t(f"""
         v_cmp_ne_u32 vcc, 0, {SMR}
         s_cbranch_vccnz {L('exit')}
+    """)
+    # the column cache, once per entry (the wait: the first step may be a 'D' step, which reads 1/n into crcp again)
+    col_cache(t, mid, multi, SMR)
+    t(f"""
+        s_waitcnt lgkmcnt(0)
         s_branch {L('blk_setup')}
     """)
     # ================= 'I' step: read words move one column up, "left" is the previous lane.  The column
-    # descriptors do not move and INS reads this lane's own cell, so everything that does not depend on the neighbour
-    # waves -- the descriptor's summary bits, the lane-table reads, INS -- is done in front of the hand-shake poll.
+    # descriptors do not move, so nothing is derived from them here: the column cache holds it.  What does not depend
+    # on the neighbour waves -- the one lane-table read, INS (it reads this lane's own cell) -- is done in front of the
+    # hand-shake poll.
     t.label("mode_i")
-    # (summary bits of the band-interior columns only: the mask 0xbc comes per lane, zero in the lanes of the band's edge
-    # columns and beyond -- one instruction where a mask and a select used to be; a middle wave holds no such lanes)
-    t(f"v_and_b32 {SMR}, {'0xbc' if mid else O('livebc')}, {O('rc0')}")
+    pads(t)
     if multi:
         poll_issue(t, "I", first, last)
     book(t, "I")
-    # (every wave but the first: X0 ... X3 are waiting for the 'I' exchange record issued with the poll -- its read word
-    # lands in X3 -- so the scratch is SD; the first wave reads no 'I' record and X3 is free)
-    shr_tables(t, X3 if first else SD)
+    shr_tables(t)
     t(f"v_add_u32_sdwa {DRUN}, {O('LMr')}, {O('one')} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD")
     ins_part(t, "I", X4, X5, O("sb"), (f"v_mov_b32 {O('TMv')}, {MATV}", f"v_mov_b32 {O('TMr')}, {O('R1')}"))
     if first:
@@ -796,7 +832,7 @@ def gen_role(role):
         """)
     sub_read(t)
     t("s_waitcnt lgkmcnt(1)")          # the candidate's source record (the substitution score may still be on its way)
-    shr_pass(t, mid, "_I", SMR, lambda: del_part(t, "I", X4, X5, O("sb")), lambda: del_part(t, "I", SD, P0, O("sb")), multi)
+    shr_pass(t, mid, "_I", lambda: del_part(t, "I", X4, X5, O("sb")), lambda: del_part(t, "I", SD, P0, O("sb")), multi)
     len_pass(t, mid, "_I", "I", first, last, multi)
     tail(t, "I", first, last, multi)
     # ================= 'D' step: reference words (and the column descriptors) move one column down, "top" is the
@@ -806,6 +842,7 @@ def gen_role(role):
     # lane's cell is in its own registers too, and INS goes there as well; the other waves take the cell of the wave
     # above's first lane from the exchange record, behind the poll.
     t.label("mode_d")
+    pads(t)
     t(f"""
         v_readlane_b32 {O('sx')}, {O('rqz')}, {O('rqidx')}
         s_bitcmp1_b32 {O('sx')}, 7
@@ -834,9 +871,9 @@ def gen_role(role):
             v_mov_b32_dpp {O('rc1')}, {O('rc1')} wave_shl:1 row_mask:0xf bank_mask:0xf
             v_mov_b32 {O('TMr')}, {X2}
             s_add_i32 {O('rqidx')}, {O('rqidx')}, 1
-            v_and_b32 {SMR}, {O('livebc')}, {O('rc0')}
             v_writelane_b32 {O('rc1')}, {O('sx')}, 63
         """)
+        col_cache(t, mid, multi, SMR)
         shr_tables(t)
         ins_part(t, "D", X4, X5, O("sb"))
         if multi:
@@ -855,9 +892,9 @@ def gen_role(role):
             v_mov_b32_dpp {O('rc1')}, {O('rc1')} wave_shl:1 row_mask:0xf bank_mask:0xf
             v_writelane_b32 {O('rc0')}, {O('sx')}, 63
             v_readlane_b32 {O('sx')}, {O('rqx')}, {O('rqidx')}
-            v_and_b32 {SMR}, {'0xbc' if mid else O('livebc')}, {O('rc0')}
         """)
-        shr_tables(t, X4)
+        col_cache(t, mid, multi, SMR)
+        shr_tables(t)
         t(f"""
             v_writelane_b32 {O('refx')}, {O('sx')}, 63
             v_readlane_b32 {O('sx')}, {O('rqw')}, {O('rqidx')}
@@ -882,7 +919,7 @@ def gen_role(role):
         """)
         ins_part(t, "D", X4, X5, O("sb"))
         t("s_waitcnt lgkmcnt(1)")
-    shr_pass(t, mid, "_D", SMR, lambda: del_part(t, "D", X4, X5, O("sb")), lambda: del_part(t, "D", SD, P0, O("sb")), multi)
+    shr_pass(t, mid, "_D", lambda: del_part(t, "D", X4, X5, O("sb")), lambda: del_part(t, "D", SD, P0, O("sb")), multi)
     len_pass(t, mid, "_D", "D", first, last, multi)
     tail(t, "D", first, last, multi)
     t.lines = t.main
@@ -1074,6 +1111,8 @@ def operands(role):
     if last:
         outs += [("wfill", "+s", "a_wfill"), ("dlim", "+s", "a_dlim")]
     outs += [("sx", "=&s", "a_sx")]
+    outs += [("cidx", "=&v", "a_cidx"), ("crcp", "=&v", "a_crcp"), ("cbase", "=&v", "a_cbase"), ("cper", "=&v", "a_cper"),
+             ("csf", "=&s", "a_csf"), ("ctwo", "=&s", "a_ctwo"), ("cnone", "=&s", "a_cnone")]
     ins = [("stepsg", "s", "steps_g"), ("laneid", "v", "a_laneid"), ("b1", "s", "a_b1"), ("hw16", "s", "a_hw16"), ("ringb", "s", "ring_bytes"),
            ("tbs4", "s", "tbstride4"), ("n0", "s", "env.n0_lanes"), ("tbg", "s", "tb_g"), ("istart", "s", "a_istart"),
            ("iext", "s", "a_iext"), ("winaddr", "s", "a_winaddr"), ("wmask", "s", "a_wmask"), ("clampv", "s", "a_clampv"),
@@ -1103,10 +1142,13 @@ def main():
     here = os.path.dirname(os.path.abspath(__file__))
     out_path = os.path.join(here, "fill_step_asm.inc")
     args = sys.argv[1:]
-    while args:                      # timing-only ablations: --nopoll / --nolen, with --out FILE
+    while args:                      # timing-only variants: --nopoll / --nolen / --pad KIND:N, with --out FILE
         a = args.pop(0)
         if a in ("--nopoll", "--nolen"):
             ABLATE[a[2:]] = True
+        elif a == "--pad":               # timing-only: KIND:N, KIND in valu / salu / bperm
+            kind, n = args.pop(0).split(":")
+            PAD[kind] = int(n)
         elif a == "--out":
             out_path = args.pop(0)
     out = ["// fill_step_asm.inc -- GENERATED by gen_fill_asm.py (do not edit): the plain-step loop of fill_kernel as gfx950",

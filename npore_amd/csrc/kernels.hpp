@@ -890,6 +890,11 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
                 unsigned long long a_mask = stepmask, a_nmask = nextmask;
                 int a_kbase = 64 * ((a_bl >> 6) + 2) - 1;           // first step byte of the window after the next one, for lane 0
                 unsigned long long a_sa, a_sb, a_sc;
+                // the text's column cache (gen_fill_asm.py): what a step derives from rc0 alone, kept from one 'D' step to the
+                // next; built where the text is entered and dead where it is left
+                uint32_t a_cidx, a_crcp, a_cbase, a_cper;
+                unsigned long long a_csf, a_ctwo, a_cnone;
+                (void)a_cnone;
                 int a_wfill = uni(wfill);
                 int a_dlim = a_wfill - r - WIN_SLACK - 1;       // (the 'D' step that makes the L window refill)
                 const int bl_in = a_bl, sdel_in = a_sdel;

@@ -317,6 +317,15 @@ int npore_bam_format_sam(npore_bam *bam, const int64_t *idx, int64_t n, const ch
 int npore_bam_format_bam(npore_bam *bam, const int64_t *idx, int64_t n, const char *finals, const int64_t *final_off,
                          const int64_t *final_len, const int32_t *status, int threads, const uint8_t **recs,
                          int64_t *recs_len);
+/* ... as FULL records (NPORE_OUT_FULL), on the host: the reference and query codes are packed here (npore_bam_pack) for NM. */
+int npore_bam_format_bam_full(npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
+                              const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
+                              const uint8_t **recs, int64_t *recs_len);
+/* The device side of the FULL records on a caller's final CIGARs: the same inputs through the staging, the unpack, NM,
+ * placement and emit kernels; the records to recs[cap] (*recs_len bytes), the reads' NM counts to nm[n]. */
+int npore_debug_format_bam_full_device(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
+                                       int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len,
+                                       const int32_t *status, uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm);
 /* What the NEXT npore_bam_realign_file / _sequential / npore_bam_write_file on the handle appends to its out_path
  * (the setting holds for that one run): NPORE_OUT_SAM, the text, or NPORE_OUT_BAM, the records of npore_bam_format_bam in
  * BGZF members with STORED deflate blocks -- the record stream cut every 65 280 bytes counted from the run's first
@@ -344,6 +353,13 @@ int npore_bam_format_bam(npore_bam *bam, const int64_t *idx, int64_t n, const ch
  * parse -- wherever that block is smaller than the literals-only one; otherwise the member is the one NPORE_OUT_DEFLATE
  * alone writes.  The rule is csrc/deflate_code.hpp's; the device finds the matches too. */
 #define NPORE_OUT_MATCH 8
+/* flags, NPORE_OUT_BAM only, together with NPORE_OUT_EOF or NPORE_OUT_PART (the value 16 alone stays refused, as it was
+ * before the flag existed) and with any of the others: FULL records (`--records full`) -- the input record with only what the
+ * realignment changes replaced: its fixed fields (mates included), whole bases and qualities (clips included), the CIGAR as
+ * the input's clip words around the final CIGAR, the input's tags without NM MD cs de dv CG, and a recomputed NM (over the
+ * code arrays align() got: IUPAC letters other than N count as N); a long CIGAR's CG tag behind NM.  Built on the device in
+ * the default pipeline, by the host twin otherwise.  npore_bam_write_file has no reference: NPORE_E_UNSUPPORTED. */
+#define NPORE_OUT_FULL 16
 int npore_bam_set_output(npore_bam *bam, int format, const char *bai_path, int flags);
 /* Of the last BAM-mode run on the handle: out4[0] records written, [1] bytes of the record stream, [2] 1 = the index was
  * written, 0 = none was asked for, -1 = the records were not in coordinate order (no index), [3] size of the file. */

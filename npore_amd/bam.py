@@ -324,6 +324,112 @@ def bam_record(rd, final, references=None):
     return struct.pack("<i", len(body)) + body
 
 
+# ---- --records full: the pure-Python statement of csrc/bam_reader.hpp's FULL RECORD and csrc/nm_rec.hpp -------------
+STALE_TAGS = (b"NM", b"MD", b"cs", b"de", b"dv", b"CG")      # what a realignment invalidates
+
+
+def _aux_value_len(aux, q, typ):
+    """Bytes of the value of a tag of type `typ` whose value begins at aux[q]; None: it cannot be stepped over."""
+    if typ in b"cCA":
+        n = 1
+    elif typ in b"sS":
+        n = 2
+    elif typ in b"iIf":
+        n = 4
+    elif typ in b"ZH":
+        z = aux.find(b"\0", q)
+        if z < 0:
+            return None
+        n = z - q + 1
+    elif typ == b"B":
+        if q + 5 > len(aux):
+            return None
+        width = {b"c": 1, b"C": 1, b"s": 2, b"S": 2, b"i": 4, b"I": 4, b"f": 4}.get(aux[q:q + 1])
+        if width is None:
+            return None
+        n = 5 + struct.unpack_from("<I", aux, q + 1)[0] * width
+    else:
+        return None
+    return n if q + n <= len(aux) else None
+
+
+def filter_aux(aux):
+    """The tags a FULL record keeps of the input's aux bytes: all of them in input order but STALE_TAGS; a tag that cannot
+    be stepped over ends the list -- it and everything behind it are dropped."""
+    aux = bytes(aux)
+    out, q = [], 0
+    while q + 3 <= len(aux):
+        n = _aux_value_len(aux, q + 3, aux[q + 2:q + 3])
+        if n is None:
+            break
+        if aux[q:q + 2] not in STALE_TAGS:
+            out.append(aux[q:q + 3 + n])
+        q += 3 + n
+    return b"".join(out)
+
+
+def nm_of(ref_codes, seq_codes, final):
+    """NM of a final CIGAR text over the code arrays align() got ('NACGT-' -> 0 ... 5, anything else 0): the bases under I
+    and D, and the positions under M where the codes differ or either is 0 (a position beyond an array has code 0)."""
+    import re
+    nm = a = b = 0
+    for n, op in re.findall(r"(\d+)([MIDNSHP=X])", final):
+        n = int(n)
+        if op in "M=X":
+            for q in range(n):
+                rc = int(ref_codes[a + q]) if a + q < len(ref_codes) else 0
+                sc = int(seq_codes[b + q]) if b + q < len(seq_codes) else 0
+                nm += rc != sc or rc == 0 or sc == 0
+            a, b = a + n, b + n
+        elif op == "I":
+            nm, b = nm + n, b + n
+        elif op == "D":
+            nm, a = nm + n, a + n
+        elif op == "N":
+            a += n
+        elif op == "S":
+            b += n
+    return nm
+
+
+def full_record(raw, ref_codes, seq_codes, final):
+    """The FULL record (--records full, with its block_size word) of the input record `raw` (block_size word first) with
+    its final CIGAR: the statement npore_bam_format_bam_full and the device path are tested against."""
+    import re
+    raw = bytes(raw)
+    ref_id, pos, l_rn, mapq, _bin, n_cig, flag, l_seq, nref, npos, tlen = struct.unpack_from("<iiBBHHHiiii", raw, 4)
+    q = 36
+    name = raw[q:q + l_rn]
+    q += l_rn
+    cigar = [(c & 15, c >> 4) for c in struct.unpack_from(f"<{n_cig}I", raw, q)]
+    q += 4 * n_cig
+    body = raw[q:q + (l_seq + 1) // 2 + l_seq]            # bases and qualities as they lie
+    aux = raw[q + len(body):4 + struct.unpack_from("<i", raw, 0)[0]]
+    cigar = resolve_long_cigar(cigar, l_seq, ref_id, pos, aux)
+    reflen = sum(n for op, n in cigar if op in (0, 2, 3, 7, 8))
+    lead = []
+    if cigar and cigar[0][0] == 5:
+        lead.append(cigar[0])
+    if len(cigar) > len(lead) and cigar[len(lead)][0] == 4:
+        lead.append(cigar[len(lead)])
+    rest, trail = cigar[len(lead):], []
+    if rest and rest[-1][0] == 5:
+        trail.insert(0, rest.pop())
+    if rest and rest[-1][0] == 4:
+        trail.insert(0, rest.pop())
+    fin = [("MIDNSHP=X".index(op), int(n)) for n, op in re.findall(r"(\d+)([MIDNSHP=X])", final)]
+    words = b"".join(struct.pack("<I", (n << 4) | op) for op, n in lead + fin + trail)
+    nm = nm_of(ref_codes, seq_codes, final)
+    tags = filter_aux(aux) + b"NM" + (b"C" + struct.pack("<B", nm) if nm <= 0xFF else b"S" + struct.pack("<H", nm) if nm <= 0xFFFF
+                                      else b"I" + struct.pack("<I", nm))
+    if len(words) // 4 > MAX_CIGAR_OPS:
+        tags += b"CGBI" + struct.pack("<I", len(words) // 4) + words
+        words = struct.pack("<II", (l_seq << 4) | 4, (reflen << 4) | 3)
+    out = (struct.pack("<iiBBHHHiiii", ref_id, pos, l_rn, mapq, reg2bin(pos, pos + max(1, reflen)), len(words) // 4, flag, l_seq,
+                       nref, npos, tlen) + name + words + body + tags)
+    return struct.pack("<i", len(out)) + out
+
+
 def bgzf_stored(data):
     """`data` as BGZF members with stored deflate blocks, cut every BGZF_STORED_PAYLOAD bytes."""
     out = []
@@ -1048,7 +1154,25 @@ class NativeBam:
                                                    fl.ctypes.data, st.ctypes.data, threads, C.byref(recs), C.byref(recs_len)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def set_output(self, out_format="sam", bai=None, eof=True, compress="none"):
+    def format_bam_full(self, fasta, idx, finals, status, threads=0):
+        """FULL records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam_full)."""
+        import ctypes as C
+        idx = np.ascontiguousarray(idx, np.int64)
+        n = len(idx)
+        fb = [f.encode() for f in finals]
+        fo = np.zeros(n + 1, np.int64)
+        np.cumsum([len(f) for f in fb], out=fo[1:])
+        fl = np.diff(fo)
+        buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
+        st = np.ascontiguousarray(status, np.int32)
+        fmap = self.fasta_map(fasta)
+        recs, recs_len = C.c_void_p(), C.c_int64()
+        self._check(self._lib.npore_bam_format_bam_full(self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data,
+                                                        fo.ctypes.data, fl.ctypes.data, st.ctypes.data, threads, C.byref(recs),
+                                                        C.byref(recs_len)))
+        return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
+
+    def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference"):
         """What the NEXT realign_file / realign_sequential / write_file on this handle appends to its output path
         (npore_bam_set_output; the setting holds for that one run): "sam", or "bam" -- records in stored BGZF members behind
         what lies in the file (the header's members: create_bam_header) and `bai` written when the records went out in
@@ -1056,13 +1180,19 @@ class NativeBam:
         and `bai` is a sidecar whose offsets count from PART_BASE (dist.gather_bam_parts shifts and merges them).
         compress: "none", stored members, "huffman", every member one dynamic-Huffman block of literals, or "match", of
         literals and length / distance pairs where that is smaller
-        (NPORE_OUT_DEFLATE; "bam" only)."""
+        (NPORE_OUT_DEFLATE; "bam" only).  records: "reference", the reference's SAM line in binary, or "full", the input
+        record with only what the realignment changes replaced (NPORE_OUT_FULL; "bam" only)."""
         if compress not in ("none", "huffman", "match"):
             raise ValueError("compress must be 'none', 'huffman' or 'match'")
+        if records not in ("reference", "full"):
+            raise ValueError("records must be 'reference' or 'full'")
+        if records == "full" and out_format != "bam":
+            raise ValueError("records 'full' needs out_format 'bam'")
         if compress != "none" and out_format != "bam":
             raise ValueError("compress needs out_format 'bam'")
         flags = 0 if out_format != "bam" else 1 if eof else 2       # NPORE_OUT_EOF / NPORE_OUT_PART
         flags |= {"none": 0, "huffman": 4, "match": 12}[compress]  # NPORE_OUT_DEFLATE, NPORE_OUT_MATCH
+        flags |= 16 if records == "full" else 0                    # NPORE_OUT_FULL
         self._check(self._lib.npore_bam_set_output(self.handle, {"sam": 0, "bam": 1}[out_format], os.fsencode(bai) if bai else None, flags))
 
     def output_info(self):
@@ -1118,12 +1248,12 @@ class NativeBam:
 
     def realign_sequential(self, ctx, fasta, regions, out_path, batch_reads=4000, max_reads=0, r=30, max_b_rows=20000,
                            indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, out_format="sam", bai=None, eof=True,
-                           compress="none"):
+                           compress="none", records="reference"):
         """ONE PASS over the file: inflate, filter by `regions` [(contig, start, stop)] (at most one per contig, in header
         order), batch, realign, write -- npore_bam_realign_sequential.  Returns (reads selected, [(ordinal, status)] of
         the first bad reads, (refused, inconsistent)); raises OnePassUnsupported when the regions or the file's
         order rule the one-pass run out (the caller truncates the output and takes the indexed path).
-        out_format / bai / eof: set_output for this run ("bam": records instead of text)."""
+        out_format / bai / eof / compress / records: set_output for this run ("bam": records instead of text)."""
         ids = {n: i for i, n in enumerate(self.references)}
         rid = np.array([ids.get(c, -2) for c, _, _ in regions], np.int32)
         beg = np.array([s for _, s, _ in regions], np.int64)
@@ -1133,7 +1263,7 @@ class NativeBam:
         counts = np.zeros(3, np.int64)
         bad_ord, bad_st = np.zeros(max(bad_cap, 1), np.int64), np.zeros(max(bad_cap, 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress)
+        self.set_output(out_format, bai, eof, compress, records)
         rc = self._lib.npore_bam_realign_sequential(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, len(regions), rid.ctypes.data,
                                                     beg.ctypes.data, end.ctypes.data, int(max_reads or 0), int(batch_reads), indel_start,
                                                     indel_extend, max_b_rows, r, threads, os.fsencode(out_path), counts.ctypes.data,
@@ -1165,14 +1295,14 @@ class NativeBam:
         return (memoryview((C.c_char * sam_len.value).from_address(sam.value)) if sam_len.value else memoryview(b"")), st[:n]
 
     def realign_file(self, ctx, fasta, idx, out_sam, batch_reads=4000, r=30, max_b_rows=20000, indel_start=5.0,
-                     indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none"):
+                     indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none", records="reference"):
         """All selected reads, batch by batch, appended to out_sam by the library with packing, GPU work and
         formatting/writing of neighbouring batches overlapped.  Returns status[n].
-        out_format / bai / eof: set_output for this run ("bam": records instead of text)."""
+        out_format / bai / eof / compress / records: set_output for this run ("bam": records instead of text)."""
         idx = np.ascontiguousarray(idx, np.int64)
         st = np.zeros(max(len(idx), 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress)
+        self.set_output(out_format, bai, eof, compress, records)
         self._check(self._lib.npore_bam_realign_file(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data,
                                                      len(idx), int(batch_reads), indel_start, indel_extend, max_b_rows, r,
                                                      threads, os.fsencode(out_sam), st.ctypes.data))
@@ -1219,7 +1349,7 @@ class NativeBam:
 
 
 def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0, out_format="sam", bai=None,
-                   eof=True, compress="none"):
+                   eof=True, compress="none", records="reference"):
     """realign_reads() through the library; returns the number of reads handed in.  batch_reads > 0: the whole
     index list in overlapped batches written by the library itself; 0: one batch, text written here.
     threads: host threads of the parallel host stages (0 = all cores; one process per GPU: dist.host_threads_per_rank).
@@ -1230,7 +1360,8 @@ def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_
         return 0
     if batch_reads > 0:
         text, status = None, bam.realign_file(ctx, fasta, idx, out_sam, batch_reads=batch_reads, r=r, max_b_rows=max_b_rows,
-                                              threads=threads, out_format=out_format, bai=bai, eof=eof, compress=compress)
+                                              threads=threads, out_format=out_format, bai=bai, eof=eof, compress=compress,
+                                              records=records)
     else:
         text, status = bam.realign_batch(ctx, fasta, idx, r=r, max_b_rows=max_b_rows, threads=threads)
     bad = np.nonzero(status)[0]
@@ -1568,7 +1699,8 @@ def write_bam(path, references, records, level=6):
     name, flag, ref_id, pos, mapq, cigar [(op, len)], seq (str over =ACMGRSVTWYHKDBN), qual (bytes or None),
     hp (int or None); optional: tags (raw tag bytes written in front of HP), long_cigar (True: the CIGAR goes out as
     the placeholder <l_seq>S<reflen>N with the real words in a CG:B,I tag behind HP, as for every record of more than
-    65 535 operations; "i": the same with subtype i; "front": the CG tag in front of `tags` and HP)."""
+    65 535 operations; "i": the same with subtype i; "front": the CG tag in front of `tags` and HP), next_ref_id, next_pos,
+    tlen (the mate fields; -1, -1, 0 without)."""
     ref_len_of_op = (1, 0, 1, 1, 0, 0, 0, 1, 1)
     text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join(f"@SQ\tSN:{n}\tLN:{l}\n" for n, l in references)
     out = bytearray(b"BAM\1" + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", len(references)))
@@ -1591,7 +1723,7 @@ def write_bam(path, references, records, level=6):
             reflen = sum(ln * ref_len_of_op[op] for op, ln in r["cigar"])
             cig = struct.pack("<II", (len(seq) << 4) | 4, (reflen << 4) | 3)
         body = struct.pack("<iiBBHHHiiii", r["ref_id"], r["pos"], len(name), r.get("mapq", 60), 4680, len(cig) // 4,
-                           r["flag"], len(seq), -1, -1, 0) + name + cig + packed + qual + aux
+                           r["flag"], len(seq), r.get("next_ref_id", -1), r.get("next_pos", -1), r.get("tlen", 0)) + name + cig + packed + qual + aux
         out += struct.pack("<i", len(body)) + body
     with open(path, "wb") as fh:
         for p in range(0, len(out), 0xFF00):      # BGZF blocks of < 64 KiB

@@ -32,7 +32,7 @@ struct BamEmit {
     uint8_t *d_recs;             // the batch's record buffer
     int64_t cap;
     unsigned long long *d_cursor;
-    const int64_t *h_hp;         // [n_reads] page-locked: the reads' HP values
+    const int64_t *h_hp;         // [n_reads] page-locked: the reads' HP values (full: the bytes of kept aux in the staged heads)
     int64_t *h_rec_len;          // [n_reads] page-locked: bytes of every read's record (0: not written)
     unsigned long long *h_total; // page-locked: bytes of the batch's records
     // NPORE_OUT_DEFLATE (bam_deflate_kernels.hpp; deflate false: stored members, nothing more on the device): the three
@@ -41,6 +41,7 @@ struct BamEmit {
     DeflateParams dfl{};
     uint32_t *h_sizes = nullptr; // [dfl.max_members] page-locked
     int64_t *h_info = nullptr;   // [4] page-locked: DeflateParams::info
+    bool full = false;           // NPORE_OUT_FULL: FULL records (the heads staged with STAGE_FULL), NM counted on the device
 };
 
 struct npore_batch_slot;        // a batch of the BAM -> SAM pipeline (npore_api.cpp)
@@ -61,6 +62,7 @@ struct WorkSet {
     DevBuf in_raw;               // device pack (unpack_kernels.hpp): the group's record heads
     DevBuf coff;                 // compacted texts: where each read of the group begins in the batch's compact buffer
     DevBuf in_hp, rec_off, rec_len;   // BAM records built on the device: the group's HP values, its records' places and sizes
+    DevBuf nm;                        // ... FULL records: the group's NM counts
     HostBuf h_off;
     hipEvent_t evc[4] = {};      // H2D start / end, D2H start / end of a staged group
     bool staged = false;
@@ -82,7 +84,7 @@ struct WorkSet {
                                         &WorkSet::refl, &WorkSet::seql, &WorkSet::tb, &WorkSet::cout_, &WorkSet::clen, &WorkSet::cstat,
                                         &WorkSet::cnruns, &WorkSet::in_refs, &WorkSet::in_seqs, &WorkSet::in_cigs, &WorkSet::in_off,
                                         &WorkSet::out, &WorkSet::out_len, &WorkSet::status, &WorkSet::in_raw, &WorkSet::coff,
-                                        &WorkSet::in_hp, &WorkSet::rec_off, &WorkSet::rec_len};
+                                        &WorkSet::in_hp, &WorkSet::rec_off, &WorkSet::rec_len, &WorkSet::nm};
         for (auto m : all) (this->*m).match(o.*m);
     }
 };
@@ -389,6 +391,7 @@ int reserve_group(WorkSet *w, const GroupPlan &p, const AlignArgs &a)
     if (p.mode != OutMode::BamRecords) return NPORE_OK;
     for (DevBuf *b : {&w->in_hp, &w->rec_off, &w->rec_len})
         if (int rc = b->ensure(nr * 8 + 64)) return rc;
+    if (a.bam->full) return w->nm.ensure(nr * 4 + 64);
     return NPORE_OK;
 }
 
@@ -599,8 +602,15 @@ int post_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs &
         bp.read_base = out.read_base; bp.n_reads = nr;
         bp.recs = a.bam->d_recs; bp.cap = a.bam->cap; bp.cursor = a.bam->d_cursor;
         bp.rec_off = w->rec_off.as<int64_t>(); bp.rec_len = w->rec_len.as<int64_t>();
-        hipLaunchKernelGGL(place_bam_records_kernel, dim3(1), dim3(256), 0, s, bp);
-        hipLaunchKernelGGL(emit_bam_records_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
+        if (a.bam->full) {                    // FULL records: NM from the code arrays the standardisation probed, then the same two steps
+            bp.refs = sp.refs; bp.seqs = sp.seqs; bp.nm = w->nm.as<int32_t>();
+            hipLaunchKernelGGL(nm_count_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
+            hipLaunchKernelGGL(place_bam_full_kernel, dim3(1), dim3(256), 0, s, bp);
+            hipLaunchKernelGGL(emit_bam_full_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
+        } else {
+            hipLaunchKernelGGL(place_bam_records_kernel, dim3(1), dim3(256), 0, s, bp);
+            hipLaunchKernelGGL(emit_bam_records_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
+        }
         if (a.bam->deflate && p.g1 == a.n_reads) launch_deflate(a.bam->dfl, s);      // the batch's records are complete
     } else if (p.mode == OutMode::CompactText) {  // the texts to the front of the batch's compact buffer (unpack_kernels.hpp)
         if (p.g0 == 0) HIP_TRY(hipMemsetAsync(a.compact->d_cursor, 0, 8, s));

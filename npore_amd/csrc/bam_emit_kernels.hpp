@@ -13,6 +13,9 @@
 //                             soft clip on (an odd clip moves every nibble), the quality slice, the HP tag.
 // A final CIGAR of more than 65 535 operations goes out as htslib writes it (bam_reader.hpp RECORD): two placeholder words
 // in the CIGAR's place, the real words in a CG:B,I tag behind HP -- 16 bytes more, in both kernels.
+// FULL records (NPORE_OUT_FULL, bam_reader.hpp FULL RECORD) have three kernels of their own at the end of this file --
+// nm_count_kernel in front of the same two steps, place_bam_full_kernel and emit_bam_full_kernel --; the two above are
+// what they were.
 // The host then takes the batch's bytes as they lie (BgzfStoredWriter) and the records' lengths for its index.
 // Both run beside the next batch's fill kernel and keep to what the other light kernels keep to: at most
 // 64 vector registers; the placement's 2 KB of LDS are less than a fill workgroup leaves free, the assembly has none.
@@ -20,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "nm_rec.hpp"
 #include "unpack_kernels.hpp"
 
 namespace npore {
@@ -29,7 +33,7 @@ struct BamEmitParams {
     const int64_t *raw_off;        // [n_reads + 1]
     const int64_t *ref_off;        // [n_reads + 1]: reference length of read k = ref_off[k + 1] - ref_off[k]
     const int64_t *seq_off;        // [n_reads + 1]: bases without the soft clips
-    const int64_t *hp;             // [n_reads] the HP tag's value (0: none)
+    const int64_t *hp;             // [n_reads] the HP tag's value (0: none); FULL records: the bytes of kept aux behind the qualities
     const uint8_t *words;          // the slots: the final CIGAR as words (standardize_words_kernel)
     const int64_t *words_off;      // [reads of the target + 1]
     const int64_t *words_len;      // bytes of words per read (<= 0: none)
@@ -40,6 +44,9 @@ struct BamEmitParams {
     unsigned long long *cursor;    // bytes of it in use
     int64_t *rec_off;              // [n_reads] of this group: where the read's record begins
     int64_t *rec_len;              // [n_reads]: its bytes (0: the read is not written; -1: no room)
+    // FULL records only (nm_count_kernel): the group's code arrays, which ref_off / seq_off index, and the reads' NM
+    const uint8_t *refs = nullptr, *seqs = nullptr;
+    int32_t *nm = nullptr;         // [n_reads]
 };
 
 __device__ __forceinline__ int bam_hp_bytes(int64_t hp)
@@ -72,15 +79,18 @@ __device__ __forceinline__ int64_t bam_record_size(const BamEmitParams &p, int64
     return 36 + (int64_t)f[8] + wl + (sl + 1) / 2 + sl + 3 + bam_hp_bytes(p.hp[k]) + (bam_long_cigar(wl) ? 16 : 0);
 }
 
+__device__ __forceinline__ int64_t bam_full_record_size(const BamEmitParams &p, int64_t k);
+
 // one workgroup of 256: every thread sizes a contiguous share of the reads; their places follow from the sums of the shares
-__global__ __launch_bounds__(256) void place_bam_records_kernel(BamEmitParams p)
+template <bool FULL>
+__device__ __forceinline__ void place_records(const BamEmitParams &p)
 {
     __shared__ int64_t s_sum[257];
     const int t = threadIdx.x;
     const int64_t n = p.n_reads, seg = (n + 255) / 256;
     const int64_t k0 = min(n, t * seg), k1 = min(n, k0 + seg);
     int64_t mine = 0;
-    for (int64_t k = k0; k < k1; k++) mine += bam_record_size(p, k);
+    for (int64_t k = k0; k < k1; k++) mine += FULL ? bam_full_record_size(p, k) : bam_record_size(p, k);
     s_sum[t + 1] = mine;
     __syncthreads();
     if (t == 0) {
@@ -91,12 +101,14 @@ __global__ __launch_bounds__(256) void place_bam_records_kernel(BamEmitParams p)
     __syncthreads();
     int64_t at = s_sum[t];
     for (int64_t k = k0; k < k1; k++) {
-        const int64_t sz = bam_record_size(p, k);
+        const int64_t sz = FULL ? bam_full_record_size(p, k) : bam_record_size(p, k);
         p.rec_off[k] = at;
         p.rec_len[k] = at + sz <= p.cap ? sz : -1;
         at += sz;
     }
 }
+__global__ __launch_bounds__(256) void place_bam_records_kernel(BamEmitParams p) { place_records<false>(p); }
+__global__ __launch_bounds__(256) void place_bam_full_kernel(BamEmitParams p) { place_records<true>(p); }
 
 // dst[j] = src[j] (NIB == 0) or the bytes one nibble further on, src[j] << 4 | src[j + 1] >> 4 (NIB == 1), j in [0, n),
 // by the 64 lanes of a wavefront: four bytes per store where dst is aligned, each from two aligned words of the source;
@@ -204,6 +216,139 @@ __global__ __launch_bounds__(64) void emit_bam_records_kernel(BamEmitParams p)
         if (lane < 4) o[lane] = (uint8_t)"CGBI"[lane];
         else if (lane < 8) o[lane] = (uint8_t)((uint32_t)(wl >> 2) >> (8 * (lane - 4)));
         wave_copy<0>(o + 8, p.words + p.words_off[g], wl, false, lane);
+    }
+}
+
+// ---- FULL records (bam_reader.hpp FULL RECORD; host twin: bam_record_full_into) ------------------------------------------
+// The staged head carries the kept aux bytes behind the qualities (hostio.hpp STAGE_FULL; p.hp[k]: how many), so bases,
+// qualities and tags are ONE contiguous copy; the clip words come from the staged CIGAR; NM is counted by nm_count_kernel
+// between the standardisation and the placement.
+
+// NM (nm_rec.hpp) of every read of the group: one wavefront per read over tiles of 64 CIGAR words.  Lane l holds word l of
+// the tile; wave prefix sums of the reference and the query consumption give every word its two positions; I and D add
+// their lengths in their lanes; an M run is compared 64 positions per round, one ballot + popcount each.
+__global__ __launch_bounds__(64) void nm_count_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    const int64_t g = p.read_base + k;
+    const int64_t n = (p.status[g] & 32) || p.words_len[g] <= 0 ? 0 : p.words_len[g] >> 2;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(p.words + p.words_off[g]);      // (the slots lie at multiples of 4)
+    const uint8_t *ref = p.refs + p.ref_off[k], *seq = p.seqs + p.seq_off[k];
+    const int64_t rl = p.ref_off[k + 1] - p.ref_off[k], sl = p.seq_off[k + 1] - p.seq_off[k];
+    int64_t a0 = 0, b0 = 0;                  // consumed in front of the tile
+    uint32_t whole = 0, differ = 0;          // per lane: bases under I and D; the same in every lane: compared positions that count
+    for (int64_t t0 = 0; t0 < n; t0 += 64) {
+        const uint32_t v = t0 + lane < n ? w[t0 + lane] : 0u;       // (behind the end: `0M`)
+        const uint32_t op = v & 15u, len = v >> 4, use = nm_consumes(op);
+        if (nm_counts_whole(op)) whole += len;
+        const uint32_t ra = (use & 1u) ? len : 0u, qa = (use & 2u) ? len : 0u;
+        uint32_t ri = ra, qi = qa;           // inclusive sums over the tile (a read has fewer than 2^31 ops)
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t x = (uint32_t)__shfl_up((int)ri, d), y = (uint32_t)__shfl_up((int)qi, d);
+            if (lane >= d) { ri += x; qi += y; }
+        }
+        unsigned long long runs = __builtin_amdgcn_ballot_w64(nm_compares(op) && len > 0);
+        while (runs) {
+            const int j = (int)__builtin_ctzll(runs);
+            runs &= runs - 1;
+            const uint32_t lj = (uint32_t)__shfl((int)len, j);
+            const int64_t aj = a0 + (uint32_t)__shfl((int)(ri - ra), j), bj = b0 + (uint32_t)__shfl((int)(qi - qa), j);
+            for (uint32_t q0 = 0; q0 < lj; q0 += 64) {
+                const uint32_t q = q0 + (uint32_t)lane;
+                const bool d = q < lj && nm_differs(ref, rl, aj + q, seq, sl, bj + q);
+                differ += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(d));
+            }
+        }
+        a0 += (uint32_t)__shfl((int)ri, 63);
+        b0 += (uint32_t)__shfl((int)qi, 63);
+    }
+    for (int d = 32; d; d >>= 1) whole += (uint32_t)__shfl_xor((int)whole, d);
+    if (lane == 0) p.nm[k] = (int32_t)(whole + differ);
+}
+
+// what both FULL kernels need of read k: the clip words [0, ci) and [cj, nc) of the staged CIGAR (bam_reader.hpp
+// full_clip_words), the sizes of the parts, the record's size (0: not written)
+struct BamFullShape {
+    const uint8_t *f, *cg, *sq;
+    int nc, ci, cj, nmb;
+    bool lng;
+    int64_t wl, n_cig, l_seq, aux, size;
+};
+__device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, int64_t k)
+{
+    BamFullShape s;
+    const int64_t g = p.read_base + k;
+    s.f = p.raw + p.raw_off[k] + 4;
+    staged_cigar(s.f, s.cg, s.nc, s.sq);
+    auto op_of = [&](int c) { return ld32(s.cg + 4 * (size_t)c) & 15u; };
+    s.ci = 0;
+    s.cj = s.nc;
+    if (s.ci < s.cj && op_of(s.ci) == 5) s.ci++;
+    if (s.ci < s.cj && op_of(s.ci) == 4) s.ci++;
+    if (s.cj > s.ci && op_of(s.cj - 1) == 5) s.cj--;
+    if (s.cj > s.ci && op_of(s.cj - 1) == 4) s.cj--;
+    s.wl = p.words_len[g] > 0 ? p.words_len[g] : 0;
+    s.n_cig = s.ci + (s.wl >> 2) + (s.nc - s.cj);
+    s.lng = s.n_cig > 0xFFFF;
+    s.l_seq = (int32_t)ld32(s.f + 16);
+    s.aux = p.hp[k];
+    const uint32_t nm = (uint32_t)p.nm[k];
+    s.nmb = nm <= 0xFFu ? 1 : nm <= 0xFFFFu ? 2 : 4;
+    s.size = (p.status[g] & 32) ? 0
+                                : 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb +
+                                      (s.lng ? 8 + 4 * s.n_cig : 0);
+    return s;
+}
+__device__ __forceinline__ int64_t bam_full_record_size(const BamEmitParams &p, int64_t k) { return bam_full_shape(p, k).size; }
+
+// one wavefront per read
+__global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    const int64_t size = p.rec_len[k];
+    if (size <= 0) return;
+    const int64_t g = p.read_base + k;
+    const BamFullShape s = bam_full_shape(p, k);
+    const uint8_t *f = s.f;
+    const int32_t pos = (int32_t)ld32(f + 4);
+    const int l_rn = f[8];
+    const int64_t reflen = p.ref_off[k + 1] - p.ref_off[k], body = (s.l_seq + 1) / 2 + s.l_seq + s.aux;
+    auto put32 = [](uint8_t *q, uint32_t w) { q[0] = (uint8_t)w; q[1] = (uint8_t)(w >> 8); q[2] = (uint8_t)(w >> 16); q[3] = (uint8_t)(w >> 24); };
+    uint8_t *o = p.recs + p.rec_off[k];
+    if (lane < 9) {                                              // block_size and the fixed fields, a word per lane: the input's but bin and n_cigar_op
+        uint32_t w = ld32(f + 4 * (lane > 0 ? lane - 1 : 0));
+        if (lane == 0) w = (uint32_t)(size - 4);
+        if (lane == 3) w = (uint32_t)l_rn | (uint32_t)f[9] << 8 | bam_reg2bin_dev(pos, (int64_t)pos + max((int64_t)1, reflen)) << 16;
+        if (lane == 4) w = (s.lng ? 2u : (uint32_t)s.n_cig) | ld16(f + 14) << 16;
+        put32(o + 4 * lane, w);
+    }
+    o += 36;
+    for (int j = lane; j < l_rn; j += 64) o[j] = f[32 + j];
+    o += l_rn;
+    uint8_t *cw = o;                                             // where the CIGAR words go
+    if (s.lng) {                                                 // the placeholder here, CG:B,I behind NM
+        cw = o + 8 + body + 3 + s.nmb + 8;
+        if (lane < 2) put32(o + 4 * lane, lane == 0 ? ((uint32_t)s.l_seq << 4 | 4u) : ((uint32_t)reflen << 4 | 3u));
+        if (lane >= 4 && lane < 8) cw[lane - 12] = (uint8_t)"CGBI"[lane - 4];
+        if (lane >= 8 && lane < 12) cw[lane - 12] = (uint8_t)((uint32_t)s.n_cig >> (8 * (lane - 8)));
+        o += 8;
+    } else {
+        o += 4 * s.n_cig;
+    }
+    wave_copy<0>(cw, s.cg, 4 * (int64_t)s.ci, false, lane);
+    wave_copy<0>(cw + 4 * s.ci, p.words + p.words_off[g], s.wl, false, lane);
+    wave_copy<0>(cw + 4 * s.ci + s.wl, s.cg + 4 * (int64_t)s.cj, 4 * (int64_t)(s.nc - s.cj), false, lane);
+    wave_copy<0>(o, s.sq, body, false, lane);                    // bases, qualities, kept aux: as they lie in the staged head
+    o += body;
+    if (lane == 0) {
+        const uint32_t nm = (uint32_t)p.nm[k];
+        o[0] = 'N'; o[1] = 'M';
+        o[2] = (uint8_t)(s.nmb == 1 ? 'C' : s.nmb == 2 ? 'S' : 'I');
+        for (int q = 0; q < s.nmb; q++) o[3 + q] = (uint8_t)(nm >> (8 * q));
     }
 }
 

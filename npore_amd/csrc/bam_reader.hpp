@@ -7,6 +7,7 @@
 #include "../../include/npore_amd.h"
 #include "hostio.hpp"
 #include "deflate_code.hpp"
+#include "nm_rec.hpp"
 
 #include <sys/uio.h>
 
@@ -643,6 +644,22 @@ inline int format_sam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
 //     BEHIND HP carries the words: 'C' 'G' 'B' 'I', the 32-bit count n, the n words.  Size: 36 + l_read_name + 8 +
 //     (l_seq + 1) / 2 + l_seq + 3 + {1, 2, 4} + 8 + 4 * n.  bin, tlen and the index entry come from the real reference
 //     length as always.  (The input side of the same rule: hostio.hpp rec_cigar.)
+// FULL RECORD (NPORE_OUT_FULL, `--records full`; RECORD above stays the default and its bytes do not change).  The input
+//   record with only what the realignment changes replaced:
+//   - refID, pos, mapq, flag, the name, l_seq, next_refID, next_pos and tlen are the input's; bin as above;
+//   - the 4-bit bases and the qualities are the input's, whole: clips included, no nibble moves, copied verbatim (a
+//     leading 0xFF included);
+//   - the CIGAR is the input's leading clip words, the final standardised CIGAR, the input's trailing clip words, not
+//     merged.  The clip words are those of the record's real CIGAR (rec_cigar).  Lead: word 0 if it is H, then the next
+//     word if it is S; trail: the mirror image at the end, over the words the lead left (full_clip_words) -- rec_clips'
+//     recognition plus the H words it steps over; an H with no S beside it is kept too;
+//   - the tags are the input's aux bytes in input order minus NM MD cs de dv CG (hostio.hpp filter_aux); HP stays where
+//     and as it was, none is made when the input has none;
+//   - a recomputed NM (nm_rec.hpp) follows them as the smallest unsigned type: C, S, I (bam_hp_tag_bytes);
+//   - more than 65 535 operations, clips included: the CIGAR field holds the placeholder `l_seq << 4 | 4`,
+//     `reflen << 4 | 3` with the full l_seq, and CG:B,I with ALL the words goes behind NM.
+//   Size: 36 + l_read_name + 4 * n_cigar (8 when long) + (l_seq + 1) / 2 + l_seq + kept aux + 3 + {1, 2, 4} (+ 8 + 4 * n
+//   when long).
 // FILE.  BGZF with STORED deflate members (level 0, what `samtools view -u` writes): 18 bytes of gzip header with the BC
 //   field, one stored block (01 LEN NLEN), the payload, CRC-32 and ISIZE -- payload + 31 bytes.  The header (text +
 //   reference list) lies in members of its own; the record stream is cut every 65 280 payload bytes counted from the
@@ -754,18 +771,123 @@ inline int64_t bam_record_into(const RecView &r, const char *final_text, int64_t
     return size;
 }
 
+// FULL RECORD's clip words of a real CIGAR: the lead is words [0, i), the trail words [j, n)
+inline void full_clip_words(const RecCigar &cg, uint32_t &i, uint32_t &j)
+{
+    i = 0;
+    j = cg.n;
+    if (i < j && (cg.op(i) & 15u) == 5) i++;
+    if (i < j && (cg.op(i) & 15u) == 4) i++;
+    if (j > i && (cg.op(j - 1) & 15u) == 5) j--;
+    if (j > i && (cg.op(j - 1) & 15u) == 4) j--;
+}
+inline uint32_t cigar_op_code(char c)
+{
+    return c == 'M' ? 0 : c == 'I' ? 1 : c == 'D' ? 2 : c == 'N' ? 3 : c == 'S' ? 4 : c == 'H' ? 5 : c == 'P' ? 6 : c == '=' ? 7 : 8;
+}
+// NM (nm_rec.hpp) of a final CIGAR text over the read's code arrays; -1: no CIGAR text
+inline int64_t nm_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl)
+{
+    const int64_t ops = cigar_text_ops(t, n);
+    if (ops < 0) return -1;
+    std::vector<uint8_t> words((size_t)ops * 4 + 4);
+    uint32_t len = 0;
+    uint8_t *o = words.data();
+    for (int64_t q = 0; q < n; q++) {
+        if (t[q] >= '0' && t[q] <= '9') { len = len * 10 + (uint32_t)(t[q] - '0'); continue; }
+        const uint32_t w = len << 4 | cigar_op_code(t[q]);
+        std::memcpy(o, &w, 4);
+        o += 4;
+        len = 0;
+    }
+    return nm_of_words(words.data(), ops, ref, rl, seq, sl);
+}
+// bam_record_into's twin for the FULL RECORD; nm: the read's NM (nm_of_text)
+inline int64_t bam_record_full_into(const RecView &r, const char *final_text, int64_t final_len, int32_t status, int64_t nm, uint8_t *dst,
+                                    BamRecMeta *meta = nullptr)
+{
+    if (status & NPORE_ST_BAD_INPUT) return 0;
+    const RecCigar in_cg = rec_cigar(r);
+    const int64_t n_fin = cigar_text_ops(final_text, final_len);
+    if (n_fin < 0 || nm < 0) return -1;
+    uint32_t ci, cj;
+    full_clip_words(in_cg, ci, cj);
+    const int64_t n_cig = (int64_t)ci + n_fin + (int64_t)(in_cg.n - cj);
+    const bool lng = n_cig > 0xFFFF;
+    const int64_t l_seq = r.l_seq(), nb = (l_seq + 1) / 2, aux = filter_aux(r.aux(), r.end(), nullptr);
+    const int l_rn = r.l_read_name(), nmb = bam_hp_tag_bytes(nm);
+    const int64_t size = 36 + l_rn + (lng ? 8 : 4 * n_cig) + nb + l_seq + aux + 3 + nmb + (lng ? 8 + 4 * n_cig : 0);
+    if (!dst) return size;
+    const int64_t reflen = rec_ref_len(in_cg);
+    auto w32 = [](uint8_t *o, uint32_t v) { std::memcpy(o, &v, 4); };
+    auto w16 = [](uint8_t *o, uint16_t v) { std::memcpy(o, &v, 2); };
+    uint8_t *o = dst;
+    w32(o, (uint32_t)(size - 4));
+    std::memcpy(o + 4, r.p, 32);                     // the input's fixed fields; bin and n_cigar_op are this record's
+    w16(o + 14, (uint16_t)bam_reg2bin(r.pos(), (int64_t)r.pos() + std::max<int64_t>(1, reflen)));
+    w16(o + 16, (uint16_t)(lng ? 2 : n_cig));
+    o += 36;
+    std::memcpy(o, r.name(), (size_t)l_rn);
+    o += l_rn;
+    uint8_t *const seq_at = lng ? o + 8 : o + 4 * n_cig;
+    if (lng) {                                       // the words go behind NM
+        w32(o, (uint32_t)l_seq << 4 | 4u);
+        w32(o + 4, (uint32_t)reflen << 4 | 3u);
+        o = seq_at + nb + l_seq + aux + 3 + nmb;
+        std::memcpy(o, "CGBI", 4);
+        w32(o + 4, (uint32_t)n_cig);
+        o += 8;
+    }
+    std::memcpy(o, in_cg.w, 4 * (size_t)ci);
+    o += 4 * (size_t)ci;
+    {
+        uint32_t len = 0;
+        for (int64_t q = 0; q < final_len; q++) {
+            const char c = final_text[q];
+            if (c >= '0' && c <= '9') { len = len * 10 + (uint32_t)(c - '0'); continue; }
+            w32(o, len << 4 | cigar_op_code(c));
+            o += 4;
+            len = 0;
+        }
+    }
+    std::memcpy(o, in_cg.w + 4 * (size_t)cj, 4 * (size_t)(in_cg.n - cj));
+    o = seq_at;
+    std::memcpy(o, r.seq(), (size_t)(nb + l_seq));
+    o += nb + l_seq;
+    filter_aux(r.aux(), r.end(), o);
+    o += aux;
+    o[0] = 'N'; o[1] = 'M';
+    o[2] = (uint8_t)(nmb == 1 ? 'C' : nmb == 2 ? 'S' : 'I');
+    { const uint32_t v = (uint32_t)nm; std::memcpy(o + 3, &v, (size_t)nmb); }
+    if (meta) *meta = BamRecMeta{r.ref_id(), r.pos(), reflen, size};
+    return size;
+}
+// the code arrays of a batch's reads (what align() got): FULL records count NM from them
+struct ReadCodes {
+    const uint8_t *refs; const int64_t *ref_off;
+    const uint8_t *seqs; const int64_t *seq_off;
+};
+
 // format_sam_into's twin for BAM records: the kept reads' records one after the other in `out`, *out_len bytes;
 // meta (may be null): one entry per WRITTEN record, in order
 inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, const char *finals, const int64_t *final_off,
                            const int64_t *final_len, const int32_t *status, int threads, RawBuf &out, int64_t *out_len,
-                           std::vector<BamRecMeta> *meta)
+                           std::vector<BamRecMeta> *meta, const ReadCodes *full = nullptr)
 {
     if (!b || n < 0 || !out_len || (n > 0 && (!finals || !final_off || !final_len || !status)))
         return fail(NPORE_E_INVALID, "bad argument");
-    std::vector<int64_t> off((size_t)n + 1, 0);
+    std::vector<int64_t> off((size_t)n + 1, 0), nm(full ? (size_t)n : 0, 0);
     std::atomic<int> bad{0};
+    // (full: the FULL RECORD, its NM counted once, between the two passes)
+    auto record = [&](int64_t k, uint8_t *dst, BamRecMeta *m) {
+        return full ? bam_record_full_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], nm[(size_t)k], dst, m)
+                    : bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], dst, m);
+    };
     parallel_for(n, threads, [&](int64_t k) {
-        const int64_t sz = bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], nullptr);
+        if (full && !(status[k] & NPORE_ST_BAD_INPUT))
+            nm[(size_t)k] = nm_of_text(finals + final_off[k], final_len[k], full->refs + full->ref_off[k], full->ref_off[k + 1] - full->ref_off[k],
+                                       full->seqs + full->seq_off[k], full->seq_off[k + 1] - full->seq_off[k]);
+        const int64_t sz = record(k, nullptr, nullptr);
         if (sz < 0) bad++;
         off[(size_t)k + 1] = std::max<int64_t>(sz, 0);
     });
@@ -776,8 +898,7 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     if (meta) all.resize((size_t)n);
     parallel_for(n, threads, [&](int64_t k) {
         if (off[(size_t)k + 1] > off[(size_t)k])
-            bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], reinterpret_cast<uint8_t *>(out.p) + off[(size_t)k],
-                            meta ? &all[(size_t)k] : nullptr);
+            record(k, reinterpret_cast<uint8_t *>(out.p) + off[(size_t)k], meta ? &all[(size_t)k] : nullptr);
     });
     if (meta) {
         meta->clear();

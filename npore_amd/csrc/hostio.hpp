@@ -743,34 +743,65 @@ inline void rec_clips(const RecCigar &cg, int64_t &lead, int64_t &trail)
 }
 inline void rec_clips(const RecView &r, int64_t &lead, int64_t &trail) { rec_clips(rec_cigar(r), lead, trail); }
 
+// ---- the tags a FULL record keeps (bam_reader.hpp FULL RECORD) ----------------------------------------------------------
+// The input's aux bytes [q, end) in input order without the tags the realignment makes stale -- NM MD cs de dv CG, by
+// their case-sensitive two-letter names -- copied to dst (nullptr: only counted); returns their bytes.  A tag that
+// cannot be stepped over (aux_value_bytes returns 0) ends the list: it and everything behind it are dropped (rec_cigar's
+// rule), and so are fewer than three bytes behind the last tag.
+inline bool aux_tag_is_stale(const uint8_t *q)
+{
+    static const char stale[6][3] = {"NM", "MD", "cs", "de", "dv", "CG"};
+    for (const char *t : stale)
+        if (q[0] == (uint8_t)t[0] && q[1] == (uint8_t)t[1]) return true;
+    return false;
+}
+inline int64_t filter_aux(const uint8_t *q, const uint8_t *end, uint8_t *dst)
+{
+    int64_t n = 0;
+    while (q + 3 <= end) {
+        const size_t w = aux_value_bytes(q + 3, end, (char)q[2]);
+        if (!w) break;
+        if (!aux_tag_is_stale(q)) {
+            if (dst) std::memcpy(dst + n, q, 3 + w);
+            n += (int64_t)(3 + w);
+        }
+        q += 3 + w;
+    }
+    return n;
+}
+
 // ---- staged heads: what the device gets of a record ------------------------------------------------------------------
 // The kernels that read records (unpack, BAM emit, recount, purity) get each record's HEAD as it lies in the BAM stream
-// -- block_size word | 32 bytes of fixed fields | name | CIGAR words | 4-bit bases | (with_quals) qualities -- with ONE
+// -- block_size word | 32 bytes of fixed fields | name | CIGAR words | 4-bit bases | (STAGE_QUALS on) qualities |
+// (STAGE_FULL) the kept aux bytes (filter_aux: the filter runs here, the device never parses tags) -- with ONE
 // difference: the CIGAR words are the record's real ones (rec_cigar: those of the CG tag for a long-CIGAR record, in the
 // place of the placeholder), and their count is 32-bit: its low half in the n_cigar_op field, its high half in the `bin`
 // field, which no kernel reads (the emit kernel recomputes the bin).  stage_record_head() writes both halves for every
 // record; staged_cigar() (staged_head.hpp) is the one reader, on the device and on the host.
-inline int64_t staged_head_bytes(const RecView &r, const RecCigar &cg, bool with_quals)
+enum : int { STAGE_HEAD = 0, STAGE_QUALS = 1, STAGE_FULL = 2 };      // (0 / 1: what `bool with_quals` used to say)
+inline int64_t staged_head_bytes(const RecView &r, const RecCigar &cg, int form)
 {
-    return 4 + 32 + (int64_t)r.l_read_name() + 4 * (int64_t)cg.n + (int64_t)((with_quals ? r.aux() : r.qual()) - r.seq());
+    return 4 + 32 + (int64_t)r.l_read_name() + 4 * (int64_t)cg.n + (int64_t)((form != STAGE_HEAD ? r.aux() : r.qual()) - r.seq()) +
+           (form == STAGE_FULL ? filter_aux(r.aux(), r.end(), nullptr) : 0);
 }
-inline int64_t staged_head_bytes(const uint8_t *rec, bool with_quals)
+inline int64_t staged_head_bytes(const uint8_t *rec, int form)
 {
     const RecView r = rec_view(rec);
-    return staged_head_bytes(r, rec_cigar(r), with_quals);
+    return staged_head_bytes(r, rec_cigar(r), form);
 }
-// rec: the record, block_size word first; dst: staged_head_bytes(rec, with_quals) bytes
-inline void stage_record_head(const uint8_t *rec, bool with_quals, uint8_t *dst)
+// rec: the record, block_size word first; dst: staged_head_bytes(rec, form) bytes
+inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst)
 {
     const RecView r = rec_view(rec);
     const RecCigar cg = rec_cigar(r);
-    const size_t fixed = 4 + 32 + (size_t)r.l_read_name(), tail = (size_t)((with_quals ? r.aux() : r.qual()) - r.seq());
+    const size_t fixed = 4 + 32 + (size_t)r.l_read_name(), tail = (size_t)((form != STAGE_HEAD ? r.aux() : r.qual()) - r.seq());
     if (cg.w == r.cigar()) std::memcpy(dst, rec, fixed + 4 * (size_t)cg.n + tail);
     else {
         std::memcpy(dst, rec, fixed);
         std::memcpy(dst + fixed, cg.w, 4 * (size_t)cg.n);
         std::memcpy(dst + fixed + 4 * (size_t)cg.n, r.seq(), tail);
     }
+    if (form == STAGE_FULL) filter_aux(r.aux(), r.end(), dst + fixed + 4 * (size_t)cg.n + tail);
     dst[4 + 10] = (uint8_t)(cg.n >> 16); dst[4 + 11] = (uint8_t)(cg.n >> 24);      // bin: the count's high half
     dst[4 + 12] = (uint8_t)cg.n; dst[4 + 13] = (uint8_t)(cg.n >> 8);
 }

@@ -1496,10 +1496,154 @@ try {
 }
 NPORE_CATCH_INT
 
+namespace {
+// the code arrays align() would get of the fetched records (pack_records), for the FULL records' NM
+struct PackedCodes {
+    std::vector<int64_t> ro, so, co;
+    std::vector<uint8_t> refs, seqs;
+    std::vector<char> cigs;
+    int pack(const npore_bam *b, const RecFetch &rf, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n, int threads)
+    {
+        for (auto *v : {&ro, &so, &co}) v->assign((size_t)n + 1, 0);
+        pack_sizes_of(rf, n, ro.data(), so.data(), co.data(), threads);
+        refs.resize((size_t)ro[(size_t)n] + 64); seqs.resize((size_t)so[(size_t)n] + 64); cigs.resize((size_t)co[(size_t)n] + 64);
+        return pack_records(b, rf, fa, fasta_of_ref, n, refs.data(), ro.data(), seqs.data(), so.data(), cigs.data(), co.data(), threads);
+    }
+};
+}  // namespace
+
+int npore_bam_format_bam_full(npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
+                              const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
+                              const uint8_t **recs, int64_t *recs_len)
+try {
+    if (!pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs) return fail(NPORE_E_INVALID, "bad argument");
+    if (int rc = fetch_records(b, idx, n, threads, b->api_fetch)) return rc;
+    PackedCodes pc;
+    if (int rc = pc.pack(b, b->api_fetch, fa, fasta_of_ref, n, threads)) return rc;
+    const ReadCodes codes{pc.refs.data(), pc.ro.data(), pc.seqs.data(), pc.so.data()};
+    const int rc = format_bam_into(b, b->api_fetch, n, finals, final_off, final_len, status, threads, b->recs, recs_len, nullptr, &codes);
+    *recs = reinterpret_cast<const uint8_t *>(b->recs.p);
+    return rc;
+}
+NPORE_CATCH_INT
+
+// The device side of the FULL records on a caller's final CIGARs: the inputs of npore_bam_format_bam_full through the
+// staging (STAGE_FULL), unpack_records_kernel, nm_count_kernel, place_bam_full_kernel and emit_bam_full_kernel, and back
+int npore_debug_format_bam_full_device(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
+                                       int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status,
+                                       uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm)
+try {
+    if (!ctx || !pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs_len || cap < 0 || (cap > 0 && !recs) ||
+        (n > 0 && (!finals || !final_off || !final_len || !status || !nm)))
+        return fail(NPORE_E_INVALID, "bad argument");
+    *recs_len = 0;
+    if (n == 0) return NPORE_OK;
+    if (int rc = quiesce(ctx)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (int rc = device_fasta(ctx, b, fa, fasta_of_ref)) return rc;
+    RecFetch &rf = b->api_fetch;
+    if (int rc = fetch_records(b, idx, n, 0, rf)) return rc;
+    // host side: sizes, staged heads, the finals as words in slots at multiples of 4
+    const size_t N = (size_t)n;
+    std::vector<int64_t> off(5 * (N + 1), 0), aux(N, 0), wlen(N, 0);       // ref, seq, cig, words, raw offsets
+    int64_t *ro = off.data(), *so = ro + (N + 1), *co = so + (N + 1), *wo = co + (N + 1), *rawo = wo + (N + 1);
+    pack_sizes_of(rf, n, ro, so, co, 0);
+    int64_t bound = 0;
+    for (size_t k = 0; k < N; k++) {
+        const RecView r = rec_of(rf, (int64_t)k);
+        const int32_t rid = r.ref_id();
+        if (rid < 0 || rid >= (int32_t)b->ref_names.size() || fasta_of_ref[rid] < 0 || fasta_of_ref[rid] >= (int)fa->names.size())
+            return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
+        const int64_t ops = (status[k] & NPORE_ST_BAD_INPUT) ? 0 : cigar_text_ops(finals + final_off[k], final_len[k]);
+        if (ops < 0) return fail(NPORE_E_UNSUPPORTED, "a final CIGAR is no CIGAR text (BAM output)");
+        aux[k] = filter_aux(r.aux(), r.end(), nullptr);
+        wlen[k] = 4 * ops;
+        wo[k + 1] = wo[k] + 4 * ops + 16;
+        rawo[k + 1] = rawo[k] + ((staged_head_bytes(rf.ptr[k], STAGE_FULL) + 7) & ~7ll);
+        bound += 36 + r.l_read_name() + 4 * ops + 32 + ((int64_t)r.l_seq() + 1) / 2 + r.l_seq() + aux[k] + 7 + 16;
+    }
+    std::vector<uint8_t> raw((size_t)rawo[N] + 64, 0), words((size_t)wo[N] + 64, 0);
+    for (size_t k = 0; k < N; k++) {
+        stage_record_head(rf.ptr[k], STAGE_FULL, raw.data() + rawo[k]);
+        if (status[k] & NPORE_ST_BAD_INPUT) continue;
+        uint32_t len = 0;
+        uint8_t *o = words.data() + wo[k];
+        for (int64_t q = 0; q < final_len[k]; q++) {
+            const char c = finals[final_off[k] + q];
+            if (c >= '0' && c <= '9') { len = len * 10 + (uint32_t)(c - '0'); continue; }
+            const uint32_t w = len << 4 | cigar_op_code(c);
+            std::memcpy(o, &w, 4);
+            o += 4;
+            len = 0;
+        }
+    }
+    DevBuf d_raw, d_off, d_words, d_wlen, d_aux, d_status, d_refs, d_seqs, d_cigs, d_recs, d_cursor, d_rec_off, d_rec_len, d_nm;
+    if (int rc = d_raw.ensure(raw.size())) return rc;
+    if (int rc = d_off.ensure(off.size() * 8)) return rc;
+    if (int rc = d_words.ensure(words.size())) return rc;
+    if (int rc = d_refs.ensure((size_t)ro[N] + 64)) return rc;
+    if (int rc = d_seqs.ensure((size_t)so[N] + 64)) return rc;
+    if (int rc = d_cigs.ensure((size_t)co[N] + 64)) return rc;
+    if (int rc = d_recs.ensure((size_t)bound + 64)) return rc;
+    if (int rc = d_cursor.ensure(64)) return rc;
+    if (int rc = d_status.ensure(N * 4 + 64)) return rc;
+    if (int rc = d_nm.ensure(N * 4 + 64)) return rc;
+    for (DevBuf *d : {&d_wlen, &d_aux, &d_rec_off, &d_rec_len})
+        if (int rc = d->ensure(N * 8 + 64)) return rc;
+    HIP_TRY(hipMemcpy(d_raw.p, raw.data(), raw.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_words.p, words.data(), words.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_wlen.p, wlen.data(), N * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aux.p, aux.data(), N * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_status.p, status, N * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_cursor.p, 0, 8));
+    const int64_t *o64 = d_off.as<int64_t>();
+    hipStream_t st = ctx->s_post;
+    UnpackParams up;
+    up.raw = d_raw.as<uint8_t>(); up.raw_off = o64 + 4 * (n + 1);
+    up.ctg = ctx->d_ctg.as<CtgEntry>(); up.n_ctg = ctx->n_ctg;
+    up.refs = d_refs.as<uint8_t>(); up.ref_off = o64;
+    up.seqs = d_seqs.as<uint8_t>(); up.seq_off = o64 + (n + 1);
+    up.cigs = d_cigs.as<char>(); up.cig_off = o64 + 2 * (n + 1);
+    up.n_reads = n;
+    hipLaunchKernelGGL(unpack_records_kernel, dim3((unsigned)n), dim3(256), 0, st, up);
+    BamEmitParams bp;
+    bp.raw = up.raw; bp.raw_off = up.raw_off; bp.ref_off = up.ref_off; bp.seq_off = up.seq_off;
+    bp.hp = d_aux.as<int64_t>();
+    bp.words = d_words.as<uint8_t>(); bp.words_off = o64 + 3 * (n + 1); bp.words_len = d_wlen.as<int64_t>(); bp.status = d_status.as<int32_t>();
+    bp.read_base = 0; bp.n_reads = n;
+    bp.recs = d_recs.as<uint8_t>(); bp.cap = bound; bp.cursor = d_cursor.as<unsigned long long>();
+    bp.rec_off = d_rec_off.as<int64_t>(); bp.rec_len = d_rec_len.as<int64_t>();
+    bp.refs = up.refs; bp.seqs = up.seqs; bp.nm = d_nm.as<int32_t>();
+    hipLaunchKernelGGL(nm_count_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
+    hipLaunchKernelGGL(place_bam_full_kernel, dim3(1), dim3(256), 0, st, bp);
+    hipLaunchKernelGGL(emit_bam_full_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    unsigned long long total = 0;
+    std::vector<int64_t> rlen(N, 0);
+    HIP_TRY(hipMemcpy(&total, d_cursor.p, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rlen.data(), d_rec_len.p, N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nm, d_nm.p, N * 4, hipMemcpyDeviceToHost));
+    int64_t sum = 0;
+    for (size_t k = 0; k < N; k++) {
+        if (rlen[k] < 0) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
+        sum += rlen[k];
+    }
+    if ((int64_t)total > bound || sum != (int64_t)total) return fail(NPORE_E_HIP, "internal: BAM record sizes do not add up");
+    if ((int64_t)total > cap) return fail(NPORE_E_INVALID, "the records need more room than the caller gave");
+    if (total > 0) HIP_TRY(hipMemcpy(recs, d_recs.p, (size_t)total, hipMemcpyDeviceToHost));
+    *recs_len = (int64_t)total;
+    return NPORE_OK;
+}
+NPORE_CATCH_INT
+
 int npore_bam_set_output(npore_bam *b, int format, const char *bai_path, int flags)
 {
-    if (!b || (format != NPORE_OUT_SAM && format != NPORE_OUT_BAM) || (flags & ~(NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE | NPORE_OUT_MATCH)) ||
-        ((flags & NPORE_OUT_DEFLATE) && format != NPORE_OUT_BAM) || ((flags & NPORE_OUT_MATCH) && !(flags & NPORE_OUT_DEFLATE)))
+    if (!b || (format != NPORE_OUT_SAM && format != NPORE_OUT_BAM) ||
+        (flags & ~(NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE | NPORE_OUT_MATCH | NPORE_OUT_FULL)) ||
+        ((flags & (NPORE_OUT_DEFLATE | NPORE_OUT_FULL)) && format != NPORE_OUT_BAM) || ((flags & NPORE_OUT_MATCH) && !(flags & NPORE_OUT_DEFLATE)) ||
+        ((flags & NPORE_OUT_FULL) && !(flags & (NPORE_OUT_EOF | NPORE_OUT_PART))))      // (a FULL run says what it writes: the end of a file or a rank's part)
         return fail(NPORE_E_INVALID, "bad argument");
     b->out_format = format;
     b->out_bai = (format == NPORE_OUT_BAM && bai_path) ? bai_path : "";
@@ -1527,6 +1671,8 @@ try {
     b->out_bai.clear();
     b->out_flags = 0;
     std::fill(b->out_info, b->out_info + 4, 0);
+    if (flags & NPORE_OUT_FULL)
+        return fail(NPORE_E_UNSUPPORTED, "npore_bam_write_file has no reference to count NM from: FULL records come from a realign run or npore_bam_format_bam_full");
     if (int rc = w.open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0,
                         out_deflate_mode(flags), host_threads(threads)))
         return rc;
@@ -1577,9 +1723,12 @@ int slot_pack_records(const npore_bam *b, const npore_fasta *fa, const int32_t *
 // (the host glue reads the base arrays).
 // as_bam (BAM mode): each record up to the end of its QUALITIES (the tags stay on the host), the reads' HP values, slots of
 // 4 bytes per op + 16 (CIGAR words instead of text), and the bound of the batch's record bytes.
+// full (FULL records): the kept aux bytes behind the qualities (STAGE_FULL) and their number in the HP values' place; the
+// bound grows by the clips' bases, four clip words, the kept aux and NM.
 int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, int64_t n, int threads, npore_batch_slot &s, bool compact = false,
-                  bool as_bam = false)
+                  bool as_bam = false, bool full = false)
 {
+    const int form = !as_bam ? STAGE_HEAD : full ? STAGE_FULL : STAGE_QUALS;
     if (as_bam)
         if (int rc = s.hp_pin.ensure((size_t)n * 8 + 64)) return rc;
     s.rec_cap = 0;
@@ -1593,13 +1742,15 @@ int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, 
         const int32_t rid = r.ref_id();
         const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
         if (fi < 0 || fi >= n_fasta) return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
-        s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_head_bytes(r, rec_cigar(r), as_bam);
+        const int64_t aux = full ? filter_aux(r.aux(), r.end(), nullptr) : 0;
+        s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_head_bytes(r, rec_cigar(r), as_bam) + aux;
         const int64_t cap = (s.ro[(size_t)k + 1] - s.ro[(size_t)k]) + (s.so[(size_t)k + 1] - s.so[(size_t)k]);
         s.oo[(size_t)k + 1] = s.oo[(size_t)k] + (as_bam ? 4 : 2) * cap + 16;
         if (as_bam) {
             const int64_t sl = s.so[(size_t)k + 1] - s.so[(size_t)k];
-            reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = rec_hp(r);
+            reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = full ? aux : rec_hp(r);
             s.rec_cap += 36 + r.l_read_name() + 4 * cap + 16 + (sl + 1) / 2 + sl + 7 + 16;      // (+ 16: placeholder and CG tag head of a long final CIGAR)
+            if (full) s.rec_cap += ((int64_t)r.l_seq() + 1) / 2 + r.l_seq() - (sl + 1) / 2 - sl + 16 + aux;
         }
     }
     if (int rc = s.raw.ensure((size_t)s.rawo[(size_t)n] + 64)) return rc;
@@ -1610,7 +1761,7 @@ int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, 
         for (int64_t k = t * per; k < std::min(n, (t + 1) * per); k++) {
             char *dst = s.raw.p + s.rawo[(size_t)k];
             const size_t len = (size_t)(s.rawo[(size_t)k + 1] - s.rawo[(size_t)k]);
-            stage_record_head(s.rf.ptr[(size_t)k], as_bam, reinterpret_cast<uint8_t *>(dst));
+            stage_record_head(s.rf.ptr[(size_t)k], form, reinterpret_cast<uint8_t *>(dst));
             cache_writeback(dst, len);         // page-locked staging about to cross PCIe: out of this core's cache first (hostio.hpp)
         }
     });
@@ -1632,11 +1783,12 @@ int slot_align(npore_ctx *ctx, int64_t n, float indel_start, float indel_extend,
 }
 // realign_read's glue (src/bam.pyx:65-78) and the SAM lines; reads refused by align() have no string and get an empty CIGAR
 int slot_post(const npore_bam *b, int64_t n, const int32_t *status, int threads, npore_batch_slot &s, double *ms_std = nullptr,
-              bool device_glue = false, bool as_bam = false)
+              bool device_glue = false, bool as_bam = false, bool full = false)
 {
-    // SAM text, or (a BAM-mode file run) the same reads' records
+    // SAM text, or (a BAM-mode file run) the same reads' records (full: FULL records, NM from the slot's code arrays)
+    const ReadCodes codes{reinterpret_cast<const uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<const uint8_t *>(s.seqs.p), s.so.data()};
     auto format_into = [&](const char *finals, const int64_t *final_off) {
-        return as_bam ? format_bam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len, &s.meta)
+        return as_bam ? format_bam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len, &s.meta, full ? &codes : nullptr)
                       : format_sam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len);
     };
     if (device_glue) {          // the slots hold the final CIGAR text already (standardize_kernel)
@@ -1752,10 +1904,12 @@ struct RunOutput {
     FILE *fh = nullptr;
     std::unique_ptr<BgzfStoredWriter> bw;
     npore_bam *b = nullptr;
+    bool full = false;           // NPORE_OUT_FULL: FULL records
     int open(npore_bam *bam, const char *out_path, int threads)
     {
         b = bam;
         const int format = b->out_format, flags = b->out_flags;
+        full = format == NPORE_OUT_BAM && (flags & NPORE_OUT_FULL) != 0;
         const std::string bai = b->out_bai;
         b->out_format = NPORE_OUT_SAM;
         b->out_flags = 0;
@@ -1783,7 +1937,7 @@ struct RunOutput {
 template <class Acquire, class OnStatus>
 int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, float indel_start, float indel_extend,
                   int max_b_rows, int r, int threads, FILE *fh, bool serial_acquire, Acquire acquire, OnStatus on_status,
-                  BgzfStoredWriter *bw = nullptr)
+                  BgzfStoredWriter *bw = nullptr, bool full = false)
 {
     // (run_core refuses them too, but on a worker thread: refuse here, before a batch is read or a record written)
     if (!std::isfinite(indel_start) || !std::isfinite(indel_extend))
@@ -1858,7 +2012,7 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
                 if (serial_acquire) { bump(acquired); bumped = true; }
                 s.m = m > 0 ? m : 0;
                 if (m < 0) s.rc = (int)m;
-                else if (m > 0) s.rc = dpack ? slot_pack_raw(b, fasta_of_ref, n_fasta, m, pack_threads, s, glue, dev_bam)
+                else if (m > 0) s.rc = dpack ? slot_pack_raw(b, fasta_of_ref, n_fasta, m, pack_threads, s, glue, dev_bam, full)
                                              : slot_pack_records(b, fa, fasta_of_ref, m, pack_threads, s, glue, glue);
                 if (s.rc) s.err = npore_last_error();
             } catch (const std::exception &e) {
@@ -1887,7 +2041,7 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             t0 = std::chrono::steady_clock::now();
             double ms_std = 0.0;
             try {
-                t.rc = dev_bam ? slot_fetch_records(m, st, t, dev_deflate) : slot_post(b, m, st, post_threads, t, &ms_std, glue, bw != nullptr);
+                t.rc = dev_bam ? slot_fetch_records(m, st, t, dev_deflate) : slot_post(b, m, st, post_threads, t, &ms_std, glue, bw != nullptr, full);
             } catch (const std::exception &e) {
                 fail(NPORE_E_NOMEM, std::string("SAM text of a batch: ") + e.what());
                 t.rc = NPORE_E_NOMEM;
@@ -1939,6 +2093,7 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
                 (rc = s.reclen_pin.ensure((size_t)m * 8 + 64)) || (rc = s.total_pin.ensure(64))) { err = "batch buffers"; break; }
             emit = BamEmit{s.d_recs.as<uint8_t>(), s.rec_cap, s.d_cursor.as<unsigned long long>(), reinterpret_cast<const int64_t *>(s.hp_pin.p),
                            reinterpret_cast<int64_t *>(s.reclen_pin.p), reinterpret_cast<unsigned long long *>(s.total_pin.p)};
+            emit.full = full;
             if (dev_deflate) {
                 if ((rc = slot_deflate_buffers(s, s.rec_cap, bw->deflate_mode()))) { err = "batch buffers"; break; }
                 emit.deflate = true;
@@ -2032,7 +2187,7 @@ try {
                                return rcf ? (int64_t)rcf : m;
                            },
                            [&](int64_t k, int64_t m, const int32_t *st) { std::memcpy(status + k * batch_reads, st, (size_t)m * 4); },
-                           out.bw.get());
+                           out.bw.get(), out.full);
     return out.close(rc);
 }
 NPORE_CATCH_INT
@@ -2063,7 +2218,7 @@ try {
     };
     int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, out.fh, true,
                            [&](int64_t, npore_batch_slot &s) { return walker.next_batch(s.rf, s.keep, batch_reads); }, on_status,
-                           out.bw.get());
+                           out.bw.get(), out.full);
     counts[0] = ordinal0;
     return out.close(rc);
 }

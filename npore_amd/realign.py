@@ -64,6 +64,10 @@ def argparser():
                              "of literals (no match search); `match`, of literals and length/distance pairs (a hash of four bytes, a "
                              "greedy parse) wherever that is smaller.  Both are coded on the GPU in the default pipeline.  The records, "
                              "the cuts and the index's meaning are the same.")
+    parser.add_argument("--records", choices=("reference", "full"), default="reference",
+                        help="--out_format bam: `reference`, each record is the reference's SAM line in binary (clips cut off, mate "
+                             "fields cleared, HP the only tag); `full`, the input record with only what the realignment changes "
+                             "replaced: clipped bases, mate fields and tags stay (NM MD cs de dv dropped), NM recounted on the GPU.")
     parser.add_argument("--python_io", action="store_true",
                         help="Use the pure-Python BAM reader / SAM writer (the restatement the native one is tested against).")
     return parser
@@ -74,6 +78,13 @@ def main():
         print("\nERROR: --plot is not available in npore_amd (matplotlib reports are out of scope).")
         sys.exit(1)
     native = not cfg.args.python_io
+    records = getattr(cfg.args, "records", "reference")
+    if records == "full" and getattr(cfg.args, "out_format", "sam") != "bam":
+        print("\nERROR: --records full needs --out_format bam.")
+        sys.exit(1)
+    if records == "full" and not native:
+        print("\nERROR: --records full is written by the library's file pipeline: not with --python_io.")
+        sys.exit(1)
     # one process per GPU: the host stages of a rank use its share of the node's cores, and the BAM is inflated
     # once per node (local rank 0; the other ranks map its copy, bam.NativeBam)
     threads = dist_mod.host_threads_per_rank() if int(os.environ.get("LOCAL_WORLD_SIZE", "1")) > 1 else 0
@@ -138,7 +149,7 @@ def main():
         open(out_sam, "w").close()
     # BAM: the index beside the file (a rank's part: a sidecar with part-relative offsets, merged by dist.gather_bam_parts);
     # the EOF member ends the whole file, not a part
-    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress) if as_bam else {}
+    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress, records=records) if as_bam else {}
     gather = dist_mod.gather_bam_parts if as_bam else dist_mod.gather_parts
 
     print("> extracting read data from BAM")

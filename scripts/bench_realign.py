@@ -50,7 +50,7 @@ def _encode_span(job):
     """Worker: reads first ... first + count - 1 of the bench generator as BAM records (bytes) + their stretch of the contig.
     Qualities: one uniform draw per base over phred 0 ... 93, as the reference's own fixture generator does
     (test/generate_bam.py:63,79: chr(randint(33, 127)) per base) -- or the constant 20 of rounds 3 - 4 (`const_qual`)."""
-    seed, first, count, ref_len, const_qual, per_ctg = job
+    seed, first, count, ref_len, const_qual, per_ctg, tags = job
     dec = np.frombuffer(b"NACGT", np.uint8)
     recs, contig = [], []
     for k in range(first, first + count):
@@ -74,21 +74,25 @@ def _encode_span(job):
         name = f"read{k}".encode() + b"\0"
         body = struct.pack("<iiBBHHHiiii", k // per_ctg, (k % per_ctg) * ref_len, len(name), 60, 4680, len(lens), 0, len(sq), -1, -1, 0) + \
             name + cig + packed + qual + b"HPC" + bytes([k % 3])
+        if tags:        # (--tags: a read group and an ML-like array of l_seq / 2 bytes behind HP)
+            ml = np.random.Generator(np.random.PCG64(seed * 104729 + k)).integers(0, 256, len(sq) // 2, dtype=np.uint8).tobytes()
+            body += b"RGZbench\0" + b"MLBC" + struct.pack("<I", len(ml)) + ml
         recs.append(struct.pack("<i", len(body)) + body)
         contig.append(dec[rf].tobytes())
         assert len(rf) == ref_len
     return b"".join(recs), b"".join(contig)
 
 
-def build_inputs(tmp, n, distinct, ref_len, seed, const_qual=False, procs=0):
+def build_inputs(tmp, n, distinct, ref_len, seed, const_qual=False, procs=0, tags=False):
     """The BAM (BGZF, zlib level 1) and FASTA of `n` reads laid end to end on one contig.  distinct = 0 (default): every
     read is its own draw of the generator, made on a pool of worker processes; distinct = d < n: the first d reads'
-    record block repeated at the byte level (rounds 3 - 4: 4 000 distinct reads x 24)."""
+    record block repeated at the byte level (rounds 3 - 4: 4 000 distinct reads x 24).  tags: every read carries an RG:Z and a
+    B,C array of l_seq / 2 bytes."""
     import multiprocessing as mp
     distinct = n if distinct <= 0 else min(distinct, n)
     procs = procs or max(1, min(16, len(os.sched_getaffinity(0))))
     span = 250
-    jobs = [(seed, k, min(span, distinct - k), ref_len, const_qual, READS_PER_CONTIG) for k in range(0, distinct, span)]
+    jobs = [(seed, k, min(span, distinct - k), ref_len, const_qual, READS_PER_CONTIG, tags) for k in range(0, distinct, span)]
     recs, contig = [], []
     with mp.get_context("spawn").Pool(procs) as pool:
         for r_, c_ in pool.imap(_encode_span, jobs):
@@ -131,7 +135,7 @@ def start_output(a, out, nb):
     """The header of the output file, and what the realign calls need to write behind it in a.out_format."""
     if a.out_format == "bam":
         bam.create_bam_header(out, nb)
-        return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai", compress=a.bam_compress)
+        return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai", compress=a.bam_compress, records=a.records)
     bam.create_header(out, nb)
     return {}
 
@@ -253,12 +257,18 @@ def main():
                     help="--out_format bam: stored members, or every member one dynamic-Huffman block coded on the GPU, of literals "
                          "(huffman) or of literals and matches (match); the line's "
                          "`output_bytes` is the size of the one-pass leg's file")
+    ap.add_argument("--records", choices=("reference", "full"), default="reference",
+                    help="--out_format bam: the reference's records, or (full) the input records with only what the realignment changes replaced")
+    ap.add_argument("--tags", action="store_true",
+                    help="every synthetic read carries an RG:Z tag and a B,C array of l_seq / 2 bytes (an ML-like load for --records full)")
     ap.add_argument("--gen-into", default=None, help=argparse.SUPPRESS)       # (internal: make the inputs in this directory and exit)
     a = ap.parse_args()
     if a.bam_compress != "none" and a.out_format != "bam":
         ap.error("--bam_compress needs --out_format bam")
+    if a.records == "full" and a.out_format != "bam":
+        ap.error("--records full needs --out_format bam")
     if a.gen_into:
-        print(json.dumps(build_inputs(a.gen_into, a.reads, a.distinct, a.ref_len, a.seed, a.const_qual)))
+        print(json.dumps(build_inputs(a.gen_into, a.reads, a.distinct, a.ref_len, a.seed, a.const_qual, tags=a.tags)))
         return
     sub, nps, _, _ = aln.load_default_tables()
     with tempfile.TemporaryDirectory(dir=a.tmp) as tmp:
@@ -267,7 +277,7 @@ def main():
         # not count towards this process's peak RSS)
         import subprocess
         gen = subprocess.run([sys.executable, os.path.abspath(__file__), "--gen-into", tmp, "--reads", str(a.reads), "--distinct", str(a.distinct),
-                              "--ref-len", str(a.ref_len), "--seed", str(a.seed)] + (["--const-qual"] if a.const_qual else []),
+                              "--ref-len", str(a.ref_len), "--seed", str(a.seed)] + (["--const-qual"] if a.const_qual else []) + (["--tags"] if a.tags else []),
                              capture_output=True, text=True)
         if gen.returncode != 0:
             sys.exit("input generation failed:\n" + gen.stderr[-3000:])
@@ -337,7 +347,7 @@ def main():
                 "one_pass": one_pass, "one_pass_output_identical": same_one_pass,
                 "reads": a.reads, "distinct_reads": a.reads if a.distinct <= 0 else min(a.distinct, a.reads),
                 "qualities": "constant 20" if a.const_qual else "uniform per base over phred 0 ... 93 (reference test/generate_bam.py:63,79)",
-                "ref_len": a.ref_len, "r": a.r, "batch": a.batch, "out_format": a.out_format, "bam_compress": a.bam_compress,
+                "ref_len": a.ref_len, "r": a.r, "batch": a.batch, "out_format": a.out_format, "bam_compress": a.bam_compress, "records": a.records, "tags": a.tags,
                 "output_bytes": os.path.getsize(out + ".o"),
                 "host_cpus": len(os.sched_getaffinity(0)), "bam_bytes": os.path.getsize(bp),
                 "resident": resident, "streamed": streamed, "streamed_output_identical": same,

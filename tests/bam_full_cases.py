@@ -64,6 +64,14 @@ HP_TAGS = [None, b"HPC\x02", b"HPS" + struct.pack("<H", 300), b"HPI" + p32(70000
 HP_VALUES = [0, 2, 300, 70000, -1, -129, -40000]
 
 
+# the clips of a read (leading, trailing) and the tags in front of and behind its HP: read k takes CLIPS[k % 8], FRONT_TAGS[k % 4],
+# HP_TAGS[k % 7] and BACK_TAGS[(k // 2) % 4] (genome_scale_cases.py deals the same tables)
+CLIPS = [([], []), ([(S, 3)], []), ([(H, 4), (S, 4)], [(S, 2), (H, 7)]), ([(H, 5)], []), ([(S, 1)], [(S, 2)]), ([], [(H, 6)]),
+         ([(S, 4)], [(S, 5)]), ([(H, 1)], [(H, 1)])]
+FRONT_TAGS = [b"RGZgrp1\0", b"NMC\x05" + b"RGZg2\0", b"MLBC" + p32(6) + bytes([0, 255, 3, 4, 5, 6]), b""]
+BACK_TAGS = [b"PSi" + struct.pack("<i", 12345), b"MDZ10A5\0" + b"mvBc" + p32(3) + bytes([1, 0, 1]), b"", b"SAZctg,1,+,5S,60,0;\0" + b"def" + struct.pack("<f", .1)]
+
+
 def full_records(seed=5, n_reads=24, ref_len=1500):
     """(references, {contig name: bases}, records for bam.write_bam, [the real CIGAR of each]): reads with soft clips of even
     and odd length, H + S at both ends, an H without S at either end, no clips, N / ambiguity codes, both strands, reads
@@ -73,10 +81,7 @@ def full_records(seed=5, n_reads=24, ref_len=1500):
     refs, seqs, cigs = synth.make_batch(77, n_reads, ref_len=ref_len, p_np=0.1)
     dec = lambda a: "".join("NACGT"[x] for x in a)
     contig, recs = [], []
-    clips = [([], []), ([(S, 3)], []), ([(H, 4), (S, 4)], [(S, 2), (H, 7)]), ([(H, 5)], []), ([(S, 1)], [(S, 2)]), ([], [(H, 6)]),
-             ([(S, 4)], [(S, 5)]), ([(H, 1)], [(H, 1)])]
-    front = [b"RGZgrp1\0", b"NMC\x05" + b"RGZg2\0", b"MLBC" + p32(6) + bytes([0, 255, 3, 4, 5, 6]), b""]
-    back = [b"PSi" + struct.pack("<i", 12345), b"MDZ10A5\0" + b"mvBc" + p32(3) + bytes([1, 0, 1]), b"", b"SAZctg,1,+,5S,60,0;\0" + b"def" + struct.pack("<f", .1)]
+    clips, front, back = CLIPS, FRONT_TAGS, BACK_TAGS
     for k, (rf, sq, cg) in enumerate(zip(refs, seqs, cigs)):
         pos = len(contig) + 20
         contig += list("ACGT"[x] for x in rng.integers(0, 4, 20)) + list(dec(rf))

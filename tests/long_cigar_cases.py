@@ -98,8 +98,9 @@ def lookalikes(seed=4):
 
 
 def expected_pack(record, cigar, contig):
-    """(reference codes, query codes, expanded CIGAR) of `record` read with `cigar`: the contig under the alignment, the
-    bases without the soft clips, the operations without S and H ('NACGT-' -> 0..5)."""
+    """(reference codes, query codes, expanded CIGAR) of `record` read with `cigar`: the contig under the alignment -- N where
+    the alignment runs past the contig's end --, the bases without the soft clips, the operations without S and H
+    ('NACGT-' -> 0..5)."""
     code = {c: i for i, c in enumerate("NACGT-")}
     lead = cigar[0][1] if cigar[0][0] == S else cigar[1][1] if len(cigar) > 1 and cigar[0][0] == H and cigar[1][0] == S else 0
     trail = 0
@@ -110,6 +111,7 @@ def expected_pack(record, cigar, contig):
     seq = record["seq"]
     sl = max(0, len(seq) - lead - trail)
     refs = [code.get(c, 0) for c in contig[record["pos"]:record["pos"] + ref_len(cigar)]]
+    refs += [0] * (ref_len(cigar) - len(refs))                 # zeros (N) where the slice leaves the contig (unpack)
     seqs = [code.get(c, 0) for c in seq[lead:lead + sl]]
     ops = "".join("MIDNSHP=X"[op] * ln for op, ln in cigar if op not in (S, H))
     return np.array(refs, np.uint8), np.array(seqs, np.uint8), ops.encode()

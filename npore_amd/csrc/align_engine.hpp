@@ -1,6 +1,7 @@
 // align_engine.hpp -- the device path of a batch of reads: a context's work sets, the geometry of a fill launch, and a
 // group of reads through its stages (plan, reservation, upload, preparation, fill, traceback + output, download),
-// group after group through the three-stage pipeline (run_core).  Included by npore_api.cpp, the only translation unit.
+// group after group through the three-stage pipeline (run_core).  Included by npore_api.cpp, the only translation unit,
+// in front of file_pipeline.hpp, which drives it batch by batch.
 #pragma once
 #include <atomic>
 #include <cmath>
@@ -44,7 +45,7 @@ struct BamEmit {
     bool full = false;           // NPORE_OUT_FULL: FULL records (the heads staged with STAGE_FULL), NM counted on the device
 };
 
-struct npore_batch_slot;        // a batch of the BAM -> SAM pipeline (npore_api.cpp)
+struct npore_batch_slot;        // a batch of the BAM -> SAM pipeline (file_pipeline.hpp)
 
 // Work buffers of one group of reads on its way through the device stages (grow-only, reused).  A context has
 // N_SETS of them: while the fill kernel works on one group, the next group is prepared in another set and the previous

@@ -1,7 +1,7 @@
-// npore_api.cpp -- C ABI (include/npore_amd.h), the batch slots and the file pipeline; the only translation unit.
-// Compiled with hipcc for gfx950 only.  There is no CPU execution path for the
-// DP here: without a gfx950 device npore_ctx_create fails.  The device path of a batch of reads lives in align_engine.hpp;
-// what reads BAM / FASTA files and writes SAM text needs no device and lives in bam_reader.hpp / hostio.hpp.
+// npore_api.cpp -- C ABI (include/npore_amd.h): the entry points; the only translation unit.  Compiled with hipcc for gfx950 only.
+// There is no CPU execution path for the DP here: without a gfx950 device npore_ctx_create fails.  The device path of a batch of reads
+// lives in align_engine.hpp, the batch slots and the file pipeline's stages in file_pipeline.hpp, the order of its batches in
+// batch_order.hpp; what reads BAM / FASTA files and writes SAM text needs no device and lives in bam_reader.hpp / hostio.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,10 +10,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <condition_variable>
-#include <future>
 #include <limits>
-#include <mutex>
 #include <memory>
 #include <string>
 #include <thread>
@@ -32,6 +29,7 @@
 #include "confusion_kernels.hpp"
 #include "purity_kernels.hpp"
 #include "align_engine.hpp"
+#include "file_pipeline.hpp"
 
 // No C++ exception may cross the C ABI: the entry points that allocate are function-try-blocks ending in one of these.
 #define NPORE_CATCH_INT                                                                             \
@@ -40,79 +38,6 @@
 #define NPORE_CATCH_PTR                                                                             \
     catch (const std::bad_alloc &) { fail(NPORE_E_NOMEM, "out of host memory"); return nullptr; }  \
     catch (const std::exception &e) { fail(NPORE_E_INVALID, std::string("internal: ") + e.what()); return nullptr; }
-
-// One batch on its way through the BAM -> SAM pipeline: host staging (page-locked where it crosses PCIe) and offsets.
-struct npore_batch_slot {
-    PinnedBuf refs, seqs, cigs, alns;
-    RawBuf finals, sam;
-    PinnedBuf raw;               // device pack: the heads of the batch's records (fixed fields ... 4-bit bases), one after the other
-    std::vector<int64_t> rawo;   // ... and where each starts
-    // device glue: the batch's texts compacted on the device (unpack_kernels.hpp compact_texts_kernel) -- the compact buffer
-    // and its cursor there, the copied front of it and the reads' offsets here (page-locked)
-    DevBuf d_ctext, d_cursor;
-    PinnedBuf ctext_pin, coff_pin;
-    // BAM mode, records built on the device: the batch's record buffer there (the cursor is d_cursor) and its upper bound,
-    // the reads' HP values, and what comes back: the records' lengths, their total, the bytes
-    DevBuf d_recs;
-    int64_t rec_cap = 0;
-    PinnedBuf hp_pin, reclen_pin, total_pin, recs_pin;
-    // ... with NPORE_OUT_DEFLATE (bam_deflate_kernels.hpp): the members' plans, sizes and places, the coded members, the
-    // batch's four numbers; the size table and the numbers here; recs_pin then holds members | head fragment | tail fragment
-    DevBuf d_plans, d_sizes, d_moff, d_comp, d_info;
-    DevBuf d_htab, d_tokens;               // NPORE_OUT_MATCH: per member the hash table (2^15 positions) and the tokens
-    PinnedBuf sizes_pin, info_pin;
-    int64_t max_members = 0;
-    int64_t frag[4] = {0, 0, 0, 0};        // of the fetched batch: members, their bytes, head bytes, tail bytes
-    int64_t ctext_copied = 0;              // bytes of the compact buffer the batch's last group sent behind its kernels
-    PinnedBuf olen_pin, st_pin;            // lengths / status bits of an ASYNCHRONOUS batch land here (page-locked: a copy into
-                                           // pageable memory would make the enqueueing call wait for the whole batch)
-    hipEvent_t done = nullptr;             // ... behind which this event is recorded (npore_bam_realign_file)
-    std::vector<std::shared_ptr<RawBuf>> keep;   // one-pass ingest: the inflated windows the batch's records lie in
-    ~npore_batch_slot() { if (done) (void)hipEventDestroy(done); }
-    RecFetch rf;                 // the batch's BAM records (streamed handles: inflated for the batch)
-    double t_ms[6] = {0, 0, 0, 0, 0, 0};   // npore_bam_realign_file: fetch + pack, align call, standardise, format, write, (spare)
-    std::vector<int64_t> ro, so, co, oo, fo, olen, flen;
-    std::vector<BamRecMeta> meta;  // BAM output: what the index needs of every record written (sam then holds record bytes)
-    int64_t sam_len = 0;
-    int64_t m = 0;               // reads of the batch
-    int rc = 0;
-    std::string err;
-};
-
-namespace {
-int out_deflate_mode(int flags) { return !(flags & NPORE_OUT_DEFLATE) ? 0 : (flags & NPORE_OUT_MATCH) ? DEFLATE_MODE_MATCH : DEFLATE_MODE_HUFFMAN; }
-// NPORE_OUT_DEFLATE on the device: room for the most members `bytes` record bytes can hold
-int slot_deflate_buffers(npore_batch_slot &s, int64_t bytes, int mode)
-{
-    const int64_t mm = bytes / (int64_t)BGZF_STORED_PAYLOAD + 1;
-    s.max_members = mm;
-    if (mode == DEFLATE_MODE_MATCH) {       // a member's hash table and its tokens (a token per byte at the most)
-        if (int rc = s.d_htab.ensure((size_t)mm * sizeof(uint16_t) << DEFLATE_HASH_BITS)) return rc;
-        if (int rc = s.d_tokens.ensure((size_t)mm * BGZF_STORED_PAYLOAD * sizeof(uint32_t) + 64)) return rc;
-    }
-    if (int rc = s.d_plans.ensure((size_t)mm * sizeof(DeflateMemberPlan))) return rc;
-    if (int rc = s.d_sizes.ensure((size_t)mm * 4 + 64)) return rc;
-    if (int rc = s.d_moff.ensure((size_t)mm * 8 + 64)) return rc;
-    if (int rc = s.d_comp.ensure((size_t)mm * (BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD) + 2 * BGZF_STORED_PAYLOAD + 64)) return rc;      // (members, two fragments)
-    if (int rc = s.d_info.ensure(64)) return rc;
-    if (int rc = s.sizes_pin.ensure((size_t)mm * 4 + 64)) return rc;
-    return s.info_pin.ensure(64);
-}
-DeflateParams slot_deflate_params(npore_batch_slot &s, const uint8_t *d_recs, const unsigned long long *d_total, unsigned long long *d_stream_pos,
-                                  int mode)
-{
-    DeflateParams dp{};
-    dp.mode = mode;
-    if (mode == DEFLATE_MODE_MATCH) { dp.htab = s.d_htab.as<uint16_t>(); dp.tokens = s.d_tokens.as<uint32_t>(); }
-    dp.recs = d_recs; dp.total = d_total; dp.stream_pos = d_stream_pos;
-    dp.plans = s.d_plans.as<DeflateMemberPlan>(); dp.sizes = s.d_sizes.as<uint32_t>(); dp.off = s.d_moff.as<int64_t>();
-    dp.comp = s.d_comp.as<uint8_t>();
-    dp.comp_cap = s.max_members * (int64_t)(BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD);
-    dp.max_members = s.max_members;
-    dp.info = s.d_info.as<int64_t>();
-    return dp;
-}
-}  // namespace
 
 extern "C" {
 
@@ -211,30 +136,6 @@ void npore_ctx_destroy(npore_ctx *ctx)
     (void)hipDeviceSynchronize();       // nothing of this context may still be running: only then do its members die
     for (auto *sp : ctx->slots) delete sp;
     delete ctx;
-}
-
-// The FASTA on the device (once per FASTA and context) and, per BAM reference, where its contig lies there.
-static int device_fasta(npore_ctx *ctx, const npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref)
-{
-    const size_t bytes = fa->off.empty() ? 0 : (size_t)fa->off.back();
-    if (ctx->d_fasta_serial != fa->serial || ctx->d_fasta_bytes != bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (int rc = ctx->d_fasta.ensure(bytes + 64)) return rc;
-        HIP_TRY(hipMemcpy(ctx->d_fasta.p, fa->bases.p, bytes, hipMemcpyHostToDevice));
-        ctx->d_fasta_serial = fa->serial;
-        ctx->d_fasta_bytes = bytes;
-    }
-    const size_t nref = b->ref_names.size();
-    std::vector<CtgEntry> tab(std::max<size_t>(1, nref), CtgEntry{nullptr, 0});
-    for (size_t k = 0; k < nref; k++) {
-        const int fi = fasta_of_ref[k];
-        if (fi >= 0 && fi < (int)fa->names.size()) tab[k] = CtgEntry{ctx->d_fasta.as<char>() + fa->off[(size_t)fi], fa->len((size_t)fi)};
-    }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));       // (no group of an earlier run still reads the table)
-    if (int rc = ctx->d_ctg.ensure(tab.size() * sizeof(CtgEntry))) return rc;
-    HIP_TRY(hipMemcpy(ctx->d_ctg.p, tab.data(), tab.size() * sizeof(CtgEntry), hipMemcpyHostToDevice));
-    ctx->n_ctg = (int)nref;
-    return NPORE_OK;
 }
 
 int npore_align_batch(npore_ctx *ctx, int64_t n_reads, const uint8_t *refs, const int64_t *ref_off,
@@ -1665,17 +1566,11 @@ try {
         return fail(NPORE_E_INVALID, "bad argument");
     if (b->out_format != NPORE_OUT_BAM) return fail(NPORE_E_INVALID, "npore_bam_write_file writes BAM: npore_bam_set_output first");
     BgzfStoredWriter w;
-    const std::string bai = b->out_bai;
-    const int flags = b->out_flags;
-    b->out_format = NPORE_OUT_SAM;                   // (the setting holds for one run)
-    b->out_bai.clear();
-    b->out_flags = 0;
-    std::fill(b->out_info, b->out_info + 4, 0);
-    if (flags & NPORE_OUT_FULL)
+    const OutputSetting o = take_output_setting(b);
+    if (o.flags & NPORE_OUT_FULL)
         return fail(NPORE_E_UNSUPPORTED, "npore_bam_write_file has no reference to count NM from: FULL records come from a realign run or npore_bam_format_bam_full");
-    if (int rc = w.open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0,
-                        out_deflate_mode(flags), host_threads(threads)))
-        return rc;
+    if (int rc = w.open(out_path, b->ref_names.size(), o.bai.empty() ? nullptr : o.bai.c_str(), (o.flags & NPORE_OUT_EOF) != 0,
+                        (o.flags & NPORE_OUT_PART) != 0, out_deflate_mode(o.flags), host_threads(threads))) return rc;
     std::vector<BamRecMeta> meta;
     for (int64_t k0 = 0; k0 < n; k0 += batch_reads) {
         const int64_t m = std::min(batch_reads, n - k0);
@@ -1688,470 +1583,35 @@ try {
 }
 NPORE_CATCH_INT
 
-namespace {
-// pack the selected records into the slot (inputs of npore_align_batch) and size its output buffers
-// (the records are in s.rf already)
-int slot_pack_records(const npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n, int threads, npore_batch_slot &s,
-                      bool device_glue = false, bool compact = false)
-{
-    for (auto *v : {&s.ro, &s.so, &s.co, &s.oo, &s.fo}) v->assign((size_t)n + 1, 0);
-    s.olen.assign((size_t)n, 0);
-    s.flen.assign((size_t)n, 0);
-    pack_sizes_of(s.rf, n, s.ro.data(), s.so.data(), s.co.data(), threads);
-    if (int rc = s.refs.ensure((size_t)s.ro[(size_t)n] + 64)) return rc;
-    if (int rc = s.seqs.ensure((size_t)s.so[(size_t)n] + 64)) return rc;
-    if (int rc = s.cigs.ensure((size_t)s.co[(size_t)n] + 64)) return rc;
-    if (!fa || !fasta_of_ref) return fail(NPORE_E_INVALID, "bad argument");
-    if (int rc = pack_records(b, s.rf, fa, fasta_of_ref, n, reinterpret_cast<uint8_t *>(s.refs.p), s.ro.data(),
-                              reinterpret_cast<uint8_t *>(s.seqs.p), s.so.data(), s.cigs.p, s.co.data(), threads, true))
-        return rc;
-    for (int64_t k = 0; k < n; k++) {
-        const int64_t cap = (s.ro[(size_t)k + 1] - s.ro[(size_t)k]) + (s.so[(size_t)k + 1] - s.so[(size_t)k]);
-        // (device glue: the slot receives the collapsed CIGAR text instead of the op string -- 2 bytes per op + 16 always suffice)
-        s.oo[(size_t)k + 1] = s.oo[(size_t)k] + (device_glue ? 2 * cap + 16 : cap);
-        s.fo[(size_t)k + 1] = s.fo[(size_t)k] + 2 * cap + 16;
-    }
-    // (compact: the texts come back compacted -- file_pipeline --, no page-locked copy of the slots is needed)
-    if (!compact)
-        if (int rc = s.alns.ensure((size_t)s.oo[(size_t)n] + 64)) return rc;
-    if (!device_glue && !s.finals.ensure((size_t)s.fo[(size_t)n] + 64)) return fail(NPORE_E_NOMEM, "batch buffers");     // (a RawBuf: hostio.hpp)
-    return NPORE_OK;
-}
-// device pack: the sizes as above, and instead of the three arrays the HEADS of the records (block_size word, fixed fields,
-// name, CIGAR words, 4-bit bases -- about half of a record; qualities and tags are not needed on the device) copied one
-// after the other into the slot's page-locked buffer; unpack_kernels.hpp does the rest per group.  Device glue only
-// (the host glue reads the base arrays).
-// as_bam (BAM mode): each record up to the end of its QUALITIES (the tags stay on the host), the reads' HP values, slots of
-// 4 bytes per op + 16 (CIGAR words instead of text), and the bound of the batch's record bytes.
-// full (FULL records): the kept aux bytes behind the qualities (STAGE_FULL) and their number in the HP values' place; the
-// bound grows by the clips' bases, four clip words, the kept aux and NM.
-int slot_pack_raw(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, int64_t n, int threads, npore_batch_slot &s, bool compact = false,
-                  bool as_bam = false, bool full = false)
-{
-    const int form = !as_bam ? STAGE_HEAD : full ? STAGE_FULL : STAGE_QUALS;
-    if (as_bam)
-        if (int rc = s.hp_pin.ensure((size_t)n * 8 + 64)) return rc;
-    s.rec_cap = 0;
-    for (auto *v : {&s.ro, &s.so, &s.co, &s.oo, &s.fo}) v->assign((size_t)n + 1, 0);
-    s.rawo.assign((size_t)n + 1, 0);
-    s.olen.assign((size_t)n, 0);
-    s.flen.assign((size_t)n, 0);
-    pack_sizes_of(s.rf, n, s.ro.data(), s.so.data(), s.co.data(), threads);
-    for (int64_t k = 0; k < n; k++) {
-        const RecView r = rec_of(s.rf, k);
-        const int32_t rid = r.ref_id();
-        const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
-        if (fi < 0 || fi >= n_fasta) return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
-        const int64_t aux = full ? filter_aux(r.aux(), r.end(), nullptr) : 0;
-        s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_head_bytes(r, rec_cigar(r), as_bam) + aux;
-        const int64_t cap = (s.ro[(size_t)k + 1] - s.ro[(size_t)k]) + (s.so[(size_t)k + 1] - s.so[(size_t)k]);
-        s.oo[(size_t)k + 1] = s.oo[(size_t)k] + (as_bam ? 4 : 2) * cap + 16;
-        if (as_bam) {
-            const int64_t sl = s.so[(size_t)k + 1] - s.so[(size_t)k];
-            reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = full ? aux : rec_hp(r);
-            s.rec_cap += 36 + r.l_read_name() + 4 * cap + 16 + (sl + 1) / 2 + sl + 7 + 16;      // (+ 16: placeholder and CG tag head of a long final CIGAR)
-            if (full) s.rec_cap += ((int64_t)r.l_seq() + 1) / 2 + r.l_seq() - (sl + 1) / 2 - sl + 16 + aux;
-        }
-    }
-    if (int rc = s.raw.ensure((size_t)s.rawo[(size_t)n] + 64)) return rc;
-    if (!compact)
-        if (int rc = s.alns.ensure((size_t)s.oo[(size_t)n] + 64)) return rc;
-    const int64_t per = 16;
-    parallel_for((n + per - 1) / per, threads, [&](int64_t t) {
-        for (int64_t k = t * per; k < std::min(n, (t + 1) * per); k++) {
-            char *dst = s.raw.p + s.rawo[(size_t)k];
-            const size_t len = (size_t)(s.rawo[(size_t)k + 1] - s.rawo[(size_t)k]);
-            stage_record_head(s.rf.ptr[(size_t)k], form, reinterpret_cast<uint8_t *>(dst));
-            cache_writeback(dst, len);         // page-locked staging about to cross PCIe: out of this core's cache first (hostio.hpp)
-        }
-    });
-    return NPORE_OK;
-}
-int slot_pack(const npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n, int threads,
-              npore_batch_slot &s)
-{
-    if (!pack_args_ok(b, idx, n)) return fail(NPORE_E_INVALID, "bad argument");
-    if (int rc = fetch_records(b, idx, n, threads, s.rf)) return rc;
-    return slot_pack_records(b, fa, fasta_of_ref, n, threads, s);
-}
-int slot_align(npore_ctx *ctx, int64_t n, float indel_start, float indel_extend, int max_b_rows, int r, int32_t *status,
-               npore_batch_slot &s)
-{
-    return npore_align_batch(ctx, n, reinterpret_cast<uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<uint8_t *>(s.seqs.p),
-                             s.so.data(), s.cigs.p, s.co.data(), indel_start, indel_extend, max_b_rows, r, s.alns.p, s.oo.data(),
-                             s.olen.data(), status);
-}
-// realign_read's glue (src/bam.pyx:65-78) and the SAM lines; reads refused by align() have no string and get an empty CIGAR
-int slot_post(const npore_bam *b, int64_t n, const int32_t *status, int threads, npore_batch_slot &s, double *ms_std = nullptr,
-              bool device_glue = false, bool as_bam = false, bool full = false)
-{
-    // SAM text, or (a BAM-mode file run) the same reads' records (full: FULL records, NM from the slot's code arrays)
-    const ReadCodes codes{reinterpret_cast<const uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<const uint8_t *>(s.seqs.p), s.so.data()};
-    auto format_into = [&](const char *finals, const int64_t *final_off) {
-        return as_bam ? format_bam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len, &s.meta, full ? &codes : nullptr)
-                      : format_sam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len);
-    };
-    if (device_glue) {          // the slots hold the final CIGAR text already (standardize_kernel)
-        if (ms_std) *ms_std = 0.0;
-        for (int64_t k = 0; k < n; k++) s.flen[(size_t)k] = s.olen[(size_t)k] > 0 ? s.olen[(size_t)k] : 0;
-        if (s.ctext_copied > 0) {          // ... compacted (file_pipeline): the front of the compact buffer is here, the rest is fetched now
-            const int64_t *coff = reinterpret_cast<const int64_t *>(s.coff_pin.p);
-            int64_t extent = 0;
-            for (int64_t k = 0; k < n; k++) {
-                if (s.flen[(size_t)k] > 0 && coff[k] < 0) return fail(NPORE_E_HIP, "internal: compact text buffer overflow");
-                if (s.flen[(size_t)k] > 0) extent = std::max(extent, coff[k] + s.flen[(size_t)k]);
-            }
-            if (extent > s.ctext_copied) {        // (texts far longer than usual: 0.5 bytes per base were sent with the batch)
-                if (int rc = s.ctext_pin.ensure((size_t)extent + 64)) return rc;
-                HIP_TRY(hipMemcpy(s.ctext_pin.p, s.d_ctext.p, (size_t)extent, hipMemcpyDeviceToHost));
-                s.ctext_copied = extent;
-            }
-            return format_into(s.ctext_pin.p, coff);
-        }
-        return format_into(s.alns.p, s.oo.data());
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint8_t *refs = reinterpret_cast<const uint8_t *>(s.refs.p), *seqs = reinterpret_cast<const uint8_t *>(s.seqs.p);
-    parallel_for(n, threads, [&](int64_t k) {
-        const int64_t l = s.olen[(size_t)k] > 0 ? s.olen[(size_t)k] : 0;
-        s.flen[(size_t)k] = standardize_collapsed_into(s.alns.p + s.oo[(size_t)k], l, refs + s.ro[(size_t)k],     // 2 bytes per op + 16 always suffice
-                                                       s.ro[(size_t)k + 1] - s.ro[(size_t)k], seqs + s.so[(size_t)k],
-                                                       s.so[(size_t)k + 1] - s.so[(size_t)k], s.finals.p + s.fo[(size_t)k]);
-    });
-    if (ms_std) *ms_std = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return format_into(s.finals.p, s.fo.data());
-}
-// BAM mode, records built on the device: nothing is formatted here -- the batch's bytes as they lie there, into page-locked
-// memory, and from the records' lengths what the writer's index needs (reference, position and span are the input record's)
-int slot_fetch_records(int64_t n, const int32_t *status, npore_batch_slot &s, bool deflate)
-{
-    const int64_t total = (int64_t)*reinterpret_cast<const unsigned long long *>(s.total_pin.p);
-    const int64_t *len = reinterpret_cast<const int64_t *>(s.reclen_pin.p);
-    if (total < 0 || total > s.rec_cap) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
-    s.meta.clear();
-    int64_t sum = 0;
-    for (int64_t k = 0; k < n; k++) {
-        if (len[k] < 0) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
-        if ((len[k] == 0) != ((status[k] & NPORE_ST_BAD_INPUT) != 0)) return fail(NPORE_E_HIP, "internal: BAM records and status bits disagree");
-        if (len[k] == 0) continue;
-        const RecView r = rec_of(s.rf, k);
-        s.meta.push_back(BamRecMeta{r.ref_id(), r.pos(), s.ro[(size_t)k + 1] - s.ro[(size_t)k], len[k]});
-        sum += len[k];
-    }
-    if (sum != total) return fail(NPORE_E_HIP, "internal: BAM record sizes do not add up");
-    if (deflate) {          // exactly the coded members and the two raw fragments around them
-        const int64_t *info = reinterpret_cast<const int64_t *>(s.info_pin.p);
-        const int64_t nm = info[0], comp = info[1], head = info[2], tail = info[3];
-        if (nm < 0 || nm > s.max_members || head < 0 || tail < 0 || head + nm * (int64_t)BGZF_STORED_PAYLOAD + tail != total || comp < 0 ||
-            comp > nm * (int64_t)(BGZF_STORED_PAYLOAD + BGZF_STORED_OVERHEAD))
-            return fail(NPORE_E_HIP, "internal: the coded members do not add up to the batch's bytes");
-        // (one copy: the fragments lie behind the last member -- emit_deflate_kernel)
-        if (int rc = s.recs_pin.ensure((size_t)(comp + head + tail) + 64)) return rc;
-        if (comp + head + tail > 0) HIP_TRY(hipMemcpy(s.recs_pin.p, s.d_comp.p, (size_t)(comp + head + tail), hipMemcpyDeviceToHost));
-        std::copy(info, info + 4, s.frag);
-        s.sam_len = total;
-        return NPORE_OK;
-    }
-    if (int rc = s.recs_pin.ensure((size_t)total + 64)) return rc;
-    if (total > 0) HIP_TRY(hipMemcpy(s.recs_pin.p, s.d_recs.p, (size_t)total, hipMemcpyDeviceToHost));
-    s.sam_len = total;
-    return NPORE_OK;
-}
-}  // namespace
-
-
 int npore_bam_realign_batch(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
                             int64_t n, float indel_start, float indel_extend, int max_b_rows, int r, int threads,
                             const char **sam, int64_t *sam_len, int32_t *status)
 try {
     if (!ctx || !b || !status || !sam || !sam_len) return fail(NPORE_E_INVALID, "null argument");
     using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
     HIP_TRY(hipSetDevice(ctx->device));
+    if (!pack_args_ok(b, idx, n)) return fail(NPORE_E_INVALID, "bad argument");
     if (!ctx->slots[0]) ctx->slots[0] = new npore_batch_slot();
     npore_batch_slot &s = *ctx->slots[0];
+    const PipeMode host{};                 // one synchronous batch: host pack, host glue, SAM text
     auto t0 = clk::now();
-    if (int rc = slot_pack(b, fa, fasta_of_ref, idx, n, threads, s)) return rc;
+    s.m = n;
+    if (int rc = fetch_records(b, idx, n, threads, s.rf)) return rc;
+    if (int rc = slot_pack(b, fa, fasta_of_ref, threads, s, host)) return rc;
     b->stage_ms[0] = ms_since(t0);
     t0 = clk::now();
-    if (int rc = slot_align(ctx, n, indel_start, indel_extend, max_b_rows, r, status, s)) return rc;
+    if (int rc = npore_align_batch(ctx, n, reinterpret_cast<uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<uint8_t *>(s.seqs.p), s.so.data(), s.cigs.p,
+                                   s.co.data(), indel_start, indel_extend, max_b_rows, r, s.alns.p, s.oo.data(), s.olen.data(), status)) return rc;
     b->stage_ms[1] = ms_since(t0);
     t0 = clk::now();
     double ms_std = 0.0;
-    const int rc = slot_post(b, n, status, threads, s, &ms_std);
+    const int rc = slot_collect(b, status, threads, s, host, &ms_std);
     b->stage_ms[2] = ms_std;
     b->stage_ms[3] = ms_since(t0) - ms_std;
-    *sam = s.sam.p;
-    *sam_len = s.sam_len;
+    *sam = s.sam.p; *sam_len = s.sam_len;
     return rc;
 }
 NPORE_CATCH_INT
-
-}  // extern "C"
-
-namespace {
-// The BAM -> SAM pipeline over a stream of batches.  Stages: records + pack (helper threads, two batches ahead) | the
-// device path of ONE context through its asynchronous entry point -- a batch is enqueued the moment it is packed and
-// the call returns at once, so up to N_SETS batches are on the device, the upload / preparation of one and the
-// traceback / download of another beside the fill kernel of a third (run_core) | standardise + SAM text + ordered write
-// (helper threads, each behind the event recorded behind its batch's download).  A slot carries a batch through all
-// stages; six slots cover two being packed, three on the device and one being written.
-//   acquire(k, slot) -> the records of batch k in slot.rf: their number, 0 = no further batch, < 0 = failure (fail() called);
-//     serial_acquire: called in batch order (the one-pass reader), else from the packing threads as they come;
-//   on_status(k, m, status bits): in batch order, in front of the batch's text.
-// Where a file run's output goes: the SAM text's FILE, or (npore_bam_set_output, which holds for one run) the BAM writer
-struct RunOutput {
-    FILE *fh = nullptr;
-    std::unique_ptr<BgzfStoredWriter> bw;
-    npore_bam *b = nullptr;
-    bool full = false;           // NPORE_OUT_FULL: FULL records
-    int open(npore_bam *bam, const char *out_path, int threads)
-    {
-        b = bam;
-        const int format = b->out_format, flags = b->out_flags;
-        full = format == NPORE_OUT_BAM && (flags & NPORE_OUT_FULL) != 0;
-        const std::string bai = b->out_bai;
-        b->out_format = NPORE_OUT_SAM;
-        b->out_flags = 0;
-        b->out_bai.clear();
-        std::fill(b->out_info, b->out_info + 4, 0);
-        if (format == NPORE_OUT_BAM) {
-            bw.reset(new BgzfStoredWriter());
-            return bw->open(out_path, b->ref_names.size(), bai.empty() ? nullptr : bai.c_str(), (flags & NPORE_OUT_EOF) != 0, (flags & NPORE_OUT_PART) != 0,
-                            out_deflate_mode(flags), std::max(1, host_threads(threads) / 2));
-        }
-        fh = std::fopen(out_path, "ab");
-        return fh ? NPORE_OK : fail(NPORE_E_INVALID, std::string("cannot open '") + out_path + "' for appending");
-    }
-    int close(int rc)
-    {
-        if (fh && std::fclose(fh) != 0 && rc == NPORE_OK) rc = fail(NPORE_E_INVALID, "close failed");
-        fh = nullptr;
-        if (bw && rc == NPORE_OK) rc = bw->finish(b->out_info);
-        bw.reset();
-        return rc;
-    }
-    ~RunOutput() { if (fh) std::fclose(fh); }
-};
-
-template <class Acquire, class OnStatus>
-int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, float indel_start, float indel_extend,
-                  int max_b_rows, int r, int threads, FILE *fh, bool serial_acquire, Acquire acquire, OnStatus on_status,
-                  BgzfStoredWriter *bw = nullptr, bool full = false)
-{
-    // (run_core refuses them too, but on a worker thread: refuse here, before a batch is read or a record written)
-    if (!std::isfinite(indel_start) || !std::isfinite(indel_extend))
-        return fail(NPORE_E_INVALID, "indel_start and indel_extend must be finite");
-    for (auto &sp : ctx->slots)
-        if (!sp) sp = new npore_batch_slot();
-    const auto wall0 = std::chrono::steady_clock::now();
-    for (auto &sp : ctx->slots) { std::fill(sp->t_ms, sp->t_ms + 6, 0.0); sp->rc = 0; sp->m = 0; }
-    ctx->file_mark[0] = ctx->totals[0] + ctx->totals[1] + ctx->totals[2];
-    ctx->file_mark[1] = ctx->totals[3] + ctx->totals[4];
-    constexpr int S = npore_ctx::N_SLOTS;
-    // Several batches are in the host stages at once (two being packed, up to two being written): each stage gets half
-    // of the CPUs, so that the process does not run five times as many busy threads as it has CPUs -- under a cgroup quota
-    // that ends in the whole process being throttled for the rest of the scheduling period
-    const int half_threads = std::max(1, host_threads(threads) / 2);
-    // (experiments: NPORE_PACK_THREADS / NPORE_POST_THREADS override the split)
-    const int pack_threads = std::getenv("NPORE_PACK_THREADS") ? std::max(1, std::atoi(std::getenv("NPORE_PACK_THREADS"))) : half_threads;
-    const int post_threads = std::getenv("NPORE_POST_THREADS") ? std::max(1, std::atoi(std::getenv("NPORE_POST_THREADS"))) : half_threads;
-    const bool glue = ctx->device_glue != 0;      // realign_read's glue on the device: the slots receive the final CIGAR text
-    // ... and align()'s inputs unpacked from the records on the device (the host glue needs the base arrays on the host)
-    const bool dpack = glue && ctx->device_pack != 0 && !(std::getenv("NPORE_DEVICE_PACK") && std::atoi(std::getenv("NPORE_DEVICE_PACK")) == 0);
-    if (dpack)
-        if (int rc = device_fasta(ctx, b, fa, fasta_of_ref)) return rc;
-    const int n_fasta = (int)fa->names.size();
-    // BAM mode: the records are built on the device where the default pipeline runs (device pack + device glue:
-    // bam_emit_kernels.hpp); with the host glue or the host pack the host twin makes them (format_bam_into)
-    const bool dev_bam = bw != nullptr && dpack;
-    // ... and with NPORE_OUT_DEFLATE the whole members inside a batch are coded there too (bam_deflate_kernels.hpp); the
-    // run's stream position starts at 0
-    const bool dev_deflate = dev_bam && bw->deflate();
-    if (dev_deflate) {
-        if (int rc = ctx->d_stream_pos.ensure(64)) return rc;
-        HIP_TRY(hipMemset(ctx->d_stream_pos.p, 0, 8));
-    }
-    // NPORE_PIPE_TRACE=1: one line per batch and stage boundary on stderr (ms since the call began)
-    const bool trace = std::getenv("NPORE_PIPE_TRACE") != nullptr;
-    std::mutex trace_m;
-    auto mark = [&](const char *what, int64_t k) {
-        if (!trace) return;
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-        std::lock_guard<std::mutex> lk(trace_m);
-        std::fprintf(stderr, "pipe %8.2f ms  batch %3lld  %s\n", ms, (long long)k, what);
-    };
-    std::vector<std::future<void>> packed, posted;
-    // batches leave in input order: `written` counts the batches that are through (written, or given up on);
-    // `acquired` the batches whose records have been taken from a serial source
-    std::mutex gate_m;
-    std::condition_variable gate_cv;
-    int64_t written = 0, acquired = 0;
-    auto wait_for = [&](int64_t &counter, int64_t upto) {
-        std::unique_lock<std::mutex> lk(gate_m);
-        gate_cv.wait(lk, [&] { return counter >= upto; });
-    };
-    auto bump = [&](int64_t &counter) {
-        { std::lock_guard<std::mutex> lk(gate_m); counter++; }
-        gate_cv.notify_all();
-    };
-    auto start_pack = [&](int64_t k) {
-        packed.push_back(std::async(std::launch::async, [&, k] {
-            npore_batch_slot &s = *ctx->slots[(size_t)(k % S)];
-            if (k >= S) wait_for(written, k - S + 1);          // the slot's previous batch has been written
-            if (serial_acquire) wait_for(acquired, k);
-            const auto t0 = std::chrono::steady_clock::now();
-            mark("acquire begins", k);
-            s.keep.clear();
-            s.rc = 0;
-            s.m = 0;
-            bool bumped = !serial_acquire;
-            try {                                       // (no exception may leave a task unseen: the batch fails instead)
-                const int64_t m = acquire(k, s);
-                mark("acquired", k);
-                if (serial_acquire) { bump(acquired); bumped = true; }
-                s.m = m > 0 ? m : 0;
-                if (m < 0) s.rc = (int)m;
-                else if (m > 0) s.rc = dpack ? slot_pack_raw(b, fasta_of_ref, n_fasta, m, pack_threads, s, glue, dev_bam, full)
-                                             : slot_pack_records(b, fa, fasta_of_ref, m, pack_threads, s, glue, glue);
-                if (s.rc) s.err = npore_last_error();
-            } catch (const std::exception &e) {
-                s.rc = NPORE_E_NOMEM;
-                s.err = std::string("batch preparation: ") + e.what();
-                s.m = 0;
-            }
-            if (!bumped) bump(acquired);                // (the batches behind this one must not wait for ever)
-            s.t_ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            mark("packed", k);
-        }));
-    };
-    auto start_post = [&](int64_t k) {
-        posted.push_back(std::async(std::launch::async, [&, k] {
-            npore_batch_slot &t = *ctx->slots[(size_t)(k % S)];
-            struct Through { decltype(wait_for) &w; decltype(bump) &m; int64_t &c; int64_t k; ~Through() { w(c, k); m(c); } } through{wait_for, bump, written, k};
-            if (t.rc) return;
-            (void)hipSetDevice(ctx->device);
-            auto t0 = std::chrono::steady_clock::now();
-            if (hipEventSynchronize(t.done) != hipSuccess) { t.rc = NPORE_E_HIP; t.err = "waiting for a batch failed"; return; }
-            mark("device done", k);
-            t.t_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            const int64_t m = t.m;
-            std::memcpy(t.olen.data(), t.olen_pin.p, (size_t)m * 8);
-            const int32_t *st = reinterpret_cast<const int32_t *>(t.st_pin.p);
-            t0 = std::chrono::steady_clock::now();
-            double ms_std = 0.0;
-            try {
-                t.rc = dev_bam ? slot_fetch_records(m, st, t, dev_deflate) : slot_post(b, m, st, post_threads, t, &ms_std, glue, bw != nullptr, full);
-            } catch (const std::exception &e) {
-                fail(NPORE_E_NOMEM, std::string("SAM text of a batch: ") + e.what());
-                t.rc = NPORE_E_NOMEM;
-            }
-            const double ms_post = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            t.t_ms[2] += ms_std;
-            t.t_ms[3] += ms_post - ms_std;
-            if (t.rc) { t.err = npore_last_error(); return; }
-            mark("text made", k);
-            wait_for(written, k);                              // records in input order
-            on_status(k, m, st);
-            t0 = std::chrono::steady_clock::now();
-            if (dev_deflate) {
-                const uint8_t *q = reinterpret_cast<const uint8_t *>(t.recs_pin.p);
-                // (recs_pin: members | head fragment | tail fragment)
-                if (bw->add_coded(q + t.frag[1], t.frag[2], q, reinterpret_cast<const uint32_t *>(t.sizes_pin.p), t.frag[0],
-                                  q + t.frag[1] + t.frag[2], t.frag[3], t.meta.data(), (int64_t)t.meta.size())) { t.rc = NPORE_E_INVALID; t.err = npore_last_error(); }
-            } else if (bw) {
-                const char *bytes = dev_bam ? t.recs_pin.p : t.sam.p;
-                if (bw->add(reinterpret_cast<const uint8_t *>(bytes), t.sam_len, t.meta.data(), (int64_t)t.meta.size())) { t.rc = NPORE_E_INVALID; t.err = npore_last_error(); }
-            } else if (std::fwrite(t.sam.p, 1, (size_t)t.sam_len, fh) != (size_t)t.sam_len) { t.rc = NPORE_E_INVALID; t.err = "short write"; }
-            t.t_ms[4] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            mark("written", k);
-            t.keep.clear();
-        }));
-    };
-    int rc = NPORE_OK;
-    std::string err;
-    start_pack(0);
-    start_pack(1);
-    for (int64_t k = 0; rc == NPORE_OK; k++) {
-        npore_batch_slot &s = *ctx->slots[(size_t)(k % S)];
-        packed[(size_t)k].wait();
-        if (s.rc) { rc = s.rc; err = s.err; break; }
-        if (s.m == 0) break;                                   // the source is exhausted
-        start_pack(k + 2);
-        const int64_t m = s.m;
-        if ((rc = s.olen_pin.ensure((size_t)m * 8 + 64)) || (rc = s.st_pin.ensure((size_t)m * 4 + 64))) { err = "batch buffers"; break; }
-        if (!s.done && hipEventCreateWithFlags(&s.done, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) { rc = NPORE_E_HIP; err = "hipEventCreate"; break; }
-        // (returns once the batch's groups are enqueued; waits only when all work sets of the context are still busy)
-        mark("enqueue begins", k);
-        // device glue: the texts come back compacted -- the front of the batch's compact buffer (0.5 bytes per base are
-        // sent with the batch's last group; what usual reads need is a quarter of that) and the reads' offsets
-        TextCompact cmp{};
-        BamEmit emit{};
-        s.ctext_copied = 0;
-        if (dev_bam) {
-            if ((rc = s.d_recs.ensure((size_t)s.rec_cap + 64)) || (rc = s.d_cursor.ensure(64)) || (rc = s.ctext_pin.ensure(64)) ||
-                (rc = s.reclen_pin.ensure((size_t)m * 8 + 64)) || (rc = s.total_pin.ensure(64))) { err = "batch buffers"; break; }
-            emit = BamEmit{s.d_recs.as<uint8_t>(), s.rec_cap, s.d_cursor.as<unsigned long long>(), reinterpret_cast<const int64_t *>(s.hp_pin.p),
-                           reinterpret_cast<int64_t *>(s.reclen_pin.p), reinterpret_cast<unsigned long long *>(s.total_pin.p)};
-            emit.full = full;
-            if (dev_deflate) {
-                if ((rc = slot_deflate_buffers(s, s.rec_cap, bw->deflate_mode()))) { err = "batch buffers"; break; }
-                emit.deflate = true;
-                emit.dfl = slot_deflate_params(s, s.d_recs.as<uint8_t>(), s.d_cursor.as<unsigned long long>(), ctx->d_stream_pos.as<unsigned long long>(),
-                                               bw->deflate_mode());
-                emit.h_sizes = reinterpret_cast<uint32_t *>(s.sizes_pin.p);
-                emit.h_info = reinterpret_cast<int64_t *>(s.info_pin.p);
-            }
-        } else if (glue) {
-            // (a text takes whole 16-byte granules of the compact buffer: at most 15 bytes more than its slot)
-            const int64_t slots = s.oo[(size_t)m] + 16 * m, bound = std::min(slots, slots / 4 + 4096);
-            if ((rc = s.d_ctext.ensure((size_t)slots + 64)) || (rc = s.d_cursor.ensure(64)) || (rc = s.ctext_pin.ensure((size_t)bound + 64)) ||
-                (rc = s.coff_pin.ensure((size_t)m * 8 + 64))) { err = "batch buffers"; break; }
-            cmp = TextCompact{s.d_ctext.as<uint8_t>(), s.d_cursor.as<unsigned long long>(), slots,
-                              reinterpret_cast<int64_t *>(s.coff_pin.p), s.ctext_pin.p, bound};
-            s.ctext_copied = bound;
-        }
-        char *const out_host = glue ? s.ctext_pin.p : s.alns.p;      // (with the compaction nothing is copied there)
-        AlignArgs a = host_batch_args(m, s.ro.data(), s.so.data(), s.co.data(), indel_start, indel_extend, max_b_rows, r, out_host,
-                                      s.oo.data(), reinterpret_cast<int64_t *>(s.olen_pin.p), reinterpret_cast<int32_t *>(s.st_pin.p));
-        if (dpack) {
-            a.h_raw = reinterpret_cast<uint8_t *>(s.raw.p); a.h_raw_off = s.rawo.data();
-            a.d_ctg = ctx->d_ctg.as<CtgEntry>(); a.n_ctg = ctx->n_ctg;
-        } else {
-            a.h_refs = reinterpret_cast<uint8_t *>(s.refs.p); a.h_seqs = reinterpret_cast<uint8_t *>(s.seqs.p); a.h_cigs = s.cigs.p;
-        }
-        a.final_text = glue;
-        if (dev_bam) a.bam = &emit;
-        else if (glue) a.compact = &cmp;                             // (read while the groups are enqueued, not behind the call)
-        s.rc = align_batch(ctx, a, false);
-        if (s.rc) { rc = s.rc; err = npore_last_error(); s.err = err; break; }
-        if (hipEventRecord(s.done, ctx->s_post) != hipSuccess) { rc = NPORE_E_HIP; err = "hipEventRecord"; s.rc = rc; s.err = err; break; }
-        mark("enqueued", k);
-        start_post(k);
-    }
-    for (auto &f : packed) if (f.valid()) f.wait();
-    for (auto &f : posted) if (f.valid()) f.wait();
-    {
-        const int rcw = npore_ctx_wait(ctx);                   // stage clocks of every group; a failure found while a work set was recycled
-        if (rcw && rc == NPORE_OK) { rc = rcw; err = npore_last_error(); }
-    }
-    for (auto &sp : ctx->slots) {
-        if (rc == NPORE_OK && sp->rc) { rc = sp->rc; err = sp->err; }
-        sp->keep.clear();
-    }
-    // stage clocks of this call: sums over the batches of the time each stage's thread spent (stages of
-    // neighbouring batches overlap, so the sums exceed the wall time), the wall time, and the GPU's share
-    std::fill(b->file_ms, b->file_ms + 8, 0.0);
-    for (auto &sp : ctx->slots)
-        for (int q = 0; q < 5; q++) b->file_ms[q] += sp->t_ms[q];
-    b->file_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-    b->file_ms[6] = ctx->totals[0] + ctx->totals[1] + ctx->totals[2] - ctx->file_mark[0];     // stage clocks of the device path (prep + fill + traceback;
-    b->file_ms[7] = ctx->totals[3] + ctx->totals[4] - ctx->file_mark[1];                     // H2D + D2H): SUMS over groups that run beside each other
-    return rc == NPORE_OK ? NPORE_OK : fail(rc, err);
-}
-}  // namespace
-
-extern "C" {
 
 int npore_bam_set_share(npore_bam *b, int rank, int world, const char *bai_path)
 try {
@@ -2173,21 +1633,19 @@ int npore_bam_realign_file(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, 
                            int64_t n, int64_t batch_reads, float indel_start, float indel_extend, int max_b_rows, int r,
                            int threads, const char *out_path, int32_t *status)
 try {
-    if (!ctx || !b || !fa || !fasta_of_ref || !out_path || (n > 0 && (!idx || !status)) || batch_reads < 1) return fail(NPORE_E_INVALID, "bad argument");
-    if (!pack_args_ok(b, idx, n)) return fail(NPORE_E_INVALID, "bad argument");
+    if (!ctx || !b || !fa || !fasta_of_ref || !out_path || (n > 0 && (!idx || !status)) || batch_reads < 1 || !pack_args_ok(b, idx, n))
+        return fail(NPORE_E_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(ctx->device));
     RunOutput out;
     if (int rco = out.open(b, out_path, threads)) return rco;
-    const int64_t nb = (n + batch_reads - 1) / batch_reads;
-    int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, out.fh, false,
+    int rc = file_pipeline(ctx, b, fa, fasta_of_ref, AlignKnobs{indel_start, indel_extend, max_b_rows, r}, threads, out, false,
                            [&](int64_t k, npore_batch_slot &s) -> int64_t {
-                               if (k >= nb) return 0;
                                const int64_t m = std::min(batch_reads, n - k * batch_reads);
+                               if (m <= 0) return 0;
                                const int rcf = fetch_records(b, idx + k * batch_reads, m, threads, s.rf);
                                return rcf ? (int64_t)rcf : m;
                            },
-                           [&](int64_t k, int64_t m, const int32_t *st) { std::memcpy(status + k * batch_reads, st, (size_t)m * 4); },
-                           out.bw.get(), out.full);
+                           [&](int64_t k, int64_t m, const int32_t *st) { std::memcpy(status + k * batch_reads, st, (size_t)m * 4); });
     return out.close(rc);
 }
 NPORE_CATCH_INT
@@ -2216,9 +1674,8 @@ try {
             }
         ordinal0 += m;
     };
-    int rc = file_pipeline(ctx, b, fa, fasta_of_ref, indel_start, indel_extend, max_b_rows, r, threads, out.fh, true,
-                           [&](int64_t, npore_batch_slot &s) { return walker.next_batch(s.rf, s.keep, batch_reads); }, on_status,
-                           out.bw.get(), out.full);
+    int rc = file_pipeline(ctx, b, fa, fasta_of_ref, AlignKnobs{indel_start, indel_extend, max_b_rows, r}, threads, out, true,
+                           [&](int64_t, npore_batch_slot &s) { return walker.next_batch(s.rf, s.keep, batch_reads); }, on_status);
     counts[0] = ordinal0;
     return out.close(rc);
 }

@@ -247,7 +247,7 @@ def copy_call(what, dst, src, nib, clear_low, n):
 def copy_calls(records, n_final_ops, batch_reads):
     """Every wave_copy call of emit_bam_records_kernel over the reads in batches of batch_reads, as copy_call() tuples, and
     the records' offsets in their batch.  Where source and destination lie is what the code does (align_engine.hpp,
-    npore_api.cpp slot_pack_raw): a batch's staged heads lie back to back, without padding, from the start of an
+    file_pipeline.hpp slot_pack_heads): a batch's staged heads lie back to back, without padding, from the start of an
     allocation (these reads are one group per batch: upload_group copies the slice to the buffer's start); the CIGAR words
     lie in slots at multiples of 4; the batch's records lie back to back from the start of the record buffer (the cursor is
     set to 0 with a batch's first group).  Allocations are aligned to more than 4."""

@@ -244,6 +244,50 @@ def test_contig_missing_from_the_fasta(ctx, files, route):
     assert sam.read_text() == "".join(text.splitlines(keepends=True)[:gs.BATCH])
 
 
+def test_contig_missing_from_the_fasta_late_in_a_run(ctx, files, route):
+    """the same refusal several batches into a run, with earlier batches on the device: the decoy's read among the main
+    records, in coordinate order -- behind chrBig's.  The call fails, the text holds whole batches in front of the decoy's
+    and nothing else, and the context goes on as before"""
+    tmp, bp, dp, fa = files
+    text, st, finals = route
+    references, refs, records, decoy = gs.case()
+    mixed = sorted(gs.plain(records) + decoy, key=lambda r: (r["ref_id"], r["pos"]))
+    at = [r["name"] for r in mixed].index("onDecoy")
+    assert at // gs.BATCH >= 3 and mixed[:at] == gs.plain(records)[:at]
+    mp = str(tmp / "mixed.bam")
+    bam.write_bam(mp, references, mixed)
+    bam.write_bai(mp)
+    lines = text.splitlines(keepends=True)
+    # the text of the first j whole batches, for every j in front of the decoy's batch (a refused read has no line)
+    prefixes = ["".join(lines[:int(((st[:j * gs.BATCH] & 32) == 0).sum())]) for j in range(at // gs.BATCH + 1)]
+    everything = [(n, 0, l) for n, l in gs.HEADER]
+    nf = bam.NativeFasta(fa)
+    for how in ("device_pack", "host_pack", "one_pass"):
+        ctx.set("device_pack", 0 if how == "host_pack" else 1)
+        nb = bam.NativeBam(mp, one_pass=how == "one_pass")
+        sam = tmp / f"mixed_{how}.sam"
+        try:
+            with pytest.raises(RuntimeError, match="not in the FASTA"):
+                if how == "one_pass":
+                    nb.realign_sequential(ctx, nf, everything, str(sam), batch_reads=gs.BATCH, r=30)
+                else:
+                    idx = nb.select(everything)
+                    assert len(idx) == len(mixed)
+                    nb.realign_file(ctx, nf, idx, str(sam), batch_reads=gs.BATCH, r=30)
+        finally:
+            ctx.set("device_pack", 1)
+            nb.close()
+        got = sam.read_text() if sam.exists() else ""
+        assert got in prefixes, (how, len(got), [len(p) for p in prefixes])
+        nb = bam.NativeBam(bp)
+        idx = nb.select(gs.whole_regions())
+        again = tmp / f"after_mixed_{how}.sam"
+        st_again = nb.realign_file(ctx, nf, idx, str(again), batch_reads=gs.BATCH, r=30)
+        nb.close()
+        assert np.array_equal(st_again, st) and again.read_text() == text, how
+    nf.close()
+
+
 # ---- 6. two ranks ---------------------------------------------------------------------------------------------------------------
 def test_two_ranks_at_genome_coordinates(files):
     tmp, bp, dp, fa = files

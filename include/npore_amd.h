@@ -326,6 +326,17 @@ int npore_bam_format_bam_full(npore_bam *bam, const npore_fasta *fa, const int32
 int npore_debug_format_bam_full_device(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
                                        int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len,
                                        const int32_t *status, uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm);
+/* The two above with `flags`: NPORE_OUT_MD (the only bit they know; anything else: NPORE_E_INVALID) puts the MD tag behind NM
+ * -- 'M' 'D' 'Z' text NUL, the text over the final CIGAR and the two code arrays (csrc/md_rec.hpp) --, 0 gives the bytes of
+ * the entry points above.  The device entry point also returns the reads' MD text lengths in md_len[n] (0: a refused read;
+ * may be NULL without the flag): md_size_kernel in front of the placement, emit_md_kernel behind the records. */
+int npore_bam_format_bam_full_md(npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
+                                 const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
+                                 const uint8_t **recs, int64_t *recs_len, int flags);
+int npore_debug_format_bam_full_md_device(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
+                                          int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len,
+                                          const int32_t *status, uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm, int flags,
+                                          int32_t *md_len);
 /* What the NEXT npore_bam_realign_file / _sequential / npore_bam_write_file on the handle appends to its out_path
  * (the setting holds for that one run): NPORE_OUT_SAM, the text, or NPORE_OUT_BAM, the records of npore_bam_format_bam in
  * BGZF members with STORED deflate blocks -- the record stream cut every 65 280 bytes counted from the run's first
@@ -360,6 +371,13 @@ int npore_debug_format_bam_full_device(npore_ctx *ctx, npore_bam *bam, const npo
  * code arrays align() got: IUPAC letters other than N count as N); a long CIGAR's CG tag behind NM.  Built on the device in
  * the default pipeline, by the host twin otherwise.  npore_bam_write_file has no reference: NPORE_E_UNSUPPORTED. */
 #define NPORE_OUT_FULL 16
+/* flags, only together with NPORE_OUT_FULL (32 alone, or 32 | NPORE_OUT_EOF, stay refused, as before the flag existed): the MD
+ * tag (`--md`) behind the recomputed NM of every FULL record -- 'M' 'D' 'Z' text NUL, kept aux, NM, MD, CG in that order.  The
+ * text is csrc/md_rec.hpp's, over the final CIGAR and the code arrays NM is counted on, so the two cannot disagree: matches
+ * counted up to the next mismatch (its reference letter) or deletion ('^' and its reference letters), the closing count.  It
+ * is `samtools calmd`'s text with NM's one difference: an IUPAC letter other than N counts as a mismatch and prints as N.
+ * Sized and written on the device in the default pipeline (md_size_kernel, emit_md_kernel), by the host twin otherwise. */
+#define NPORE_OUT_MD 32
 int npore_bam_set_output(npore_bam *bam, int format, const char *bai_path, int flags);
 /* Of the last BAM-mode run on the handle: out4[0] records written, [1] bytes of the record stream, [2] 1 = the index was
  * written, 0 = none was asked for, -1 = the records were not in coordinate order (no index), [3] size of the file. */

@@ -392,9 +392,41 @@ def nm_of(ref_codes, seq_codes, final):
     return nm
 
 
-def full_record(raw, ref_codes, seq_codes, final):
+def md_of(ref_codes, seq_codes, final):
+    """MD of a final CIGAR text over the code arrays align() got (csrc/md_rec.hpp, beside nm_of): the matches counted up to
+    the next position under M where the codes differ or either is 0 -- the count, then the reference's letter --, or up to
+    the next D -- the count, '^', the reference's letters --, and the closing count.  LETTER = "NACGTN"; a position beyond
+    an array has code 0.  `samtools calmd`'s text but for nm_of's difference: an IUPAC letter other than N has code 0, so it
+    counts as a mismatch and prints as N."""
+    import re
+    letter = "NACGTN"
+    out, u, a, b = [], 0, 0, 0
+    for n, op in re.findall(r"(\d+)([MIDNSHP=X])", final):
+        n = int(n)
+        if op in "M=X":
+            for q in range(n):
+                rc = int(ref_codes[a + q]) if a + q < len(ref_codes) else 0
+                sc = int(seq_codes[b + q]) if b + q < len(seq_codes) else 0
+                if rc != sc or rc == 0 or sc == 0:
+                    out.append(f"{u}{letter[rc]}")
+                    u = 0
+                else:
+                    u += 1
+            a, b = a + n, b + n
+        elif op == "D" and n > 0:
+            out.append(f"{u}^" + "".join(letter[int(ref_codes[a + q]) if a + q < len(ref_codes) else 0] for q in range(n)))
+            u, a = 0, a + n
+        elif op == "N":
+            a += n
+        elif op in "IS":
+            b += n
+    return "".join(out) + str(u)
+
+
+def full_record(raw, ref_codes, seq_codes, final, md=False):
     """The FULL record (--records full, with its block_size word) of the input record `raw` (block_size word first) with
-    its final CIGAR: the statement npore_bam_format_bam_full and the device path are tested against."""
+    its final CIGAR: the statement npore_bam_format_bam_full and the device path are tested against.  md: with the MD tag
+    (md_of) behind NM, as NPORE_OUT_MD writes it."""
     import re
     raw = bytes(raw)
     ref_id, pos, l_rn, mapq, _bin, n_cig, flag, l_seq, nref, npos, tlen = struct.unpack_from("<iiBBHHHiiii", raw, 4)
@@ -422,6 +454,8 @@ def full_record(raw, ref_codes, seq_codes, final):
     nm = nm_of(ref_codes, seq_codes, final)
     tags = filter_aux(aux) + b"NM" + (b"C" + struct.pack("<B", nm) if nm <= 0xFF else b"S" + struct.pack("<H", nm) if nm <= 0xFFFF
                                       else b"I" + struct.pack("<I", nm))
+    if md:
+        tags += b"MDZ" + md_of(ref_codes, seq_codes, final).encode() + b"\0"
     if len(words) // 4 > MAX_CIGAR_OPS:
         tags += b"CGBI" + struct.pack("<I", len(words) // 4) + words
         words = struct.pack("<II", (l_seq << 4) | 4, (reflen << 4) | 3)
@@ -1154,8 +1188,9 @@ class NativeBam:
                                                    fl.ctypes.data, st.ctypes.data, threads, C.byref(recs), C.byref(recs_len)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def format_bam_full(self, fasta, idx, finals, status, threads=0):
-        """FULL records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam_full)."""
+    def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False):
+        """FULL records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam_full;
+        md: with the MD tag behind NM, npore_bam_format_bam_full_md with NPORE_OUT_MD)."""
         import ctypes as C
         idx = np.ascontiguousarray(idx, np.int64)
         n = len(idx)
@@ -1167,12 +1202,12 @@ class NativeBam:
         st = np.ascontiguousarray(status, np.int32)
         fmap = self.fasta_map(fasta)
         recs, recs_len = C.c_void_p(), C.c_int64()
-        self._check(self._lib.npore_bam_format_bam_full(self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data,
-                                                        fo.ctypes.data, fl.ctypes.data, st.ctypes.data, threads, C.byref(recs),
-                                                        C.byref(recs_len)))
+        args = (self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
+                st.ctypes.data, threads, C.byref(recs), C.byref(recs_len))
+        self._check(self._lib.npore_bam_format_bam_full_md(*args, 32) if md else self._lib.npore_bam_format_bam_full(*args))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference"):
+    def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False):
         """What the NEXT realign_file / realign_sequential / write_file on this handle appends to its output path
         (npore_bam_set_output; the setting holds for that one run): "sam", or "bam" -- records in stored BGZF members behind
         what lies in the file (the header's members: create_bam_header) and `bai` written when the records went out in
@@ -1181,18 +1216,22 @@ class NativeBam:
         compress: "none", stored members, "huffman", every member one dynamic-Huffman block of literals, or "match", of
         literals and length / distance pairs where that is smaller
         (NPORE_OUT_DEFLATE; "bam" only).  records: "reference", the reference's SAM line in binary, or "full", the input
-        record with only what the realignment changes replaced (NPORE_OUT_FULL; "bam" only)."""
+        record with only what the realignment changes replaced (NPORE_OUT_FULL; "bam" only).  md: the MD tag behind the
+        recounted NM of every FULL record (NPORE_OUT_MD; records "full" only)."""
         if compress not in ("none", "huffman", "match"):
             raise ValueError("compress must be 'none', 'huffman' or 'match'")
         if records not in ("reference", "full"):
             raise ValueError("records must be 'reference' or 'full'")
         if records == "full" and out_format != "bam":
             raise ValueError("records 'full' needs out_format 'bam'")
+        if md and records != "full":
+            raise ValueError("md needs records 'full'")
         if compress != "none" and out_format != "bam":
             raise ValueError("compress needs out_format 'bam'")
         flags = 0 if out_format != "bam" else 1 if eof else 2       # NPORE_OUT_EOF / NPORE_OUT_PART
         flags |= {"none": 0, "huffman": 4, "match": 12}[compress]  # NPORE_OUT_DEFLATE, NPORE_OUT_MATCH
         flags |= 16 if records == "full" else 0                    # NPORE_OUT_FULL
+        flags |= 32 if md else 0                                   # NPORE_OUT_MD
         self._check(self._lib.npore_bam_set_output(self.handle, {"sam": 0, "bam": 1}[out_format], os.fsencode(bai) if bai else None, flags))
 
     def output_info(self):
@@ -1248,12 +1287,12 @@ class NativeBam:
 
     def realign_sequential(self, ctx, fasta, regions, out_path, batch_reads=4000, max_reads=0, r=30, max_b_rows=20000,
                            indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, out_format="sam", bai=None, eof=True,
-                           compress="none", records="reference"):
+                           compress="none", records="reference", md=False):
         """ONE PASS over the file: inflate, filter by `regions` [(contig, start, stop)] (at most one per contig, in header
         order), batch, realign, write -- npore_bam_realign_sequential.  Returns (reads selected, [(ordinal, status)] of
         the first bad reads, (refused, inconsistent)); raises OnePassUnsupported when the regions or the file's
         order rule the one-pass run out (the caller truncates the output and takes the indexed path).
-        out_format / bai / eof / compress / records: set_output for this run ("bam": records instead of text)."""
+        out_format / bai / eof / compress / records / md: set_output for this run ("bam": records instead of text)."""
         ids = {n: i for i, n in enumerate(self.references)}
         rid = np.array([ids.get(c, -2) for c, _, _ in regions], np.int32)
         beg = np.array([s for _, s, _ in regions], np.int64)
@@ -1263,7 +1302,7 @@ class NativeBam:
         counts = np.zeros(3, np.int64)
         bad_ord, bad_st = np.zeros(max(bad_cap, 1), np.int64), np.zeros(max(bad_cap, 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records)
+        self.set_output(out_format, bai, eof, compress, records, md)
         rc = self._lib.npore_bam_realign_sequential(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, len(regions), rid.ctypes.data,
                                                     beg.ctypes.data, end.ctypes.data, int(max_reads or 0), int(batch_reads), indel_start,
                                                     indel_extend, max_b_rows, r, threads, os.fsencode(out_path), counts.ctypes.data,
@@ -1295,14 +1334,14 @@ class NativeBam:
         return (memoryview((C.c_char * sam_len.value).from_address(sam.value)) if sam_len.value else memoryview(b"")), st[:n]
 
     def realign_file(self, ctx, fasta, idx, out_sam, batch_reads=4000, r=30, max_b_rows=20000, indel_start=5.0,
-                     indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none", records="reference"):
+                     indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False):
         """All selected reads, batch by batch, appended to out_sam by the library with packing, GPU work and
         formatting/writing of neighbouring batches overlapped.  Returns status[n].
-        out_format / bai / eof / compress / records: set_output for this run ("bam": records instead of text)."""
+        out_format / bai / eof / compress / records / md: set_output for this run ("bam": records instead of text)."""
         idx = np.ascontiguousarray(idx, np.int64)
         st = np.zeros(max(len(idx), 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records)
+        self.set_output(out_format, bai, eof, compress, records, md)
         self._check(self._lib.npore_bam_realign_file(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data,
                                                      len(idx), int(batch_reads), indel_start, indel_extend, max_b_rows, r,
                                                      threads, os.fsencode(out_sam), st.ctypes.data))
@@ -1349,7 +1388,7 @@ class NativeBam:
 
 
 def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0, out_format="sam", bai=None,
-                   eof=True, compress="none", records="reference"):
+                   eof=True, compress="none", records="reference", md=False):
     """realign_reads() through the library; returns the number of reads handed in.  batch_reads > 0: the whole
     index list in overlapped batches written by the library itself; 0: one batch, text written here.
     threads: host threads of the parallel host stages (0 = all cores; one process per GPU: dist.host_threads_per_rank).
@@ -1361,7 +1400,7 @@ def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_
     if batch_reads > 0:
         text, status = None, bam.realign_file(ctx, fasta, idx, out_sam, batch_reads=batch_reads, r=r, max_b_rows=max_b_rows,
                                               threads=threads, out_format=out_format, bai=bai, eof=eof, compress=compress,
-                                              records=records)
+                                              records=records, md=md)
     else:
         text, status = bam.realign_batch(ctx, fasta, idx, r=r, max_b_rows=max_b_rows, threads=threads)
     bad = np.nonzero(status)[0]

@@ -15,7 +15,8 @@
 // in the CIGAR's place, the real words in a CG:B,I tag behind HP -- 16 bytes more, in both kernels.
 // FULL records (NPORE_OUT_FULL, bam_reader.hpp FULL RECORD) have three kernels of their own at the end of this file --
 // nm_count_kernel in front of the same two steps, place_bam_full_kernel and emit_bam_full_kernel --; the two above are
-// what they were.
+// what they were.  With NPORE_OUT_MD beside it the MD tag follows NM (md_rec.hpp): md_size_kernel between nm_count_kernel
+// and the placement, emit_md_kernel behind emit_bam_full_kernel -- ONE walk (md_walk), launched with two sinks.
 // The host then takes the batch's bytes as they lie (BgzfStoredWriter) and the records' lengths for its index.
 // Both run beside the next batch's fill kernel and keep to what the other light kernels keep to: at most
 // 64 vector registers; the placement's 2 KB of LDS are less than a fill workgroup leaves free, the assembly has none.
@@ -23,6 +24,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "md_rec.hpp"
 #include "nm_rec.hpp"
 #include "unpack_kernels.hpp"
 
@@ -47,6 +49,7 @@ struct BamEmitParams {
     // FULL records only (nm_count_kernel): the group's code arrays, which ref_off / seq_off index, and the reads' NM
     const uint8_t *refs = nullptr, *seqs = nullptr;
     int32_t *nm = nullptr;         // [n_reads]
+    int32_t *md_len = nullptr;     // [n_reads] NPORE_OUT_MD (md_size_kernel): bytes of the read's MD text; null: no MD tag
 };
 
 __device__ __forceinline__ int bam_hp_bytes(int64_t hp)
@@ -275,6 +278,7 @@ struct BamFullShape {
     int nc, ci, cj, nmb;
     bool lng;
     int64_t wl, n_cig, l_seq, aux, size;
+    int64_t mdb;                   // bytes of the MD tag behind NM (4 + its text; 0: none)
 };
 __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, int64_t k)
 {
@@ -296,8 +300,9 @@ __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, i
     s.aux = p.hp[k];
     const uint32_t nm = (uint32_t)p.nm[k];
     s.nmb = nm <= 0xFFu ? 1 : nm <= 0xFFFFu ? 2 : 4;
+    s.mdb = p.md_len ? 4 + (int64_t)p.md_len[k] : 0;
     s.size = (p.status[g] & 32) ? 0
-                                : 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb +
+                                : 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb +
                                       (s.lng ? 8 + 4 * s.n_cig : 0);
     return s;
 }
@@ -330,8 +335,8 @@ __global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
     for (int j = lane; j < l_rn; j += 64) o[j] = f[32 + j];
     o += l_rn;
     uint8_t *cw = o;                                             // where the CIGAR words go
-    if (s.lng) {                                                 // the placeholder here, CG:B,I behind NM
-        cw = o + 8 + body + 3 + s.nmb + 8;
+    if (s.lng) {                                                 // the placeholder here, CG:B,I behind NM (and MD)
+        cw = o + 8 + body + 3 + s.nmb + s.mdb + 8;
         if (lane < 2) put32(o + 4 * lane, lane == 0 ? ((uint32_t)s.l_seq << 4 | 4u) : ((uint32_t)reflen << 4 | 3u));
         if (lane >= 4 && lane < 8) cw[lane - 12] = (uint8_t)"CGBI"[lane - 4];
         if (lane >= 8 && lane < 12) cw[lane - 12] = (uint8_t)((uint32_t)s.n_cig >> (8 * (lane - 8)));
@@ -350,6 +355,111 @@ __global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
         o[2] = (uint8_t)(s.nmb == 1 ? 'C' : s.nmb == 2 ? 'S' : 'I');
         for (int q = 0; q < s.nmb; q++) o[3 + q] = (uint8_t)(nm >> (8 * q));
     }
+}
+
+// ---- the MD tag of a FULL record (NPORE_OUT_MD; md_rec.hpp states the rule and holds the sequential twin) ----------------
+// One wavefront per read over tiles of 64 CIGAR words, as nm_count_kernel: lane l holds word l, wave prefix sums place every
+// word on both arrays, the M-type and D words are visited in word order.  `at` (bytes of text so far) and `u` (matches
+// since the last item) are the same in every lane.
+//   M word, 64 positions per round: the ballot of nm_differs gives the events.  An event lane's count is the distance to
+//     the previous set bit of the round (the round's first event: u + its lane), its bytes digits(count) + 1, its place a
+//     wave prefix sum of those bytes over the event lanes; the carry out is u + the round's positions where the round has no
+//     event, otherwise the positions behind the last event.
+//   D word: the count's digits and '^' by lane 0, then the letters with the lanes striding over them.
+// The walk is ONE function over a sink (md_rec.hpp): md_size_kernel runs it with MdCount, emit_md_kernel with MdStore, so
+// size and text cannot differ.  Returns the text's length (no NUL).
+template <class Sink>
+__device__ __forceinline__ uint32_t md_walk(const BamEmitParams &p, int64_t k, int lane, const Sink &sink)
+{
+    const int64_t g = p.read_base + k;
+    const int64_t n = p.words_len[g] <= 0 ? 0 : p.words_len[g] >> 2;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(p.words + p.words_off[g]);      // (the slots lie at multiples of 4)
+    const uint8_t *ref = p.refs + p.ref_off[k], *seq = p.seqs + p.seq_off[k];
+    const int64_t rl = p.ref_off[k + 1] - p.ref_off[k], sl = p.seq_off[k + 1] - p.seq_off[k];
+    const unsigned long long below_me = (1ull << lane) - 1ull;
+    int64_t a0 = 0, b0 = 0;                  // consumed in front of the tile
+    uint32_t at = 0, u = 0;
+    for (int64_t t0 = 0; t0 < n; t0 += 64) {
+        const uint32_t v = t0 + lane < n ? w[t0 + lane] : 0u;       // (behind the end: `0M`)
+        const uint32_t op = v & 15u, len = v >> 4, use = nm_consumes(op);
+        const uint32_t ra = (use & 1u) ? len : 0u, qa = (use & 2u) ? len : 0u;
+        uint32_t ri = ra, qi = qa;           // inclusive sums over the tile
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t x = (uint32_t)__shfl_up((int)ri, d), y = (uint32_t)__shfl_up((int)qi, d);
+            if (lane >= d) { ri += x; qi += y; }
+        }
+        unsigned long long runs = __builtin_amdgcn_ballot_w64((nm_compares(op) || op == 2u) && len > 0);
+        while (runs) {
+            const int j = (int)__builtin_ctzll(runs);
+            runs &= runs - 1;
+            const uint32_t lj = (uint32_t)__shfl((int)len, j), opj = (uint32_t)__shfl((int)op, j);
+            const int64_t aj = a0 + (uint32_t)__shfl((int)(ri - ra), j), bj = b0 + (uint32_t)__shfl((int)(qi - qa), j);
+            if (opj == 2u) {
+                const int nd = md_digits(u);
+                if (lane == 0) {
+                    md_put_decimal(sink, at, u, nd);
+                    sink.put(at + nd, (uint8_t)'^');
+                }
+                at += (uint32_t)nd + 1u;
+                for (uint32_t q = (uint32_t)lane; q < lj; q += 64) sink.put(at + q, md_letter(md_ref_code(ref, rl, aj + q)));
+                at += lj;
+                u = 0;
+                continue;
+            }
+            for (uint32_t q0 = 0; q0 < lj; q0 += 64) {
+                const uint32_t q = q0 + (uint32_t)lane, in_round = min(64u, lj - q0);
+                const bool d = q < lj && nm_differs(ref, rl, aj + q, seq, sl, bj + q);
+                const unsigned long long ev = __builtin_amdgcn_ballot_w64(d);
+                if (!ev) { u += in_round; continue; }
+                const unsigned long long before = ev & below_me;
+                const uint32_t cnt = before ? (uint32_t)(lane - 1 - (63 - (int)__builtin_clzll(before))) : u + (uint32_t)lane;
+                const int nd = md_digits(cnt);
+                const uint32_t bytes = d ? (uint32_t)nd + 1u : 0u;
+                uint32_t incl = bytes;
+                for (int s = 1; s < 64; s <<= 1) {
+                    const uint32_t x = (uint32_t)__shfl_up((int)incl, s);
+                    if (lane >= s) incl += x;
+                }
+                if (d) {
+                    const uint32_t mine = at + incl - bytes;
+                    md_put_decimal(sink, mine, cnt, nd);
+                    sink.put(mine + nd, md_letter(md_ref_code(ref, rl, aj + q)));
+                }
+                at += (uint32_t)__shfl((int)incl, 63);
+                u = in_round - 1u - (uint32_t)(63 - (int)__builtin_clzll(ev));
+            }
+        }
+        a0 += (uint32_t)__shfl((int)ri, 63);
+        b0 += (uint32_t)__shfl((int)qi, 63);
+    }
+    const int nd = md_digits(u);
+    if (lane == 0) md_put_decimal(sink, at, u, nd);
+    return at + (uint32_t)nd;
+}
+
+// bytes of every read's MD text (0: the read is refused and has no record), between nm_count_kernel and the placement
+__global__ __launch_bounds__(64) void md_size_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    const uint32_t len = (p.status[p.read_base + k] & 32) ? 0u : md_walk(p, k, lane, MdCount{});
+    if (lane == 0) p.md_len[k] = (int32_t)len;
+}
+
+// 'M' 'D' 'Z' text NUL behind the record's NM (bam_full_shape), behind emit_bam_full_kernel on its stream
+__global__ __launch_bounds__(64) void emit_md_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    if (p.rec_len[k] <= 0) return;
+    const BamFullShape s = bam_full_shape(p, k);
+    uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb;
+    if (lane < 3) o[lane] = (uint8_t)"MDZ"[lane];
+    const int64_t cap = p.md_len[k];
+    md_walk(p, k, lane, MdStore{o + 3, cap});
+    if (lane == 0) o[3 + cap] = 0;
 }
 
 }  // namespace npore

@@ -7,6 +7,7 @@
 #include "../../include/npore_amd.h"
 #include "hostio.hpp"
 #include "deflate_code.hpp"
+#include "md_rec.hpp"
 #include "nm_rec.hpp"
 
 #include <sys/uio.h>
@@ -656,10 +657,14 @@ inline int format_sam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
 //   - the tags are the input's aux bytes in input order minus NM MD cs de dv CG (hostio.hpp filter_aux); HP stays where
 //     and as it was, none is made when the input has none;
 //   - a recomputed NM (nm_rec.hpp) follows them as the smallest unsigned type: C, S, I (bam_hp_tag_bytes);
+//   - with NPORE_OUT_MD (`--md`) the MD tag (md_rec.hpp) follows NM: 'M' 'D' 'Z', the text, NUL -- 4 + its length bytes.  It is
+//     `samtools calmd`'s text but for what NM already differs in: an IUPAC letter other than N counts as a mismatch and
+//     prints as N.  Without the flag no MD is written (the input's is stale and dropped);
 //   - more than 65 535 operations, clips included: the CIGAR field holds the placeholder `l_seq << 4 | 4`,
-//     `reflen << 4 | 3` with the full l_seq, and CG:B,I with ALL the words goes behind NM.
-//   Size: 36 + l_read_name + 4 * n_cigar (8 when long) + (l_seq + 1) / 2 + l_seq + kept aux + 3 + {1, 2, 4} (+ 8 + 4 * n
-//   when long).
+//     `reflen << 4 | 3` with the full l_seq, and CG:B,I with ALL the words goes behind NM (behind MD where there is one:
+//     kept aux, NM, MD, CG).
+//   Size: 36 + l_read_name + 4 * n_cigar (8 when long) + (l_seq + 1) / 2 + l_seq + kept aux + 3 + {1, 2, 4} (+ 4 + MD text)
+//   (+ 8 + 4 * n when long).
 // FILE.  BGZF with STORED deflate members (level 0, what `samtools view -u` writes): 18 bytes of gzip header with the BC
 //   field, one stored block (01 LEN NLEN), the payload, CRC-32 and ISIZE -- payload + 31 bytes.  The header (text +
 //   reference list) lies in members of its own; the record stream is cut every 65 280 payload bytes counted from the
@@ -785,11 +790,9 @@ inline uint32_t cigar_op_code(char c)
 {
     return c == 'M' ? 0 : c == 'I' ? 1 : c == 'D' ? 2 : c == 'N' ? 3 : c == 'S' ? 4 : c == 'H' ? 5 : c == 'P' ? 6 : c == '=' ? 7 : 8;
 }
-// NM (nm_rec.hpp) of a final CIGAR text over the read's code arrays; -1: no CIGAR text
-inline int64_t nm_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl)
+// the words `len << 4 | op` of a final CIGAR text of `ops` operations (cigar_text_ops)
+inline std::vector<uint8_t> cigar_text_words(const char *t, int64_t n, int64_t ops)
 {
-    const int64_t ops = cigar_text_ops(t, n);
-    if (ops < 0) return -1;
     std::vector<uint8_t> words((size_t)ops * 4 + 4);
     uint32_t len = 0;
     uint8_t *o = words.data();
@@ -800,11 +803,28 @@ inline int64_t nm_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t 
         o += 4;
         len = 0;
     }
-    return nm_of_words(words.data(), ops, ref, rl, seq, sl);
+    return words;
 }
-// bam_record_into's twin for the FULL RECORD; nm: the read's NM (nm_of_text)
+// NM (nm_rec.hpp) of a final CIGAR text over the read's code arrays; -1: no CIGAR text
+inline int64_t nm_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl)
+{
+    const int64_t ops = cigar_text_ops(t, n);
+    if (ops < 0) return -1;
+    return nm_of_words(cigar_text_words(t, n, ops).data(), ops, ref, rl, seq, sl);
+}
+// MD (md_rec.hpp) of a final CIGAR text over the read's code arrays, sized and then written; false: no CIGAR text
+inline bool md_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, std::string &md)
+{
+    const int64_t ops = cigar_text_ops(t, n);
+    if (ops < 0) return false;
+    const std::vector<uint8_t> words = cigar_text_words(t, n, ops);
+    md.assign((size_t)md_size_of_words(words.data(), ops, ref, rl, seq, sl), '\0');
+    md_into_words(words.data(), ops, ref, rl, seq, sl, reinterpret_cast<uint8_t *>(&md[0]), (int64_t)md.size());
+    return true;
+}
+// bam_record_into's twin for the FULL RECORD; nm: the read's NM (nm_of_text); md: its MD text (md_of_text), or none
 inline int64_t bam_record_full_into(const RecView &r, const char *final_text, int64_t final_len, int32_t status, int64_t nm, uint8_t *dst,
-                                    BamRecMeta *meta = nullptr)
+                                    BamRecMeta *meta = nullptr, const std::string *md = nullptr)
 {
     if (status & NPORE_ST_BAD_INPUT) return 0;
     const RecCigar in_cg = rec_cigar(r);
@@ -816,7 +836,8 @@ inline int64_t bam_record_full_into(const RecView &r, const char *final_text, in
     const bool lng = n_cig > 0xFFFF;
     const int64_t l_seq = r.l_seq(), nb = (l_seq + 1) / 2, aux = filter_aux(r.aux(), r.end(), nullptr);
     const int l_rn = r.l_read_name(), nmb = bam_hp_tag_bytes(nm);
-    const int64_t size = 36 + l_rn + (lng ? 8 : 4 * n_cig) + nb + l_seq + aux + 3 + nmb + (lng ? 8 + 4 * n_cig : 0);
+    const int64_t mdb = md ? 4 + (int64_t)md->size() : 0;
+    const int64_t size = 36 + l_rn + (lng ? 8 : 4 * n_cig) + nb + l_seq + aux + 3 + nmb + mdb + (lng ? 8 + 4 * n_cig : 0);
     if (!dst) return size;
     const int64_t reflen = rec_ref_len(in_cg);
     auto w32 = [](uint8_t *o, uint32_t v) { std::memcpy(o, &v, 4); };
@@ -830,10 +851,10 @@ inline int64_t bam_record_full_into(const RecView &r, const char *final_text, in
     std::memcpy(o, r.name(), (size_t)l_rn);
     o += l_rn;
     uint8_t *const seq_at = lng ? o + 8 : o + 4 * n_cig;
-    if (lng) {                                       // the words go behind NM
+    if (lng) {                                       // the words go behind NM (and MD)
         w32(o, (uint32_t)l_seq << 4 | 4u);
         w32(o + 4, (uint32_t)reflen << 4 | 3u);
-        o = seq_at + nb + l_seq + aux + 3 + nmb;
+        o = seq_at + nb + l_seq + aux + 3 + nmb + mdb;
         std::memcpy(o, "CGBI", 4);
         w32(o + 4, (uint32_t)n_cig);
         o += 8;
@@ -859,13 +880,19 @@ inline int64_t bam_record_full_into(const RecView &r, const char *final_text, in
     o[0] = 'N'; o[1] = 'M';
     o[2] = (uint8_t)(nmb == 1 ? 'C' : nmb == 2 ? 'S' : 'I');
     { const uint32_t v = (uint32_t)nm; std::memcpy(o + 3, &v, (size_t)nmb); }
+    if (md) {
+        o += 3 + nmb;
+        std::memcpy(o, "MDZ", 3);
+        std::memcpy(o + 3, md->c_str(), md->size() + 1);
+    }
     if (meta) *meta = BamRecMeta{r.ref_id(), r.pos(), reflen, size};
     return size;
 }
-// the code arrays of a batch's reads (what align() got): FULL records count NM from them
+// the code arrays of a batch's reads (what align() got): FULL records count NM from them, and write MD from them (md)
 struct ReadCodes {
     const uint8_t *refs; const int64_t *ref_off;
     const uint8_t *seqs; const int64_t *seq_off;
+    bool md = false;
 };
 
 // format_sam_into's twin for BAM records: the kept reads' records one after the other in `out`, *out_len bytes;
@@ -877,16 +904,21 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     if (!b || n < 0 || !out_len || (n > 0 && (!finals || !final_off || !final_len || !status)))
         return fail(NPORE_E_INVALID, "bad argument");
     std::vector<int64_t> off((size_t)n + 1, 0), nm(full ? (size_t)n : 0, 0);
+    std::vector<std::string> md(full && full->md ? (size_t)n : 0);
     std::atomic<int> bad{0};
-    // (full: the FULL RECORD, its NM counted once, between the two passes)
+    // (full: the FULL RECORD, its NM counted and its MD written once, between the two passes)
     auto record = [&](int64_t k, uint8_t *dst, BamRecMeta *m) {
-        return full ? bam_record_full_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], nm[(size_t)k], dst, m)
+        return full ? bam_record_full_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], nm[(size_t)k], dst, m,
+                                           full->md ? &md[(size_t)k] : nullptr)
                     : bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], dst, m);
     };
     parallel_for(n, threads, [&](int64_t k) {
-        if (full && !(status[k] & NPORE_ST_BAD_INPUT))
-            nm[(size_t)k] = nm_of_text(finals + final_off[k], final_len[k], full->refs + full->ref_off[k], full->ref_off[k + 1] - full->ref_off[k],
-                                       full->seqs + full->seq_off[k], full->seq_off[k + 1] - full->seq_off[k]);
+        if (full && !(status[k] & NPORE_ST_BAD_INPUT)) {
+            const uint8_t *ref = full->refs + full->ref_off[k], *seq = full->seqs + full->seq_off[k];
+            const int64_t rl = full->ref_off[k + 1] - full->ref_off[k], sl = full->seq_off[k + 1] - full->seq_off[k];
+            nm[(size_t)k] = nm_of_text(finals + final_off[k], final_len[k], ref, rl, seq, sl);
+            if (full->md) md_of_text(finals + final_off[k], final_len[k], ref, rl, seq, sl, md[(size_t)k]);
+        }
         const int64_t sz = record(k, nullptr, nullptr);
         if (sz < 0) bad++;
         off[(size_t)k + 1] = std::max<int64_t>(sz, 0);

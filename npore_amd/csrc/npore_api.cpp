@@ -1416,12 +1416,20 @@ struct PackedCodes {
 int npore_bam_format_bam_full(npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
                               const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
                               const uint8_t **recs, int64_t *recs_len)
+{
+    return npore_bam_format_bam_full_md(b, fa, fasta_of_ref, idx, n, finals, final_off, final_len, status, threads, recs, recs_len, 0);
+}
+
+// ... with flags: NPORE_OUT_MD, the MD tag behind NM (0: the records above)
+int npore_bam_format_bam_full_md(npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
+                                 const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
+                                 const uint8_t **recs, int64_t *recs_len, int flags)
 try {
-    if (!pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs) return fail(NPORE_E_INVALID, "bad argument");
+    if (!pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs || (flags & ~NPORE_OUT_MD)) return fail(NPORE_E_INVALID, "bad argument");
     if (int rc = fetch_records(b, idx, n, threads, b->api_fetch)) return rc;
     PackedCodes pc;
     if (int rc = pc.pack(b, b->api_fetch, fa, fasta_of_ref, n, threads)) return rc;
-    const ReadCodes codes{pc.refs.data(), pc.ro.data(), pc.seqs.data(), pc.so.data()};
+    const ReadCodes codes{pc.refs.data(), pc.ro.data(), pc.seqs.data(), pc.so.data(), (flags & NPORE_OUT_MD) != 0};
     const int rc = format_bam_into(b, b->api_fetch, n, finals, final_off, final_len, status, threads, b->recs, recs_len, nullptr, &codes);
     *recs = reinterpret_cast<const uint8_t *>(b->recs.p);
     return rc;
@@ -1433,9 +1441,19 @@ NPORE_CATCH_INT
 int npore_debug_format_bam_full_device(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
                                        int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status,
                                        uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm)
+{
+    return npore_debug_format_bam_full_md_device(ctx, b, fa, fasta_of_ref, idx, n, finals, final_off, final_len, status, recs, cap, recs_len, nm, 0, nullptr);
+}
+
+// ... with flags: NPORE_OUT_MD puts md_size_kernel in front of the placement and emit_md_kernel behind the records; the
+// reads' MD text lengths to md_len[n]
+int npore_debug_format_bam_full_md_device(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
+                                          int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status,
+                                          uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm, int flags, int32_t *md_len)
 try {
-    if (!ctx || !pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs_len || cap < 0 || (cap > 0 && !recs) ||
-        (n > 0 && (!finals || !final_off || !final_len || !status || !nm)))
+    const bool md = (flags & NPORE_OUT_MD) != 0;
+    if (!ctx || !pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs_len || cap < 0 || (cap > 0 && !recs) || (flags & ~NPORE_OUT_MD) ||
+        (n > 0 && (!finals || !final_off || !final_len || !status || !nm || (md && !md_len))))
         return fail(NPORE_E_INVALID, "bad argument");
     *recs_len = 0;
     if (n == 0) return NPORE_OK;
@@ -1476,9 +1494,12 @@ try {
             std::memcpy(o, &w, 4);
             o += 4;
             len = 0;
+            // (MD: a caller's final may cover more reference than the read has -- three bytes per position it covers, 11 per word)
+            if (md) bound += 3 * (int64_t)((nm_consumes(w & 15u) & 1u) ? w >> 4 : 0u) + 11;
         }
+        if (md) bound += 4 + 11;
     }
-    DevBuf d_raw, d_off, d_words, d_wlen, d_aux, d_status, d_refs, d_seqs, d_cigs, d_recs, d_cursor, d_rec_off, d_rec_len, d_nm;
+    DevBuf d_md, d_raw, d_off, d_words, d_wlen, d_aux, d_status, d_refs, d_seqs, d_cigs, d_recs, d_cursor, d_rec_off, d_rec_len, d_nm;
     if (int rc = d_raw.ensure(raw.size())) return rc;
     if (int rc = d_off.ensure(off.size() * 8)) return rc;
     if (int rc = d_words.ensure(words.size())) return rc;
@@ -1489,6 +1510,7 @@ try {
     if (int rc = d_cursor.ensure(64)) return rc;
     if (int rc = d_status.ensure(N * 4 + 64)) return rc;
     if (int rc = d_nm.ensure(N * 4 + 64)) return rc;
+    if (int rc = md ? d_md.ensure(N * 4 + 64) : 0) return rc;
     for (DevBuf *d : {&d_wlen, &d_aux, &d_rec_off, &d_rec_len})
         if (int rc = d->ensure(N * 8 + 64)) return rc;
     HIP_TRY(hipMemcpy(d_raw.p, raw.data(), raw.size(), hipMemcpyHostToDevice));
@@ -1516,9 +1538,12 @@ try {
     bp.recs = d_recs.as<uint8_t>(); bp.cap = bound; bp.cursor = d_cursor.as<unsigned long long>();
     bp.rec_off = d_rec_off.as<int64_t>(); bp.rec_len = d_rec_len.as<int64_t>();
     bp.refs = up.refs; bp.seqs = up.seqs; bp.nm = d_nm.as<int32_t>();
+    if (md) bp.md_len = d_md.as<int32_t>();
     hipLaunchKernelGGL(nm_count_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
+    if (md) hipLaunchKernelGGL(md_size_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
     hipLaunchKernelGGL(place_bam_full_kernel, dim3(1), dim3(256), 0, st, bp);
     hipLaunchKernelGGL(emit_bam_full_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
+    if (md) hipLaunchKernelGGL(emit_md_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     unsigned long long total = 0;
@@ -1526,6 +1551,7 @@ try {
     HIP_TRY(hipMemcpy(&total, d_cursor.p, 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rlen.data(), d_rec_len.p, N * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(nm, d_nm.p, N * 4, hipMemcpyDeviceToHost));
+    if (md) HIP_TRY(hipMemcpy(md_len, d_md.p, N * 4, hipMemcpyDeviceToHost));
     int64_t sum = 0;
     for (size_t k = 0; k < N; k++) {
         if (rlen[k] < 0) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
@@ -1542,7 +1568,8 @@ NPORE_CATCH_INT
 int npore_bam_set_output(npore_bam *b, int format, const char *bai_path, int flags)
 {
     if (!b || (format != NPORE_OUT_SAM && format != NPORE_OUT_BAM) ||
-        (flags & ~(NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE | NPORE_OUT_MATCH | NPORE_OUT_FULL)) ||
+        (flags & ~(NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE | NPORE_OUT_MATCH | NPORE_OUT_FULL | NPORE_OUT_MD)) ||
+        ((flags & NPORE_OUT_MD) && !(flags & NPORE_OUT_FULL)) ||               // (MD is a tag of the FULL records)
         ((flags & (NPORE_OUT_DEFLATE | NPORE_OUT_FULL)) && format != NPORE_OUT_BAM) || ((flags & NPORE_OUT_MATCH) && !(flags & NPORE_OUT_DEFLATE)) ||
         ((flags & NPORE_OUT_FULL) && !(flags & (NPORE_OUT_EOF | NPORE_OUT_PART))))      // (a FULL run says what it writes: the end of a file or a rank's part)
         return fail(NPORE_E_INVALID, "bad argument");

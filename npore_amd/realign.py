@@ -68,6 +68,10 @@ def argparser():
                         help="--out_format bam: `reference`, each record is the reference's SAM line in binary (clips cut off, mate "
                              "fields cleared, HP the only tag); `full`, the input record with only what the realignment changes "
                              "replaced: clipped bases, mate fields and tags stay (NM MD cs de dv dropped), NM recounted on the GPU.")
+    parser.add_argument("--md", action="store_true",
+                        help="--records full: write the MD tag behind the recounted NM, built on the GPU from the final CIGAR and the "
+                             "bases NM is counted on (`samtools calmd`'s text, but an IUPAC letter other than N counts as a mismatch "
+                             "and prints as N, as it does in NM).  Without it the records carry no MD: the input's is stale.")
     parser.add_argument("--python_io", action="store_true",
                         help="Use the pure-Python BAM reader / SAM writer (the restatement the native one is tested against).")
     return parser
@@ -81,6 +85,10 @@ def main():
     records = getattr(cfg.args, "records", "reference")
     if records == "full" and getattr(cfg.args, "out_format", "sam") != "bam":
         print("\nERROR: --records full needs --out_format bam.")
+        sys.exit(1)
+    md = bool(getattr(cfg.args, "md", False))
+    if md and records != "full":
+        print("\nERROR: --md needs --records full.")
         sys.exit(1)
     if records == "full" and not native:
         print("\nERROR: --records full is written by the library's file pipeline: not with --python_io.")
@@ -149,7 +157,7 @@ def main():
         open(out_sam, "w").close()
     # BAM: the index beside the file (a rank's part: a sidecar with part-relative offsets, merged by dist.gather_bam_parts);
     # the EOF member ends the whole file, not a part
-    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress, records=records) if as_bam else {}
+    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress, records=records, md=md) if as_bam else {}
     gather = dist_mod.gather_bam_parts if as_bam else dist_mod.gather_parts
 
     print("> extracting read data from BAM")

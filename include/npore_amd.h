@@ -221,7 +221,13 @@ int npore_total_timing(npore_ctx *ctx, double *ms, int n);
  * (src/bam.pyx:65-78) on the device, 0 = on the host from the op strings; "device_pack" (default 1, with the device
  * glue): align()'s inputs (src/bam.pyx:42, 45, 59-61) unpacked from the BAM records on the device, 0 = packed on the
  * host and uploaded.  "cms_batch_reads" (default 4000): records per batch of npore_bam_confusion and
- * npore_bam_purity.  "purity_window" (default 2^22, 64 .. 2^24): positions per counter window of npore_bam_purity. */
+ * npore_bam_purity.  "purity_window" (default 2^22, 64 .. 2^24): positions per counter window of npore_bam_purity.
+ * "device_inflate" (default 0): the one-pass BAM readers of npore_bam_confusion, npore_bam_purity and
+ * npore_bam_realign_sequential inflate the file's BGZF blocks on the device (csrc/inflate_kernels.hpp: one wave per block,
+ * one launch per window of NPORE_BAM_WINDOW_BLOCKS blocks, 4096 by default in this mode) instead of on the host's threads;
+ * the host still checks every block's CRC-32 and inflates what the device declined.  The results are the same either
+ * way.  During a realignment the inflate kernel waits for the fill kernel's persistent workgroups and takes turns with
+ * them: that combination is tested for equal output only, not for speed.  The indexed readers are not affected. */
 int npore_ctx_set(npore_ctx *ctx, const char *key, int64_t value);
 
 /* Batch sizing.  The DP of a chunk (at most max_b_rows anti-diagonals of a read; reference src/aln.pyx:344-358,
@@ -419,6 +425,12 @@ int npore_bam_set_share(npore_bam *bam, int rank, int world, const char *bai_pat
 /* out4: [0] a share is set, [1] / [2] its first byte and its end in the inflated stream (-1: nothing / the end of the
  * file), [3] the BGZF block it begins in (tests). */
 int npore_bam_share_info(const npore_bam *bam, int64_t *out4);
+/* The BGZF inflation of the last npore_bam_confusion / npore_bam_purity / npore_bam_realign_sequential on the handle under
+ * "device_inflate" (npore_ctx_set): out8 = [0] blocks inflated on the device, [1] blocks the device declined that the host
+ * inflated, [2] blocks the device accepted whose CRC-32 failed, then given to the host, [3] launches, [4] nanoseconds of the
+ * kernel alone (events), [5] compressed bytes copied up, [6] inflated bytes copied down, [7] 1 if the device inflation was
+ * installed.  All zeros after a run that inflated on the host. */
+int npore_bam_inflate_info(const npore_bam *bam, int64_t *out8);
 int npore_bam_realign_sequential(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref,
                                  int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
                                  int64_t max_reads, int64_t batch_reads, float indel_start, float indel_extend,
@@ -506,6 +518,18 @@ int npore_debug_inflate(const uint8_t *in, int64_t in_len, uint8_t *out, int64_t
  * or a negative NPORE_E_* code. */
 int npore_debug_inflate_pair(const uint8_t *in_a, int64_t in_len_a, uint8_t *out_a, int64_t out_len_a, const uint8_t *in_b,
                              int64_t in_len_b, uint8_t *out_b, int64_t out_len_b, int force);
+/* The device decoder of "device_inflate" (csrc/inflate_wave.hpp, one wave per stream) on n independent raw DEFLATE
+ * streams in ONE launch: stream k is in[in_off[k] .. in_off[k] + in_len[k]) and must inflate to exactly out_len[k]
+ * (<= 65 536) bytes at out + out_off[k]; every range must lie inside in[in_bytes] / out[out_bytes].  The whole of `out` is
+ * copied up first and copied down whole afterwards, so bytes between and around the streams' ranges come back as they
+ * went in unless the kernel wrote there.  status[k]: 1 = inflated, 0 = malformed, or declined as csrc/inflate.hpp declines
+ * (a literal / length code of a single symbol).  Returns NPORE_OK or a negative NPORE_E_* code. */
+int npore_debug_inflate_device(npore_ctx *ctx, const uint8_t *in, int64_t in_bytes, const int64_t *in_off, const int64_t *in_len,
+                               uint8_t *out, int64_t out_bytes, const int64_t *out_off, const int64_t *out_len, int64_t n,
+                               int32_t *status);
+/* The host twin of that decoder: the same code with the loop over a wave's lanes written out.  Host code, no GPU. */
+int npore_debug_inflate_wave_host(const uint8_t *in, int64_t in_bytes, const int64_t *in_off, const int64_t *in_len, uint8_t *out,
+                                  int64_t out_bytes, const int64_t *out_off, const int64_t *out_len, int64_t n, int32_t *status);
 /* The CRC-32 (RFC 1952) the BGZF readers check every member's inflated bytes with (csrc/crc32.hpp: folding by carry-less
  * multiplication where the CPU has it): crc32(crc, p, n) of zlib, `crc` = the value so far (0 at the start).  Returns the
  * new value (0 ... 2^32 - 1) or a negative NPORE_E_* code.  Host code, no GPU. */

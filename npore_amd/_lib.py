@@ -102,6 +102,11 @@ SIGNATURES = {
     "npore_bam_file_timing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "npore_debug_inflate": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int]),
     "npore_debug_inflate_pair": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int]),
+    "npore_debug_inflate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.c_void_p, C.c_int64, C.c_void_p]),
+    "npore_debug_inflate_wave_host": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                C.c_int64, C.c_void_p]),
+    "npore_bam_inflate_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "npore_debug_crc32": (C.c_int64, [C.c_void_p, C.c_int64, C.c_uint32]),
     "npore_debug_deflate_member": (C.c_int64, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "npore_debug_deflate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,

@@ -1241,6 +1241,16 @@ class NativeBam:
         self._check(self._lib.npore_bam_output_info(self.handle, info.ctypes.data))
         return dict(zip(("records", "stream_bytes", "indexed", "file_bytes"), (int(x) for x in info)))
 
+    def inflate_info(self):
+        """Of the last confusion / purity / realign_sequential run on the handle, the BGZF inflation on the device
+        (Context.set("device_inflate", 1); npore_bam_inflate_info): blocks inflated on the device, blocks it declined that
+        the host inflated, blocks whose CRC failed and went to the host, launches, nanoseconds of the kernel alone,
+        compressed bytes copied up, inflated bytes copied down, 1 if the device inflation was installed.  All zeros after a
+        run that inflated on the host."""
+        info = np.zeros(8, np.int64)
+        self._check(self._lib.npore_bam_inflate_info(self.handle, info.ctypes.data))
+        return tuple(int(x) for x in info)
+
     def _after_bam_run(self, out_format):
         if out_format == "bam" and self.output_info()["indexed"] < 0:
             print(NOT_SORTED_MSG)
@@ -1560,6 +1570,7 @@ def get_confusion_matrices():
             # straight from the records, on the GPU (confusion_from_bam): an annotation-only context of its own
             from . import aln
             ctx = aln.Context(None, None, device=int(getattr(cfg.args, "device", 0)) % max(aln.device_count(), 1))
+            ctx.set("device_inflate", getattr(cfg.args, "bam_inflate", "host") == "device")
             try:
                 *total, tallies = confusion_from_bam(ctx, cfg.args.bam, cfg.args.ref, ranges, min_bq=cfg.args.cms_min_bq,
                                                      exclude_flags=cfg.args.cms_exclude_flags)

@@ -122,6 +122,7 @@ struct npore_ctx {
     int device_glue = 1;        // BAM -> SAM pipeline: realign_read's glue on the device (0: on the host, from the op strings)
     int coresident = 1;         // kernel shapes that fit beside a fill kernel for a group that overlaps another one's
     int device_pack = 1;        // BAM -> SAM pipeline with the glue on the device: align()'s inputs unpacked from the records on the device
+    int device_inflate = 0;     // one-pass BAM readers: the BGZF blocks inflated on the device (inflate_kernels.hpp), 0: on the host's threads
     // device pack: the FASTA of the current run on the device (uploaded once per FASTA), the contig of every BAM reference
     DevBuf d_fasta, d_ctg;
     DevBuf d_stream_pos;        // BAM out, NPORE_OUT_DEFLATE: where the next batch's records begin in the run's record stream (8 bytes)

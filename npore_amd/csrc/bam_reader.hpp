@@ -1253,8 +1253,12 @@ struct BamWindow {
 class BamWindowSource {
 public:
     static constexpr size_t HEAD = 4u << 20;
-    BamWindowSource(const npore_bam *b, int threads) : b_(b), inflate_threads_(threads)
+    // inflate: who inflates a window's blocks in place of bgzf_inflate_range (empty: nobody).  With one, a window is 4096
+    // blocks by default: the device decoder (inflate_kernels.hpp) runs one wave per block, and 1024 of them are one wave
+    // per SIMD -- a dependent chain with nobody to hide it
+    BamWindowSource(const npore_bam *b, int threads, BgzfInflateFn inflate = nullptr) : b_(b), inflate_threads_(threads), inflate_(std::move(inflate))
     {
+        if (inflate_) win_blocks_ = 4096;
         if (const char *e = std::getenv("NPORE_BAM_WINDOW_BLOCKS")) win_blocks_ = (size_t)std::max(1, std::atoi(e));
         if (const char *e = std::getenv("NPORE_BAM_WINDOWS_AHEAD")) depth_ = std::max(1, std::atoi(e));
         if (const char *e = std::getenv("NPORE_INFLATE_THREADS")) inflate_threads_ = std::max(1, std::atoi(e));
@@ -1285,7 +1289,10 @@ public:
             ready_.pop_front();
         }
         cv_.notify_all();
-        if (!pd.ok || pd.b0 != next_block_) { fail(NPORE_E_INVALID, "corrupt BGZF block (or out of memory)"); return -1; }
+        if (!pd.ok || pd.b0 != next_block_) {
+            fail(NPORE_E_INVALID, pd.err.empty() ? std::string("corrupt BGZF block (or out of memory)") : pd.err);
+            return -1;
+        }
         std::shared_ptr<RawBuf> nw = pd.buf;
         uint8_t *d0 = reinterpret_cast<uint8_t *>(nw->p) + HEAD;
         if (c > HEAD) {                                          // a record longer than the room in front: copy once
@@ -1305,7 +1312,7 @@ public:
     }
 
 private:
-    struct Pending { std::shared_ptr<RawBuf> buf; size_t bytes = 0, b0 = 0, b1 = 0; bool ok = false; };
+    struct Pending { std::shared_ptr<RawBuf> buf; size_t bytes = 0, b0 = 0, b1 = 0; bool ok = false; std::string err; };
     void inflate_ahead(size_t b0)                                // the inflater thread
     {
         const size_t end = b_->blocks.size();
@@ -1322,8 +1329,13 @@ private:
             pd.bytes = (size_t)(w1 - w0);
             try {                                                // (no exception may leave a thread: next() sees ok == false)
                 pd.buf = std::make_shared<RawBuf>();
-                pd.ok = pd.buf->ensure(HEAD + pd.bytes + 8) &&
-                        bgzf_inflate_range(*b_->file, b_->blocks, b0, pd.b1, reinterpret_cast<uint8_t *>(pd.buf->p) + HEAD, inflate_threads_);
+                uint8_t *const d = pd.buf->ensure(HEAD + pd.bytes + 8) ? reinterpret_cast<uint8_t *>(pd.buf->p) + HEAD : nullptr;
+                if (d && inflate_) {
+                    pd.ok = inflate_(*b_->file, b_->blocks, b0, pd.b1, d, inflate_threads_);
+                    if (!pd.ok) pd.err = g_err;                  // (the hook's words are this thread's: next() passes them on)
+                } else {
+                    pd.ok = d && bgzf_inflate_range(*b_->file, b_->blocks, b0, pd.b1, d, inflate_threads_);
+                }
             } catch (...) {
                 pd.ok = false;
             }
@@ -1338,6 +1350,7 @@ private:
     const npore_bam *b_;
     size_t win_blocks_ = 1024;
     int depth_ = 3, inflate_threads_;
+    BgzfInflateFn inflate_;
     size_t next_block_ = 0;                  // the block the next window begins with (the walking thread's)
     std::mutex m_;                           // guards ready_, stop_, ended_
     std::condition_variable cv_;
@@ -1367,8 +1380,8 @@ inline int one_pass_args_check(const npore_bam *b, int n_regions, const int32_t 
 class BamRecordWalker {
 public:
     BamRecordWalker(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
-                    int64_t max_reads, int threads, uint32_t drop_flags = 0x100 | 0x800 | 0x4)
-        : b_(b), src_(b, threads), n_regions_(n_regions), ref_id_(ref_id), start_(start), stop_(stop), max_reads_(max_reads),
+                    int64_t max_reads, int threads, uint32_t drop_flags = 0x100 | 0x800 | 0x4, BgzfInflateFn inflate = nullptr)
+        : b_(b), src_(b, threads, std::move(inflate)), n_regions_(n_regions), ref_id_(ref_id), start_(start), stop_(stop), max_reads_(max_reads),
           drop_flags_(drop_flags), done_(n_regions == 0)
     {
         if (!b->has_share) return;

@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -475,6 +476,9 @@ inline bool bgzf_inflate_range(const PreadFile &f, const std::vector<BgzfBlock> 
     });
     return bad == 0;
 }
+// ... or by whoever the caller names (BamWindowSource's hook: the same arguments, the same result; what fail() was given on
+// the calling thread says why not).  The HIP unit's DeviceInflater (inflate_kernels.hpp) is one; this file knows none.
+using BgzfInflateFn = std::function<bool(const PreadFile &, const std::vector<BgzfBlock> &, size_t, size_t, uint8_t *, int)>;
 
 // Virtual offsets of a .bai index's LINEAR index (SAM specification 5.2: per reference, for every 16 kb window the
 // virtual file offset -- compressed offset of a BGZF block << 16 | offset inside the inflated block -- of the first
@@ -574,6 +578,7 @@ struct npore_bam {
     int out_format = 0, out_flags = 0;
     std::string out_bai;
     int64_t out_info[4] = {0, 0, 0, 0};
+    int64_t inflate_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the device inflation of the last run on the handle (npore_bam_inflate_info)
     npore::RawBuf recs;                   // record bytes of the last npore_bam_format_bam
     double stage_ms[4] = {0, 0, 0, 0};    // last npore_bam_realign_batch: pack, align, standardise, format
     double file_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // last npore_bam_realign_file (npore_bam_file_timing)

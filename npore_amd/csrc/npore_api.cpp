@@ -28,6 +28,7 @@
 #include "bam_emit_kernels.hpp"
 #include "confusion_kernels.hpp"
 #include "purity_kernels.hpp"
+#include "inflate_kernels.hpp"
 #include "align_engine.hpp"
 #include "file_pipeline.hpp"
 
@@ -38,6 +39,23 @@
 #define NPORE_CATCH_PTR                                                                             \
     catch (const std::bad_alloc &) { fail(NPORE_E_NOMEM, "out of host memory"); return nullptr; }  \
     catch (const std::exception &e) { fail(NPORE_E_INVALID, std::string("internal: ") + e.what()); return nullptr; }
+
+namespace {
+// The device inflation of ONE run on a handle (npore_ctx_set "device_inflate"): made in front of the run's BamRecordWalker,
+// so that the walker -- and its inflater thread, the hook's only caller -- has gone when this does; leaves what
+// npore_bam_inflate_info reports on the handle (all zeros after a host run).
+struct InflateRun {
+    npore_bam *b;
+    std::unique_ptr<npore::DeviceInflater> dev;
+    InflateRun(const npore_ctx *ctx, npore_bam *b_) : b(b_)
+    {
+        for (int64_t &v : b->inflate_info) v = 0;
+        if (ctx->device_inflate) dev.reset(new npore::DeviceInflater(ctx->device));
+    }
+    ~InflateRun() { if (dev) dev->info(b->inflate_info); }
+    npore::BgzfInflateFn hook() const { return dev ? dev->hook() : npore::BgzfInflateFn(); }
+};
+}  // namespace
 
 extern "C" {
 
@@ -383,6 +401,7 @@ try {
     else if (k == "coresident") ctx->coresident = value != 0;
     else if (k == "device_glue") ctx->device_glue = value != 0;
     else if (k == "device_pack") ctx->device_pack = value != 0;
+    else if (k == "device_inflate") ctx->device_inflate = value != 0;
     else if (k == "cms_batch_reads") { if (value < 1) return fail(NPORE_E_INVALID, "cms_batch_reads: at least 1"); ctx->cms_batch_reads = value; }
     else if (k == "purity_window") { if (value < 64 || value > (1ll << 24)) return fail(NPORE_E_INVALID, "purity_window: 64 .. 2^24"); ctx->purity_window = value; }
     else if (k == "fill_streams") { if (value < 1 || value > 2) return fail(NPORE_E_INVALID, "fill_streams: 1 or 2"); ctx->fill_streams = (int)value; }
@@ -596,12 +615,13 @@ try {
     const bool one_pass = b->file && !b->blocks.empty() && b->rec_off.empty();
     const int threads = 0;
     const int64_t batch_reads = ctx->cms_batch_reads;
+    InflateRun infl(ctx, b);
     std::unique_ptr<BamRecordWalker> walker;
     std::vector<int64_t> idx;
     int64_t idx_at = 0;
     if (one_pass) {
         if (int rc = one_pass_args_check(b, (int)h_rid.size(), h_rid.data(), 0)) return rc;
-        walker.reset(new BamRecordWalker(b, (int)h_rid.size(), h_rid.data(), h_lo.data(), h_hi.data(), 0, threads, 0u));
+        walker.reset(new BamRecordWalker(b, (int)h_rid.size(), h_rid.data(), h_lo.data(), h_hi.data(), 0, threads, 0u, infl.hook()));
     } else {
         const int64_t k = bam_select(b, (int)h_rid.size(), h_rid.data(), h_lo.data(), h_hi.data(), 0, nullptr, 0, 0u);
         if (k < 0) return (int)k;
@@ -1028,11 +1048,12 @@ try {
 
     const bool one_pass = b->file && !b->blocks.empty() && b->rec_off.empty();
     const int threads = 0;
+    InflateRun infl(ctx, b);
     if (one_pass) {
         // ONE PASS over a coordinate-sorted file: the windows advance with the records; a record that reaches past the
         // window's end is carried (a copy of its head) into the next one
         if (int rc = one_pass_args_check(b, (int)h_rid.size(), h_rid.data(), 0)) return rc;
-        BamRecordWalker walker(b, (int)h_rid.size(), h_rid.data(), h_lo.data(), h_hi.data(), 0, threads, 0u);
+        BamRecordWalker walker(b, (int)h_rid.size(), h_rid.data(), h_lo.data(), h_hi.data(), 0, threads, 0u, infl.hook());
         std::vector<std::shared_ptr<RawBuf>> keep;
         struct Carried { std::vector<uint8_t> bytes; int64_t w1, ins_ops; };
         std::vector<Carried> carry;
@@ -1163,6 +1184,62 @@ int npore_debug_inflate_pair(const uint8_t *in_a, int64_t in_len_a, uint8_t *out
     if (ob && (std::memcmp(out_b, cb.data(), (size_t)out_len_b) || std::memcmp(out_b, cb.data() + out_len_b, (size_t)out_len_b)))
         return fail(NPORE_E_INVALID, "copies of stream b differ");
     return (oa ? 1 : 0) | (ob ? 2 : 0);
+}
+
+// n streams and where their bytes go: every range inside its buffer, no stream longer than a BGZF member's
+static bool inflate_wave_args_ok(const uint8_t *in, int64_t in_bytes, const int64_t *in_off, const int64_t *in_len, const uint8_t *out, int64_t out_bytes,
+                                 const int64_t *out_off, const int64_t *out_len, int64_t n, const int32_t *status)
+{
+    if (n < 0 || in_bytes < 0 || out_bytes < 0 || (in_bytes > 0 && !in) || (out_bytes > 0 && !out)) return false;
+    if (n > 0 && (!in_off || !in_len || !out_off || !out_len || !status)) return false;
+    for (int64_t k = 0; k < n; k++)
+        if (in_off[k] < 0 || in_len[k] < 0 || in_len[k] > (int64_t)IW_MAX_IN || in_off[k] > in_bytes - in_len[k] || out_off[k] < 0 || out_len[k] < 0 ||
+            out_len[k] > (int64_t)IW_MAX_OUT || out_off[k] > out_bytes - out_len[k])
+            return false;
+    return true;
+}
+
+int npore_debug_inflate_wave_host(const uint8_t *in, int64_t in_bytes, const int64_t *in_off, const int64_t *in_len, uint8_t *out, int64_t out_bytes,
+                                  const int64_t *out_off, const int64_t *out_len, int64_t n, int32_t *status)
+{
+    if (!inflate_wave_args_ok(in, in_bytes, in_off, in_len, out, out_bytes, out_off, out_len, n, status)) return fail(NPORE_E_INVALID, "bad argument");
+    inflate_wave_host(in, in_off, in_len, out, out_off, out_len, n, status);
+    return NPORE_OK;
+}
+
+int npore_debug_inflate_device(npore_ctx *ctx, const uint8_t *in, int64_t in_bytes, const int64_t *in_off, const int64_t *in_len, uint8_t *out,
+                               int64_t out_bytes, const int64_t *out_off, const int64_t *out_len, int64_t n, int32_t *status)
+try {
+    if (!ctx || !inflate_wave_args_ok(in, in_bytes, in_off, in_len, out, out_bytes, out_off, out_len, n, status)) return fail(NPORE_E_INVALID, "bad argument");
+    if (int rc = quiesce(ctx)) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (n == 0) return NPORE_OK;
+    DevBuf d_in, d_out, d_meta;
+    if (int rc = d_in.ensure((size_t)in_bytes + 64)) return rc;
+    if (int rc = d_out.ensure((size_t)out_bytes + 64)) return rc;
+    if (int rc = d_meta.ensure((size_t)n * 36)) return rc;
+    int64_t *const dm = d_meta.as<int64_t>();
+    int32_t *const d_status = reinterpret_cast<int32_t *>(dm + 4 * n);
+    hipStream_t s = ctx->s_post;
+    if (in_bytes > 0) HIP_TRY(hipMemcpyAsync(d_in.p, in, (size_t)in_bytes, hipMemcpyHostToDevice, s));
+    if (out_bytes > 0) HIP_TRY(hipMemcpyAsync(d_out.p, out, (size_t)out_bytes, hipMemcpyHostToDevice, s));
+    const int64_t *const host4[4] = {in_off, in_len, out_off, out_len};
+    for (int q = 0; q < 4; q++) HIP_TRY(hipMemcpyAsync(dm + q * n, host4[q], (size_t)n * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_status, 0, (size_t)n * 4, s));
+    launch_inflate_blocks(d_in.as<uint8_t>(), dm, dm + n, d_out.as<uint8_t>(), dm + 2 * n, dm + 3 * n, n, d_status, s);
+    HIP_TRY(hipGetLastError());
+    if (out_bytes > 0) HIP_TRY(hipMemcpyAsync(out, d_out.p, (size_t)out_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return NPORE_OK;
+}
+NPORE_CATCH_INT
+
+int npore_bam_inflate_info(const npore_bam *b, int64_t *out8)
+{
+    if (!b || !out8) return fail(NPORE_E_INVALID, "null argument");
+    for (int k = 0; k < 8; k++) out8[k] = b->inflate_info[k];
+    return NPORE_OK;
 }
 
 int64_t npore_debug_crc32(const uint8_t *p, int64_t n, uint32_t crc)
@@ -1688,7 +1765,8 @@ try {
     if (int rc = one_pass_args_check(b, n_regions, ref_id, max_reads)) return rc;
     counts[0] = counts[1] = counts[2] = 0;
     HIP_TRY(hipSetDevice(ctx->device));
-    BamRecordWalker walker(b, n_regions, ref_id, start, stop, max_reads, threads);
+    InflateRun infl(ctx, b);
+    BamRecordWalker walker(b, n_regions, ref_id, start, stop, max_reads, threads, 0x100 | 0x800 | 0x4, infl.hook());
     RunOutput out;
     if (int rco = out.open(b, out_path, threads)) return rco;
     int64_t n_bad = 0, ordinal0 = 0;

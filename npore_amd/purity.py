@@ -155,6 +155,9 @@ def argparser():
     p.add_argument("--min_bq", type=int, default=13, help="entries of lower base quality are dropped (mpileup -Q)")
     p.add_argument("--exclude_flags", type=lambda x: int(x, 0), default=0x704, help="records with one of these flag bits are left out")
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--bam_inflate", choices=("host", "device"), default="host",
+                   help="one-pass reader: the BAMs' BGZF blocks are inflated on the CPU threads, or on the GPU, one wave per block; "
+                        "the histograms are the same")
     p.add_argument("--max_score_positions", type=int, default=50_000_000,
                    help="PREFIX{idx}.npy (the per-position scores) is written only for regions of at most this many positions")
     return p
@@ -165,6 +168,9 @@ def main(argv=None):
     from .bam import NativeBam
     args = argparser().parse_args(argv)
     ctx = aln.Context(None, None, max_n=6, max_l=100, device=args.device)
+    ctx.set("device_inflate", args.bam_inflate == "device")
+    if args.bam_inflate == "device" and os.environ.get("NPORE_BAM_ONE_PASS", "1") == "0":
+        print("    (--bam_inflate device has no effect: the indexed reader inflates on the host)")
     report, hists = {"bams": []}, []
     try:
         for idx, path in enumerate(args.bams):

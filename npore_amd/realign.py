@@ -72,6 +72,10 @@ def argparser():
                         help="--records full: write the MD tag behind the recounted NM, built on the GPU from the final CIGAR and the "
                              "bases NM is counted on (`samtools calmd`'s text, but an IUPAC letter other than N counts as a mismatch "
                              "and prints as N, as it does in NM).  Without it the records carry no MD: the input's is stale.")
+    parser.add_argument("--bam_inflate", choices=("host", "device"), default="host",
+                        help="One-pass reader: where the input BAM's BGZF blocks are inflated: `host`, on the CPU threads; `device`, "
+                             "on the GPU, one wave per block (also for --recalc_cms --cms_source bam).  The output is the same.  "
+                             "During the realignment the inflate kernel takes turns with the fill kernel.")
     parser.add_argument("--python_io", action="store_true",
                         help="Use the pure-Python BAM reader / SAM writer (the restatement the native one is tested against).")
     return parser
@@ -121,6 +125,8 @@ def main():
             bam.close()
             one_pass = False
             bam = bam_mod.NativeBam(cfg.args.bam, threads=threads)
+    if getattr(cfg.args, "bam_inflate", "host") == "device" and not one_pass:
+        print("    (--bam_inflate device has no effect: " + ("--python_io" if not native else "the indexed reader") + " inflates on the host)")
     bam_mod.get_bam_regions(bam, ref_seqs)
 
     if cfg.args.recalc_cms:              # src/realign.py:92-95 + src/bam.pyx:166-200
@@ -164,6 +170,7 @@ def main():
     start = perf_counter()
     n_dev = max(aln.device_count(), 1)
     ctx = aln.Context(cfg.args.sub_scores, cfg.args.np_scores, device=cfg.args.device % n_dev)
+    ctx.set("device_inflate", getattr(cfg.args, "bam_inflate", "host") == "device")
     n = 0
     done = False
     if native and one_pass:

@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--window", type=int, default=0, help="purity_window (0: the default)")
     ap.add_argument("--procs", type=int, default=max(1, min(16, len(os.sched_getaffinity(0)))))
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--inflate", choices=("host", "device"), default="host",
+                    help="where the one-pass reader inflates the BAM's BGZF blocks (Context.set device_inflate)")
     ap.add_argument("--tmp", default=None)
     ap.add_argument("--out", default=None, help="also write the line to this file")
     a = ap.parse_args()
@@ -52,6 +54,8 @@ def main():
            "positions": purity.merged_positions(regions, {c: e for c, _, e in regions}), "cpus": a.procs}
     ctx = aln.Context(None, None, max_n=6, max_l=100, device=0)
     ctx.set("cms_batch_reads", a.batch)
+    ctx.set("device_inflate", a.inflate == "device")
+    res["inflate"] = a.inflate
     if a.window:
         ctx.set("purity_window", a.window)
     runs = {"purity": [], "confusion": []}

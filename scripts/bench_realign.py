@@ -262,6 +262,8 @@ def main():
     ap.add_argument("--md", action="store_true", help="--records full: with the MD tag behind NM, built on the GPU")
     ap.add_argument("--tags", action="store_true",
                     help="every synthetic read carries an RG:Z tag and a B,C array of l_seq / 2 bytes (an ML-like load for --records full)")
+    ap.add_argument("--inflate", choices=("host", "device"), default="host",
+                    help="where the one-pass reader inflates the BAM's BGZF blocks (Context.set device_inflate)")
     ap.add_argument("--gen-into", default=None, help=argparse.SUPPRESS)       # (internal: make the inputs in this directory and exit)
     a = ap.parse_args()
     if a.bam_compress != "none" and a.out_format != "bam":
@@ -287,6 +289,7 @@ def main():
         bp, fa, clen = json.loads(gen.stdout.strip().splitlines()[-1])
         t_gen = time.perf_counter() - t
         ctx = aln.Context(sub, nps)
+        ctx.set("device_inflate", a.inflate == "device")      # (the one-pass leg's reader; the indexed legs inflate on the host)
         cfg.args = argparse.Namespace(max_n=6, max_l=100, regions=regions_of(clen), max_reads=0)
         out = os.path.join(tmp, "out.sam")
         # the STREAMED handle first: ru_maxrss is the peak of the whole process so far, and the resident handle holds

@@ -53,6 +53,8 @@ def main():
     ap.add_argument("--text-reads", type=int, default=160)
     ap.add_argument("--procs", type=int, default=max(1, min(16, len(os.sched_getaffinity(0)))))
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--inflate", choices=("host", "device"), default="host",
+                    help="where the one-pass reader inflates the BAM's BGZF blocks (Context.set device_inflate)")
     ap.add_argument("--tmp", default=None)
     ap.add_argument("--out", default=None, help="also write the line to this file")
     a = ap.parse_args()
@@ -69,6 +71,8 @@ def main():
            "bam_mb": round(os.path.getsize(bp) / 1e6, 1), "generate_s": round(gen_s, 1), "cpus": a.procs}
     ctx = aln.Context(None, None, max_n=6, max_l=100, device=0)
     ctx.set("cms_batch_reads", a.batch)
+    ctx.set("device_inflate", a.inflate == "device")
+    res["inflate"] = a.inflate
     for tag in ("_first", ""):
         t0 = time.perf_counter()
         subs, nps, inss, dels, t = bam.confusion_from_bam(ctx, bp, fa, ranges)

@@ -1,0 +1,217 @@
+"""BGZF in on the device: inflate_blocks_kernel (csrc/inflate_kernels.hpp, the decoder of csrc/inflate_wave.hpp with one
+wave per stream) against its host twin on the shared cases of inflate_device_cases.py, and the readers of
+npore_bam_confusion / npore_bam_purity / npore_bam_realign_sequential with Context.set("device_inflate", 1) against the
+same readers inflating on the host.  Exact equality throughout."""
+import os
+import struct
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, REPO
+from npore_amd import aln, bam, cfg, purity, realign
+import inflate_device_cases as idc
+from test_bam_out import Hdr, header_len, split_records
+
+pytestmark = pytest.mark.gpu
+DATA = os.path.join(GOLDEN, "data")
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = aln.Context(None, None, max_n=6, max_l=100, device=0)        # an annotation-only context will do for the decoder
+    yield c
+    c.close()
+
+
+@pytest.mark.parametrize("launch", idc.launches() + idc.corrupt_launches(), ids=lambda l: l.name)
+def test_kernel_equals_host_twin(ctx, launch):
+    """Status and bytes equal the twin's, stream by stream, and the whole output buffer -- guards, neighbours, what a
+    refused stream left in its own range -- equals the twin's.  The corrupt corpus goes through in one launch like any
+    other input (test_inflate_wave.py and scripts/asan_inflate_wave.sh have passed it through the twin on a CPU)."""
+    want_status, want_out = idc.twin(launch)
+    status, out = idc.device(ctx, launch)
+    assert set(np.unique(status).tolist()) <= {0, 1}
+    differ = np.nonzero(status != want_status)[0]
+    assert differ.size == 0, [(int(k), launch.cases[k][0], int(status[k])) for k in differ[:5]]
+    for k in range(len(launch.cases)):
+        if status[k] == 1:
+            assert launch.piece(out, k) == launch.piece(want_out, k), launch.cases[k][0]
+    assert launch.guards_intact(out), "wrote outside a block"
+    assert np.array_equal(out, want_out), int(np.nonzero(out != want_out)[0][0])
+
+
+def nonempty_members(path):
+    raw, p, n = open(path, "rb").read(), 0, 0
+    while p < len(raw):
+        bsize = struct.unpack_from("<H", raw, p + 16)[0] + 1
+        n += struct.unpack_from("<I", raw, p + bsize - 4)[0] > 0
+        p += bsize
+    return n
+
+
+@pytest.fixture(scope="module")
+def written_bams(tmp_path_factory):
+    """{compress: path} of one record stream of a few dozen BGZF members, written by bam.BamRecordWriter as stored, Huffman
+    and match-coded members (the last two: the project's own coding, so reading them back is a round trip), + its FASTA"""
+    tmp = tmp_path_factory.mktemp("inflate_device")
+    sys.path.insert(0, os.path.join(REPO, "scripts"))
+    import bench_realign
+    bp, fa, clen = bench_realign.build_inputs(str(tmp), 420, 0, 3000, 17, procs=2)
+    stream = bam._bgzf_decompress(bp)
+    src = bam.BamFile(bp)
+    recs = [r for _, r in split_records(stream[header_len(stream):])]
+    out = {}
+    for compress in ("none", "huffman", "match"):
+        path = str(tmp / f"{compress}.bam")
+        bam.create_bam_header(path, Hdr(src.references, src.lengths))
+        w = bam.BamRecordWriter(path, compress=compress)
+        w.add(recs)
+        w.close()
+        assert nonempty_members(path) >= 24
+        out[compress] = path
+    return out, fa, [(n, 0, l) for n, l in zip(src.references, src.lengths)]
+
+
+def _both_routes(path, fasta, ranges, window, monkeypatch):
+    """(confusion, purity, inflate_info of each) of one file with device_inflate 0 and 1"""
+    if window:
+        monkeypatch.setenv("NPORE_BAM_WINDOW_BLOCKS", window)
+    else:
+        monkeypatch.delenv("NPORE_BAM_WINDOW_BLOCKS", raising=False)
+    res = {}
+    for mode in (0, 1):
+        c = aln.Context(None, None, max_n=6, max_l=100, device=0)
+        try:
+            c.set("device_inflate", mode)
+            h = bam.NativeBam(path, one_pass=True, share=False)
+            try:
+                cms = bam.confusion_from_bam(c, h, fasta, ranges)
+                info_c = h.inflate_info()
+            finally:
+                h.close()
+            h = bam.NativeBam(path, one_pass=True, share=False)
+            try:
+                pur = purity.purity_from_bam(c, h, ranges, per_position=True)
+                info_p = h.inflate_info()
+            finally:
+                h.close()
+        finally:
+            c.close()
+        res[mode] = (cms, pur, info_c, info_p)
+    return res
+
+
+def _check_routes(path, fasta, ranges, window, monkeypatch):
+    res = _both_routes(path, fasta, ranges, window, monkeypatch)
+    (cms0, pur0, ic0, ip0), (cms1, pur1, ic1, ip1) = res[0], res[1]
+    tally = lambda t: {k: v for k, v in t.items() if not k.endswith("_ns")}     # (the kernels' time is no count)
+    assert all(np.array_equal(a, b) for a, b in zip(cms0[:4], cms1[:4])) and tally(cms0[4]) == tally(cms1[4])
+    assert int(cms1[0].sum()) > 0
+    assert np.array_equal(pur0[0], pur1[0]) and np.array_equal(pur0[1], pur1[1]) and np.array_equal(pur0[3], pur1[3])
+    assert tally(pur0[2]) == tally(pur1[2])
+    assert ic0 == (0,) * 8 and ip0 == (0,) * 8
+    n_blocks = nonempty_members(path)
+    for info in (ic1, ip1):
+        assert info[0] == n_blocks and info[1] == 0 and info[2] == 0 and info[7] == 1, info
+        want_launches = n_blocks if window == "1" else -(-(n_blocks + 1) // 2) if window == "2" else 1
+        assert info[3] >= 1 and abs(info[3] - want_launches) <= 1, (info, want_launches)     # (the empty EOF member may share a window)
+        assert info[4] > 0 and info[5] > 0 and info[6] == sum(struct.unpack("<I", m[-4:])[0] for m in _members_raw(path))
+
+
+def _members_raw(path):
+    raw, p = open(path, "rb").read(), 0
+    while p < len(raw):
+        bsize = struct.unpack_from("<H", raw, p + 16)[0] + 1
+        yield raw[p:p + bsize]
+        p += bsize
+
+
+@pytest.mark.parametrize("window", [None, "1", "2"])
+def test_readers_on_golden_bam(window, monkeypatch):
+    f = bam.BamFile(os.path.join(DATA, "reads.bam"))
+    ranges = [(n, 0, l) for n, l in zip(f.references, f.lengths)]
+    _check_routes(os.path.join(DATA, "reads.bam"), os.path.join(DATA, "ref.fasta"), ranges, window, monkeypatch)
+
+
+@pytest.mark.parametrize("window", [None, "1", "2"])
+@pytest.mark.parametrize("compress", ["none", "huffman", "match"])
+def test_readers_on_written_bams(written_bams, compress, window, monkeypatch):
+    paths, fasta, ranges = written_bams
+    _check_routes(paths[compress], fasta, ranges, window, monkeypatch)
+
+
+def _sam_records(path):
+    return [l for l in open(path) if not l.startswith("@")]
+
+
+def test_realign_sequential_with_device_inflate(tmp_path, written_bams):
+    """The realignment of the golden BAM reads the same records either way and writes the records of npore_realigned.sam,
+    also as rank 0 and rank 1 of 2 on the golden .bai (the golden file's records lie in one block: rank 1's share is empty,
+    either way); a share that really starts mid-file: rank 1 of 2 on the Huffman-coded BAM of a few dozen members."""
+    sub, nps, _, _ = aln.load_default_tables()
+    c = aln.Context(sub, nps, device=0)
+    try:
+        def run(path, fasta, mode, share, tag):
+            c.set("device_inflate", mode)
+            h = bam.NativeBam(path, one_pass=True, share=False)
+            try:
+                begin = h.set_share(share, 2)[1] if share is not None else 0
+                regions = [(n, 0, l) for n, l in zip(h.references, h.lengths)]
+                out = str(tmp_path / f"{tag}_m{mode}_s{share}.sam")
+                n, bad, _ = h.realign_sequential(c, fasta, regions, out, batch_reads=4 if tag == "golden" else 64, r=30)
+                info = h.inflate_info()
+            finally:
+                h.close()
+            assert not bad
+            if mode == 0:
+                assert info == (0,) * 8, info
+            else:
+                assert info[7] == 1 and info[2] == 0 and (info[0] > 0 or n == 0), info
+            return open(out, "rb").read(), n, begin
+
+        nf = bam.NativeFasta(os.path.join(DATA, "ref.fasta"))
+        try:
+            outs = {(mode, share): run(os.path.join(DATA, "reads.bam"), nf, mode, share, "golden")[0] for mode in (0, 1) for share in (None, 0, 1)}
+        finally:
+            nf.close()
+        for share in (None, 0, 1):
+            assert outs[0, share] == outs[1, share], share
+        assert outs[1, 0] + outs[1, 1] == outs[1, None]
+        got = outs[1, None].decode().splitlines(keepends=True)
+        want = {l.split("\t")[0]: l for l in _sam_records(os.path.join(DATA, "npore_realigned.sam"))}
+        assert len(got) == len(want) == 10
+        for line in got:
+            assert line == want[line.split("\t")[0]]
+        paths, fasta, _ = written_bams
+        bam.write_bai(paths["huffman"])
+        nf = bam.NativeFasta(fasta)
+        try:
+            (text0, n0, begin0), (text1, n1, begin1) = (run(paths["huffman"], nf, mode, 1, "written") for mode in (0, 1))
+        finally:
+            nf.close()
+        assert begin0 == begin1 > 65536 and 0 < n0 == n1 < 420 and text0 == text1
+    finally:
+        c.close()
+
+
+def test_realign_cli_recalc_cms_with_device_inflate(tmp_path, monkeypatch):
+    """`realign --bam_inflate device --recalc_cms --cms_source bam --recalc_exit` writes the matrices of `--bam_inflate host`."""
+    monkeypatch.chdir(tmp_path)
+    old = cfg.args
+    got = {}
+    try:
+        for mode in ("host", "device"):
+            out = tmp_path / mode
+            cfg.args = realign.argparser().parse_args(
+                ["--bam", os.path.join(DATA, "reads.bam"), "--ref", os.path.join(DATA, "ref.fasta"), "--out_prefix", str(tmp_path / "o"),
+                 "--recalc_cms", "--recalc_exit", "--cms_source", "bam", "--stats_dir", str(out), "--chunk_width", "97", "--bam_inflate", mode])
+            with pytest.raises(SystemExit) as ex:
+                realign.main()
+            assert ex.value.code == 0
+            got[mode] = [np.load(os.path.join(out, f"{k}_cm.npy")) for k in ("subs", "nps", "inss", "dels")]
+    finally:
+        cfg.args = old
+    assert all(np.array_equal(a, b) for a, b in zip(got["host"], got["device"])) and got["device"][0].sum() > 4000
+    assert realign.argparser().parse_args(["--bam", "x", "--ref", "y", "--out_prefix", "z"]).bam_inflate == "host"

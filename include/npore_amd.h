@@ -385,6 +385,30 @@ int npore_debug_format_bam_full_md_device(npore_ctx *ctx, npore_bam *bam, const 
  * Sized and written on the device in the default pipeline (md_size_kernel, emit_md_kernel), by the host twin otherwise. */
 #define NPORE_OUT_MD 32
 int npore_bam_set_output(npore_bam *bam, int format, const char *bai_path, int flags);
+/* Further tags of the FULL records of the NEXT run (`--cs short|long`, `--de`): call it behind an npore_bam_set_output whose
+ * format is NPORE_OUT_BAM and whose flags hold NPORE_OUT_FULL -- otherwise, and for any other bit, NPORE_E_INVALID.  Every
+ * npore_bam_set_output sets the tags back to 0.  The order in a record: kept aux, NM, MD, cs, de, CG.
+ * NPORE_TAG_CS: 'c' 's' 'Z' text NUL, minimap2's cs in its short form -- `:<n>` for every stretch of compared positions that do
+ * not differ, `*<ref><read>` for one that does, `+<read letters>`, `-<reference letters>`, letters lowercase --;
+ * with NPORE_TAG_CS_LONG (only beside NPORE_TAG_CS) the long form, `=<REFERENCE LETTERS>` in the place of `:<n>`.
+ * NPORE_TAG_DE: 'd' 'e' 'f' and a float, minimap2's gap-compressed per-base divergence (X + G) / (E + X + G) over the same walk:
+ * E and X the compared positions that do not and that do differ, G the I and D words.
+ * Both follow csrc/cs_rec.hpp, over the final CIGAR and the code arrays NM and MD are written on, so the four cannot disagree;
+ * the one difference from minimap2 is theirs: an IUPAC letter other than N counts as a mismatch (and prints as n) where
+ * minimap2 leaves ambiguous bases out.  `~` is never written: a final CIGAR has no N.  Sized and written on the device in the
+ * default pipeline (cs_size_kernel, emit_cs_kernel), by the host twin otherwise. */
+#define NPORE_TAG_CS 1
+#define NPORE_TAG_CS_LONG 2
+#define NPORE_TAG_DE 4
+int npore_bam_set_output_tags(npore_bam *bam, int tags);
+/* npore_bam_format_bam_full_md and npore_debug_format_bam_full_md_device with `tags` (NPORE_TAG_*; 0: their bytes) */
+int npore_bam_format_bam_full_tags(npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
+                                   const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
+                                   const uint8_t **recs, int64_t *recs_len, int flags, int tags);
+int npore_debug_format_bam_full_tags_device(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
+                                            int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len,
+                                            const int32_t *status, uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm, int flags,
+                                            int32_t *md_len, int tags);
 /* Of the last BAM-mode run on the handle: out4[0] records written, [1] bytes of the record stream, [2] 1 = the index was
  * written, 0 = none was asked for, -1 = the records were not in coordinate order (no index), [3] size of the file. */
 int npore_bam_output_info(const npore_bam *bam, int64_t *out4);

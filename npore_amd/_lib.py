@@ -85,7 +85,13 @@ SIGNATURES = {
     "npore_debug_format_bam_full_md_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                         C.c_int, C.c_void_p]),
+    "npore_bam_format_bam_full_tags": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "npore_debug_format_bam_full_tags_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                          C.c_int, C.c_void_p, C.c_int]),
     "npore_bam_set_output": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int]),
+    "npore_bam_set_output_tags": (C.c_int, [C.c_void_p, C.c_int]),
     "npore_bam_output_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "npore_bam_write_file": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_char_p]),

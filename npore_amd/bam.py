@@ -423,10 +423,91 @@ def md_of(ref_codes, seq_codes, final):
     return "".join(out) + str(u)
 
 
-def full_record(raw, ref_codes, seq_codes, final, md=False):
+def _cs_items(ref_codes, seq_codes, final):
+    """The final CIGAR as the items cs and de are made of, over the code arrays align() got: ("=", reference codes) for every
+    maximal stretch of compared positions that do not differ -- a position differs where the codes are unequal or either is 0,
+    as for NM and MD; a stretch runs on through neighbouring M / = / X words and ends at an I, D or N word and at a differing
+    position --, ("*", reference code, read code) for a differing position, ("+", read codes) and ("-", reference codes) for
+    an I and a D word.  N only advances the reference, S the read; a word of length 0 does nothing; a position beyond an
+    array has code 0."""
+    import re
+    code = lambda arr, at: int(arr[at]) if at < len(arr) else 0
+    items, run, a, b = [], [], 0, 0
+
+    def close():
+        if run:
+            items.append(("=", list(run)))
+            run.clear()
+    for n, op in re.findall(r"(\d+)([MIDNSHP=X])", final):
+        n = int(n)
+        if n == 0:
+            continue
+        if op in "M=X":
+            for q in range(n):
+                rc, sc = code(ref_codes, a + q), code(seq_codes, b + q)
+                if rc != sc or rc == 0 or sc == 0:
+                    close()
+                    items.append(("*", rc, sc))
+                else:
+                    run.append(rc)
+            a, b = a + n, b + n
+        elif op == "I":
+            close()
+            items.append(("+", [code(seq_codes, b + q) for q in range(n)]))
+            b += n
+        elif op == "D":
+            close()
+            items.append(("-", [code(ref_codes, a + q) for q in range(n)]))
+            a += n
+        elif op == "N":
+            close()
+            a += n
+        elif op == "S":
+            b += n
+    close()
+    return items
+
+
+def cs_of(ref_codes, seq_codes, final, long=False):
+    """minimap2's cs of a final CIGAR text over the code arrays align() got (beside nm_of and md_of): `:<n>` for a stretch of n
+    compared positions that do not differ -- long: `=` and the reference's letters in upper case --, `*<ref><read>` for a
+    position that differs, `+<read letters>` for an insertion, `-<reference letters>` for a deletion; letters lowercase,
+    "nacgtn" by code.  `~` is never written (a final CIGAR has no N).  minimap2's text but for nm_of's difference: an IUPAC
+    letter other than N has code 0, counts as a mismatch and prints as n."""
+    low, up = "nacgtn", "NACGTN"
+    out = []
+    for it in _cs_items(ref_codes, seq_codes, final):
+        if it[0] == "=":
+            out.append("=" + "".join(up[c] for c in it[1]) if long else f":{len(it[1])}")
+        elif it[0] == "*":
+            out.append("*" + low[it[1]] + low[it[2]])
+        else:
+            out.append(it[0] + "".join(low[c] for c in it[1]))
+    return "".join(out)
+
+
+def de_of(ref_codes, seq_codes, final):
+    """minimap2's de, the gap-compressed per-base divergence, of the same walk as a float32: (X + G) / (E + X + G) with E and X
+    the compared positions that do not and that do differ and G the I and D words (each one gap open); 0 over nothing."""
+    items = _cs_items(ref_codes, seq_codes, final)
+    e = sum(len(it[1]) for it in items if it[0] == "=")
+    x = sum(1 for it in items if it[0] == "*")
+    g = sum(1 for it in items if it[0] in "+-")
+    return np.float32((x + g) / (e + x + g)) if e + x + g else np.float32(0.0)
+
+
+def output_tags(cs, de):
+    """NPORE_TAG_* of the options cs (None, "short", "long") and de"""
+    if cs not in (None, "short", "long"):
+        raise ValueError("cs must be None, 'short' or 'long'")
+    return {None: 0, "short": 1, "long": 3}[cs] | (4 if de else 0)
+
+
+def full_record(raw, ref_codes, seq_codes, final, md=False, cs=None, de=False):
     """The FULL record (--records full, with its block_size word) of the input record `raw` (block_size word first) with
     its final CIGAR: the statement npore_bam_format_bam_full and the device path are tested against.  md: with the MD tag
-    (md_of) behind NM, as NPORE_OUT_MD writes it."""
+    (md_of) behind NM, as NPORE_OUT_MD writes it; cs ("short" / "long") and de: with cs_of / de_of behind that, as
+    NPORE_TAG_CS / NPORE_TAG_DE write them."""
     import re
     raw = bytes(raw)
     ref_id, pos, l_rn, mapq, _bin, n_cig, flag, l_seq, nref, npos, tlen = struct.unpack_from("<iiBBHHHiiii", raw, 4)
@@ -456,6 +537,10 @@ def full_record(raw, ref_codes, seq_codes, final, md=False):
                                       else b"I" + struct.pack("<I", nm))
     if md:
         tags += b"MDZ" + md_of(ref_codes, seq_codes, final).encode() + b"\0"
+    if cs:
+        tags += b"csZ" + cs_of(ref_codes, seq_codes, final, long=cs == "long").encode() + b"\0"
+    if de:
+        tags += b"def" + struct.pack("<f", de_of(ref_codes, seq_codes, final))
     if len(words) // 4 > MAX_CIGAR_OPS:
         tags += b"CGBI" + struct.pack("<I", len(words) // 4) + words
         words = struct.pack("<II", (l_seq << 4) | 4, (reflen << 4) | 3)
@@ -1188,9 +1273,10 @@ class NativeBam:
                                                    fl.ctypes.data, st.ctypes.data, threads, C.byref(recs), C.byref(recs_len)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False):
+    def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False, cs=None, de=False):
         """FULL records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam_full;
-        md: with the MD tag behind NM, npore_bam_format_bam_full_md with NPORE_OUT_MD)."""
+        md: with the MD tag behind NM, npore_bam_format_bam_full_md with NPORE_OUT_MD; cs "short" / "long", de: with those
+        tags behind MD, npore_bam_format_bam_full_tags with NPORE_TAG_*)."""
         import ctypes as C
         idx = np.ascontiguousarray(idx, np.int64)
         n = len(idx)
@@ -1204,10 +1290,12 @@ class NativeBam:
         recs, recs_len = C.c_void_p(), C.c_int64()
         args = (self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
                 st.ctypes.data, threads, C.byref(recs), C.byref(recs_len))
-        self._check(self._lib.npore_bam_format_bam_full_md(*args, 32) if md else self._lib.npore_bam_format_bam_full(*args))
+        tags = output_tags(cs, de)
+        self._check(self._lib.npore_bam_format_bam_full_tags(*args, 32 if md else 0, tags) if tags else
+                    self._lib.npore_bam_format_bam_full_md(*args, 32) if md else self._lib.npore_bam_format_bam_full(*args))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False):
+    def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False, cs=None, de=False):
         """What the NEXT realign_file / realign_sequential / write_file on this handle appends to its output path
         (npore_bam_set_output; the setting holds for that one run): "sam", or "bam" -- records in stored BGZF members behind
         what lies in the file (the header's members: create_bam_header) and `bai` written when the records went out in
@@ -1217,7 +1305,8 @@ class NativeBam:
         literals and length / distance pairs where that is smaller
         (NPORE_OUT_DEFLATE; "bam" only).  records: "reference", the reference's SAM line in binary, or "full", the input
         record with only what the realignment changes replaced (NPORE_OUT_FULL; "bam" only).  md: the MD tag behind the
-        recounted NM of every FULL record (NPORE_OUT_MD; records "full" only)."""
+        recounted NM of every FULL record (NPORE_OUT_MD; records "full" only).  cs: "short" or "long", minimap2's cs tag behind
+        that, de: its de tag behind that (npore_bam_set_output_tags, NPORE_TAG_*; records "full" only)."""
         if compress not in ("none", "huffman", "match"):
             raise ValueError("compress must be 'none', 'huffman' or 'match'")
         if records not in ("reference", "full"):
@@ -1226,6 +1315,9 @@ class NativeBam:
             raise ValueError("records 'full' needs out_format 'bam'")
         if md and records != "full":
             raise ValueError("md needs records 'full'")
+        tags = output_tags(cs, de)
+        if tags and records != "full":
+            raise ValueError("cs and de need records 'full'")
         if compress != "none" and out_format != "bam":
             raise ValueError("compress needs out_format 'bam'")
         flags = 0 if out_format != "bam" else 1 if eof else 2       # NPORE_OUT_EOF / NPORE_OUT_PART
@@ -1233,6 +1325,8 @@ class NativeBam:
         flags |= 16 if records == "full" else 0                    # NPORE_OUT_FULL
         flags |= 32 if md else 0                                   # NPORE_OUT_MD
         self._check(self._lib.npore_bam_set_output(self.handle, {"sam": 0, "bam": 1}[out_format], os.fsencode(bai) if bai else None, flags))
+        if tags:
+            self._check(self._lib.npore_bam_set_output_tags(self.handle, tags))
 
     def output_info(self):
         """Of the last BAM-mode run: records written, bytes of the record stream, index (1 written, 0 none asked for, -1 the
@@ -1297,12 +1391,12 @@ class NativeBam:
 
     def realign_sequential(self, ctx, fasta, regions, out_path, batch_reads=4000, max_reads=0, r=30, max_b_rows=20000,
                            indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, out_format="sam", bai=None, eof=True,
-                           compress="none", records="reference", md=False):
+                           compress="none", records="reference", md=False, cs=None, de=False):
         """ONE PASS over the file: inflate, filter by `regions` [(contig, start, stop)] (at most one per contig, in header
         order), batch, realign, write -- npore_bam_realign_sequential.  Returns (reads selected, [(ordinal, status)] of
         the first bad reads, (refused, inconsistent)); raises OnePassUnsupported when the regions or the file's
         order rule the one-pass run out (the caller truncates the output and takes the indexed path).
-        out_format / bai / eof / compress / records / md: set_output for this run ("bam": records instead of text)."""
+        out_format / bai / eof / compress / records / md / cs / de: set_output for this run ("bam": records instead of text)."""
         ids = {n: i for i, n in enumerate(self.references)}
         rid = np.array([ids.get(c, -2) for c, _, _ in regions], np.int32)
         beg = np.array([s for _, s, _ in regions], np.int64)
@@ -1312,7 +1406,7 @@ class NativeBam:
         counts = np.zeros(3, np.int64)
         bad_ord, bad_st = np.zeros(max(bad_cap, 1), np.int64), np.zeros(max(bad_cap, 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records, md)
+        self.set_output(out_format, bai, eof, compress, records, md, cs, de)
         rc = self._lib.npore_bam_realign_sequential(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, len(regions), rid.ctypes.data,
                                                     beg.ctypes.data, end.ctypes.data, int(max_reads or 0), int(batch_reads), indel_start,
                                                     indel_extend, max_b_rows, r, threads, os.fsencode(out_path), counts.ctypes.data,
@@ -1344,14 +1438,15 @@ class NativeBam:
         return (memoryview((C.c_char * sam_len.value).from_address(sam.value)) if sam_len.value else memoryview(b"")), st[:n]
 
     def realign_file(self, ctx, fasta, idx, out_sam, batch_reads=4000, r=30, max_b_rows=20000, indel_start=5.0,
-                     indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False):
+                     indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False,
+                     cs=None, de=False):
         """All selected reads, batch by batch, appended to out_sam by the library with packing, GPU work and
         formatting/writing of neighbouring batches overlapped.  Returns status[n].
-        out_format / bai / eof / compress / records / md: set_output for this run ("bam": records instead of text)."""
+        out_format / bai / eof / compress / records / md / cs / de: set_output for this run ("bam": records instead of text)."""
         idx = np.ascontiguousarray(idx, np.int64)
         st = np.zeros(max(len(idx), 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records, md)
+        self.set_output(out_format, bai, eof, compress, records, md, cs, de)
         self._check(self._lib.npore_bam_realign_file(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data,
                                                      len(idx), int(batch_reads), indel_start, indel_extend, max_b_rows, r,
                                                      threads, os.fsencode(out_sam), st.ctypes.data))
@@ -1398,7 +1493,7 @@ class NativeBam:
 
 
 def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0, out_format="sam", bai=None,
-                   eof=True, compress="none", records="reference", md=False):
+                   eof=True, compress="none", records="reference", md=False, cs=None, de=False):
     """realign_reads() through the library; returns the number of reads handed in.  batch_reads > 0: the whole
     index list in overlapped batches written by the library itself; 0: one batch, text written here.
     threads: host threads of the parallel host stages (0 = all cores; one process per GPU: dist.host_threads_per_rank).
@@ -1410,7 +1505,7 @@ def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_
     if batch_reads > 0:
         text, status = None, bam.realign_file(ctx, fasta, idx, out_sam, batch_reads=batch_reads, r=r, max_b_rows=max_b_rows,
                                               threads=threads, out_format=out_format, bai=bai, eof=eof, compress=compress,
-                                              records=records, md=md)
+                                              records=records, md=md, cs=cs, de=de)
     else:
         text, status = bam.realign_batch(ctx, fasta, idx, r=r, max_b_rows=max_b_rows, threads=threads)
     bad = np.nonzero(status)[0]

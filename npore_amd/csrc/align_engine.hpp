@@ -44,6 +44,7 @@ struct BamEmit {
     int64_t *h_info = nullptr;   // [4] page-locked: DeflateParams::info
     bool full = false;           // NPORE_OUT_FULL: FULL records (the heads staged with STAGE_FULL), NM counted on the device
     bool md = false;             // ... NPORE_OUT_MD beside it: the MD tag behind NM, sized and written on the device (md_rec.hpp)
+    int tags = 0;                // ... NPORE_TAG_*: cs / de behind that, sized and written on the device (cs_rec.hpp)
 };
 
 struct npore_batch_slot;        // a batch of the BAM -> SAM pipeline (file_pipeline.hpp)
@@ -65,6 +66,7 @@ struct WorkSet {
     DevBuf coff;                 // compacted texts: where each read of the group begins in the batch's compact buffer
     DevBuf in_hp, rec_off, rec_len;   // BAM records built on the device: the group's HP values, its records' places and sizes
     DevBuf nm, md_len;                // ... FULL records: the group's NM counts; NPORE_OUT_MD: the bytes of its MD texts
+    DevBuf cs_len, de_val;            // ... NPORE_TAG_*: the bytes of its cs texts, its de values
     HostBuf h_off;
     hipEvent_t evc[4] = {};      // H2D start / end, D2H start / end of a staged group
     bool staged = false;
@@ -86,7 +88,7 @@ struct WorkSet {
                                         &WorkSet::refl, &WorkSet::seql, &WorkSet::tb, &WorkSet::cout_, &WorkSet::clen, &WorkSet::cstat,
                                         &WorkSet::cnruns, &WorkSet::in_refs, &WorkSet::in_seqs, &WorkSet::in_cigs, &WorkSet::in_off,
                                         &WorkSet::out, &WorkSet::out_len, &WorkSet::status, &WorkSet::in_raw, &WorkSet::coff,
-                                        &WorkSet::in_hp, &WorkSet::rec_off, &WorkSet::rec_len, &WorkSet::nm, &WorkSet::md_len};
+                                        &WorkSet::in_hp, &WorkSet::rec_off, &WorkSet::rec_len, &WorkSet::nm, &WorkSet::md_len, &WorkSet::cs_len, &WorkSet::de_val};
         for (auto m : all) (this->*m).match(o.*m);
     }
 };
@@ -395,6 +397,8 @@ int reserve_group(WorkSet *w, const GroupPlan &p, const AlignArgs &a)
     for (DevBuf *b : {&w->in_hp, &w->rec_off, &w->rec_len})
         if (int rc = b->ensure(nr * 8 + 64)) return rc;
     if (int rc = a.bam->md ? w->md_len.ensure(nr * 4 + 64) : 0) return rc;
+    if (int rc = a.bam->tags ? w->cs_len.ensure(nr * 4 + 64) : 0) return rc;
+    if (int rc = a.bam->tags ? w->de_val.ensure(nr * 4 + 64) : 0) return rc;
     if (a.bam->full) return w->nm.ensure(nr * 4 + 64);
     return NPORE_OK;
 }
@@ -609,11 +613,14 @@ int post_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs &
         if (a.bam->full) {                    // FULL records: NM from the code arrays the standardisation probed, then the same two steps
             bp.refs = sp.refs; bp.seqs = sp.seqs; bp.nm = w->nm.as<int32_t>();
             if (a.bam->md) bp.md_len = w->md_len.as<int32_t>();      // (MD: its size in front of the placement, its text behind the record)
+            if (a.bam->tags) { bp.tags = a.bam->tags; bp.cs_len = w->cs_len.as<int32_t>(); bp.de = w->de_val.as<float>(); }      // (cs / de: the same)
             hipLaunchKernelGGL(nm_count_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
             if (bp.md_len) hipLaunchKernelGGL(md_size_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
+            if (bp.tags) hipLaunchKernelGGL(cs_size_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
             hipLaunchKernelGGL(place_bam_full_kernel, dim3(1), dim3(256), 0, s, bp);
             hipLaunchKernelGGL(emit_bam_full_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
             if (bp.md_len) hipLaunchKernelGGL(emit_md_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
+            if (bp.tags) hipLaunchKernelGGL(emit_cs_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
         } else {
             hipLaunchKernelGGL(place_bam_records_kernel, dim3(1), dim3(256), 0, s, bp);
             hipLaunchKernelGGL(emit_bam_records_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);

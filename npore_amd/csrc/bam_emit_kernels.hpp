@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/npore_amd.h"
+#include "cs_rec.hpp"
 #include "md_rec.hpp"
 #include "nm_rec.hpp"
 #include "unpack_kernels.hpp"
@@ -50,6 +52,10 @@ struct BamEmitParams {
     const uint8_t *refs = nullptr, *seqs = nullptr;
     int32_t *nm = nullptr;         // [n_reads]
     int32_t *md_len = nullptr;     // [n_reads] NPORE_OUT_MD (md_size_kernel): bytes of the read's MD text; null: no MD tag
+    // NPORE_TAG_* (cs_size_kernel): which of cs / de follow MD, the bytes of the read's cs text, its de value
+    int tags = 0;
+    int32_t *cs_len = nullptr;     // [n_reads], with any tag (0 without NPORE_TAG_CS)
+    float *de = nullptr;           // [n_reads], with any tag
 };
 
 __device__ __forceinline__ int bam_hp_bytes(int64_t hp)
@@ -279,6 +285,7 @@ struct BamFullShape {
     bool lng;
     int64_t wl, n_cig, l_seq, aux, size;
     int64_t mdb;                   // bytes of the MD tag behind NM (4 + its text; 0: none)
+    int64_t csb, deb;              // bytes of the cs tag behind that (4 + its text; 0: none) and of the de tag (7; 0: none)
 };
 __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, int64_t k)
 {
@@ -301,9 +308,11 @@ __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, i
     const uint32_t nm = (uint32_t)p.nm[k];
     s.nmb = nm <= 0xFFu ? 1 : nm <= 0xFFFFu ? 2 : 4;
     s.mdb = p.md_len ? 4 + (int64_t)p.md_len[k] : 0;
+    s.csb = (p.tags & NPORE_TAG_CS) ? 4 + (int64_t)p.cs_len[k] : 0;
+    s.deb = (p.tags & NPORE_TAG_DE) ? 7 : 0;
     s.size = (p.status[g] & 32) ? 0
                                 : 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb +
-                                      (s.lng ? 8 + 4 * s.n_cig : 0);
+                                      s.csb + s.deb + (s.lng ? 8 + 4 * s.n_cig : 0);
     return s;
 }
 __device__ __forceinline__ int64_t bam_full_record_size(const BamEmitParams &p, int64_t k) { return bam_full_shape(p, k).size; }
@@ -335,8 +344,8 @@ __global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
     for (int j = lane; j < l_rn; j += 64) o[j] = f[32 + j];
     o += l_rn;
     uint8_t *cw = o;                                             // where the CIGAR words go
-    if (s.lng) {                                                 // the placeholder here, CG:B,I behind NM (and MD)
-        cw = o + 8 + body + 3 + s.nmb + s.mdb + 8;
+    if (s.lng) {                                                 // the placeholder here, CG:B,I behind NM (and MD, cs, de)
+        cw = o + 8 + body + 3 + s.nmb + s.mdb + s.csb + s.deb + 8;
         if (lane < 2) put32(o + 4 * lane, lane == 0 ? ((uint32_t)s.l_seq << 4 | 4u) : ((uint32_t)reflen << 4 | 3u));
         if (lane >= 4 && lane < 8) cw[lane - 12] = (uint8_t)"CGBI"[lane - 4];
         if (lane >= 8 && lane < 12) cw[lane - 12] = (uint8_t)((uint32_t)s.n_cig >> (8 * (lane - 8)));
@@ -460,6 +469,161 @@ __global__ __launch_bounds__(64) void emit_md_kernel(BamEmitParams p)
     const int64_t cap = p.md_len[k];
     md_walk(p, k, lane, MdStore{o + 3, cap});
     if (lane == 0) o[3 + cap] = 0;
+}
+
+// ---- the cs and de tags of a FULL record (NPORE_TAG_CS / NPORE_TAG_DE; cs_rec.hpp states the rule and holds the sequential twin) ----
+// md_walk's frame: one wavefront per read over tiles of 64 CIGAR words, the M-type, I, D and N words of a tile visited in word
+// order; `at` (bytes of text so far), `u` (the open stretch's positions, carried across words and tiles) and the counts E X G
+// are the same in every lane.
+//   I / D word: the open stretch's `:count` (short form) by lane 0, the sign by lane 0, then a lane per base, codes to letters,
+//     64 bases per round.  N only ends the stretch.
+//   M-type word, 64 positions per round, the ballot of nm_differs gives the differing lanes.  Every lane knows the bytes of its
+//     own item and a wave prefix sum of those bytes places it:
+//       short form: a differing lane writes `:count` -- the distance to the previous differing lane of the round, u + its lane
+//         for the round's first; nothing when that is 0 -- and `*` and its two letters;
+//       long form: a differing lane writes its three bytes, every other lane its reference letter, with `=` in front where
+//         the lane before it differs (lane 0: where no stretch is open).
+//     The carry out is u + the round's positions where nothing differs, otherwise the positions behind the last differing one.
+// The walk is ONE function over a sink: cs_size_kernel runs it with MdCount, emit_cs_kernel with MdStore, so size and text
+// cannot differ.  Returns the text's length (no NUL), the counts in c.
+template <bool LNG, class Sink>
+__device__ __forceinline__ uint32_t cs_walk(const BamEmitParams &p, int64_t k, int lane, const Sink &sink, CsCounts &c)
+{
+    const int64_t g = p.read_base + k;
+    const int64_t n = p.words_len[g] <= 0 ? 0 : p.words_len[g] >> 2;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(p.words + p.words_off[g]);      // (the slots lie at multiples of 4)
+    const uint8_t *ref = p.refs + p.ref_off[k], *seq = p.seqs + p.seq_off[k];
+    const int64_t rl = p.ref_off[k + 1] - p.ref_off[k], sl = p.seq_off[k + 1] - p.seq_off[k];
+    const unsigned long long below_me = (1ull << lane) - 1ull;
+    int64_t a0 = 0, b0 = 0;                  // consumed in front of the tile
+    uint32_t at = 0, u = 0;
+    auto end_stretch = [&]() {
+        if (!LNG && u > 0) {
+            const int nd = md_digits(u);
+            if (lane == 0) {
+                sink.put(at, (uint8_t)':');
+                md_put_decimal(sink, at + 1u, u, nd);
+            }
+            at += 1u + (uint32_t)nd;
+        }
+        u = 0;
+    };
+    for (int64_t t0 = 0; t0 < n; t0 += 64) {
+        const uint32_t v = t0 + lane < n ? w[t0 + lane] : 0u;       // (behind the end: `0M`)
+        const uint32_t op = v & 15u, len = v >> 4, use = nm_consumes(op);
+        const uint32_t ra = (use & 1u) ? len : 0u, qa = (use & 2u) ? len : 0u;
+        uint32_t ri = ra, qi = qa;           // inclusive sums over the tile
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t x = (uint32_t)__shfl_up((int)ri, d), y = (uint32_t)__shfl_up((int)qi, d);
+            if (lane >= d) { ri += x; qi += y; }
+        }
+        unsigned long long runs = __builtin_amdgcn_ballot_w64((nm_compares(op) || (op >= 1u && op <= 3u)) && len > 0);
+        while (runs) {
+            const int j = (int)__builtin_ctzll(runs);
+            runs &= runs - 1;
+            const uint32_t lj = (uint32_t)__shfl((int)len, j), opj = (uint32_t)__shfl((int)op, j);
+            const int64_t aj = a0 + (uint32_t)__shfl((int)(ri - ra), j), bj = b0 + (uint32_t)__shfl((int)(qi - qa), j);
+            if (!nm_compares(opj)) {
+                end_stretch();
+                if (opj == 3u) continue;
+                if (lane == 0) sink.put(at, (uint8_t)(opj == 1u ? '+' : '-'));
+                at += 1u;
+                const uint8_t *arr = opj == 1u ? seq : ref;
+                const int64_t al = opj == 1u ? sl : rl, from = opj == 1u ? bj : aj;
+                for (uint32_t q = (uint32_t)lane; q < lj; q += 64) sink.put(at + q, cs_lower(cs_code(arr, al, from + q)));
+                at += lj;
+                c.g++;
+                continue;
+            }
+            for (uint32_t q0 = 0; q0 < lj; q0 += 64) {
+                const uint32_t q = q0 + (uint32_t)lane, in_round = min(64u, lj - q0);
+                const bool d = q < lj && nm_differs(ref, rl, aj + q, seq, sl, bj + q);
+                const unsigned long long ev = __builtin_amdgcn_ballot_w64(d);
+                const uint32_t n_ev = (uint32_t)__builtin_popcountll(ev);
+                c.x += n_ev;
+                c.e += in_round - n_ev;
+                if (!LNG && !ev) { u += in_round; continue; }
+                const unsigned long long before = ev & below_me;
+                uint32_t cnt = 0, bytes = 0;
+                int nd = 0;
+                if (LNG) {
+                    const bool opens = lane == 0 ? u == 0u : ((ev >> (lane - 1)) & 1ull) != 0;
+                    bytes = q >= lj ? 0u : d ? 3u : opens ? 2u : 1u;
+                } else {
+                    cnt = before ? (uint32_t)(lane - 1 - (63 - (int)__builtin_clzll(before))) : u + (uint32_t)lane;
+                    nd = md_digits(cnt);
+                    bytes = d ? 3u + (cnt > 0u ? 1u + (uint32_t)nd : 0u) : 0u;
+                }
+                uint32_t incl = bytes;
+                for (int s = 1; s < 64; s <<= 1) {
+                    const uint32_t x = (uint32_t)__shfl_up((int)incl, s);
+                    if (lane >= s) incl += x;
+                }
+                uint32_t mine = at + incl - bytes;
+                if (d) {
+                    if (!LNG && cnt > 0u) {
+                        sink.put(mine, (uint8_t)':');
+                        md_put_decimal(sink, mine + 1u, cnt, nd);
+                        mine += 1u + (uint32_t)nd;
+                    }
+                    sink.put(mine, (uint8_t)'*');
+                    sink.put(mine + 1u, cs_lower(cs_code(ref, rl, aj + q)));
+                    sink.put(mine + 2u, cs_lower(cs_code(seq, sl, bj + q)));
+                } else if (LNG && q < lj) {
+                    if (bytes == 2u) sink.put(mine, (uint8_t)'=');
+                    sink.put(mine + bytes - 1u, md_letter(cs_code(ref, rl, aj + q)));
+                }
+                at += (uint32_t)__shfl((int)incl, 63);
+                u = ev ? in_round - 1u - (uint32_t)(63 - (int)__builtin_clzll(ev)) : u + in_round;
+            }
+        }
+        a0 += (uint32_t)__shfl((int)ri, 63);
+        b0 += (uint32_t)__shfl((int)qi, 63);
+    }
+    end_stretch();
+    return at;
+}
+
+// bytes of every read's cs text and its de value (0, 0.0f: the read is refused and has no record), beside md_size_kernel in front
+// of the placement; only NPORE_TAG_DE: the walk runs for the counts and the size stays 0
+__global__ __launch_bounds__(64) void cs_size_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    CsCounts c;
+    uint32_t len = 0;
+    if (!(p.status[p.read_base + k] & 32)) len = (p.tags & NPORE_TAG_CS_LONG) ? cs_walk<true>(p, k, lane, MdCount{}, c) : cs_walk<false>(p, k, lane, MdCount{}, c);
+    if (lane == 0) {
+        p.cs_len[k] = (p.tags & NPORE_TAG_CS) ? (int32_t)len : 0;
+        p.de[k] = de_of_counts(c.e, c.x, c.g);
+    }
+}
+
+// 'c' 's' 'Z' text NUL and 'd' 'e' 'f' value behind the record's NM and MD (bam_full_shape), behind emit_bam_full_kernel (and
+// emit_md_kernel) on its stream
+__global__ __launch_bounds__(64) void emit_cs_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    if (p.rec_len[k] <= 0) return;
+    const BamFullShape s = bam_full_shape(p, k);
+    uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb;
+    if (s.csb) {
+        if (lane < 3) o[lane] = (uint8_t)"csZ"[lane];
+        const int64_t cap = p.cs_len[k];
+        CsCounts c;
+        if (p.tags & NPORE_TAG_CS_LONG) cs_walk<true>(p, k, lane, MdStore{o + 3, cap}, c);
+        else cs_walk<false>(p, k, lane, MdStore{o + 3, cap}, c);
+        if (lane == 0) o[3 + cap] = 0;
+        o += s.csb;
+    }
+    if (s.deb) {
+        const uint32_t bits = __float_as_uint(p.de[k]);
+        if (lane < 3) o[lane] = (uint8_t)"def"[lane];
+        else if (lane < 7) o[lane] = (uint8_t)(bits >> (8 * (lane - 3)));
+    }
 }
 
 }  // namespace npore

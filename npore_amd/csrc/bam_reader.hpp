@@ -7,6 +7,7 @@
 #include "../../include/npore_amd.h"
 #include "hostio.hpp"
 #include "deflate_code.hpp"
+#include "cs_rec.hpp"
 #include "md_rec.hpp"
 #include "nm_rec.hpp"
 
@@ -663,6 +664,9 @@ inline int format_sam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
 //   - more than 65 535 operations, clips included: the CIGAR field holds the placeholder `l_seq << 4 | 4`,
 //     `reflen << 4 | 3` with the full l_seq, and CG:B,I with ALL the words goes behind NM (behind MD where there is one:
 //     kept aux, NM, MD, CG).
+//   - with NPORE_TAG_CS / NPORE_TAG_DE (`--cs`, `--de`, npore_bam_set_output_tags) cs and de (cs_rec.hpp) follow MD: 'c' 's' 'Z',
+//     the text, NUL -- 4 + its length bytes -- and 'd' 'e' 'f' and a float -- 7 bytes: kept aux, NM, MD, cs, de, CG.  They are
+//     minimap2's but for what NM already differs in: an IUPAC letter other than N counts as a mismatch.
 //   Size: 36 + l_read_name + 4 * n_cigar (8 when long) + (l_seq + 1) / 2 + l_seq + kept aux + 3 + {1, 2, 4} (+ 4 + MD text)
 //   (+ 8 + 4 * n when long).
 // FILE.  BGZF with STORED deflate members (level 0, what `samtools view -u` writes): 18 bytes of gzip header with the BC
@@ -822,9 +826,47 @@ inline bool md_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t rl,
     md_into_words(words.data(), ops, ref, rl, seq, sl, reinterpret_cast<uint8_t *>(&md[0]), (int64_t)md.size());
     return true;
 }
-// bam_record_into's twin for the FULL RECORD; nm: the read's NM (nm_of_text); md: its MD text (md_of_text), or none
+// cs (cs_rec.hpp; lng: the long form) of a final CIGAR text over the read's code arrays, sized and then written; false: no
+// CIGAR text
+inline bool cs_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, bool lng, std::string &cs)
+{
+    const int64_t ops = cigar_text_ops(t, n);
+    if (ops < 0) return false;
+    const std::vector<uint8_t> words = cigar_text_words(t, n, ops);
+    cs.assign((size_t)cs_size_of_words(words.data(), ops, ref, rl, seq, sl, lng), '\0');
+    cs_into_words(words.data(), ops, ref, rl, seq, sl, lng, reinterpret_cast<uint8_t *>(&cs[0]), (int64_t)cs.size());
+    return true;
+}
+// de (cs_rec.hpp) of the same, from the size pass's counts; false: no CIGAR text
+inline bool de_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, float &de)
+{
+    const int64_t ops = cigar_text_ops(t, n);
+    if (ops < 0) return false;
+    CsCounts c;
+    cs_size_of_words(cigar_text_words(t, n, ops).data(), ops, ref, rl, seq, sl, false, &c);
+    de = de_of_counts(c.e, c.x, c.g);
+    return true;
+}
+// the bytes of the cs and de tags (NPORE_TAG_*) as they follow MD in a FULL record
+inline void cs_de_tags_of_text(int tags, const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, std::string &out)
+{
+    out.clear();
+    std::string cs;
+    if ((tags & NPORE_TAG_CS) && cs_of_text(t, n, ref, rl, seq, sl, (tags & NPORE_TAG_CS_LONG) != 0, cs)) {
+        out.append("csZ").append(cs);
+        out.push_back('\0');
+    }
+    float de = 0.0f;
+    if ((tags & NPORE_TAG_DE) && de_of_text(t, n, ref, rl, seq, sl, de)) {
+        char v[4];
+        std::memcpy(v, &de, 4);
+        out.append("def").append(v, 4);
+    }
+}
+// bam_record_into's twin for the FULL RECORD; nm: the read's NM (nm_of_text); md: its MD text (md_of_text), or none; more: the
+// bytes of its cs and de tags (cs_de_tags_of_text), or none
 inline int64_t bam_record_full_into(const RecView &r, const char *final_text, int64_t final_len, int32_t status, int64_t nm, uint8_t *dst,
-                                    BamRecMeta *meta = nullptr, const std::string *md = nullptr)
+                                    BamRecMeta *meta = nullptr, const std::string *md = nullptr, const std::string *more = nullptr)
 {
     if (status & NPORE_ST_BAD_INPUT) return 0;
     const RecCigar in_cg = rec_cigar(r);
@@ -836,7 +878,7 @@ inline int64_t bam_record_full_into(const RecView &r, const char *final_text, in
     const bool lng = n_cig > 0xFFFF;
     const int64_t l_seq = r.l_seq(), nb = (l_seq + 1) / 2, aux = filter_aux(r.aux(), r.end(), nullptr);
     const int l_rn = r.l_read_name(), nmb = bam_hp_tag_bytes(nm);
-    const int64_t mdb = md ? 4 + (int64_t)md->size() : 0;
+    const int64_t mdb = (md ? 4 + (int64_t)md->size() : 0) + (more ? (int64_t)more->size() : 0);      // (MD, cs, de)
     const int64_t size = 36 + l_rn + (lng ? 8 : 4 * n_cig) + nb + l_seq + aux + 3 + nmb + mdb + (lng ? 8 + 4 * n_cig : 0);
     if (!dst) return size;
     const int64_t reflen = rec_ref_len(in_cg);
@@ -851,7 +893,7 @@ inline int64_t bam_record_full_into(const RecView &r, const char *final_text, in
     std::memcpy(o, r.name(), (size_t)l_rn);
     o += l_rn;
     uint8_t *const seq_at = lng ? o + 8 : o + 4 * n_cig;
-    if (lng) {                                       // the words go behind NM (and MD)
+    if (lng) {                                       // the words go behind NM (and MD, cs, de)
         w32(o, (uint32_t)l_seq << 4 | 4u);
         w32(o + 4, (uint32_t)reflen << 4 | 3u);
         o = seq_at + nb + l_seq + aux + 3 + nmb + mdb;
@@ -880,19 +922,23 @@ inline int64_t bam_record_full_into(const RecView &r, const char *final_text, in
     o[0] = 'N'; o[1] = 'M';
     o[2] = (uint8_t)(nmb == 1 ? 'C' : nmb == 2 ? 'S' : 'I');
     { const uint32_t v = (uint32_t)nm; std::memcpy(o + 3, &v, (size_t)nmb); }
+    o += 3 + nmb;
     if (md) {
-        o += 3 + nmb;
         std::memcpy(o, "MDZ", 3);
         std::memcpy(o + 3, md->c_str(), md->size() + 1);
+        o += 4 + md->size();
     }
+    if (more) std::memcpy(o, more->data(), more->size());
     if (meta) *meta = BamRecMeta{r.ref_id(), r.pos(), reflen, size};
     return size;
 }
-// the code arrays of a batch's reads (what align() got): FULL records count NM from them, and write MD from them (md)
+// the code arrays of a batch's reads (what align() got): FULL records count NM from them, and write MD (md) and cs / de
+// (tags: NPORE_TAG_*) from them
 struct ReadCodes {
     const uint8_t *refs; const int64_t *ref_off;
     const uint8_t *seqs; const int64_t *seq_off;
     bool md = false;
+    int tags = 0;
 };
 
 // format_sam_into's twin for BAM records: the kept reads' records one after the other in `out`, *out_len bytes;
@@ -904,12 +950,12 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     if (!b || n < 0 || !out_len || (n > 0 && (!finals || !final_off || !final_len || !status)))
         return fail(NPORE_E_INVALID, "bad argument");
     std::vector<int64_t> off((size_t)n + 1, 0), nm(full ? (size_t)n : 0, 0);
-    std::vector<std::string> md(full && full->md ? (size_t)n : 0);
+    std::vector<std::string> md(full && full->md ? (size_t)n : 0), more(full && full->tags ? (size_t)n : 0);
     std::atomic<int> bad{0};
-    // (full: the FULL RECORD, its NM counted and its MD written once, between the two passes)
+    // (full: the FULL RECORD, its NM counted and its MD, cs and de written once, between the two passes)
     auto record = [&](int64_t k, uint8_t *dst, BamRecMeta *m) {
         return full ? bam_record_full_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], nm[(size_t)k], dst, m,
-                                           full->md ? &md[(size_t)k] : nullptr)
+                                           full->md ? &md[(size_t)k] : nullptr, full->tags ? &more[(size_t)k] : nullptr)
                     : bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], dst, m);
     };
     parallel_for(n, threads, [&](int64_t k) {
@@ -918,6 +964,7 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
             const int64_t rl = full->ref_off[k + 1] - full->ref_off[k], sl = full->seq_off[k + 1] - full->seq_off[k];
             nm[(size_t)k] = nm_of_text(finals + final_off[k], final_len[k], ref, rl, seq, sl);
             if (full->md) md_of_text(finals + final_off[k], final_len[k], ref, rl, seq, sl, md[(size_t)k]);
+            if (full->tags) cs_de_tags_of_text(full->tags, finals + final_off[k], final_len[k], ref, rl, seq, sl, more[(size_t)k]);
         }
         const int64_t sz = record(k, nullptr, nullptr);
         if (sz < 0) bad++;

@@ -73,11 +73,11 @@ DeflateParams slot_deflate_params(npore_batch_slot &s, const uint8_t *d_recs, co
 }
 
 // npore_bam_set_output holds for ONE run: the run that writes takes the setting and leaves the default behind
-struct OutputSetting { int format, flags; std::string bai; };
+struct OutputSetting { int format, flags, tags; std::string bai; };
 OutputSetting take_output_setting(npore_bam *b)
 {
-    OutputSetting o{b->out_format, b->out_flags, b->out_bai};
-    b->out_format = NPORE_OUT_SAM; b->out_flags = 0; b->out_bai.clear();
+    OutputSetting o{b->out_format, b->out_flags, b->out_tags, b->out_bai};
+    b->out_format = NPORE_OUT_SAM; b->out_flags = 0; b->out_tags = 0; b->out_bai.clear();
     std::fill(b->out_info, b->out_info + 4, 0);
     return o;
 }
@@ -88,6 +88,7 @@ struct PipeMode {
     bool dpack = false;          // ... and align()'s inputs unpacked from the records on the device (the host glue needs the base arrays on the host)
     bool bam = false, full = false;     // BAM records out instead of SAM text; NPORE_OUT_FULL: FULL records
     bool md = false;             // ... NPORE_OUT_MD: with the MD tag behind NM
+    int tags = 0;                // ... NPORE_TAG_*: with cs / de behind that
     int deflate = 0;             // the writer's DEFLATE_MODE_*, 0: stored members
     // BAM mode: the records are built on the device where the default pipeline runs (device pack + device glue:
     // bam_emit_kernels.hpp); with the host glue or the host pack the host twin makes them (format_bam_into)
@@ -102,12 +103,14 @@ struct RunOutput {
     std::unique_ptr<BgzfStoredWriter> bw;
     npore_bam *b = nullptr;
     bool full = false, md = false;      // NPORE_OUT_FULL, NPORE_OUT_MD
+    int tags = 0;                       // NPORE_TAG_*
     int open(npore_bam *bam, const char *out_path, int threads)
     {
         b = bam;
         const OutputSetting o = take_output_setting(b);
         full = o.format == NPORE_OUT_BAM && (o.flags & NPORE_OUT_FULL) != 0;
         md = full && (o.flags & NPORE_OUT_MD) != 0;
+        tags = full ? o.tags : 0;
         if (o.format == NPORE_OUT_BAM) {
             bw.reset(new BgzfStoredWriter());
             return bw->open(out_path, b->ref_names.size(), o.bai.empty() ? nullptr : o.bai.c_str(), (o.flags & NPORE_OUT_EOF) != 0,
@@ -141,7 +144,7 @@ PipeMode pipe_mode(const npore_ctx *ctx, const RunOutput &out)      // (NPORE_DE
 {
     const char *e = std::getenv("NPORE_DEVICE_PACK");
     const bool glue = ctx->device_glue != 0, dpack = glue && ctx->device_pack != 0 && !(e && std::atoi(e) == 0);
-    return PipeMode{glue, dpack, out.bw != nullptr, out.full, out.md, out.bw ? out.bw->deflate_mode() : 0};
+    return PipeMode{glue, dpack, out.bw != nullptr, out.full, out.md, out.tags, out.bw ? out.bw->deflate_mode() : 0};
 }
 
 // The FASTA on the device (once per FASTA and context) and, per BAM reference, where its contig lies there.
@@ -206,7 +209,8 @@ int slot_pack_arrays(const npore_bam *b, const npore_fasta *fa, const int32_t *f
 // FULL records: the kept aux bytes behind the qualities (STAGE_FULL) and their number in the HP values' place; the
 // bound grows by the clips' bases, four clip words, the kept aux and NM; with MD by 4 + 3 * reflen + 11 (three bytes per
 // reference position is the worst text, `0^A` repeated -- `0A` takes two per compared position --, and the closing count
-// has at most 10 digits).
+// has at most 10 digits); with cs by 4 + 3 * (reflen + seqlen) -- no item of the text has more than three bytes per base it
+// covers (cs_rec.hpp, Size) --, with de by 7.
 int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, int threads, npore_batch_slot &s, const PipeMode &pm)
 {
     const int64_t n = s.m;
@@ -228,6 +232,7 @@ int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta
             s.rec_cap += 36 + r.l_read_name() + 4 * cap + 16 + (sl + 1) / 2 + sl + 7 + 16;      // (+ 16: placeholder and CG tag head of a long final CIGAR)
             if (pm.full) s.rec_cap += ((int64_t)r.l_seq() + 1) / 2 + r.l_seq() - (sl + 1) / 2 - sl + 16 + aux;
             if (pm.md) s.rec_cap += 4 + 3 * (s.ro[(size_t)k + 1] - s.ro[(size_t)k]) + 11;
+            if (pm.tags) s.rec_cap += 4 + 3 * (s.ro[(size_t)k + 1] - s.ro[(size_t)k] + sl) + 7;
         }
     }
     if (int rc = s.raw.ensure((size_t)s.rawo[(size_t)n] + 64)) return rc;
@@ -262,7 +267,7 @@ int slot_enqueue(npore_ctx *ctx, npore_batch_slot &s, const PipeMode &pm, const 
             (rc = s.reclen_pin.ensure((size_t)m * 8 + 64)) || (rc = s.total_pin.ensure(64))) return fail(rc, "batch buffers");
         s.emit = BamEmit{s.d_recs.as<uint8_t>(), s.rec_cap, s.d_cursor.as<unsigned long long>(), reinterpret_cast<const int64_t *>(s.hp_pin.p),
                          reinterpret_cast<int64_t *>(s.reclen_pin.p), reinterpret_cast<unsigned long long *>(s.total_pin.p)};
-        s.emit.full = pm.full; s.emit.md = pm.md;
+        s.emit.full = pm.full; s.emit.md = pm.md; s.emit.tags = pm.tags;
         if (pm.dev_deflate()) {
             if ((rc = slot_deflate_buffers(s, s.rec_cap, pm.deflate))) return fail(rc, "batch buffers");
             s.emit.dfl = slot_deflate_params(s, s.d_recs.as<uint8_t>(), s.d_cursor.as<unsigned long long>(), ctx->d_stream_pos.as<unsigned long long>(),
@@ -336,7 +341,7 @@ int slot_collect(const npore_bam *b, const int32_t *status, int threads, npore_b
 {
     if (pm.dev_records()) return slot_fetch_records(status, s, pm);
     const int64_t n = s.m;
-    const ReadCodes codes{reinterpret_cast<const uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<const uint8_t *>(s.seqs.p), s.so.data(), pm.md};
+    const ReadCodes codes{reinterpret_cast<const uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<const uint8_t *>(s.seqs.p), s.so.data(), pm.md, pm.tags};
     auto format_into = [&](const char *finals, const int64_t *final_off) {          // (FULL records: NM and MD from the slot's code arrays)
         return pm.bam ? format_bam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len, &s.meta, pm.full ? &codes : nullptr)
                       : format_sam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len);

@@ -575,7 +575,7 @@ struct npore_bam {
     size_t share_block = 0;               // the BGZF block share_begin lies in
     // npore_bam_set_output: what the NEXT file run on the handle writes (0 = SAM text, 1 = BAM records in stored BGZF
     // members), where its .bai goes ("" = none), NPORE_OUT_* flags; out_info: what that run wrote (npore_bam_output_info)
-    int out_format = 0, out_flags = 0;
+    int out_format = 0, out_flags = 0, out_tags = 0;
     std::string out_bai;
     int64_t out_info[4] = {0, 0, 0, 0};
     int64_t inflate_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the device inflation of the last run on the handle (npore_bam_inflate_info)

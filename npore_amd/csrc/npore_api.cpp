@@ -1501,12 +1501,27 @@ int npore_bam_format_bam_full(npore_bam *b, const npore_fasta *fa, const int32_t
 int npore_bam_format_bam_full_md(npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
                                  const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
                                  const uint8_t **recs, int64_t *recs_len, int flags)
+{
+    return npore_bam_format_bam_full_tags(b, fa, fasta_of_ref, idx, n, finals, final_off, final_len, status, threads, recs, recs_len, flags, 0);
+}
+
+// NPORE_TAG_CS alone or with NPORE_TAG_CS_LONG, NPORE_TAG_DE, or nothing
+static bool output_tags_ok(int tags)
+{
+    return !(tags & ~(NPORE_TAG_CS | NPORE_TAG_CS_LONG | NPORE_TAG_DE)) && (!(tags & NPORE_TAG_CS_LONG) || (tags & NPORE_TAG_CS));
+}
+
+// ... and with tags: NPORE_TAG_*, cs and de behind MD (0: the records above)
+int npore_bam_format_bam_full_tags(npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
+                                   const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
+                                   const uint8_t **recs, int64_t *recs_len, int flags, int tags)
 try {
-    if (!pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs || (flags & ~NPORE_OUT_MD)) return fail(NPORE_E_INVALID, "bad argument");
+    if (!pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs || (flags & ~NPORE_OUT_MD) || !output_tags_ok(tags))
+        return fail(NPORE_E_INVALID, "bad argument");
     if (int rc = fetch_records(b, idx, n, threads, b->api_fetch)) return rc;
     PackedCodes pc;
     if (int rc = pc.pack(b, b->api_fetch, fa, fasta_of_ref, n, threads)) return rc;
-    const ReadCodes codes{pc.refs.data(), pc.ro.data(), pc.seqs.data(), pc.so.data(), (flags & NPORE_OUT_MD) != 0};
+    const ReadCodes codes{pc.refs.data(), pc.ro.data(), pc.seqs.data(), pc.so.data(), (flags & NPORE_OUT_MD) != 0, tags};
     const int rc = format_bam_into(b, b->api_fetch, n, finals, final_off, final_len, status, threads, b->recs, recs_len, nullptr, &codes);
     *recs = reinterpret_cast<const uint8_t *>(b->recs.p);
     return rc;
@@ -1527,9 +1542,19 @@ int npore_debug_format_bam_full_device(npore_ctx *ctx, npore_bam *b, const npore
 int npore_debug_format_bam_full_md_device(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
                                           int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status,
                                           uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm, int flags, int32_t *md_len)
+{
+    return npore_debug_format_bam_full_tags_device(ctx, b, fa, fasta_of_ref, idx, n, finals, final_off, final_len, status, recs, cap, recs_len, nm, flags,
+                                                   md_len, 0);
+}
+
+// ... and with tags: NPORE_TAG_* puts cs_size_kernel beside md_size_kernel and emit_cs_kernel behind emit_md_kernel
+int npore_debug_format_bam_full_tags_device(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
+                                            int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status,
+                                            uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm, int flags, int32_t *md_len, int tags)
 try {
     const bool md = (flags & NPORE_OUT_MD) != 0;
     if (!ctx || !pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs_len || cap < 0 || (cap > 0 && !recs) || (flags & ~NPORE_OUT_MD) ||
+        !output_tags_ok(tags) ||
         (n > 0 && (!finals || !final_off || !final_len || !status || !nm || (md && !md_len))))
         return fail(NPORE_E_INVALID, "bad argument");
     *recs_len = 0;
@@ -1573,10 +1598,13 @@ try {
             len = 0;
             // (MD: a caller's final may cover more reference than the read has -- three bytes per position it covers, 11 per word)
             if (md) bound += 3 * (int64_t)((nm_consumes(w & 15u) & 1u) ? w >> 4 : 0u) + 11;
+            // (cs: three bytes per base a word covers at the most -- cs_rec.hpp, Size)
+            if (tags && nm_consumes(w & 15u)) bound += 3 * (int64_t)(w >> 4);
         }
         if (md) bound += 4 + 11;
+        if (tags) bound += 4 + 7;
     }
-    DevBuf d_md, d_raw, d_off, d_words, d_wlen, d_aux, d_status, d_refs, d_seqs, d_cigs, d_recs, d_cursor, d_rec_off, d_rec_len, d_nm;
+    DevBuf d_cs, d_de, d_md, d_raw, d_off, d_words, d_wlen, d_aux, d_status, d_refs, d_seqs, d_cigs, d_recs, d_cursor, d_rec_off, d_rec_len, d_nm;
     if (int rc = d_raw.ensure(raw.size())) return rc;
     if (int rc = d_off.ensure(off.size() * 8)) return rc;
     if (int rc = d_words.ensure(words.size())) return rc;
@@ -1588,6 +1616,8 @@ try {
     if (int rc = d_status.ensure(N * 4 + 64)) return rc;
     if (int rc = d_nm.ensure(N * 4 + 64)) return rc;
     if (int rc = md ? d_md.ensure(N * 4 + 64) : 0) return rc;
+    if (int rc = tags ? d_cs.ensure(N * 4 + 64) : 0) return rc;
+    if (int rc = tags ? d_de.ensure(N * 4 + 64) : 0) return rc;
     for (DevBuf *d : {&d_wlen, &d_aux, &d_rec_off, &d_rec_len})
         if (int rc = d->ensure(N * 8 + 64)) return rc;
     HIP_TRY(hipMemcpy(d_raw.p, raw.data(), raw.size(), hipMemcpyHostToDevice));
@@ -1616,11 +1646,14 @@ try {
     bp.rec_off = d_rec_off.as<int64_t>(); bp.rec_len = d_rec_len.as<int64_t>();
     bp.refs = up.refs; bp.seqs = up.seqs; bp.nm = d_nm.as<int32_t>();
     if (md) bp.md_len = d_md.as<int32_t>();
+    if (tags) { bp.tags = tags; bp.cs_len = d_cs.as<int32_t>(); bp.de = d_de.as<float>(); }
     hipLaunchKernelGGL(nm_count_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
     if (md) hipLaunchKernelGGL(md_size_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
+    if (tags) hipLaunchKernelGGL(cs_size_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
     hipLaunchKernelGGL(place_bam_full_kernel, dim3(1), dim3(256), 0, st, bp);
     hipLaunchKernelGGL(emit_bam_full_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
     if (md) hipLaunchKernelGGL(emit_md_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
+    if (tags) hipLaunchKernelGGL(emit_cs_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     unsigned long long total = 0;
@@ -1653,6 +1686,15 @@ int npore_bam_set_output(npore_bam *b, int format, const char *bai_path, int fla
     b->out_format = format;
     b->out_bai = (format == NPORE_OUT_BAM && bai_path) ? bai_path : "";
     b->out_flags = flags;
+    b->out_tags = 0;
+    return NPORE_OK;
+}
+
+int npore_bam_set_output_tags(npore_bam *b, int tags)
+{
+    if (!b || !output_tags_ok(tags) || b->out_format != NPORE_OUT_BAM || !(b->out_flags & NPORE_OUT_FULL))      // (cs and de are tags of the FULL records)
+        return fail(NPORE_E_INVALID, "bad argument");
+    b->out_tags = tags;
     return NPORE_OK;
 }
 

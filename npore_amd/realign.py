@@ -72,6 +72,14 @@ def argparser():
                         help="--records full: write the MD tag behind the recounted NM, built on the GPU from the final CIGAR and the "
                              "bases NM is counted on (`samtools calmd`'s text, but an IUPAC letter other than N counts as a mismatch "
                              "and prints as N, as it does in NM).  Without it the records carry no MD: the input's is stale.")
+    parser.add_argument("--cs", choices=("short", "long"), default=None,
+                        help="--records full: write minimap2's cs tag behind NM (and MD), built on the GPU from the final CIGAR and "
+                             "the bases NM is counted on: `short`, `:<n>` for matches, `long`, `=<LETTERS>`.  As in NM, an IUPAC "
+                             "letter other than N counts as a mismatch (minimap2 leaves ambiguous bases out).  Without it the "
+                             "records carry no cs: the input's is stale.")
+    parser.add_argument("--de", action="store_true",
+                        help="--records full: write minimap2's de tag (gap-compressed per-base divergence, a float) behind cs, "
+                             "counted on the GPU in the same walk.  Without it the records carry no de: the input's is stale.")
     parser.add_argument("--bam_inflate", choices=("host", "device"), default="host",
                         help="One-pass reader: where the input BAM's BGZF blocks are inflated: `host`, on the CPU threads; `device`, "
                              "on the GPU, one wave per block (also for --recalc_cms --cms_source bam).  The output is the same.  "
@@ -93,6 +101,10 @@ def main():
     md = bool(getattr(cfg.args, "md", False))
     if md and records != "full":
         print("\nERROR: --md needs --records full.")
+        sys.exit(1)
+    cs, de = getattr(cfg.args, "cs", None), bool(getattr(cfg.args, "de", False))
+    if (cs or de) and records != "full":
+        print(f"\nERROR: {'--cs' if cs else '--de'} needs --out_format bam --records full.")
         sys.exit(1)
     if records == "full" and not native:
         print("\nERROR: --records full is written by the library's file pipeline: not with --python_io.")
@@ -163,7 +175,7 @@ def main():
         open(out_sam, "w").close()
     # BAM: the index beside the file (a rank's part: a sidecar with part-relative offsets, merged by dist.gather_bam_parts);
     # the EOF member ends the whole file, not a part
-    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress, records=records, md=md) if as_bam else {}
+    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress, records=records, md=md, cs=cs, de=de) if as_bam else {}
     gather = dist_mod.gather_bam_parts if as_bam else dist_mod.gather_parts
 
     print("> extracting read data from BAM")

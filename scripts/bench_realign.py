@@ -135,7 +135,7 @@ def start_output(a, out, nb):
     """The header of the output file, and what the realign calls need to write behind it in a.out_format."""
     if a.out_format == "bam":
         bam.create_bam_header(out, nb)
-        return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai", compress=a.bam_compress, records=a.records, md=a.md)
+        return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai", compress=a.bam_compress, records=a.records, md=a.md, cs=a.cs, de=a.de)
     bam.create_header(out, nb)
     return {}
 
@@ -260,6 +260,8 @@ def main():
     ap.add_argument("--records", choices=("reference", "full"), default="reference",
                     help="--out_format bam: the reference's records, or (full) the input records with only what the realignment changes replaced")
     ap.add_argument("--md", action="store_true", help="--records full: with the MD tag behind NM, built on the GPU")
+    ap.add_argument("--cs", choices=("short", "long"), default=None, help="--records full: with the cs tag behind NM / MD, built on the GPU")
+    ap.add_argument("--de", action="store_true", help="--records full: with the de tag behind that, counted on the GPU")
     ap.add_argument("--tags", action="store_true",
                     help="every synthetic read carries an RG:Z tag and a B,C array of l_seq / 2 bytes (an ML-like load for --records full)")
     ap.add_argument("--inflate", choices=("host", "device"), default="host",
@@ -272,6 +274,8 @@ def main():
         ap.error("--records full needs --out_format bam")
     if a.md and a.records != "full":
         ap.error("--md needs --records full")
+    if (a.cs or a.de) and a.records != "full":
+        ap.error("--cs / --de need --records full")
     if a.gen_into:
         print(json.dumps(build_inputs(a.gen_into, a.reads, a.distinct, a.ref_len, a.seed, a.const_qual, tags=a.tags)))
         return
@@ -353,7 +357,7 @@ def main():
                 "one_pass": one_pass, "one_pass_output_identical": same_one_pass,
                 "reads": a.reads, "distinct_reads": a.reads if a.distinct <= 0 else min(a.distinct, a.reads),
                 "qualities": "constant 20" if a.const_qual else "uniform per base over phred 0 ... 93 (reference test/generate_bam.py:63,79)",
-                "ref_len": a.ref_len, "r": a.r, "batch": a.batch, "out_format": a.out_format, "bam_compress": a.bam_compress, "records": a.records, "md": a.md, "tags": a.tags,
+                "ref_len": a.ref_len, "r": a.r, "batch": a.batch, "out_format": a.out_format, "bam_compress": a.bam_compress, "records": a.records, "md": a.md, "cs": a.cs, "de": a.de, "tags": a.tags,
                 "output_bytes": os.path.getsize(out + ".o"),
                 "host_cpus": len(os.sched_getaffinity(0)), "bam_bytes": os.path.getsize(bp),
                 "resident": resident, "streamed": streamed, "streamed_output_identical": same,

@@ -4,9 +4,16 @@ host twin, test_gpu_inflate_device.py through the gfx950 kernel.  No tests here.
 A case is (name, raw, out_len, want): the raw DEFLATE stream, the size its output must have, and the bytes (None: the
 stream is malformed for that size and must get status 0; FUZZ: whatever zlib says).  A launch places cases in one input and
 one output buffer: inputs at odd offsets, outputs back to back (guard = 0) or with 32 bytes of 0xA5 around each (guard = 32).
+
+Where zlib's compressor does not go: BitWriter writes any block type from explicit code lengths, hand_built_cases() states
+the edges of the format with it (codes of 15 bits, one or no distance code, the header's limits, repeats, the code-length
+code, the last bit of a stream, hundreds of blocks), mutant_cases() flips every bit of the head of six small streams and
+gives each mutant the size zlib inflates it to, and mixed_members() / damaged_files() cut a BAM's stream into BGZF members
+of every kind for the readers.
 """
 import functools
 import os
+import struct
 import zlib
 
 import numpy as np
@@ -95,6 +102,455 @@ class FixedWriter:
 
 def _literals(n, seed):
     return bytes(np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8))
+
+
+# ---- a writer for any block type: stored, fixed, dynamic from explicit code lengths; several blocks in one stream
+FIXED_LIT = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8
+FIXED_DIST = [5] * 32
+CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+CL_EXTRA = {16: 2, 17: 3, 18: 7}
+CL_ALL = [4] * 13 + [5] * 6                                          # a complete code over all 19 symbols: 13 / 16 + 6 / 32
+
+
+def canonical_codes(lengths):
+    """{symbol: (code, bits)} of the code lengths, RFC 1951 3.2.2 (the codes of an over-subscribed set are cut to their bits)"""
+    count = [0] * 16
+    for n in lengths:
+        count[n] += 1
+    count[0] = 0
+    code, first = 0, [0] * 16
+    for b in range(1, 16):
+        code = (code + count[b - 1]) << 1
+        first[b] = code
+    out = {}
+    for s, n in enumerate(lengths):
+        if n:
+            out[s] = (first[n] & ((1 << n) - 1), n)
+            first[n] += 1
+    return out
+
+
+def flat_lens(symbols, n):
+    """n code lengths: a complete code over the (two or more) symbols, each of k - 1 or k bits"""
+    symbols = sorted(set(symbols))
+    k = (len(symbols) - 1).bit_length()
+    short = (1 << k) - len(symbols)
+    lens = [0] * n
+    for j, s in enumerate(symbols):
+        lens[s] = k - 1 if j < short else k
+    return lens
+
+
+def plain_items(lens):
+    return [(n, 0) for n in lens]
+
+
+def run_items(lens):
+    """the lengths with their runs of zeros as repeats 17 and 18, as a compressor would send them"""
+    items, i = [], 0
+    while i < len(lens):
+        j = i
+        while j < len(lens) and lens[j] == 0:
+            j += 1
+        run = j - i
+        while run >= 3:
+            take = min(run, 138)
+            items.append((18, take - 11) if take >= 11 else (17, take - 3))
+            run -= take
+            i += take
+        if i < len(lens):
+            items.append((lens[i], 0))
+            i += 1
+    return items
+
+
+def expand_items(items):
+    """the code lengths a valid item list [(code-length symbol, value of its extra bits)] stands for"""
+    lens = []
+    for s, x in items:
+        assert 0 <= x < (1 << CL_EXTRA.get(s, 0))
+        if s < 16:
+            lens.append(s)
+        elif s == 16:
+            lens += [lens[-1]] * (3 + x)
+        else:
+            lens += [0] * ((3 if s == 17 else 11) + x)
+    return lens
+
+
+class BitWriter(FixedWriter):
+    """A stream block by block: stored(), fixed() or dynamic(), then literals() / match() / symbol() / raw codes, eob();
+    done() gives the stream.  `made` follows what the stream must inflate to (tracked calls only)."""
+
+    def __init__(self):
+        self.acc, self.n, self.out, self.made = 0, 0, bytearray(), bytearray()
+        self.lit, self.dist, self.headers_at = {}, {}, []
+
+    def position(self):
+        return 8 * len(self.out) + self.n
+
+    def stored(self, data, final=0, nlen=None):
+        self.headers_at.append(self.position())
+        self.bits(final, 1)
+        self.bits(0, 2)
+        self.bits(0, -self.n % 8)
+        self.out += struct.pack("<HH", len(data), (len(data) ^ 0xFFFF) if nlen is None else nlen) + data
+        self.made += data
+
+    def fixed(self, final=1):
+        self.headers_at.append(self.position())
+        self.bits(final, 1)
+        self.bits(1, 2)
+        self.lit, self.dist = canonical_codes(FIXED_LIT), canonical_codes(FIXED_DIST)
+
+    def dynamic(self, lit_lens=None, dist_lens=None, final=1, cl_lens=None, hclen=None, items=None, hlit=None, hdist=None):
+        """lit_lens / dist_lens: the codes of the block's symbols (None: what `items` expands to, cut at hlit); items: how
+        the lengths are sent (None: one by one); cl_lens / hclen: the code-length code (None: CL_ALL, as many as needed);
+        hlit / hdist: the counts the header announces (None: those of the lists)"""
+        if items is None:
+            items = plain_items(list(lit_lens) + list(dist_lens))
+        if lit_lens is None:
+            lens = expand_items(items)
+            lit_lens, dist_lens = lens[:hlit], lens[hlit:]
+        hlit = len(lit_lens) if hlit is None else hlit
+        hdist = len(dist_lens) if hdist is None else hdist
+        cl_lens = CL_ALL if cl_lens is None else cl_lens
+        if hclen is None:
+            hclen = max([4] + [i + 1 for i in range(19) if cl_lens[CL_ORDER[i]]])
+        self.headers_at.append(self.position())
+        self.bits(final, 1)
+        self.bits(2, 2)
+        self.bits(hlit - 257, 5)
+        self.bits(hdist - 1, 5)
+        self.bits(hclen - 4, 4)
+        for i in range(hclen):
+            self.bits(cl_lens[CL_ORDER[i]], 3)
+        cl = canonical_codes(cl_lens)
+        for s, x in items:
+            self.code(*cl[s])
+            self.bits(x, CL_EXTRA.get(s, 0))
+        self.lit, self.dist = canonical_codes(lit_lens), canonical_codes(dist_lens)
+
+    def symbol(self, s):
+        self.code(*self.lit[s])
+
+    def dist_symbol(self, s):
+        self.code(*self.dist[s])
+
+    def match(self, length, dist, track=True, len_symbol=None):
+        k = max(i for i in range(29) if LEN_BASE[i] <= length and (i == 28 or length < 258)) if len_symbol is None else len_symbol - 257
+        assert 0 <= length - LEN_BASE[k] < (1 << LEN_EXTRA[k])
+        self.symbol(257 + k)
+        self.bits(length - LEN_BASE[k], LEN_EXTRA[k])
+        j = max(i for i in range(30) if DIST_BASE[i] <= dist)
+        self.dist_symbol(j)
+        self.bits(dist - DIST_BASE[j], DIST_EXTRA[j])
+        if track:
+            for _ in range(length):
+                self.made.append(self.made[-dist])
+
+    def eob(self):
+        self.symbol(256)
+
+    def done(self):
+        return bytes(self.out + (bytes([self.acc]) if self.n else b""))
+
+    def end(self):
+        self.eob()
+        return self.done()
+
+
+def _same_as_fixed_writer():
+    """the streams of fixed_cases() come out of BitWriter byte for byte"""
+    for d, length in ((1, 3), (7, 258), (4097, 65), (32768, 257)):
+        a, b = FixedWriter(), BitWriter()
+        b.fixed()
+        for w in (a, b):
+            w.literals(_literals(d, d * 1000 + length))
+            w.match(length, d)
+            w.literals(b"Z")
+            w.match(3, 1)
+            w.match(min(length, 258), min(d, 2))
+        assert a.end() == b.end() and a.made == b.made, (d, length)
+
+
+_same_as_fixed_writer()
+
+
+def zlib_refusal(raw):
+    """zlib's words for refusing the stream (None: it does not refuse it, though it may want more input)"""
+    try:
+        zlib.decompressobj(-15).decompress(raw, IW_MAX_OUT + 2)
+    except zlib.error as e:
+        return str(e)
+    return None
+
+
+IW_MAX_OUT = 65536
+LETTERS15 = tuple(sorted(b"ACGTNacgtn#$%&*"))
+LONG_LENS = list(range(1, 15)) + [15, 15]                            # complete: 1/2 + ... + 2^-14 + 2 * 2^-15 = 1
+
+
+def long_literal_lens(low_long):
+    """literal / length code lengths 1, 2, ... 14, 15, 15 over LETTERS15 and 256 (low_long: the long codes on the low symbols)"""
+    lens = [0] * 257
+    for s, n in zip(LETTERS15 + (256,), LONG_LENS[::-1] if low_long else LONG_LENS):
+        lens[s] = n
+    return lens
+
+
+def _letters(n, seed, letters=LETTERS15):
+    """every letter three times, then n random ones"""
+    rng = np.random.default_rng(seed)
+    return bytes(letters) * 3 + bytes(rng.choice(np.array(letters, np.uint8), n))
+
+
+def long_literal_stream(low_long, items=plain_items, n=400):
+    w = BitWriter()
+    lens = long_literal_lens(low_long)
+    w.dynamic(lens, [0], items=items(lens + [0]))
+    w.literals(_letters(n, 31 + low_long))
+    return w
+
+
+def one_distance_stream(sym, items=plain_items):
+    """a block whose only distance code is one bit for distance symbol `sym`, with matches through it"""
+    w = BitWriter()
+    if DIST_BASE[sym] > 300:                                         # the bytes such a distance reaches back over
+        w.fixed(final=0)
+        w.literals(_literals(97, sym))
+        while len(w.made) < DIST_BASE[sym] + 100:
+            w.match(258, 97)
+        w.eob()
+    lit, dist = flat_lens(list(b"pqrstuvw") + [256, 257, 260, 285], 286), [0] * sym + [1]
+    w.dynamic(lit, dist, items=items(lit + dist))
+    w.literals(_letters(80, sym, tuple(b"pqrstuvw")))
+    lo, hi = DIST_BASE[sym], min(DIST_BASE[sym] + (1 << DIST_EXTRA[sym]) - 1, len(w.made))
+    for length, d in ((3, lo), (258, hi), (6, lo), (3, hi)):
+        w.match(length, d)
+        w.literals(b"q")
+    w.eob()
+    return w
+
+
+def lone_eob_payload(data):
+    """An empty non-final dynamic block whose literal / length code is the end-of-block code alone (one bit), then the
+    data in a stored block: legal (zlib takes it), one of the oddities the decoders here may decline"""
+    w = BitWriter()
+    w.dynamic([0] * 256 + [1], [0], final=0, items=run_items([0] * 256 + [1, 0]))
+    w.eob()
+    w.stored(data, final=1)
+    return w.done()
+
+
+@functools.lru_cache(None)
+def hand_built_cases():
+    """Streams zlib's compressor never writes, each stated symbol by symbol; a malformed one is named "bad: ..." and is
+    checked to be refused by zlib for the reason it was built for."""
+    cases = []
+
+    def add(name, w, why=False, raw=None, n=None):
+        """why: False = valid; else the stream is malformed, and zlib's words contain `why` (None: it only runs short)"""
+        raw = w.done() if raw is None else raw
+        n = len(w.made) if n is None else n
+        if why is False:
+            want = bytes(w.made)
+            assert zlib_inflate(raw, n) == want, name
+            cases.append((name, raw, n, want))
+        else:
+            said = zlib_refusal(raw)
+            assert zlib_inflate(raw, n) is None and (said is None if why is None else said is not None and why in said), (name, said)
+            cases.append(("bad: " + name, raw, n, None))
+
+    def body(w, text=b"lit-only body"):
+        w.literals(text)
+        w.eob()
+        return w
+
+    # -- long codes: beyond the primary tables (10 bits literal / length, 8 bits distance)
+    for low_long in (0, 1):
+        w = long_literal_stream(low_long)
+        w.eob()
+        add("literal codes of 1 to 15 bits" + (", long ones low" if low_long else ""), w)
+    far_lit = flat_lens(list(b"abcdefghijklmnop") + [256, 257, 285], 286)
+    for which in ("smallest", "largest"):
+        w = BitWriter()
+        w.dynamic(far_lit, LONG_LENS)
+        w.literals(_letters(260, 41, tuple(b"abcdefghijklmnop")))
+        for j in range(16):
+            d = DIST_BASE[j] if which == "smallest" else DIST_BASE[j] + (1 << DIST_EXTRA[j]) - 1
+            for length in (3, 258):
+                w.match(length, d)
+                w.literals(bytes([97 + (j + length) % 16]))
+        w.eob()
+        add("distance codes of 1 to 15 bits, %s distances" % which, w)
+    # -- one distance code of one bit; no distance code
+    for sym in (0, 11, 29):
+        add("one distance code, symbol %d" % sym, one_distance_stream(sym))
+    few = flat_lens(list(b"xyz") + [256, 257], 258)
+    w = BitWriter()
+    w.dynamic(few, [1])
+    w.literals(b"xyzzy")
+    w.symbol(257)
+    w.code(1, 1)                                                    # the 1-bit code that has no symbol
+    w.eob()
+    add("the unassigned 1-bit distance code", w, "invalid distance code", n=8)
+    for name, dist in (("one distance code of 2 bits", [2]), ("two distance codes of 2 bits", [2, 2]), ("three 1-bit distance codes", [1, 1, 1])):
+        w = BitWriter()
+        w.dynamic(few, dist)
+        add(name, body(w, b"xyzzy"), "invalid distances set")
+    w = BitWriter()
+    w.dynamic(few, [0])
+    add("no distance code, literals only", body(w, b"xyzzy" * 40))
+    w = BitWriter()
+    w.dynamic(few, [0])
+    w.literals(b"xyzzy")
+    w.symbol(257)
+    w.bits(0, 5)
+    w.eob()
+    add("a length symbol without any distance code", w, "invalid distance code", n=8)
+    # -- a literal / length code of a single symbol
+    data = _letters(200, 43)
+    raw = lone_eob_payload(data)
+    assert zlib_inflate(raw, len(data)) == data
+    cases.append(("lone end-of-block code, then stored", raw, len(data), data))
+    w = BitWriter()
+    w.dynamic(flat_lens(b"wxyz", 257), [0])
+    w.literals(b"xyzzy")
+    add("a literal set without 256", w, "missing end-of-block")
+    # -- header limits
+    w = BitWriter()
+    w.fixed(final=0)
+    w.literals(_literals(128, 47))
+    for _ in range(127):
+        w.match(258, 128)
+    w.eob()
+    assert len(w.made) >= 32768
+    w.dynamic(flat_lens(list(b"hijklmno") + [256, 284, 285], 286), flat_lens([28, 29], 30))
+    w.literals(b"limno")
+    for length, d, s in ((258, 16385, None), (258, 24577, 284), (227, 32768, None), (258, 24576, 284), (257, 32768, None), (258, 32768, None)):
+        w.match(length, d, len_symbol=s)
+        w.literals(b"k")
+    w.eob()
+    add("HLIT 286 and HDIST 30, 258 as 285 and as 284 + 31", w)
+    for hlit, hdist in ((287, 2), (288, 2), (257, 31), (257, 32)):
+        w = BitWriter()
+        w.dynamic(flat_lens(list(b"xyz") + [256], hlit), flat_lens([0, 1], hdist))
+        add("HLIT %d, HDIST %d" % (hlit, hdist), body(w, b"xyzzy"), "too many length or distance symbols")
+    for s in (286, 287):
+        w = BitWriter()
+        w.fixed()
+        w.literals(b"abc")
+        w.symbol(s)
+        w.bits(0, 5)
+        w.eob()
+        add("fixed block, literal/length symbol %d" % s, w, "invalid literal/length code", n=6)
+    for s in (30, 31):
+        w = BitWriter()
+        w.fixed()
+        w.literals(b"abc")
+        w.symbol(257)
+        w.dist_symbol(s)
+        w.eob()
+        add("fixed block, distance symbol %d" % s, w, "invalid distance code", n=6)
+    # -- repeats in the code lengths
+    lens = flat_lens([138, 139, 140, 256], 257) + [0]
+    w = BitWriter()
+    w.dynamic(items=[(18, 127)] + plain_items(lens[138:]), hlit=257)
+    assert w.lit == canonical_codes(lens[:257])
+    add("repeat 18 with 138 zeros", body(w, bytes([138, 139, 140, 139] * 30)))
+    lens = [0] * 255 + [2]                                          # 255, 256, 257 and the four distance codes: 2 bits, by one repeat
+    lens[65] = lens[66] = 3
+    w = BitWriter()
+    w.dynamic(items=plain_items(lens) + [(16, 3)], hlit=258)
+    assert len(w.lit) == 5 and w.dist == canonical_codes([2, 2, 2, 2])
+    w.literals(bytes([65, 66, 255, 66, 65]))
+    for d in (1, 2, 3, 4, 2):
+        w.match(3, d)
+        w.literals(bytes([255]))
+    w.eob()
+    add("repeat 16 across the literal / distance boundary", w)
+    w = BitWriter()                                                 # 0: 2 bits | 17: three zeros | 16: three more | 7, 8: 2 bits | zeros | 256: 2 bits | no distance code
+    w.dynamic(items=[(2, 0), (17, 0), (16, 0), (2, 0), (2, 0), (18, 127), (18, 98), (2, 0), (0, 0)], hlit=257)
+    assert sorted(w.lit) == [0, 7, 8, 256]
+    add("repeat 16 directly after a 17", body(w, bytes([0, 7, 8, 8, 7, 0] * 20)))
+    lens = flat_lens(list(b"xyz") + [256], 257) + [0]
+    w = BitWriter()
+    w.dynamic(lens[:257], lens[257:], items=[(16, 0)] + plain_items(lens[3:]))
+    add("repeat 16 as the first item", body(w, b"xyzzy"), "invalid bit length repeat")
+    w = BitWriter()
+    w.dynamic(lens[:257], lens[257:], items=plain_items(lens[:250]) + [(18, 127)])
+    add("a repeat past HLIT + HDIST", body(w, b"xyzzy"), "invalid bit length repeat")
+    # -- the code-length code
+    lens = long_literal_lens(0)
+    w = BitWriter()
+    w.dynamic(lens, [0], cl_lens=[4] * 16 + [0] * 3)
+    add("HCLEN 19, sixteen 4-bit code-length codes", body(w, _letters(300, 53)))
+    lens = flat_lens(list(b"xyz") + [256], 257)
+    w = BitWriter()
+    w.dynamic(lens, [0], cl_lens=[0] * 19, hclen=4, items=[])
+    w.bits(0, 8 * 48)
+    add("HCLEN 4, every code-length code absent", w, "missing end-of-block", n=5)
+    for name, cl in (("a single 1-bit code-length code", [1] + [0] * 18), ("three 1-bit code-length codes", [1, 1, 1] + [0] * 16)):
+        w = BitWriter()
+        w.dynamic(lens, [0], cl_lens=cl, items=[(0, 0)] * 258)
+        w.bits(0, 64)
+        add(name, w, "invalid code lengths set", n=5)
+    for name, n in (("three 2-bit literal codes (incomplete)", 2), ("three 1-bit literal codes (over-subscribed)", 1)):
+        bad = [0] * 257
+        bad[120] = bad[121] = bad[256] = n
+        w = BitWriter()
+        w.dynamic(bad, [0])
+        add(name, body(w, b"xyyx"), "invalid literal/lengths set")
+    # -- the end of the stream, bit by bit: a 9-bit literal more moves the last bit of the end-of-block code by one
+    ends = set()
+    for k in range(8):
+        w = BitWriter()
+        w.fixed()
+        w.literals(b"end" + bytes(range(200, 200 + k)))
+        w.eob()
+        ends.add(w.position() % 8)
+        add("the last code ends at bit %d" % (w.position() % 8), w)
+        add("the last code ends at bit %d, last byte cut off" % (w.position() % 8), w, None, raw=w.done()[:-1])
+        add("the last code ends at bit %d, a zero byte behind" % (w.position() % 8), w, raw=w.done() + b"\0")
+    assert len(ends) == 8
+    # -- many blocks
+    w = BitWriter()
+    for _ in range(300):
+        w.fixed(final=0)
+        w.eob()
+    w.fixed()
+    add("300 empty fixed blocks, then three literals", body(w, b"abc"))
+    w = BitWriter()
+    for k in range(201):
+        w.stored(b"", final=int(k == 200))
+    add("201 empty stored blocks", w)
+    w = BitWriter()
+    rng = np.random.default_rng(59)
+    for k in range(40):
+        w.fixed(final=0)
+        w.literals(b"round %2d " % k + bytes(range(150, 150 + k % 8)))      # (k % 8 literals of 9 bits: the next header's bit offset)
+        w.match(3 + k, 4 + k % 5)
+        w.eob()
+        w.stored(bytes(rng.integers(0, 256, 61 + 13 * k, dtype=np.uint8)))
+    lens = long_literal_lens(1)
+    w.dynamic(lens, [0], items=run_items(lens + [0]))
+    w.literals(_letters(100, 61))
+    w.eob()
+    assert len(w.headers_at) == 81 and {p % 8 for p in w.headers_at[1:80:2]} == set(range(8))      # (the stored blocks' headers)
+    add("40 rounds of fixed and stored blocks, then a dynamic one", w)
+    w = BitWriter()
+    w.stored(_literals(65535, 67))
+    w.stored(b"!", final=1)
+    add("stored blocks of 65535 bytes and 1 byte", w)
+    return tuple(cases)
+
+
+def oversize_case():
+    """an out_len beyond a BGZF member's 65 536 bytes: refused for its size alone, nothing written"""
+    raw = next(c[1] for c in hand_built_cases() if c[0] == "stored blocks of 65535 bytes and 1 byte")
+    assert zlib_inflate(raw, IW_MAX_OUT + 1) is None
+    return ("bad: out_len 65537", raw, IW_MAX_OUT + 1, None)
 
 
 def fixed_cases():
@@ -187,7 +643,7 @@ def valid_and_malformed_cases():
         cases.append(("reads.bam block %d" % i, pay, isize, zlib.decompress(pay, -15)))
     for name, raw, n, want in cases:
         assert zlib_inflate(raw, n) == want, name
-    return tuple(cases + fixed_cases())
+    return tuple(cases + fixed_cases() + list(hand_built_cases()))
 
 
 @functools.lru_cache(None)
@@ -272,6 +728,145 @@ def corrupt_launches():
     return (Launch("corrupt guard", corrupt_cases(), GUARD), Launch("corrupt tight", mixed + [good], 0))
 
 
+def zlib_size(raw):
+    """the size zlib inflates the stream to, or None where it refuses it, wants more input or gives more than a member's 65 536 bytes"""
+    d = zlib.decompressobj(-15)
+    try:
+        out = d.decompress(raw, IW_MAX_OUT + 1)
+    except zlib.error:
+        return None
+    return len(out) if d.eof and len(out) <= IW_MAX_OUT else None
+
+
+MUTATED_BYTES = 96
+OTHER_SIZE = 500
+
+
+@functools.lru_cache(None)
+def mutant_bases():
+    rng = np.random.default_rng(23)
+    reads = bytes(rng.choice(np.frombuffer(b"ACGTN", np.uint8), 300)) + bytes(rng.integers(33, 75, 200, dtype=np.uint8))
+    w = long_literal_stream(0, run_items, 600)
+    w.eob()
+    return (("level 6, bases and qualities", deflate(reads, 6)), ("level 9, repetitive", deflate(b"GATTACA-gattaca+" * 24, 9)),
+            ("Z_FIXED, two-bit symbols", deflate(bytes(rng.integers(0, 4, 400, dtype=np.uint8)), 6, zlib.Z_FIXED)),
+            ("level 0", deflate(bytes(rng.integers(0, 256, 100, dtype=np.uint8)), 0)),
+            ("literal codes of 1 to 15 bits", w.done()), ("one distance code, symbol 11", one_distance_stream(11, run_items).done()))
+
+
+@functools.lru_cache(None)
+def mutant_cases():
+    """Every single-bit flip of the first MUTATED_BYTES bytes of each base.  A mutant's out_len is the size zlib inflates it
+    to (so that a stream zlib accepts is one the decoder must get right, not one it may refuse for its size), OTHER_SIZE
+    where zlib does not; want: zlib's bytes, or None."""
+    out = []
+    for name, base in mutant_bases():
+        assert zlib_size(base) is not None, name
+        for bit in range(8 * min(len(base), MUTATED_BYTES)):
+            raw = bytearray(base)
+            raw[bit >> 3] ^= 1 << (bit & 7)
+            raw = bytes(raw)
+            n = zlib_size(raw)
+            n = OTHER_SIZE if n is None else n
+            out.append(("%s, bit %d" % (name, bit), raw, n, zlib_inflate(raw, n)))
+    return tuple(out)
+
+
+@functools.lru_cache(None)
+def mutant_launches():
+    return (Launch("mutants guard", mutant_cases(), GUARD), Launch("mutants tight", mutant_cases(), 0))
+
+
+@functools.lru_cache(None)
+def oversize_launch():
+    """Not for the debug entries (they refuse such a table as a whole: test_inflate_wave.py); for the stand-alone program."""
+    good = next(c for c in valid_and_malformed_cases() if c[0] == "stored, by hand")
+    return Launch("oversize guard", [good, oversize_case(), good], GUARD)
+
+
+# ---- BGZF files whose members are chosen by hand
+EMPTY_PAYLOAD = bytes([3, 0])
+LONE_KIND = "lone end-of-block"
+
+
+def bgzf_member(payload, data, crc=None):
+    """one BGZF member: the gzip header with the BC subfield, the payload, the CRC-32 (crc: another one) and ISIZE of the data"""
+    return (struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 0xFF, 6, 66, 67, 2, len(payload) + 25) + payload +
+            struct.pack("<II", zlib.crc32(data) if crc is None else crc, len(data)))
+
+
+def _sync_flushed(data):
+    c, a, b = zlib.compressobj(6, zlib.DEFLATED, -15), len(data) // 3, 2 * len(data) // 3
+    return c.compress(data[:a]) + c.flush(zlib.Z_SYNC_FLUSH) + c.compress(data[a:b]) + c.flush(zlib.Z_SYNC_FLUSH) + c.compress(data[b:]) + c.flush()
+
+
+MEMBER_KINDS = (("level 9", lambda d: deflate(d, 9)), ("Z_FIXED", lambda d: deflate(d, 6, zlib.Z_FIXED)), ("level 0", lambda d: deflate(d, 0)),
+                ("sync-flushed", _sync_flushed))
+
+
+def mixed_members(stream, lo=3000, hi=8000, seed=71):
+    """[(kind, payload, data)]: the stream cut into members of lo to hi bytes that rotate through MEMBER_KINDS, every fifth one
+    lone_eob_payload; an empty member behind every seventh, two of them once, and the end-of-file member"""
+    rng = np.random.default_rng(seed)
+    out, p, k, turn = [], 0, 0, 0
+    while p < len(stream):
+        data = bytes(stream[p:p + int(rng.integers(lo, hi))])
+        p += len(data)
+        k += 1
+        if k % 5 == 0:
+            kind, payload = LONE_KIND, lone_eob_payload(data)
+        else:
+            kind, payload = MEMBER_KINDS[turn % 4][0], MEMBER_KINDS[turn % 4][1](data)
+            turn += 1
+        assert zlib_inflate(payload, len(data)) == data
+        out.append((kind, payload, data))
+        if k % 7 == 0:
+            out += [("empty", EMPTY_PAYLOAD, b"")] * (2 if k == 14 else 1)
+    return out + [("empty", EMPTY_PAYLOAD, b"")]
+
+
+def member_bytes(members):
+    return [bgzf_member(payload, data) for _, payload, data in members]
+
+
+def damaged_files(members, first=17):
+    """{what: (index, the file's members as bytes)}: ONE member changed, none of the `first` members an open call may read"""
+    def pick(kind, ok=lambda payload: True):
+        return next(i for i in range(first, len(members)) if members[i][0] == kind and ok(members[i][1]))
+
+    def with_member(i, member):
+        out = member_bytes(members)
+        out[i] = member
+        return i, out
+
+    res = {}
+    i = pick("Z_FIXED")
+    res["crc"] = with_member(i, bgzf_member(members[i][1], members[i][2], zlib.crc32(members[i][2]) ^ 0x10))
+    i = pick("level 0")                                             # (one stored block: 01 LEN NLEN, then the bytes)
+    _, payload, data = members[i]
+    bad = bytearray(payload)
+    bad[5 + len(data) // 2] ^= 0x40
+    assert zlib_inflate(bytes(bad), len(data)) not in (None, data)
+    res["stored byte"] = with_member(i, bgzf_member(bytes(bad), data))
+    i = pick("level 9", lambda payload: payload[0] >> 1 & 3 == 2)
+    _, payload, data = members[i]
+    for bit in range(3, 17 + 3 * 19):                               # HLIT, HDIST, HCLEN, the code-length code's lengths
+        bad = bytearray(payload)
+        bad[bit >> 3] ^= 1 << (bit & 7)
+        if zlib_refusal(bytes(bad)) is not None:
+            break
+    assert zlib_refusal(bytes(bad)) is not None
+    res["header bit"] = with_member(i, bgzf_member(bytes(bad), data))
+    return res
+
+
+def twin_declines(members):
+    """how many of the non-empty members the host twin -- hence the device -- leaves to the host decoder"""
+    launch = Launch("members", [(kind, payload, len(data), data) for kind, payload, data in members if data], 0)
+    status, _ = _call(_lib.load().npore_debug_inflate_wave_host, launch)
+    return int((status == 0).sum())
+
+
 def _call(fn, launch, *head):
     out = launch.fresh_out()
     status = np.full(len(launch.cases), -7, np.int32)
@@ -295,11 +890,13 @@ def device(ctx, launch):
 
 
 def dump_corpus(path):
-    """Every launch as scripts/asan_inflate_wave.cpp reads it (the stand-alone sanitizer run of the host twin)."""
+    """Every launch as scripts/asan_inflate_wave.cpp reads it (the stand-alone sanitizer run of the host twin); expect: 1 zlib
+    accepts and csrc/inflate.hpp takes the stream, 0 malformed, -1 either (fuzz, mutants, the oddities inflate.hpp declines)"""
     with open(path, "wb") as fh:
-        for launch in launches() + corrupt_launches():
+        for launch in launches() + corrupt_launches() + mutant_launches() + (oversize_launch(),):
             n = len(launch.cases)
-            expect = np.array([-1 if c[3] is FUZZ else 0 if c[3] is None else -1 if not _host_takes(c) else 1 for c in launch.cases], np.int32)
+            either = launch in mutant_launches()
+            expect = np.array([-1 if either or c[3] is FUZZ else 0 if c[3] is None else -1 if not _host_takes(c) else 1 for c in launch.cases], np.int32)
             fh.write(b"IWL1" + np.array([n, launch.inp.size, launch.out_bytes], np.int64).tobytes())
             for a in (launch.in_off, launch.in_len, launch.out_off, launch.out_len):
                 fh.write(a.tobytes())

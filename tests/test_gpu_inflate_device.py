@@ -44,6 +44,20 @@ def test_kernel_equals_host_twin(ctx, launch):
     assert np.array_equal(out, want_out), int(np.nonzero(out != want_out)[0][0])
 
 
+@pytest.mark.parametrize("guard", (0, idc.GUARD))
+def test_kernel_takes_the_deflate_limit_members(ctx, guard):
+    """The blocks this tree's coder writes at its limits (deflate_limit_cases.py: codes of 15 bits in both alphabets, tokens of
+    48 bits, 65 280 bytes each, within the 65 536 of the entry): status 1 and the payload, as the host twin has it."""
+    import deflate_limit_cases as dlc
+    launch = dlc.inflate_launch(guard)
+    want_status, want_out = idc.twin(launch)
+    status, out = idc.device(ctx, launch)
+    assert (status == 1).all() and np.array_equal(status, want_status)
+    for k, case in enumerate(launch.cases):
+        assert launch.piece(out, k) == case[3], case[0]
+    assert launch.guards_intact(out) and np.array_equal(out, want_out)
+
+
 def test_out_len_beyond_a_member_is_refused_unread(ctx):
     """the device entry refuses a table with 65 537 bytes of output as a whole, as the host twin's entry does: no launch"""
     launch = idc.oversize_launch()

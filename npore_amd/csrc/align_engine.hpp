@@ -614,17 +614,8 @@ int post_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs &
             bp.refs = sp.refs; bp.seqs = sp.seqs; bp.nm = w->nm.as<int32_t>();
             if (a.bam->md) bp.md_len = w->md_len.as<int32_t>();      // (MD: its size in front of the placement, its text behind the record)
             if (a.bam->tags) { bp.tags = a.bam->tags; bp.cs_len = w->cs_len.as<int32_t>(); bp.de = w->de_val.as<float>(); }      // (cs / de: the same)
-            hipLaunchKernelGGL(nm_count_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
-            if (bp.md_len) hipLaunchKernelGGL(md_size_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
-            if (bp.tags) hipLaunchKernelGGL(cs_size_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
-            hipLaunchKernelGGL(place_bam_full_kernel, dim3(1), dim3(256), 0, s, bp);
-            hipLaunchKernelGGL(emit_bam_full_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
-            if (bp.md_len) hipLaunchKernelGGL(emit_md_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
-            if (bp.tags) hipLaunchKernelGGL(emit_cs_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
-        } else {
-            hipLaunchKernelGGL(place_bam_records_kernel, dim3(1), dim3(256), 0, s, bp);
-            hipLaunchKernelGGL(emit_bam_records_kernel, dim3((unsigned)nr), dim3(64), 0, s, bp);
         }
+        launch_bam_emit(bp, a.bam->full, s);
         if (a.bam->deflate && p.g1 == a.n_reads) launch_deflate(a.bam->dfl, s);      // the batch's records are complete
     } else if (p.mode == OutMode::CompactText) {  // the texts to the front of the batch's compact buffer (unpack_kernels.hpp)
         if (p.g0 == 0) HIP_TRY(hipMemsetAsync(a.compact->d_cursor, 0, 8, s));

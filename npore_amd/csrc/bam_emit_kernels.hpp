@@ -3,23 +3,24 @@
 // bam_reader.hpp states the record and holds the host twin (bam_record_into).  Almost everything a record needs is on
 // the device already: the input record up to the end of its qualities (what unpack_records_kernel reads, uploaded a
 // little further in this mode), and the final CIGAR, which standardize_words_kernel (kernels.hpp) leaves as
-// `len << 4 | op` words in the read's slot.  Two kernels per group of reads, behind its standardisation, on the
-// traceback stream:
-//   place_bam_records_kernel  one workgroup: every kept read's size, 36 + l_read_name + 4 * n_cigar + (l_seq + 1) / 2 +
-//                             l_seq + tag, and a scan over the sizes -- the group's records lie one after the other, in
-//                             input order, behind those of the batch's groups before it (a cursor that the groups, which
-//                             follow each other on one stream, hand on);
-//   emit_bam_records_kernel   one wavefront per read: fixed fields, name, CIGAR words, the 4-bit bases from the leading
-//                             soft clip on (an odd clip moves every nibble), the quality slice, the HP tag.
+// `len << 4 | op` words in the read's slot.  launch_bam_emit, at the end of this file, states what runs per group of reads,
+// behind its standardisation, on the traceback stream.  Either form is a placement and an assembly:
+//   place_bam_*_kernel  one workgroup: every kept read's size and a scan over the sizes -- the group's records lie one after
+//                       the other, in input order, behind those of the batch's groups before it (a cursor that the groups,
+//                       which follow each other on one stream, hand on);
+//   emit_bam_*_kernel   one wavefront per read: fixed fields, name, CIGAR words, bases, qualities, tags.
+// The reference form (place_bam_records_kernel, emit_bam_records_kernel) writes the 4-bit bases from the leading soft clip on
+// (an odd clip moves every nibble), the quality slice and the HP tag.  FULL records (NPORE_OUT_FULL, bam_reader.hpp FULL
+// RECORD; place_bam_full_kernel, emit_bam_full_kernel) keep clips and aux and end in tags made from the final CIGAR, each by a
+// kernel in front of the placement, which needs its size, and, where it is a text, one behind the assembly, which writes it:
+//   NM       nm_count_kernel                   (nm_rec.hpp)
+//   MD       md_size_kernel, emit_md_kernel    (md_rec.hpp, NPORE_OUT_MD): ONE walk, md_walk, launched with two sinks
+//   cs, de   cs_size_kernel, emit_cs_kernel    (cs_rec.hpp, NPORE_TAG_*): ONE walk, cs_walk, likewise
 // A final CIGAR of more than 65 535 operations goes out as htslib writes it (bam_reader.hpp RECORD): two placeholder words
-// in the CIGAR's place, the real words in a CG:B,I tag behind HP -- 16 bytes more, in both kernels.
-// FULL records (NPORE_OUT_FULL, bam_reader.hpp FULL RECORD) have three kernels of their own at the end of this file --
-// nm_count_kernel in front of the same two steps, place_bam_full_kernel and emit_bam_full_kernel --; the two above are
-// what they were.  With NPORE_OUT_MD beside it the MD tag follows NM (md_rec.hpp): md_size_kernel between nm_count_kernel
-// and the placement, emit_md_kernel behind emit_bam_full_kernel -- ONE walk (md_walk), launched with two sinks.
+// in the CIGAR's place, the real words in a CG:B,I tag behind the other tags, in either form.
 // The host then takes the batch's bytes as they lie (BgzfStoredWriter) and the records' lengths for its index.
-// Both run beside the next batch's fill kernel and keep to what the other light kernels keep to: at most
-// 64 vector registers; the placement's 2 KB of LDS are less than a fill workgroup leaves free, the assembly has none.
+// All run beside the next batch's fill kernel and keep to what the other light kernels keep to: at most
+// 64 vector registers; the placement's 2 KB of LDS are less than a fill workgroup leaves free, the others have none.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,6 +58,11 @@ struct BamEmitParams {
     int32_t *cs_len = nullptr;     // [n_reads], with any tag (0 without NPORE_TAG_CS)
     float *de = nullptr;           // [n_reads], with any tag
 };
+
+__device__ __forceinline__ void st32(uint8_t *q, uint32_t w)      // little-endian, unaligned
+{
+    q[0] = (uint8_t)w; q[1] = (uint8_t)(w >> 8); q[2] = (uint8_t)(w >> 16); q[3] = (uint8_t)(w >> 24);
+}
 
 __device__ __forceinline__ int bam_hp_bytes(int64_t hp)
 {
@@ -189,8 +195,7 @@ __global__ __launch_bounds__(64) void emit_bam_records_kernel(BamEmitParams p)
             case 8: w = (uint32_t)reflen; break;
             default: break;
         }
-        uint8_t *q = o + 4 * lane;
-        q[0] = (uint8_t)w; q[1] = (uint8_t)(w >> 8); q[2] = (uint8_t)(w >> 16); q[3] = (uint8_t)(w >> 24);
+        st32(o + 4 * lane, w);
     }
     o += 36;
     for (int j = lane; j < l_rn; j += 64) o[j] = f[32 + j];
@@ -198,8 +203,7 @@ __global__ __launch_bounds__(64) void emit_bam_records_kernel(BamEmitParams p)
     if (lng) {                                                   // the placeholder: <l_seq>S<reflen>N
         if (lane < 2) {
             const uint32_t w = lane == 0 ? ((uint32_t)sl << 4 | 4u) : ((uint32_t)reflen << 4 | 3u);
-            uint8_t *q = o + 4 * lane;
-            q[0] = (uint8_t)w; q[1] = (uint8_t)(w >> 8); q[2] = (uint8_t)(w >> 16); q[3] = (uint8_t)(w >> 24);
+            st32(o + 4 * lane, w);
         }
         o += 8;
     } else {
@@ -331,14 +335,13 @@ __global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
     const int32_t pos = (int32_t)ld32(f + 4);
     const int l_rn = f[8];
     const int64_t reflen = p.ref_off[k + 1] - p.ref_off[k], body = (s.l_seq + 1) / 2 + s.l_seq + s.aux;
-    auto put32 = [](uint8_t *q, uint32_t w) { q[0] = (uint8_t)w; q[1] = (uint8_t)(w >> 8); q[2] = (uint8_t)(w >> 16); q[3] = (uint8_t)(w >> 24); };
     uint8_t *o = p.recs + p.rec_off[k];
     if (lane < 9) {                                              // block_size and the fixed fields, a word per lane: the input's but bin and n_cigar_op
         uint32_t w = ld32(f + 4 * (lane > 0 ? lane - 1 : 0));
         if (lane == 0) w = (uint32_t)(size - 4);
         if (lane == 3) w = (uint32_t)l_rn | (uint32_t)f[9] << 8 | bam_reg2bin_dev(pos, (int64_t)pos + max((int64_t)1, reflen)) << 16;
         if (lane == 4) w = (s.lng ? 2u : (uint32_t)s.n_cig) | ld16(f + 14) << 16;
-        put32(o + 4 * lane, w);
+        st32(o + 4 * lane, w);
     }
     o += 36;
     for (int j = lane; j < l_rn; j += 64) o[j] = f[32 + j];
@@ -346,7 +349,7 @@ __global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
     uint8_t *cw = o;                                             // where the CIGAR words go
     if (s.lng) {                                                 // the placeholder here, CG:B,I behind NM (and MD, cs, de)
         cw = o + 8 + body + 3 + s.nmb + s.mdb + s.csb + s.deb + 8;
-        if (lane < 2) put32(o + 4 * lane, lane == 0 ? ((uint32_t)s.l_seq << 4 | 4u) : ((uint32_t)reflen << 4 | 3u));
+        if (lane < 2) st32(o + 4 * lane, lane == 0 ? ((uint32_t)s.l_seq << 4 | 4u) : ((uint32_t)reflen << 4 | 3u));
         if (lane >= 4 && lane < 8) cw[lane - 12] = (uint8_t)"CGBI"[lane - 4];
         if (lane >= 8 && lane < 12) cw[lane - 12] = (uint8_t)((uint32_t)s.n_cig >> (8 * (lane - 8)));
         o += 8;
@@ -410,7 +413,7 @@ __device__ __forceinline__ uint32_t md_walk(const BamEmitParams &p, int64_t k, i
                     sink.put(at + nd, (uint8_t)'^');
                 }
                 at += (uint32_t)nd + 1u;
-                for (uint32_t q = (uint32_t)lane; q < lj; q += 64) sink.put(at + q, md_letter(md_ref_code(ref, rl, aj + q)));
+                for (uint32_t q = (uint32_t)lane; q < lj; q += 64) sink.put(at + q, md_letter(code_at(ref, rl, aj + q)));
                 at += lj;
                 u = 0;
                 continue;
@@ -432,7 +435,7 @@ __device__ __forceinline__ uint32_t md_walk(const BamEmitParams &p, int64_t k, i
                 if (d) {
                     const uint32_t mine = at + incl - bytes;
                     md_put_decimal(sink, mine, cnt, nd);
-                    sink.put(mine + nd, md_letter(md_ref_code(ref, rl, aj + q)));
+                    sink.put(mine + nd, md_letter(code_at(ref, rl, aj + q)));
                 }
                 at += (uint32_t)__shfl((int)incl, 63);
                 u = in_round - 1u - (uint32_t)(63 - (int)__builtin_clzll(ev));
@@ -530,7 +533,7 @@ __device__ __forceinline__ uint32_t cs_walk(const BamEmitParams &p, int64_t k, i
                 at += 1u;
                 const uint8_t *arr = opj == 1u ? seq : ref;
                 const int64_t al = opj == 1u ? sl : rl, from = opj == 1u ? bj : aj;
-                for (uint32_t q = (uint32_t)lane; q < lj; q += 64) sink.put(at + q, cs_lower(cs_code(arr, al, from + q)));
+                for (uint32_t q = (uint32_t)lane; q < lj; q += 64) sink.put(at + q, cs_lower(code_at(arr, al, from + q)));
                 at += lj;
                 c.g++;
                 continue;
@@ -567,11 +570,11 @@ __device__ __forceinline__ uint32_t cs_walk(const BamEmitParams &p, int64_t k, i
                         mine += 1u + (uint32_t)nd;
                     }
                     sink.put(mine, (uint8_t)'*');
-                    sink.put(mine + 1u, cs_lower(cs_code(ref, rl, aj + q)));
-                    sink.put(mine + 2u, cs_lower(cs_code(seq, sl, bj + q)));
+                    sink.put(mine + 1u, cs_lower(code_at(ref, rl, aj + q)));
+                    sink.put(mine + 2u, cs_lower(code_at(seq, sl, bj + q)));
                 } else if (LNG && q < lj) {
                     if (bytes == 2u) sink.put(mine, (uint8_t)'=');
-                    sink.put(mine + bytes - 1u, md_letter(cs_code(ref, rl, aj + q)));
+                    sink.put(mine + bytes - 1u, md_letter(code_at(ref, rl, aj + q)));
                 }
                 at += (uint32_t)__shfl((int)incl, 63);
                 u = ev ? in_round - 1u - (uint32_t)(63 - (int)__builtin_clzll(ev)) : u + in_round;
@@ -624,6 +627,25 @@ __global__ __launch_bounds__(64) void emit_cs_kernel(BamEmitParams p)
         if (lane < 3) o[lane] = (uint8_t)"def"[lane];
         else if (lane < 7) o[lane] = (uint8_t)(bits >> (8 * (lane - 3)));
     }
+}
+
+// What a group's records take, in order, on stream s: the reference form's two kernels, or (full) the FULL form's with the tags
+// that p names -- p.md_len: MD; p.tags: cs / de.
+inline void launch_bam_emit(const BamEmitParams &p, bool full, hipStream_t s)
+{
+    const dim3 reads((unsigned)p.n_reads), wave(64);             // one wavefront per read; the placements: one workgroup
+    if (!full) {
+        hipLaunchKernelGGL(place_bam_records_kernel, dim3(1), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(emit_bam_records_kernel, reads, wave, 0, s, p);
+        return;
+    }
+    hipLaunchKernelGGL(nm_count_kernel, reads, wave, 0, s, p);
+    if (p.md_len) hipLaunchKernelGGL(md_size_kernel, reads, wave, 0, s, p);
+    if (p.tags) hipLaunchKernelGGL(cs_size_kernel, reads, wave, 0, s, p);
+    hipLaunchKernelGGL(place_bam_full_kernel, dim3(1), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(emit_bam_full_kernel, reads, wave, 0, s, p);
+    if (p.md_len) hipLaunchKernelGGL(emit_md_kernel, reads, wave, 0, s, p);
+    if (p.tags) hipLaunchKernelGGL(emit_cs_kernel, reads, wave, 0, s, p);
 }
 
 }  // namespace npore

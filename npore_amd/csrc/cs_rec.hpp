@@ -4,7 +4,7 @@
 //
 // Both are written over the read's FINAL CIGAR words (`len << 4 | op`, the clip words excluded as for NM and MD) on the two code
 // arrays align() got ('NACGT-' -> 0 ... 5, anything else 0), with nm_rec.hpp's nm_consumes / nm_compares / nm_differs, so NM,
-// MD, cs and de cannot disagree:
+// MD, cs and de cannot disagree (the sequential twins also share their walk over the words, nm_rec.hpp cigar_words_each):
 //   u = 0                                    compared positions that did not differ since the stretch began
 //   for every word (op, len), len > 0 (a word of length 0 does nothing):
 //     M = X : for each position: if nm_differs(...)  end the stretch, emit '*', lower[ref code], lower[read code];   X += 1
@@ -53,14 +53,13 @@ NPORE_NM_HD float de_of_counts(uint32_t e, uint32_t x, uint32_t g)
     return den > 0.0 ? (float)(((double)x + (double)g) / den) : 0.0f;
 }
 NPORE_NM_HD uint8_t cs_lower(uint32_t code) { return (uint8_t)"nacgtn"[code < 6u ? code : 0u]; }
-NPORE_NM_HD uint32_t cs_code(const uint8_t *arr, int64_t len, int64_t at) { return at < len ? arr[at] : 0u; }
 
 // cs of n CIGAR words at w (little-endian, unaligned), sequentially, into the sink: the text's length (no NUL); the counts to c
 template <class Sink>
 inline int64_t cs_walk_words(const uint8_t *w, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, bool lng,
                              const Sink &sink, CsCounts *c = nullptr)
 {
-    int64_t at = 0, a = 0, b = 0;
+    int64_t at = 0;
     uint32_t u = 0;
     CsCounts cnt;
     auto end_stretch = [&]() {
@@ -72,23 +71,21 @@ inline int64_t cs_walk_words(const uint8_t *w, int64_t n, const uint8_t *ref, in
         }
         u = 0;
     };
-    for (int64_t i = 0; i < n; i++) {
-        const uint32_t v = (uint32_t)w[4 * i] | (uint32_t)w[4 * i + 1] << 8 | (uint32_t)w[4 * i + 2] << 16 | (uint32_t)w[4 * i + 3] << 24;
-        const uint32_t op = v & 15u, len = v >> 4, use = nm_consumes(op);
-        if (len == 0) continue;
+    cigar_words_each(w, n, [&](uint32_t op, uint32_t len, int64_t a, int64_t b) {
+        if (len == 0) return;
         if (nm_compares(op)) {
             for (uint32_t q = 0; q < len; q++) {
                 if (nm_differs(ref, rl, a + q, seq, sl, b + q)) {
                     end_stretch();
                     sink.put(at++, (uint8_t)'*');
-                    sink.put(at++, cs_lower(cs_code(ref, rl, a + q)));
-                    sink.put(at++, cs_lower(cs_code(seq, sl, b + q)));
+                    sink.put(at++, cs_lower(code_at(ref, rl, a + q)));
+                    sink.put(at++, cs_lower(code_at(seq, sl, b + q)));
                     cnt.x++;
                     continue;
                 }
                 if (lng) {
                     if (u == 0) sink.put(at++, (uint8_t)'=');
-                    sink.put(at++, md_letter(cs_code(ref, rl, a + q)));
+                    sink.put(at++, md_letter(code_at(ref, rl, a + q)));
                 }
                 u++;
                 cnt.e++;
@@ -96,14 +93,12 @@ inline int64_t cs_walk_words(const uint8_t *w, int64_t n, const uint8_t *ref, in
         } else if (op == 1 || op == 2) {
             end_stretch();
             sink.put(at++, (uint8_t)(op == 1 ? '+' : '-'));
-            for (uint32_t q = 0; q < len; q++) sink.put(at++, op == 1 ? cs_lower(cs_code(seq, sl, b + q)) : cs_lower(cs_code(ref, rl, a + q)));
+            for (uint32_t q = 0; q < len; q++) sink.put(at++, op == 1 ? cs_lower(code_at(seq, sl, b + q)) : cs_lower(code_at(ref, rl, a + q)));
             cnt.g++;
         } else if (op == 3) {
             end_stretch();
         }
-        if (use & 1u) a += len;
-        if (use & 2u) b += len;
-    }
+    });
     end_stretch();
     if (c) *c = cnt;
     return at;

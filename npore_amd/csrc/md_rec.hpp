@@ -3,7 +3,8 @@
 // md_of_text, plain g++), the way nm_rec.hpp, purity_rec.hpp and confusion_rec.hpp are.
 //
 // MD is written over the read's FINAL CIGAR words (`len << 4 | op`) on the two code arrays align() got ('NACGT-' -> 0 ... 5,
-// anything else 0), with nm_rec.hpp's nm_consumes / nm_compares / nm_differs, so NM and MD cannot disagree:
+// anything else 0), with nm_rec.hpp's nm_consumes / nm_compares / nm_differs, so NM and MD cannot disagree (the sequential
+// twins also share their walk over the words, nm_rec.hpp cigar_words_each):
 //   u = 0                                    compared positions that matched since the last item
 //   for every word (op, len), len > 0:
 //     M = X : for each position: if nm_differs(...)  emit decimal(u), LETTER[ref code], u = 0
@@ -36,7 +37,6 @@ struct MdStore {
 };
 
 NPORE_NM_HD uint8_t md_letter(uint32_t code) { return (uint8_t)"NACGTN"[code < 6u ? code : 0u]; }
-NPORE_NM_HD uint32_t md_ref_code(const uint8_t *ref, int64_t rl, int64_t a) { return a < rl ? ref[a] : 0u; }
 // decimal digits of u (1 ... 10)
 NPORE_NM_HD int md_digits(uint32_t u)
 {
@@ -57,7 +57,7 @@ NPORE_NM_HD void md_put_decimal(const Sink &sink, int64_t at, uint32_t u, int nd
 template <class Sink>
 inline int64_t md_walk_words(const uint8_t *w, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, const Sink &sink)
 {
-    int64_t at = 0, a = 0, b = 0;
+    int64_t at = 0;
     uint32_t u = 0;
     auto count = [&]() {
         const int nd = md_digits(u);
@@ -65,23 +65,19 @@ inline int64_t md_walk_words(const uint8_t *w, int64_t n, const uint8_t *ref, in
         at += nd;
         u = 0;
     };
-    for (int64_t c = 0; c < n; c++) {
-        const uint32_t v = (uint32_t)w[4 * c] | (uint32_t)w[4 * c + 1] << 8 | (uint32_t)w[4 * c + 2] << 16 | (uint32_t)w[4 * c + 3] << 24;
-        const uint32_t op = v & 15u, len = v >> 4, use = nm_consumes(op);
+    cigar_words_each(w, n, [&](uint32_t op, uint32_t len, int64_t a, int64_t b) {
         if (nm_compares(op)) {
             for (uint32_t q = 0; q < len; q++) {
                 if (!nm_differs(ref, rl, a + q, seq, sl, b + q)) { u++; continue; }
                 count();
-                sink.put(at++, md_letter(md_ref_code(ref, rl, a + q)));
+                sink.put(at++, md_letter(code_at(ref, rl, a + q)));
             }
         } else if (op == 2 && len > 0) {
             count();
             sink.put(at++, (uint8_t)'^');
-            for (uint32_t q = 0; q < len; q++) sink.put(at++, md_letter(md_ref_code(ref, rl, a + q)));
+            for (uint32_t q = 0; q < len; q++) sink.put(at++, md_letter(code_at(ref, rl, a + q)));
         }
-        if (use & 1u) a += len;
-        if (use & 2u) b += len;
-    }
+    });
     count();
     return at;
 }

@@ -1647,13 +1647,7 @@ try {
     bp.refs = up.refs; bp.seqs = up.seqs; bp.nm = d_nm.as<int32_t>();
     if (md) bp.md_len = d_md.as<int32_t>();
     if (tags) { bp.tags = tags; bp.cs_len = d_cs.as<int32_t>(); bp.de = d_de.as<float>(); }
-    hipLaunchKernelGGL(nm_count_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
-    if (md) hipLaunchKernelGGL(md_size_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
-    if (tags) hipLaunchKernelGGL(cs_size_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
-    hipLaunchKernelGGL(place_bam_full_kernel, dim3(1), dim3(256), 0, st, bp);
-    hipLaunchKernelGGL(emit_bam_full_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
-    if (md) hipLaunchKernelGGL(emit_md_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
-    if (tags) hipLaunchKernelGGL(emit_cs_kernel, dim3((unsigned)n), dim3(64), 0, st, bp);
+    launch_bam_emit(bp, true, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
     unsigned long long total = 0;

@@ -1,6 +1,7 @@
 """Inputs shared by tests/test_bam_cs.py and tests/test_gpu_bam_cs.py (--records full --cs / --de, NPORE_TAG_*): the table of the
 rule's examples on raw code arrays (codes 0 and 5 on either side included), the crafted reads at which the device walk can go
-wrong -- besides those of bam_md_cases, which both tests run as well --, a cs reader for the identities, and the splice that
+wrong -- besides those of bam_md_cases, which both tests run as well --, the reads at the seams of the device walks' frame
+(seam_reads), a cs reader for the identities, and the splice that
 turns today's record into the record with the new tags.  Every expectation is written down from the rule
 (csrc/cs_rec.hpp), not from a run."""
 import re
@@ -233,6 +234,54 @@ def crafted_reads(seed=17):
     both = sorted(zip(records, finals), key=lambda rf: rf[0]["pos"])
     out = ([("ctg", len(contig))], {"ctg": contig}, [r for r, _ in both], [f for _, f in both], pinned)
     _CRAFTED[seed] = out
+    return out
+
+
+_SEAMS = {}
+
+
+def seam_reads(seed=23):
+    """(references, refs, records, finals): reads at the seams of the device walks' frame (csrc/bam_emit_kernels.hpp: tiles
+    of 64 words, rounds of 64 positions), where the carry between the rounds of one word meets the carry between two tiles
+    of words.  The last word of a tile -- word 64, in the last
+    read word 128 -- is an M of 1, 64, 65 or 129 positions that continues a stretch begun in the = word before it; positions
+    differ at the in-round offsets 0 and 63 and at the first position of the next round (64, 128), at the word's first and last
+    position alone, or nowhere, so that the open stretch leaves the tile; the next tile begins with an M-type word, an I and
+    a D in turn.  Computed once, shared, never changed."""
+    if seed in _SEAMS:
+        return _SEAMS[seed]
+    rng = np.random.default_rng(seed)
+    contig = lc.random_contig(rng, 12000)
+    records, finals = [], []
+
+    def add(name, pos, front, seam, diffs, nxt):
+        runs = front + [(M, seam), nxt, (M, 4), (D, 1), (EQ, 70)]
+        q0 = sum(ln for op, ln in front if op in (M, EQ, X, I))     # the seam word's first query base
+        seq, at = [], pos
+        for op, ln in runs:
+            if op in (M, EQ, X):
+                seq += list(contig[at:at + ln])
+            elif op == I:
+                seq += list(lc.random_contig(rng, ln))
+            if op in (M, EQ, X, D):
+                at += ln
+        for d in diffs:
+            seq[q0 + d] = mc.other(seq[q0 + d])
+        records.append(dict(name=name, flag=0, ref_id=0, pos=pos, mapq=40, seq="".join(seq), cigar=[(M if op in (EQ, X) else op, ln) for op, ln in runs],
+                            qual=bytes(rng.integers(0, 50, len(seq)).tolist()), tags=b"", _status=0, _ctg="ctg"))
+        finals.append("".join(f"{ln}{OPS[op]}" for op, ln in runs))
+        return at
+
+    pos = 50
+    front = [(M, 2), (I, 1)] * 31 + [(EQ, 3)]                      # words 1 ... 63
+    for i, seam in enumerate((1, 64, 65, 129)):
+        patterns = ([d for d in (0, 63, 64, 127, 128) if d < seam], [], sorted({0, seam - 1}))
+        for j, nxt in enumerate(((X, 5), (I, 3), (D, 3))):          # every pattern meets every kind of next word
+            pos = add(f"seam{seam}{OPS[nxt[0]]}", pos, front, seam, patterns[(i + j) % 3], nxt) + 30
+    add("seam128", pos, [(M, 2), (D, 1)] * 63 + [(EQ, 1)], 65, [0, 63, 64], (I, 2))
+    assert all(len(words_of(f)) in (68, 132) and words_of(f)[len(words_of(f)) - 5] & 15 == M for f in finals)      # the seam word ends a tile
+    out = ([("ctg", len(contig))], {"ctg": contig}, records, finals)
+    _SEAMS[seed] = out
     return out
 
 

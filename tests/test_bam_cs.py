@@ -95,6 +95,28 @@ def test_host_twin_equals_statement(crafted):
             assert s["got"][(md, cs, de)] == cc.want_stream(raws, s["records"], s["refs"], s["finals"], s["status"], md=md, cs=cs, de=de), (key, md, cs, de)
 
 
+def test_seam_reads_host_twin_equals_statement(tmp_path):
+    """the reads at the seams of the device walk's frame (cc.seam_reads): the host twin, which the device is held to, against
+    bam.full_record in every combination"""
+    references, refs, records, finals = cc.seam_reads()
+    bp, fa = fc.write_inputs(tmp_path, references, refs, records, "seam")
+    nb, nf, idx = open_pair(bp, fa)
+    assert len(idx) == len(records) == 13
+    raws, status = fc.input_records(bp), np.zeros(len(records), np.int32)
+    for md, cs, de in COMBOS:
+        assert nb.format_bam_full(nf, idx, finals, status, md=md, cs=cs, de=de) == cc.want_stream(raws, records, refs, finals, status, md=md, cs=cs, de=de), (md, cs, de)
+    # what the seams are for, pinned by hand on the read where nothing differs: (2M1I) x 31, then ONE stretch from the = word
+    # through the M at the tile's end into the next tile's X and M, the deleted base, the closing = word
+    k = [r["name"] for r in records].index("seam64X")
+    assert finals[k] == "2M1I" * 31 + "3=64M5X4M1D70="
+    last_ins = 3 * 30 + 2                                        # the read's 31st inserted base
+    stretch = 3 + 64 + 5 + 4
+    deleted = records[k]["pos"] + 2 * 31 + stretch               # the reference base under D
+    text = cc.new_tags_of(split_records(nb.format_bam_full(nf, idx, finals, status, cs="short"))[k][1])[0]
+    assert text.endswith(f"+{records[k]['seq'][last_ins].lower()}:{stretch}-{refs['ctg'][deleted].lower()}:70"), text
+    nb.close(); nf.close()
+
+
 # ---- 3. the texts pinned by hand, the order of the tags, the alignments -----------------------------------------------------------
 def test_crafted_reads(crafted):
     tmp, sets = crafted

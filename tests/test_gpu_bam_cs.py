@@ -54,12 +54,14 @@ def device_full_tags(ctx, nb, nf, idx, finals, status, want_len, md, cs, de):
 
 
 # ---- 1. the crafted and the random reads through the debug entry, every combination --------------------------------------------
-@pytest.mark.parametrize("which", ["cs", "md", "random"])
+@pytest.mark.parametrize("which", ["cs", "md", "random", "seam"])
 def test_device_equals_host(ctx, tmp_path, which):
     if which == "random":
         references, refs, records, finals, _ = mc.random_reads()
         for r in records:
             r.setdefault("_status", 0)
+    elif which == "seam":                                            # the seams of the walks' frame: a tile's last word, a round's last position
+        references, refs, records, finals = cc.seam_reads()
     else:
         references, refs, records, finals, _ = (cc if which == "cs" else mc).crafted_reads()
     bp, fa = fc.write_inputs(tmp_path, references, refs, records, which)

@@ -47,6 +47,7 @@ extern "C" {
 #define NPORE_ST_OUT_OF_CHUNK 16 /* traceback left the chunk (UB in the reference) */
 #define NPORE_ST_BAD_INPUT 32   /* CIGAR/sequence lengths disagree, bad op or base code */
 #define NPORE_ST_OUT_CAP 64     /* caller's output slot too small */
+#define NPORE_ST_PASSED 128     /* not realigned, written as it came (npore_bam_set_output_pass); no error */
 
 typedef struct npore_ctx npore_ctx;
 
@@ -289,6 +290,14 @@ int npore_bam_ref_has_reads(const npore_bam *bam, int i);
 int64_t npore_bam_select(const npore_bam *bam, int n_regions, const int32_t *ref_id, const int64_t *start,
                          const int64_t *stop, int64_t max_reads, int64_t *out_idx, int64_t cap);
 
+/* npore_bam_select that also keeps the records a run passes through (npore_bam_set_output_pass): a record whose flag has a
+ * bit of flag_mask -- a subset of 0x904, anything else: NPORE_E_INVALID -- is selected under the same region, order and
+ * max_reads rules as a read and counts towards max_reads; one without a reference length (a placed, unmapped record has no
+ * CIGAR) overlaps a region as if its length were 1, as htslib has it -- that holds for such records only.  Unplaced records
+ * (refID < 0) stay out.  flag_mask 0 returns exactly what npore_bam_select returns. */
+int64_t npore_bam_select_pass(const npore_bam *bam, int n_regions, const int32_t *ref_id, const int64_t *start,
+                              const int64_t *stop, int64_t max_reads, int flag_mask, int64_t *out_idx, int64_t cap);
+
 /* {contig: upper-cased sequence} of a FASTA file (reference: pysam.FastaFile / Bio.SeqIO callers). */
 npore_fasta *npore_fasta_open(const char *path);
 void npore_fasta_close(npore_fasta *fa);
@@ -300,7 +309,8 @@ const char *npore_fasta_seq(const npore_fasta *fa, int i);
 
 /* Inputs of npore_align_batch for the selected records (src/bam.pyx:59-61): expanded CIGAR without S/H,
  * query bases without the soft clips and the reference slice [pos, pos + reference_length) as codes.
- * fasta_of_ref[bam reference id] = index of that contig in `fa` (or -1).  Sizes first, then the fill. */
+ * fasta_of_ref[bam reference id] = index of that contig in `fa` (or -1).  Sizes first, then the fill.
+ * A record that passes under the handle's npore_bam_set_output_pass mask gives align() nothing: its three slices are empty. */
 int npore_bam_pack_sizes(const npore_bam *bam, const int64_t *idx, int64_t n, int64_t *ref_off, int64_t *seq_off,
                          int64_t *cig_off);
 int npore_bam_pack(const npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
@@ -409,6 +419,29 @@ int npore_debug_format_bam_full_tags_device(npore_ctx *ctx, npore_bam *bam, cons
                                             int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len,
                                             const int32_t *status, uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm, int flags,
                                             int32_t *md_len, int tags);
+/* PASS-THROUGH (`--pass_through`): which records the NEXT run writes as they came instead of leaving them out.  A record PASSES
+ * iff `flag & flag_mask` is non-zero; flag_mask is a subset of 0x904 -- secondary (0x100), supplementary (0x800), placed but
+ * unmapped (0x4) -- and 0, the default, is the reference's behaviour (src/bam.pyx:31-32 drops all three).  Call it behind an
+ * npore_bam_set_output whose format is NPORE_OUT_BAM and whose flags hold NPORE_OUT_FULL -- otherwise, and for any other bit,
+ * NPORE_E_INVALID.  Every npore_bam_set_output sets the mask back to 0; the mask holds for the next run.
+ * A passing record is selected under the same region, order and max_reads rules as a read (npore_bam_select_pass; the readers of
+ * npore_bam_realign_sequential drop `0x904 & ~flag_mask`; npore_bam_realign_file takes the indices the caller selected), is
+ * staged verbatim, gives align() nothing (no chunk, no fill work, no traceback), and its output record is the input record
+ * byte for byte: every tag stays (NM MD cs de dv too: the alignment did not change), a long CIGAR stays placeholder + CG tag.
+ * One wave of emit_bam_full_kernel copies it into its place among the realigned records; a stored or coded member can span
+ * both kinds.  Its status is NPORE_ST_PASSED; the index takes its own reference length (0 counts as 1).
+ * Still left out: unplaced records (refID < 0), and reads align() refuses (NPORE_ST_BAD_INPUT, reported as before) -- writing
+ * those as they came would need their unfiltered tags, which the staged form of a read does not keep. */
+int npore_bam_set_output_pass(npore_bam *bam, int flag_mask);
+/* npore_bam_format_bam_full_tags and npore_debug_format_bam_full_tags_device with `pass_mask` (a subset of 0x904; 0: their bytes):
+ * a record that passes is the input's bytes; the device entry point returns nm = md_len = 0 for it. */
+int npore_bam_format_bam_full_pass(npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
+                                   const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
+                                   const uint8_t **recs, int64_t *recs_len, int flags, int tags, int pass_mask);
+int npore_debug_format_bam_full_pass_device(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
+                                            int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len,
+                                            const int32_t *status, uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm, int flags,
+                                            int32_t *md_len, int tags, int pass_mask);
 /* Of the last BAM-mode run on the handle: out4[0] records written, [1] bytes of the record stream, [2] 1 = the index was
  * written, 0 = none was asked for, -1 = the records were not in coordinate order (no index), [3] size of the file. */
 int npore_bam_output_info(const npore_bam *bam, int64_t *out4);
@@ -434,8 +467,8 @@ int npore_bam_realign_file(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa
  * contig, in the order of the BAM header: the tool's default whole-contig regions; same overlap / flag / max_reads
  * rules as npore_bam_select), batched, and sent through the same overlapped stages as npore_bam_realign_file -- no
  * record index, no second inflation, memory bounded by the batches in flight.  `bam`: a handle opened in mode 3
- * (header only) or 2.  counts[3]: reads selected, reads refused (NPORE_ST_BAD_INPUT, not written), reads with an
- * inconsistent traceback; bad_ord / bad_status[bad_cap]: ordinal (among the selected reads) and status bits of the
+ * (header only) or 2.  counts[3]: reads selected (records that pass through included: npore_bam_set_output_pass), reads
+ * refused (NPORE_ST_BAD_INPUT, not written), reads with an inconsistent traceback (NPORE_ST_PASSED is neither); bad_ord / bad_status[bad_cap]: ordinal (among the selected reads) and status bits of the
  * first such reads.  NPORE_E_UNSUPPORTED: the regions or the file's order rule the one-pass run out (the BAM is not
  * sorted by reference, several regions per contig) -- nothing usable was written: truncate and use the indexed path. */
 /* Several processes (one per GPU) on ONE file, each in one pass (the reference feeds all its workers from one sequential

@@ -64,6 +64,7 @@ SIGNATURES = {
     "npore_bam_ref_len": (C.c_int64, [C.c_void_p, C.c_int]),
     "npore_bam_ref_has_reads": (C.c_int, [C.c_void_p, C.c_int]),
     "npore_bam_select": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "npore_bam_select_pass": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64]),
     "npore_fasta_open": (C.c_void_p, [C.c_char_p]),
     "npore_fasta_close": (None, [C.c_void_p]),
     "npore_fasta_n": (C.c_int, [C.c_void_p]),
@@ -92,6 +93,12 @@ SIGNATURES = {
                                                           C.c_int, C.c_void_p, C.c_int]),
     "npore_bam_set_output": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int]),
     "npore_bam_set_output_tags": (C.c_int, [C.c_void_p, C.c_int]),
+    "npore_bam_set_output_pass": (C.c_int, [C.c_void_p, C.c_int]),
+    "npore_bam_format_bam_full_pass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "npore_debug_format_bam_full_pass_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                          C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "npore_bam_output_info": (C.c_int, [C.c_void_p, C.c_void_p]),
     "npore_bam_write_file": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_char_p]),

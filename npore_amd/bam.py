@@ -1017,6 +1017,12 @@ class NativeFastaSeqs:
         return list(self)
 
 
+# --pass_through (npore_bam_set_output_pass): the flag bits whose records a FULL-record run can write as they came -- secondary,
+# supplementary, placed but unmapped -- and the status bit such a record gets
+PASS_FLAGS = 0x100 | 0x800 | 0x4
+ST_PASSED = 128
+
+
 class OnePassUnsupported(RuntimeError):
     """NativeBam.realign_sequential cannot serve these regions / this file in one pass (take the indexed path)."""
 
@@ -1203,8 +1209,9 @@ class NativeBam:
     def refs_with_reads(self):
         return {i for i in range(len(self.references)) if self._lib.npore_bam_ref_has_reads(self.handle, i)}
 
-    def select(self, regions, max_reads=0):
-        """Record indices of the reads get_read_data would yield for [(contig, start, stop)]."""
+    def select(self, regions, max_reads=0, pass_mask=0):
+        """Record indices of the reads get_read_data would yield for [(contig, start, stop)]; pass_mask (a subset of
+        PASS_FLAGS): with the records of those flag bits, which a --pass_through run writes as they came (npore_bam_select_pass)."""
         ids = {n: i for i, n in enumerate(self.references)}
         rid = np.array([ids.get(c, -2) for c, _, _ in regions], np.int32)
         beg = np.array([s for _, s, _ in regions], np.int64)
@@ -1212,12 +1219,24 @@ class NativeBam:
         # two calls: the count first (cap = 0 writes nothing), then exactly that many entries -- a read overlapping
         # several regions is listed once per region, so n_records * n_regions is the only a-priori bound
         args = (self.handle, len(regions), rid.ctypes.data, beg.ctypes.data, end.ctypes.data, int(max_reads or 0))
+        if pass_mask:
+            return self._select_pass(args, int(pass_mask))
         k = self._lib.npore_bam_select(*args, None, 0)
         if k < 0:
             from . import _lib
             raise RuntimeError(_lib.last_error())
         out = np.zeros(max(int(k), 1), np.int64)
         k2 = self._lib.npore_bam_select(*args, out.ctypes.data, len(out))
+        assert k2 == k
+        return out[:k]
+
+    def _select_pass(self, args, pass_mask):
+        k = self._lib.npore_bam_select_pass(*args, pass_mask, None, 0)
+        if k < 0:
+            from . import _lib
+            raise RuntimeError(_lib.last_error())
+        out = np.zeros(max(int(k), 1), np.int64)
+        k2 = self._lib.npore_bam_select_pass(*args, pass_mask, out.ctypes.data, len(out))
         assert k2 == k
         return out[:k]
 
@@ -1273,10 +1292,11 @@ class NativeBam:
                                                    fl.ctypes.data, st.ctypes.data, threads, C.byref(recs), C.byref(recs_len)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False, cs=None, de=False):
+    def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False, cs=None, de=False, pass_mask=0):
         """FULL records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam_full;
         md: with the MD tag behind NM, npore_bam_format_bam_full_md with NPORE_OUT_MD; cs "short" / "long", de: with those
-        tags behind MD, npore_bam_format_bam_full_tags with NPORE_TAG_*)."""
+        tags behind MD, npore_bam_format_bam_full_tags with NPORE_TAG_*; pass_mask: the records with one of those flag bits as
+        they came, npore_bam_format_bam_full_pass)."""
         import ctypes as C
         idx = np.ascontiguousarray(idx, np.int64)
         n = len(idx)
@@ -1291,11 +1311,13 @@ class NativeBam:
         args = (self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
                 st.ctypes.data, threads, C.byref(recs), C.byref(recs_len))
         tags = output_tags(cs, de)
-        self._check(self._lib.npore_bam_format_bam_full_tags(*args, 32 if md else 0, tags) if tags else
+        self._check(self._lib.npore_bam_format_bam_full_pass(*args, 32 if md else 0, tags, int(pass_mask)) if pass_mask else
+                    self._lib.npore_bam_format_bam_full_tags(*args, 32 if md else 0, tags) if tags else
                     self._lib.npore_bam_format_bam_full_md(*args, 32) if md else self._lib.npore_bam_format_bam_full(*args))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False, cs=None, de=False):
+    def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False, cs=None, de=False,
+                   pass_mask=0):
         """What the NEXT realign_file / realign_sequential / write_file on this handle appends to its output path
         (npore_bam_set_output; the setting holds for that one run): "sam", or "bam" -- records in stored BGZF members behind
         what lies in the file (the header's members: create_bam_header) and `bai` written when the records went out in
@@ -1306,7 +1328,11 @@ class NativeBam:
         (NPORE_OUT_DEFLATE; "bam" only).  records: "reference", the reference's SAM line in binary, or "full", the input
         record with only what the realignment changes replaced (NPORE_OUT_FULL; "bam" only).  md: the MD tag behind the
         recounted NM of every FULL record (NPORE_OUT_MD; records "full" only).  cs: "short" or "long", minimap2's cs tag behind
-        that, de: its de tag behind that (npore_bam_set_output_tags, NPORE_TAG_*; records "full" only)."""
+        that, de: its de tag behind that (npore_bam_set_output_tags, NPORE_TAG_*; records "full" only).  pass_mask: a subset of
+        PASS_FLAGS -- the records with one of those flag bits are written as they came (npore_bam_set_output_pass; records
+        "full" only)."""
+        if pass_mask and records != "full":
+            raise ValueError("pass_mask needs records 'full'")
         if compress not in ("none", "huffman", "match"):
             raise ValueError("compress must be 'none', 'huffman' or 'match'")
         if records not in ("reference", "full"):
@@ -1327,6 +1353,8 @@ class NativeBam:
         self._check(self._lib.npore_bam_set_output(self.handle, {"sam": 0, "bam": 1}[out_format], os.fsencode(bai) if bai else None, flags))
         if tags:
             self._check(self._lib.npore_bam_set_output_tags(self.handle, tags))
+        if pass_mask:
+            self._check(self._lib.npore_bam_set_output_pass(self.handle, int(pass_mask)))
 
     def output_info(self):
         """Of the last BAM-mode run: records written, bytes of the record stream, index (1 written, 0 none asked for, -1 the
@@ -1391,12 +1419,14 @@ class NativeBam:
 
     def realign_sequential(self, ctx, fasta, regions, out_path, batch_reads=4000, max_reads=0, r=30, max_b_rows=20000,
                            indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, out_format="sam", bai=None, eof=True,
-                           compress="none", records="reference", md=False, cs=None, de=False):
+                           compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0):
         """ONE PASS over the file: inflate, filter by `regions` [(contig, start, stop)] (at most one per contig, in header
         order), batch, realign, write -- npore_bam_realign_sequential.  Returns (reads selected, [(ordinal, status)] of
-        the first bad reads, (refused, inconsistent)); raises OnePassUnsupported when the regions or the file's
+        the first bad reads, (refused, inconsistent)) -- the reads selected include the records that pass through (pass_mask),
+        which are not bad reads; raises OnePassUnsupported when the regions or the file's
         order rule the one-pass run out (the caller truncates the output and takes the indexed path).
-        out_format / bai / eof / compress / records / md / cs / de: set_output for this run ("bam": records instead of text)."""
+        out_format / bai / eof / compress / records / md / cs / de / pass_mask: set_output for this run ("bam": records instead
+        of text)."""
         ids = {n: i for i, n in enumerate(self.references)}
         rid = np.array([ids.get(c, -2) for c, _, _ in regions], np.int32)
         beg = np.array([s for _, s, _ in regions], np.int64)
@@ -1406,7 +1436,7 @@ class NativeBam:
         counts = np.zeros(3, np.int64)
         bad_ord, bad_st = np.zeros(max(bad_cap, 1), np.int64), np.zeros(max(bad_cap, 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records, md, cs, de)
+        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask)
         rc = self._lib.npore_bam_realign_sequential(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, len(regions), rid.ctypes.data,
                                                     beg.ctypes.data, end.ctypes.data, int(max_reads or 0), int(batch_reads), indel_start,
                                                     indel_extend, max_b_rows, r, threads, os.fsencode(out_path), counts.ctypes.data,
@@ -1439,14 +1469,15 @@ class NativeBam:
 
     def realign_file(self, ctx, fasta, idx, out_sam, batch_reads=4000, r=30, max_b_rows=20000, indel_start=5.0,
                      indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False,
-                     cs=None, de=False):
+                     cs=None, de=False, pass_mask=0):
         """All selected reads, batch by batch, appended to out_sam by the library with packing, GPU work and
-        formatting/writing of neighbouring batches overlapped.  Returns status[n].
-        out_format / bai / eof / compress / records / md / cs / de: set_output for this run ("bam": records instead of text)."""
+        formatting/writing of neighbouring batches overlapped.  Returns status[n] (ST_PASSED: written as it came).
+        out_format / bai / eof / compress / records / md / cs / de / pass_mask: set_output for this run ("bam": records instead of
+        text); with pass_mask, idx comes from select(..., pass_mask=pass_mask)."""
         idx = np.ascontiguousarray(idx, np.int64)
         st = np.zeros(max(len(idx), 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records, md, cs, de)
+        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask)
         self._check(self._lib.npore_bam_realign_file(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data,
                                                      len(idx), int(batch_reads), indel_start, indel_extend, max_b_rows, r,
                                                      threads, os.fsencode(out_sam), st.ctypes.data))
@@ -1493,7 +1524,7 @@ class NativeBam:
 
 
 def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0, out_format="sam", bai=None,
-                   eof=True, compress="none", records="reference", md=False, cs=None, de=False):
+                   eof=True, compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0):
     """realign_reads() through the library; returns the number of reads handed in.  batch_reads > 0: the whole
     index list in overlapped batches written by the library itself; 0: one batch, text written here.
     threads: host threads of the parallel host stages (0 = all cores; one process per GPU: dist.host_threads_per_rank).
@@ -1505,10 +1536,10 @@ def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_
     if batch_reads > 0:
         text, status = None, bam.realign_file(ctx, fasta, idx, out_sam, batch_reads=batch_reads, r=r, max_b_rows=max_b_rows,
                                               threads=threads, out_format=out_format, bai=bai, eof=eof, compress=compress,
-                                              records=records, md=md, cs=cs, de=de)
+                                              records=records, md=md, cs=cs, de=de, pass_mask=pass_mask)
     else:
         text, status = bam.realign_batch(ctx, fasta, idx, r=r, max_b_rows=max_b_rows, threads=threads)
-    bad = np.nonzero(status)[0]
+    bad = np.nonzero(np.asarray(status) & ~ST_PASSED)[0]       # (a record that passed through is no bad read)
     for k in bad:
         if status[k] & 32:
             print(f"\nERROR: read #{int(idx[k])}: CIGAR does not match sequence lengths; skipped.")

@@ -45,6 +45,7 @@ struct BamEmit {
     bool full = false;           // NPORE_OUT_FULL: FULL records (the heads staged with STAGE_FULL), NM counted on the device
     bool md = false;             // ... NPORE_OUT_MD beside it: the MD tag behind NM, sized and written on the device (md_rec.hpp)
     int tags = 0;                // ... NPORE_TAG_*: cs / de behind that, sized and written on the device (cs_rec.hpp)
+    uint32_t pass_mask = 0;      // ... npore_bam_set_output_pass: records with these flag bits pass through (staged_head.hpp)
 };
 
 struct npore_batch_slot;        // a batch of the BAM -> SAM pipeline (file_pipeline.hpp)
@@ -474,6 +475,7 @@ int upload_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs
         up.seqs = w->in_seqs.as<uint8_t>(); up.seq_off = d_off + (nr + 1);
         up.cigs = w->in_cigs.as<char>(); up.cig_off = d_off + 2 * (nr + 1);
         up.n_reads = nr;
+        up.pass_mask = a.bam && a.bam->full ? a.bam->pass_mask : 0;
         hipLaunchKernelGGL(unpack_records_kernel, dim3((unsigned)nr), dim3(256), 0, s, up);
         HIP_TRY(hipGetLastError());
     }
@@ -612,6 +614,7 @@ int post_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs &
         bp.rec_off = w->rec_off.as<int64_t>(); bp.rec_len = w->rec_len.as<int64_t>();
         if (a.bam->full) {                    // FULL records: NM from the code arrays the standardisation probed, then the same two steps
             bp.refs = sp.refs; bp.seqs = sp.seqs; bp.nm = w->nm.as<int32_t>();
+            bp.pass_mask = a.bam->pass_mask;
             if (a.bam->md) bp.md_len = w->md_len.as<int32_t>();      // (MD: its size in front of the placement, its text behind the record)
             if (a.bam->tags) { bp.tags = a.bam->tags; bp.cs_len = w->cs_len.as<int32_t>(); bp.de = w->de_val.as<float>(); }      // (cs / de: the same)
         }

@@ -57,6 +57,9 @@ struct BamEmitParams {
     int tags = 0;
     int32_t *cs_len = nullptr;     // [n_reads], with any tag (0 without NPORE_TAG_CS)
     float *de = nullptr;           // [n_reads], with any tag
+    // FULL records, npore_bam_set_output_pass: reads whose staged flag has one of these bits pass (staged_head.hpp) -- their staged
+    // head is the whole input record and so is their output record; nm, md_len, cs_len and de are 0 for them
+    uint32_t pass_mask = 0;
 };
 
 __device__ __forceinline__ void st32(uint8_t *q, uint32_t w)      // little-endian, unaligned
@@ -246,6 +249,10 @@ __global__ __launch_bounds__(64) void nm_count_kernel(BamEmitParams p)
     if (k >= p.n_reads) return;
     const int lane = threadIdx.x;
     const int64_t g = p.read_base + k;
+    if (staged_passes(p.raw + p.raw_off[k] + 4, p.pass_mask)) {
+        if (lane == 0) p.nm[k] = 0;
+        return;
+    }
     const int64_t n = (p.status[g] & 32) || p.words_len[g] <= 0 ? 0 : p.words_len[g] >> 2;
     const uint32_t *w = reinterpret_cast<const uint32_t *>(p.words + p.words_off[g]);      // (the slots lie at multiples of 4)
     const uint8_t *ref = p.refs + p.ref_off[k], *seq = p.seqs + p.seq_off[k];
@@ -286,7 +293,7 @@ __global__ __launch_bounds__(64) void nm_count_kernel(BamEmitParams p)
 struct BamFullShape {
     const uint8_t *f, *cg, *sq;
     int nc, ci, cj, nmb;
-    bool lng;
+    bool lng, pass;                // pass: the record is the staged head's bytes (staged_head.hpp); only f and size are set
     int64_t wl, n_cig, l_seq, aux, size;
     int64_t mdb;                   // bytes of the MD tag behind NM (4 + its text; 0: none)
     int64_t csb, deb;              // bytes of the cs tag behind that (4 + its text; 0: none) and of the de tag (7; 0: none)
@@ -296,6 +303,11 @@ __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, i
     BamFullShape s;
     const int64_t g = p.read_base + k;
     s.f = p.raw + p.raw_off[k] + 4;
+    s.pass = staged_passes(s.f, p.pass_mask);
+    if (s.pass) {
+        s.size = (p.status[g] & 32) ? 0 : staged_pass_bytes(s.f);
+        return s;
+    }
     staged_cigar(s.f, s.cg, s.nc, s.sq);
     auto op_of = [&](int c) { return ld32(s.cg + 4 * (size_t)c) & 15u; };
     s.ci = 0;
@@ -332,6 +344,10 @@ __global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
     const int64_t g = p.read_base + k;
     const BamFullShape s = bam_full_shape(p, k);
     const uint8_t *f = s.f;
+    if (s.pass) {                                                // the input record as it was staged, block_size word first
+        wave_copy<0>(p.recs + p.rec_off[k], f - 4, size, false, lane);
+        return;
+    }
     const int32_t pos = (int32_t)ld32(f + 4);
     const int l_rn = f[8];
     const int64_t reflen = p.ref_off[k + 1] - p.ref_off[k], body = (s.l_seq + 1) / 2 + s.l_seq + s.aux;
@@ -455,7 +471,8 @@ __global__ __launch_bounds__(64) void md_size_kernel(BamEmitParams p)
     const int64_t k = blockIdx.x;
     if (k >= p.n_reads) return;
     const int lane = threadIdx.x;
-    const uint32_t len = (p.status[p.read_base + k] & 32) ? 0u : md_walk(p, k, lane, MdCount{});
+    const bool none = (p.status[p.read_base + k] & 32) || staged_passes(p.raw + p.raw_off[k] + 4, p.pass_mask);
+    const uint32_t len = none ? 0u : md_walk(p, k, lane, MdCount{});
     if (lane == 0) p.md_len[k] = (int32_t)len;
 }
 
@@ -467,6 +484,7 @@ __global__ __launch_bounds__(64) void emit_md_kernel(BamEmitParams p)
     const int lane = threadIdx.x;
     if (p.rec_len[k] <= 0) return;
     const BamFullShape s = bam_full_shape(p, k);
+    if (s.pass) return;
     uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb;
     if (lane < 3) o[lane] = (uint8_t)"MDZ"[lane];
     const int64_t cap = p.md_len[k];
@@ -596,7 +614,7 @@ __global__ __launch_bounds__(64) void cs_size_kernel(BamEmitParams p)
     const int lane = threadIdx.x;
     CsCounts c;
     uint32_t len = 0;
-    if (!(p.status[p.read_base + k] & 32)) len = (p.tags & NPORE_TAG_CS_LONG) ? cs_walk<true>(p, k, lane, MdCount{}, c) : cs_walk<false>(p, k, lane, MdCount{}, c);
+    if (!(p.status[p.read_base + k] & 32) && !staged_passes(p.raw + p.raw_off[k] + 4, p.pass_mask)) len = (p.tags & NPORE_TAG_CS_LONG) ? cs_walk<true>(p, k, lane, MdCount{}, c) : cs_walk<false>(p, k, lane, MdCount{}, c);
     if (lane == 0) {
         p.cs_len[k] = (p.tags & NPORE_TAG_CS) ? (int32_t)len : 0;
         p.de[k] = de_of_counts(c.e, c.x, c.g);
@@ -612,6 +630,7 @@ __global__ __launch_bounds__(64) void emit_cs_kernel(BamEmitParams p)
     const int lane = threadIdx.x;
     if (p.rec_len[k] <= 0) return;
     const BamFullShape s = bam_full_shape(p, k);
+    if (s.pass) return;
     uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb;
     if (s.csb) {
         if (lane < 3) o[lane] = (uint8_t)"csZ"[lane];

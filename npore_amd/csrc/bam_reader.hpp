@@ -360,8 +360,11 @@ inline int bam_dump_inflated(const npore_bam *b, const char *path)
 }
 
 inline int64_t bam_select(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
-                          int64_t max_reads, int64_t *out_idx, int64_t cap, uint32_t drop_flags = 0x100 | 0x800 | 0x4)
+                          int64_t max_reads, int64_t *out_idx, int64_t cap, uint32_t drop_flags = PASS_FLAGS, uint32_t pass_mask = 0)
 {
+    // pass_mask (staged_head.hpp): records with one of these flag bits are kept, to pass through; such a record without a
+    // reference length (a placed, unmapped one has no CIGAR) overlaps as if its length were 1, as htslib has it
+    drop_flags &= ~pass_mask;
     if (!b || (n_regions > 0 && (!ref_id || !start || !stop)) || (cap > 0 && !out_idx)) return fail(NPORE_E_INVALID, "null argument");
     int64_t kept = 0;
     for (int g = 0; g < n_regions; g++) {
@@ -376,7 +379,8 @@ inline int64_t bam_select(const npore_bam *b, int n_regions, const int32_t *ref_
         }
         for (size_t q = first; q < recs.size(); q++) {
             const int64_t i = recs[q];
-            const int64_t pos = b->m_pos[(size_t)i], rl = b->m_span[(size_t)i];
+            int64_t pos = b->m_pos[(size_t)i], rl = b->m_span[(size_t)i];
+            if (rl == 0 && record_passes(b->m_flag[(size_t)i], pass_mask)) rl = 1;
             if (b->ref_sorted[(size_t)ref_id[g]] && pos >= stop[g]) break;
             if (!(pos < stop[g] && pos + rl > start[g])) continue;                 // overlaps [start, stop)
             if (max_reads > 0 && kept >= max_reads) return kept;                   // src/bam.pyx:29-30
@@ -449,7 +453,8 @@ inline int fetch_records(const npore_bam *b, const int64_t *idx, int64_t n, int 
     if (!bam_fetch(*b, idx, n, threads, rf, err)) return fail(NPORE_E_INVALID, "BAM records: " + err);
     return NPORE_OK;
 }
-inline void pack_sizes_of(const RecFetch &rf, int64_t n, int64_t *ref_off, int64_t *seq_off, int64_t *cig_off, int threads = 0)
+// pass_mask: a record that passes (staged_head.hpp) gives align() nothing -- its three slices are empty
+inline void pack_sizes_of(const RecFetch &rf, int64_t n, int64_t *ref_off, int64_t *seq_off, int64_t *cig_off, int threads = 0, uint32_t pass_mask = 0)
 {
     // per read (a 10 kb read has thousands of CIGAR operations: all cores), then the prefix sums
     ref_off[0] = seq_off[0] = cig_off[0] = 0;
@@ -457,6 +462,7 @@ inline void pack_sizes_of(const RecFetch &rf, int64_t n, int64_t *ref_off, int64
     parallel_for((n + per - 1) / per, threads, [&](int64_t t) {
         for (int64_t k = t * per; k < std::min(n, (t + 1) * per); k++) {
             const RecView r = rec_of(rf, k);
+            if (staged_passes(r.p, pass_mask)) { ref_off[k + 1] = seq_off[k + 1] = cig_off[k + 1] = 0; continue; }
             const RecCigar cg = rec_cigar(r);
             int64_t lead, trail, ops = 0, rl = 0;
             rec_clips(cg, lead, trail);
@@ -475,7 +481,7 @@ inline void pack_sizes_of(const RecFetch &rf, int64_t n, int64_t *ref_off, int64
 
 inline int pack_records(const npore_bam *b, const RecFetch &rf, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n,
                  uint8_t *refs, const int64_t *ref_off, uint8_t *seqs, const int64_t *seq_off, char *cigs,
-                 const int64_t *cig_off, int threads, bool for_upload = false)
+                 const int64_t *cig_off, int threads, bool for_upload = false, uint32_t pass_mask = 0)
 {
     std::atomic<int> bad{0};
     parallel_for(n, threads, [&](int64_t k) {
@@ -483,6 +489,7 @@ inline int pack_records(const npore_bam *b, const RecFetch &rf, const npore_fast
         const int32_t rid = r.ref_id();
         const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
         if (fi < 0 || fi >= (int)fa->names.size()) { bad++; return; }
+        if (staged_passes(r.p, pass_mask)) return;      // (its slices are empty: pack_sizes_of)
         // reference bases: FASTA slice [pos, pos + reference_length), what pysam rebuilds from MD (src/bam.pyx:45)
         const char *ctg = fa->seq((size_t)fi);
         const int64_t ctg_len = fa->len((size_t)fi);
@@ -939,6 +946,7 @@ struct ReadCodes {
     const uint8_t *seqs; const int64_t *seq_off;
     bool md = false;
     int tags = 0;
+    uint32_t pass_mask = 0;        // records that pass (staged_head.hpp): written as they came, their slices above are empty
 };
 
 // format_sam_into's twin for BAM records: the kept reads' records one after the other in `out`, *out_len bytes;
@@ -953,13 +961,23 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     std::vector<std::string> md(full && full->md ? (size_t)n : 0), more(full && full->tags ? (size_t)n : 0);
     std::atomic<int> bad{0};
     // (full: the FULL RECORD, its NM counted and its MD, cs and de written once, between the two passes)
+    const uint32_t pass_mask = full ? full->pass_mask : 0;
+    // a record that passes: the input's bytes; the index gets the input record's own reference length
+    auto passed = [&](int64_t k, uint8_t *dst, BamRecMeta *m) -> int64_t {
+        const RecView r = rec_of(rf, k);
+        const int64_t size = staged_pass_bytes(r.p);
+        if (dst) std::memcpy(dst, rf.ptr[(size_t)k], (size_t)size);
+        if (dst && m) *m = BamRecMeta{r.ref_id(), r.pos(), rec_ref_len(r), size};
+        return size;
+    };
     auto record = [&](int64_t k, uint8_t *dst, BamRecMeta *m) {
+        if (staged_passes(rec_of(rf, k).p, pass_mask)) return passed(k, dst, m);
         return full ? bam_record_full_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], nm[(size_t)k], dst, m,
                                            full->md ? &md[(size_t)k] : nullptr, full->tags ? &more[(size_t)k] : nullptr)
                     : bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], dst, m);
     };
     parallel_for(n, threads, [&](int64_t k) {
-        if (full && !(status[k] & NPORE_ST_BAD_INPUT)) {
+        if (full && !(status[k] & NPORE_ST_BAD_INPUT) && !staged_passes(rec_of(rf, k).p, pass_mask)) {
             const uint8_t *ref = full->refs + full->ref_off[k], *seq = full->seqs + full->seq_off[k];
             const int64_t rl = full->ref_off[k + 1] - full->ref_off[k], sl = full->seq_off[k + 1] - full->seq_off[k];
             nm[(size_t)k] = nm_of_text(finals + final_off[k], final_len[k], ref, rl, seq, sl);
@@ -1427,9 +1445,9 @@ inline int one_pass_args_check(const npore_bam *b, int n_regions, const int32_t 
 class BamRecordWalker {
 public:
     BamRecordWalker(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
-                    int64_t max_reads, int threads, uint32_t drop_flags = 0x100 | 0x800 | 0x4, BgzfInflateFn inflate = nullptr)
+                    int64_t max_reads, int threads, uint32_t drop_flags = PASS_FLAGS, BgzfInflateFn inflate = nullptr, uint32_t pass_mask = 0)
         : b_(b), src_(b, threads, std::move(inflate)), n_regions_(n_regions), ref_id_(ref_id), start_(start), stop_(stop), max_reads_(max_reads),
-          drop_flags_(drop_flags), done_(n_regions == 0)
+          drop_flags_(drop_flags & ~pass_mask), pass_mask_(pass_mask), done_(n_regions == 0)
     {
         if (!b->has_share) return;
         if (b->share_begin == UINT64_MAX) done_ = true;          // nothing left for this rank
@@ -1476,7 +1494,8 @@ public:
             while (g_ < n_regions_ && ref_id_[g_] < rid) g_++;
             if (g_ == n_regions_) { done_ = true; break; }
             if (ref_id_[g_] != rid) continue;
-            const int64_t pos = rv.pos(), rl = rec_ref_len(rv);
+            int64_t pos = rv.pos(), rl = rec_ref_len(rv);
+            if (rl == 0 && staged_passes(rv.p, pass_mask_)) rl = 1;              // (bam_select's rule for a record that passes)
             if (!(pos < stop_[g_] && pos + rl > start_[g_])) continue;           // overlaps [start, stop)
             if (max_reads_ > 0 && kept_ >= max_reads_) { done_ = true; break; }  // src/bam.pyx:29-30
             if ((uint32_t)rv.flag() & drop_flags_) continue;                     // secondary / supplementary / unmapped, :31-32
@@ -1513,6 +1532,7 @@ private:
     int g_ = 0;                              // the region the walk has reached
     const int64_t max_reads_;
     const uint32_t drop_flags_;              // (the realigner's; the recount of the confusion matrices filters for itself)
+    const uint32_t pass_mask_;               // ... without these bits: such records pass through (staged_head.hpp)
     int64_t kept_ = 0;
     int32_t last_rid_ = -1;                  // (the sorted-by-reference check)
     bool done_;

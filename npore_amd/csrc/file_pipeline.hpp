@@ -73,11 +73,11 @@ DeflateParams slot_deflate_params(npore_batch_slot &s, const uint8_t *d_recs, co
 }
 
 // npore_bam_set_output holds for ONE run: the run that writes takes the setting and leaves the default behind
-struct OutputSetting { int format, flags, tags; std::string bai; };
+struct OutputSetting { int format, flags, tags; std::string bai; int pass; };
 OutputSetting take_output_setting(npore_bam *b)
 {
-    OutputSetting o{b->out_format, b->out_flags, b->out_tags, b->out_bai};
-    b->out_format = NPORE_OUT_SAM; b->out_flags = 0; b->out_tags = 0; b->out_bai.clear();
+    OutputSetting o{b->out_format, b->out_flags, b->out_tags, b->out_bai, b->out_pass};
+    b->out_format = NPORE_OUT_SAM; b->out_flags = 0; b->out_tags = 0; b->out_pass = 0; b->out_bai.clear();
     std::fill(b->out_info, b->out_info + 4, 0);
     return o;
 }
@@ -90,6 +90,7 @@ struct PipeMode {
     bool md = false;             // ... NPORE_OUT_MD: with the MD tag behind NM
     int tags = 0;                // ... NPORE_TAG_*: with cs / de behind that
     int deflate = 0;             // the writer's DEFLATE_MODE_*, 0: stored members
+    uint32_t pass_mask = 0;      // ... npore_bam_set_output_pass (FULL records only): records with these flag bits pass through
     // BAM mode: the records are built on the device where the default pipeline runs (device pack + device glue:
     // bam_emit_kernels.hpp); with the host glue or the host pack the host twin makes them (format_bam_into)
     bool dev_records() const { return bam && dpack; }
@@ -104,6 +105,7 @@ struct RunOutput {
     npore_bam *b = nullptr;
     bool full = false, md = false;      // NPORE_OUT_FULL, NPORE_OUT_MD
     int tags = 0;                       // NPORE_TAG_*
+    uint32_t pass_mask = 0;             // npore_bam_set_output_pass
     int open(npore_bam *bam, const char *out_path, int threads)
     {
         b = bam;
@@ -111,6 +113,7 @@ struct RunOutput {
         full = o.format == NPORE_OUT_BAM && (o.flags & NPORE_OUT_FULL) != 0;
         md = full && (o.flags & NPORE_OUT_MD) != 0;
         tags = full ? o.tags : 0;
+        pass_mask = full ? (uint32_t)o.pass : 0;
         if (o.format == NPORE_OUT_BAM) {
             bw.reset(new BgzfStoredWriter());
             return bw->open(out_path, b->ref_names.size(), o.bai.empty() ? nullptr : o.bai.c_str(), (o.flags & NPORE_OUT_EOF) != 0,
@@ -144,7 +147,7 @@ PipeMode pipe_mode(const npore_ctx *ctx, const RunOutput &out)      // (NPORE_DE
 {
     const char *e = std::getenv("NPORE_DEVICE_PACK");
     const bool glue = ctx->device_glue != 0, dpack = glue && ctx->device_pack != 0 && !(e && std::atoi(e) == 0);
-    return PipeMode{glue, dpack, out.bw != nullptr, out.full, out.md, out.tags, out.bw ? out.bw->deflate_mode() : 0};
+    return PipeMode{glue, dpack, out.bw != nullptr, out.full, out.md, out.tags, out.bw ? out.bw->deflate_mode() : 0, out.pass_mask};
 }
 
 // The FASTA on the device (once per FASTA and context) and, per BAM reference, where its contig lies there.
@@ -179,7 +182,7 @@ void slot_pack_sizes(npore_batch_slot &s, int threads, const PipeMode &pm)
     for (auto *v : {&s.ro, &s.so, &s.co, &s.oo, &s.fo}) v->assign(n + 1, 0);
     s.olen.assign(n, 0);
     s.flen.assign(n, 0);
-    pack_sizes_of(s.rf, s.m, s.ro.data(), s.so.data(), s.co.data(), threads);
+    pack_sizes_of(s.rf, s.m, s.ro.data(), s.so.data(), s.co.data(), threads, pm.pass_mask);
     for (size_t k = 0; k < n; k++) {
         const int64_t cap = (s.ro[k + 1] - s.ro[k]) + (s.so[k + 1] - s.so[k]);
         s.oo[k + 1] = s.oo[k] + (!pm.glue ? cap : (pm.dev_records() ? 4 : 2) * cap + 16);
@@ -195,7 +198,7 @@ int slot_pack_arrays(const npore_bam *b, const npore_fasta *fa, const int32_t *f
     if ((rce = s.refs.ensure((size_t)s.ro[n] + 64)) || (rce = s.seqs.ensure((size_t)s.so[n] + 64)) || (rce = s.cigs.ensure((size_t)s.co[n] + 64))) return rce;
     if (!fa || !fasta_of_ref) return fail(NPORE_E_INVALID, "bad argument");
     if (int rc = pack_records(b, s.rf, fa, fasta_of_ref, s.m, reinterpret_cast<uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<uint8_t *>(s.seqs.p),
-                              s.so.data(), s.cigs.p, s.co.data(), threads, true)) return rc;
+                              s.so.data(), s.cigs.p, s.co.data(), threads, true, pm.pass_mask)) return rc;
     // (device glue: the texts come back compacted -- slot_enqueue --, neither a page-locked copy of the slots nor the host glue's finals)
     if (pm.glue) return NPORE_OK;
     if (int rc = s.alns.ensure((size_t)s.oo[n] + 64)) return rc;
@@ -211,6 +214,8 @@ int slot_pack_arrays(const npore_bam *b, const npore_fasta *fa, const int32_t *f
 // reference position is the worst text, `0^A` repeated -- `0A` takes two per compared position --, and the closing count
 // has at most 10 digits); with cs by 4 + 3 * (reflen + seqlen) -- no item of the text has more than three bytes per base it
 // covers (cs_rec.hpp, Size) --, with de by 7.
+// A record that passes (PipeMode::pass_mask, staged_head.hpp): the block_size word and the whole record are staged, and the
+// bound grows by exactly those 4 + block_size bytes -- an ML-like array of tens of kilobytes included.
 int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, int threads, npore_batch_slot &s, const PipeMode &pm)
 {
     const int64_t n = s.m;
@@ -223,6 +228,12 @@ int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta
         const int32_t rid = r.ref_id();
         const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
         if (fi < 0 || fi >= n_fasta) return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
+        if (pm.full && staged_passes(r.p, pm.pass_mask)) {
+            s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_pass_bytes(r.p);
+            reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = 0;
+            s.rec_cap += staged_pass_bytes(r.p);
+            continue;
+        }
         const int64_t aux = pm.full ? filter_aux(r.aux(), r.end(), nullptr) : 0;
         s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_head_bytes(r, rec_cigar(r), pm.bam ? STAGE_QUALS : STAGE_HEAD) + aux;
         const int64_t cap = (s.ro[(size_t)k + 1] - s.ro[(size_t)k]) + (s.so[(size_t)k + 1] - s.so[(size_t)k]);
@@ -241,7 +252,7 @@ int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta
         for (int64_t k = t * per; k < std::min(n, (t + 1) * per); k++) {
             char *dst = s.raw.p + s.rawo[(size_t)k];
             const size_t len = (size_t)(s.rawo[(size_t)k + 1] - s.rawo[(size_t)k]);
-            stage_record_head(s.rf.ptr[(size_t)k], pm.stage_form(), reinterpret_cast<uint8_t *>(dst));
+            stage_record_head(s.rf.ptr[(size_t)k], pm.stage_form(), reinterpret_cast<uint8_t *>(dst), pm.pass_mask);
             cache_writeback(dst, len);         // page-locked staging about to cross PCIe: out of this core's cache first (hostio.hpp)
         }
     });
@@ -267,7 +278,7 @@ int slot_enqueue(npore_ctx *ctx, npore_batch_slot &s, const PipeMode &pm, const 
             (rc = s.reclen_pin.ensure((size_t)m * 8 + 64)) || (rc = s.total_pin.ensure(64))) return fail(rc, "batch buffers");
         s.emit = BamEmit{s.d_recs.as<uint8_t>(), s.rec_cap, s.d_cursor.as<unsigned long long>(), reinterpret_cast<const int64_t *>(s.hp_pin.p),
                          reinterpret_cast<int64_t *>(s.reclen_pin.p), reinterpret_cast<unsigned long long *>(s.total_pin.p)};
-        s.emit.full = pm.full; s.emit.md = pm.md; s.emit.tags = pm.tags;
+        s.emit.full = pm.full; s.emit.md = pm.md; s.emit.tags = pm.tags; s.emit.pass_mask = pm.pass_mask;
         if (pm.dev_deflate()) {
             if ((rc = slot_deflate_buffers(s, s.rec_cap, pm.deflate))) return fail(rc, "batch buffers");
             s.emit.dfl = slot_deflate_params(s, s.d_recs.as<uint8_t>(), s.d_cursor.as<unsigned long long>(), ctx->d_stream_pos.as<unsigned long long>(),
@@ -314,7 +325,9 @@ int slot_fetch_records(const int32_t *status, npore_batch_slot &s, const PipeMod
         if ((len[k] == 0) != ((status[k] & NPORE_ST_BAD_INPUT) != 0)) return fail(NPORE_E_HIP, "internal: BAM records and status bits disagree");
         if (len[k] == 0) continue;
         const RecView r = rec_of(s.rf, k);
-        s.meta.push_back(BamRecMeta{r.ref_id(), r.pos(), s.ro[(size_t)k + 1] - s.ro[(size_t)k], len[k]});
+        // (a record that passed gave align() no reference slice: the index takes the input record's own reference length)
+        const int64_t span = staged_passes(r.p, pm.pass_mask) ? rec_ref_len(r) : s.ro[(size_t)k + 1] - s.ro[(size_t)k];
+        s.meta.push_back(BamRecMeta{r.ref_id(), r.pos(), span, len[k]});
         sum += len[k];
     }
     if (sum != total) return fail(NPORE_E_HIP, "internal: BAM record sizes do not add up");
@@ -341,7 +354,8 @@ int slot_collect(const npore_bam *b, const int32_t *status, int threads, npore_b
 {
     if (pm.dev_records()) return slot_fetch_records(status, s, pm);
     const int64_t n = s.m;
-    const ReadCodes codes{reinterpret_cast<const uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<const uint8_t *>(s.seqs.p), s.so.data(), pm.md, pm.tags};
+    const ReadCodes codes{reinterpret_cast<const uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<const uint8_t *>(s.seqs.p), s.so.data(), pm.md, pm.tags,
+                          pm.pass_mask};
     auto format_into = [&](const char *finals, const int64_t *final_off) {          // (FULL records: NM and MD from the slot's code arrays)
         return pm.bam ? format_bam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len, &s.meta, pm.full ? &codes : nullptr)
                       : format_sam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len);
@@ -424,6 +438,11 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             if (timed(s.t_ms[1], [&] { return hipEventSynchronize(s.done); }) != hipSuccess) { s.err = "waiting for a batch failed"; return (int)NPORE_E_HIP; }
             mark("device done", k);
             std::memcpy(s.olen.data(), s.olen_pin.p, (size_t)s.m * 8);
+            if (pm.pass_mask) {          // NPORE_ST_PASSED: not realigned, written as it came (the device left these reads' status 0)
+                int32_t *st = reinterpret_cast<int32_t *>(s.st_pin.p);
+                for (int64_t q = 0; q < s.m; q++)
+                    if (staged_passes(rec_of(s.rf, q).p, pm.pass_mask)) st[q] |= NPORE_ST_PASSED;
+            }
             double ms_std = 0.0, ms_all = 0.0;
             const int rcc = timed(ms_all, [&] { return (int)kept(s, slot_collect(b, status_of(s), post_threads, s, pm, &ms_std)); });
             s.t_ms[2] += ms_std; s.t_ms[3] += ms_all - ms_std;

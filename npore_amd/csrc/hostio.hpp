@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "glue.hpp"
+#include "staged_head.hpp"
 
 namespace npore {
 
@@ -576,6 +577,7 @@ struct npore_bam {
     // npore_bam_set_output: what the NEXT file run on the handle writes (0 = SAM text, 1 = BAM records in stored BGZF
     // members), where its .bai goes ("" = none), NPORE_OUT_* flags; out_info: what that run wrote (npore_bam_output_info)
     int out_format = 0, out_flags = 0, out_tags = 0;
+    int out_pass = 0;                     // npore_bam_set_output_pass: the flag bits whose records pass through the next run (staged_head.hpp)
     std::string out_bai;
     int64_t out_info[4] = {0, 0, 0, 0};
     int64_t inflate_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the device inflation of the last run on the handle (npore_bam_inflate_info)
@@ -784,20 +786,24 @@ inline int64_t filter_aux(const uint8_t *q, const uint8_t *end, uint8_t *dst)
 // field, which no kernel reads (the emit kernel recomputes the bin).  stage_record_head() writes both halves for every
 // record; staged_cigar() (staged_head.hpp) is the one reader, on the device and on the host.
 enum : int { STAGE_HEAD = 0, STAGE_QUALS = 1, STAGE_FULL = 2 };      // (0 / 1: what `bool with_quals` used to say)
+// pass_mask (staged_head.hpp record_passes; STAGE_FULL only): a record that passes is staged verbatim -- the block_size word
+// and the whole record as it lies in the stream, every tag, a long CIGAR still placeholder + CG tag, n_cigar_op and bin untouched
 inline int64_t staged_head_bytes(const RecView &r, const RecCigar &cg, int form)
 {
     return 4 + 32 + (int64_t)r.l_read_name() + 4 * (int64_t)cg.n + (int64_t)((form != STAGE_HEAD ? r.aux() : r.qual()) - r.seq()) +
            (form == STAGE_FULL ? filter_aux(r.aux(), r.end(), nullptr) : 0);
 }
-inline int64_t staged_head_bytes(const uint8_t *rec, int form)
+inline int64_t staged_head_bytes(const uint8_t *rec, int form, uint32_t pass_mask = 0)
 {
     const RecView r = rec_view(rec);
+    if (form == STAGE_FULL && staged_passes(r.p, pass_mask)) return staged_pass_bytes(r.p);
     return staged_head_bytes(r, rec_cigar(r), form);
 }
-// rec: the record, block_size word first; dst: staged_head_bytes(rec, form) bytes
-inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst)
+// rec: the record, block_size word first; dst: staged_head_bytes(rec, form, pass_mask) bytes
+inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst, uint32_t pass_mask = 0)
 {
     const RecView r = rec_view(rec);
+    if (form == STAGE_FULL && staged_passes(r.p, pass_mask)) { std::memcpy(dst, rec, (size_t)staged_pass_bytes(r.p)); return; }
     const RecCigar cg = rec_cigar(r);
     const size_t fixed = 4 + 32 + (size_t)r.l_read_name(), tail = (size_t)((form != STAGE_HEAD ? r.aux() : r.qual()) - r.seq());
     if (cg.w == r.cigar()) std::memcpy(dst, rec, fixed + 4 * (size_t)cg.n + tail);

@@ -1410,6 +1410,14 @@ int64_t npore_bam_select(const npore_bam *b, int n_regions, const int32_t *ref_i
     return bam_select(b, n_regions, ref_id, start, stop, max_reads, out_idx, cap);
 }
 
+// ... keeping the records whose flag has a bit of flag_mask (a subset of 0x904), to pass through (npore_bam_set_output_pass)
+int64_t npore_bam_select_pass(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
+                              int64_t max_reads, int flag_mask, int64_t *out_idx, int64_t cap)
+{
+    if (flag_mask & ~(int)PASS_FLAGS) return fail(NPORE_E_INVALID, "bad argument");
+    return bam_select(b, n_regions, ref_id, start, stop, max_reads, out_idx, cap, PASS_FLAGS, (uint32_t)flag_mask);
+}
+
 npore_fasta *npore_fasta_open(const char *path)
 try {
     if (!path) { fail(NPORE_E_INVALID, "null path"); return nullptr; }
@@ -1434,7 +1442,7 @@ try {
     if (!pack_args_ok(b, idx, n) || !ref_off || !seq_off || !cig_off) return fail(NPORE_E_INVALID, "bad argument");
     RecFetch rf;          // (local to the call: the handle is const here, and two threads may size / pack from one handle)
     if (int rc = fetch_records(b, idx, n, 0, rf)) return rc;
-    pack_sizes_of(rf, n, ref_off, seq_off, cig_off, 0);
+    pack_sizes_of(rf, n, ref_off, seq_off, cig_off, 0, (uint32_t)b->out_pass);      // (a record that passes has empty slices)
     return NPORE_OK;
 }
 NPORE_CATCH_INT
@@ -1448,7 +1456,7 @@ try {
         return fail(NPORE_E_INVALID, "bad argument");
     RecFetch rf;
     if (int rc = fetch_records(b, idx, n, threads, rf)) return rc;
-    return pack_records(b, rf, fa, fasta_of_ref, n, refs, ref_off, seqs, seq_off, cigs, cig_off, threads);
+    return pack_records(b, rf, fa, fasta_of_ref, n, refs, ref_off, seqs, seq_off, cigs, cig_off, threads, false, (uint32_t)b->out_pass);
 }
 NPORE_CATCH_INT
 
@@ -1480,12 +1488,12 @@ struct PackedCodes {
     std::vector<int64_t> ro, so, co;
     std::vector<uint8_t> refs, seqs;
     std::vector<char> cigs;
-    int pack(const npore_bam *b, const RecFetch &rf, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n, int threads)
+    int pack(const npore_bam *b, const RecFetch &rf, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n, int threads, uint32_t pass_mask = 0)
     {
         for (auto *v : {&ro, &so, &co}) v->assign((size_t)n + 1, 0);
-        pack_sizes_of(rf, n, ro.data(), so.data(), co.data(), threads);
+        pack_sizes_of(rf, n, ro.data(), so.data(), co.data(), threads, pass_mask);
         refs.resize((size_t)ro[(size_t)n] + 64); seqs.resize((size_t)so[(size_t)n] + 64); cigs.resize((size_t)co[(size_t)n] + 64);
-        return pack_records(b, rf, fa, fasta_of_ref, n, refs.data(), ro.data(), seqs.data(), so.data(), cigs.data(), co.data(), threads);
+        return pack_records(b, rf, fa, fasta_of_ref, n, refs.data(), ro.data(), seqs.data(), so.data(), cigs.data(), co.data(), threads, false, pass_mask);
     }
 };
 }  // namespace
@@ -1515,13 +1523,21 @@ static bool output_tags_ok(int tags)
 int npore_bam_format_bam_full_tags(npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
                                    const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
                                    const uint8_t **recs, int64_t *recs_len, int flags, int tags)
+{
+    return npore_bam_format_bam_full_pass(b, fa, fasta_of_ref, idx, n, finals, final_off, final_len, status, threads, recs, recs_len, flags, tags, 0);
+}
+
+// ... and with pass_mask: the records whose flag has one of its bits (a subset of 0x904) are the input's bytes (0: the records above)
+int npore_bam_format_bam_full_pass(npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,
+                                   const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
+                                   const uint8_t **recs, int64_t *recs_len, int flags, int tags, int pass_mask)
 try {
-    if (!pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs || (flags & ~NPORE_OUT_MD) || !output_tags_ok(tags))
+    if (!pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs || (flags & ~NPORE_OUT_MD) || !output_tags_ok(tags) || (pass_mask & ~(int)PASS_FLAGS))
         return fail(NPORE_E_INVALID, "bad argument");
     if (int rc = fetch_records(b, idx, n, threads, b->api_fetch)) return rc;
     PackedCodes pc;
-    if (int rc = pc.pack(b, b->api_fetch, fa, fasta_of_ref, n, threads)) return rc;
-    const ReadCodes codes{pc.refs.data(), pc.ro.data(), pc.seqs.data(), pc.so.data(), (flags & NPORE_OUT_MD) != 0, tags};
+    if (int rc = pc.pack(b, b->api_fetch, fa, fasta_of_ref, n, threads, (uint32_t)pass_mask)) return rc;
+    const ReadCodes codes{pc.refs.data(), pc.ro.data(), pc.seqs.data(), pc.so.data(), (flags & NPORE_OUT_MD) != 0, tags, (uint32_t)pass_mask};
     const int rc = format_bam_into(b, b->api_fetch, n, finals, final_off, final_len, status, threads, b->recs, recs_len, nullptr, &codes);
     *recs = reinterpret_cast<const uint8_t *>(b->recs.p);
     return rc;
@@ -1551,10 +1567,22 @@ int npore_debug_format_bam_full_md_device(npore_ctx *ctx, npore_bam *b, const np
 int npore_debug_format_bam_full_tags_device(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
                                             int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status,
                                             uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm, int flags, int32_t *md_len, int tags)
+{
+    return npore_debug_format_bam_full_pass_device(ctx, b, fa, fasta_of_ref, idx, n, finals, final_off, final_len, status, recs, cap, recs_len, nm, flags,
+                                                   md_len, tags, 0);
+}
+
+// ... and with pass_mask: a record that passes is staged verbatim, skipped by the unpack and tag kernels, placed by its own size
+// and copied by one wave
+int npore_debug_format_bam_full_pass_device(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx,
+                                            int64_t n, const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status,
+                                            uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm, int flags, int32_t *md_len, int tags,
+                                            int pass_mask)
 try {
     const bool md = (flags & NPORE_OUT_MD) != 0;
+    const uint32_t pmask = (uint32_t)pass_mask;
     if (!ctx || !pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs_len || cap < 0 || (cap > 0 && !recs) || (flags & ~NPORE_OUT_MD) ||
-        !output_tags_ok(tags) ||
+        !output_tags_ok(tags) || (pass_mask & ~(int)PASS_FLAGS) ||
         (n > 0 && (!finals || !final_off || !final_len || !status || !nm || (md && !md_len))))
         return fail(NPORE_E_INVALID, "bad argument");
     *recs_len = 0;
@@ -1568,25 +1596,27 @@ try {
     const size_t N = (size_t)n;
     std::vector<int64_t> off(5 * (N + 1), 0), aux(N, 0), wlen(N, 0);       // ref, seq, cig, words, raw offsets
     int64_t *ro = off.data(), *so = ro + (N + 1), *co = so + (N + 1), *wo = co + (N + 1), *rawo = wo + (N + 1);
-    pack_sizes_of(rf, n, ro, so, co, 0);
+    pack_sizes_of(rf, n, ro, so, co, 0, pmask);
     int64_t bound = 0;
     for (size_t k = 0; k < N; k++) {
         const RecView r = rec_of(rf, (int64_t)k);
         const int32_t rid = r.ref_id();
         if (rid < 0 || rid >= (int32_t)b->ref_names.size() || fasta_of_ref[rid] < 0 || fasta_of_ref[rid] >= (int)fa->names.size())
             return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
-        const int64_t ops = (status[k] & NPORE_ST_BAD_INPUT) ? 0 : cigar_text_ops(finals + final_off[k], final_len[k]);
+        const bool pass = staged_passes(r.p, pmask);
+        const int64_t ops = ((status[k] & NPORE_ST_BAD_INPUT) || pass) ? 0 : cigar_text_ops(finals + final_off[k], final_len[k]);
         if (ops < 0) return fail(NPORE_E_UNSUPPORTED, "a final CIGAR is no CIGAR text (BAM output)");
-        aux[k] = filter_aux(r.aux(), r.end(), nullptr);
+        aux[k] = pass ? 0 : filter_aux(r.aux(), r.end(), nullptr);
         wlen[k] = 4 * ops;
         wo[k + 1] = wo[k] + 4 * ops + 16;
-        rawo[k + 1] = rawo[k] + ((staged_head_bytes(rf.ptr[k], STAGE_FULL) + 7) & ~7ll);
+        rawo[k + 1] = rawo[k] + ((staged_head_bytes(rf.ptr[k], STAGE_FULL, pmask) + 7) & ~7ll);
+        if (pass) { bound += staged_pass_bytes(r.p); continue; }
         bound += 36 + r.l_read_name() + 4 * ops + 32 + ((int64_t)r.l_seq() + 1) / 2 + r.l_seq() + aux[k] + 7 + 16;
     }
     std::vector<uint8_t> raw((size_t)rawo[N] + 64, 0), words((size_t)wo[N] + 64, 0);
     for (size_t k = 0; k < N; k++) {
-        stage_record_head(rf.ptr[k], STAGE_FULL, raw.data() + rawo[k]);
-        if (status[k] & NPORE_ST_BAD_INPUT) continue;
+        stage_record_head(rf.ptr[k], STAGE_FULL, raw.data() + rawo[k], pmask);
+        if ((status[k] & NPORE_ST_BAD_INPUT) || staged_passes(rf.ptr[k] + 4, pmask)) continue;
         uint32_t len = 0;
         uint8_t *o = words.data() + wo[k];
         for (int64_t q = 0; q < final_len[k]; q++) {
@@ -1636,6 +1666,7 @@ try {
     up.seqs = d_seqs.as<uint8_t>(); up.seq_off = o64 + (n + 1);
     up.cigs = d_cigs.as<char>(); up.cig_off = o64 + 2 * (n + 1);
     up.n_reads = n;
+    up.pass_mask = pmask;
     hipLaunchKernelGGL(unpack_records_kernel, dim3((unsigned)n), dim3(256), 0, st, up);
     BamEmitParams bp;
     bp.raw = up.raw; bp.raw_off = up.raw_off; bp.ref_off = up.ref_off; bp.seq_off = up.seq_off;
@@ -1647,6 +1678,7 @@ try {
     bp.refs = up.refs; bp.seqs = up.seqs; bp.nm = d_nm.as<int32_t>();
     if (md) bp.md_len = d_md.as<int32_t>();
     if (tags) { bp.tags = tags; bp.cs_len = d_cs.as<int32_t>(); bp.de = d_de.as<float>(); }
+    bp.pass_mask = pmask;
     launch_bam_emit(bp, true, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
@@ -1681,6 +1713,15 @@ int npore_bam_set_output(npore_bam *b, int format, const char *bai_path, int fla
     b->out_bai = (format == NPORE_OUT_BAM && bai_path) ? bai_path : "";
     b->out_flags = flags;
     b->out_tags = 0;
+    b->out_pass = 0;
+    return NPORE_OK;
+}
+
+int npore_bam_set_output_pass(npore_bam *b, int flag_mask)
+{
+    if (!b || (flag_mask & ~(int)PASS_FLAGS) || b->out_format != NPORE_OUT_BAM || !(b->out_flags & NPORE_OUT_FULL))      // (only a FULL record can be the input's)
+        return fail(NPORE_E_INVALID, "bad argument");
+    b->out_pass = flag_mask;
     return NPORE_OK;
 }
 
@@ -1802,13 +1843,14 @@ try {
     counts[0] = counts[1] = counts[2] = 0;
     HIP_TRY(hipSetDevice(ctx->device));
     InflateRun infl(ctx, b);
-    BamRecordWalker walker(b, n_regions, ref_id, start, stop, max_reads, threads, 0x100 | 0x800 | 0x4, infl.hook());
+    // (npore_bam_set_output_pass: the reader keeps what the run passes through; the setter has seen to it that the run writes FULL records)
+    BamRecordWalker walker(b, n_regions, ref_id, start, stop, max_reads, threads, PASS_FLAGS, infl.hook(), (uint32_t)b->out_pass);
     RunOutput out;
     if (int rco = out.open(b, out_path, threads)) return rco;
     int64_t n_bad = 0, ordinal0 = 0;
     auto on_status = [&](int64_t, int64_t m, const int32_t *st) {
         for (int64_t i = 0; i < m; i++)
-            if (st[i]) {
+            if (st[i] & ~NPORE_ST_PASSED) {       // (a record that passed is neither refused nor inconsistent)
                 counts[(st[i] & NPORE_ST_BAD_INPUT) ? 1 : 2]++;
                 if (n_bad < bad_cap) { bad_ord[n_bad] = ordinal0 + i; bad_status[n_bad] = st[i]; }
                 n_bad++;

@@ -23,4 +23,22 @@ NPORE_STAGED_HD void staged_cigar(const uint8_t *f, const uint8_t *&cg, int &nc,
     sq = cg + 4 * (int64_t)nc;
 }
 
+// PASS-THROUGH (npore_bam_set_output_pass, `--pass_through`), the rule stated once: a record of a run PASSES iff
+// `flag & pass_mask` is non-zero, pass_mask a subset of 0x904 (secondary, supplementary, placed but unmapped; 0, the
+// default: nothing passes).  A passing record is selected like a read, gives align() nothing and is written as it came:
+// its staged head (STAGE_FULL) is the block_size word and the WHOLE record as it lies in the stream -- n_cigar_op and bin
+// untouched, so staged_cigar() is not for it --, and every reader of a staged head asks this predicate first.
+constexpr uint32_t PASS_FLAGS = 0x100u | 0x800u | 0x4u;
+NPORE_STAGED_HD bool record_passes(uint32_t flag, uint32_t pass_mask) { return (flag & pass_mask) != 0; }
+// ... of a staged head's (or a record's) fixed fields f
+NPORE_STAGED_HD bool staged_passes(const uint8_t *f, uint32_t pass_mask)
+{
+    return record_passes((uint32_t)f[14] | (uint32_t)f[15] << 8, pass_mask);
+}
+// bytes of a passing record's staged head and of its output record: 4 + block_size
+NPORE_STAGED_HD int64_t staged_pass_bytes(const uint8_t *f)
+{
+    return 4 + (int64_t)(int32_t)((uint32_t)f[-4] | (uint32_t)f[-3] << 8 | (uint32_t)f[-2] << 16 | (uint32_t)f[-1] << 24);
+}
+
 }  // namespace npore

@@ -31,6 +31,7 @@ struct UnpackParams {
     uint8_t *seqs; const int64_t *seq_off;
     char *cigs; const int64_t *cig_off;
     int64_t n_reads;
+    uint32_t pass_mask = 0;      // records that pass (staged_head.hpp): staged verbatim, their three slices are empty
 };
 
 __device__ __forceinline__ uint32_t ld16(const uint8_t *q) { return (uint32_t)q[0] | ((uint32_t)q[1] << 8); }
@@ -43,6 +44,7 @@ __global__ __launch_bounds__(256) void unpack_records_kernel(UnpackParams p)
     if (k >= p.n_reads) return;
     const int t = threadIdx.x;
     const uint8_t *f = p.raw + p.raw_off[k] + 4;                 // the fixed fields (hostio.hpp RecView)
+    if (staged_passes(f, p.pass_mask)) return;                   // (the whole workgroup: nothing to write, and no staged CIGAR to read)
     const int32_t rid = (int32_t)ld32(f), pos = (int32_t)ld32(f + 4);
     const uint8_t *cg, *sq;
     int nc;

@@ -80,6 +80,12 @@ def argparser():
     parser.add_argument("--de", action="store_true",
                         help="--records full: write minimap2's de tag (gap-compressed per-base divergence, a float) behind cs, "
                              "counted on the GPU in the same walk.  Without it the records carry no de: the input's is stale.")
+    parser.add_argument("--pass_through", action="store_true",
+                        help="--records full: write the records the realigner does not take -- secondary (0x100), supplementary "
+                             "(0x800) and placed but unmapped (0x4) ones -- as they came, every tag included, in their place among "
+                             "the realigned records, so that the output holds the records of the input; they count towards "
+                             "--max_reads.  Still left out: unplaced records (no reference), and reads whose CIGAR and sequence "
+                             "disagree (reported, as without the flag).  Without it such records are dropped, as the reference does.")
     parser.add_argument("--bam_inflate", choices=("host", "device"), default="host",
                         help="One-pass reader: where the input BAM's BGZF blocks are inflated: `host`, on the CPU threads; `device`, "
                              "on the GPU, one wave per block (also for --recalc_cms --cms_source bam).  The output is the same.  "
@@ -105,6 +111,10 @@ def main():
     cs, de = getattr(cfg.args, "cs", None), bool(getattr(cfg.args, "de", False))
     if (cs or de) and records != "full":
         print(f"\nERROR: {'--cs' if cs else '--de'} needs --out_format bam --records full.")
+        sys.exit(1)
+    pass_mask = bam_mod.PASS_FLAGS if getattr(cfg.args, "pass_through", False) else 0
+    if pass_mask and records != "full":
+        print("\nERROR: --pass_through needs --out_format bam --records full.")
         sys.exit(1)
     if records == "full" and not native:
         print("\nERROR: --records full is written by the library's file pipeline: not with --python_io.")
@@ -175,7 +185,8 @@ def main():
         open(out_sam, "w").close()
     # BAM: the index beside the file (a rank's part: a sidecar with part-relative offsets, merged by dist.gather_bam_parts);
     # the EOF member ends the whole file, not a part
-    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress, records=records, md=md, cs=cs, de=de) if as_bam else {}
+    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress, records=records, md=md, cs=cs, de=de,
+                  pass_mask=pass_mask) if as_bam else {}
     gather = dist_mod.gather_bam_parts if as_bam else dist_mod.gather_parts
 
     print("> extracting read data from BAM")
@@ -212,7 +223,7 @@ def main():
         if world > 1:
             n = gather(final_sam, cfg.args.out_prefix, n)
     elif native:
-        idx = bam.select(cfg.args.regions, cfg.args.max_reads)
+        idx = bam.select(cfg.args.regions, cfg.args.max_reads, pass_mask=pass_mask)
         # reads are independent: dealt by index, no data-path collective.  A resident BAM is dealt round-robin; a
         # STREAMED one in contiguous shares, so that a rank only ever inflates the blocks that hold its own reads
         # (BAM output: contiguous shares always -- the parts in rank order are then in file order, sorted and indexable)

@@ -50,7 +50,7 @@ def _encode_span(job):
     """Worker: reads first ... first + count - 1 of the bench generator as BAM records (bytes) + their stretch of the contig.
     Qualities: one uniform draw per base over phred 0 ... 93, as the reference's own fixture generator does
     (test/generate_bam.py:63,79: chr(randint(33, 127)) per base) -- or the constant 20 of rounds 3 - 4 (`const_qual`)."""
-    seed, first, count, ref_len, const_qual, per_ctg, tags = job
+    seed, first, count, ref_len, const_qual, per_ctg, tags, flagged = job
     dec = np.frombuffer(b"NACGT", np.uint8)
     recs, contig = [], []
     for k in range(first, first + count):
@@ -72,7 +72,10 @@ def _encode_span(job):
         else:
             qual = np.random.Generator(np.random.PCG64(seed * 7919 + k)).integers(0, 94, len(sq), dtype=np.uint8).tobytes()
         name = f"read{k}".encode() + b"\0"
-        body = struct.pack("<iiBBHHHiiii", k // per_ctg, (k % per_ctg) * ref_len, len(name), 60, 4680, len(lens), 0, len(sq), -1, -1, 0) + \
+        # (--flagged: that share of the records, dealt by a hash of k, is secondary / supplementary by turns -- what a run drops, or
+        # with --pass_through writes as it came)
+        flag = (0x100, 0x800)[k & 1] if (k * 2654435761 % 4294967296) < flagged * 4294967296 else 0
+        body = struct.pack("<iiBBHHHiiii", k // per_ctg, (k % per_ctg) * ref_len, len(name), 60, 4680, len(lens), flag, len(sq), -1, -1, 0) + \
             name + cig + packed + qual + b"HPC" + bytes([k % 3])
         if tags:        # (--tags: a read group and an ML-like array of l_seq / 2 bytes behind HP)
             ml = np.random.Generator(np.random.PCG64(seed * 104729 + k)).integers(0, 256, len(sq) // 2, dtype=np.uint8).tobytes()
@@ -83,16 +86,16 @@ def _encode_span(job):
     return b"".join(recs), b"".join(contig)
 
 
-def build_inputs(tmp, n, distinct, ref_len, seed, const_qual=False, procs=0, tags=False):
+def build_inputs(tmp, n, distinct, ref_len, seed, const_qual=False, procs=0, tags=False, flagged=0.0):
     """The BAM (BGZF, zlib level 1) and FASTA of `n` reads laid end to end on one contig.  distinct = 0 (default): every
     read is its own draw of the generator, made on a pool of worker processes; distinct = d < n: the first d reads'
     record block repeated at the byte level (rounds 3 - 4: 4 000 distinct reads x 24).  tags: every read carries an RG:Z and a
-    B,C array of l_seq / 2 bytes."""
+    B,C array of l_seq / 2 bytes.  flagged: the share of the records (0 ... 1) that carry the secondary or the supplementary flag."""
     import multiprocessing as mp
     distinct = n if distinct <= 0 else min(distinct, n)
     procs = procs or max(1, min(16, len(os.sched_getaffinity(0))))
     span = 250
-    jobs = [(seed, k, min(span, distinct - k), ref_len, const_qual, READS_PER_CONTIG, tags) for k in range(0, distinct, span)]
+    jobs = [(seed, k, min(span, distinct - k), ref_len, const_qual, READS_PER_CONTIG, tags, flagged) for k in range(0, distinct, span)]
     recs, contig = [], []
     with mp.get_context("spawn").Pool(procs) as pool:
         for r_, c_ in pool.imap(_encode_span, jobs):
@@ -135,7 +138,8 @@ def start_output(a, out, nb):
     """The header of the output file, and what the realign calls need to write behind it in a.out_format."""
     if a.out_format == "bam":
         bam.create_bam_header(out, nb)
-        return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai", compress=a.bam_compress, records=a.records, md=a.md, cs=a.cs, de=a.de)
+        return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai", compress=a.bam_compress, records=a.records, md=a.md, cs=a.cs, de=a.de,
+                    pass_mask=bam.PASS_FLAGS if a.pass_through else 0)
     bam.create_header(out, nb)
     return {}
 
@@ -150,7 +154,7 @@ def run_file(ctx, bp, fa, clen, a, out, stream):
     t0 = time.perf_counter()
     nb, nf = bam.NativeBam(bp, stream=stream, threads=a.threads), bam.NativeFasta(fa)
     t1 = time.perf_counter()
-    idx = nb.select(regions_of(clen))
+    idx = nb.select(regions_of(clen), pass_mask=bam.PASS_FLAGS if a.pass_through else 0)
     t2 = time.perf_counter()
     out_kw = start_output(a, out, nb)
     bam.realign_native(ctx, nb, nf, idx, out, r=a.r, batch_reads=a.batch, threads=a.threads, **out_kw)
@@ -264,6 +268,11 @@ def main():
     ap.add_argument("--de", action="store_true", help="--records full: with the de tag behind that, counted on the GPU")
     ap.add_argument("--tags", action="store_true",
                     help="every synthetic read carries an RG:Z tag and a B,C array of l_seq / 2 bytes (an ML-like load for --records full)")
+    ap.add_argument("--flagged", type=float, default=0.0,
+                    help="share (0 ... 1) of the synthetic records that carry the secondary or the supplementary flag: dropped by a run, "
+                         "written as they came with --pass_through")
+    ap.add_argument("--pass_through", action="store_true",
+                    help="--records full: the flagged records pass through (npore_bam_set_output_pass 0x904)")
     ap.add_argument("--inflate", choices=("host", "device"), default="host",
                     help="where the one-pass reader inflates the BAM's BGZF blocks (Context.set device_inflate)")
     ap.add_argument("--gen-into", default=None, help=argparse.SUPPRESS)       # (internal: make the inputs in this directory and exit)
@@ -276,8 +285,10 @@ def main():
         ap.error("--md needs --records full")
     if (a.cs or a.de) and a.records != "full":
         ap.error("--cs / --de need --records full")
+    if a.pass_through and a.records != "full":
+        ap.error("--pass_through needs --records full")
     if a.gen_into:
-        print(json.dumps(build_inputs(a.gen_into, a.reads, a.distinct, a.ref_len, a.seed, a.const_qual, tags=a.tags)))
+        print(json.dumps(build_inputs(a.gen_into, a.reads, a.distinct, a.ref_len, a.seed, a.const_qual, tags=a.tags, flagged=a.flagged)))
         return
     sub, nps, _, _ = aln.load_default_tables()
     with tempfile.TemporaryDirectory(dir=a.tmp) as tmp:
@@ -286,7 +297,8 @@ def main():
         # not count towards this process's peak RSS)
         import subprocess
         gen = subprocess.run([sys.executable, os.path.abspath(__file__), "--gen-into", tmp, "--reads", str(a.reads), "--distinct", str(a.distinct),
-                              "--ref-len", str(a.ref_len), "--seed", str(a.seed)] + (["--const-qual"] if a.const_qual else []) + (["--tags"] if a.tags else []),
+                              "--ref-len", str(a.ref_len), "--seed", str(a.seed)] + (["--const-qual"] if a.const_qual else []) + (["--tags"] if a.tags else []) +
+                             ["--flagged", str(a.flagged)],
                              capture_output=True, text=True)
         if gen.returncode != 0:
             sys.exit("input generation failed:\n" + gen.stderr[-3000:])
@@ -358,6 +370,7 @@ def main():
                 "reads": a.reads, "distinct_reads": a.reads if a.distinct <= 0 else min(a.distinct, a.reads),
                 "qualities": "constant 20" if a.const_qual else "uniform per base over phred 0 ... 93 (reference test/generate_bam.py:63,79)",
                 "ref_len": a.ref_len, "r": a.r, "batch": a.batch, "out_format": a.out_format, "bam_compress": a.bam_compress, "records": a.records, "md": a.md, "cs": a.cs, "de": a.de, "tags": a.tags,
+                "flagged": a.flagged, "pass_through": a.pass_through,
                 "output_bytes": os.path.getsize(out + ".o"),
                 "host_cpus": len(os.sched_getaffinity(0)), "bam_bytes": os.path.getsize(bp),
                 "resident": resident, "streamed": streamed, "streamed_output_identical": same,

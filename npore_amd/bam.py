@@ -1293,10 +1293,10 @@ class NativeBam:
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
     def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False, cs=None, de=False, pass_mask=0):
-        """FULL records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam_full;
-        md: with the MD tag behind NM, npore_bam_format_bam_full_md with NPORE_OUT_MD; cs "short" / "long", de: with those
-        tags behind MD, npore_bam_format_bam_full_tags with NPORE_TAG_*; pass_mask: the records with one of those flag bits as
-        they came, npore_bam_format_bam_full_pass)."""
+        """FULL records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam_full_pass,
+        the widest entry of the ladder, whose narrower ones forward to it with zeros; md: with the MD tag behind NM,
+        NPORE_OUT_MD; cs "short" / "long", de: with those tags behind MD, NPORE_TAG_*; pass_mask: the records with one of
+        those flag bits as they came)."""
         import ctypes as C
         idx = np.ascontiguousarray(idx, np.int64)
         n = len(idx)
@@ -1310,10 +1310,7 @@ class NativeBam:
         recs, recs_len = C.c_void_p(), C.c_int64()
         args = (self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
                 st.ctypes.data, threads, C.byref(recs), C.byref(recs_len))
-        tags = output_tags(cs, de)
-        self._check(self._lib.npore_bam_format_bam_full_pass(*args, 32 if md else 0, tags, int(pass_mask)) if pass_mask else
-                    self._lib.npore_bam_format_bam_full_tags(*args, 32 if md else 0, tags) if tags else
-                    self._lib.npore_bam_format_bam_full_md(*args, 32) if md else self._lib.npore_bam_format_bam_full(*args))
+        self._check(self._lib.npore_bam_format_bam_full_pass(*args, 32 if md else 0, output_tags(cs, de), int(pass_mask)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
     def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False, cs=None, de=False,

@@ -42,10 +42,8 @@ struct BamEmit {
     DeflateParams dfl{};
     uint32_t *h_sizes = nullptr; // [dfl.max_members] page-locked
     int64_t *h_info = nullptr;   // [4] page-locked: DeflateParams::info
-    bool full = false;           // NPORE_OUT_FULL: FULL records (the heads staged with STAGE_FULL), NM counted on the device
-    bool md = false;             // ... NPORE_OUT_MD beside it: the MD tag behind NM, sized and written on the device (md_rec.hpp)
-    int tags = 0;                // ... NPORE_TAG_*: cs / de behind that, sized and written on the device (cs_rec.hpp)
-    uint32_t pass_mask = 0;      // ... npore_bam_set_output_pass: records with these flag bits pass through (staged_head.hpp)
+    RecSpec rec;                 // which records (hostio.hpp): FULL ones have their heads staged with STAGE_FULL, and NM, MD, cs and de
+                                 // counted, sized and written on the device (nm_rec.hpp, md_rec.hpp, cs_rec.hpp)
 };
 
 struct npore_batch_slot;        // a batch of the BAM -> SAM pipeline (file_pipeline.hpp)
@@ -82,6 +80,14 @@ struct WorkSet {
     // An idle set takes the capacities of one that has just been given a group: the groups of a run are alike, so its
     // own first group then finds its buffers in place instead of allocating tens of GB in front of its kernels (with
     // three sets that was the THIRD step of a run -- 0.4 s in a timed region that had two warm-up steps)
+    // The per-read arrays of the FULL records' tag kernels (nm, md_len, cs_len, de_val) for nr reads of a run that writes `rec`
+    int reserve_emit_tags(const RecSpec &rec, size_t nr)
+    {
+        if (int rc = rec.md ? md_len.ensure(nr * 4 + 64) : 0) return rc;
+        if (int rc = rec.tags ? cs_len.ensure(nr * 4 + 64) : 0) return rc;
+        if (int rc = rec.tags ? de_val.ensure(nr * 4 + 64) : 0) return rc;
+        return rec.full ? nm.ensure(nr * 4 + 64) : NPORE_OK;
+    }
     void presize_like(const WorkSet &o)
     {
         DevBuf WorkSet::*const all[] = {&WorkSet::rd_i32, &WorkSet::rd_i64, &WorkSet::steps, &WorkSet::inss, &WorkSet::descs, &WorkSet::sched,
@@ -397,11 +403,7 @@ int reserve_group(WorkSet *w, const GroupPlan &p, const AlignArgs &a)
     if (p.mode != OutMode::BamRecords) return NPORE_OK;
     for (DevBuf *b : {&w->in_hp, &w->rec_off, &w->rec_len})
         if (int rc = b->ensure(nr * 8 + 64)) return rc;
-    if (int rc = a.bam->md ? w->md_len.ensure(nr * 4 + 64) : 0) return rc;
-    if (int rc = a.bam->tags ? w->cs_len.ensure(nr * 4 + 64) : 0) return rc;
-    if (int rc = a.bam->tags ? w->de_val.ensure(nr * 4 + 64) : 0) return rc;
-    if (a.bam->full) return w->nm.ensure(nr * 4 + 64);
-    return NPORE_OK;
+    return w->reserve_emit_tags(a.bam->rec, nr);
 }
 
 // The device addresses of a group whose buffers are reserved: the preparation's arrays (the later stages read them from
@@ -440,6 +442,42 @@ PrepParams wire_group(const npore_ctx *ctx, WorkSet *w, const GroupPlan &p, cons
     return pp;
 }
 
+// The unpack of a staged group's nr record heads into the work set's three arrays (pass_mask: these stay as they are)
+UnpackParams wire_unpack(WorkSet *w, int64_t nr, const CtgEntry *ctg, int n_ctg, uint32_t pass_mask)
+{
+    const int64_t *d_off = w->in_off.as<int64_t>();
+    UnpackParams up;
+    up.raw = w->in_raw.as<uint8_t>(); up.raw_off = d_off + 4 * (nr + 1);
+    up.ctg = ctg; up.n_ctg = n_ctg;
+    up.refs = w->in_refs.as<uint8_t>(); up.ref_off = d_off;
+    up.seqs = w->in_seqs.as<uint8_t>(); up.seq_off = d_off + (nr + 1);
+    up.cigs = w->in_cigs.as<char>(); up.cig_off = d_off + 2 * (nr + 1);
+    up.n_reads = nr;
+    up.pass_mask = pass_mask;
+    return up;
+}
+// The emit launch of a staged group of nr reads whose final CIGARs lie as words in the work set's output slots (the group's
+// own slice: read_base 0), for the records `rec` names, into the record buffer recs / cap / cursor
+BamEmitParams wire_bam_emit(WorkSet *w, int64_t nr, uint8_t *recs, int64_t cap, unsigned long long *cursor, const RecSpec &rec)
+{
+    const int64_t *d_off = w->in_off.as<int64_t>();      // (offsets of refs, seqs, CIGARs, output slots, record heads, nr + 1 each)
+    BamEmitParams bp;
+    bp.raw = w->in_raw.as<uint8_t>(); bp.raw_off = d_off + 4 * (nr + 1);
+    bp.ref_off = d_off; bp.seq_off = d_off + (nr + 1);
+    bp.hp = w->in_hp.as<int64_t>();
+    bp.words = w->out.as<uint8_t>(); bp.words_off = d_off + 3 * (nr + 1); bp.words_len = w->out_len.as<int64_t>(); bp.status = w->status.as<int32_t>();
+    bp.read_base = 0; bp.n_reads = nr;
+    bp.recs = recs; bp.cap = cap; bp.cursor = cursor;
+    bp.rec_off = w->rec_off.as<int64_t>(); bp.rec_len = w->rec_len.as<int64_t>();
+    if (rec.full) {                       // FULL records: NM from the group's code arrays, then the same two steps
+        bp.refs = w->in_refs.as<uint8_t>(); bp.seqs = w->in_seqs.as<uint8_t>(); bp.nm = w->nm.as<int32_t>();
+        bp.pass_mask = rec.pass_mask;
+        if (rec.md) bp.md_len = w->md_len.as<int32_t>();      // (MD: its size in front of the placement, its text behind the record)
+        if (rec.tags) { bp.tags = rec.tags; bp.cs_len = w->cs_len.as<int32_t>(); bp.de = w->de_val.as<float>(); }      // (cs / de: the same)
+    }
+    return bp;
+}
+
 // ---- the stages of a group.  Each enqueues, none waits for the device.
 
 // A staged group's slice to the device: bases + CIGAR ops as they lie (or the record heads, unpacked there into the same
@@ -467,16 +505,8 @@ int upload_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs
         HIP_TRY(hipMemcpyAsync(w->in_hp.p, a.bam->h_hp + g0, (size_t)nr * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(w->evc[1], s));
     if (p.raw) {
-        const int64_t *d_off = w->in_off.as<int64_t>();
-        UnpackParams up;
-        up.raw = w->in_raw.as<uint8_t>(); up.raw_off = d_off + 4 * (nr + 1);
-        up.ctg = a.d_ctg; up.n_ctg = a.n_ctg;
-        up.refs = w->in_refs.as<uint8_t>(); up.ref_off = d_off;
-        up.seqs = w->in_seqs.as<uint8_t>(); up.seq_off = d_off + (nr + 1);
-        up.cigs = w->in_cigs.as<char>(); up.cig_off = d_off + 2 * (nr + 1);
-        up.n_reads = nr;
-        up.pass_mask = a.bam && a.bam->full ? a.bam->pass_mask : 0;
-        hipLaunchKernelGGL(unpack_records_kernel, dim3((unsigned)nr), dim3(256), 0, s, up);
+        hipLaunchKernelGGL(unpack_records_kernel, dim3((unsigned)nr), dim3(256), 0, s,
+                           wire_unpack(w, nr, a.d_ctg, a.n_ctg, a.bam ? a.bam->rec.pass_mask : PASS_NONE));
         HIP_TRY(hipGetLastError());
     }
     return NPORE_OK;
@@ -603,22 +633,7 @@ int post_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs &
     else hipLaunchKernelGGL(standardize_kernel, dim3((unsigned)nr), dim3(64), 0, s, sp);
     if (p.mode == OutMode::BamRecords) {          // the group's records behind those of the groups before it (bam_emit_kernels.hpp)
         if (p.g0 == 0) HIP_TRY(hipMemsetAsync(a.bam->d_cursor, 0, 8, s));
-        const int64_t *d_off = w->in_off.as<int64_t>();
-        BamEmitParams bp;
-        bp.raw = w->in_raw.as<uint8_t>(); bp.raw_off = d_off + 4 * (nr + 1);
-        bp.ref_off = d_off; bp.seq_off = d_off + (nr + 1);
-        bp.hp = w->in_hp.as<int64_t>();
-        bp.words = sp.out; bp.words_off = sp.out_off; bp.words_len = sp.out_len; bp.status = sp.status;
-        bp.read_base = out.read_base; bp.n_reads = nr;
-        bp.recs = a.bam->d_recs; bp.cap = a.bam->cap; bp.cursor = a.bam->d_cursor;
-        bp.rec_off = w->rec_off.as<int64_t>(); bp.rec_len = w->rec_len.as<int64_t>();
-        if (a.bam->full) {                    // FULL records: NM from the code arrays the standardisation probed, then the same two steps
-            bp.refs = sp.refs; bp.seqs = sp.seqs; bp.nm = w->nm.as<int32_t>();
-            bp.pass_mask = a.bam->pass_mask;
-            if (a.bam->md) bp.md_len = w->md_len.as<int32_t>();      // (MD: its size in front of the placement, its text behind the record)
-            if (a.bam->tags) { bp.tags = a.bam->tags; bp.cs_len = w->cs_len.as<int32_t>(); bp.de = w->de_val.as<float>(); }      // (cs / de: the same)
-        }
-        launch_bam_emit(bp, a.bam->full, s);
+        launch_bam_emit(wire_bam_emit(w, nr, a.bam->d_recs, a.bam->cap, a.bam->d_cursor, a.bam->rec), a.bam->rec.full, s);
         if (a.bam->deflate && p.g1 == a.n_reads) launch_deflate(a.bam->dfl, s);      // the batch's records are complete
     } else if (p.mode == OutMode::CompactText) {  // the texts to the front of the batch's compact buffer (unpack_kernels.hpp)
         if (p.g0 == 0) HIP_TRY(hipMemsetAsync(a.compact->d_cursor, 0, 8, s));

@@ -360,7 +360,7 @@ inline int bam_dump_inflated(const npore_bam *b, const char *path)
 }
 
 inline int64_t bam_select(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
-                          int64_t max_reads, int64_t *out_idx, int64_t cap, uint32_t drop_flags = PASS_FLAGS, uint32_t pass_mask = 0)
+                          int64_t max_reads, int64_t *out_idx, int64_t cap, uint32_t drop_flags = PASS_FLAGS, uint32_t pass_mask = PASS_NONE)
 {
     // pass_mask (staged_head.hpp): records with one of these flag bits are kept, to pass through; such a record without a
     // reference length (a placed, unmapped one has no CIGAR) overlaps as if its length were 1, as htslib has it
@@ -454,7 +454,7 @@ inline int fetch_records(const npore_bam *b, const int64_t *idx, int64_t n, int 
     return NPORE_OK;
 }
 // pass_mask: a record that passes (staged_head.hpp) gives align() nothing -- its three slices are empty
-inline void pack_sizes_of(const RecFetch &rf, int64_t n, int64_t *ref_off, int64_t *seq_off, int64_t *cig_off, int threads = 0, uint32_t pass_mask = 0)
+inline void pack_sizes_of(const RecFetch &rf, int64_t n, int64_t *ref_off, int64_t *seq_off, int64_t *cig_off, int threads, uint32_t pass_mask)
 {
     // per read (a 10 kb read has thousands of CIGAR operations: all cores), then the prefix sums
     ref_off[0] = seq_off[0] = cig_off[0] = 0;
@@ -481,7 +481,7 @@ inline void pack_sizes_of(const RecFetch &rf, int64_t n, int64_t *ref_off, int64
 
 inline int pack_records(const npore_bam *b, const RecFetch &rf, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n,
                  uint8_t *refs, const int64_t *ref_off, uint8_t *seqs, const int64_t *seq_off, char *cigs,
-                 const int64_t *cig_off, int threads, bool for_upload = false, uint32_t pass_mask = 0)
+                 const int64_t *cig_off, int threads, bool for_upload, uint32_t pass_mask)
 {
     std::atomic<int> bad{0};
     parallel_for(n, threads, [&](int64_t k) {
@@ -823,61 +823,39 @@ inline int64_t nm_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t 
     if (ops < 0) return -1;
     return nm_of_words(cigar_text_words(t, n, ops).data(), ops, ref, rl, seq, sl);
 }
-// MD (md_rec.hpp) of a final CIGAR text over the read's code arrays, sized and then written; false: no CIGAR text
-inline bool md_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, std::string &md)
+// MD (md_rec.hpp) of a final CIGAR's `ops` words over the read's code arrays, sized and then written
+inline void md_of_words(const uint8_t *w, int64_t ops, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, std::string &md)
 {
-    const int64_t ops = cigar_text_ops(t, n);
-    if (ops < 0) return false;
-    const std::vector<uint8_t> words = cigar_text_words(t, n, ops);
-    md.assign((size_t)md_size_of_words(words.data(), ops, ref, rl, seq, sl), '\0');
-    md_into_words(words.data(), ops, ref, rl, seq, sl, reinterpret_cast<uint8_t *>(&md[0]), (int64_t)md.size());
-    return true;
+    md.assign((size_t)md_size_of_words(w, ops, ref, rl, seq, sl), '\0');
+    md_into_words(w, ops, ref, rl, seq, sl, reinterpret_cast<uint8_t *>(&md[0]), (int64_t)md.size());
 }
-// cs (cs_rec.hpp; lng: the long form) of a final CIGAR text over the read's code arrays, sized and then written; false: no
-// CIGAR text
-inline bool cs_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, bool lng, std::string &cs)
-{
-    const int64_t ops = cigar_text_ops(t, n);
-    if (ops < 0) return false;
-    const std::vector<uint8_t> words = cigar_text_words(t, n, ops);
-    cs.assign((size_t)cs_size_of_words(words.data(), ops, ref, rl, seq, sl, lng), '\0');
-    cs_into_words(words.data(), ops, ref, rl, seq, sl, lng, reinterpret_cast<uint8_t *>(&cs[0]), (int64_t)cs.size());
-    return true;
-}
-// de (cs_rec.hpp) of the same, from the size pass's counts; false: no CIGAR text
-inline bool de_of_text(const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, float &de)
-{
-    const int64_t ops = cigar_text_ops(t, n);
-    if (ops < 0) return false;
-    CsCounts c;
-    cs_size_of_words(cigar_text_words(t, n, ops).data(), ops, ref, rl, seq, sl, false, &c);
-    de = de_of_counts(c.e, c.x, c.g);
-    return true;
-}
-// the bytes of the cs and de tags (NPORE_TAG_*) as they follow MD in a FULL record
-inline void cs_de_tags_of_text(int tags, const char *t, int64_t n, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, std::string &out)
+// the bytes of the cs and de tags (NPORE_TAG_*; cs_rec.hpp) of the same as they follow MD in a FULL record: cs sized and then
+// written, de from the size pass's counts
+inline void cs_de_tags_of_words(int tags, const uint8_t *w, int64_t ops, const uint8_t *ref, int64_t rl, const uint8_t *seq, int64_t sl, std::string &out)
 {
     out.clear();
-    std::string cs;
-    if ((tags & NPORE_TAG_CS) && cs_of_text(t, n, ref, rl, seq, sl, (tags & NPORE_TAG_CS_LONG) != 0, cs)) {
-        out.append("csZ").append(cs);
-        out.push_back('\0');
+    if (tags & NPORE_TAG_CS) {
+        const bool lng = (tags & NPORE_TAG_CS_LONG) != 0;
+        const int64_t size = cs_size_of_words(w, ops, ref, rl, seq, sl, lng);
+        out.assign("csZ").append((size_t)size + 1, '\0');
+        cs_into_words(w, ops, ref, rl, seq, sl, lng, reinterpret_cast<uint8_t *>(&out[3]), size);
     }
-    float de = 0.0f;
-    if ((tags & NPORE_TAG_DE) && de_of_text(t, n, ref, rl, seq, sl, de)) {
+    if (tags & NPORE_TAG_DE) {
+        CsCounts c;
+        cs_size_of_words(w, ops, ref, rl, seq, sl, false, &c);
+        const float de = de_of_counts(c.e, c.x, c.g);
         char v[4];
         std::memcpy(v, &de, 4);
         out.append("def").append(v, 4);
     }
 }
-// bam_record_into's twin for the FULL RECORD; nm: the read's NM (nm_of_text); md: its MD text (md_of_text), or none; more: the
-// bytes of its cs and de tags (cs_de_tags_of_text), or none
-inline int64_t bam_record_full_into(const RecView &r, const char *final_text, int64_t final_len, int32_t status, int64_t nm, uint8_t *dst,
-                                    BamRecMeta *meta = nullptr, const std::string *md = nullptr, const std::string *more = nullptr)
+// bam_record_into's twin for the FULL RECORD over the final CIGAR's n_fin words (< 0: the text was no CIGAR); nm: the read's NM
+// (nm_of_words); md: its MD text (md_of_words), or none; more: the bytes of its cs and de tags (cs_de_tags_of_words), or none
+inline int64_t bam_record_full_words_into(const RecView &r, const uint8_t *fin_words, int64_t n_fin, int32_t status, int64_t nm, uint8_t *dst,
+                                          BamRecMeta *meta = nullptr, const std::string *md = nullptr, const std::string *more = nullptr)
 {
     if (status & NPORE_ST_BAD_INPUT) return 0;
     const RecCigar in_cg = rec_cigar(r);
-    const int64_t n_fin = cigar_text_ops(final_text, final_len);
     if (n_fin < 0 || nm < 0) return -1;
     uint32_t ci, cj;
     full_clip_words(in_cg, ci, cj);
@@ -910,16 +888,8 @@ inline int64_t bam_record_full_into(const RecView &r, const char *final_text, in
     }
     std::memcpy(o, in_cg.w, 4 * (size_t)ci);
     o += 4 * (size_t)ci;
-    {
-        uint32_t len = 0;
-        for (int64_t q = 0; q < final_len; q++) {
-            const char c = final_text[q];
-            if (c >= '0' && c <= '9') { len = len * 10 + (uint32_t)(c - '0'); continue; }
-            w32(o, len << 4 | cigar_op_code(c));
-            o += 4;
-            len = 0;
-        }
-    }
+    std::memcpy(o, fin_words, 4 * (size_t)n_fin);
+    o += 4 * (size_t)n_fin;
     std::memcpy(o, in_cg.w + 4 * (size_t)cj, 4 * (size_t)(in_cg.n - cj));
     o = seq_at;
     std::memcpy(o, r.seq(), (size_t)(nb + l_seq));
@@ -939,29 +909,39 @@ inline int64_t bam_record_full_into(const RecView &r, const char *final_text, in
     if (meta) *meta = BamRecMeta{r.ref_id(), r.pos(), reflen, size};
     return size;
 }
-// the code arrays of a batch's reads (what align() got): FULL records count NM from them, and write MD (md) and cs / de
-// (tags: NPORE_TAG_*) from them
+// ... of a single read's final CIGAR TEXT (one tag or one record is wanted: the sanitizer programs; a batch goes through
+// format_bam_into, which parses each text once)
+inline int64_t bam_record_full_into(const RecView &r, const char *final_text, int64_t final_len, int32_t status, int64_t nm, uint8_t *dst)
+{
+    const int64_t n_fin = cigar_text_ops(final_text, final_len);
+    if ((status & NPORE_ST_BAD_INPUT) || n_fin < 0) return (status & NPORE_ST_BAD_INPUT) ? 0 : -1;
+    return bam_record_full_words_into(r, cigar_text_words(final_text, final_len, n_fin).data(), n_fin, status, nm, dst);
+}
+// The records a batch writes (rec), and for FULL records the code arrays of its reads (what align() got): NM is counted from
+// them, MD and cs / de written from them; the slices of a record that passes are empty
 struct ReadCodes {
-    const uint8_t *refs; const int64_t *ref_off;
-    const uint8_t *seqs; const int64_t *seq_off;
-    bool md = false;
-    int tags = 0;
-    uint32_t pass_mask = 0;        // records that pass (staged_head.hpp): written as they came, their slices above are empty
+    RecSpec rec;
+    const uint8_t *refs = nullptr; const int64_t *ref_off = nullptr;
+    const uint8_t *seqs = nullptr; const int64_t *seq_off = nullptr;
 };
 
 // format_sam_into's twin for BAM records: the kept reads' records one after the other in `out`, *out_len bytes;
 // meta (may be null): one entry per WRITTEN record, in order
 inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, const char *finals, const int64_t *final_off,
                            const int64_t *final_len, const int32_t *status, int threads, RawBuf &out, int64_t *out_len,
-                           std::vector<BamRecMeta> *meta, const ReadCodes *full = nullptr)
+                           std::vector<BamRecMeta> *meta, const ReadCodes &codes)
 {
     if (!b || n < 0 || !out_len || (n > 0 && (!finals || !final_off || !final_len || !status)))
         return fail(NPORE_E_INVALID, "bad argument");
-    std::vector<int64_t> off((size_t)n + 1, 0), nm(full ? (size_t)n : 0, 0);
-    std::vector<std::string> md(full && full->md ? (size_t)n : 0), more(full && full->tags ? (size_t)n : 0);
+    const RecSpec &rec = codes.rec;
+    std::vector<int64_t> off((size_t)n + 1, 0), nm(rec.full ? (size_t)n : 0, 0);
+    // (FULL records: a read's final CIGAR text becomes words ONCE -- NM, MD, cs, de and the record all take the words, counted
+    // and written between the two passes; a text that is no CIGAR leaves the read's vector empty: -1 words)
+    std::vector<std::vector<uint8_t>> words(rec.full ? (size_t)n : 0);
+    auto n_words = [&](int64_t k) { return (int64_t)words[(size_t)k].size() / 4 - 1; };
+    std::vector<std::string> md(rec.md ? (size_t)n : 0), more(rec.tags ? (size_t)n : 0);
     std::atomic<int> bad{0};
-    // (full: the FULL RECORD, its NM counted and its MD, cs and de written once, between the two passes)
-    const uint32_t pass_mask = full ? full->pass_mask : 0;
+    const uint32_t pass_mask = rec.pass_mask;
     // a record that passes: the input's bytes; the index gets the input record's own reference length
     auto passed = [&](int64_t k, uint8_t *dst, BamRecMeta *m) -> int64_t {
         const RecView r = rec_of(rf, k);
@@ -972,17 +952,20 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     };
     auto record = [&](int64_t k, uint8_t *dst, BamRecMeta *m) {
         if (staged_passes(rec_of(rf, k).p, pass_mask)) return passed(k, dst, m);
-        return full ? bam_record_full_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], nm[(size_t)k], dst, m,
-                                           full->md ? &md[(size_t)k] : nullptr, full->tags ? &more[(size_t)k] : nullptr)
-                    : bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], dst, m);
+        return rec.full ? bam_record_full_words_into(rec_of(rf, k), words[(size_t)k].data(), n_words(k), status[k], nm[(size_t)k], dst, m,
+                                                     rec.md ? &md[(size_t)k] : nullptr, rec.tags ? &more[(size_t)k] : nullptr)
+                        : bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], dst, m);
     };
     parallel_for(n, threads, [&](int64_t k) {
-        if (full && !(status[k] & NPORE_ST_BAD_INPUT) && !staged_passes(rec_of(rf, k).p, pass_mask)) {
-            const uint8_t *ref = full->refs + full->ref_off[k], *seq = full->seqs + full->seq_off[k];
-            const int64_t rl = full->ref_off[k + 1] - full->ref_off[k], sl = full->seq_off[k + 1] - full->seq_off[k];
-            nm[(size_t)k] = nm_of_text(finals + final_off[k], final_len[k], ref, rl, seq, sl);
-            if (full->md) md_of_text(finals + final_off[k], final_len[k], ref, rl, seq, sl, md[(size_t)k]);
-            if (full->tags) cs_de_tags_of_text(full->tags, finals + final_off[k], final_len[k], ref, rl, seq, sl, more[(size_t)k]);
+        const int64_t ops = rec.full && !(status[k] & NPORE_ST_BAD_INPUT) && !staged_passes(rec_of(rf, k).p, pass_mask)
+                                ? cigar_text_ops(finals + final_off[k], final_len[k]) : -1;
+        if (ops >= 0) {
+            const uint8_t *w = (words[(size_t)k] = cigar_text_words(finals + final_off[k], final_len[k], ops)).data();
+            const uint8_t *ref = codes.refs + codes.ref_off[k], *seq = codes.seqs + codes.seq_off[k];
+            const int64_t rl = codes.ref_off[k + 1] - codes.ref_off[k], sl = codes.seq_off[k + 1] - codes.seq_off[k];
+            nm[(size_t)k] = nm_of_words(w, ops, ref, rl, seq, sl);
+            if (rec.md) md_of_words(w, ops, ref, rl, seq, sl, md[(size_t)k]);
+            if (rec.tags) cs_de_tags_of_words(rec.tags, w, ops, ref, rl, seq, sl, more[(size_t)k]);
         }
         const int64_t sz = record(k, nullptr, nullptr);
         if (sz < 0) bad++;
@@ -1445,7 +1428,7 @@ inline int one_pass_args_check(const npore_bam *b, int n_regions, const int32_t 
 class BamRecordWalker {
 public:
     BamRecordWalker(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
-                    int64_t max_reads, int threads, uint32_t drop_flags = PASS_FLAGS, BgzfInflateFn inflate = nullptr, uint32_t pass_mask = 0)
+                    int64_t max_reads, int threads, uint32_t drop_flags = PASS_FLAGS, BgzfInflateFn inflate = nullptr, uint32_t pass_mask = PASS_NONE)
         : b_(b), src_(b, threads, std::move(inflate)), n_regions_(n_regions), ref_id_(ref_id), start_(start), stop_(stop), max_reads_(max_reads),
           drop_flags_(drop_flags & ~pass_mask), pass_mask_(pass_mask), done_(n_regions == 0)
     {

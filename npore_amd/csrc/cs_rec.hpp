@@ -1,6 +1,6 @@
 // cs_rec.hpp -- the cs and de tags of a realigned read (BAM out, FULL records with NPORE_TAG_CS / NPORE_TAG_DE): the rule, stated
 // ONCE and compiled for the gfx950 kernels (bam_emit_kernels.hpp cs_size_kernel / emit_cs_kernel) and for the host twin
-// (bam_reader.hpp cs_of_text / de_of_text, plain g++), the way md_rec.hpp and nm_rec.hpp are.
+// (bam_reader.hpp cs_de_tags_of_words, plain g++), the way md_rec.hpp and nm_rec.hpp are.
 //
 // Both are written over the read's FINAL CIGAR words (`len << 4 | op`, the clip words excluded as for NM and MD) on the two code
 // arrays align() got ('NACGT-' -> 0 ... 5, anything else 0), with nm_rec.hpp's nm_consumes / nm_compares / nm_differs, so NM,

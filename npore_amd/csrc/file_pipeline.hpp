@@ -73,11 +73,11 @@ DeflateParams slot_deflate_params(npore_batch_slot &s, const uint8_t *d_recs, co
 }
 
 // npore_bam_set_output holds for ONE run: the run that writes takes the setting and leaves the default behind
-struct OutputSetting { int format, flags, tags; std::string bai; int pass; };
+struct OutputSetting { int format, flags; std::string bai; RecSpec rec; };
 OutputSetting take_output_setting(npore_bam *b)
 {
-    OutputSetting o{b->out_format, b->out_flags, b->out_tags, b->out_bai, b->out_pass};
-    b->out_format = NPORE_OUT_SAM; b->out_flags = 0; b->out_tags = 0; b->out_pass = 0; b->out_bai.clear();
+    OutputSetting o{b->out_format, b->out_flags, b->out_bai, b->out_rec};
+    b->out_format = NPORE_OUT_SAM; b->out_flags = 0; b->out_rec = RecSpec{}; b->out_bai.clear();
     std::fill(b->out_info, b->out_info + 4, 0);
     return o;
 }
@@ -86,16 +86,14 @@ OutputSetting take_output_setting(npore_bam *b)
 struct PipeMode {
     bool glue = false;           // realign_read's glue on the device: the slots receive the final CIGAR text
     bool dpack = false;          // ... and align()'s inputs unpacked from the records on the device (the host glue needs the base arrays on the host)
-    bool bam = false, full = false;     // BAM records out instead of SAM text; NPORE_OUT_FULL: FULL records
-    bool md = false;             // ... NPORE_OUT_MD: with the MD tag behind NM
-    int tags = 0;                // ... NPORE_TAG_*: with cs / de behind that
+    bool bam = false;            // BAM records out instead of SAM text ...
+    RecSpec rec;                 // ... which records (hostio.hpp; the run's: RunOutput::open)
     int deflate = 0;             // the writer's DEFLATE_MODE_*, 0: stored members
-    uint32_t pass_mask = 0;      // ... npore_bam_set_output_pass (FULL records only): records with these flag bits pass through
     // BAM mode: the records are built on the device where the default pipeline runs (device pack + device glue:
     // bam_emit_kernels.hpp); with the host glue or the host pack the host twin makes them (format_bam_into)
     bool dev_records() const { return bam && dpack; }
     bool dev_deflate() const { return dev_records() && deflate != 0; }      // ... and coded into whole members there too (bam_deflate_kernels.hpp)
-    int stage_form() const { return !bam ? STAGE_HEAD : full ? STAGE_FULL : STAGE_QUALS; }      // of the device pack's record heads
+    int stage_form() const { return !bam ? STAGE_HEAD : rec.full ? STAGE_FULL : STAGE_QUALS; }      // of the device pack's record heads
 };
 
 // Where a file run's output goes: the SAM text's FILE, or (npore_bam_set_output) the BAM writer
@@ -103,17 +101,12 @@ struct RunOutput {
     FILE *fh = nullptr;
     std::unique_ptr<BgzfStoredWriter> bw;
     npore_bam *b = nullptr;
-    bool full = false, md = false;      // NPORE_OUT_FULL, NPORE_OUT_MD
-    int tags = 0;                       // NPORE_TAG_*
-    uint32_t pass_mask = 0;             // npore_bam_set_output_pass
+    RecSpec rec;                        // the records the run writes, as the setters built them (rec_spec_of)
     int open(npore_bam *bam, const char *out_path, int threads)
     {
         b = bam;
         const OutputSetting o = take_output_setting(b);
-        full = o.format == NPORE_OUT_BAM && (o.flags & NPORE_OUT_FULL) != 0;
-        md = full && (o.flags & NPORE_OUT_MD) != 0;
-        tags = full ? o.tags : 0;
-        pass_mask = full ? (uint32_t)o.pass : 0;
+        rec = o.rec;
         if (o.format == NPORE_OUT_BAM) {
             bw.reset(new BgzfStoredWriter());
             return bw->open(out_path, b->ref_names.size(), o.bai.empty() ? nullptr : o.bai.c_str(), (o.flags & NPORE_OUT_EOF) != 0,
@@ -147,7 +140,11 @@ PipeMode pipe_mode(const npore_ctx *ctx, const RunOutput &out)      // (NPORE_DE
 {
     const char *e = std::getenv("NPORE_DEVICE_PACK");
     const bool glue = ctx->device_glue != 0, dpack = glue && ctx->device_pack != 0 && !(e && std::atoi(e) == 0);
-    return PipeMode{glue, dpack, out.bw != nullptr, out.full, out.md, out.tags, out.bw ? out.bw->deflate_mode() : 0, out.pass_mask};
+    PipeMode pm;
+    pm.glue = glue; pm.dpack = dpack;
+    pm.bam = out.bw != nullptr; pm.rec = out.rec;
+    pm.deflate = out.bw ? out.bw->deflate_mode() : 0;
+    return pm;
 }
 
 // The FASTA on the device (once per FASTA and context) and, per BAM reference, where its contig lies there.
@@ -182,7 +179,7 @@ void slot_pack_sizes(npore_batch_slot &s, int threads, const PipeMode &pm)
     for (auto *v : {&s.ro, &s.so, &s.co, &s.oo, &s.fo}) v->assign(n + 1, 0);
     s.olen.assign(n, 0);
     s.flen.assign(n, 0);
-    pack_sizes_of(s.rf, s.m, s.ro.data(), s.so.data(), s.co.data(), threads, pm.pass_mask);
+    pack_sizes_of(s.rf, s.m, s.ro.data(), s.so.data(), s.co.data(), threads, pm.rec.pass_mask);
     for (size_t k = 0; k < n; k++) {
         const int64_t cap = (s.ro[k + 1] - s.ro[k]) + (s.so[k + 1] - s.so[k]);
         s.oo[k + 1] = s.oo[k] + (!pm.glue ? cap : (pm.dev_records() ? 4 : 2) * cap + 16);
@@ -198,7 +195,7 @@ int slot_pack_arrays(const npore_bam *b, const npore_fasta *fa, const int32_t *f
     if ((rce = s.refs.ensure((size_t)s.ro[n] + 64)) || (rce = s.seqs.ensure((size_t)s.so[n] + 64)) || (rce = s.cigs.ensure((size_t)s.co[n] + 64))) return rce;
     if (!fa || !fasta_of_ref) return fail(NPORE_E_INVALID, "bad argument");
     if (int rc = pack_records(b, s.rf, fa, fasta_of_ref, s.m, reinterpret_cast<uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<uint8_t *>(s.seqs.p),
-                              s.so.data(), s.cigs.p, s.co.data(), threads, true, pm.pass_mask)) return rc;
+                              s.so.data(), s.cigs.p, s.co.data(), threads, true, pm.rec.pass_mask)) return rc;
     // (device glue: the texts come back compacted -- slot_enqueue --, neither a page-locked copy of the slots nor the host glue's finals)
     if (pm.glue) return NPORE_OK;
     if (int rc = s.alns.ensure((size_t)s.oo[n] + 64)) return rc;
@@ -208,14 +205,9 @@ int slot_pack_arrays(const npore_bam *b, const npore_fasta *fa, const int32_t *f
 // name, CIGAR words, 4-bit bases -- about half of a record; qualities and tags are not needed on the device) copied one
 // after the other into the slot's page-locked buffer; unpack_kernels.hpp does the rest per group.
 // BAM mode: each record up to the end of its QUALITIES (the tags stay on the host), the reads' HP values, and the bound of the
-// batch's record bytes.
-// FULL records: the kept aux bytes behind the qualities (STAGE_FULL) and their number in the HP values' place; the
-// bound grows by the clips' bases, four clip words, the kept aux and NM; with MD by 4 + 3 * reflen + 11 (three bytes per
-// reference position is the worst text, `0^A` repeated -- `0A` takes two per compared position --, and the closing count
-// has at most 10 digits); with cs by 4 + 3 * (reflen + seqlen) -- no item of the text has more than three bytes per base it
-// covers (cs_rec.hpp, Size) --, with de by 7.
-// A record that passes (PipeMode::pass_mask, staged_head.hpp): the block_size word and the whole record are staged, and the
-// bound grows by exactly those 4 + block_size bytes -- an ML-like array of tens of kilobytes included.
+// batch's record bytes, s.rec_cap (its terms: hostio.hpp).
+// FULL records: the kept aux bytes behind the qualities (STAGE_FULL) and their number in the HP values' place.
+// A record that passes (RecSpec::pass_mask, staged_head.hpp): the block_size word and the whole record are staged.
 int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, int threads, npore_batch_slot &s, const PipeMode &pm)
 {
     const int64_t n = s.m;
@@ -228,22 +220,20 @@ int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta
         const int32_t rid = r.ref_id();
         const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
         if (fi < 0 || fi >= n_fasta) return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
-        if (pm.full && staged_passes(r.p, pm.pass_mask)) {
+        if (staged_passes(r.p, pm.rec.pass_mask)) {
             s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_pass_bytes(r.p);
             reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = 0;
             s.rec_cap += staged_pass_bytes(r.p);
             continue;
         }
-        const int64_t aux = pm.full ? filter_aux(r.aux(), r.end(), nullptr) : 0;
+        const int64_t aux = pm.rec.full ? filter_aux(r.aux(), r.end(), nullptr) : 0;
         s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_head_bytes(r, rec_cigar(r), pm.bam ? STAGE_QUALS : STAGE_HEAD) + aux;
-        const int64_t cap = (s.ro[(size_t)k + 1] - s.ro[(size_t)k]) + (s.so[(size_t)k + 1] - s.so[(size_t)k]);
-        if (pm.bam) {
-            const int64_t sl = s.so[(size_t)k + 1] - s.so[(size_t)k];
-            reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = pm.full ? aux : rec_hp(r);
-            s.rec_cap += 36 + r.l_read_name() + 4 * cap + 16 + (sl + 1) / 2 + sl + 7 + 16;      // (+ 16: placeholder and CG tag head of a long final CIGAR)
-            if (pm.full) s.rec_cap += ((int64_t)r.l_seq() + 1) / 2 + r.l_seq() - (sl + 1) / 2 - sl + 16 + aux;
-            if (pm.md) s.rec_cap += 4 + 3 * (s.ro[(size_t)k + 1] - s.ro[(size_t)k]) + 11;
-            if (pm.tags) s.rec_cap += 4 + 3 * (s.ro[(size_t)k + 1] - s.ro[(size_t)k] + sl) + 7;
+        if (pm.bam) {          // (a final CIGAR has no more words than the read's reference positions and bases: the slot's size too)
+            const int64_t rl = s.ro[(size_t)k + 1] - s.ro[(size_t)k], sl = s.so[(size_t)k + 1] - s.so[(size_t)k];
+            reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = pm.rec.full ? aux : rec_hp(r);
+            s.rec_cap += pm.rec.full ? full_record_bound(r.l_read_name(), rl + sl, r.l_seq(), aux) : ref_record_bound(r.l_read_name(), rl + sl, sl);
+            if (pm.rec.md) s.rec_cap += md_tag_bound(rl, 1);
+            if (pm.rec.tags) s.rec_cap += cs_de_tags_bound(rl + sl);
         }
     }
     if (int rc = s.raw.ensure((size_t)s.rawo[(size_t)n] + 64)) return rc;
@@ -252,7 +242,7 @@ int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta
         for (int64_t k = t * per; k < std::min(n, (t + 1) * per); k++) {
             char *dst = s.raw.p + s.rawo[(size_t)k];
             const size_t len = (size_t)(s.rawo[(size_t)k + 1] - s.rawo[(size_t)k]);
-            stage_record_head(s.rf.ptr[(size_t)k], pm.stage_form(), reinterpret_cast<uint8_t *>(dst), pm.pass_mask);
+            stage_record(s.rf.ptr[(size_t)k], pm.stage_form(), reinterpret_cast<uint8_t *>(dst), pm.rec);
             cache_writeback(dst, len);         // page-locked staging about to cross PCIe: out of this core's cache first (hostio.hpp)
         }
     });
@@ -276,9 +266,11 @@ int slot_enqueue(npore_ctx *ctx, npore_batch_slot &s, const PipeMode &pm, const 
     if (pm.dev_records()) {
         if ((rc = s.d_recs.ensure((size_t)s.rec_cap + 64)) || (rc = s.d_cursor.ensure(64)) || (rc = s.ctext_pin.ensure(64)) ||
             (rc = s.reclen_pin.ensure((size_t)m * 8 + 64)) || (rc = s.total_pin.ensure(64))) return fail(rc, "batch buffers");
-        s.emit = BamEmit{s.d_recs.as<uint8_t>(), s.rec_cap, s.d_cursor.as<unsigned long long>(), reinterpret_cast<const int64_t *>(s.hp_pin.p),
-                         reinterpret_cast<int64_t *>(s.reclen_pin.p), reinterpret_cast<unsigned long long *>(s.total_pin.p)};
-        s.emit.full = pm.full; s.emit.md = pm.md; s.emit.tags = pm.tags; s.emit.pass_mask = pm.pass_mask;
+        s.emit = BamEmit{};
+        s.emit.rec = pm.rec;
+        s.emit.d_recs = s.d_recs.as<uint8_t>(); s.emit.cap = s.rec_cap; s.emit.d_cursor = s.d_cursor.as<unsigned long long>();
+        s.emit.h_hp = reinterpret_cast<const int64_t *>(s.hp_pin.p); s.emit.h_rec_len = reinterpret_cast<int64_t *>(s.reclen_pin.p);
+        s.emit.h_total = reinterpret_cast<unsigned long long *>(s.total_pin.p);
         if (pm.dev_deflate()) {
             if ((rc = slot_deflate_buffers(s, s.rec_cap, pm.deflate))) return fail(rc, "batch buffers");
             s.emit.dfl = slot_deflate_params(s, s.d_recs.as<uint8_t>(), s.d_cursor.as<unsigned long long>(), ctx->d_stream_pos.as<unsigned long long>(),
@@ -326,7 +318,7 @@ int slot_fetch_records(const int32_t *status, npore_batch_slot &s, const PipeMod
         if (len[k] == 0) continue;
         const RecView r = rec_of(s.rf, k);
         // (a record that passed gave align() no reference slice: the index takes the input record's own reference length)
-        const int64_t span = staged_passes(r.p, pm.pass_mask) ? rec_ref_len(r) : s.ro[(size_t)k + 1] - s.ro[(size_t)k];
+        const int64_t span = staged_passes(r.p, pm.rec.pass_mask) ? rec_ref_len(r) : s.ro[(size_t)k + 1] - s.ro[(size_t)k];
         s.meta.push_back(BamRecMeta{r.ref_id(), r.pos(), span, len[k]});
         sum += len[k];
     }
@@ -354,10 +346,9 @@ int slot_collect(const npore_bam *b, const int32_t *status, int threads, npore_b
 {
     if (pm.dev_records()) return slot_fetch_records(status, s, pm);
     const int64_t n = s.m;
-    const ReadCodes codes{reinterpret_cast<const uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<const uint8_t *>(s.seqs.p), s.so.data(), pm.md, pm.tags,
-                          pm.pass_mask};
+    const ReadCodes codes{pm.rec, reinterpret_cast<const uint8_t *>(s.refs.p), s.ro.data(), reinterpret_cast<const uint8_t *>(s.seqs.p), s.so.data()};
     auto format_into = [&](const char *finals, const int64_t *final_off) {          // (FULL records: NM and MD from the slot's code arrays)
-        return pm.bam ? format_bam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len, &s.meta, pm.full ? &codes : nullptr)
+        return pm.bam ? format_bam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len, &s.meta, codes)
                       : format_sam_into(b, s.rf, n, finals, final_off, s.flen.data(), status, threads, s.sam, &s.sam_len);
     };
     if (pm.glue) {          // the device has left the final CIGAR texts (standardize_kernel), compacted: the front of that buffer is here
@@ -438,10 +429,10 @@ int file_pipeline(npore_ctx *ctx, npore_bam *b, const npore_fasta *fa, const int
             if (timed(s.t_ms[1], [&] { return hipEventSynchronize(s.done); }) != hipSuccess) { s.err = "waiting for a batch failed"; return (int)NPORE_E_HIP; }
             mark("device done", k);
             std::memcpy(s.olen.data(), s.olen_pin.p, (size_t)s.m * 8);
-            if (pm.pass_mask) {          // NPORE_ST_PASSED: not realigned, written as it came (the device left these reads' status 0)
+            if (pm.rec.pass_mask) {          // NPORE_ST_PASSED: not realigned, written as it came (the device left these reads' status 0)
                 int32_t *st = reinterpret_cast<int32_t *>(s.st_pin.p);
                 for (int64_t q = 0; q < s.m; q++)
-                    if (staged_passes(rec_of(s.rf, q).p, pm.pass_mask)) st[q] |= NPORE_ST_PASSED;
+                    if (staged_passes(rec_of(s.rf, q).p, pm.rec.pass_mask)) st[q] |= NPORE_ST_PASSED;
             }
             double ms_std = 0.0, ms_all = 0.0;
             const int rcc = timed(ms_all, [&] { return (int)kept(s, slot_collect(b, status_of(s), post_threads, s, pm, &ms_std)); });

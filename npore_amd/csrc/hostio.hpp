@@ -39,6 +39,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/npore_amd.h"
 #include "glue.hpp"
 #include "staged_head.hpp"
 
@@ -541,6 +542,26 @@ struct BamRecMeta {
     int64_t span;                         // reference length
     int64_t bytes;                        // the record with its block_size word
 };
+// The record a run writes, from the setters through to the emit launch; the default: the reference's records.  Only
+// rec_spec_of makes another, so a spec without `full` has everything else zero wherever it is read.
+struct RecSpec {
+    bool full = false;                    // NPORE_OUT_FULL: FULL records (bam_reader.hpp FULL RECORD) ...
+    bool md = false;                      // ... NPORE_OUT_MD: with the MD tag behind NM
+    int tags = 0;                         // ... NPORE_TAG_*: with cs / de behind that
+    uint32_t pass_mask = 0;               // ... records with one of these flag bits pass through (staged_head.hpp)
+};
+// THE rules of the output options: defined bits only, CS_LONG beside CS, md / tags / pass on FULL records, FULL records in BAM
+inline bool rec_spec_of(int format, int flags, int tags, int pass, RecSpec &out)
+{
+    const int all_flags = NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE | NPORE_OUT_MATCH | NPORE_OUT_FULL | NPORE_OUT_MD;
+    const bool full = (flags & NPORE_OUT_FULL) != 0;
+    if ((flags & ~all_flags) || (tags & ~(NPORE_TAG_CS | NPORE_TAG_CS_LONG | NPORE_TAG_DE)) || (pass & ~(int)PASS_FLAGS) ||
+        ((tags & NPORE_TAG_CS_LONG) && !(tags & NPORE_TAG_CS)) || (!full && ((flags & NPORE_OUT_MD) || tags || pass)) ||
+        (full && format != NPORE_OUT_BAM))
+        return false;
+    out = RecSpec{full, (flags & NPORE_OUT_MD) != 0, tags, (uint32_t)pass};
+    return true;
+}
 }  // namespace npore
 
 // ---- handles ---------------------------------------------------------------------------------
@@ -575,9 +596,10 @@ struct npore_bam {
     uint64_t share_begin = 0, share_end = UINT64_MAX;
     size_t share_block = 0;               // the BGZF block share_begin lies in
     // npore_bam_set_output: what the NEXT file run on the handle writes (0 = SAM text, 1 = BAM records in stored BGZF
-    // members), where its .bai goes ("" = none), NPORE_OUT_* flags; out_info: what that run wrote (npore_bam_output_info)
-    int out_format = 0, out_flags = 0, out_tags = 0;
-    int out_pass = 0;                     // npore_bam_set_output_pass: the flag bits whose records pass through the next run (staged_head.hpp)
+    // members), where its .bai goes ("" = none), NPORE_OUT_* flags, the records (out_rec: the three setters build it);
+    // out_info: what that run wrote (npore_bam_output_info)
+    int out_format = 0, out_flags = 0;
+    npore::RecSpec out_rec;
     std::string out_bai;
     int64_t out_info[4] = {0, 0, 0, 0};
     int64_t inflate_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // the device inflation of the last run on the handle (npore_bam_inflate_info)
@@ -786,24 +808,22 @@ inline int64_t filter_aux(const uint8_t *q, const uint8_t *end, uint8_t *dst)
 // field, which no kernel reads (the emit kernel recomputes the bin).  stage_record_head() writes both halves for every
 // record; staged_cigar() (staged_head.hpp) is the one reader, on the device and on the host.
 enum : int { STAGE_HEAD = 0, STAGE_QUALS = 1, STAGE_FULL = 2 };      // (0 / 1: what `bool with_quals` used to say)
-// pass_mask (staged_head.hpp record_passes; STAGE_FULL only): a record that passes is staged verbatim -- the block_size word
-// and the whole record as it lies in the stream, every tag, a long CIGAR still placeholder + CG tag, n_cigar_op and bin untouched
+constexpr uint32_t PASS_NONE = 0;      // the mask under which nothing passes (staged_head.hpp record_passes)
 inline int64_t staged_head_bytes(const RecView &r, const RecCigar &cg, int form)
 {
     return 4 + 32 + (int64_t)r.l_read_name() + 4 * (int64_t)cg.n + (int64_t)((form != STAGE_HEAD ? r.aux() : r.qual()) - r.seq()) +
            (form == STAGE_FULL ? filter_aux(r.aux(), r.end(), nullptr) : 0);
 }
-inline int64_t staged_head_bytes(const uint8_t *rec, int form, uint32_t pass_mask = 0)
+// A READ's head -- nothing passes here: the recount, the purity run, and a run's reads below
+inline int64_t staged_head_bytes(const uint8_t *rec, int form)
 {
     const RecView r = rec_view(rec);
-    if (form == STAGE_FULL && staged_passes(r.p, pass_mask)) return staged_pass_bytes(r.p);
     return staged_head_bytes(r, rec_cigar(r), form);
 }
-// rec: the record, block_size word first; dst: staged_head_bytes(rec, form, pass_mask) bytes
-inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst, uint32_t pass_mask = 0)
+// rec: the record, block_size word first; dst: staged_head_bytes(rec, form) bytes
+inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst)
 {
     const RecView r = rec_view(rec);
-    if (form == STAGE_FULL && staged_passes(r.p, pass_mask)) { std::memcpy(dst, rec, (size_t)staged_pass_bytes(r.p)); return; }
     const RecCigar cg = rec_cigar(r);
     const size_t fixed = 4 + 32 + (size_t)r.l_read_name(), tail = (size_t)((form != STAGE_HEAD ? r.aux() : r.qual()) - r.seq());
     if (cg.w == r.cigar()) std::memcpy(dst, rec, fixed + 4 * (size_t)cg.n + tail);
@@ -816,6 +836,31 @@ inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst, uint32
     dst[4 + 10] = (uint8_t)(cg.n >> 16); dst[4 + 11] = (uint8_t)(cg.n >> 24);      // bin: the count's high half
     dst[4 + 12] = (uint8_t)cg.n; dst[4 + 13] = (uint8_t)(cg.n >> 8);
 }
+// A RUN's record under its spec (there is no default: a run names what it writes).  A record that passes (staged_head.hpp
+// record_passes; STAGE_FULL only) is staged verbatim -- the block_size word and the whole record as it lies in the stream, every
+// tag, a long CIGAR still placeholder + CG tag, n_cigar_op and bin untouched; every other record is a read: its head
+inline int64_t staged_record_bytes(const uint8_t *rec, int form, const RecSpec &spec)
+{
+    return form == STAGE_FULL && staged_passes(rec + 4, spec.pass_mask) ? staged_pass_bytes(rec + 4) : staged_head_bytes(rec, form);
+}
+inline void stage_record(const uint8_t *rec, int form, uint8_t *dst, const RecSpec &spec)
+{
+    if (form == STAGE_FULL && staged_passes(rec + 4, spec.pass_mask)) std::memcpy(dst, rec, (size_t)staged_pass_bytes(rec + 4));
+    else stage_record_head(rec, form, dst);
+}
+
+// ---- the record buffer's bound: what one read's record takes at the most, term by term ---------------------------------
+// The reference's record over `words` final CIGAR words and `sl` unclipped bases: fixed fields, name, words, bases,
+// qualities, HP (+ 16: placeholder and CG tag head of a long final CIGAR).  The FULL record instead carries all l_seq
+// bases, up to four clip words and the kept aux, and NM for HP.  MD: three bytes per reference position covered is the
+// worst text, `0^A` repeated -- `0A` takes two per compared position --, and each of its `counts` numbers has at most 10
+// digits (a batch's own finals cover the read's reference: one closing count; a caller's words may not: one per word).
+// cs: no item of the text has more than three bytes per base it covers (cs_rec.hpp, Size); de: 7.  A record that passes
+// takes exactly its staged_pass_bytes (staged_head.hpp) -- an ML-like array of tens of kilobytes included.
+inline int64_t ref_record_bound(int64_t name, int64_t words, int64_t sl) { return 36 + name + 4 * words + 16 + (sl + 1) / 2 + sl + 7 + 16; }
+inline int64_t full_record_bound(int64_t name, int64_t words, int64_t l_seq, int64_t aux) { return 36 + name + 4 * words + 32 + (l_seq + 1) / 2 + l_seq + aux + 7 + 16; }
+inline int64_t md_tag_bound(int64_t ref_covered, int64_t counts) { return 4 + 3 * ref_covered + 11 * counts; }
+inline int64_t cs_de_tags_bound(int64_t bases_covered) { return 4 + 3 * bases_covered + 7; }
 
 // integer HP tag or 0 (src/bam.pyx:46)
 inline int64_t rec_hp(const RecView &r)

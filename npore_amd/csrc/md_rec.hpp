@@ -1,6 +1,6 @@
 // md_rec.hpp -- the MD tag of a realigned read (BAM out, FULL records with NPORE_OUT_MD): the rule, stated ONCE and compiled
 // for the gfx950 kernels (bam_emit_kernels.hpp md_size_kernel / emit_md_kernel) and for the host twin (bam_reader.hpp
-// md_of_text, plain g++), the way nm_rec.hpp, purity_rec.hpp and confusion_rec.hpp are.
+// md_of_words, plain g++), the way nm_rec.hpp, purity_rec.hpp and confusion_rec.hpp are.
 //
 // MD is written over the read's FINAL CIGAR words (`len << 4 | op`) on the two code arrays align() got ('NACGT-' -> 0 ... 5,
 // anything else 0), with nm_rec.hpp's nm_consumes / nm_compares / nm_differs, so NM and MD cannot disagree (the sequential

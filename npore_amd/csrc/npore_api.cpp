@@ -1442,7 +1442,7 @@ try {
     if (!pack_args_ok(b, idx, n) || !ref_off || !seq_off || !cig_off) return fail(NPORE_E_INVALID, "bad argument");
     RecFetch rf;          // (local to the call: the handle is const here, and two threads may size / pack from one handle)
     if (int rc = fetch_records(b, idx, n, 0, rf)) return rc;
-    pack_sizes_of(rf, n, ref_off, seq_off, cig_off, 0, (uint32_t)b->out_pass);      // (a record that passes has empty slices)
+    pack_sizes_of(rf, n, ref_off, seq_off, cig_off, 0, b->out_rec.pass_mask);      // (a record that passes has empty slices)
     return NPORE_OK;
 }
 NPORE_CATCH_INT
@@ -1456,7 +1456,7 @@ try {
         return fail(NPORE_E_INVALID, "bad argument");
     RecFetch rf;
     if (int rc = fetch_records(b, idx, n, threads, rf)) return rc;
-    return pack_records(b, rf, fa, fasta_of_ref, n, refs, ref_off, seqs, seq_off, cigs, cig_off, threads, false, (uint32_t)b->out_pass);
+    return pack_records(b, rf, fa, fasta_of_ref, n, refs, ref_off, seqs, seq_off, cigs, cig_off, threads, false, b->out_rec.pass_mask);
 }
 NPORE_CATCH_INT
 
@@ -1476,7 +1476,7 @@ int npore_bam_format_bam(npore_bam *b, const int64_t *idx, int64_t n, const char
 try {
     if (!pack_args_ok(b, idx, n) || !recs) return fail(NPORE_E_INVALID, "bad argument");
     if (int rc = fetch_records(b, idx, n, threads, b->api_fetch)) return rc;
-    const int rc = format_bam_into(b, b->api_fetch, n, finals, final_off, final_len, status, threads, b->recs, recs_len, nullptr);
+    const int rc = format_bam_into(b, b->api_fetch, n, finals, final_off, final_len, status, threads, b->recs, recs_len, nullptr, ReadCodes{});
     *recs = reinterpret_cast<const uint8_t *>(b->recs.p);
     return rc;
 }
@@ -1488,7 +1488,7 @@ struct PackedCodes {
     std::vector<int64_t> ro, so, co;
     std::vector<uint8_t> refs, seqs;
     std::vector<char> cigs;
-    int pack(const npore_bam *b, const RecFetch &rf, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n, int threads, uint32_t pass_mask = 0)
+    int pack(const npore_bam *b, const RecFetch &rf, const npore_fasta *fa, const int32_t *fasta_of_ref, int64_t n, int threads, uint32_t pass_mask)
     {
         for (auto *v : {&ro, &so, &co}) v->assign((size_t)n + 1, 0);
         pack_sizes_of(rf, n, ro.data(), so.data(), co.data(), threads, pass_mask);
@@ -1513,10 +1513,11 @@ int npore_bam_format_bam_full_md(npore_bam *b, const npore_fasta *fa, const int3
     return npore_bam_format_bam_full_tags(b, fa, fasta_of_ref, idx, n, finals, final_off, final_len, status, threads, recs, recs_len, flags, 0);
 }
 
-// NPORE_TAG_CS alone or with NPORE_TAG_CS_LONG, NPORE_TAG_DE, or nothing
-static bool output_tags_ok(int tags)
+// The FULL records of the host and debug entries, whose `flags` know NPORE_OUT_MD alone: what the three setters make of the same
+// options for a FULL BAM run (rec_spec_of)
+static bool full_rec_spec(int flags, int tags, int pass_mask, RecSpec &rec)
 {
-    return !(tags & ~(NPORE_TAG_CS | NPORE_TAG_CS_LONG | NPORE_TAG_DE)) && (!(tags & NPORE_TAG_CS_LONG) || (tags & NPORE_TAG_CS));
+    return !(flags & ~NPORE_OUT_MD) && rec_spec_of(NPORE_OUT_BAM, NPORE_OUT_FULL | flags, tags, pass_mask, rec);
 }
 
 // ... and with tags: NPORE_TAG_*, cs and de behind MD (0: the records above)
@@ -1532,13 +1533,13 @@ int npore_bam_format_bam_full_pass(npore_bam *b, const npore_fasta *fa, const in
                                    const char *finals, const int64_t *final_off, const int64_t *final_len, const int32_t *status, int threads,
                                    const uint8_t **recs, int64_t *recs_len, int flags, int tags, int pass_mask)
 try {
-    if (!pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs || (flags & ~NPORE_OUT_MD) || !output_tags_ok(tags) || (pass_mask & ~(int)PASS_FLAGS))
-        return fail(NPORE_E_INVALID, "bad argument");
+    RecSpec rec;
+    if (!pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs || !full_rec_spec(flags, tags, pass_mask, rec)) return fail(NPORE_E_INVALID, "bad argument");
     if (int rc = fetch_records(b, idx, n, threads, b->api_fetch)) return rc;
     PackedCodes pc;
-    if (int rc = pc.pack(b, b->api_fetch, fa, fasta_of_ref, n, threads, (uint32_t)pass_mask)) return rc;
-    const ReadCodes codes{pc.refs.data(), pc.ro.data(), pc.seqs.data(), pc.so.data(), (flags & NPORE_OUT_MD) != 0, tags, (uint32_t)pass_mask};
-    const int rc = format_bam_into(b, b->api_fetch, n, finals, final_off, final_len, status, threads, b->recs, recs_len, nullptr, &codes);
+    if (int rc = pc.pack(b, b->api_fetch, fa, fasta_of_ref, n, threads, rec.pass_mask)) return rc;
+    const ReadCodes codes{rec, pc.refs.data(), pc.ro.data(), pc.seqs.data(), pc.so.data()};
+    const int rc = format_bam_into(b, b->api_fetch, n, finals, final_off, final_len, status, threads, b->recs, recs_len, nullptr, codes);
     *recs = reinterpret_cast<const uint8_t *>(b->recs.p);
     return rc;
 }
@@ -1579,11 +1580,9 @@ int npore_debug_format_bam_full_pass_device(npore_ctx *ctx, npore_bam *b, const 
                                             uint8_t *recs, int64_t cap, int64_t *recs_len, int32_t *nm, int flags, int32_t *md_len, int tags,
                                             int pass_mask)
 try {
-    const bool md = (flags & NPORE_OUT_MD) != 0;
-    const uint32_t pmask = (uint32_t)pass_mask;
-    if (!ctx || !pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs_len || cap < 0 || (cap > 0 && !recs) || (flags & ~NPORE_OUT_MD) ||
-        !output_tags_ok(tags) || (pass_mask & ~(int)PASS_FLAGS) ||
-        (n > 0 && (!finals || !final_off || !final_len || !status || !nm || (md && !md_len))))
+    RecSpec rec;
+    if (!ctx || !pack_args_ok(b, idx, n) || !fa || !fasta_of_ref || !recs_len || cap < 0 || (cap > 0 && !recs) || !full_rec_spec(flags, tags, pass_mask, rec) ||
+        (n > 0 && (!finals || !final_off || !final_len || !status || !nm || (rec.md && !md_len))))
         return fail(NPORE_E_INVALID, "bad argument");
     *recs_len = 0;
     if (n == 0) return NPORE_OK;
@@ -1592,102 +1591,71 @@ try {
     if (int rc = device_fasta(ctx, b, fa, fasta_of_ref)) return rc;
     RecFetch &rf = b->api_fetch;
     if (int rc = fetch_records(b, idx, n, 0, rf)) return rc;
-    // host side: sizes, staged heads, the finals as words in slots at multiples of 4
+    // stage: sizes, staged heads, the finals as words in slots at multiples of 4, the record buffer's bound (hostio.hpp)
     const size_t N = (size_t)n;
     std::vector<int64_t> off(5 * (N + 1), 0), aux(N, 0), wlen(N, 0);       // ref, seq, cig, words, raw offsets
     int64_t *ro = off.data(), *so = ro + (N + 1), *co = so + (N + 1), *wo = co + (N + 1), *rawo = wo + (N + 1);
-    pack_sizes_of(rf, n, ro, so, co, 0, pmask);
+    pack_sizes_of(rf, n, ro, so, co, 0, rec.pass_mask);
+    std::vector<std::vector<uint8_t>> fin(N);
     int64_t bound = 0;
     for (size_t k = 0; k < N; k++) {
         const RecView r = rec_of(rf, (int64_t)k);
         const int32_t rid = r.ref_id();
         if (rid < 0 || rid >= (int32_t)b->ref_names.size() || fasta_of_ref[rid] < 0 || fasta_of_ref[rid] >= (int)fa->names.size())
             return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
-        const bool pass = staged_passes(r.p, pmask);
-        const int64_t ops = ((status[k] & NPORE_ST_BAD_INPUT) || pass) ? 0 : cigar_text_ops(finals + final_off[k], final_len[k]);
+        const bool pass = staged_passes(r.p, rec.pass_mask), bad = (status[k] & NPORE_ST_BAD_INPUT) != 0;
+        const int64_t ops = (bad || pass) ? 0 : cigar_text_ops(finals + final_off[k], final_len[k]);
         if (ops < 0) return fail(NPORE_E_UNSUPPORTED, "a final CIGAR is no CIGAR text (BAM output)");
         aux[k] = pass ? 0 : filter_aux(r.aux(), r.end(), nullptr);
         wlen[k] = 4 * ops;
         wo[k + 1] = wo[k] + 4 * ops + 16;
-        rawo[k + 1] = rawo[k] + ((staged_head_bytes(rf.ptr[k], STAGE_FULL, pmask) + 7) & ~7ll);
-        if (pass) { bound += staged_pass_bytes(r.p); continue; }
-        bound += 36 + r.l_read_name() + 4 * ops + 32 + ((int64_t)r.l_seq() + 1) / 2 + r.l_seq() + aux[k] + 7 + 16;
+        rawo[k + 1] = rawo[k] + ((staged_record_bytes(rf.ptr[k], STAGE_FULL, rec) + 7) & ~7ll);
+        bound += pass ? staged_pass_bytes(r.p) : full_record_bound(r.l_read_name(), ops, r.l_seq(), aux[k]);
+        if (bad || pass) continue;
+        fin[k] = cigar_text_words(finals + final_off[k], final_len[k], ops);
+        int64_t ref_covered = 0, covered = 0;      // (a caller's final may cover more reference than the read has, and close a count at every word)
+        for (int64_t q = 0; q < ops; q++) {
+            const uint32_t w = rd32(fin[k].data() + 4 * q), use = nm_consumes(w & 15u);
+            if (use & 1u) ref_covered += w >> 4;
+            if (use) covered += w >> 4;
+        }
+        if (rec.md) bound += md_tag_bound(ref_covered, ops + 1);
+        if (rec.tags) bound += cs_de_tags_bound(covered);
     }
     std::vector<uint8_t> raw((size_t)rawo[N] + 64, 0), words((size_t)wo[N] + 64, 0);
     for (size_t k = 0; k < N; k++) {
-        stage_record_head(rf.ptr[k], STAGE_FULL, raw.data() + rawo[k], pmask);
-        if ((status[k] & NPORE_ST_BAD_INPUT) || staged_passes(rf.ptr[k] + 4, pmask)) continue;
-        uint32_t len = 0;
-        uint8_t *o = words.data() + wo[k];
-        for (int64_t q = 0; q < final_len[k]; q++) {
-            const char c = finals[final_off[k] + q];
-            if (c >= '0' && c <= '9') { len = len * 10 + (uint32_t)(c - '0'); continue; }
-            const uint32_t w = len << 4 | cigar_op_code(c);
-            std::memcpy(o, &w, 4);
-            o += 4;
-            len = 0;
-            // (MD: a caller's final may cover more reference than the read has -- three bytes per position it covers, 11 per word)
-            if (md) bound += 3 * (int64_t)((nm_consumes(w & 15u) & 1u) ? w >> 4 : 0u) + 11;
-            // (cs: three bytes per base a word covers at the most -- cs_rec.hpp, Size)
-            if (tags && nm_consumes(w & 15u)) bound += 3 * (int64_t)(w >> 4);
-        }
-        if (md) bound += 4 + 11;
-        if (tags) bound += 4 + 7;
+        stage_record(rf.ptr[k], STAGE_FULL, raw.data() + rawo[k], rec);
+        if (wlen[k]) std::memcpy(words.data() + wo[k], fin[k].data(), (size_t)wlen[k]);
     }
-    DevBuf d_cs, d_de, d_md, d_raw, d_off, d_words, d_wlen, d_aux, d_status, d_refs, d_seqs, d_cigs, d_recs, d_cursor, d_rec_off, d_rec_len, d_nm;
-    if (int rc = d_raw.ensure(raw.size())) return rc;
-    if (int rc = d_off.ensure(off.size() * 8)) return rc;
-    if (int rc = d_words.ensure(words.size())) return rc;
-    if (int rc = d_refs.ensure((size_t)ro[N] + 64)) return rc;
-    if (int rc = d_seqs.ensure((size_t)so[N] + 64)) return rc;
-    if (int rc = d_cigs.ensure((size_t)co[N] + 64)) return rc;
-    if (int rc = d_recs.ensure((size_t)bound + 64)) return rc;
-    if (int rc = d_cursor.ensure(64)) return rc;
-    if (int rc = d_status.ensure(N * 4 + 64)) return rc;
-    if (int rc = d_nm.ensure(N * 4 + 64)) return rc;
-    if (int rc = md ? d_md.ensure(N * 4 + 64) : 0) return rc;
-    if (int rc = tags ? d_cs.ensure(N * 4 + 64) : 0) return rc;
-    if (int rc = tags ? d_de.ensure(N * 4 + 64) : 0) return rc;
-    for (DevBuf *d : {&d_wlen, &d_aux, &d_rec_off, &d_rec_len})
+    // ... into a work set as upload_group leaves a staged group there, and the shared wiring (align_engine.hpp)
+    WorkSet w;
+    DevBuf d_recs, d_cursor;
+    int rce = 0;
+    if ((rce = w.in_raw.ensure(raw.size())) || (rce = w.in_off.ensure(off.size() * 8)) || (rce = w.out.ensure(words.size())) ||
+        (rce = w.in_refs.ensure((size_t)ro[N] + 64)) || (rce = w.in_seqs.ensure((size_t)so[N] + 64)) || (rce = w.in_cigs.ensure((size_t)co[N] + 64)) ||
+        (rce = d_recs.ensure((size_t)bound + 64)) || (rce = d_cursor.ensure(64)) || (rce = w.status.ensure(N * 4 + 64)) || (rce = w.reserve_emit_tags(rec, N)))
+        return rce;
+    for (DevBuf *d : {&w.out_len, &w.in_hp, &w.rec_off, &w.rec_len})
         if (int rc = d->ensure(N * 8 + 64)) return rc;
-    HIP_TRY(hipMemcpy(d_raw.p, raw.data(), raw.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_words.p, words.data(), words.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_wlen.p, wlen.data(), N * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_aux.p, aux.data(), N * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_status.p, status, N * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.in_raw.p, raw.data(), raw.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.in_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.out.p, words.data(), words.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.out_len.p, wlen.data(), N * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.in_hp.p, aux.data(), N * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(w.status.p, status, N * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemset(d_cursor.p, 0, 8));
-    const int64_t *o64 = d_off.as<int64_t>();
     hipStream_t st = ctx->s_post;
-    UnpackParams up;
-    up.raw = d_raw.as<uint8_t>(); up.raw_off = o64 + 4 * (n + 1);
-    up.ctg = ctx->d_ctg.as<CtgEntry>(); up.n_ctg = ctx->n_ctg;
-    up.refs = d_refs.as<uint8_t>(); up.ref_off = o64;
-    up.seqs = d_seqs.as<uint8_t>(); up.seq_off = o64 + (n + 1);
-    up.cigs = d_cigs.as<char>(); up.cig_off = o64 + 2 * (n + 1);
-    up.n_reads = n;
-    up.pass_mask = pmask;
-    hipLaunchKernelGGL(unpack_records_kernel, dim3((unsigned)n), dim3(256), 0, st, up);
-    BamEmitParams bp;
-    bp.raw = up.raw; bp.raw_off = up.raw_off; bp.ref_off = up.ref_off; bp.seq_off = up.seq_off;
-    bp.hp = d_aux.as<int64_t>();
-    bp.words = d_words.as<uint8_t>(); bp.words_off = o64 + 3 * (n + 1); bp.words_len = d_wlen.as<int64_t>(); bp.status = d_status.as<int32_t>();
-    bp.read_base = 0; bp.n_reads = n;
-    bp.recs = d_recs.as<uint8_t>(); bp.cap = bound; bp.cursor = d_cursor.as<unsigned long long>();
-    bp.rec_off = d_rec_off.as<int64_t>(); bp.rec_len = d_rec_len.as<int64_t>();
-    bp.refs = up.refs; bp.seqs = up.seqs; bp.nm = d_nm.as<int32_t>();
-    if (md) bp.md_len = d_md.as<int32_t>();
-    if (tags) { bp.tags = tags; bp.cs_len = d_cs.as<int32_t>(); bp.de = d_de.as<float>(); }
-    bp.pass_mask = pmask;
-    launch_bam_emit(bp, true, st);
+    hipLaunchKernelGGL(unpack_records_kernel, dim3((unsigned)n), dim3(256), 0, st, wire_unpack(&w, n, ctx->d_ctg.as<CtgEntry>(), ctx->n_ctg, rec.pass_mask));
+    launch_bam_emit(wire_bam_emit(&w, n, d_recs.as<uint8_t>(), bound, d_cursor.as<unsigned long long>(), rec), true, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
+    // copy back
     unsigned long long total = 0;
     std::vector<int64_t> rlen(N, 0);
     HIP_TRY(hipMemcpy(&total, d_cursor.p, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rlen.data(), d_rec_len.p, N * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(nm, d_nm.p, N * 4, hipMemcpyDeviceToHost));
-    if (md) HIP_TRY(hipMemcpy(md_len, d_md.p, N * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rlen.data(), w.rec_len.p, N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nm, w.nm.p, N * 4, hipMemcpyDeviceToHost));
+    if (rec.md) HIP_TRY(hipMemcpy(md_len, w.md_len.p, N * 4, hipMemcpyDeviceToHost));
     int64_t sum = 0;
     for (size_t k = 0; k < N; k++) {
         if (rlen[k] < 0) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
@@ -1703,35 +1671,28 @@ NPORE_CATCH_INT
 
 int npore_bam_set_output(npore_bam *b, int format, const char *bai_path, int flags)
 {
-    if (!b || (format != NPORE_OUT_SAM && format != NPORE_OUT_BAM) ||
-        (flags & ~(NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE | NPORE_OUT_MATCH | NPORE_OUT_FULL | NPORE_OUT_MD)) ||
-        ((flags & NPORE_OUT_MD) && !(flags & NPORE_OUT_FULL)) ||               // (MD is a tag of the FULL records)
-        ((flags & (NPORE_OUT_DEFLATE | NPORE_OUT_FULL)) && format != NPORE_OUT_BAM) || ((flags & NPORE_OUT_MATCH) && !(flags & NPORE_OUT_DEFLATE)) ||
-        ((flags & NPORE_OUT_FULL) && !(flags & (NPORE_OUT_EOF | NPORE_OUT_PART))))      // (a FULL run says what it writes: the end of a file or a rank's part)
+    // the writer's own rules (a FULL run says what it writes: the end of a file or a rank's part); the records': rec_spec_of
+    RecSpec rec;
+    if (!b || (format != NPORE_OUT_SAM && format != NPORE_OUT_BAM) || ((flags & NPORE_OUT_DEFLATE) && format != NPORE_OUT_BAM) ||
+        ((flags & NPORE_OUT_MATCH) && !(flags & NPORE_OUT_DEFLATE)) || ((flags & NPORE_OUT_FULL) && !(flags & (NPORE_OUT_EOF | NPORE_OUT_PART))) ||
+        !rec_spec_of(format, flags, 0, 0, rec))
         return fail(NPORE_E_INVALID, "bad argument");
     b->out_format = format;
     b->out_bai = (format == NPORE_OUT_BAM && bai_path) ? bai_path : "";
     b->out_flags = flags;
-    b->out_tags = 0;
-    b->out_pass = 0;
+    b->out_rec = rec;
     return NPORE_OK;
 }
 
-int npore_bam_set_output_pass(npore_bam *b, int flag_mask)
+// The two setters behind a FULL npore_bam_set_output (only a FULL record can be the input's or carry cs and de): the setting's
+// spec made again with the one option replaced
+static int set_output_option(npore_bam *b, int tags, int pass)
 {
-    if (!b || (flag_mask & ~(int)PASS_FLAGS) || b->out_format != NPORE_OUT_BAM || !(b->out_flags & NPORE_OUT_FULL))      // (only a FULL record can be the input's)
-        return fail(NPORE_E_INVALID, "bad argument");
-    b->out_pass = flag_mask;
+    if (!b || !b->out_rec.full || !rec_spec_of(b->out_format, b->out_flags, tags, pass, b->out_rec)) return fail(NPORE_E_INVALID, "bad argument");
     return NPORE_OK;
 }
-
-int npore_bam_set_output_tags(npore_bam *b, int tags)
-{
-    if (!b || !output_tags_ok(tags) || b->out_format != NPORE_OUT_BAM || !(b->out_flags & NPORE_OUT_FULL))      // (cs and de are tags of the FULL records)
-        return fail(NPORE_E_INVALID, "bad argument");
-    b->out_tags = tags;
-    return NPORE_OK;
-}
+int npore_bam_set_output_pass(npore_bam *b, int flag_mask) { return set_output_option(b, b ? b->out_rec.tags : 0, flag_mask); }
+int npore_bam_set_output_tags(npore_bam *b, int tags) { return set_output_option(b, tags, b ? (int)b->out_rec.pass_mask : 0); }
 
 int npore_bam_output_info(const npore_bam *b, int64_t *out4)
 {
@@ -1748,7 +1709,7 @@ try {
     if (b->out_format != NPORE_OUT_BAM) return fail(NPORE_E_INVALID, "npore_bam_write_file writes BAM: npore_bam_set_output first");
     BgzfStoredWriter w;
     const OutputSetting o = take_output_setting(b);
-    if (o.flags & NPORE_OUT_FULL)
+    if (o.rec.full)
         return fail(NPORE_E_UNSUPPORTED, "npore_bam_write_file has no reference to count NM from: FULL records come from a realign run or npore_bam_format_bam_full");
     if (int rc = w.open(out_path, b->ref_names.size(), o.bai.empty() ? nullptr : o.bai.c_str(), (o.flags & NPORE_OUT_EOF) != 0,
                         (o.flags & NPORE_OUT_PART) != 0, out_deflate_mode(o.flags), host_threads(threads))) return rc;
@@ -1757,7 +1718,7 @@ try {
         const int64_t m = std::min(batch_reads, n - k0);
         if (int rc = fetch_records(b, idx + k0, m, threads, b->api_fetch)) return rc;
         int64_t len = 0;
-        if (int rc = format_bam_into(b, b->api_fetch, m, finals, final_off + k0, final_len + k0, status + k0, threads, b->recs, &len, &meta)) return rc;
+        if (int rc = format_bam_into(b, b->api_fetch, m, finals, final_off + k0, final_len + k0, status + k0, threads, b->recs, &len, &meta, ReadCodes{})) return rc;
         if (int rc = w.add(reinterpret_cast<const uint8_t *>(b->recs.p), len, meta.data(), (int64_t)meta.size())) return rc;
     }
     return w.finish(b->out_info);
@@ -1844,7 +1805,7 @@ try {
     HIP_TRY(hipSetDevice(ctx->device));
     InflateRun infl(ctx, b);
     // (npore_bam_set_output_pass: the reader keeps what the run passes through; the setter has seen to it that the run writes FULL records)
-    BamRecordWalker walker(b, n_regions, ref_id, start, stop, max_reads, threads, PASS_FLAGS, infl.hook(), (uint32_t)b->out_pass);
+    BamRecordWalker walker(b, n_regions, ref_id, start, stop, max_reads, threads, PASS_FLAGS, infl.hook(), b->out_rec.pass_mask);
     RunOutput out;
     if (int rco = out.open(b, out_path, threads)) return rco;
     int64_t n_bad = 0, ordinal0 = 0;

@@ -187,3 +187,118 @@ def test_cli_refuses_pass_through_without_full_records(case, tmp_path):
     text = subprocess.run([sys.executable, "-m", "npore_amd.realign", "--help"], cwd=REPO, capture_output=True, text=True, timeout=120).stdout
     flat = " ".join(text.split())
     assert "--pass_through" in flat and "unplaced" in flat and "0x100" in flat and "0x800" in flat and "0x4" in flat
+
+
+# ---- the record spec (csrc/hostio.hpp RecSpec, rec_spec_of): one statement of the output options' rules behind every entry ------
+def ladder_args(case, idx):
+    """the arguments the four host entries share, and where they leave the records"""
+    import ctypes as C
+    nb, finals, status = case["nb"], case["finals"], case["status"]
+    fb = [finals[k].encode() for k in idx]
+    fo = np.zeros(len(idx) + 1, np.int64)
+    np.cumsum([len(f) for f in fb], out=fo[1:])
+    fl, buf, st = np.ascontiguousarray(np.diff(fo)), np.frombuffer(b"".join(fb) + b"\0", np.uint8), np.ascontiguousarray(status[idx])
+    recs, n = C.c_void_p(), C.c_int64()
+    keep = (fo, fl, buf, st, idx)
+    args = (nb.handle, case["nf"].handle, nb.fasta_map(case["nf"]).ctypes.data, idx.ctypes.data, len(idx), buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
+            st.ctypes.data, 0, C.byref(recs), C.byref(n))
+    return args, (lambda: C.string_at(recs.value, n.value)), keep
+
+
+@pytest.mark.parametrize("mask", [0, 0x4, 0x100, 0x800, 0x904])
+def test_the_ladder_forwards_agree(case, mask):
+    """All twelve (md, cs, de) combinations: every entry of npore_bam_format_bam_full{,_md,_tags,_pass} that can say the combination
+    -- a narrower one where the options it lacks are zero, the widest always -- returns the same bytes, NativeBam.format_bam_full's."""
+    nb, lib = case["nb"], case["nb"]._lib
+    idx = np.array(pc.py_select(case["raws"], [(0, 0, 1 << 28), (1, 0, 1 << 28)], 0, mask), np.int64)
+    args, got, _keep = ladder_args(case, idx)
+    combos = [(md, cs, de) for md in (False, True) for cs in (None, "short", "long") for de in (False, True)]
+    assert len(combos) == 12
+    for md, cs, de in combos:
+        flags, tags = 32 if md else 0, bam.output_tags(cs, de)
+        want = nb.format_bam_full(case["nf"], idx, [case["finals"][k] for k in idx], case["status"][idx], md=md, cs=cs, de=de, pass_mask=mask)
+        assert len(split_records(want)) == len(idx) - 1            # (the refused read is absent)
+        calls = [lambda: lib.npore_bam_format_bam_full_pass(*args, flags, tags, mask)]
+        if mask == 0:
+            calls.append(lambda: lib.npore_bam_format_bam_full_tags(*args, flags, tags))
+        if mask == 0 and tags == 0:
+            calls.append(lambda: lib.npore_bam_format_bam_full_md(*args, flags))
+        if mask == 0 and tags == 0 and not md:
+            calls.append(lambda: lib.npore_bam_format_bam_full(*args))
+        for k, call in enumerate(calls):
+            assert call() == 0 and got() == want, (mask, md, cs, de, k)
+
+
+def spec_ok(fmt, flags, tags, pas):
+    """csrc/hostio.hpp rec_spec_of restated: defined bits only, CS_LONG beside CS, md / tags / pass on FULL records, FULL records in BAM"""
+    full = bool(flags & 16)
+    return not (flags & ~63 or tags & ~7 or pas & ~0x904 or (tags & 2 and not tags & 1) or (not full and (flags & 32 or tags or pas)) or (full and fmt != 1))
+
+
+def set_output_ok(fmt, flags):
+    """... and npore_bam_set_output's own: a known format, DEFLATE in BAM, MATCH beside DEFLATE, a FULL run ends a file or writes a part"""
+    return fmt in (0, 1) and not (flags & 4 and fmt != 1) and not (flags & 8 and not flags & 4) and not (flags & 16 and not flags & 3) and spec_ok(fmt, flags, 0, 0)
+
+
+def test_the_rule_table(case):
+    """Every (format, flags, tags, pass) over the defined bits and one undefined bit each, through npore_bam_set_output, _pass and
+    _tags in that order on a fresh handle: accepted and refused as the rules above say.  And the host entry accepts (flags, tags,
+    pass) exactly when the setters accept them for a FULL BAM run."""
+    lib = case["nb"]._lib
+    flag_sets = list(range(64)) + [64, 64 | 16 | 1]
+    tag_sets, pass_sets = list(range(8)) + [8], [a | b | c for a in (0, 4) for b in (0, 0x100) for c in (0, 0x800)] + [0x400]
+    for fmt in (0, 1, 2):
+        for flags in flag_sets:
+            e1 = set_output_ok(fmt, flags)
+            if not e1:                                           # nothing is held: every option is refused (one handle serves them all)
+                nb = bam.NativeBam(case["bp"], stream=False)
+                assert lib.npore_bam_set_output(nb.handle, fmt, None, flags) != 0, (fmt, flags)
+                for tags in tag_sets:
+                    assert lib.npore_bam_set_output_tags(nb.handle, tags) != 0, (fmt, flags, tags)
+                for pas in pass_sets:
+                    assert lib.npore_bam_set_output_pass(nb.handle, pas) != 0, (fmt, flags, pas)
+                nb.close()
+                continue
+            for tags in tag_sets:
+                for pas in pass_sets:
+                    nb = bam.NativeBam(case["bp"], stream=False)
+                    held = bool(flags & 16)
+                    e2 = held and spec_ok(fmt, flags, 0, pas)
+                    e3 = held and spec_ok(fmt, flags, tags, pas if e2 else 0)
+                    got = (lib.npore_bam_set_output(nb.handle, fmt, None, flags) == 0, lib.npore_bam_set_output_pass(nb.handle, pas) == 0,
+                           lib.npore_bam_set_output_tags(nb.handle, tags) == 0)
+                    nb.close()
+                    assert got == (True, e2, e3), (fmt, flags, tags, pas)
+    nb = case["nb"]
+    args, _got, _keep = ladder_args(case, np.zeros(0, np.int64))
+    for flags in (0, 32, 64, 32 | 64, 16, 1):                    # (the entry's flags know NPORE_OUT_MD alone: FULL and the writer's bits are not its to take)
+        for tags in tag_sets:
+            for pas in pass_sets:
+                assert lib.npore_bam_set_output(nb.handle, 1, None, 16 | 1) == 0
+                setters = flags in (0, 32) and lib.npore_bam_set_output(nb.handle, 1, None, 16 | 1 | flags) == 0 and \
+                    lib.npore_bam_set_output_pass(nb.handle, pas) == 0 and lib.npore_bam_set_output_tags(nb.handle, tags) == 0
+                assert setters == (flags in (0, 32) and spec_ok(1, 16 | 1 | flags, tags, pas))
+                assert (lib.npore_bam_format_bam_full_pass(*args, flags, tags, pas) == 0) == setters, (flags, tags, pas)
+    assert lib.npore_bam_set_output(nb.handle, 0, None, 0) == 0
+
+
+def test_the_setting_is_spent_once(case, tmp_path):
+    """A run takes the setting and leaves the default: npore_bam_write_file, which refuses FULL records, is such a run -- behind it
+    the handle writes SAM again, _pass and _tags are refused as on a fresh handle, and the mask npore_bam_pack_sizes sees is gone."""
+    nb, lib = case["nb"], case["nb"]._lib
+    idx = np.arange(40, dtype=np.int64)
+    sizes = lambda: [np.diff(a).tolist() for a in nb.pack(case["nf"], idx)[1::2]]
+    without = sizes()
+    assert lib.npore_bam_set_output(nb.handle, 1, None, 16 | 32 | 1) == 0
+    assert lib.npore_bam_set_output_pass(nb.handle, 0x904) == 0 and lib.npore_bam_set_output_tags(nb.handle, 1 | 2 | 4) == 0
+    assert sizes() != without
+    out = tmp_path / "never.bam"
+    assert lib.npore_bam_write_file(nb.handle, None, 0, 1, None, None, None, None, 0, str(out).encode()) != 0
+    assert b"FULL records" in lib.npore_last_error() and not out.exists()      # (refused for what the setting said, which it thereby took)
+    assert sizes() == without
+    for mask in (0, 0x4, 0x904):
+        assert lib.npore_bam_set_output_pass(nb.handle, mask) != 0, mask
+    for tags in (0, 1, 4, 7):
+        assert lib.npore_bam_set_output_tags(nb.handle, tags) != 0, tags
+    assert lib.npore_bam_write_file(nb.handle, None, 0, 1, None, None, None, None, 0, str(out).encode()) != 0      # (SAM again: no BAM run)
+    assert b"npore_bam_set_output first" in lib.npore_last_error() and not out.exists()

@@ -237,3 +237,41 @@ def test_cli_pass_through(case):
     out = subprocess.run(common + ["--out_prefix", prefix], cwd=REPO, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     assert record_stream(prefix + ".bam") == case["nb"].format_bam_full(case["nf"], case["reads"], case["finals"], case["st"], **TAGS)
+
+
+# ---- the debug ladder: the narrow entries are the widest with zeros (one record spec behind all four) ---------------------------
+def test_device_ladder_forwards_agree(ctx, case):
+    """npore_debug_format_bam_full{,_md,_tags,_pass}_device on the file: every entry that can say the options equals the widest at
+    zero-extended arguments, and both equal the host twin -- with everything off, with MD, with MD + cs long + de, and (the widest
+    alone can say it) those with mask 0x904."""
+    nb, nf, lib = case["nb"], case["nf"], case["nb"]._lib
+    final_of, st_of = dict(zip(case["reads"].tolist(), case["finals"])), dict(zip(case["reads"].tolist(), case["st"].tolist()))
+    cap = sum(len(r) for r in case["raws"]) * 3 + (1 << 16)
+    fmap = nb.fasta_map(nf)
+    for mask, md, cs, de in ((0, False, None, False), (0, True, None, False), (0, True, "long", True), (MASK, True, "long", True)):
+        idx = np.array(pc.py_select(case["raws"], [(0, 0, 1 << 28), (1, 0, 1 << 28)], 0, mask), np.int64)
+        finals = [final_of.get(int(k), "") for k in idx]
+        status = np.array([st_of.get(int(k), 0) for k in idx], np.int32)
+        n, flags, tags = len(idx), 32 if md else 0, bam.output_tags(cs, de)
+        fb = [f.encode() for f in finals]
+        fo = np.zeros(n + 1, np.int64)
+        np.cumsum([len(f) for f in fb], out=fo[1:])
+        fl, buf = np.ascontiguousarray(np.diff(fo)), np.frombuffer(b"".join(fb) + b"\0", np.uint8)
+        want = nb.format_bam_full(nf, idx, finals, status, md=md, cs=cs, de=de, pass_mask=mask)
+        assert len(split_records(want)) == n - 1
+
+        def run(entry, *more):
+            recs, nm, mdl, got = np.zeros(cap, np.uint8), np.full(n, -1, np.int32), np.full(n, -1, np.int32), C.c_int64()
+            more = tuple(mdl.ctypes.data if m is Ellipsis else m for m in more)
+            nb._check(getattr(lib, entry)(ctx.handle, nb.handle, nf.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data,
+                                          fl.ctypes.data, status.ctypes.data, recs.ctypes.data, cap, C.byref(got), nm.ctypes.data, *more))
+            return recs[:got.value].tobytes(), nm.tolist(), mdl.tolist() if md else None
+
+        wide = run("npore_debug_format_bam_full_pass_device", flags, ..., tags, mask)
+        assert wide[0] == want, (mask, md, cs, de)
+        if mask == 0:
+            assert run("npore_debug_format_bam_full_tags_device", flags, ..., tags) == wide
+        if mask == 0 and tags == 0:
+            assert run("npore_debug_format_bam_full_md_device", flags, ...) == wide
+        if mask == 0 and tags == 0 and not md:
+            assert run("npore_debug_format_bam_full_device") == wide

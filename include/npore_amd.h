@@ -470,14 +470,23 @@ int npore_bam_realign_file(npore_ctx *ctx, npore_bam *bam, const npore_fasta *fa
  * (header only) or 2.  counts[3]: reads selected (records that pass through included: npore_bam_set_output_pass), reads
  * refused (NPORE_ST_BAD_INPUT, not written), reads with an inconsistent traceback (NPORE_ST_PASSED is neither); bad_ord / bad_status[bad_cap]: ordinal (among the selected reads) and status bits of the
  * first such reads.  NPORE_E_UNSUPPORTED: the regions or the file's order rule the one-pass run out (the BAM is not
- * sorted by reference, several regions per contig) -- nothing usable was written: truncate and use the indexed path. */
+ * sorted by reference, several regions per contig) -- nothing usable was written: truncate and use the indexed path.
+ * NPORE_E_INVALID with a message that names the .bai and calls it stale: a mode-3 handle took npore_bam_ref_has_reads
+ * from the .bai beside the file, and the walk met a record on a contig which that index declares empty -- regions made
+ * from it would leave reads out without a word, so the run ends (rebuild or remove the index). */
 /* Several processes (one per GPU) on ONE file, each in one pass (the reference feeds all its workers from one sequential
  * read, src/bam.pyx:18-47 + src/realign.py:110-114): process `rank` of `world` walks a contiguous stretch of the record
  * stream -- the records that start between two cut points taken from the LINEAR index of the file's .bai (bai_path; each
  * entry is the virtual offset of a record: SAM specification 5.2), chosen at rank / world of the compressed file -- so every
  * block is inflated once per node, no record index is built, and the ranks' part files concatenated in rank order are in
  * file order.  The next npore_bam_realign_sequential on the handle walks that stretch only (max_reads must be 0).
- * world == 1 clears the share.  NPORE_E_UNSUPPORTED: no usable .bai (the caller takes the indexed reader). */
+ * world == 1 clears the share.  NPORE_E_UNSUPPORTED: no usable .bai (the caller takes the indexed reader).
+ * The index is another file, and it may be stale or somebody else's: EVERY rank checks ALL the cuts, so the answer depends
+ * on the two files and on `world`, never on `rank` -- every non-zero linear offset of the index must name the first byte
+ * of one of this file's BGZF members, exactly, and an offset inside what that member inflates to; at every cut a sound
+ * record must start (on a contig of the header, at a position within it), followed by another or by the end of the
+ * stream (the member is inflated to see: world - 1 small inflations per call).  Anything else: NPORE_E_UNSUPPORTED, and
+ * the message names the index.  File times are not looked at (a copy or a checkout scrambles them). */
 int npore_bam_set_share(npore_bam *bam, int rank, int world, const char *bai_path);
 /* out4: [0] a share is set, [1] / [2] its first byte and its end in the inflated stream (-1: nothing / the end of the
  * file), [3] the BGZF block it begins in (tests). */

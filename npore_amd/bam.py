@@ -1027,6 +1027,12 @@ class OnePassUnsupported(RuntimeError):
     """NativeBam.realign_sequential cannot serve these regions / this file in one pass (take the indexed path)."""
 
 
+class StaleIndex(RuntimeError):
+    """The .bai beside the BAM declares a contig empty on which the one-pass walk met a record: the default regions made
+    from it would leave reads out.  The message names the index; the run ends (no other reader is taken: the regions are
+    the index's too)."""
+
+
 class NativeBam:
     """A BAM file inflated and indexed by the library (same attributes as BamFile where realign needs them)."""
 
@@ -1445,6 +1451,10 @@ class NativeBam:
             # kernels do not cover (the same code) would fail there in the same way, after a whole indexing pass
             if "one-pass ingest" in msg or "not sorted by reference" in msg:
                 raise OnePassUnsupported(msg)
+        if rc != 0:
+            from . import _lib
+            if "the index is stale" in _lib.last_error():
+                raise StaleIndex(_lib.last_error())
         self._check(rc)
         self._after_bam_run(out_format)
         nb = int(min(bad_cap, counts[1] + counts[2]))

@@ -197,6 +197,7 @@ inline npore_bam *bam_open_streamed(const char *path, int threads, std::unique_p
             }
             have_header = true;
             p = hdr_end;
+            b->first_record = base + hdr_end;
         }
         offs.clear();
         for (size_t nx = 0;; p = nx) {
@@ -237,13 +238,14 @@ inline npore_bam *bam_open_header_only(const char *path, int threads, std::uniqu
         }
         size_t hdr_end = 0;
         const int rc = bam_parse_header(b, reinterpret_cast<const uint8_t *>(head.p), n, &hdr_end);
-        if (rc == 1) break;
+        if (rc == 1) { b->first_record = hdr_end; break; }
         if (rc == 0 || b1 == b->blocks.size()) { fail(NPORE_E_INVALID, std::string("'") + path + "' is not a BAM file"); return nullptr; }
     }
     bam_finish_index(b);                                 // (empty per-reference lists)
     // which contigs have reads (get_bam_regions' default keeps only those, src/util.py:16-93 with bam.count() > 0): from
     // the file's .bai when there is one (a reference with bins or linear-index entries has records) -- otherwise unknown
-    // without a pass over the records: every contig is assumed to have some
+    // without a pass over the records: every contig is assumed to have some.  What the index says is a claim that the
+    // one-pass walk checks against the records it meets (has_reads_index): a stale index ends the run, it drops nothing
     b->ref_has_reads.assign(b->ref_names.size(), 1);
     {
         const std::string p0 = std::string(path) + ".bai";
@@ -253,7 +255,7 @@ inline npore_bam *bam_open_header_only(const char *path, int threads, std::uniqu
         std::vector<uint64_t> offs;
         std::vector<uint8_t> has;
         for (const std::string &cand : {p0, p1})
-            if (bai_linear_offsets(cand.c_str(), offs, &has) && has.size() == b->ref_names.size()) { b->ref_has_reads = has; break; }
+            if (bai_linear_offsets(cand.c_str(), offs, &has) && has.size() == b->ref_names.size()) { b->ref_has_reads = has; b->has_reads_index = cand; break; }
     }
     return hold.release();
 }
@@ -392,7 +394,50 @@ inline int64_t bam_select(const npore_bam *b, int n_regions, const int32_t *ref_
     return kept;
 }
 
-// ONE-PASS handle, several processes: the stretch of the record stream that `rank` of `world` walks (npore_bam.share_*)
+// Does a record start at offset `abs` of the inflated stream, which lies in member `blk`?  What a cut of a share must
+// be: the record there is framed WHOLE within the stream and sound, lies on a contig of the header (or on none) at a
+// position within it, and behind it the stream ends or another such record follows.  Inflates `blk` and, where the two
+// records reach further, the members behind it; a block_size that points beyond the stream's end inflates nothing more.
+inline bool share_cut_is_record_start(const npore_bam *b, size_t blk, uint64_t abs)
+{
+    const uint64_t base = b->blocks[blk].out_off;
+    std::vector<uint8_t> buf;
+    size_t have = 0, b1 = blk;                               // members [blk, b1) inflated: buf[0 .. have) = stream[base ..)
+    auto more = [&]() -> bool {                              // the next member that holds anything
+        for (; b1 < b->blocks.size(); b1++) {
+            const size_t len = (size_t)b->blocks[b1].out_len;
+            if (!len) continue;
+            buf.resize(have + len + 8);
+            if (!bgzf_inflate_range(*b->file, b->blocks, b1, b1 + 1, buf.data() + have, 1)) return false;
+            have += len;
+            b1++;
+            return true;
+        }
+        return false;
+    };
+    const int64_t n_ref = (int64_t)b->ref_names.size();
+    auto record_at = [&](size_t p, size_t &next) -> bool {
+        for (;;) {
+            const Frame f = frame_record(buf.data(), have, p, next);
+            if (f == Frame::WHOLE) break;
+            if (f == Frame::CORRUPT) return false;
+            if (p + 4 <= have && base + p + 4 + (uint64_t)rdi32(buf.data() + p) > b->data_size) return false;
+            if (!more()) return false;
+        }
+        const uint8_t *q = buf.data() + p;
+        if (!record_is_sound(q)) return false;
+        const int64_t rid = rdi32(q + 4), pos = rdi32(q + 8);
+        return rid >= -1 && rid < n_ref && (rid < 0 || (pos >= 0 && pos < b->ref_lens[(size_t)rid]));
+    };
+    size_t nx = 0, nx2 = 0;
+    if (!more() || !record_at((size_t)(abs - base), nx)) return false;
+    return base + nx == b->data_size || record_at(nx, nx2);
+}
+
+// ONE-PASS handle, several processes: the stretch of the record stream that `rank` of `world` walks (npore_bam.share_*).
+// The index is another file and may be stale or somebody else's, so EVERY rank locates and checks ALL world + 1 cuts:
+// whether the ranks walk shares or take the indexed reader depends on the two files and on `world`, never on `rank` --
+// a rank that decided for itself would deal the reads differently from the rest (records twice, records missing).
 inline int bam_set_share(npore_bam *b, int rank, int world, const char *bai_path)
 {
     if (!b || world < 1 || rank < 0 || rank >= world) return fail(NPORE_E_INVALID, "bad argument");
@@ -403,8 +448,10 @@ inline int bam_set_share(npore_bam *b, int rank, int world, const char *bai_path
     b->share_block = 0;
     if (world == 1) return NPORE_OK;
     std::vector<uint64_t> cuts;
-    if (!bai_path || !bai_linear_offsets(bai_path, cuts) || cuts.empty())
+    std::vector<uint8_t> has;
+    if (!bai_path || !bai_linear_offsets(bai_path, cuts, &has) || has.size() != b->ref_names.size() || cuts.empty())
         return fail(NPORE_E_UNSUPPORTED, "no usable .bai linear index: the record stream cannot be dealt without a pass over it");
+    const std::string foreign = std::string("the index '") + bai_path + "' does not belong to this BAM file (is it stale?)";
     // the first record of the stretch whose compressed offset lies at or behind k / world of the file
     const uint64_t c0 = b->blocks.front().in_off, c1 = b->blocks.back().in_off + b->blocks.back().in_len;
     auto cut_of = [&](int k) -> uint64_t {
@@ -414,27 +461,31 @@ inline int bam_set_share(npore_bam *b, int rank, int world, const char *bai_path
         auto it = std::lower_bound(cuts.begin(), cuts.end(), target << 16);
         return it == cuts.end() ? UINT64_MAX : *it;
     };
-    // virtual offset -> block of the table and offset in the inflated stream (false: the index is not this file's)
+    // virtual offset -> block of the table and offset in the inflated stream (false: the index is not this file's): the
+    // compressed half is where a member begins, exactly, the other half lies inside what that member inflates to
     auto locate = [&](uint64_t v, size_t &blk, uint64_t &abs) -> bool {
         const uint64_t coff = v >> 16, uoff = v & 0xFFFFu;
-        // a block's payload begins a gzip header's length behind the block: the block that starts at `coff` is the first
-        // one whose payload offset lies behind it
-        size_t lo = 0, hi = b->blocks.size();
-        while (lo < hi) { const size_t mid = (lo + hi) / 2; if (b->blocks[mid].in_off > coff) hi = mid; else lo = mid + 1; }
-        if (lo == b->blocks.size() || b->blocks[lo].in_off - coff > 4096 || uoff >= b->blocks[lo].out_len) return false;
-        blk = lo;
-        abs = b->blocks[lo].out_off + uoff;
-        return true;
+        auto it = std::lower_bound(b->blocks.begin(), b->blocks.end(), coff, [](const BgzfBlock &k, uint64_t c) { return k.mem_off < c; });
+        if (it == b->blocks.end() || it->mem_off != coff || uoff >= it->out_len) return false;
+        blk = (size_t)(it - b->blocks.begin());
+        abs = it->out_off + uoff;
+        return abs >= b->first_record;
     };
-    const uint64_t v0 = cut_of(rank), v1 = cut_of(rank + 1);
-    if (v0 == UINT64_MAX) { b->share_begin = b->share_end = UINT64_MAX; }       // nothing left for this rank
-    else if (v0 != 0) {
-        if (!locate(v0, b->share_block, b->share_begin)) return fail(NPORE_E_UNSUPPORTED, "the .bai index does not belong to this BAM file");
+    // EVERY offset of the index lies in this file's block table (a search each, nothing inflated): the answer is then the
+    // same at every `world`, also at one whose own cuts happen to be among the offsets that still fit
+    size_t blk = 0;
+    uint64_t abs = 0, seen = 0;                              // (neighbouring cuts are often the same entry: checked once)
+    for (const uint64_t v : cuts)
+        if (!locate(v, blk, abs)) return fail(NPORE_E_UNSUPPORTED, foreign);
+    for (int k = 1; k < world; k++) {
+        const uint64_t v = cut_of(k);
+        if (v == UINT64_MAX) break;                          // nothing left from here on
+        if (v != seen && (!locate(v, blk, abs) || !share_cut_is_record_start(b, blk, abs))) return fail(NPORE_E_UNSUPPORTED, foreign);
+        seen = v;
+        if (k == rank) { b->share_block = blk; b->share_begin = abs; }
+        if (k == rank + 1) b->share_end = abs;
     }
-    if (v1 != UINT64_MAX && v0 != UINT64_MAX) {
-        size_t blk;
-        if (!locate(v1, blk, b->share_end)) return fail(NPORE_E_UNSUPPORTED, "the .bai index does not belong to this BAM file");
-    }
+    if (cut_of(rank) == UINT64_MAX) b->share_begin = b->share_end = UINT64_MAX;       // nothing left for this rank
     b->has_share = true;
     return NPORE_OK;
 }
@@ -1430,7 +1481,8 @@ public:
     BamRecordWalker(const npore_bam *b, int n_regions, const int32_t *ref_id, const int64_t *start, const int64_t *stop,
                     int64_t max_reads, int threads, uint32_t drop_flags = PASS_FLAGS, BgzfInflateFn inflate = nullptr, uint32_t pass_mask = PASS_NONE)
         : b_(b), src_(b, threads, std::move(inflate)), n_regions_(n_regions), ref_id_(ref_id), start_(start), stop_(stop), max_reads_(max_reads),
-          drop_flags_(drop_flags & ~pass_mask), pass_mask_(pass_mask), done_(n_regions == 0)
+          drop_flags_(drop_flags & ~pass_mask), pass_mask_(pass_mask), index_claims_(!b->has_reads_index.empty()),
+          done_(n_regions == 0 && !index_claims_)          // (no region at all may be the index's doing: walk to the first placed record)
     {
         if (!b->has_share) return;
         if (b->share_begin == UINT64_MAX) done_ = true;          // nothing left for this rank
@@ -1474,6 +1526,12 @@ public:
             if (rid < 0) continue;                               // unplaced
             if (rid < last_rid_) return fail(NPORE_E_UNSUPPORTED, "the BAM is not sorted by reference: one-pass ingest needs a coordinate-sorted file");
             last_rid_ = rid;
+            // the contigs without reads are the index's claim (bam_open_header_only), and the default regions leave them
+            // out: a record on one of them -- met between two regions, or where the walk stops behind the last -- says
+            // that the index is stale, and reads would be missing from the output without a word
+            if (index_claims_ && (size_t)rid < b_->ref_has_reads.size() && !b_->ref_has_reads[(size_t)rid])
+                return fail(NPORE_E_INVALID, "the index '" + b_->has_reads_index + "' says that contig '" + b_->ref_names[(size_t)rid] +
+                                                 "' has no reads, but the BAM has some: the index is stale (rebuild or remove it)");
             while (g_ < n_regions_ && ref_id_[g_] < rid) g_++;
             if (g_ == n_regions_) { done_ = true; break; }
             if (ref_id_[g_] != rid) continue;
@@ -1516,8 +1574,9 @@ private:
     const int64_t max_reads_;
     const uint32_t drop_flags_;              // (the realigner's; the recount of the confusion matrices filters for itself)
     const uint32_t pass_mask_;               // ... without these bits: such records pass through (staged_head.hpp)
+    const bool index_claims_;                // ref_has_reads is what a .bai said: checked against every placed record met
     int64_t kept_ = 0;
-    int32_t last_rid_ = -1;                  // (the sorted-by-reference check)
+    int32_t last_rid_ = -1;                // (the sorted-by-reference check)
     bool done_;
 };
 

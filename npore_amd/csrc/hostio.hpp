@@ -245,7 +245,9 @@ struct ByteSpan {
     const uint8_t &operator[](size_t i) const { return p[i]; }
 };
 
-struct BgzfBlock { uint64_t in_off, in_len, out_off, out_len; };    // deflate payload in the file; its place in the stream
+// deflate payload in the file; its place in the stream; where the member itself (its gzip header) begins in the file --
+// the compressed half of a virtual offset
+struct BgzfBlock { uint64_t in_off, in_len, out_off, out_len, mem_off; };
 
 // header of the BGZF member at p[0 .. avail): payload offset and member size; false = not the header of a BGZF member
 // (need = bytes wanted, when more input could help; 0 when none can)
@@ -341,7 +343,7 @@ inline bool bgzf_inflate(const ByteSpan &raw, int threads, RawBuf &out, size_t &
     while (p + 18 <= raw.size()) {
         size_t po, pl, isz, bs, need;
         if (!bgzf_member(raw.data() + p, raw.size() - p, po, pl, isz, bs, need)) { is_bgzf = false; break; }
-        blocks.push_back({p + po, pl, total, isz});
+        blocks.push_back({p + po, pl, total, isz, p});
         total += isz;
         p += bs;
     }
@@ -445,7 +447,7 @@ inline bool bgzf_scan(const PreadFile &f, std::vector<BgzfBlock> &blocks, uint64
         if (buf.size() < 4 + HEAD) buf.resize(4 + HEAD);
         if (!f.read(nx - 4, buf.data(), 4 + have)) return false;
         const size_t isz = rd32(buf.data());
-        blocks.push_back({fp + po, bs - po - 8, total, isz});
+        blocks.push_back({fp + po, bs - po - 8, total, isz, fp});
         total += isz;
         fp = nx;
     }
@@ -493,35 +495,37 @@ inline bool bai_linear_offsets(const char *path, std::vector<uint64_t> &out, std
     const uint8_t *p = mf.p;
     const size_t n = mf.n;
     size_t q = 4;
-    auto have = [&](size_t k) { return q + k <= n; };
-    if (!have(4)) return false;
+    // every count is bounded by the bytes that are left before anything is sized by it or looped over: a reference takes
+    // eight bytes at least (n_bin, n_intv), a bin eight (its id, n_chunk), a chunk sixteen, a linear entry eight
+    auto have = [&](size_t k) { return k <= n - q; };
     const int32_t n_ref = (int32_t)rd32(p + q); q += 4;
-    if (n_ref < 0) return false;
+    if (n_ref < 0 || (size_t)n_ref > (n - q) / 8) return false;
     out.clear();
-    if (ref_has_reads) ref_has_reads->assign((size_t)n_ref, 0);
+    std::vector<uint8_t> has((size_t)n_ref, 0);
     for (int32_t r = 0; r < n_ref; r++) {
         if (!have(4)) return false;
         const int32_t n_bin = (int32_t)rd32(p + q); q += 4;
-        if (n_bin < 0) return false;
-        if (ref_has_reads && n_bin > 0) (*ref_has_reads)[(size_t)r] = 1;
+        if (n_bin < 0 || (size_t)n_bin > (n - q) / 8) return false;
+        if (n_bin > 0) has[(size_t)r] = 1;
         for (int32_t b = 0; b < n_bin; b++) {
             if (!have(8)) return false;
             const int32_t n_chunk = (int32_t)rd32(p + q + 4); q += 8;
-            if (n_chunk < 0 || !have((size_t)n_chunk * 16)) return false;
+            if (n_chunk < 0 || (size_t)n_chunk > (n - q) / 16) return false;
             q += (size_t)n_chunk * 16;
         }
         if (!have(4)) return false;
         const int32_t n_intv = (int32_t)rd32(p + q); q += 4;
-        if (n_intv < 0 || !have((size_t)n_intv * 8)) return false;
+        if (n_intv < 0 || (size_t)n_intv > (n - q) / 8) return false;
         for (int32_t k = 0; k < n_intv; k++) {
             const uint64_t v = (uint64_t)rd32(p + q) | ((uint64_t)rd32(p + q + 4) << 32);
             q += 8;
             if (v) {
                 out.push_back(v);
-                if (ref_has_reads) (*ref_has_reads)[(size_t)r] = 1;
+                has[(size_t)r] = 1;
             }
         }
     }
+    if (ref_has_reads) ref_has_reads->swap(has);
     std::sort(out.begin(), out.end());
     out.erase(std::unique(out.begin(), out.end()), out.end());
     return true;
@@ -574,6 +578,10 @@ struct npore_bam {
     std::vector<std::string> ref_names;
     std::vector<int64_t> ref_lens;
     std::vector<uint8_t> ref_has_reads;
+    // ONE-PASS handle: the .bai that ref_has_reads was taken from ("" = from no index).  An index is a CLAIM about the
+    // file: a record the one-pass walk meets on a contig that this one declared empty ends the run (BamRecordWalker)
+    std::string has_reads_index;
+    uint64_t first_record = 0;            // where the header ends in the inflated stream (0: not known)
     // STREAMED mode (large files): the inflated stream is never held as a whole.  The handle keeps the BGZF block
     // table and, per record, what selection needs (below); the bytes of a batch of records are inflated on demand
     // from the blocks that hold them (RecFetch).  data == nullptr then.

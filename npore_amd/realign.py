@@ -132,8 +132,13 @@ def main():
     # Several ranks on one file: each walks a contiguous stretch of the record stream in one pass, cut at record starts taken
     # from the .bai linear index (bam.NativeBam.set_share) -- the counterpart of the reference feeding all its workers from
     # one sequential read (src/bam.pyx:18-47, src/realign.py:110-114); without a .bai, or with --max_reads (the ranks cannot
-    # know how many reads the others keep), the indexed reader.  The choice depends on the files and flags alone: every
-    # rank makes the same one.
+    # know how many reads the others keep), the indexed reader.  The index is another file and may be stale or somebody
+    # else's, so set_share locates and checks ALL the cuts on every rank (member starts, record starts: csrc/bam_reader.hpp
+    # bam_set_share) -- the choice depends on the two files, the flags and the number of ranks, never on the rank: every
+    # rank makes the same one.  (A rank that fell back on its own would take a share of ALL reads while the others walk
+    # their stretches: reads twice, reads missing, no error.)
+    # The .bai also says which contigs have reads, and the default regions leave out the others: the one-pass walk checks
+    # that claim against the records it meets, and a record on such a contig ends the run (bam.StaleIndex).
     world_size = dist_mod.world()[1]
     one_pass = (native and cfg.args.batch_reads > 0 and not getattr(cfg.args, "bed", None)
                 and os.environ.get("NPORE_BAM_ONE_PASS", "1") != "0" and bam_mod.NativeBam.is_bgzf(cfg.args.bam)
@@ -206,6 +211,10 @@ def main():
                 print(f"\nERROR: read #{k} of the selected reads: " +
                       ("CIGAR does not match sequence lengths; skipped." if st & 32 else f"inconsistent traceback (status {st})"))
             done = True
+        except bam_mod.StaleIndex as e:
+            # the regions came from the index's word on which contigs have reads: no reader can mend that here
+            print(f"\nERROR: {e}.")
+            sys.exit(1)
         except bam_mod.OnePassUnsupported as e:
             if world > 1 and "regions" not in str(e) and "region per contig" not in str(e):
                 # found in the DATA of one rank's stretch (a file that is not sorted): the other ranks may not have seen it,

@@ -76,4 +76,34 @@ try {
     return fail(NPORE_E_NOMEM, e.what());
 }
 
+// What bam_set_share decides for EVERY rank of `world` on one one-pass handle, without a walk: rc[rank] is its return
+// code, span[2 * rank] / span[2 * rank + 1] the stretch it leaves in the handle (offsets into the inflated stream; -1:
+// the end of the file).  Returns 0, or a negative code when the BAM itself does not open.
+int bam_walk_shares(const char *path, const char *bai, int world, int32_t *rc, int64_t *span)
+try {
+    std::unique_ptr<npore_bam> b(bam_open(path, 2, 3, nullptr));
+    if (!b) return NPORE_E_INVALID;
+    for (int rank = 0; rank < world; rank++) {
+        rc[rank] = bam_set_share(b.get(), rank, world, bai);
+        span[2 * rank] = b->share_begin == UINT64_MAX ? -1 : (int64_t)b->share_begin;
+        span[2 * rank + 1] = b->share_end == UINT64_MAX ? -1 : (int64_t)b->share_end;
+        if (rc[rank] == NPORE_OK && !b->has_share) return fail(NPORE_E_INVALID, "a share that the handle does not have");
+    }
+    return 0;
+} catch (const std::exception &e) {
+    return fail(NPORE_E_NOMEM, e.what());
+}
+
+// has[k] = 1 where a one-pass handle on `path` says that contig k has reads (from the .bai beside the file, or, with
+// none that it trusts, every contig).  Returns the number of contigs (the first `cap` are written), or a negative code.
+int bam_walk_refs_with_reads(const char *path, uint8_t *has, int cap)
+try {
+    std::unique_ptr<npore_bam> b(bam_open(path, 2, 3, nullptr));
+    if (!b) return NPORE_E_INVALID;
+    for (int k = 0; k < (int)b->ref_has_reads.size() && k < cap; k++) has[k] = b->ref_has_reads[(size_t)k];
+    return (int)b->ref_has_reads.size();
+} catch (const std::exception &e) {
+    return fail(NPORE_E_NOMEM, e.what());
+}
+
 }  // extern "C"

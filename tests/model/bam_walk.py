@@ -30,6 +30,10 @@ def load():
         lib.bam_walk_one_pass.argtypes = [C.c_char_p] + regions + [C.c_int64, C.c_int, C.c_int, C.c_char_p, C.c_int64, C.c_void_p, C.c_int64]
         lib.bam_walk_one_pass.restype = C.c_int64
         lib.bam_walk_last_error.restype = C.c_char_p
+        lib.bam_walk_shares.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.bam_walk_shares.restype = C.c_int
+        lib.bam_walk_refs_with_reads.argtypes = [C.c_char_p, C.c_void_p, C.c_int]
+        lib.bam_walk_refs_with_reads.restype = C.c_int
         _LIB = lib
     return _LIB
 
@@ -56,6 +60,27 @@ def _call(fn, path, regions, *args):
 def select(path, regions, max_reads=0):
     """offsets in the inflated stream of the records npore_bam_select keeps on a resident handle"""
     return _call(load().bam_walk_select, path, regions, int(max_reads))
+
+
+def shares(path, bai, world):
+    """what bam_set_share decides for every rank of `world`: (rc[world], [(begin, end)] per rank -- offsets into the
+    inflated stream, -1: the end of the file)"""
+    lib = load()
+    rc, span = np.zeros(world, np.int32), np.zeros(2 * world, np.int64)
+    r = lib.bam_walk_shares(os.fsencode(path), os.fsencode(bai) if bai else None, int(world), rc.ctypes.data, span.ctypes.data)
+    if r < 0:
+        raise WalkError(f"{r}: {lib.bam_walk_last_error().decode()}")
+    return rc.tolist(), [(int(span[2 * k]), int(span[2 * k + 1])) for k in range(world)]
+
+
+def refs_with_reads(path):
+    """the contigs that a one-pass handle on `path` says have reads"""
+    lib = load()
+    has = np.zeros(4096, np.uint8)
+    n = lib.bam_walk_refs_with_reads(os.fsencode(path), has.ctypes.data, len(has))
+    if n < 0:
+        raise WalkError(f"{n}: {lib.bam_walk_last_error().decode()}")
+    return {k for k in range(n) if has[k]}
 
 
 def one_pass(path, regions, max_reads=0, rank=0, world=1, bai=None, batch_reads=7):

@@ -917,20 +917,7 @@ def test_fill_step_asm_is_generated_and_counter_clean(tmp_path):
     assert any(rule == "R3" for rule, _, _, _ in chk.findings(1, [ln for ln in G.gen_role(1)][:-1]))
 
 
-def _share_test_bam(tmp_path):
-    """400 records of 200 ... 900 bases on two contigs (300 + 100), sorted.  Returns (BAM path, records)."""
-    recs, pos = [], 0
-    rng = np.random.default_rng(3)
-    for k in range(400):
-        n = int(rng.integers(200, 900))
-        seq = "".join(rng.choice(list("ACGT"), n))
-        recs.append(dict(name=f"r{k}", flag=0, ref_id=k // 300, pos=pos % 200_000, cigar=[(0, n)], seq=seq, qual=bytes(rng.integers(0, 94, n, dtype=np.uint8)), hp=None))
-        pos += int(rng.integers(100, 1200))
-        if k == 299:
-            pos = 0
-    path = str(tmp_path / "s.bam")
-    bam.write_bam(path, [("a", 300_000), ("b", 300_000)], recs, level=1)
-    return path, recs
+from bai_trust_cases import share_test_bam as _share_test_bam    # (400 records on two contigs: the file of the share tests)
 
 
 def test_bam_shares_begin_at_record_starts(tmp_path):

@@ -410,6 +410,18 @@ int npore_bam_set_output(npore_bam *bam, int format, const char *bai_path, int f
 #define NPORE_TAG_CS 1
 #define NPORE_TAG_CS_LONG 2
 #define NPORE_TAG_DE 4
+/* One more bit of the same word (here, and in `tags` of the *_full_tags / *_full_pass entry points below) that is the CIGAR's
+ * FORM and not a tag (`--eqx`): the final CIGAR of every FULL record goes out with `=` and `X` in the place of `M`, as
+ * `minimap2 --eqx` writes it (csrc/eqx_rec.hpp).  Every compared position is X where NM counts it (the codes differ or either
+ * is 0) and = otherwise, whatever the op it lay under; the positions are run-length coded through neighbouring compared words
+ * up to the next I D N S H P word, which is copied; words of length 0 are left out; the input's clip words stay around the
+ * result.  So NM = bases under I, D and X, and NM, MD, cs and de are those of the run without the bit.  More than 65 535
+ * operations, which this form reaches several times sooner, go to CG:B,I as always.  Valid where the tags are: behind
+ * NPORE_OUT_BAM + NPORE_OUT_FULL; set back by every npore_bam_set_output; a record that passes is written as it came.  Split
+ * on the device in the default pipeline (eqx_size_kernel, emit_eqx_kernel), by the host twin otherwise.
+ * Its value is 32 and not the word's next bit: 8, 16 and 64 have been refused as undefined since the tags came, and callers
+ * that probe for them keep their answer. */
+#define NPORE_CIGAR_EQX 32
 int npore_bam_set_output_tags(npore_bam *bam, int tags);
 /* npore_bam_format_bam_full_md and npore_debug_format_bam_full_md_device with `tags` (NPORE_TAG_*; 0: their bytes) */
 int npore_bam_format_bam_full_tags(npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,

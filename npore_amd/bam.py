@@ -496,18 +496,56 @@ def de_of(ref_codes, seq_codes, final):
     return np.float32((x + g) / (e + x + g)) if e + x + g else np.float32(0.0)
 
 
-def output_tags(cs, de):
-    """NPORE_TAG_* of the options cs (None, "short", "long") and de"""
+def eqx_of(ref_codes, seq_codes, final):
+    """The =/X form of a final CIGAR text over the code arrays align() got (csrc/eqx_rec.hpp, beside nm_of, md_of and cs_of):
+    every position under M, = or X -- whichever it was -- is X where nm_of counts it (the codes differ or either is 0; a
+    position beyond an array has code 0) and = otherwise; the positions are run-length coded, a run going on through
+    neighbouring M / = / X words; a word of any other op and length > 0 ends the run and follows it as it is; a word of
+    length 0 is left out."""
+    import re
+    code = lambda arr, at: int(arr[at]) if at < len(arr) else 0
+    out, cls, run, a, b = [], "", 0, 0, 0
+    for n, op in re.findall(r"(\d+)([MIDNSHP=X])", final):
+        n = int(n)
+        if n == 0:
+            continue
+        if op in "M=X":
+            for q in range(n):
+                rc, sc = code(ref_codes, a + q), code(seq_codes, b + q)
+                c = "X" if rc != sc or rc == 0 or sc == 0 else "="
+                if run and c != cls:
+                    out.append(f"{run}{cls}")
+                    run = 0
+                cls, run = c, run + 1
+            a, b = a + n, b + n
+            continue
+        if run:
+            out.append(f"{run}{cls}")
+            run = 0
+        out.append(f"{n}{op}")
+        if op in "DN":
+            a += n
+        elif op in "IS":
+            b += n
+    if run:
+        out.append(f"{run}{cls}")
+    return "".join(out)
+
+
+def output_tags(cs, de, eqx=False):
+    """The word npore_bam_set_output_tags takes: NPORE_TAG_* of the options cs (None, "short", "long") and de, and
+    NPORE_CIGAR_EQX of eqx"""
     if cs not in (None, "short", "long"):
         raise ValueError("cs must be None, 'short' or 'long'")
-    return {None: 0, "short": 1, "long": 3}[cs] | (4 if de else 0)
+    return {None: 0, "short": 1, "long": 3}[cs] | (4 if de else 0) | (32 if eqx else 0)
 
 
-def full_record(raw, ref_codes, seq_codes, final, md=False, cs=None, de=False):
+def full_record(raw, ref_codes, seq_codes, final, md=False, cs=None, de=False, eqx=False):
     """The FULL record (--records full, with its block_size word) of the input record `raw` (block_size word first) with
     its final CIGAR: the statement npore_bam_format_bam_full and the device path are tested against.  md: with the MD tag
     (md_of) behind NM, as NPORE_OUT_MD writes it; cs ("short" / "long") and de: with cs_of / de_of behind that, as
-    NPORE_TAG_CS / NPORE_TAG_DE write them."""
+    NPORE_TAG_CS / NPORE_TAG_DE write them; eqx: the final CIGAR in its =/X form (eqx_of) between the clip words, as
+    NPORE_CIGAR_EQX writes it -- the tags are those of `final` either way."""
     import re
     raw = bytes(raw)
     ref_id, pos, l_rn, mapq, _bin, n_cig, flag, l_seq, nref, npos, tlen = struct.unpack_from("<iiBBHHHiiii", raw, 4)
@@ -530,7 +568,7 @@ def full_record(raw, ref_codes, seq_codes, final, md=False, cs=None, de=False):
         trail.insert(0, rest.pop())
     if rest and rest[-1][0] == 4:
         trail.insert(0, rest.pop())
-    fin = [("MIDNSHP=X".index(op), int(n)) for n, op in re.findall(r"(\d+)([MIDNSHP=X])", final)]
+    fin = [("MIDNSHP=X".index(op), int(n)) for n, op in re.findall(r"(\d+)([MIDNSHP=X])", eqx_of(ref_codes, seq_codes, final) if eqx else final)]
     words = b"".join(struct.pack("<I", (n << 4) | op) for op, n in lead + fin + trail)
     nm = nm_of(ref_codes, seq_codes, final)
     tags = filter_aux(aux) + b"NM" + (b"C" + struct.pack("<B", nm) if nm <= 0xFF else b"S" + struct.pack("<H", nm) if nm <= 0xFFFF
@@ -1298,11 +1336,11 @@ class NativeBam:
                                                    fl.ctypes.data, st.ctypes.data, threads, C.byref(recs), C.byref(recs_len)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False, cs=None, de=False, pass_mask=0):
+    def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False, cs=None, de=False, pass_mask=0, eqx=False):
         """FULL records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam_full_pass,
         the widest entry of the ladder, whose narrower ones forward to it with zeros; md: with the MD tag behind NM,
         NPORE_OUT_MD; cs "short" / "long", de: with those tags behind MD, NPORE_TAG_*; pass_mask: the records with one of
-        those flag bits as they came)."""
+        those flag bits as they came; eqx: the final CIGARs in =/X form, NPORE_CIGAR_EQX)."""
         import ctypes as C
         idx = np.ascontiguousarray(idx, np.int64)
         n = len(idx)
@@ -1316,11 +1354,11 @@ class NativeBam:
         recs, recs_len = C.c_void_p(), C.c_int64()
         args = (self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
                 st.ctypes.data, threads, C.byref(recs), C.byref(recs_len))
-        self._check(self._lib.npore_bam_format_bam_full_pass(*args, 32 if md else 0, output_tags(cs, de), int(pass_mask)))
+        self._check(self._lib.npore_bam_format_bam_full_pass(*args, 32 if md else 0, output_tags(cs, de, eqx), int(pass_mask)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
     def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False, cs=None, de=False,
-                   pass_mask=0):
+                   pass_mask=0, eqx=False):
         """What the NEXT realign_file / realign_sequential / write_file on this handle appends to its output path
         (npore_bam_set_output; the setting holds for that one run): "sam", or "bam" -- records in stored BGZF members behind
         what lies in the file (the header's members: create_bam_header) and `bai` written when the records went out in
@@ -1333,6 +1371,7 @@ class NativeBam:
         recounted NM of every FULL record (NPORE_OUT_MD; records "full" only).  cs: "short" or "long", minimap2's cs tag behind
         that, de: its de tag behind that (npore_bam_set_output_tags, NPORE_TAG_*; records "full" only).  pass_mask: a subset of
         PASS_FLAGS -- the records with one of those flag bits are written as they came (npore_bam_set_output_pass; records
+        "full" only).  eqx: the final CIGAR of every FULL record in =/X form (NPORE_CIGAR_EQX, in the tags' word; records
         "full" only)."""
         if pass_mask and records != "full":
             raise ValueError("pass_mask needs records 'full'")
@@ -1344,9 +1383,9 @@ class NativeBam:
             raise ValueError("records 'full' needs out_format 'bam'")
         if md and records != "full":
             raise ValueError("md needs records 'full'")
-        tags = output_tags(cs, de)
+        tags = output_tags(cs, de, eqx)
         if tags and records != "full":
-            raise ValueError("cs and de need records 'full'")
+            raise ValueError("cs, de and eqx need records 'full'")
         if compress != "none" and out_format != "bam":
             raise ValueError("compress needs out_format 'bam'")
         flags = 0 if out_format != "bam" else 1 if eof else 2       # NPORE_OUT_EOF / NPORE_OUT_PART
@@ -1422,13 +1461,13 @@ class NativeBam:
 
     def realign_sequential(self, ctx, fasta, regions, out_path, batch_reads=4000, max_reads=0, r=30, max_b_rows=20000,
                            indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, out_format="sam", bai=None, eof=True,
-                           compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0):
+                           compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0, eqx=False):
         """ONE PASS over the file: inflate, filter by `regions` [(contig, start, stop)] (at most one per contig, in header
         order), batch, realign, write -- npore_bam_realign_sequential.  Returns (reads selected, [(ordinal, status)] of
         the first bad reads, (refused, inconsistent)) -- the reads selected include the records that pass through (pass_mask),
         which are not bad reads; raises OnePassUnsupported when the regions or the file's
         order rule the one-pass run out (the caller truncates the output and takes the indexed path).
-        out_format / bai / eof / compress / records / md / cs / de / pass_mask: set_output for this run ("bam": records instead
+        out_format / bai / eof / compress / records / md / cs / de / pass_mask / eqx: set_output for this run ("bam": records instead
         of text)."""
         ids = {n: i for i, n in enumerate(self.references)}
         rid = np.array([ids.get(c, -2) for c, _, _ in regions], np.int32)
@@ -1439,7 +1478,7 @@ class NativeBam:
         counts = np.zeros(3, np.int64)
         bad_ord, bad_st = np.zeros(max(bad_cap, 1), np.int64), np.zeros(max(bad_cap, 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask)
+        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask, eqx)
         rc = self._lib.npore_bam_realign_sequential(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, len(regions), rid.ctypes.data,
                                                     beg.ctypes.data, end.ctypes.data, int(max_reads or 0), int(batch_reads), indel_start,
                                                     indel_extend, max_b_rows, r, threads, os.fsencode(out_path), counts.ctypes.data,
@@ -1476,15 +1515,15 @@ class NativeBam:
 
     def realign_file(self, ctx, fasta, idx, out_sam, batch_reads=4000, r=30, max_b_rows=20000, indel_start=5.0,
                      indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False,
-                     cs=None, de=False, pass_mask=0):
+                     cs=None, de=False, pass_mask=0, eqx=False):
         """All selected reads, batch by batch, appended to out_sam by the library with packing, GPU work and
         formatting/writing of neighbouring batches overlapped.  Returns status[n] (ST_PASSED: written as it came).
-        out_format / bai / eof / compress / records / md / cs / de / pass_mask: set_output for this run ("bam": records instead of
+        out_format / bai / eof / compress / records / md / cs / de / pass_mask / eqx: set_output for this run ("bam": records instead of
         text); with pass_mask, idx comes from select(..., pass_mask=pass_mask)."""
         idx = np.ascontiguousarray(idx, np.int64)
         st = np.zeros(max(len(idx), 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask)
+        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask, eqx)
         self._check(self._lib.npore_bam_realign_file(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data,
                                                      len(idx), int(batch_reads), indel_start, indel_extend, max_b_rows, r,
                                                      threads, os.fsencode(out_sam), st.ctypes.data))
@@ -1531,7 +1570,7 @@ class NativeBam:
 
 
 def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0, out_format="sam", bai=None,
-                   eof=True, compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0):
+                   eof=True, compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0, eqx=False):
     """realign_reads() through the library; returns the number of reads handed in.  batch_reads > 0: the whole
     index list in overlapped batches written by the library itself; 0: one batch, text written here.
     threads: host threads of the parallel host stages (0 = all cores; one process per GPU: dist.host_threads_per_rank).
@@ -1543,7 +1582,7 @@ def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_
     if batch_reads > 0:
         text, status = None, bam.realign_file(ctx, fasta, idx, out_sam, batch_reads=batch_reads, r=r, max_b_rows=max_b_rows,
                                               threads=threads, out_format=out_format, bai=bai, eof=eof, compress=compress,
-                                              records=records, md=md, cs=cs, de=de, pass_mask=pass_mask)
+                                              records=records, md=md, cs=cs, de=de, pass_mask=pass_mask, eqx=eqx)
     else:
         text, status = bam.realign_batch(ctx, fasta, idx, r=r, max_b_rows=max_b_rows, threads=threads)
     bad = np.nonzero(np.asarray(status) & ~ST_PASSED)[0]       # (a record that passed through is no bad read)

@@ -16,6 +16,9 @@
 //   NM       nm_count_kernel                   (nm_rec.hpp)
 //   MD       md_size_kernel, emit_md_kernel    (md_rec.hpp, NPORE_OUT_MD): ONE walk, md_walk, launched with two sinks
 //   cs, de   cs_size_kernel, emit_cs_kernel    (cs_rec.hpp, NPORE_TAG_*): ONE walk, cs_walk, likewise
+// and, the same way, in the CIGAR's =/X form where that is asked for:
+//   =/X      eqx_size_kernel, emit_eqx_kernel  (eqx_rec.hpp, NPORE_CIGAR_EQX): ONE walk, eqx_walk, likewise -- the placement
+//                                              takes the number of split words, the assembly leaves their span to the walk
 // A final CIGAR of more than 65 535 operations goes out as htslib writes it (bam_reader.hpp RECORD): two placeholder words
 // in the CIGAR's place, the real words in a CG:B,I tag behind the other tags, in either form.
 // The host then takes the batch's bytes as they lie (BgzfStoredWriter) and the records' lengths for its index.
@@ -27,6 +30,7 @@
 
 #include "../../include/npore_amd.h"
 #include "cs_rec.hpp"
+#include "eqx_rec.hpp"
 #include "md_rec.hpp"
 #include "nm_rec.hpp"
 #include "unpack_kernels.hpp"
@@ -60,6 +64,9 @@ struct BamEmitParams {
     // FULL records, npore_bam_set_output_pass: reads whose staged flag has one of these bits pass (staged_head.hpp) -- their staged
     // head is the whole input record and so is their output record; nm, md_len, cs_len and de are 0 for them
     uint32_t pass_mask = 0;
+    // NPORE_CIGAR_EQX (eqx_size_kernel): the words of the read's final CIGAR in =/X form (0 for a refused or passing read); null:
+    // the final words go out as they are
+    int32_t *eqx_len = nullptr;    // [n_reads]
 };
 
 __device__ __forceinline__ void st32(uint8_t *q, uint32_t w)      // little-endian, unaligned
@@ -294,7 +301,7 @@ struct BamFullShape {
     const uint8_t *f, *cg, *sq;
     int nc, ci, cj, nmb;
     bool lng, pass;                // pass: the record is the staged head's bytes (staged_head.hpp); only f and size are set
-    int64_t wl, n_cig, l_seq, aux, size;
+    int64_t wl, n_cig, l_seq, aux, size;      // wl: bytes of the final words as they go out (NPORE_CIGAR_EQX: of the split ones)
     int64_t mdb;                   // bytes of the MD tag behind NM (4 + its text; 0: none)
     int64_t csb, deb;              // bytes of the cs tag behind that (4 + its text; 0: none) and of the de tag (7; 0: none)
 };
@@ -316,7 +323,7 @@ __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, i
     if (s.ci < s.cj && op_of(s.ci) == 4) s.ci++;
     if (s.cj > s.ci && op_of(s.cj - 1) == 5) s.cj--;
     if (s.cj > s.ci && op_of(s.cj - 1) == 4) s.cj--;
-    s.wl = p.words_len[g] > 0 ? p.words_len[g] : 0;
+    s.wl = p.eqx_len ? 4 * (int64_t)p.eqx_len[k] : p.words_len[g] > 0 ? p.words_len[g] : 0;
     s.n_cig = s.ci + (s.wl >> 2) + (s.nc - s.cj);
     s.lng = s.n_cig > 0xFFFF;
     s.l_seq = (int32_t)ld32(s.f + 16);
@@ -332,6 +339,12 @@ __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, i
     return s;
 }
 __device__ __forceinline__ int64_t bam_full_record_size(const BamEmitParams &p, int64_t k) { return bam_full_shape(p, k).size; }
+// where the CIGAR words of read k's record lie: behind the name, or (long) behind the tags and CG:B,I's eight bytes
+__device__ __forceinline__ uint8_t *bam_full_words_at(const BamEmitParams &p, int64_t k, const BamFullShape &s)
+{
+    uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8];
+    return s.lng ? o + 8 + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb + s.csb + s.deb + 8 : o;
+}
 
 // one wavefront per read
 __global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
@@ -373,7 +386,7 @@ __global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
         o += 4 * s.n_cig;
     }
     wave_copy<0>(cw, s.cg, 4 * (int64_t)s.ci, false, lane);
-    wave_copy<0>(cw + 4 * s.ci, p.words + p.words_off[g], s.wl, false, lane);
+    if (!p.eqx_len) wave_copy<0>(cw + 4 * s.ci, p.words + p.words_off[g], s.wl, false, lane);      // (=/X form: emit_eqx_kernel's span)
     wave_copy<0>(cw + 4 * s.ci + s.wl, s.cg + 4 * (int64_t)s.cj, 4 * (int64_t)(s.nc - s.cj), false, lane);
     wave_copy<0>(o, s.sq, body, false, lane);                    // bases, qualities, kept aux: as they lie in the staged head
     o += body;
@@ -648,8 +661,109 @@ __global__ __launch_bounds__(64) void emit_cs_kernel(BamEmitParams p)
     }
 }
 
+// ---- the =/X form of a FULL record's CIGAR (NPORE_CIGAR_EQX; eqx_rec.hpp states the rule and holds the sequential twin) ----
+// cs_walk's frame: one wavefront per read over tiles of 64 CIGAR words, the words of length > 0 of a tile visited in word
+// order.  The open run (`cls`, its op, and `run`, its positions; run == 0: none) and `cnt` (words out so far) are the same
+// in every lane and are carried across rounds, words and tiles.
+//   a word that is not compared: lane 0 closes the open run -- its word at cnt -- and copies the word behind it.
+//   M-type word, 64 positions per round: the ballot of nm_differs gives every lane's class and the class of the lane below it
+//     (lane 0: the open run's).  A lane whose class differs from the one below is a BOUNDARY: it writes the run that ends in
+//     front of it -- the class below, the distance to the previous boundary of the round (the round's first boundary: run +
+//     its lane) -- at cnt + the boundaries below it.  The carry out: the last position's class; run + the round's positions
+//     where the round has no boundary, otherwise the positions from the last boundary on.
+// The walk is ONE function over a sink (eqx_rec.hpp): eqx_size_kernel runs it with EqxCount, emit_eqx_kernel with EqxStore, so
+// count and words cannot differ.  Returns the number of words.
+template <class Sink>
+__device__ __forceinline__ uint32_t eqx_walk(const BamEmitParams &p, int64_t k, int lane, const Sink &sink)
+{
+    const int64_t g = p.read_base + k;
+    const int64_t n = p.words_len[g] <= 0 ? 0 : p.words_len[g] >> 2;
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(p.words + p.words_off[g]);      // (the slots lie at multiples of 4)
+    const uint8_t *ref = p.refs + p.ref_off[k], *seq = p.seqs + p.seq_off[k];
+    const int64_t rl = p.ref_off[k + 1] - p.ref_off[k], sl = p.seq_off[k + 1] - p.seq_off[k];
+    const unsigned long long below_me = (1ull << lane) - 1ull;
+    int64_t a0 = 0, b0 = 0;                  // consumed in front of the tile
+    uint32_t cnt = 0, run = 0, cls = EQX_EQ;
+    auto close_run = [&]() {
+        if (run > 0) {
+            if (lane == 0) sink.put(cnt, run << 4 | cls);
+            cnt++;
+        }
+        run = 0;
+    };
+    for (int64_t t0 = 0; t0 < n; t0 += 64) {
+        const uint32_t v = t0 + lane < n ? w[t0 + lane] : 0u;       // (behind the end: `0M`)
+        const uint32_t op = v & 15u, len = v >> 4, use = nm_consumes(op);
+        const uint32_t ra = (use & 1u) ? len : 0u, qa = (use & 2u) ? len : 0u;
+        uint32_t ri = ra, qi = qa;           // inclusive sums over the tile
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t x = (uint32_t)__shfl_up((int)ri, d), y = (uint32_t)__shfl_up((int)qi, d);
+            if (lane >= d) { ri += x; qi += y; }
+        }
+        unsigned long long runs = __builtin_amdgcn_ballot_w64(len > 0);
+        while (runs) {
+            const int j = (int)__builtin_ctzll(runs);
+            runs &= runs - 1;
+            const uint32_t vj = (uint32_t)__shfl((int)v, j), lj = vj >> 4;
+            if (!nm_compares(vj & 15u)) {
+                close_run();
+                if (lane == 0) sink.put(cnt, vj);
+                cnt++;
+                continue;
+            }
+            const int64_t aj = a0 + (uint32_t)__shfl((int)(ri - ra), j), bj = b0 + (uint32_t)__shfl((int)(qi - qa), j);
+            for (uint32_t q0 = 0; q0 < lj; q0 += 64) {
+                const uint32_t q = q0 + (uint32_t)lane, in_round = min(64u, lj - q0);
+                const bool d = q < lj && nm_differs(ref, rl, aj + q, seq, sl, bj + q);
+                const unsigned long long ev = __builtin_amdgcn_ballot_w64(d);
+                const unsigned long long valid = in_round < 64u ? (1ull << in_round) - 1ull : ~0ull;
+                const bool opens = run > 0 && cls != ((ev & 1ull) ? EQX_X : EQX_EQ);       // lane 0 ends the carried run
+                const unsigned long long bd = ((ev ^ (ev << 1)) & valid & ~1ull) | (opens ? 1ull : 0ull);
+                if ((bd >> lane) & 1ull) {
+                    const unsigned long long before = bd & below_me;
+                    const uint32_t length = before ? (uint32_t)(lane - (63 - (int)__builtin_clzll(before))) : run + (uint32_t)lane;
+                    const uint32_t below = lane == 0 ? cls : ((ev >> (lane - 1)) & 1ull) ? EQX_X : EQX_EQ;
+                    sink.put(cnt + (uint32_t)__builtin_popcountll(before), length << 4 | below);
+                }
+                cnt += (uint32_t)__builtin_popcountll(bd);
+                run = bd ? in_round - (uint32_t)(63 - (int)__builtin_clzll(bd)) : run + in_round;
+                cls = ((ev >> (in_round - 1u)) & 1ull) ? EQX_X : EQX_EQ;
+            }
+        }
+        a0 += (uint32_t)__shfl((int)ri, 63);
+        b0 += (uint32_t)__shfl((int)qi, 63);
+    }
+    close_run();
+    return cnt;
+}
+
+// words of every read's final CIGAR in =/X form (0: the read is refused or passes), beside md_size_kernel and cs_size_kernel in
+// front of the placement, which takes the record's n_cigar_op, its CG decision and its size from it (bam_full_shape)
+__global__ __launch_bounds__(64) void eqx_size_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    const bool none = (p.status[p.read_base + k] & 32) || staged_passes(p.raw + p.raw_off[k] + 4, p.pass_mask);
+    const uint32_t cnt = none ? 0u : eqx_walk(p, k, lane, EqxCount{});
+    if (lane == 0) p.eqx_len[k] = (int32_t)cnt;
+}
+
+// the split words between the record's clip words, in the CIGAR field or (long) behind CG:B,I's count: the span that
+// emit_bam_full_kernel, in front of this one on its stream, left out
+__global__ __launch_bounds__(64) void emit_eqx_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    if (p.rec_len[k] <= 0) return;
+    const BamFullShape s = bam_full_shape(p, k);
+    if (s.pass) return;
+    eqx_walk(p, k, lane, EqxStore{bam_full_words_at(p, k, s) + 4 * s.ci, (int64_t)p.eqx_len[k]});
+}
+
 // What a group's records take, in order, on stream s: the reference form's two kernels, or (full) the FULL form's with the tags
-// that p names -- p.md_len: MD; p.tags: cs / de.
+// that p names -- p.md_len: MD; p.tags' NPORE_TAG_CS / NPORE_TAG_DE: cs / de -- and (p.eqx_len) the CIGAR's =/X form.
 inline void launch_bam_emit(const BamEmitParams &p, bool full, hipStream_t s)
 {
     const dim3 reads((unsigned)p.n_reads), wave(64);             // one wavefront per read; the placements: one workgroup
@@ -658,13 +772,16 @@ inline void launch_bam_emit(const BamEmitParams &p, bool full, hipStream_t s)
         hipLaunchKernelGGL(emit_bam_records_kernel, reads, wave, 0, s, p);
         return;
     }
+    const bool cs_de = (p.tags & (NPORE_TAG_CS | NPORE_TAG_DE)) != 0;
     hipLaunchKernelGGL(nm_count_kernel, reads, wave, 0, s, p);
     if (p.md_len) hipLaunchKernelGGL(md_size_kernel, reads, wave, 0, s, p);
-    if (p.tags) hipLaunchKernelGGL(cs_size_kernel, reads, wave, 0, s, p);
+    if (cs_de) hipLaunchKernelGGL(cs_size_kernel, reads, wave, 0, s, p);
+    if (p.eqx_len) hipLaunchKernelGGL(eqx_size_kernel, reads, wave, 0, s, p);
     hipLaunchKernelGGL(place_bam_full_kernel, dim3(1), dim3(256), 0, s, p);
     hipLaunchKernelGGL(emit_bam_full_kernel, reads, wave, 0, s, p);
     if (p.md_len) hipLaunchKernelGGL(emit_md_kernel, reads, wave, 0, s, p);
-    if (p.tags) hipLaunchKernelGGL(emit_cs_kernel, reads, wave, 0, s, p);
+    if (cs_de) hipLaunchKernelGGL(emit_cs_kernel, reads, wave, 0, s, p);
+    if (p.eqx_len) hipLaunchKernelGGL(emit_eqx_kernel, reads, wave, 0, s, p);
 }
 
 }  // namespace npore

@@ -8,6 +8,7 @@
 #include "hostio.hpp"
 #include "deflate_code.hpp"
 #include "cs_rec.hpp"
+#include "eqx_rec.hpp"
 #include "md_rec.hpp"
 #include "nm_rec.hpp"
 
@@ -725,6 +726,9 @@ inline int format_sam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
 //   - with NPORE_TAG_CS / NPORE_TAG_DE (`--cs`, `--de`, npore_bam_set_output_tags) cs and de (cs_rec.hpp) follow MD: 'c' 's' 'Z',
 //     the text, NUL -- 4 + its length bytes -- and 'd' 'e' 'f' and a float -- 7 bytes: kept aux, NM, MD, cs, de, CG.  They are
 //     minimap2's but for what NM already differs in: an IUPAC letter other than N counts as a mismatch.
+//   - with NPORE_CIGAR_EQX (`--eqx`, the same setter's word) the final standardised CIGAR stands between the clip words in its
+//     =/X form (eqx_rec.hpp): every compared position = or X by NM's predicate, run-length coded through neighbouring compared
+//     words.  n_cigar counts the split words, so the placeholder + CG form begins several times sooner; the tags do not change.
 //   Size: 36 + l_read_name + 4 * n_cigar (8 when long) + (l_seq + 1) / 2 + l_seq + kept aux + 3 + {1, 2, 4} (+ 4 + MD text)
 //   (+ 8 + 4 * n when long).
 // FILE.  BGZF with STORED deflate members (level 0, what `samtools view -u` writes): 18 bytes of gzip header with the BC
@@ -990,7 +994,8 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     // and written between the two passes; a text that is no CIGAR leaves the read's vector empty: -1 words)
     std::vector<std::vector<uint8_t>> words(rec.full ? (size_t)n : 0);
     auto n_words = [&](int64_t k) { return (int64_t)words[(size_t)k].size() / 4 - 1; };
-    std::vector<std::string> md(rec.md ? (size_t)n : 0), more(rec.tags ? (size_t)n : 0);
+    const int cs_de = rec.cs_de();
+    std::vector<std::string> md(rec.md ? (size_t)n : 0), more(cs_de ? (size_t)n : 0);
     std::atomic<int> bad{0};
     const uint32_t pass_mask = rec.pass_mask;
     // a record that passes: the input's bytes; the index gets the input record's own reference length
@@ -1004,7 +1009,7 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     auto record = [&](int64_t k, uint8_t *dst, BamRecMeta *m) {
         if (staged_passes(rec_of(rf, k).p, pass_mask)) return passed(k, dst, m);
         return rec.full ? bam_record_full_words_into(rec_of(rf, k), words[(size_t)k].data(), n_words(k), status[k], nm[(size_t)k], dst, m,
-                                                     rec.md ? &md[(size_t)k] : nullptr, rec.tags ? &more[(size_t)k] : nullptr)
+                                                     rec.md ? &md[(size_t)k] : nullptr, cs_de ? &more[(size_t)k] : nullptr)
                         : bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], dst, m);
     };
     parallel_for(n, threads, [&](int64_t k) {
@@ -1016,7 +1021,9 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
             const int64_t rl = codes.ref_off[k + 1] - codes.ref_off[k], sl = codes.seq_off[k + 1] - codes.seq_off[k];
             nm[(size_t)k] = nm_of_words(w, ops, ref, rl, seq, sl);
             if (rec.md) md_of_words(w, ops, ref, rl, seq, sl, md[(size_t)k]);
-            if (rec.tags) cs_de_tags_of_words(rec.tags, w, ops, ref, rl, seq, sl, more[(size_t)k]);
+            if (cs_de) cs_de_tags_of_words(cs_de, w, ops, ref, rl, seq, sl, more[(size_t)k]);
+            // (NPORE_CIGAR_EQX: the record takes the split words; NM, MD, cs and de are the same on either form)
+            if (rec.eqx()) words[(size_t)k] = eqx_of_words(w, ops, ref, rl, seq, sl);
         }
         const int64_t sz = record(k, nullptr, nullptr);
         if (sz < 0) bad++;

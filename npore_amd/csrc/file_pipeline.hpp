@@ -233,7 +233,7 @@ int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta
             reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = pm.rec.full ? aux : rec_hp(r);
             s.rec_cap += pm.rec.full ? full_record_bound(r.l_read_name(), rl + sl, r.l_seq(), aux) : ref_record_bound(r.l_read_name(), rl + sl, sl);
             if (pm.rec.md) s.rec_cap += md_tag_bound(rl, 1);
-            if (pm.rec.tags) s.rec_cap += cs_de_tags_bound(rl + sl);
+            if (pm.rec.cs_de()) s.rec_cap += cs_de_tags_bound(rl + sl);      // (NPORE_CIGAR_EQX adds nothing: eqx_rec.hpp, Size)
         }
     }
     if (int rc = s.raw.ensure((size_t)s.rawo[(size_t)n] + 64)) return rc;

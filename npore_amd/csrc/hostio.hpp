@@ -551,15 +551,17 @@ struct BamRecMeta {
 struct RecSpec {
     bool full = false;                    // NPORE_OUT_FULL: FULL records (bam_reader.hpp FULL RECORD) ...
     bool md = false;                      // ... NPORE_OUT_MD: with the MD tag behind NM
-    int tags = 0;                         // ... NPORE_TAG_*: with cs / de behind that
+    int tags = 0;                         // ... the setters' word: NPORE_TAG_* (cs / de behind that) and NPORE_CIGAR_EQX
     uint32_t pass_mask = 0;               // ... records with one of these flag bits pass through (staged_head.hpp)
+    int cs_de() const { return tags & (NPORE_TAG_CS | NPORE_TAG_CS_LONG | NPORE_TAG_DE); }      // the tags of the word (0: neither cs nor de)
+    bool eqx() const { return (tags & NPORE_CIGAR_EQX) != 0; }                                  // its other bit: the final CIGAR in =/X form
 };
 // THE rules of the output options: defined bits only, CS_LONG beside CS, md / tags / pass on FULL records, FULL records in BAM
 inline bool rec_spec_of(int format, int flags, int tags, int pass, RecSpec &out)
 {
     const int all_flags = NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE | NPORE_OUT_MATCH | NPORE_OUT_FULL | NPORE_OUT_MD;
     const bool full = (flags & NPORE_OUT_FULL) != 0;
-    if ((flags & ~all_flags) || (tags & ~(NPORE_TAG_CS | NPORE_TAG_CS_LONG | NPORE_TAG_DE)) || (pass & ~(int)PASS_FLAGS) ||
+    if ((flags & ~all_flags) || (tags & ~(NPORE_TAG_CS | NPORE_TAG_CS_LONG | NPORE_TAG_DE | NPORE_CIGAR_EQX)) || (pass & ~(int)PASS_FLAGS) ||
         ((tags & NPORE_TAG_CS_LONG) && !(tags & NPORE_TAG_CS)) || (!full && ((flags & NPORE_OUT_MD) || tags || pass)) ||
         (full && format != NPORE_OUT_BAM))
         return false;

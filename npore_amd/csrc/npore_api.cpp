@@ -1613,14 +1613,16 @@ try {
         bound += pass ? staged_pass_bytes(r.p) : full_record_bound(r.l_read_name(), ops, r.l_seq(), aux[k]);
         if (bad || pass) continue;
         fin[k] = cigar_text_words(finals + final_off[k], final_len[k], ops);
-        int64_t ref_covered = 0, covered = 0;      // (a caller's final may cover more reference than the read has, and close a count at every word)
+        int64_t ref_covered = 0, covered = 0, compared = 0;      // (a caller's final may cover more reference than the read has, and close a count at every word)
         for (int64_t q = 0; q < ops; q++) {
             const uint32_t w = rd32(fin[k].data() + 4 * q), use = nm_consumes(w & 15u);
             if (use & 1u) ref_covered += w >> 4;
             if (use) covered += w >> 4;
+            if (nm_compares(w & 15u)) compared += w >> 4;
         }
         if (rec.md) bound += md_tag_bound(ref_covered, ops + 1);
-        if (rec.tags) bound += cs_de_tags_bound(covered);
+        if (rec.cs_de()) bound += cs_de_tags_bound(covered);
+        if (rec.eqx()) bound += 4 * compared;      // (=/X form: at most a word per compared position more, eqx_rec.hpp)
     }
     std::vector<uint8_t> raw((size_t)rawo[N] + 64, 0), words((size_t)wo[N] + 64, 0);
     for (size_t k = 0; k < N; k++) {

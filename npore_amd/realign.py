@@ -80,6 +80,11 @@ def argparser():
     parser.add_argument("--de", action="store_true",
                         help="--records full: write minimap2's de tag (gap-compressed per-base divergence, a float) behind cs, "
                              "counted on the GPU in the same walk.  Without it the records carry no de: the input's is stale.")
+    parser.add_argument("--eqx", action="store_true",
+                        help="--records full: write the final CIGAR with `=` and `X` in the place of `M`, as `minimap2 --eqx` does, "
+                             "split on the GPU from the final CIGAR and the bases NM is counted on: X where NM counts a mismatch "
+                             "(an IUPAC letter other than N included), = elsewhere; NM, MD, cs and de do not change.  More than "
+                             "65 535 operations, which this form reaches sooner, go to the CG tag.  Without it the CIGAR has M.")
     parser.add_argument("--pass_through", action="store_true",
                         help="--records full: write the records the realigner does not take -- secondary (0x100), supplementary "
                              "(0x800) and placed but unmapped (0x4) ones -- as they came, every tag included, in their place among "
@@ -111,6 +116,10 @@ def main():
     cs, de = getattr(cfg.args, "cs", None), bool(getattr(cfg.args, "de", False))
     if (cs or de) and records != "full":
         print(f"\nERROR: {'--cs' if cs else '--de'} needs --out_format bam --records full.")
+        sys.exit(1)
+    eqx = bool(getattr(cfg.args, "eqx", False))
+    if eqx and records != "full":
+        print("\nERROR: --eqx needs --out_format bam --records full.")
         sys.exit(1)
     pass_mask = bam_mod.PASS_FLAGS if getattr(cfg.args, "pass_through", False) else 0
     if pass_mask and records != "full":
@@ -191,7 +200,7 @@ def main():
     # BAM: the index beside the file (a rank's part: a sidecar with part-relative offsets, merged by dist.gather_bam_parts);
     # the EOF member ends the whole file, not a part
     out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress, records=records, md=md, cs=cs, de=de,
-                  pass_mask=pass_mask) if as_bam else {}
+                  pass_mask=pass_mask, eqx=eqx) if as_bam else {}
     gather = dist_mod.gather_bam_parts if as_bam else dist_mod.gather_parts
 
     print("> extracting read data from BAM")

@@ -139,7 +139,7 @@ def start_output(a, out, nb):
     if a.out_format == "bam":
         bam.create_bam_header(out, nb)
         return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai", compress=a.bam_compress, records=a.records, md=a.md, cs=a.cs, de=a.de,
-                    pass_mask=bam.PASS_FLAGS if a.pass_through else 0)
+                    pass_mask=bam.PASS_FLAGS if a.pass_through else 0, eqx=a.eqx)
     bam.create_header(out, nb)
     return {}
 
@@ -266,6 +266,7 @@ def main():
     ap.add_argument("--md", action="store_true", help="--records full: with the MD tag behind NM, built on the GPU")
     ap.add_argument("--cs", choices=("short", "long"), default=None, help="--records full: with the cs tag behind NM / MD, built on the GPU")
     ap.add_argument("--de", action="store_true", help="--records full: with the de tag behind that, counted on the GPU")
+    ap.add_argument("--eqx", action="store_true", help="--records full: the final CIGAR with = and X in the place of M, split on the GPU")
     ap.add_argument("--tags", action="store_true",
                     help="every synthetic read carries an RG:Z tag and a B,C array of l_seq / 2 bytes (an ML-like load for --records full)")
     ap.add_argument("--flagged", type=float, default=0.0,
@@ -285,6 +286,8 @@ def main():
         ap.error("--md needs --records full")
     if (a.cs or a.de) and a.records != "full":
         ap.error("--cs / --de need --records full")
+    if a.eqx and a.records != "full":
+        ap.error("--eqx needs --records full")
     if a.pass_through and a.records != "full":
         ap.error("--pass_through needs --records full")
     if a.gen_into:
@@ -369,7 +372,7 @@ def main():
                 "one_pass": one_pass, "one_pass_output_identical": same_one_pass,
                 "reads": a.reads, "distinct_reads": a.reads if a.distinct <= 0 else min(a.distinct, a.reads),
                 "qualities": "constant 20" if a.const_qual else "uniform per base over phred 0 ... 93 (reference test/generate_bam.py:63,79)",
-                "ref_len": a.ref_len, "r": a.r, "batch": a.batch, "out_format": a.out_format, "bam_compress": a.bam_compress, "records": a.records, "md": a.md, "cs": a.cs, "de": a.de, "tags": a.tags,
+                "ref_len": a.ref_len, "r": a.r, "batch": a.batch, "out_format": a.out_format, "bam_compress": a.bam_compress, "records": a.records, "md": a.md, "cs": a.cs, "de": a.de, "eqx": a.eqx, "tags": a.tags,
                 "flagged": a.flagged, "pass_through": a.pass_through,
                 "output_bytes": os.path.getsize(out + ".o"),
                 "host_cpus": len(os.sched_getaffinity(0)), "bam_bytes": os.path.getsize(bp),

@@ -422,6 +422,17 @@ int npore_bam_set_output(npore_bam *bam, int format, const char *bai_path, int f
  * Its value is 32 and not the word's next bit: 8, 16 and 64 have been refused as undefined since the tags came, and callers
  * that probe for them keep their answer. */
 #define NPORE_CIGAR_EQX 32
+/* And one that is a tag again (`--oc`): the ORIGINAL CIGAR of every read whose alignment the run CHANGED, in the standard OC:Z
+ * tag, as the realigners that rewrite CIGARs in place keep it (csrc/oc_rec.hpp).  A read is unchanged iff its input CIGAR
+ * between the clip words -- words of length 0 dropped, = and X read as M, neighbouring words of equal op merged -- is its final
+ * CIGAR word for word; that does not depend on NPORE_CIGAR_EQX, NPORE_OUT_MD or the tags.  The text is every word of the input's
+ * real CIGAR as it stands (clips and words of length 0 included, those of CG:B,I for a long input): 'O' 'C' 'Z' text NUL behind
+ * NM, MD, cs and de, in front of CG.  The position never changes, so OC alone restores the record; no OP is written.  Under the
+ * bit an input's own OC is dropped with the stale tags, so no record carries two and an UNCHANGED read carries none; without
+ * the bit an input's OC stays as it came.  A record that passes is written as it came, its OC included.  Valid where the other
+ * bits are; set back by every npore_bam_set_output.  Decided, sized and written on the device in the default pipeline
+ * (oc_size_kernel, emit_oc_kernel), by the host twin otherwise.  Its value is 256: 8, 16, 64 and 128 stay refused. */
+#define NPORE_TAG_OC 256
 int npore_bam_set_output_tags(npore_bam *bam, int tags);
 /* npore_bam_format_bam_full_md and npore_debug_format_bam_full_md_device with `tags` (NPORE_TAG_*; 0: their bytes) */
 int npore_bam_format_bam_full_tags(npore_bam *bam, const npore_fasta *fa, const int32_t *fasta_of_ref, const int64_t *idx, int64_t n,

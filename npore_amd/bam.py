@@ -353,16 +353,18 @@ def _aux_value_len(aux, q, typ):
     return n if q + n <= len(aux) else None
 
 
-def filter_aux(aux):
-    """The tags a FULL record keeps of the input's aux bytes: all of them in input order but STALE_TAGS; a tag that cannot
-    be stepped over ends the list -- it and everything behind it are dropped."""
+def filter_aux(aux, oc=False):
+    """The tags a FULL record keeps of the input's aux bytes: all of them in input order but STALE_TAGS -- and, under the
+    option oc (NPORE_TAG_OC: the run writes its own), OC; a tag that cannot be stepped over ends the list -- it and
+    everything behind it are dropped."""
+    stale = STALE_TAGS + ((b"OC",) if oc else ())
     aux = bytes(aux)
     out, q = [], 0
     while q + 3 <= len(aux):
         n = _aux_value_len(aux, q + 3, aux[q + 2:q + 3])
         if n is None:
             break
-        if aux[q:q + 2] not in STALE_TAGS:
+        if aux[q:q + 2] not in stale:
             out.append(aux[q:q + 3 + n])
         q += 3 + n
     return b"".join(out)
@@ -532,20 +534,47 @@ def eqx_of(ref_codes, seq_codes, final):
     return "".join(out)
 
 
-def output_tags(cs, de, eqx=False):
-    """The word npore_bam_set_output_tags takes: NPORE_TAG_* of the options cs (None, "short", "long") and de, and
+def oc_of(words):
+    """The text of the OC tag (csrc/oc_rec.hpp) of an input CIGAR's words [(op, length)]: every word as it stands, its length
+    in decimal and its letter -- clips and words of length 0 included, nothing merged, nothing mapped."""
+    return "".join(f"{n}{'MIDNSHP=X???????'[op]}" for op, n in words)
+
+
+def cigar_changed(words, final_text):
+    """Whether a realignment CHANGED a read (csrc/oc_rec.hpp): words [(op, length)] is its input CIGAR between the clip words,
+    final_text its final CIGAR in M form.  The canonical form of the input -- words of length 0 dropped, = and X read as M,
+    neighbouring words of equal op merged -- is compared with the final's words as they stand: unchanged iff they are the
+    same words, in number too."""
+    import re
+    canon = []
+    for op, n in words:
+        if n == 0:
+            continue
+        op = 0 if op in (7, 8) else op
+        if canon and canon[-1][0] == op:
+            canon[-1][1] += n
+        else:
+            canon.append([op, n])
+    fin = [["MIDNSHP=X".index(op), int(n)] for n, op in re.findall(r"(\d+)([MIDNSHP=X])", final_text)]
+    return canon != fin
+
+
+def output_tags(cs, de, eqx=False, oc=False):
+    """The word npore_bam_set_output_tags takes: NPORE_TAG_* of the options cs (None, "short", "long"), de and oc, and
     NPORE_CIGAR_EQX of eqx"""
     if cs not in (None, "short", "long"):
         raise ValueError("cs must be None, 'short' or 'long'")
-    return {None: 0, "short": 1, "long": 3}[cs] | (4 if de else 0) | (32 if eqx else 0)
+    return {None: 0, "short": 1, "long": 3}[cs] | (4 if de else 0) | (32 if eqx else 0) | (256 if oc else 0)
 
 
-def full_record(raw, ref_codes, seq_codes, final, md=False, cs=None, de=False, eqx=False):
+def full_record(raw, ref_codes, seq_codes, final, md=False, cs=None, de=False, eqx=False, oc=False):
     """The FULL record (--records full, with its block_size word) of the input record `raw` (block_size word first) with
     its final CIGAR: the statement npore_bam_format_bam_full and the device path are tested against.  md: with the MD tag
     (md_of) behind NM, as NPORE_OUT_MD writes it; cs ("short" / "long") and de: with cs_of / de_of behind that, as
     NPORE_TAG_CS / NPORE_TAG_DE write them; eqx: the final CIGAR in its =/X form (eqx_of) between the clip words, as
-    NPORE_CIGAR_EQX writes it -- the tags are those of `final` either way."""
+    NPORE_CIGAR_EQX writes it -- the tags are those of `final` either way; oc: with the input's CIGAR as OC:Z (oc_of) behind
+    those where `final` is not the input's canonical form (cigar_changed), and without the input's own OC either way, as
+    NPORE_TAG_OC writes it."""
     import re
     raw = bytes(raw)
     ref_id, pos, l_rn, mapq, _bin, n_cig, flag, l_seq, nref, npos, tlen = struct.unpack_from("<iiBBHHHiiii", raw, 4)
@@ -571,7 +600,7 @@ def full_record(raw, ref_codes, seq_codes, final, md=False, cs=None, de=False, e
     fin = [("MIDNSHP=X".index(op), int(n)) for n, op in re.findall(r"(\d+)([MIDNSHP=X])", eqx_of(ref_codes, seq_codes, final) if eqx else final)]
     words = b"".join(struct.pack("<I", (n << 4) | op) for op, n in lead + fin + trail)
     nm = nm_of(ref_codes, seq_codes, final)
-    tags = filter_aux(aux) + b"NM" + (b"C" + struct.pack("<B", nm) if nm <= 0xFF else b"S" + struct.pack("<H", nm) if nm <= 0xFFFF
+    tags = filter_aux(aux, oc) + b"NM" + (b"C" + struct.pack("<B", nm) if nm <= 0xFF else b"S" + struct.pack("<H", nm) if nm <= 0xFFFF
                                       else b"I" + struct.pack("<I", nm))
     if md:
         tags += b"MDZ" + md_of(ref_codes, seq_codes, final).encode() + b"\0"
@@ -579,6 +608,8 @@ def full_record(raw, ref_codes, seq_codes, final, md=False, cs=None, de=False, e
         tags += b"csZ" + cs_of(ref_codes, seq_codes, final, long=cs == "long").encode() + b"\0"
     if de:
         tags += b"def" + struct.pack("<f", de_of(ref_codes, seq_codes, final))
+    if oc and cigar_changed(rest, final):
+        tags += b"OCZ" + oc_of(cigar).encode() + b"\0"
     if len(words) // 4 > MAX_CIGAR_OPS:
         tags += b"CGBI" + struct.pack("<I", len(words) // 4) + words
         words = struct.pack("<II", (l_seq << 4) | 4, (reflen << 4) | 3)
@@ -1336,11 +1367,12 @@ class NativeBam:
                                                    fl.ctypes.data, st.ctypes.data, threads, C.byref(recs), C.byref(recs_len)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False, cs=None, de=False, pass_mask=0, eqx=False):
+    def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False, cs=None, de=False, pass_mask=0, eqx=False, oc=False):
         """FULL records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam_full_pass,
         the widest entry of the ladder, whose narrower ones forward to it with zeros; md: with the MD tag behind NM,
         NPORE_OUT_MD; cs "short" / "long", de: with those tags behind MD, NPORE_TAG_*; pass_mask: the records with one of
-        those flag bits as they came; eqx: the final CIGARs in =/X form, NPORE_CIGAR_EQX)."""
+        those flag bits as they came; eqx: the final CIGARs in =/X form, NPORE_CIGAR_EQX; oc: OC:Z on the reads that changed,
+        NPORE_TAG_OC)."""
         import ctypes as C
         idx = np.ascontiguousarray(idx, np.int64)
         n = len(idx)
@@ -1354,11 +1386,11 @@ class NativeBam:
         recs, recs_len = C.c_void_p(), C.c_int64()
         args = (self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
                 st.ctypes.data, threads, C.byref(recs), C.byref(recs_len))
-        self._check(self._lib.npore_bam_format_bam_full_pass(*args, 32 if md else 0, output_tags(cs, de, eqx), int(pass_mask)))
+        self._check(self._lib.npore_bam_format_bam_full_pass(*args, 32 if md else 0, output_tags(cs, de, eqx, oc), int(pass_mask)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
     def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False, cs=None, de=False,
-                   pass_mask=0, eqx=False):
+                   pass_mask=0, eqx=False, oc=False):
         """What the NEXT realign_file / realign_sequential / write_file on this handle appends to its output path
         (npore_bam_set_output; the setting holds for that one run): "sam", or "bam" -- records in stored BGZF members behind
         what lies in the file (the header's members: create_bam_header) and `bai` written when the records went out in
@@ -1372,7 +1404,8 @@ class NativeBam:
         that, de: its de tag behind that (npore_bam_set_output_tags, NPORE_TAG_*; records "full" only).  pass_mask: a subset of
         PASS_FLAGS -- the records with one of those flag bits are written as they came (npore_bam_set_output_pass; records
         "full" only).  eqx: the final CIGAR of every FULL record in =/X form (NPORE_CIGAR_EQX, in the tags' word; records
-        "full" only)."""
+        "full" only).  oc: the input's CIGAR as OC:Z on every read whose alignment changed; the input's own OC is dropped, so an
+        unchanged read has none (NPORE_TAG_OC, in the tags' word; records "full" only)."""
         if pass_mask and records != "full":
             raise ValueError("pass_mask needs records 'full'")
         if compress not in ("none", "huffman", "match"):
@@ -1383,9 +1416,9 @@ class NativeBam:
             raise ValueError("records 'full' needs out_format 'bam'")
         if md and records != "full":
             raise ValueError("md needs records 'full'")
-        tags = output_tags(cs, de, eqx)
+        tags = output_tags(cs, de, eqx, oc)
         if tags and records != "full":
-            raise ValueError("cs, de and eqx need records 'full'")
+            raise ValueError("cs, de, eqx and oc need records 'full'")
         if compress != "none" and out_format != "bam":
             raise ValueError("compress needs out_format 'bam'")
         flags = 0 if out_format != "bam" else 1 if eof else 2       # NPORE_OUT_EOF / NPORE_OUT_PART
@@ -1461,14 +1494,14 @@ class NativeBam:
 
     def realign_sequential(self, ctx, fasta, regions, out_path, batch_reads=4000, max_reads=0, r=30, max_b_rows=20000,
                            indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, out_format="sam", bai=None, eof=True,
-                           compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0, eqx=False):
+                           compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0, eqx=False, oc=False):
         """ONE PASS over the file: inflate, filter by `regions` [(contig, start, stop)] (at most one per contig, in header
         order), batch, realign, write -- npore_bam_realign_sequential.  Returns (reads selected, [(ordinal, status)] of
         the first bad reads, (refused, inconsistent)) -- the reads selected include the records that pass through (pass_mask),
         which are not bad reads; raises OnePassUnsupported when the regions or the file's
         order rule the one-pass run out (the caller truncates the output and takes the indexed path).
-        out_format / bai / eof / compress / records / md / cs / de / pass_mask / eqx: set_output for this run ("bam": records instead
-        of text)."""
+        out_format / bai / eof / compress / records / md / cs / de / pass_mask / eqx / oc: set_output for this run ("bam": records
+        instead of text)."""
         ids = {n: i for i, n in enumerate(self.references)}
         rid = np.array([ids.get(c, -2) for c, _, _ in regions], np.int32)
         beg = np.array([s for _, s, _ in regions], np.int64)
@@ -1478,7 +1511,7 @@ class NativeBam:
         counts = np.zeros(3, np.int64)
         bad_ord, bad_st = np.zeros(max(bad_cap, 1), np.int64), np.zeros(max(bad_cap, 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask, eqx)
+        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask, eqx, oc)
         rc = self._lib.npore_bam_realign_sequential(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, len(regions), rid.ctypes.data,
                                                     beg.ctypes.data, end.ctypes.data, int(max_reads or 0), int(batch_reads), indel_start,
                                                     indel_extend, max_b_rows, r, threads, os.fsencode(out_path), counts.ctypes.data,
@@ -1515,15 +1548,15 @@ class NativeBam:
 
     def realign_file(self, ctx, fasta, idx, out_sam, batch_reads=4000, r=30, max_b_rows=20000, indel_start=5.0,
                      indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False,
-                     cs=None, de=False, pass_mask=0, eqx=False):
+                     cs=None, de=False, pass_mask=0, eqx=False, oc=False):
         """All selected reads, batch by batch, appended to out_sam by the library with packing, GPU work and
         formatting/writing of neighbouring batches overlapped.  Returns status[n] (ST_PASSED: written as it came).
-        out_format / bai / eof / compress / records / md / cs / de / pass_mask / eqx: set_output for this run ("bam": records instead of
-        text); with pass_mask, idx comes from select(..., pass_mask=pass_mask)."""
+        out_format / bai / eof / compress / records / md / cs / de / pass_mask / eqx / oc: set_output for this run ("bam": records
+        instead of text); with pass_mask, idx comes from select(..., pass_mask=pass_mask)."""
         idx = np.ascontiguousarray(idx, np.int64)
         st = np.zeros(max(len(idx), 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask, eqx)
+        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask, eqx, oc)
         self._check(self._lib.npore_bam_realign_file(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data,
                                                      len(idx), int(batch_reads), indel_start, indel_extend, max_b_rows, r,
                                                      threads, os.fsencode(out_sam), st.ctypes.data))
@@ -1570,7 +1603,8 @@ class NativeBam:
 
 
 def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0, out_format="sam", bai=None,
-                   eof=True, compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0, eqx=False):
+                   eof=True, compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0, eqx=False,
+                   oc=False):
     """realign_reads() through the library; returns the number of reads handed in.  batch_reads > 0: the whole
     index list in overlapped batches written by the library itself; 0: one batch, text written here.
     threads: host threads of the parallel host stages (0 = all cores; one process per GPU: dist.host_threads_per_rank).
@@ -1582,7 +1616,7 @@ def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_
     if batch_reads > 0:
         text, status = None, bam.realign_file(ctx, fasta, idx, out_sam, batch_reads=batch_reads, r=r, max_b_rows=max_b_rows,
                                               threads=threads, out_format=out_format, bai=bai, eof=eof, compress=compress,
-                                              records=records, md=md, cs=cs, de=de, pass_mask=pass_mask, eqx=eqx)
+                                              records=records, md=md, cs=cs, de=de, pass_mask=pass_mask, eqx=eqx, oc=oc)
     else:
         text, status = bam.realign_batch(ctx, fasta, idx, r=r, max_b_rows=max_b_rows, threads=threads)
     bad = np.nonzero(np.asarray(status) & ~ST_PASSED)[0]       # (a record that passed through is no bad read)

@@ -67,6 +67,7 @@ struct WorkSet {
     DevBuf nm, md_len;                // ... FULL records: the group's NM counts; NPORE_OUT_MD: the bytes of its MD texts
     DevBuf cs_len, de_val;            // ... NPORE_TAG_*: the bytes of its cs texts, its de values
     DevBuf eqx_len;                   // ... NPORE_CIGAR_EQX: the words of its final CIGARs in =/X form
+    DevBuf oc_len;                    // ... NPORE_TAG_OC: the bytes of its OC texts (0: the read did not change)
     HostBuf h_off;
     hipEvent_t evc[4] = {};      // H2D start / end, D2H start / end of a staged group
     bool staged = false;
@@ -81,13 +82,14 @@ struct WorkSet {
     // An idle set takes the capacities of one that has just been given a group: the groups of a run are alike, so its
     // own first group then finds its buffers in place instead of allocating tens of GB in front of its kernels (with
     // three sets that was the THIRD step of a run -- 0.4 s in a timed region that had two warm-up steps)
-    // The per-read arrays of the FULL records' tag kernels (nm, md_len, cs_len, de_val, eqx_len) for nr reads of a run that writes `rec`
+    // The per-read arrays of the FULL records' tag kernels (nm, md_len, cs_len, de_val, eqx_len, oc_len) for nr reads of a run that writes `rec`
     int reserve_emit_tags(const RecSpec &rec, size_t nr)
     {
         if (int rc = rec.md ? md_len.ensure(nr * 4 + 64) : 0) return rc;
         if (int rc = rec.cs_de() ? cs_len.ensure(nr * 4 + 64) : 0) return rc;
         if (int rc = rec.cs_de() ? de_val.ensure(nr * 4 + 64) : 0) return rc;
         if (int rc = rec.eqx() ? eqx_len.ensure(nr * 4 + 64) : 0) return rc;
+        if (int rc = rec.oc() ? oc_len.ensure(nr * 4 + 64) : 0) return rc;
         return rec.full ? nm.ensure(nr * 4 + 64) : NPORE_OK;
     }
     void presize_like(const WorkSet &o)
@@ -98,7 +100,7 @@ struct WorkSet {
                                         &WorkSet::cnruns, &WorkSet::in_refs, &WorkSet::in_seqs, &WorkSet::in_cigs, &WorkSet::in_off,
                                         &WorkSet::out, &WorkSet::out_len, &WorkSet::status, &WorkSet::in_raw, &WorkSet::coff,
                                         &WorkSet::in_hp, &WorkSet::rec_off, &WorkSet::rec_len, &WorkSet::nm, &WorkSet::md_len, &WorkSet::cs_len, &WorkSet::de_val,
-                                        &WorkSet::eqx_len};
+                                        &WorkSet::eqx_len, &WorkSet::oc_len};
         for (auto m : all) (this->*m).match(o.*m);
     }
 };
@@ -478,6 +480,7 @@ BamEmitParams wire_bam_emit(WorkSet *w, int64_t nr, uint8_t *recs, int64_t cap, 
         if (rec.md) bp.md_len = w->md_len.as<int32_t>();      // (MD: its size in front of the placement, its text behind the record)
         if (rec.cs_de()) { bp.tags = rec.cs_de(); bp.cs_len = w->cs_len.as<int32_t>(); bp.de = w->de_val.as<float>(); }      // (cs / de: the same)
         if (rec.eqx()) bp.eqx_len = w->eqx_len.as<int32_t>();      // (=/X: the count of its words in front of the placement, the words behind the record)
+        if (rec.oc()) bp.oc_len = w->oc_len.as<int32_t>();         // (OC: changed or not and its size in front of the placement, its text behind the record)
     }
     return bp;
 }

@@ -19,6 +19,9 @@
 // and, the same way, in the CIGAR's =/X form where that is asked for:
 //   =/X      eqx_size_kernel, emit_eqx_kernel  (eqx_rec.hpp, NPORE_CIGAR_EQX): ONE walk, eqx_walk, likewise -- the placement
 //                                              takes the number of split words, the assembly leaves their span to the walk
+// and the read's ORIGINAL CIGAR where the run changed it and that is asked for:
+//   OC       oc_size_kernel, emit_oc_kernel    (oc_rec.hpp, NPORE_TAG_OC): changed or not is decided in front of the placement, which
+//                                              the host could not do -- it never sees the final words; ONE walk, oc_walk, likewise
 // A final CIGAR of more than 65 535 operations goes out as htslib writes it (bam_reader.hpp RECORD): two placeholder words
 // in the CIGAR's place, the real words in a CG:B,I tag behind the other tags, in either form.
 // The host then takes the batch's bytes as they lie (BgzfStoredWriter) and the records' lengths for its index.
@@ -33,6 +36,7 @@
 #include "eqx_rec.hpp"
 #include "md_rec.hpp"
 #include "nm_rec.hpp"
+#include "oc_rec.hpp"
 #include "unpack_kernels.hpp"
 
 namespace npore {
@@ -67,6 +71,9 @@ struct BamEmitParams {
     // NPORE_CIGAR_EQX (eqx_size_kernel): the words of the read's final CIGAR in =/X form (0 for a refused or passing read); null:
     // the final words go out as they are
     int32_t *eqx_len = nullptr;    // [n_reads]
+    // NPORE_TAG_OC (oc_size_kernel): the bytes of the read's OC text (0: the read is refused, passes or did not change -- no tag);
+    // null: no OC tags
+    int32_t *oc_len = nullptr;     // [n_reads]
 };
 
 __device__ __forceinline__ void st32(uint8_t *q, uint32_t w)      // little-endian, unaligned
@@ -304,7 +311,19 @@ struct BamFullShape {
     int64_t wl, n_cig, l_seq, aux, size;      // wl: bytes of the final words as they go out (NPORE_CIGAR_EQX: of the split ones)
     int64_t mdb;                   // bytes of the MD tag behind NM (4 + its text; 0: none)
     int64_t csb, deb;              // bytes of the cs tag behind that (4 + its text; 0: none) and of the de tag (7; 0: none)
+    int64_t ocb;                   // bytes of the OC tag behind those (4 + its text; 0: none)
 };
+// the clip words [0, ci) and [cj, nc) of a staged CIGAR's nc words at cg (bam_reader.hpp full_clip_words)
+__device__ __forceinline__ void staged_clip_words(const uint8_t *cg, int nc, int &ci, int &cj)
+{
+    auto op_of = [&](int c) { return ld32(cg + 4 * (size_t)c) & 15u; };
+    ci = 0;
+    cj = nc;
+    if (ci < cj && op_of(ci) == 5) ci++;
+    if (ci < cj && op_of(ci) == 4) ci++;
+    if (cj > ci && op_of(cj - 1) == 5) cj--;
+    if (cj > ci && op_of(cj - 1) == 4) cj--;
+}
 __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, int64_t k)
 {
     BamFullShape s;
@@ -316,13 +335,7 @@ __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, i
         return s;
     }
     staged_cigar(s.f, s.cg, s.nc, s.sq);
-    auto op_of = [&](int c) { return ld32(s.cg + 4 * (size_t)c) & 15u; };
-    s.ci = 0;
-    s.cj = s.nc;
-    if (s.ci < s.cj && op_of(s.ci) == 5) s.ci++;
-    if (s.ci < s.cj && op_of(s.ci) == 4) s.ci++;
-    if (s.cj > s.ci && op_of(s.cj - 1) == 5) s.cj--;
-    if (s.cj > s.ci && op_of(s.cj - 1) == 4) s.cj--;
+    staged_clip_words(s.cg, s.nc, s.ci, s.cj);
     s.wl = p.eqx_len ? 4 * (int64_t)p.eqx_len[k] : p.words_len[g] > 0 ? p.words_len[g] : 0;
     s.n_cig = s.ci + (s.wl >> 2) + (s.nc - s.cj);
     s.lng = s.n_cig > 0xFFFF;
@@ -333,9 +346,10 @@ __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, i
     s.mdb = p.md_len ? 4 + (int64_t)p.md_len[k] : 0;
     s.csb = (p.tags & NPORE_TAG_CS) ? 4 + (int64_t)p.cs_len[k] : 0;
     s.deb = (p.tags & NPORE_TAG_DE) ? 7 : 0;
+    s.ocb = p.oc_len && p.oc_len[k] ? 4 + (int64_t)p.oc_len[k] : 0;
     s.size = (p.status[g] & 32) ? 0
                                 : 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb +
-                                      s.csb + s.deb + (s.lng ? 8 + 4 * s.n_cig : 0);
+                                      s.csb + s.deb + s.ocb + (s.lng ? 8 + 4 * s.n_cig : 0);
     return s;
 }
 __device__ __forceinline__ int64_t bam_full_record_size(const BamEmitParams &p, int64_t k) { return bam_full_shape(p, k).size; }
@@ -343,7 +357,7 @@ __device__ __forceinline__ int64_t bam_full_record_size(const BamEmitParams &p, 
 __device__ __forceinline__ uint8_t *bam_full_words_at(const BamEmitParams &p, int64_t k, const BamFullShape &s)
 {
     uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8];
-    return s.lng ? o + 8 + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb + s.csb + s.deb + 8 : o;
+    return s.lng ? o + 8 + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb + s.csb + s.deb + s.ocb + 8 : o;
 }
 
 // one wavefront per read
@@ -376,8 +390,8 @@ __global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
     for (int j = lane; j < l_rn; j += 64) o[j] = f[32 + j];
     o += l_rn;
     uint8_t *cw = o;                                             // where the CIGAR words go
-    if (s.lng) {                                                 // the placeholder here, CG:B,I behind NM (and MD, cs, de)
-        cw = o + 8 + body + 3 + s.nmb + s.mdb + s.csb + s.deb + 8;
+    if (s.lng) {                                                 // the placeholder here, CG:B,I behind NM (and MD, cs, de, OC)
+        cw = o + 8 + body + 3 + s.nmb + s.mdb + s.csb + s.deb + s.ocb + 8;
         if (lane < 2) st32(o + 4 * lane, lane == 0 ? ((uint32_t)s.l_seq << 4 | 4u) : ((uint32_t)reflen << 4 | 3u));
         if (lane >= 4 && lane < 8) cw[lane - 12] = (uint8_t)"CGBI"[lane - 4];
         if (lane >= 8 && lane < 12) cw[lane - 12] = (uint8_t)((uint32_t)s.n_cig >> (8 * (lane - 8)));
@@ -762,8 +776,138 @@ __global__ __launch_bounds__(64) void emit_eqx_kernel(BamEmitParams p)
     eqx_walk(p, k, lane, EqxStore{bam_full_words_at(p, k, s) + 4 * s.ci, (int64_t)p.eqx_len[k]});
 }
 
+// ---- the OC tag of a FULL record (NPORE_TAG_OC; oc_rec.hpp states the rule and holds the sequential twins) --------------------
+// One wavefront per read over tiles of 64 words of the read's STAGED CIGAR (staged_cigar: its real words), tile t holding the
+// words [64 t, 64 t + 64), lane l word 64 t + l; the clip words [0, ci) and [cj, nc) as bam_full_shape finds them.
+
+// CHANGED: the parallel form of oc_changed_words.  A lane is LIVE where its word lies in [ci, cj) and has length > 0.  A live lane
+// BEGINS a run where its mapped op differs from the previous live word's -- the previous live lane of the tile, or the open run
+// carried in (op `rop`; `runs`, the runs begun so far, 0: none).  The run a lane belongs to has the index runs + (begins at or
+// below the lane) - 1; a run's length within the tile is a difference of the exclusive prefix sums (64 bits) at the two lanes
+// that begin it and the next.  A lane that begins a run CLOSES the one in front of it and compares it -- op, length, index -- with
+// its final word; the open run (rop, rlen, its index runs - 1) is carried wave-uniformly and closed at the end, where the count
+// is compared with nf.  The first difference ends the walk: the answer is the same in every lane.
+__device__ __forceinline__ bool oc_changed(const BamEmitParams &p, int64_t k, int lane, const uint8_t *cg, int ci, int cj)
+{
+    const int64_t g = p.read_base + k;
+    const int64_t nf = p.words_len[g] <= 0 ? 0 : p.words_len[g] >> 2;
+    const uint32_t *fin = reinterpret_cast<const uint32_t *>(p.words + p.words_off[g]);      // (the slots lie at multiples of 4)
+    const unsigned long long below_me = (1ull << lane) - 1ull;
+    int64_t runs = 0;
+    uint32_t rop = 0;
+    unsigned long long rlen = 0;
+    for (int64_t t0 = 0; t0 < cj; t0 += 64) {
+        const int64_t c = t0 + lane;
+        const bool in = c >= ci && c < cj;
+        const uint32_t v = in ? ld32(cg + 4 * c) : 0u;
+        const uint32_t op = oc_canon_op(v & 15u), len = v >> 4;
+        const unsigned long long live = __builtin_amdgcn_ballot_w64(len > 0);
+        if (!live) continue;
+        const unsigned long long before = live & below_me;
+        const int prev = before ? 63 - (int)__builtin_clzll(before) : 0;
+        const uint32_t op_prev = (uint32_t)__shfl((int)op, prev);
+        const bool begins = len > 0 && (before ? op != op_prev : (runs == 0 || op != rop));
+        const unsigned long long bd = __builtin_amdgcn_ballot_w64(begins);
+        unsigned long long incl = len;       // inclusive sums of the lengths over the tile
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned long long x = (unsigned long long)__shfl_up((long long)incl, d);
+            if (lane >= d) incl += x;
+        }
+        const unsigned long long excl = incl - len, whole = (unsigned long long)__shfl((long long)incl, 63);
+        // the run in front of a lane that begins one: from the previous beginning of the tile, or the carried one
+        const unsigned long long bd_before = bd & below_me;
+        const int from = bd_before ? 63 - (int)__builtin_clzll(bd_before) : 0;
+        const unsigned long long excl_from = (unsigned long long)__shfl((long long)excl, from);
+        const int64_t closed = runs + (int64_t)__builtin_popcountll(bd_before) - 1;      // its index (-1: there is none)
+        bool differs = false;
+        if (begins && closed >= 0) {
+            const unsigned long long length = bd_before ? excl - excl_from : rlen + excl;
+            const uint32_t cop = before ? op_prev : rop;
+            const uint32_t f = closed < nf ? fin[closed] : 0u;
+            differs = closed >= nf || (f & 15u) != cop || (unsigned long long)(f >> 4) != length;
+        }
+        if (__builtin_amdgcn_ballot_w64(differs)) return true;
+        if (bd) {
+            const int last = 63 - (int)__builtin_clzll(bd);
+            rop = (uint32_t)__shfl((int)op, last);
+            rlen = whole - (unsigned long long)__shfl((long long)excl, last);
+            runs += (int64_t)__builtin_popcountll(bd);
+        } else {
+            rlen += whole;
+        }
+    }
+    if (runs != nf) return true;
+    if (runs == 0) return false;
+    const uint32_t f = fin[runs - 1];
+    return (f & 15u) != rop || (unsigned long long)(f >> 4) != rlen;
+}
+
+// TEXT: every word of the tile is its lane's -- digits(length) + 1 bytes at a wave prefix sum of those bytes behind `at`, the bytes
+// of the tiles before (the same in every lane).  The walk is ONE function over a sink (oc_rec.hpp): oc_size_kernel runs it with
+// OcCount, emit_oc_kernel with OcStore, so size and text cannot differ.  Returns the text's length (no NUL).
+template <class Sink>
+__device__ __forceinline__ uint32_t oc_walk(const uint8_t *cg, int nc, int lane, const Sink &sink)
+{
+    uint32_t at = 0;
+    for (int64_t t0 = 0; t0 < nc; t0 += 64) {
+        const bool in = t0 + lane < nc;
+        const uint32_t v = in ? ld32(cg + 4 * (t0 + lane)) : 0u;
+        const int nd = md_digits(v >> 4);
+        const uint32_t bytes = in ? (uint32_t)nd + 1u : 0u;
+        uint32_t incl = bytes;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t x = (uint32_t)__shfl_up((int)incl, d);
+            if (lane >= d) incl += x;
+        }
+        if (in) {
+            const uint32_t mine = at + incl - bytes;
+            md_put_decimal(sink, mine, v >> 4, nd);
+            sink.put(mine + nd, oc_letter(v & 15u));
+        }
+        at += (uint32_t)__shfl((int)incl, 63);
+    }
+    return at;
+}
+
+// bytes of every read's OC text (0: the read is refused, passes or did not change), beside the other size kernels in front of
+// the placement, which takes the tag's bytes from it (bam_full_shape)
+__global__ __launch_bounds__(64) void oc_size_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    const uint8_t *f = p.raw + p.raw_off[k] + 4;
+    uint32_t len = 0;
+    if (!(p.status[p.read_base + k] & 32) && !staged_passes(f, p.pass_mask)) {
+        const uint8_t *cg, *sq;
+        int nc, ci, cj;
+        staged_cigar(f, cg, nc, sq);
+        staged_clip_words(cg, nc, ci, cj);
+        if (oc_changed(p, k, lane, cg, ci, cj)) len = oc_walk(cg, nc, lane, OcCount{});
+    }
+    if (lane == 0) p.oc_len[k] = (int32_t)len;
+}
+
+// 'O' 'C' 'Z' text NUL behind the record's NM, MD, cs and de (bam_full_shape), behind emit_bam_full_kernel (and emit_md_kernel,
+// emit_cs_kernel) on its stream; byte stores: the tag has any alignment
+__global__ __launch_bounds__(64) void emit_oc_kernel(BamEmitParams p)
+{
+    const int64_t k = blockIdx.x;
+    if (k >= p.n_reads) return;
+    const int lane = threadIdx.x;
+    const int64_t cap = p.oc_len[k];
+    if (cap == 0 || p.rec_len[k] <= 0) return;
+    const BamFullShape s = bam_full_shape(p, k);
+    if (s.pass) return;
+    uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb +
+                 s.csb + s.deb;
+    if (lane < 3) o[lane] = (uint8_t)"OCZ"[lane];
+    oc_walk(s.cg, s.nc, lane, OcStore{o + 3, cap});
+    if (lane == 0) o[3 + cap] = 0;
+}
+
 // What a group's records take, in order, on stream s: the reference form's two kernels, or (full) the FULL form's with the tags
-// that p names -- p.md_len: MD; p.tags' NPORE_TAG_CS / NPORE_TAG_DE: cs / de -- and (p.eqx_len) the CIGAR's =/X form.
+// that p names -- p.md_len: MD; p.tags' NPORE_TAG_CS / NPORE_TAG_DE: cs / de; p.oc_len: OC -- and (p.eqx_len) the CIGAR's =/X form.
 inline void launch_bam_emit(const BamEmitParams &p, bool full, hipStream_t s)
 {
     const dim3 reads((unsigned)p.n_reads), wave(64);             // one wavefront per read; the placements: one workgroup
@@ -777,11 +921,13 @@ inline void launch_bam_emit(const BamEmitParams &p, bool full, hipStream_t s)
     if (p.md_len) hipLaunchKernelGGL(md_size_kernel, reads, wave, 0, s, p);
     if (cs_de) hipLaunchKernelGGL(cs_size_kernel, reads, wave, 0, s, p);
     if (p.eqx_len) hipLaunchKernelGGL(eqx_size_kernel, reads, wave, 0, s, p);
+    if (p.oc_len) hipLaunchKernelGGL(oc_size_kernel, reads, wave, 0, s, p);
     hipLaunchKernelGGL(place_bam_full_kernel, dim3(1), dim3(256), 0, s, p);
     hipLaunchKernelGGL(emit_bam_full_kernel, reads, wave, 0, s, p);
     if (p.md_len) hipLaunchKernelGGL(emit_md_kernel, reads, wave, 0, s, p);
     if (cs_de) hipLaunchKernelGGL(emit_cs_kernel, reads, wave, 0, s, p);
     if (p.eqx_len) hipLaunchKernelGGL(emit_eqx_kernel, reads, wave, 0, s, p);
+    if (p.oc_len) hipLaunchKernelGGL(emit_oc_kernel, reads, wave, 0, s, p);
 }
 
 }  // namespace npore

@@ -11,6 +11,7 @@
 #include "eqx_rec.hpp"
 #include "md_rec.hpp"
 #include "nm_rec.hpp"
+#include "oc_rec.hpp"
 
 #include <sys/uio.h>
 
@@ -729,6 +730,9 @@ inline int format_sam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
 //   - with NPORE_CIGAR_EQX (`--eqx`, the same setter's word) the final standardised CIGAR stands between the clip words in its
 //     =/X form (eqx_rec.hpp): every compared position = or X by NM's predicate, run-length coded through neighbouring compared
 //     words.  n_cigar counts the split words, so the placeholder + CG form begins several times sooner; the tags do not change.
+//   - with NPORE_TAG_OC (`--oc`, the same setter's word) a read whose alignment CHANGED (oc_rec.hpp: the canonical M form of its
+//     input CIGAR between the clip words is not its final CIGAR) carries its input's real CIGAR as OC:Z behind de: kept aux, NM,
+//     MD, cs, de, OC, CG.  The kept aux then leaves an input's OC out as well, so an unchanged read has none.
 //   Size: 36 + l_read_name + 4 * n_cigar (8 when long) + (l_seq + 1) / 2 + l_seq + kept aux + 3 + {1, 2, 4} (+ 4 + MD text)
 //   (+ 8 + 4 * n when long).
 // FILE.  BGZF with STORED deflate members (level 0, what `samtools view -u` writes): 18 bytes of gzip header with the BC
@@ -905,9 +909,11 @@ inline void cs_de_tags_of_words(int tags, const uint8_t *w, int64_t ops, const u
     }
 }
 // bam_record_into's twin for the FULL RECORD over the final CIGAR's n_fin words (< 0: the text was no CIGAR); nm: the read's NM
-// (nm_of_words); md: its MD text (md_of_words), or none; more: the bytes of its cs and de tags (cs_de_tags_of_words), or none
+// (nm_of_words); md: its MD text (md_of_words), or none; more: the bytes of its cs, de and OC tags (cs_de_tags_of_words,
+// oc_tag_of_words), or none; drop_oc: filter_aux's -- the run writes OC (RecSpec::oc())
 inline int64_t bam_record_full_words_into(const RecView &r, const uint8_t *fin_words, int64_t n_fin, int32_t status, int64_t nm, uint8_t *dst,
-                                          BamRecMeta *meta = nullptr, const std::string *md = nullptr, const std::string *more = nullptr)
+                                          BamRecMeta *meta = nullptr, const std::string *md = nullptr, const std::string *more = nullptr,
+                                          bool drop_oc = false)
 {
     if (status & NPORE_ST_BAD_INPUT) return 0;
     const RecCigar in_cg = rec_cigar(r);
@@ -916,9 +922,9 @@ inline int64_t bam_record_full_words_into(const RecView &r, const uint8_t *fin_w
     full_clip_words(in_cg, ci, cj);
     const int64_t n_cig = (int64_t)ci + n_fin + (int64_t)(in_cg.n - cj);
     const bool lng = n_cig > 0xFFFF;
-    const int64_t l_seq = r.l_seq(), nb = (l_seq + 1) / 2, aux = filter_aux(r.aux(), r.end(), nullptr);
+    const int64_t l_seq = r.l_seq(), nb = (l_seq + 1) / 2, aux = filter_aux(r.aux(), r.end(), nullptr, drop_oc);
     const int l_rn = r.l_read_name(), nmb = bam_hp_tag_bytes(nm);
-    const int64_t mdb = (md ? 4 + (int64_t)md->size() : 0) + (more ? (int64_t)more->size() : 0);      // (MD, cs, de)
+    const int64_t mdb = (md ? 4 + (int64_t)md->size() : 0) + (more ? (int64_t)more->size() : 0);      // (MD, cs, de, OC)
     const int64_t size = 36 + l_rn + (lng ? 8 : 4 * n_cig) + nb + l_seq + aux + 3 + nmb + mdb + (lng ? 8 + 4 * n_cig : 0);
     if (!dst) return size;
     const int64_t reflen = rec_ref_len(in_cg);
@@ -949,7 +955,7 @@ inline int64_t bam_record_full_words_into(const RecView &r, const uint8_t *fin_w
     o = seq_at;
     std::memcpy(o, r.seq(), (size_t)(nb + l_seq));
     o += nb + l_seq;
-    filter_aux(r.aux(), r.end(), o);
+    filter_aux(r.aux(), r.end(), o, drop_oc);
     o += aux;
     o[0] = 'N'; o[1] = 'M';
     o[2] = (uint8_t)(nmb == 1 ? 'C' : nmb == 2 ? 'S' : 'I');
@@ -995,7 +1001,8 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     std::vector<std::vector<uint8_t>> words(rec.full ? (size_t)n : 0);
     auto n_words = [&](int64_t k) { return (int64_t)words[(size_t)k].size() / 4 - 1; };
     const int cs_de = rec.cs_de();
-    std::vector<std::string> md(rec.md ? (size_t)n : 0), more(cs_de ? (size_t)n : 0);
+    const bool oc = rec.oc(), has_more = cs_de || oc;
+    std::vector<std::string> md(rec.md ? (size_t)n : 0), more(has_more ? (size_t)n : 0);
     std::atomic<int> bad{0};
     const uint32_t pass_mask = rec.pass_mask;
     // a record that passes: the input's bytes; the index gets the input record's own reference length
@@ -1009,7 +1016,7 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
     auto record = [&](int64_t k, uint8_t *dst, BamRecMeta *m) {
         if (staged_passes(rec_of(rf, k).p, pass_mask)) return passed(k, dst, m);
         return rec.full ? bam_record_full_words_into(rec_of(rf, k), words[(size_t)k].data(), n_words(k), status[k], nm[(size_t)k], dst, m,
-                                                     rec.md ? &md[(size_t)k] : nullptr, cs_de ? &more[(size_t)k] : nullptr)
+                                                     rec.md ? &md[(size_t)k] : nullptr, has_more ? &more[(size_t)k] : nullptr, oc)
                         : bam_record_into(rec_of(rf, k), finals + final_off[k], final_len[k], status[k], dst, m);
     };
     parallel_for(n, threads, [&](int64_t k) {
@@ -1022,6 +1029,12 @@ inline int format_bam_into(const npore_bam *b, const RecFetch &rf, int64_t n, co
             nm[(size_t)k] = nm_of_words(w, ops, ref, rl, seq, sl);
             if (rec.md) md_of_words(w, ops, ref, rl, seq, sl, md[(size_t)k]);
             if (cs_de) cs_de_tags_of_words(cs_de, w, ops, ref, rl, seq, sl, more[(size_t)k]);
+            if (oc) {              // OC behind them, on a read whose final words are not its input's canonical form (oc_rec.hpp)
+                const RecCigar in_cg = rec_cigar(rec_of(rf, k));
+                uint32_t ci, cj;
+                full_clip_words(in_cg, ci, cj);
+                if (oc_changed_words(in_cg.w, ci, cj, w, ops)) oc_tag_of_words(in_cg.w, in_cg.n, more[(size_t)k]);
+            }
             // (NPORE_CIGAR_EQX: the record takes the split words; NM, MD, cs and de are the same on either form)
             if (rec.eqx()) words[(size_t)k] = eqx_of_words(w, ops, ref, rl, seq, sl);
         }

@@ -226,14 +226,16 @@ int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta
             s.rec_cap += staged_pass_bytes(r.p);
             continue;
         }
-        const int64_t aux = pm.rec.full ? filter_aux(r.aux(), r.end(), nullptr) : 0;
-        s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_head_bytes(r, rec_cigar(r), pm.bam ? STAGE_QUALS : STAGE_HEAD) + aux;
+        const RecCigar cg = rec_cigar(r);
+        const int64_t aux = pm.rec.full ? filter_aux(r.aux(), r.end(), nullptr, pm.rec.oc()) : 0;
+        s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_head_bytes(r, cg, pm.bam ? STAGE_QUALS : STAGE_HEAD, false) + aux;
         if (pm.bam) {          // (a final CIGAR has no more words than the read's reference positions and bases: the slot's size too)
             const int64_t rl = s.ro[(size_t)k + 1] - s.ro[(size_t)k], sl = s.so[(size_t)k + 1] - s.so[(size_t)k];
             reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = pm.rec.full ? aux : rec_hp(r);
             s.rec_cap += pm.rec.full ? full_record_bound(r.l_read_name(), rl + sl, r.l_seq(), aux) : ref_record_bound(r.l_read_name(), rl + sl, sl);
             if (pm.rec.md) s.rec_cap += md_tag_bound(rl, 1);
             if (pm.rec.cs_de()) s.rec_cap += cs_de_tags_bound(rl + sl);      // (NPORE_CIGAR_EQX adds nothing: eqx_rec.hpp, Size)
+            if (pm.rec.oc()) s.rec_cap += oc_tag_bound(cg.n);
         }
     }
     if (int rc = s.raw.ensure((size_t)s.rawo[(size_t)n] + 64)) return rc;

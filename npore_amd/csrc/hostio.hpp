@@ -551,17 +551,18 @@ struct BamRecMeta {
 struct RecSpec {
     bool full = false;                    // NPORE_OUT_FULL: FULL records (bam_reader.hpp FULL RECORD) ...
     bool md = false;                      // ... NPORE_OUT_MD: with the MD tag behind NM
-    int tags = 0;                         // ... the setters' word: NPORE_TAG_* (cs / de behind that) and NPORE_CIGAR_EQX
+    int tags = 0;                         // ... the setters' word: NPORE_TAG_* (cs / de behind that, OC behind those) and NPORE_CIGAR_EQX
     uint32_t pass_mask = 0;               // ... records with one of these flag bits pass through (staged_head.hpp)
     int cs_de() const { return tags & (NPORE_TAG_CS | NPORE_TAG_CS_LONG | NPORE_TAG_DE); }      // the tags of the word (0: neither cs nor de)
     bool eqx() const { return (tags & NPORE_CIGAR_EQX) != 0; }                                  // its other bit: the final CIGAR in =/X form
+    bool oc() const { return (tags & NPORE_TAG_OC) != 0; }                                      // ... and OC:Z on the reads that changed (oc_rec.hpp)
 };
 // THE rules of the output options: defined bits only, CS_LONG beside CS, md / tags / pass on FULL records, FULL records in BAM
 inline bool rec_spec_of(int format, int flags, int tags, int pass, RecSpec &out)
 {
     const int all_flags = NPORE_OUT_EOF | NPORE_OUT_PART | NPORE_OUT_DEFLATE | NPORE_OUT_MATCH | NPORE_OUT_FULL | NPORE_OUT_MD;
     const bool full = (flags & NPORE_OUT_FULL) != 0;
-    if ((flags & ~all_flags) || (tags & ~(NPORE_TAG_CS | NPORE_TAG_CS_LONG | NPORE_TAG_DE | NPORE_CIGAR_EQX)) || (pass & ~(int)PASS_FLAGS) ||
+    if ((flags & ~all_flags) || (tags & ~(NPORE_TAG_CS | NPORE_TAG_CS_LONG | NPORE_TAG_DE | NPORE_CIGAR_EQX | NPORE_TAG_OC)) || (pass & ~(int)PASS_FLAGS) ||
         ((tags & NPORE_TAG_CS_LONG) && !(tags & NPORE_TAG_CS)) || (!full && ((flags & NPORE_OUT_MD) || tags || pass)) ||
         (full && format != NPORE_OUT_BAM))
         return false;
@@ -784,23 +785,24 @@ inline void rec_clips(const RecView &r, int64_t &lead, int64_t &trail) { rec_cli
 
 // ---- the tags a FULL record keeps (bam_reader.hpp FULL RECORD) ----------------------------------------------------------
 // The input's aux bytes [q, end) in input order without the tags the realignment makes stale -- NM MD cs de dv CG, by
-// their case-sensitive two-letter names -- copied to dst (nullptr: only counted); returns their bytes.  A tag that
-// cannot be stepped over (aux_value_bytes returns 0) ends the list: it and everything behind it are dropped (rec_cigar's
-// rule), and so are fewer than three bytes behind the last tag.
-inline bool aux_tag_is_stale(const uint8_t *q)
+// their case-sensitive two-letter names, and with drop_oc (a run under NPORE_TAG_OC, RecSpec::oc()) OC as well: the run
+// writes its own on the reads it changed, so no record carries two, and the device never parses tags -- copied to dst
+// (nullptr: only counted); returns their bytes.  A tag that cannot be stepped over (aux_value_bytes returns 0) ends the
+// list: it and everything behind it are dropped (rec_cigar's rule), and so are fewer than three bytes behind the last tag.
+inline bool aux_tag_is_stale(const uint8_t *q, bool drop_oc)
 {
     static const char stale[6][3] = {"NM", "MD", "cs", "de", "dv", "CG"};
     for (const char *t : stale)
         if (q[0] == (uint8_t)t[0] && q[1] == (uint8_t)t[1]) return true;
-    return false;
+    return drop_oc && q[0] == 'O' && q[1] == 'C';
 }
-inline int64_t filter_aux(const uint8_t *q, const uint8_t *end, uint8_t *dst)
+inline int64_t filter_aux(const uint8_t *q, const uint8_t *end, uint8_t *dst, bool drop_oc)
 {
     int64_t n = 0;
     while (q + 3 <= end) {
         const size_t w = aux_value_bytes(q + 3, end, (char)q[2]);
         if (!w) break;
-        if (!aux_tag_is_stale(q)) {
+        if (!aux_tag_is_stale(q, drop_oc)) {
             if (dst) std::memcpy(dst + n, q, 3 + w);
             n += (int64_t)(3 + w);
         }
@@ -808,6 +810,8 @@ inline int64_t filter_aux(const uint8_t *q, const uint8_t *end, uint8_t *dst)
     }
     return n;
 }
+// ... of no run: the six stale tags alone (the model programs under tests/; every caller in the library names its run's)
+inline int64_t filter_aux(const uint8_t *q, const uint8_t *end, uint8_t *dst) { return filter_aux(q, end, dst, false); }
 
 // ---- staged heads: what the device gets of a record ------------------------------------------------------------------
 // The kernels that read records (unpack, BAM emit, recount, purity) get each record's HEAD as it lies in the BAM stream
@@ -819,19 +823,19 @@ inline int64_t filter_aux(const uint8_t *q, const uint8_t *end, uint8_t *dst)
 // record; staged_cigar() (staged_head.hpp) is the one reader, on the device and on the host.
 enum : int { STAGE_HEAD = 0, STAGE_QUALS = 1, STAGE_FULL = 2 };      // (0 / 1: what `bool with_quals` used to say)
 constexpr uint32_t PASS_NONE = 0;      // the mask under which nothing passes (staged_head.hpp record_passes)
-inline int64_t staged_head_bytes(const RecView &r, const RecCigar &cg, int form)
+inline int64_t staged_head_bytes(const RecView &r, const RecCigar &cg, int form, bool drop_oc)
 {
     return 4 + 32 + (int64_t)r.l_read_name() + 4 * (int64_t)cg.n + (int64_t)((form != STAGE_HEAD ? r.aux() : r.qual()) - r.seq()) +
-           (form == STAGE_FULL ? filter_aux(r.aux(), r.end(), nullptr) : 0);
+           (form == STAGE_FULL ? filter_aux(r.aux(), r.end(), nullptr, drop_oc) : 0);
 }
-// A READ's head -- nothing passes here: the recount, the purity run, and a run's reads below
-inline int64_t staged_head_bytes(const uint8_t *rec, int form)
+// A READ's head -- nothing passes here: the recount, the purity run, and a run's reads below (drop_oc: filter_aux's, STAGE_FULL only)
+inline int64_t staged_head_bytes(const uint8_t *rec, int form, bool drop_oc)
 {
     const RecView r = rec_view(rec);
-    return staged_head_bytes(r, rec_cigar(r), form);
+    return staged_head_bytes(r, rec_cigar(r), form, drop_oc);
 }
-// rec: the record, block_size word first; dst: staged_head_bytes(rec, form) bytes
-inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst)
+// rec: the record, block_size word first; dst: staged_head_bytes(rec, form, drop_oc) bytes
+inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst, bool drop_oc)
 {
     const RecView r = rec_view(rec);
     const RecCigar cg = rec_cigar(r);
@@ -842,21 +846,24 @@ inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst)
         std::memcpy(dst + fixed, cg.w, 4 * (size_t)cg.n);
         std::memcpy(dst + fixed + 4 * (size_t)cg.n, r.seq(), tail);
     }
-    if (form == STAGE_FULL) filter_aux(r.aux(), r.end(), dst + fixed + 4 * (size_t)cg.n + tail);
+    if (form == STAGE_FULL) filter_aux(r.aux(), r.end(), dst + fixed + 4 * (size_t)cg.n + tail, drop_oc);
     dst[4 + 10] = (uint8_t)(cg.n >> 16); dst[4 + 11] = (uint8_t)(cg.n >> 24);      // bin: the count's high half
     dst[4 + 12] = (uint8_t)cg.n; dst[4 + 13] = (uint8_t)(cg.n >> 8);
 }
+// ... of no run (the counting paths, whose forms keep no aux, and the model programs under tests/)
+inline int64_t staged_head_bytes(const uint8_t *rec, int form) { return staged_head_bytes(rec, form, false); }
+inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst) { stage_record_head(rec, form, dst, false); }
 // A RUN's record under its spec (there is no default: a run names what it writes).  A record that passes (staged_head.hpp
 // record_passes; STAGE_FULL only) is staged verbatim -- the block_size word and the whole record as it lies in the stream, every
 // tag, a long CIGAR still placeholder + CG tag, n_cigar_op and bin untouched; every other record is a read: its head
 inline int64_t staged_record_bytes(const uint8_t *rec, int form, const RecSpec &spec)
 {
-    return form == STAGE_FULL && staged_passes(rec + 4, spec.pass_mask) ? staged_pass_bytes(rec + 4) : staged_head_bytes(rec, form);
+    return form == STAGE_FULL && staged_passes(rec + 4, spec.pass_mask) ? staged_pass_bytes(rec + 4) : staged_head_bytes(rec, form, spec.oc());
 }
 inline void stage_record(const uint8_t *rec, int form, uint8_t *dst, const RecSpec &spec)
 {
     if (form == STAGE_FULL && staged_passes(rec + 4, spec.pass_mask)) std::memcpy(dst, rec, (size_t)staged_pass_bytes(rec + 4));
-    else stage_record_head(rec, form, dst);
+    else stage_record_head(rec, form, dst, spec.oc());
 }
 
 // ---- the record buffer's bound: what one read's record takes at the most, term by term ---------------------------------
@@ -867,10 +874,13 @@ inline void stage_record(const uint8_t *rec, int form, uint8_t *dst, const RecSp
 // digits (a batch's own finals cover the read's reference: one closing count; a caller's words may not: one per word).
 // cs: no item of the text has more than three bytes per base it covers (cs_rec.hpp, Size); de: 7.  A record that passes
 // takes exactly its staged_pass_bytes (staged_head.hpp) -- an ML-like array of tens of kilobytes included.
+// OC (oc_rec.hpp): the tag's four bytes and, for each of the input's `words` real CIGAR words, its letter and a length of at most
+// 28 bits, which has at most 9 digits -- ten bytes a word; only a changed read has the tag, the bound is taken for every read.
 inline int64_t ref_record_bound(int64_t name, int64_t words, int64_t sl) { return 36 + name + 4 * words + 16 + (sl + 1) / 2 + sl + 7 + 16; }
 inline int64_t full_record_bound(int64_t name, int64_t words, int64_t l_seq, int64_t aux) { return 36 + name + 4 * words + 32 + (l_seq + 1) / 2 + l_seq + aux + 7 + 16; }
 inline int64_t md_tag_bound(int64_t ref_covered, int64_t counts) { return 4 + 3 * ref_covered + 11 * counts; }
 inline int64_t cs_de_tags_bound(int64_t bases_covered) { return 4 + 3 * bases_covered + 7; }
+inline int64_t oc_tag_bound(int64_t words) { return 4 + 10 * words; }
 
 // integer HP tag or 0 (src/bam.pyx:46)
 inline int64_t rec_hp(const RecView &r)

@@ -1606,12 +1606,13 @@ try {
         const bool pass = staged_passes(r.p, rec.pass_mask), bad = (status[k] & NPORE_ST_BAD_INPUT) != 0;
         const int64_t ops = (bad || pass) ? 0 : cigar_text_ops(finals + final_off[k], final_len[k]);
         if (ops < 0) return fail(NPORE_E_UNSUPPORTED, "a final CIGAR is no CIGAR text (BAM output)");
-        aux[k] = pass ? 0 : filter_aux(r.aux(), r.end(), nullptr);
+        aux[k] = pass ? 0 : filter_aux(r.aux(), r.end(), nullptr, rec.oc());
         wlen[k] = 4 * ops;
         wo[k + 1] = wo[k] + 4 * ops + 16;
         rawo[k + 1] = rawo[k] + ((staged_record_bytes(rf.ptr[k], STAGE_FULL, rec) + 7) & ~7ll);
         bound += pass ? staged_pass_bytes(r.p) : full_record_bound(r.l_read_name(), ops, r.l_seq(), aux[k]);
         if (bad || pass) continue;
+        if (rec.oc()) bound += oc_tag_bound(rec_cigar(r).n);
         fin[k] = cigar_text_words(finals + final_off[k], final_len[k], ops);
         int64_t ref_covered = 0, covered = 0, compared = 0;      // (a caller's final may cover more reference than the read has, and close a count at every word)
         for (int64_t q = 0; q < ops; q++) {

@@ -85,6 +85,13 @@ def argparser():
                              "split on the GPU from the final CIGAR and the bases NM is counted on: X where NM counts a mismatch "
                              "(an IUPAC letter other than N included), = elsewhere; NM, MD, cs and de do not change.  More than "
                              "65 535 operations, which this form reaches sooner, go to the CG tag.  Without it the CIGAR has M.")
+    parser.add_argument("--oc", action="store_true",
+                        help="--records full: write the input's CIGAR as the OC:Z tag on every read whose alignment the run changed, "
+                             "as GATK's IndelRealigner does -- every word as it stood, clips included; decided and written on the "
+                             "GPU.  A read is unchanged when its input CIGAR, with = and X read as M, words of length 0 dropped and "
+                             "neighbouring words of one kind merged, is its final CIGAR.  An OC the input carried is dropped, so an "
+                             "unchanged read has none.  The position never changes: no OP is written.  Without it no OC is "
+                             "written and an input's OC stays as it came.")
     parser.add_argument("--pass_through", action="store_true",
                         help="--records full: write the records the realigner does not take -- secondary (0x100), supplementary "
                              "(0x800) and placed but unmapped (0x4) ones -- as they came, every tag included, in their place among "
@@ -120,6 +127,10 @@ def main():
     eqx = bool(getattr(cfg.args, "eqx", False))
     if eqx and records != "full":
         print("\nERROR: --eqx needs --out_format bam --records full.")
+        sys.exit(1)
+    oc = bool(getattr(cfg.args, "oc", False))
+    if oc and records != "full":
+        print("\nERROR: --oc needs --out_format bam --records full.")
         sys.exit(1)
     pass_mask = bam_mod.PASS_FLAGS if getattr(cfg.args, "pass_through", False) else 0
     if pass_mask and records != "full":
@@ -200,7 +211,7 @@ def main():
     # BAM: the index beside the file (a rank's part: a sidecar with part-relative offsets, merged by dist.gather_bam_parts);
     # the EOF member ends the whole file, not a part
     out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress, records=records, md=md, cs=cs, de=de,
-                  pass_mask=pass_mask, eqx=eqx) if as_bam else {}
+                  pass_mask=pass_mask, eqx=eqx, oc=oc) if as_bam else {}
     gather = dist_mod.gather_bam_parts if as_bam else dist_mod.gather_parts
 
     print("> extracting read data from BAM")

@@ -139,7 +139,7 @@ def start_output(a, out, nb):
     if a.out_format == "bam":
         bam.create_bam_header(out, nb)
         return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai", compress=a.bam_compress, records=a.records, md=a.md, cs=a.cs, de=a.de,
-                    pass_mask=bam.PASS_FLAGS if a.pass_through else 0, eqx=a.eqx)
+                    pass_mask=bam.PASS_FLAGS if a.pass_through else 0, eqx=a.eqx, oc=a.oc)
     bam.create_header(out, nb)
     return {}
 
@@ -233,6 +233,35 @@ def run_one_pass(ctx, bp, fa, clen, a, out):
     return res
 
 
+def count_oc(path):
+    """(records, records with an OC tag) of a BAM file: the share of the reads that --oc found changed"""
+    raw, parts, at = open(path, "rb").read(), [], 0
+    while at + 18 <= len(raw):                                   # a member: 18 bytes of header with BSIZE, the deflate stream, CRC-32 and ISIZE
+        size = struct.unpack_from("<H", raw, at + 16)[0] + 1
+        parts.append(zlib.decompress(raw[at + 18:at + size - 8], -15))
+        at += size
+    data = b"".join(parts)
+    p = 12 + struct.unpack_from("<i", data, 4)[0]
+    for _ in range(struct.unpack_from("<i", data, p - 4)[0]):
+        p += 8 + struct.unpack_from("<i", data, p)[0]
+    n = with_oc = 0
+    while p + 4 <= len(data):
+        size, = struct.unpack_from("<i", data, p)
+        l_rn, n_cig, l_seq = data[p + 12], struct.unpack_from("<H", data, p + 16)[0], struct.unpack_from("<i", data, p + 20)[0]
+        aux, q = bytes(data[p + 36 + l_rn + 4 * n_cig + (l_seq + 1) // 2 + l_seq:p + 4 + size]), 0
+        while q + 3 <= len(aux):
+            if aux[q:q + 3] == b"OCZ":
+                with_oc += 1
+                break
+            w = bam._aux_value_len(aux, q + 3, aux[q + 2:q + 3])
+            if w is None:
+                break
+            q += 3 + w
+        n += 1
+        p += 4 + size
+    return n, with_oc
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reads", type=int, default=48000)
@@ -267,6 +296,7 @@ def main():
     ap.add_argument("--cs", choices=("short", "long"), default=None, help="--records full: with the cs tag behind NM / MD, built on the GPU")
     ap.add_argument("--de", action="store_true", help="--records full: with the de tag behind that, counted on the GPU")
     ap.add_argument("--eqx", action="store_true", help="--records full: the final CIGAR with = and X in the place of M, split on the GPU")
+    ap.add_argument("--oc", action="store_true", help="--records full: the input's CIGAR as OC:Z on the reads that changed, decided on the GPU")
     ap.add_argument("--tags", action="store_true",
                     help="every synthetic read carries an RG:Z tag and a B,C array of l_seq / 2 bytes (an ML-like load for --records full)")
     ap.add_argument("--flagged", type=float, default=0.0,
@@ -288,6 +318,8 @@ def main():
         ap.error("--cs / --de need --records full")
     if a.eqx and a.records != "full":
         ap.error("--eqx needs --records full")
+    if a.oc and a.records != "full":
+        ap.error("--oc needs --records full")
     if a.pass_through and a.records != "full":
         ap.error("--pass_through needs --records full")
     if a.gen_into:
@@ -372,13 +404,16 @@ def main():
                 "one_pass": one_pass, "one_pass_output_identical": same_one_pass,
                 "reads": a.reads, "distinct_reads": a.reads if a.distinct <= 0 else min(a.distinct, a.reads),
                 "qualities": "constant 20" if a.const_qual else "uniform per base over phred 0 ... 93 (reference test/generate_bam.py:63,79)",
-                "ref_len": a.ref_len, "r": a.r, "batch": a.batch, "out_format": a.out_format, "bam_compress": a.bam_compress, "records": a.records, "md": a.md, "cs": a.cs, "de": a.de, "eqx": a.eqx, "tags": a.tags,
+                "ref_len": a.ref_len, "r": a.r, "batch": a.batch, "out_format": a.out_format, "bam_compress": a.bam_compress, "records": a.records, "md": a.md, "cs": a.cs, "de": a.de, "eqx": a.eqx, "oc": a.oc, "tags": a.tags,
                 "flagged": a.flagged, "pass_through": a.pass_through,
                 "output_bytes": os.path.getsize(out + ".o"),
                 "host_cpus": len(os.sched_getaffinity(0)), "bam_bytes": os.path.getsize(bp),
                 "resident": resident, "streamed": streamed, "streamed_output_identical": same,
                 "cold_start": cold,
                 "rss_mb_before_timed_runs": round(rss0 / 1024.0, 1), "python_restatement": py, "input_generation_s": round(t_gen, 1)}
+        if a.oc:
+            n_rec, n_oc = count_oc(out + ".o")
+            line["oc_records"], line["oc_share"] = n_oc, round(n_oc / max(n_rec, 1), 4)
         print(json.dumps(line))
         ctx.close()
 

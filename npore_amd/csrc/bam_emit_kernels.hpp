@@ -22,6 +22,11 @@
 // and the read's ORIGINAL CIGAR where the run changed it and that is asked for:
 //   OC       oc_size_kernel, emit_oc_kernel    (oc_rec.hpp, NPORE_TAG_OC): changed or not is decided in front of the placement, which
 //                                              the host could not do -- it never sees the final words; ONE walk, oc_walk, likewise
+// What these share stands once: which reads get no such tags is bam_no_tags; where every part of a FULL record lies, and so
+// its size, is BamFullShape's *_at members (a new tag is a size in bam_full_shape and one more *_at); what a tag's emit kernel
+// starts from is bam_tag_shape.  The walks over the FINAL words of NM and =/X are a pick and a visit body under one wave frame
+// (cigar_tiles, differ_round, since_mark; wave_incl_sum also serves OC's two).  md_walk and cs_walk keep the same loop written
+// out: under the frame their kernels measured 2 - 3 % slower ("the emit chain's own time").
 // A final CIGAR of more than 65 535 operations goes out as htslib writes it (bam_reader.hpp RECORD): two placeholder words
 // in the CIGAR's place, the real words in a CG:B,I tag behind the other tags, in either form.
 // The host then takes the batch's bytes as they lie (BgzfStoredWriter) and the records' lengths for its index.
@@ -249,56 +254,127 @@ __global__ __launch_bounds__(64) void emit_bam_records_kernel(BamEmitParams p)
     }
 }
 
+// ---- the wave frame under the walks over a read's final CIGAR (NM, =/X; md_walk and cs_walk write the same loop out) ----
+// One wavefront per read over tiles of 64 CIGAR words: lane l holds word l of the tile (`0M` behind the end), and inclusive wave
+// sums of what the words consume place every word on the reference and on the query.  The sums fit 32 bits, a read has fewer
+// than 2^31 operations; the slots lie at multiples of 4, so the words are read as words.  A walk is a PICK of the words it
+// visits and the BODY of a visit (cigar_tiles); a compared word is taken 64 positions per round (differ_round); what a walk
+// carries from round to round, word to word and tile to tile is the same in every lane.
+
+// read k gets no tags made from its final CIGAR: it is refused and has no record, or it passes as it came (staged_head.hpp)
+__device__ __forceinline__ bool bam_no_tags(const BamEmitParams &p, int64_t k)
+{
+    return (p.status[p.read_base + k] & 32) || staged_passes(p.raw + p.raw_off[k] + 4, p.pass_mask);
+}
+
+// read k's final words and the two code arrays they walk over
+struct FinalWords {
+    int64_t n;
+    const uint32_t *w;
+    const uint8_t *ref, *seq;
+    int64_t rl, sl;
+};
+__device__ __forceinline__ FinalWords final_words(const BamEmitParams &p, int64_t k)
+{
+    const int64_t g = p.read_base + k;
+    FinalWords r;
+    r.n = p.words_len[g] <= 0 ? 0 : p.words_len[g] >> 2;
+    r.w = reinterpret_cast<const uint32_t *>(p.words + p.words_off[g]);
+    r.ref = p.refs + p.ref_off[k];
+    r.seq = p.seqs + p.seq_off[k];
+    r.rl = p.ref_off[k + 1] - p.ref_off[k];
+    r.sl = p.seq_off[k + 1] - p.seq_off[k];
+    return r;
+}
+
+// v summed over the lanes up to and including this one (uint32_t; 64 bits for oc_changed)
+template <class T>
+__device__ __forceinline__ T wave_incl_sum(T v, int lane)
+{
+    for (int d = 1; d < 64; d <<= 1) {
+        const T x = __shfl_up(v, d);
+        if (lane >= d) v += x;
+    }
+    return v;
+}
+
+// pick(op, len) is asked once for every word of the read, in the lane that holds it -- so it is also where a per-lane tally goes
+// (NM's bases under I and D).  The picked words of a tile are then visited in word order, all lanes together:
+// visit(op, len, a, b) gets the word and where it begins on the reference and on the query, the same in every lane.
+template <class Pick, class Visit>
+__device__ __forceinline__ void cigar_tiles(const FinalWords &r, int lane, Pick pick, Visit visit)
+{
+    int64_t a0 = 0, b0 = 0;                  // consumed in front of the tile
+    for (int64_t t0 = 0; t0 < r.n; t0 += 64) {
+        const uint32_t v = t0 + lane < r.n ? r.w[t0 + lane] : 0u;
+        const uint32_t op = v & 15u, len = v >> 4, use = nm_consumes(op);
+        const uint32_t ra = (use & 1u) ? len : 0u, qa = (use & 2u) ? len : 0u;
+        const uint32_t ri = wave_incl_sum(ra, lane), qi = wave_incl_sum(qa, lane);
+        unsigned long long todo = __builtin_amdgcn_ballot_w64(pick(op, len));
+        while (todo) {
+            const int j = (int)__builtin_ctzll(todo);
+            todo &= todo - 1;
+            visit(__shfl(op, j), __shfl(len, j), a0 + __shfl(ri - ra, j), b0 + __shfl(qi - qa, j));
+        }
+        a0 += __shfl(ri, 63);
+        b0 += __shfl(qi, 63);
+    }
+}
+
+// one round of a compared word of lj positions that begins at (aj, bj): lane l looks at position q = q0 + l; in_round of the 64
+// lie inside the word; d: this lane's position differs (nm_differs); ev: the lanes where it does
+struct DifferRound {
+    uint32_t q, in_round;
+    bool d;
+    unsigned long long ev;
+};
+__device__ __forceinline__ DifferRound differ_round(const FinalWords &r, int lane, uint32_t lj, int64_t aj, int64_t bj, uint32_t q0)
+{
+    DifferRound x;
+    x.q = q0 + (uint32_t)lane;
+    x.in_round = min(64u, lj - q0);
+    x.d = x.q < lj && nm_differs(r.ref, r.rl, aj + x.q, r.seq, r.sl, bj + x.q);
+    x.ev = __builtin_amdgcn_ballot_w64(x.d);
+    return x;
+}
+
+// How far a stretch reaches back from position `at` of a round, given `below`, the round's marks below `at`: to the last of
+// them -- OWN = 0: that mark's position counted (at - its position), =/X's runs begin AT a boundary; OWN = 1: not counted,
+// MD's and cs's counts begin BEHIND a differing position -- and with none below, over the round's positions so far and the
+// `carry` from the rounds before (carry + at).  at = the lane, below = marks & lanes_below(lane): the stretch that ends in front
+// of the lane; at = in_round, below = all marks (none lies further up): the carry out of the round.
+__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
+template <int OWN>
+__device__ __forceinline__ uint32_t since_mark(unsigned long long below, uint32_t at, uint32_t carry)
+{
+    return below ? at - (uint32_t)OWN - (uint32_t)(63 - (int)__builtin_clzll(below)) : carry + at;
+}
+
 // ---- FULL records (bam_reader.hpp FULL RECORD; host twin: bam_record_full_into) ------------------------------------------
 // The staged head carries the kept aux bytes behind the qualities (hostio.hpp STAGE_FULL; p.hp[k]: how many), so bases,
 // qualities and tags are ONE contiguous copy; the clip words come from the staged CIGAR; NM is counted by nm_count_kernel
 // between the standardisation and the placement.
 
-// NM (nm_rec.hpp) of every read of the group: one wavefront per read over tiles of 64 CIGAR words.  Lane l holds word l of
-// the tile; wave prefix sums of the reference and the query consumption give every word its two positions; I and D add
-// their lengths in their lanes; an M run is compared 64 positions per round, one ballot + popcount each.
+// NM (nm_rec.hpp) of every read of the group: I and D add their lengths in their lanes; an M run is a ballot + popcount a round.
 __global__ __launch_bounds__(64) void nm_count_kernel(BamEmitParams p)
 {
     const int64_t k = blockIdx.x;
     if (k >= p.n_reads) return;
     const int lane = threadIdx.x;
-    const int64_t g = p.read_base + k;
-    if (staged_passes(p.raw + p.raw_off[k] + 4, p.pass_mask)) {
-        if (lane == 0) p.nm[k] = 0;
-        return;
-    }
-    const int64_t n = (p.status[g] & 32) || p.words_len[g] <= 0 ? 0 : p.words_len[g] >> 2;
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(p.words + p.words_off[g]);      // (the slots lie at multiples of 4)
-    const uint8_t *ref = p.refs + p.ref_off[k], *seq = p.seqs + p.seq_off[k];
-    const int64_t rl = p.ref_off[k + 1] - p.ref_off[k], sl = p.seq_off[k + 1] - p.seq_off[k];
-    int64_t a0 = 0, b0 = 0;                  // consumed in front of the tile
     uint32_t whole = 0, differ = 0;          // per lane: bases under I and D; the same in every lane: compared positions that count
-    for (int64_t t0 = 0; t0 < n; t0 += 64) {
-        const uint32_t v = t0 + lane < n ? w[t0 + lane] : 0u;       // (behind the end: `0M`)
-        const uint32_t op = v & 15u, len = v >> 4, use = nm_consumes(op);
-        if (nm_counts_whole(op)) whole += len;
-        const uint32_t ra = (use & 1u) ? len : 0u, qa = (use & 2u) ? len : 0u;
-        uint32_t ri = ra, qi = qa;           // inclusive sums over the tile (a read has fewer than 2^31 ops)
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t x = (uint32_t)__shfl_up((int)ri, d), y = (uint32_t)__shfl_up((int)qi, d);
-            if (lane >= d) { ri += x; qi += y; }
-        }
-        unsigned long long runs = __builtin_amdgcn_ballot_w64(nm_compares(op) && len > 0);
-        while (runs) {
-            const int j = (int)__builtin_ctzll(runs);
-            runs &= runs - 1;
-            const uint32_t lj = (uint32_t)__shfl((int)len, j);
-            const int64_t aj = a0 + (uint32_t)__shfl((int)(ri - ra), j), bj = b0 + (uint32_t)__shfl((int)(qi - qa), j);
-            for (uint32_t q0 = 0; q0 < lj; q0 += 64) {
-                const uint32_t q = q0 + (uint32_t)lane;
-                const bool d = q < lj && nm_differs(ref, rl, aj + q, seq, sl, bj + q);
-                differ += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(d));
-            }
-        }
-        a0 += (uint32_t)__shfl((int)ri, 63);
-        b0 += (uint32_t)__shfl((int)qi, 63);
+    if (!bam_no_tags(p, k)) {
+        const FinalWords r = final_words(p, k);
+        cigar_tiles(
+            r, lane,
+            [&](uint32_t op, uint32_t len) {
+                if (nm_counts_whole(op)) whole += len;
+                return nm_compares(op) && len > 0;
+            },
+            [&](uint32_t, uint32_t lj, int64_t aj, int64_t bj) {
+                for (uint32_t q0 = 0; q0 < lj; q0 += 64) differ += (uint32_t)__builtin_popcountll(differ_round(r, lane, lj, aj, bj, q0).ev);
+            });
+        for (int d = 32; d; d >>= 1) whole += __shfl_xor(whole, d);
     }
-    for (int d = 32; d; d >>= 1) whole += (uint32_t)__shfl_xor((int)whole, d);
     if (lane == 0) p.nm[k] = (int32_t)(whole + differ);
 }
 
@@ -312,6 +388,18 @@ struct BamFullShape {
     int64_t mdb;                   // bytes of the MD tag behind NM (4 + its text; 0: none)
     int64_t csb, deb;              // bytes of the cs tag behind that (4 + its text; 0: none) and of the de tag (7; 0: none)
     int64_t ocb;                   // bytes of the OC tag behind those (4 + its text; 0: none)
+    // THE RECORD'S LAYOUT, which the FULL kernels take from here: where each part begins, in bytes from the record's block_size word.
+    // Every part lies behind the one before it, so a tag that has a size has a place, and the record ends behind the last.
+    __device__ int64_t cigar_at() const { return 36 + (int64_t)f[8]; }                      // behind the fixed fields and the name
+    __device__ int64_t body_at() const { return cigar_at() + (lng ? 8 : 4 * n_cig); }       // bases, qualities, kept aux (long: behind the placeholder)
+    __device__ int64_t nm_at() const { return body_at() + (l_seq + 1) / 2 + l_seq + aux; }
+    __device__ int64_t md_at() const { return nm_at() + 3 + nmb; }
+    __device__ int64_t cs_at() const { return md_at() + mdb; }
+    __device__ int64_t de_at() const { return cs_at() + csb; }
+    __device__ int64_t oc_at() const { return de_at() + deb; }
+    __device__ int64_t cg_at() const { return oc_at() + ocb; }                              // long only: C G B I, the count, the words
+    __device__ int64_t words_at() const { return lng ? cg_at() + 8 : cigar_at(); }          // the CIGAR words, wherever they go
+    __device__ int64_t end() const { return cg_at() + (lng ? 8 + 4 * n_cig : 0); }
 };
 // the clip words [0, ci) and [cj, nc) of a staged CIGAR's nc words at cg (bam_reader.hpp full_clip_words)
 __device__ __forceinline__ void staged_clip_words(const uint8_t *cg, int nc, int &ci, int &cj)
@@ -347,17 +435,17 @@ __device__ __forceinline__ BamFullShape bam_full_shape(const BamEmitParams &p, i
     s.csb = (p.tags & NPORE_TAG_CS) ? 4 + (int64_t)p.cs_len[k] : 0;
     s.deb = (p.tags & NPORE_TAG_DE) ? 7 : 0;
     s.ocb = p.oc_len && p.oc_len[k] ? 4 + (int64_t)p.oc_len[k] : 0;
-    s.size = (p.status[g] & 32) ? 0
-                                : 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb +
-                                      s.csb + s.deb + s.ocb + (s.lng ? 8 + 4 * s.n_cig : 0);
+    s.size = (p.status[g] & 32) ? 0 : s.end();
     return s;
 }
 __device__ __forceinline__ int64_t bam_full_record_size(const BamEmitParams &p, int64_t k) { return bam_full_shape(p, k).size; }
-// where the CIGAR words of read k's record lie: behind the name, or (long) behind the tags and CG:B,I's eight bytes
-__device__ __forceinline__ uint8_t *bam_full_words_at(const BamEmitParams &p, int64_t k, const BamFullShape &s)
+// what a kernel that writes a tag into read k's placed record starts from: the record's shape; false: there is nothing to
+// write -- no such read, no record, no room, or a record that passed as it came
+__device__ __forceinline__ bool bam_tag_shape(const BamEmitParams &p, int64_t k, BamFullShape &s)
 {
-    uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8];
-    return s.lng ? o + 8 + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb + s.csb + s.deb + s.ocb + 8 : o;
+    if (k >= p.n_reads || p.rec_len[k] <= 0) return false;
+    s = bam_full_shape(p, k);
+    return !s.pass;
 }
 
 // one wavefront per read
@@ -377,34 +465,28 @@ __global__ __launch_bounds__(64) void emit_bam_full_kernel(BamEmitParams p)
     }
     const int32_t pos = (int32_t)ld32(f + 4);
     const int l_rn = f[8];
-    const int64_t reflen = p.ref_off[k + 1] - p.ref_off[k], body = (s.l_seq + 1) / 2 + s.l_seq + s.aux;
-    uint8_t *o = p.recs + p.rec_off[k];
+    const int64_t reflen = p.ref_off[k + 1] - p.ref_off[k];
+    uint8_t *rec = p.recs + p.rec_off[k];                        // every part at its place of the shape's map
     if (lane < 9) {                                              // block_size and the fixed fields, a word per lane: the input's but bin and n_cigar_op
         uint32_t w = ld32(f + 4 * (lane > 0 ? lane - 1 : 0));
         if (lane == 0) w = (uint32_t)(size - 4);
         if (lane == 3) w = (uint32_t)l_rn | (uint32_t)f[9] << 8 | bam_reg2bin_dev(pos, (int64_t)pos + max((int64_t)1, reflen)) << 16;
         if (lane == 4) w = (s.lng ? 2u : (uint32_t)s.n_cig) | ld16(f + 14) << 16;
-        st32(o + 4 * lane, w);
+        st32(rec + 4 * lane, w);
     }
-    o += 36;
-    for (int j = lane; j < l_rn; j += 64) o[j] = f[32 + j];
-    o += l_rn;
-    uint8_t *cw = o;                                             // where the CIGAR words go
-    if (s.lng) {                                                 // the placeholder here, CG:B,I behind NM (and MD, cs, de, OC)
-        cw = o + 8 + body + 3 + s.nmb + s.mdb + s.csb + s.deb + s.ocb + 8;
-        if (lane < 2) st32(o + 4 * lane, lane == 0 ? ((uint32_t)s.l_seq << 4 | 4u) : ((uint32_t)reflen << 4 | 3u));
+    for (int j = lane; j < l_rn; j += 64) rec[36 + j] = f[32 + j];
+    uint8_t *cw = rec + s.words_at();                            // where the CIGAR words go
+    if (s.lng) {                                                 // the placeholder in the CIGAR's place, CG:B,I behind NM (and MD, cs, de, OC)
+        if (lane < 2) st32(rec + s.cigar_at() + 4 * lane, lane == 0 ? ((uint32_t)s.l_seq << 4 | 4u) : ((uint32_t)reflen << 4 | 3u));
         if (lane >= 4 && lane < 8) cw[lane - 12] = (uint8_t)"CGBI"[lane - 4];
         if (lane >= 8 && lane < 12) cw[lane - 12] = (uint8_t)((uint32_t)s.n_cig >> (8 * (lane - 8)));
-        o += 8;
-    } else {
-        o += 4 * s.n_cig;
     }
     wave_copy<0>(cw, s.cg, 4 * (int64_t)s.ci, false, lane);
     if (!p.eqx_len) wave_copy<0>(cw + 4 * s.ci, p.words + p.words_off[g], s.wl, false, lane);      // (=/X form: emit_eqx_kernel's span)
     wave_copy<0>(cw + 4 * s.ci + s.wl, s.cg + 4 * (int64_t)s.cj, 4 * (int64_t)(s.nc - s.cj), false, lane);
-    wave_copy<0>(o, s.sq, body, false, lane);                    // bases, qualities, kept aux: as they lie in the staged head
-    o += body;
+    wave_copy<0>(rec + s.body_at(), s.sq, s.nm_at() - s.body_at(), false, lane);      // bases, qualities, kept aux: as they lie in the staged head
     if (lane == 0) {
+        uint8_t *o = rec + s.nm_at();
         const uint32_t nm = (uint32_t)p.nm[k];
         o[0] = 'N'; o[1] = 'M';
         o[2] = (uint8_t)(s.nmb == 1 ? 'C' : s.nmb == 2 ? 'S' : 'I');
@@ -492,27 +574,24 @@ __device__ __forceinline__ uint32_t md_walk(const BamEmitParams &p, int64_t k, i
     return at + (uint32_t)nd;
 }
 
-// bytes of every read's MD text (0: the read is refused and has no record), between nm_count_kernel and the placement
+// bytes of every read's MD text (0: the read gets no tags), between nm_count_kernel and the placement
 __global__ __launch_bounds__(64) void md_size_kernel(BamEmitParams p)
 {
     const int64_t k = blockIdx.x;
     if (k >= p.n_reads) return;
     const int lane = threadIdx.x;
-    const bool none = (p.status[p.read_base + k] & 32) || staged_passes(p.raw + p.raw_off[k] + 4, p.pass_mask);
-    const uint32_t len = none ? 0u : md_walk(p, k, lane, MdCount{});
+    const uint32_t len = bam_no_tags(p, k) ? 0u : md_walk(p, k, lane, MdCount{});
     if (lane == 0) p.md_len[k] = (int32_t)len;
 }
 
-// 'M' 'D' 'Z' text NUL behind the record's NM (bam_full_shape), behind emit_bam_full_kernel on its stream
+// 'M' 'D' 'Z' text NUL at the record's md_at, behind emit_bam_full_kernel on its stream
 __global__ __launch_bounds__(64) void emit_md_kernel(BamEmitParams p)
 {
     const int64_t k = blockIdx.x;
-    if (k >= p.n_reads) return;
     const int lane = threadIdx.x;
-    if (p.rec_len[k] <= 0) return;
-    const BamFullShape s = bam_full_shape(p, k);
-    if (s.pass) return;
-    uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb;
+    BamFullShape s;
+    if (!bam_tag_shape(p, k, s)) return;
+    uint8_t *o = p.recs + p.rec_off[k] + s.md_at();
     if (lane < 3) o[lane] = (uint8_t)"MDZ"[lane];
     const int64_t cap = p.md_len[k];
     md_walk(p, k, lane, MdStore{o + 3, cap});
@@ -632,8 +711,8 @@ __device__ __forceinline__ uint32_t cs_walk(const BamEmitParams &p, int64_t k, i
     return at;
 }
 
-// bytes of every read's cs text and its de value (0, 0.0f: the read is refused and has no record), beside md_size_kernel in front
-// of the placement; only NPORE_TAG_DE: the walk runs for the counts and the size stays 0
+// bytes of every read's cs text and its de value (0, 0.0f: the read gets no tags), beside md_size_kernel in front of the
+// placement; only NPORE_TAG_DE: the walk runs for the counts and the size stays 0
 __global__ __launch_bounds__(64) void cs_size_kernel(BamEmitParams p)
 {
     const int64_t k = blockIdx.x;
@@ -641,34 +720,32 @@ __global__ __launch_bounds__(64) void cs_size_kernel(BamEmitParams p)
     const int lane = threadIdx.x;
     CsCounts c;
     uint32_t len = 0;
-    if (!(p.status[p.read_base + k] & 32) && !staged_passes(p.raw + p.raw_off[k] + 4, p.pass_mask)) len = (p.tags & NPORE_TAG_CS_LONG) ? cs_walk<true>(p, k, lane, MdCount{}, c) : cs_walk<false>(p, k, lane, MdCount{}, c);
+    if (!bam_no_tags(p, k)) len = (p.tags & NPORE_TAG_CS_LONG) ? cs_walk<true>(p, k, lane, MdCount{}, c) : cs_walk<false>(p, k, lane, MdCount{}, c);
     if (lane == 0) {
         p.cs_len[k] = (p.tags & NPORE_TAG_CS) ? (int32_t)len : 0;
         p.de[k] = de_of_counts(c.e, c.x, c.g);
     }
 }
 
-// 'c' 's' 'Z' text NUL and 'd' 'e' 'f' value behind the record's NM and MD (bam_full_shape), behind emit_bam_full_kernel (and
-// emit_md_kernel) on its stream
+// 'c' 's' 'Z' text NUL at the record's cs_at and 'd' 'e' 'f' value at its de_at, behind emit_bam_full_kernel (and emit_md_kernel)
+// on its stream
 __global__ __launch_bounds__(64) void emit_cs_kernel(BamEmitParams p)
 {
     const int64_t k = blockIdx.x;
-    if (k >= p.n_reads) return;
     const int lane = threadIdx.x;
-    if (p.rec_len[k] <= 0) return;
-    const BamFullShape s = bam_full_shape(p, k);
-    if (s.pass) return;
-    uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb;
+    BamFullShape s;
+    if (!bam_tag_shape(p, k, s)) return;
     if (s.csb) {
+        uint8_t *o = p.recs + p.rec_off[k] + s.cs_at();
         if (lane < 3) o[lane] = (uint8_t)"csZ"[lane];
         const int64_t cap = p.cs_len[k];
         CsCounts c;
         if (p.tags & NPORE_TAG_CS_LONG) cs_walk<true>(p, k, lane, MdStore{o + 3, cap}, c);
         else cs_walk<false>(p, k, lane, MdStore{o + 3, cap}, c);
         if (lane == 0) o[3 + cap] = 0;
-        o += s.csb;
     }
     if (s.deb) {
+        uint8_t *o = p.recs + p.rec_off[k] + s.de_at();
         const uint32_t bits = __float_as_uint(p.de[k]);
         if (lane < 3) o[lane] = (uint8_t)"def"[lane];
         else if (lane < 7) o[lane] = (uint8_t)(bits >> (8 * (lane - 3)));
@@ -676,27 +753,20 @@ __global__ __launch_bounds__(64) void emit_cs_kernel(BamEmitParams p)
 }
 
 // ---- the =/X form of a FULL record's CIGAR (NPORE_CIGAR_EQX; eqx_rec.hpp states the rule and holds the sequential twin) ----
-// cs_walk's frame: one wavefront per read over tiles of 64 CIGAR words, the words of length > 0 of a tile visited in word
-// order.  The open run (`cls`, its op, and `run`, its positions; run == 0: none) and `cnt` (words out so far) are the same
-// in every lane and are carried across rounds, words and tiles.
+// Every word of length > 0 is visited.  The open run (`cls`, its op, and `run`, its positions; run == 0: none) and `cnt` (words
+// out so far) are the same in every lane and are carried across rounds, words and tiles.
 //   a word that is not compared: lane 0 closes the open run -- its word at cnt -- and copies the word behind it.
-//   M-type word, 64 positions per round: the ballot of nm_differs gives every lane's class and the class of the lane below it
-//     (lane 0: the open run's).  A lane whose class differs from the one below is a BOUNDARY: it writes the run that ends in
-//     front of it -- the class below, the distance to the previous boundary of the round (the round's first boundary: run +
-//     its lane) -- at cnt + the boundaries below it.  The carry out: the last position's class; run + the round's positions
-//     where the round has no boundary, otherwise the positions from the last boundary on.
+//   M-type word: a round's ballot gives every lane's class and the class of the lane below it (lane 0: the open run's).  A lane
+//     whose class differs from the one below is a BOUNDARY: it writes the run that ends in front of it -- the class below, the
+//     positions from the previous boundary of the round on (the round's first boundary: run + its lane) -- at cnt + the
+//     boundaries below it.  The carry out: the last position's class; run + the round's positions where the round has no
+//     boundary, otherwise the positions from the last boundary on.
 // The walk is ONE function over a sink (eqx_rec.hpp): eqx_size_kernel runs it with EqxCount, emit_eqx_kernel with EqxStore, so
 // count and words cannot differ.  Returns the number of words.
 template <class Sink>
 __device__ __forceinline__ uint32_t eqx_walk(const BamEmitParams &p, int64_t k, int lane, const Sink &sink)
 {
-    const int64_t g = p.read_base + k;
-    const int64_t n = p.words_len[g] <= 0 ? 0 : p.words_len[g] >> 2;
-    const uint32_t *w = reinterpret_cast<const uint32_t *>(p.words + p.words_off[g]);      // (the slots lie at multiples of 4)
-    const uint8_t *ref = p.refs + p.ref_off[k], *seq = p.seqs + p.seq_off[k];
-    const int64_t rl = p.ref_off[k + 1] - p.ref_off[k], sl = p.seq_off[k + 1] - p.seq_off[k];
-    const unsigned long long below_me = (1ull << lane) - 1ull;
-    int64_t a0 = 0, b0 = 0;                  // consumed in front of the tile
+    const FinalWords r = final_words(p, k);
     uint32_t cnt = 0, run = 0, cls = EQX_EQ;
     auto close_run = [&]() {
         if (run > 0) {
@@ -705,61 +775,42 @@ __device__ __forceinline__ uint32_t eqx_walk(const BamEmitParams &p, int64_t k, 
         }
         run = 0;
     };
-    for (int64_t t0 = 0; t0 < n; t0 += 64) {
-        const uint32_t v = t0 + lane < n ? w[t0 + lane] : 0u;       // (behind the end: `0M`)
-        const uint32_t op = v & 15u, len = v >> 4, use = nm_consumes(op);
-        const uint32_t ra = (use & 1u) ? len : 0u, qa = (use & 2u) ? len : 0u;
-        uint32_t ri = ra, qi = qa;           // inclusive sums over the tile
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t x = (uint32_t)__shfl_up((int)ri, d), y = (uint32_t)__shfl_up((int)qi, d);
-            if (lane >= d) { ri += x; qi += y; }
-        }
-        unsigned long long runs = __builtin_amdgcn_ballot_w64(len > 0);
-        while (runs) {
-            const int j = (int)__builtin_ctzll(runs);
-            runs &= runs - 1;
-            const uint32_t vj = (uint32_t)__shfl((int)v, j), lj = vj >> 4;
-            if (!nm_compares(vj & 15u)) {
+    cigar_tiles(
+        r, lane, [](uint32_t, uint32_t len) { return len > 0; },
+        [&](uint32_t opj, uint32_t lj, int64_t aj, int64_t bj) {
+            if (!nm_compares(opj)) {
                 close_run();
-                if (lane == 0) sink.put(cnt, vj);
+                if (lane == 0) sink.put(cnt, lj << 4 | opj);
                 cnt++;
-                continue;
+                return;
             }
-            const int64_t aj = a0 + (uint32_t)__shfl((int)(ri - ra), j), bj = b0 + (uint32_t)__shfl((int)(qi - qa), j);
             for (uint32_t q0 = 0; q0 < lj; q0 += 64) {
-                const uint32_t q = q0 + (uint32_t)lane, in_round = min(64u, lj - q0);
-                const bool d = q < lj && nm_differs(ref, rl, aj + q, seq, sl, bj + q);
-                const unsigned long long ev = __builtin_amdgcn_ballot_w64(d);
-                const unsigned long long valid = in_round < 64u ? (1ull << in_round) - 1ull : ~0ull;
-                const bool opens = run > 0 && cls != ((ev & 1ull) ? EQX_X : EQX_EQ);       // lane 0 ends the carried run
-                const unsigned long long bd = ((ev ^ (ev << 1)) & valid & ~1ull) | (opens ? 1ull : 0ull);
+                const DifferRound x = differ_round(r, lane, lj, aj, bj, q0);
+                const unsigned long long valid = x.in_round < 64u ? (1ull << x.in_round) - 1ull : ~0ull;
+                const bool opens = run > 0 && cls != ((x.ev & 1ull) ? EQX_X : EQX_EQ);       // lane 0 ends the carried run
+                const unsigned long long bd = ((x.ev ^ (x.ev << 1)) & valid & ~1ull) | (opens ? 1ull : 0ull);
                 if ((bd >> lane) & 1ull) {
-                    const unsigned long long before = bd & below_me;
-                    const uint32_t length = before ? (uint32_t)(lane - (63 - (int)__builtin_clzll(before))) : run + (uint32_t)lane;
-                    const uint32_t below = lane == 0 ? cls : ((ev >> (lane - 1)) & 1ull) ? EQX_X : EQX_EQ;
-                    sink.put(cnt + (uint32_t)__builtin_popcountll(before), length << 4 | below);
+                    const uint32_t below = lane == 0 ? cls : ((x.ev >> (lane - 1)) & 1ull) ? EQX_X : EQX_EQ;
+                    const uint32_t slot = cnt + (uint32_t)__builtin_popcountll(bd & lanes_below(lane));
+                    sink.put(slot, since_mark<0>(bd & lanes_below(lane), (uint32_t)lane, run) << 4 | below);
                 }
                 cnt += (uint32_t)__builtin_popcountll(bd);
-                run = bd ? in_round - (uint32_t)(63 - (int)__builtin_clzll(bd)) : run + in_round;
-                cls = ((ev >> (in_round - 1u)) & 1ull) ? EQX_X : EQX_EQ;
+                run = since_mark<0>(bd, x.in_round, run);
+                cls = ((x.ev >> (x.in_round - 1u)) & 1ull) ? EQX_X : EQX_EQ;
             }
-        }
-        a0 += (uint32_t)__shfl((int)ri, 63);
-        b0 += (uint32_t)__shfl((int)qi, 63);
-    }
+        });
     close_run();
     return cnt;
 }
 
-// words of every read's final CIGAR in =/X form (0: the read is refused or passes), beside md_size_kernel and cs_size_kernel in
-// front of the placement, which takes the record's n_cigar_op, its CG decision and its size from it (bam_full_shape)
+// words of every read's final CIGAR in =/X form (0: the read gets no tags), beside md_size_kernel and cs_size_kernel in front
+// of the placement, which takes the record's n_cigar_op, its CG decision and its size from it (bam_full_shape)
 __global__ __launch_bounds__(64) void eqx_size_kernel(BamEmitParams p)
 {
     const int64_t k = blockIdx.x;
     if (k >= p.n_reads) return;
     const int lane = threadIdx.x;
-    const bool none = (p.status[p.read_base + k] & 32) || staged_passes(p.raw + p.raw_off[k] + 4, p.pass_mask);
-    const uint32_t cnt = none ? 0u : eqx_walk(p, k, lane, EqxCount{});
+    const uint32_t cnt = bam_no_tags(p, k) ? 0u : eqx_walk(p, k, lane, EqxCount{});
     if (lane == 0) p.eqx_len[k] = (int32_t)cnt;
 }
 
@@ -768,12 +819,10 @@ __global__ __launch_bounds__(64) void eqx_size_kernel(BamEmitParams p)
 __global__ __launch_bounds__(64) void emit_eqx_kernel(BamEmitParams p)
 {
     const int64_t k = blockIdx.x;
-    if (k >= p.n_reads) return;
     const int lane = threadIdx.x;
-    if (p.rec_len[k] <= 0) return;
-    const BamFullShape s = bam_full_shape(p, k);
-    if (s.pass) return;
-    eqx_walk(p, k, lane, EqxStore{bam_full_words_at(p, k, s) + 4 * s.ci, (int64_t)p.eqx_len[k]});
+    BamFullShape s;
+    if (!bam_tag_shape(p, k, s)) return;
+    eqx_walk(p, k, lane, EqxStore{p.recs + p.rec_off[k] + s.words_at() + 4 * s.ci, (int64_t)p.eqx_len[k]});
 }
 
 // ---- the OC tag of a FULL record (NPORE_TAG_OC; oc_rec.hpp states the rule and holds the sequential twins) --------------------
@@ -808,11 +857,7 @@ __device__ __forceinline__ bool oc_changed(const BamEmitParams &p, int64_t k, in
         const uint32_t op_prev = (uint32_t)__shfl((int)op, prev);
         const bool begins = len > 0 && (before ? op != op_prev : (runs == 0 || op != rop));
         const unsigned long long bd = __builtin_amdgcn_ballot_w64(begins);
-        unsigned long long incl = len;       // inclusive sums of the lengths over the tile
-        for (int d = 1; d < 64; d <<= 1) {
-            const unsigned long long x = (unsigned long long)__shfl_up((long long)incl, d);
-            if (lane >= d) incl += x;
-        }
+        const unsigned long long incl = wave_incl_sum((unsigned long long)len, lane);      // of the lengths over the tile
         const unsigned long long excl = incl - len, whole = (unsigned long long)__shfl((long long)incl, 63);
         // the run in front of a lane that begins one: from the previous beginning of the tile, or the carried one
         const unsigned long long bd_before = bd & below_me;
@@ -853,54 +898,45 @@ __device__ __forceinline__ uint32_t oc_walk(const uint8_t *cg, int nc, int lane,
         const bool in = t0 + lane < nc;
         const uint32_t v = in ? ld32(cg + 4 * (t0 + lane)) : 0u;
         const int nd = md_digits(v >> 4);
-        const uint32_t bytes = in ? (uint32_t)nd + 1u : 0u;
-        uint32_t incl = bytes;
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t x = (uint32_t)__shfl_up((int)incl, d);
-            if (lane >= d) incl += x;
-        }
+        const uint32_t bytes = in ? (uint32_t)nd + 1u : 0u, incl = wave_incl_sum(bytes, lane);
         if (in) {
             const uint32_t mine = at + incl - bytes;
             md_put_decimal(sink, mine, v >> 4, nd);
             sink.put(mine + nd, oc_letter(v & 15u));
         }
-        at += (uint32_t)__shfl((int)incl, 63);
+        at += __shfl(incl, 63);
     }
     return at;
 }
 
-// bytes of every read's OC text (0: the read is refused, passes or did not change), beside the other size kernels in front of
-// the placement, which takes the tag's bytes from it (bam_full_shape)
+// bytes of every read's OC text (0: the read gets no tags or did not change), beside the other size kernels in front of the
+// placement, which takes the tag's bytes from it (bam_full_shape)
 __global__ __launch_bounds__(64) void oc_size_kernel(BamEmitParams p)
 {
     const int64_t k = blockIdx.x;
     if (k >= p.n_reads) return;
     const int lane = threadIdx.x;
-    const uint8_t *f = p.raw + p.raw_off[k] + 4;
     uint32_t len = 0;
-    if (!(p.status[p.read_base + k] & 32) && !staged_passes(f, p.pass_mask)) {
+    if (!bam_no_tags(p, k)) {
         const uint8_t *cg, *sq;
         int nc, ci, cj;
-        staged_cigar(f, cg, nc, sq);
+        staged_cigar(p.raw + p.raw_off[k] + 4, cg, nc, sq);
         staged_clip_words(cg, nc, ci, cj);
         if (oc_changed(p, k, lane, cg, ci, cj)) len = oc_walk(cg, nc, lane, OcCount{});
     }
     if (lane == 0) p.oc_len[k] = (int32_t)len;
 }
 
-// 'O' 'C' 'Z' text NUL behind the record's NM, MD, cs and de (bam_full_shape), behind emit_bam_full_kernel (and emit_md_kernel,
-// emit_cs_kernel) on its stream; byte stores: the tag has any alignment
+// 'O' 'C' 'Z' text NUL at the record's oc_at, behind emit_bam_full_kernel (and emit_md_kernel, emit_cs_kernel) on its stream;
+// byte stores: the tag has any alignment
 __global__ __launch_bounds__(64) void emit_oc_kernel(BamEmitParams p)
 {
     const int64_t k = blockIdx.x;
-    if (k >= p.n_reads) return;
     const int lane = threadIdx.x;
-    const int64_t cap = p.oc_len[k];
-    if (cap == 0 || p.rec_len[k] <= 0) return;
-    const BamFullShape s = bam_full_shape(p, k);
-    if (s.pass) return;
-    uint8_t *o = p.recs + p.rec_off[k] + 36 + (int64_t)s.f[8] + (s.lng ? 8 : 4 * s.n_cig) + (s.l_seq + 1) / 2 + s.l_seq + s.aux + 3 + s.nmb + s.mdb +
-                 s.csb + s.deb;
+    BamFullShape s;
+    if (!bam_tag_shape(p, k, s) || !s.ocb) return;
+    uint8_t *o = p.recs + p.rec_off[k] + s.oc_at();
+    const int64_t cap = s.ocb - 4;
     if (lane < 3) o[lane] = (uint8_t)"OCZ"[lane];
     oc_walk(s.cg, s.nc, lane, OcStore{o + 3, cap});
     if (lane == 0) o[3 + cap] = 0;

@@ -16,6 +16,7 @@ Two implementations of the same logic live here:
     compare the native path with.
 write_bam() makes small BAM files for tests and benchmarks.
 """
+import dataclasses
 import os
 import struct
 import sys
@@ -561,10 +562,8 @@ def cigar_changed(words, final_text):
 
 def output_tags(cs, de, eqx=False, oc=False):
     """The word npore_bam_set_output_tags takes: NPORE_TAG_* of the options cs (None, "short", "long"), de and oc, and
-    NPORE_CIGAR_EQX of eqx"""
-    if cs not in (None, "short", "long"):
-        raise ValueError("cs must be None, 'short' or 'long'")
-    return {None: 0, "short": 1, "long": 3}[cs] | (4 if de else 0) | (32 if eqx else 0) | (256 if oc else 0)
+    NPORE_CIGAR_EQX of eqx (OutputSpec.tags)"""
+    return OutputSpec("bam", records="full", cs=cs, de=de, eqx=eqx, oc=oc).tags
 
 
 def full_record(raw, ref_codes, seq_codes, final, md=False, cs=None, de=False, eqx=False, oc=False):
@@ -1090,6 +1089,121 @@ class NativeFastaSeqs:
 # supplementary, placed but unmapped -- and the status bit such a record gets
 PASS_FLAGS = 0x100 | 0x800 | 0x4
 ST_PASSED = 128
+# the words an output setting is said in (include/npore_amd.h, NPORE_* of the same names): the flags of npore_bam_set_output and
+# of the npore_bam_format_bam_full entries (which know OUT_MD alone), and the word of npore_bam_set_output_tags
+OUT_EOF, OUT_PART, OUT_DEFLATE, OUT_MATCH, OUT_FULL, OUT_MD = 1, 2, 4, 8, 16, 32
+TAG_CS, TAG_CS_LONG, TAG_DE, CIGAR_EQX, TAG_OC = 1, 2, 4, 32, 256
+
+_COMPRESS = {"none": 0, "huffman": OUT_DEFLATE, "match": OUT_DEFLATE | OUT_MATCH}
+_CS = {None: 0, "short": TAG_CS, "long": TAG_CS | TAG_CS_LONG}
+
+
+def _needs_full(field):
+    return lambda s: bool(getattr(s, field)) and s.records != "full"
+
+
+# The rules of an output setting, in the order OutputSpec states them: what breaks the rule, the ValueError's text, and the line
+# realign prints (None: argparse's choices say it there).  realign names the first broken rule of _CLI_ORDER.
+_TAGS_NEED_FULL = "cs, de, eqx and oc need records 'full'"
+_RULES = {
+    "pass_mask": (_needs_full("pass_mask"), "pass_mask needs records 'full'", "--pass_through needs --out_format bam --records full."),
+    "compress values": (lambda s: s.compress not in _COMPRESS, "compress must be 'none', 'huffman' or 'match'", None),
+    "records values": (lambda s: s.records not in ("reference", "full"), "records must be 'reference' or 'full'", None),
+    "records": (lambda s: s.records == "full" and s.out_format != "bam", "records 'full' needs out_format 'bam'",
+                "--records full needs --out_format bam."),
+    "md": (_needs_full("md"), "md needs records 'full'", "--md needs --records full."),
+    "cs values": (lambda s: s.cs not in _CS, "cs must be None, 'short' or 'long'", None),
+    "cs": (_needs_full("cs"), _TAGS_NEED_FULL, "--cs needs --out_format bam --records full."),
+    "de": (_needs_full("de"), _TAGS_NEED_FULL, "--de needs --out_format bam --records full."),
+    "eqx": (_needs_full("eqx"), _TAGS_NEED_FULL, "--eqx needs --out_format bam --records full."),
+    "oc": (_needs_full("oc"), _TAGS_NEED_FULL, "--oc needs --out_format bam --records full."),
+    "compress": (lambda s: s.compress != "none" and s.out_format != "bam", "compress needs out_format 'bam'",
+                 "--bam_compress needs --out_format bam."),
+}
+_CLI_ORDER = ("records", "md", "cs", "de", "eqx", "oc", "pass_mask", "compress")
+
+
+class OutputSpecError(ValueError):
+    """An OutputSpec that breaks a rule; .cli is the line realign prints for it."""
+
+    def __init__(self, text, cli):
+        super().__init__(text)
+        self.cli = cli
+
+
+@dataclasses.dataclass(frozen=True)
+class OutputSpec:
+    """What a run (realign_file / realign_sequential / write_file) appends to its output path; NativeBam.set_output hands it to
+    the library.  out_format: "sam", or "bam" -- records in BGZF members behind what lies in the file (the header's members:
+    create_bam_header) and `bai` written when the records went out in coordinate order.  eof: the run ends the file (the EOF
+    member, OUT_EOF); False: it writes one rank's PART (OUT_PART) -- no EOF member, and `bai` is a sidecar whose offsets count
+    from PART_BASE (dist.gather_bam_parts shifts and merges them).  compress: "none", stored members, "huffman", every member
+    one dynamic-Huffman block of literals (OUT_DEFLATE), or "match", of literals and length / distance pairs where that is
+    smaller (OUT_MATCH beside it); "bam" only.  records: "reference", the reference's SAM line in binary, or "full", the input
+    record with only what the realignment changes replaced (OUT_FULL; "bam" only).  The rest needs records "full".  md: the MD
+    tag behind the recounted NM of every record (OUT_MD).  cs: "short" or "long", minimap2's cs tag behind that (TAG_CS,
+    TAG_CS_LONG), de: its de tag behind that (TAG_DE).  pass_mask: a subset of PASS_FLAGS -- the records with one of those flag
+    bits are written as they came (npore_bam_set_output_pass).  eqx: the final CIGAR of every record in =/X form (CIGAR_EQX, in
+    the tags' word).  oc: the input's CIGAR as OC:Z on every read whose alignment changed; the input's own OC is dropped, so an
+    unchanged read has none (TAG_OC, in the tags' word).
+    A spec that breaks one of _RULES is not made: OutputSpecError, a ValueError."""
+    out_format: str = "sam"
+    bai: object = None
+    eof: bool = True
+    compress: str = "none"
+    records: str = "reference"
+    md: bool = False
+    cs: object = None
+    de: bool = False
+    pass_mask: int = 0
+    eqx: bool = False
+    oc: bool = False
+
+    def __post_init__(self):
+        broken = [k for k, (is_broken, _, _) in _RULES.items() if is_broken(self)]
+        if broken:
+            text = _RULES[broken[0]][1]
+            raise OutputSpecError(text, next((_RULES[k][2] for k in _CLI_ORDER if k in broken), text))
+
+    @classmethod
+    def from_args(cls, args, **overrides):
+        """The spec realign's command line asks for (argparser's names; an option the namespace lacks is off); bai and eof, which
+        the command line does not say, come as overrides."""
+        said = dict(out_format=getattr(args, "out_format", "sam"), compress=getattr(args, "bam_compress", "none"),
+                    records=getattr(args, "records", "reference"), md=bool(getattr(args, "md", False)), cs=getattr(args, "cs", None),
+                    de=bool(getattr(args, "de", False)), pass_mask=PASS_FLAGS if getattr(args, "pass_through", False) else 0,
+                    eqx=bool(getattr(args, "eqx", False)), oc=bool(getattr(args, "oc", False)))
+        return cls(**{**said, **overrides})
+
+    @property
+    def format_word(self):
+        """NPORE_OUT_SAM / NPORE_OUT_BAM"""
+        return {"sam": 0, "bam": 1}[self.out_format]
+
+    @property
+    def flags(self):
+        """the flags of npore_bam_set_output"""
+        return ((0 if self.out_format != "bam" else OUT_EOF if self.eof else OUT_PART) | _COMPRESS[self.compress]
+                | (OUT_FULL if self.records == "full" else 0) | (OUT_MD if self.md else 0))
+
+    @property
+    def tags(self):
+        """the word of npore_bam_set_output_tags"""
+        return _CS[self.cs] | (TAG_DE if self.de else 0) | (CIGAR_EQX if self.eqx else 0) | (TAG_OC if self.oc else 0)
+
+
+def marshal_finals(idx, finals, status):
+    """The reads `idx` with their final CIGAR strings and status words as the format_* / write_file entries take them: (the
+    contiguous arrays, to be held while the pointers are in use; the arguments idx, n, text, offsets, lengths, status).  The
+    joined text ends in a NUL."""
+    idx = np.ascontiguousarray(idx, np.int64)
+    fb = [f.encode() for f in finals]
+    fo = np.zeros(len(idx) + 1, np.int64)
+    np.cumsum([len(f) for f in fb], out=fo[1:])
+    fl = np.ascontiguousarray(np.diff(fo))
+    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
+    st = np.ascontiguousarray(status, np.int32)
+    return (idx, buf, fo, fl, st), (idx.ctypes.data, len(idx), buf.ctypes.data, fo.ctypes.data, fl.ctypes.data, st.ctypes.data)
 
 
 class OnePassUnsupported(RuntimeError):
@@ -1338,98 +1452,41 @@ class NativeBam:
     def format_sam(self, idx, finals, status, threads=0):
         """SAM text of the selected reads given their final collapsed CIGAR strings."""
         import ctypes as C
-        idx = np.ascontiguousarray(idx, np.int64)
-        n = len(idx)
-        fb = [f.encode() for f in finals]
-        fo = np.zeros(n + 1, np.int64)
-        np.cumsum([len(f) for f in fb], out=fo[1:])
-        fl = np.diff(fo)
-        buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-        st = np.ascontiguousarray(status, np.int32)
+        _keep, reads = marshal_finals(idx, finals, status)
         sam, sam_len = C.c_void_p(), C.c_int64()
-        self._check(self._lib.npore_bam_format_sam(self.handle, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data,
-                                                   fl.ctypes.data, st.ctypes.data, threads, C.byref(sam), C.byref(sam_len)))
+        self._check(self._lib.npore_bam_format_sam(self.handle, *reads, threads, C.byref(sam), C.byref(sam_len)))
         return C.string_at(sam.value, sam_len.value).decode() if sam_len.value else ""
 
     def format_bam(self, idx, finals, status, threads=0):
         """BAM records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam)."""
         import ctypes as C
-        idx = np.ascontiguousarray(idx, np.int64)
-        n = len(idx)
-        fb = [f.encode() for f in finals]
-        fo = np.zeros(n + 1, np.int64)
-        np.cumsum([len(f) for f in fb], out=fo[1:])
-        fl = np.diff(fo)
-        buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-        st = np.ascontiguousarray(status, np.int32)
+        _keep, reads = marshal_finals(idx, finals, status)
         recs, recs_len = C.c_void_p(), C.c_int64()
-        self._check(self._lib.npore_bam_format_bam(self.handle, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data,
-                                                   fl.ctypes.data, st.ctypes.data, threads, C.byref(recs), C.byref(recs_len)))
+        self._check(self._lib.npore_bam_format_bam(self.handle, *reads, threads, C.byref(recs), C.byref(recs_len)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
     def format_bam_full(self, fasta, idx, finals, status, threads=0, md=False, cs=None, de=False, pass_mask=0, eqx=False, oc=False):
         """FULL records (bytes) of the selected reads given their final collapsed CIGAR strings (npore_bam_format_bam_full_pass,
-        the widest entry of the ladder, whose narrower ones forward to it with zeros; md: with the MD tag behind NM,
-        NPORE_OUT_MD; cs "short" / "long", de: with those tags behind MD, NPORE_TAG_*; pass_mask: the records with one of
-        those flag bits as they came; eqx: the final CIGARs in =/X form, NPORE_CIGAR_EQX; oc: OC:Z on the reads that changed,
-        NPORE_TAG_OC)."""
+        the widest entry of the ladder, whose narrower ones forward to it with zeros); md, cs, de, pass_mask, eqx, oc: as in
+        OutputSpec."""
         import ctypes as C
-        idx = np.ascontiguousarray(idx, np.int64)
-        n = len(idx)
-        fb = [f.encode() for f in finals]
-        fo = np.zeros(n + 1, np.int64)
-        np.cumsum([len(f) for f in fb], out=fo[1:])
-        fl = np.diff(fo)
-        buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-        st = np.ascontiguousarray(status, np.int32)
+        _keep, reads = marshal_finals(idx, finals, status)
         fmap = self.fasta_map(fasta)
         recs, recs_len = C.c_void_p(), C.c_int64()
-        args = (self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
-                st.ctypes.data, threads, C.byref(recs), C.byref(recs_len))
-        self._check(self._lib.npore_bam_format_bam_full_pass(*args, 32 if md else 0, output_tags(cs, de, eqx, oc), int(pass_mask)))
+        self._check(self._lib.npore_bam_format_bam_full_pass(self.handle, fasta.handle, fmap.ctypes.data, *reads, threads, C.byref(recs),
+                                                             C.byref(recs_len), OUT_MD if md else 0, output_tags(cs, de, eqx, oc),
+                                                             int(pass_mask)))
         return C.string_at(recs.value, recs_len.value) if recs_len.value else b""
 
-    def set_output(self, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False, cs=None, de=False,
-                   pass_mask=0, eqx=False, oc=False):
-        """What the NEXT realign_file / realign_sequential / write_file on this handle appends to its output path
-        (npore_bam_set_output; the setting holds for that one run): "sam", or "bam" -- records in stored BGZF members behind
-        what lies in the file (the header's members: create_bam_header) and `bai` written when the records went out in
-        coordinate order.  eof: the run ends the file (the EOF member); False: it writes one rank's PART -- no EOF member,
-        and `bai` is a sidecar whose offsets count from PART_BASE (dist.gather_bam_parts shifts and merges them).
-        compress: "none", stored members, "huffman", every member one dynamic-Huffman block of literals, or "match", of
-        literals and length / distance pairs where that is smaller
-        (NPORE_OUT_DEFLATE; "bam" only).  records: "reference", the reference's SAM line in binary, or "full", the input
-        record with only what the realignment changes replaced (NPORE_OUT_FULL; "bam" only).  md: the MD tag behind the
-        recounted NM of every FULL record (NPORE_OUT_MD; records "full" only).  cs: "short" or "long", minimap2's cs tag behind
-        that, de: its de tag behind that (npore_bam_set_output_tags, NPORE_TAG_*; records "full" only).  pass_mask: a subset of
-        PASS_FLAGS -- the records with one of those flag bits are written as they came (npore_bam_set_output_pass; records
-        "full" only).  eqx: the final CIGAR of every FULL record in =/X form (NPORE_CIGAR_EQX, in the tags' word; records
-        "full" only).  oc: the input's CIGAR as OC:Z on every read whose alignment changed; the input's own OC is dropped, so an
-        unchanged read has none (NPORE_TAG_OC, in the tags' word; records "full" only)."""
-        if pass_mask and records != "full":
-            raise ValueError("pass_mask needs records 'full'")
-        if compress not in ("none", "huffman", "match"):
-            raise ValueError("compress must be 'none', 'huffman' or 'match'")
-        if records not in ("reference", "full"):
-            raise ValueError("records must be 'reference' or 'full'")
-        if records == "full" and out_format != "bam":
-            raise ValueError("records 'full' needs out_format 'bam'")
-        if md and records != "full":
-            raise ValueError("md needs records 'full'")
-        tags = output_tags(cs, de, eqx, oc)
-        if tags and records != "full":
-            raise ValueError("cs, de, eqx and oc need records 'full'")
-        if compress != "none" and out_format != "bam":
-            raise ValueError("compress needs out_format 'bam'")
-        flags = 0 if out_format != "bam" else 1 if eof else 2       # NPORE_OUT_EOF / NPORE_OUT_PART
-        flags |= {"none": 0, "huffman": 4, "match": 12}[compress]  # NPORE_OUT_DEFLATE, NPORE_OUT_MATCH
-        flags |= 16 if records == "full" else 0                    # NPORE_OUT_FULL
-        flags |= 32 if md else 0                                   # NPORE_OUT_MD
-        self._check(self._lib.npore_bam_set_output(self.handle, {"sam": 0, "bam": 1}[out_format], os.fsencode(bai) if bai else None, flags))
-        if tags:
-            self._check(self._lib.npore_bam_set_output_tags(self.handle, tags))
-        if pass_mask:
-            self._check(self._lib.npore_bam_set_output_pass(self.handle, int(pass_mask)))
+    def set_output(self, out_format="sam", *more, **kw):
+        """What the NEXT realign_file / realign_sequential / write_file on this handle appends to its output path (the setting
+        holds for that one run): one OutputSpec, or the fields of one, in its order."""
+        spec = out_format if isinstance(out_format, OutputSpec) else OutputSpec(out_format, *more, **kw)
+        self._check(self._lib.npore_bam_set_output(self.handle, spec.format_word, os.fsencode(spec.bai) if spec.bai else None, spec.flags))
+        if spec.tags:
+            self._check(self._lib.npore_bam_set_output_tags(self.handle, spec.tags))
+        if spec.pass_mask:
+            self._check(self._lib.npore_bam_set_output_pass(self.handle, int(spec.pass_mask)))
 
     def output_info(self):
         """Of the last BAM-mode run: records written, bytes of the record stream, index (1 written, 0 none asked for, -1 the
@@ -1455,17 +1512,9 @@ class NativeBam:
     def write_file(self, idx, finals, status, out_path, batch_reads=4000, threads=0, bai=None, eof=True, compress="none"):
         """The host's part of a BAM-mode run alone (npore_bam_write_file, no GPU): the selected reads with their final
         CIGARs as records, made in batches of batch_reads and appended to out_path."""
-        idx = np.ascontiguousarray(idx, np.int64)
-        n = len(idx)
-        fb = [f.encode() for f in finals]
-        fo = np.zeros(n + 1, np.int64)
-        np.cumsum([len(f) for f in fb], out=fo[1:])
-        fl = np.ascontiguousarray(np.diff(fo))
-        buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-        st = np.ascontiguousarray(status, np.int32)
+        _keep, reads = marshal_finals(idx, finals, status)
         self.set_output("bam", bai, eof, compress)
-        self._check(self._lib.npore_bam_write_file(self.handle, idx.ctypes.data, n, int(batch_reads), buf.ctypes.data, fo.ctypes.data,
-                                                   fl.ctypes.data, st.ctypes.data, threads, os.fsencode(out_path)))
+        self._check(self._lib.npore_bam_write_file(self.handle, *reads[:2], int(batch_reads), *reads[2:], threads, os.fsencode(out_path)))
         self._after_bam_run("bam")
         return self.output_info()
 
@@ -1493,15 +1542,14 @@ class NativeBam:
         return tuple(int(x) for x in info)
 
     def realign_sequential(self, ctx, fasta, regions, out_path, batch_reads=4000, max_reads=0, r=30, max_b_rows=20000,
-                           indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, out_format="sam", bai=None, eof=True,
-                           compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0, eqx=False, oc=False):
+                           indel_start=5.0, indel_extend=1.0, threads=0, bad_cap=1000, output=None, **output_kw):
         """ONE PASS over the file: inflate, filter by `regions` [(contig, start, stop)] (at most one per contig, in header
         order), batch, realign, write -- npore_bam_realign_sequential.  Returns (reads selected, [(ordinal, status)] of
         the first bad reads, (refused, inconsistent)) -- the reads selected include the records that pass through (pass_mask),
         which are not bad reads; raises OnePassUnsupported when the regions or the file's
         order rule the one-pass run out (the caller truncates the output and takes the indexed path).
-        out_format / bai / eof / compress / records / md / cs / de / pass_mask / eqx / oc: set_output for this run ("bam": records
-        instead of text)."""
+        output, or its fields as keywords: the OutputSpec of this run ("bam": records instead of text)."""
+        output = output or OutputSpec(**output_kw)
         ids = {n: i for i, n in enumerate(self.references)}
         rid = np.array([ids.get(c, -2) for c, _, _ in regions], np.int32)
         beg = np.array([s for _, s, _ in regions], np.int64)
@@ -1511,7 +1559,7 @@ class NativeBam:
         counts = np.zeros(3, np.int64)
         bad_ord, bad_st = np.zeros(max(bad_cap, 1), np.int64), np.zeros(max(bad_cap, 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask, eqx, oc)
+        self.set_output(output)
         rc = self._lib.npore_bam_realign_sequential(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, len(regions), rid.ctypes.data,
                                                     beg.ctypes.data, end.ctypes.data, int(max_reads or 0), int(batch_reads), indel_start,
                                                     indel_extend, max_b_rows, r, threads, os.fsencode(out_path), counts.ctypes.data,
@@ -1528,7 +1576,7 @@ class NativeBam:
             if "the index is stale" in _lib.last_error():
                 raise StaleIndex(_lib.last_error())
         self._check(rc)
-        self._after_bam_run(out_format)
+        self._after_bam_run(output.out_format)
         nb = int(min(bad_cap, counts[1] + counts[2]))
         return int(counts[0]), list(zip(bad_ord[:nb].tolist(), bad_st[:nb].tolist())), (int(counts[1]), int(counts[2]))
 
@@ -1547,20 +1595,20 @@ class NativeBam:
         return (memoryview((C.c_char * sam_len.value).from_address(sam.value)) if sam_len.value else memoryview(b"")), st[:n]
 
     def realign_file(self, ctx, fasta, idx, out_sam, batch_reads=4000, r=30, max_b_rows=20000, indel_start=5.0,
-                     indel_extend=1.0, threads=0, out_format="sam", bai=None, eof=True, compress="none", records="reference", md=False,
-                     cs=None, de=False, pass_mask=0, eqx=False, oc=False):
+                     indel_extend=1.0, threads=0, output=None, **output_kw):
         """All selected reads, batch by batch, appended to out_sam by the library with packing, GPU work and
         formatting/writing of neighbouring batches overlapped.  Returns status[n] (ST_PASSED: written as it came).
-        out_format / bai / eof / compress / records / md / cs / de / pass_mask / eqx / oc: set_output for this run ("bam": records
-        instead of text); with pass_mask, idx comes from select(..., pass_mask=pass_mask)."""
+        output, or its fields as keywords: the OutputSpec of this run ("bam": records instead of text); with a pass_mask, idx
+        comes from select(..., pass_mask=pass_mask)."""
+        output = output or OutputSpec(**output_kw)
         idx = np.ascontiguousarray(idx, np.int64)
         st = np.zeros(max(len(idx), 1), np.int32)
         fmap = self.fasta_map(fasta)
-        self.set_output(out_format, bai, eof, compress, records, md, cs, de, pass_mask, eqx, oc)
+        self.set_output(output)
         self._check(self._lib.npore_bam_realign_file(ctx.handle, self.handle, fasta.handle, fmap.ctypes.data, idx.ctypes.data,
                                                      len(idx), int(batch_reads), indel_start, indel_extend, max_b_rows, r,
                                                      threads, os.fsencode(out_sam), st.ctypes.data))
-        self._after_bam_run(out_format)
+        self._after_bam_run(output.out_format)
         return st[:len(idx)]
 
     def timing(self):
@@ -1602,21 +1650,19 @@ class NativeBam:
             atexit.register(lambda f=skip: os.path.exists(f) and os.remove(f))
 
 
-def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0, out_format="sam", bai=None,
-                   eof=True, compress="none", records="reference", md=False, cs=None, de=False, pass_mask=0, eqx=False,
-                   oc=False):
+def realign_native(ctx, bam, fasta, idx, out_sam, r=30, max_b_rows=20000, batch_reads=0, threads=0, output=None, **output_kw):
     """realign_reads() through the library; returns the number of reads handed in.  batch_reads > 0: the whole
     index list in overlapped batches written by the library itself; 0: one batch, text written here.
     threads: host threads of the parallel host stages (0 = all cores; one process per GPU: dist.host_threads_per_rank).
-    out_format "bam" (with bai / eof: NativeBam.set_output) needs batch_reads > 0: the library writes the file."""
-    if out_format == "bam" and batch_reads <= 0:
+    output, or its fields as keywords: the OutputSpec of the run; "bam" needs batch_reads > 0: the library writes the file."""
+    output = output or OutputSpec(**output_kw)
+    if output.out_format == "bam" and batch_reads <= 0:
         raise ValueError("BAM output is written by the library's file pipeline: batch_reads must be positive")
-    if len(idx) == 0 and out_format != "bam":
+    if len(idx) == 0 and output.out_format != "bam":
         return 0
     if batch_reads > 0:
         text, status = None, bam.realign_file(ctx, fasta, idx, out_sam, batch_reads=batch_reads, r=r, max_b_rows=max_b_rows,
-                                              threads=threads, out_format=out_format, bai=bai, eof=eof, compress=compress,
-                                              records=records, md=md, cs=cs, de=de, pass_mask=pass_mask, eqx=eqx, oc=oc)
+                                              threads=threads, output=output)
     else:
         text, status = bam.realign_batch(ctx, fasta, idx, r=r, max_b_rows=max_b_rows, threads=threads)
     bad = np.nonzero(np.asarray(status) & ~ST_PASSED)[0]       # (a record that passed through is no bad read)

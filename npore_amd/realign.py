@@ -112,31 +112,19 @@ def main():
         print("\nERROR: --plot is not available in npore_amd (matplotlib reports are out of scope).")
         sys.exit(1)
     native = not cfg.args.python_io
-    records = getattr(cfg.args, "records", "reference")
-    if records == "full" and getattr(cfg.args, "out_format", "sam") != "bam":
-        print("\nERROR: --records full needs --out_format bam.")
+    # what the run writes, said once (bam.OutputSpec): a rank's part has its own index sidecar (part-relative offsets, merged by
+    # dist.gather_bam_parts), and the EOF member ends the whole file, not a part
+    rank, world, _ = dist_mod.world()
+    fmt = getattr(cfg.args, "out_format", "sam")
+    as_bam = fmt == "bam"
+    final_sam = f"{cfg.args.out_prefix}.{fmt}"
+    out_sam = final_sam if world == 1 else f"{cfg.args.out_prefix}.part{rank}.{fmt}"
+    try:
+        spec = bam_mod.OutputSpec.from_args(cfg.args, bai=out_sam + ".bai" if as_bam else None, eof=world == 1)
+    except bam_mod.OutputSpecError as e:
+        print(f"\nERROR: {e.cli}")
         sys.exit(1)
-    md = bool(getattr(cfg.args, "md", False))
-    if md and records != "full":
-        print("\nERROR: --md needs --records full.")
-        sys.exit(1)
-    cs, de = getattr(cfg.args, "cs", None), bool(getattr(cfg.args, "de", False))
-    if (cs or de) and records != "full":
-        print(f"\nERROR: {'--cs' if cs else '--de'} needs --out_format bam --records full.")
-        sys.exit(1)
-    eqx = bool(getattr(cfg.args, "eqx", False))
-    if eqx and records != "full":
-        print("\nERROR: --eqx needs --out_format bam --records full.")
-        sys.exit(1)
-    oc = bool(getattr(cfg.args, "oc", False))
-    if oc and records != "full":
-        print("\nERROR: --oc needs --out_format bam --records full.")
-        sys.exit(1)
-    pass_mask = bam_mod.PASS_FLAGS if getattr(cfg.args, "pass_through", False) else 0
-    if pass_mask and records != "full":
-        print("\nERROR: --pass_through needs --out_format bam --records full.")
-        sys.exit(1)
-    if records == "full" and not native:
+    if spec.records == "full" and not native:
         print("\nERROR: --records full is written by the library's file pipeline: not with --python_io.")
         sys.exit(1)
     # one process per GPU: the host stages of a rank use its share of the node's cores, and the BAM is inflated
@@ -159,14 +147,13 @@ def main():
     # their stretches: reads twice, reads missing, no error.)
     # The .bai also says which contigs have reads, and the default regions leave out the others: the one-pass walk checks
     # that claim against the records it meets, and a record on such a contig ends the run (bam.StaleIndex).
-    world_size = dist_mod.world()[1]
     one_pass = (native and cfg.args.batch_reads > 0 and not getattr(cfg.args, "bed", None)
                 and os.environ.get("NPORE_BAM_ONE_PASS", "1") != "0" and bam_mod.NativeBam.is_bgzf(cfg.args.bam)
-                and (world_size == 1 or (not cfg.args.max_reads and bam_mod.NativeBam.bai_path(cfg.args.bam) is not None)))
+                and (world == 1 or (not cfg.args.max_reads and bam_mod.NativeBam.bai_path(cfg.args.bam) is not None)))
     bam = bam_mod.NativeBam(cfg.args.bam, threads=threads, one_pass=one_pass) if native else bam_mod.BamFile(cfg.args.bam)
-    if one_pass and world_size > 1:
+    if one_pass and world > 1:
         try:
-            bam.set_share(dist_mod.world()[0], world_size)
+            bam.set_share(rank, world)
         except bam_mod.OnePassUnsupported as e:
             print(f"    ({e}: taking the indexed reader)")
             bam.close()
@@ -188,30 +175,17 @@ def main():
         cfg.args.sub_scores, cfg.args.np_scores, cfg.args.ins_scores, cfg.args.del_scores = \
             aln.load_default_tables(cfg.args.stats_dir)
 
-    rank, world, _ = dist_mod.world()
     if world > 1 and not native:
         print("\nERROR: --python_io runs on one GPU only.")
-        sys.exit(1)
-    fmt = getattr(cfg.args, "out_format", "sam")
-    as_bam = fmt == "bam"
-    compress = getattr(cfg.args, "bam_compress", "none")
-    if compress != "none" and not as_bam:
-        print("\nERROR: --bam_compress needs --out_format bam.")
         sys.exit(1)
     if as_bam and native and cfg.args.batch_reads <= 0:
         print("\nERROR: --out_format bam is written by the library's file pipeline: --batch_reads must be positive.")
         sys.exit(1)
     print(f"> creating output {fmt.upper()}")
-    final_sam = f"{cfg.args.out_prefix}.{fmt}"
-    out_sam = final_sam if world == 1 else f"{cfg.args.out_prefix}.part{rank}.{fmt}"
     if rank == 0:
         (bam_mod.create_bam_header if as_bam else bam_mod.create_header)(final_sam, bam)
     if world > 1:
         open(out_sam, "w").close()
-    # BAM: the index beside the file (a rank's part: a sidecar with part-relative offsets, merged by dist.gather_bam_parts);
-    # the EOF member ends the whole file, not a part
-    out_kw = dict(out_format=fmt, bai=out_sam + ".bai", eof=world == 1, compress=compress, records=records, md=md, cs=cs, de=de,
-                  pass_mask=pass_mask, eqx=eqx, oc=oc) if as_bam else {}
     gather = dist_mod.gather_bam_parts if as_bam else dist_mod.gather_parts
 
     print("> extracting read data from BAM")
@@ -226,7 +200,7 @@ def main():
         header_bytes = os.path.getsize(out_sam)
         try:
             n, bad, _ = bam.realign_sequential(ctx, ref_seqs, cfg.args.regions, out_sam, batch_reads=cfg.args.batch_reads,
-                                               max_reads=cfg.args.max_reads, threads=threads, **out_kw)
+                                               max_reads=cfg.args.max_reads, threads=threads, output=spec)
             for k, st in bad:
                 print(f"\nERROR: read #{k} of the selected reads: " +
                       ("CIGAR does not match sequence lengths; skipped." if st & 32 else f"inconsistent traceback (status {st})"))
@@ -252,7 +226,7 @@ def main():
         if world > 1:
             n = gather(final_sam, cfg.args.out_prefix, n)
     elif native:
-        idx = bam.select(cfg.args.regions, cfg.args.max_reads, pass_mask=pass_mask)
+        idx = bam.select(cfg.args.regions, cfg.args.max_reads, pass_mask=spec.pass_mask)
         # reads are independent: dealt by index, no data-path collective.  A resident BAM is dealt round-robin; a
         # STREAMED one in contiguous shares, so that a rank only ever inflates the blocks that hold its own reads
         # (BAM output: contiguous shares always -- the parts in rank order are then in file order, sorted and indexable)
@@ -262,7 +236,7 @@ def main():
         else:
             idx = idx[rank::world]
         print("> computing individual read realignments")
-        n += bam_mod.realign_native(ctx, bam, ref_seqs, idx, out_sam, batch_reads=cfg.args.batch_reads, threads=threads, **out_kw)
+        n += bam_mod.realign_native(ctx, bam, ref_seqs, idx, out_sam, batch_reads=cfg.args.batch_reads, threads=threads, output=spec)
         bam.close()
         ref_seqs.close()
         if world > 1:
@@ -271,7 +245,7 @@ def main():
         read_data = bam_mod.get_read_data(bam, ref_seqs)
         print("> computing individual read realignments")
         batch = []
-        writer = bam_mod.BamRecordWriter(out_sam, bai=out_sam + ".bai", compress=compress) if as_bam else None
+        writer = bam_mod.BamRecordWriter(out_sam, bai=spec.bai, compress=spec.compress) if as_bam else None
         py_kw = dict(bam_writer=writer, references=bam.references) if as_bam else {}
         for rd in read_data:
             batch.append(rd)

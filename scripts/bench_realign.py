@@ -135,13 +135,10 @@ def build_inputs(tmp, n, distinct, ref_len, seed, const_qual=False, procs=0, tag
 
 
 def start_output(a, out, nb):
-    """The header of the output file, and what the realign calls need to write behind it in a.out_format."""
-    if a.out_format == "bam":
-        bam.create_bam_header(out, nb)
-        return dict(out_format="bam", bai=None if out == "/dev/null" else out + ".bai", compress=a.bam_compress, records=a.records, md=a.md, cs=a.cs, de=a.de,
-                    pass_mask=bam.PASS_FLAGS if a.pass_through else 0, eqx=a.eqx, oc=a.oc)
-    bam.create_header(out, nb)
-    return {}
+    """The header of the output file, and the bam.OutputSpec of what the realign calls write behind it in a.out_format."""
+    as_bam = a.out_format == "bam"
+    (bam.create_bam_header if as_bam else bam.create_header)(out, nb)
+    return bam.OutputSpec.from_args(a, bai=out + ".bai" if as_bam and out != "/dev/null" else None)
 
 
 def regions_of(clen):
@@ -156,8 +153,7 @@ def run_file(ctx, bp, fa, clen, a, out, stream):
     t1 = time.perf_counter()
     idx = nb.select(regions_of(clen), pass_mask=bam.PASS_FLAGS if a.pass_through else 0)
     t2 = time.perf_counter()
-    out_kw = start_output(a, out, nb)
-    bam.realign_native(ctx, nb, nf, idx, out, r=a.r, batch_reads=a.batch, threads=a.threads, **out_kw)
+    bam.realign_native(ctx, nb, nf, idx, out, r=a.r, batch_reads=a.batch, threads=a.threads, output=start_output(a, out, nb))
     t3 = time.perf_counter()
     ft = nb.file_timing()
     wall = ft["wall_ms"] * 1e-3
@@ -209,10 +205,10 @@ def run_one_pass(ctx, bp, fa, clen, a, out):
     t0 = time.perf_counter()
     nb, nf = bam.NativeBam(bp, one_pass=True, threads=a.threads), bam.NativeFasta(fa)
     t1 = time.perf_counter()
-    out_kw = start_output(a, out, nb)
+    output = start_output(a, out, nb)
     ru0 = resource.getrusage(resource.RUSAGE_SELF)
     cg0 = cgroup_cpu_stat()
-    n, bad, _ = nb.realign_sequential(ctx, nf, regions_of(clen), out, batch_reads=a.batch, r=a.r, threads=a.threads, **out_kw)
+    n, bad, _ = nb.realign_sequential(ctx, nf, regions_of(clen), out, batch_reads=a.batch, r=a.r, threads=a.threads, output=output)
     t2 = time.perf_counter()
     ru1 = resource.getrusage(resource.RUSAGE_SELF)
     cg1 = cgroup_cpu_stat()
@@ -308,20 +304,10 @@ def main():
                     help="where the one-pass reader inflates the BAM's BGZF blocks (Context.set device_inflate)")
     ap.add_argument("--gen-into", default=None, help=argparse.SUPPRESS)       # (internal: make the inputs in this directory and exit)
     a = ap.parse_args()
-    if a.bam_compress != "none" and a.out_format != "bam":
-        ap.error("--bam_compress needs --out_format bam")
-    if a.records == "full" and a.out_format != "bam":
-        ap.error("--records full needs --out_format bam")
-    if a.md and a.records != "full":
-        ap.error("--md needs --records full")
-    if (a.cs or a.de) and a.records != "full":
-        ap.error("--cs / --de need --records full")
-    if a.eqx and a.records != "full":
-        ap.error("--eqx needs --records full")
-    if a.oc and a.records != "full":
-        ap.error("--oc needs --records full")
-    if a.pass_through and a.records != "full":
-        ap.error("--pass_through needs --records full")
+    try:
+        bam.OutputSpec.from_args(a)                  # (the options' rules: one statement, the library's own)
+    except bam.OutputSpecError as e:
+        ap.error(e.cli)
     if a.gen_into:
         print(json.dumps(build_inputs(a.gen_into, a.reads, a.distinct, a.ref_len, a.seed, a.const_qual, tags=a.tags, flagged=a.flagged)))
         return

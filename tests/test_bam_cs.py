@@ -21,7 +21,10 @@ import bam_cs_cases as cc
 import bam_full_cases as fc
 import bam_md_cases as mc
 import long_cigar_cases as lc
+from full_record_driver import host_full
 
+EOF, PART, DEFLATE, MATCH, FULL, MD = bam.OUT_EOF, bam.OUT_PART, bam.OUT_DEFLATE, bam.OUT_MATCH, bam.OUT_FULL, bam.OUT_MD      # npore_bam_set_output's flags
+CS, CS_LONG, DE = bam.TAG_CS, bam.TAG_CS_LONG, bam.TAG_DE                  # npore_bam_set_output_tags' word
 COMBOS = [(md, cs, de) for md in (False, True) for cs in cc.FORMS for de in (False, True)]
 
 
@@ -192,46 +195,35 @@ def test_random_reads(tmp_path):
 
 # ---- 5. the surface ---------------------------------------------------------------------------------------------------------------
 def test_surface(crafted, tmp_path):
-    import ctypes as C
     tmp, sets = crafted
     s = sets["cs"]
     nb, nf, idx = open_pair(s["bp"], s["fa"])
     lib = nb._lib
-    full = 16 | 1
+    full = FULL | EOF
     # tags only behind a BAM + FULL set_output; bad bits and LONG without CS refused; set_output clears them
-    assert lib.npore_bam_set_output_tags(nb.handle, 1) != 0                          # (a fresh handle writes SAM)
-    for fmt, flags in ((0, 0), (1, 1), (1, 4 | 1), (1, 2)):
+    assert lib.npore_bam_set_output_tags(nb.handle, CS) != 0                          # (a fresh handle writes SAM)
+    for fmt, flags in ((0, 0), (1, EOF), (1, DEFLATE | EOF), (1, PART)):
         assert lib.npore_bam_set_output(nb.handle, fmt, None, flags) == 0
-        for tags in (1, 3, 4, 5, 7):
+        for tags in (CS, CS | CS_LONG, DE, CS | DE, CS | CS_LONG | DE):
             assert lib.npore_bam_set_output_tags(nb.handle, tags) != 0, (fmt, flags, tags)
     assert lib.npore_bam_set_output(nb.handle, 1, None, full) == 0
-    for tags in (2, 6, 8, 9, 16, 64, -1):
+    for tags in (CS_LONG, CS_LONG | DE, 8, 8 | CS, 16, 64, -1):
         assert lib.npore_bam_set_output_tags(nb.handle, tags) != 0, tags
-    for tags in (0, 1, 3, 4, 5, 7):
+    for tags in (0, CS, CS | CS_LONG, DE, CS | DE, CS | CS_LONG | DE):
         assert lib.npore_bam_set_output_tags(nb.handle, tags) == 0, tags
     assert lib.npore_bam_set_output(nb.handle, 0, None, 0) == 0                      # ... back to SAM: the tags are gone with it
-    assert lib.npore_bam_set_output_tags(nb.handle, 1) != 0
+    assert lib.npore_bam_set_output_tags(nb.handle, CS) != 0
     # flag bit 64 is still refused by both old entry points; the ABI version is 2
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 64 | 16 | 1) != 0
-    fb = [f.encode() for f in s["finals"]]
-    fo = np.zeros(len(fb) + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    fmap = nb.fasta_map(nf)
-    recs, recs_len = C.c_void_p(), C.c_int64()
-    args = (nb.handle, nf.handle, fmap.ctypes.data, idx.ctypes.data, len(idx), buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
-            s["status"].ctypes.data, 0, C.byref(recs), C.byref(recs_len))
-    assert lib.npore_bam_format_bam_full_md(*args, 64) != 0
+    assert lib.npore_bam_set_output(nb.handle, 1, None, 64 | FULL | EOF) != 0
+    host = lambda entry, **words: host_full(nb, nf, idx, s["finals"], s["status"], entry=entry, **words)
+    assert host("_md", flags=64)[0] != 0
     assert lib.npore_abi_version() == 2
     # the new host entry point: tags = 0 is the _md entry point; bad flags and bad tags refused
-    for flags, md in ((0, False), (32, True)):
-        assert lib.npore_bam_format_bam_full_tags(*args, flags, 0) == 0
-        assert C.string_at(recs.value, recs_len.value) == s["got"][(md, None, False)]
-    assert lib.npore_bam_format_bam_full_tags(*args, 32, 5) == 0
-    assert C.string_at(recs.value, recs_len.value) == s["got"][(True, "short", True)]
-    for flags, tags in ((64, 1), (16, 1), (0, 2), (0, 8), (32, 6), (0, -1)):
-        assert lib.npore_bam_format_bam_full_tags(*args, flags, tags) != 0, (flags, tags)
+    for flags, md in ((0, False), (MD, True)):
+        assert host("_tags", flags=flags, tags=0) == (0, s["got"][(md, None, False)])
+    assert host("_tags", flags=MD, tags=CS | DE) == (0, s["got"][(True, "short", True)])
+    for flags, tags in ((64, CS), (FULL, CS), (0, CS_LONG), (0, 8), (MD, CS_LONG | DE), (0, -1)):
+        assert host("_tags", flags=flags, tags=tags)[0] != 0, (flags, tags)
     # Python: the options need records "full"; a bad form is refused
     for kw in (dict(out_format="bam", cs="short"), dict(out_format="bam", de=True), dict(out_format="sam", cs="long"),
                dict(out_format="bam", records="full", cs="both")):

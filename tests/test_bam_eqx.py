@@ -23,10 +23,13 @@ import bam_full_cases as fc
 import bam_md_cases as mc
 import bam_pass_cases as pc
 import long_cigar_cases as lc
+from full_record_driver import host_full
 
+EOF, PART, DEFLATE, MATCH, FULL, MD = bam.OUT_EOF, bam.OUT_PART, bam.OUT_DEFLATE, bam.OUT_MATCH, bam.OUT_FULL, bam.OUT_MD      # npore_bam_set_output's flags
+CS, CS_LONG, DE = bam.TAG_CS, bam.TAG_CS_LONG, bam.TAG_DE                  # npore_bam_set_output_tags' word
 ALL_TAGS = dict(md=True, cs="long", de=True)
 COMBOS = {"alone": dict(), "md": dict(md=True), "tags": ALL_TAGS}
-EQX = 32                                                         # NPORE_CIGAR_EQX
+EQX = bam.CIGAR_EQX
 
 
 def open_pair(bp, fa):
@@ -204,7 +207,6 @@ def test_cg_threshold(crafted, tmp_path):
 
 # ---- 5. the surface -------------------------------------------------------------------------------------------------------------------
 def test_surface(crafted):
-    import ctypes as C
     tmp, sets = crafted
     s = sets["eqx"]
     nb, nf, idx = open_pair(s["bp"], s["fa"])
@@ -219,44 +221,37 @@ def test_surface(crafted):
     assert declared == set(_lib.SIGNATURES)                      # no entry point was added for it
     # the bit alone, and beside every valid tag word, behind BAM + FULL; not without FULL, not in SAM format; no undefined bit
     assert lib.npore_bam_set_output_tags(nb.handle, EQX) != 0      # (a fresh handle writes SAM)
-    for fmt, flags in ((0, 0), (1, 1), (1, 4 | 1), (1, 2)):
+    for fmt, flags in ((0, 0), (1, EOF), (1, DEFLATE | EOF), (1, PART)):
         assert lib.npore_bam_set_output(nb.handle, fmt, None, flags) == 0
-        for tags in (EQX, EQX | 1, EQX | 7):
+        for tags in (EQX, EQX | CS, EQX | CS | CS_LONG | DE):
             assert lib.npore_bam_set_output_tags(nb.handle, tags) != 0, (fmt, flags, tags)
-    assert lib.npore_bam_set_output(nb.handle, 0, None, 16 | 1) != 0                  # (FULL in SAM format is refused outright)
-    for full in (16 | 1, 16 | 2, 16 | 32 | 1, 16 | 4 | 1):
+    assert lib.npore_bam_set_output(nb.handle, 0, None, FULL | EOF) != 0                  # (FULL in SAM format is refused outright)
+    for full in (FULL | EOF, FULL | PART, FULL | MD | EOF, FULL | DEFLATE | EOF):
         assert lib.npore_bam_set_output(nb.handle, 1, None, full) == 0
-        for tags in (EQX, EQX | 1, EQX | 3, EQX | 4, EQX | 7):
+        for tags in (EQX, EQX | CS, EQX | CS | CS_LONG, EQX | DE, EQX | CS | CS_LONG | DE):
             assert lib.npore_bam_set_output_tags(nb.handle, tags) == 0, tags
-        for tags in (EQX | 2, EQX | 6, 8, EQX | 8, 16, EQX | 16, 64, EQX | 64, 128, 1 << 30, -1):
+        for tags in (EQX | CS_LONG, EQX | CS_LONG | DE, 8, EQX | 8, 16, EQX | 16, 64, EQX | 64, 128, 1 << 30, -1):
             assert lib.npore_bam_set_output_tags(nb.handle, tags) != 0, tags
     # set_output sets it back: the packed sizes cannot show it, the host entry can -- a handle set to EQX and then set again
     # refuses the tags of a SAM run, and npore_bam_set_output_pass behind the bit keeps it (the pass setter rebuilds the spec)
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 16 | 1) == 0 and lib.npore_bam_set_output_tags(nb.handle, EQX) == 0
+    assert lib.npore_bam_set_output(nb.handle, 1, None, FULL | EOF) == 0 and lib.npore_bam_set_output_tags(nb.handle, EQX) == 0
     assert lib.npore_bam_set_output_pass(nb.handle, 0x904) == 0
     assert lib.npore_bam_set_output(nb.handle, 0, None, 0) == 0
     assert lib.npore_bam_set_output_tags(nb.handle, EQX) != 0 and lib.npore_bam_set_output_tags(nb.handle, 0) != 0
     # npore_bam_write_file keeps refusing FULL, with the bit as without
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 16 | 1) == 0 and lib.npore_bam_set_output_tags(nb.handle, EQX) == 0
+    assert lib.npore_bam_set_output(nb.handle, 1, None, FULL | EOF) == 0 and lib.npore_bam_set_output_tags(nb.handle, EQX) == 0
     out = tmp / "never.bam"
     assert lib.npore_bam_write_file(nb.handle, None, 0, 1, None, None, None, None, 0, str(out).encode()) != 0
     assert b"FULL records" in lib.npore_last_error() and not out.exists()
     # the host entries: the bit is accepted by _tags and _pass, refused with an undefined bit or with FULL / a writer's bit in `flags`
-    fb = [f.encode() for f in s["finals"]]
-    fo = np.zeros(len(fb) + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    recs, recs_len = C.c_void_p(), C.c_int64()
-    args = (nb.handle, nf.handle, nb.fasta_map(nf).ctypes.data, idx.ctypes.data, len(idx), buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
-            s["status"].ctypes.data, 0, C.byref(recs), C.byref(recs_len))
-    assert lib.npore_bam_format_bam_full_tags(*args, 0, EQX) == 0 and C.string_at(recs.value, recs_len.value) == s["got"]["alone"]
-    assert lib.npore_bam_format_bam_full_pass(*args, 32, EQX | 3 | 4, 0) == 0 and C.string_at(recs.value, recs_len.value) == s["got"]["tags"]
-    assert lib.npore_bam_format_bam_full_tags(*args, 0, 0) == 0 and C.string_at(recs.value, recs_len.value) == s["plain"]["alone"]
-    for flags, tags in ((0, 16), (0, EQX | 16), (0, EQX | 2), (0, EQX | 8), (16, EQX), (1, EQX), (64, EQX)):
-        assert lib.npore_bam_format_bam_full_tags(*args, flags, tags) != 0, (flags, tags)
+    host = lambda entry, **words: host_full(nb, nf, idx, s["finals"], s["status"], entry=entry, **words)
+    assert host("_tags", tags=EQX) == (0, s["got"]["alone"])
+    assert host("_pass", flags=MD, tags=EQX | CS | CS_LONG | DE) == (0, s["got"]["tags"])
+    assert host("_tags") == (0, s["plain"]["alone"])
+    for flags, tags in ((0, 16), (0, EQX | 16), (0, EQX | CS_LONG), (0, EQX | 8), (FULL, EQX), (EOF, EQX), (64, EQX)):
+        assert host("_tags", flags=flags, tags=tags)[0] != 0, (flags, tags)
     # Python: the option needs records "full"
-    assert bam.output_tags(None, False, eqx=True) == EQX and bam.output_tags("long", True, True) == EQX | 7 and bam.output_tags("short", False) == 1
+    assert bam.output_tags(None, False, eqx=True) == EQX and bam.output_tags("long", True, True) == EQX | CS | CS_LONG | DE and bam.output_tags("short", False) == CS
     for kw in (dict(out_format="bam", eqx=True), dict(out_format="sam", eqx=True), dict(out_format="bam", records="reference", eqx=True)):
         with pytest.raises(ValueError):
             nb.set_output(**kw)

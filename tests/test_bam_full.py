@@ -16,6 +16,7 @@ from test_bam_out import Hdr, decoded_lines, split_records
 import bam_full_cases as fc
 import long_cigar_cases as lc
 
+EOF, PART, DEFLATE, MATCH, FULL, MD = bam.OUT_EOF, bam.OUT_PART, bam.OUT_DEFLATE, bam.OUT_MATCH, bam.OUT_FULL, bam.OUT_MD      # npore_bam_set_output's flags
 
 def open_pair(bp, fa):
     nb, nf = bam.NativeBam(bp, stream=False), bam.NativeFasta(fa)
@@ -207,21 +208,16 @@ def test_errors_and_surface(full_inputs, tmp_path):
     tmp, bp, fa, references, refs, records, cigars, finals, status = full_inputs
     nb, nf, idx = open_pair(bp, fa)
     lib = nb._lib
-    assert lib.npore_bam_set_output(nb.handle, 0, None, 16) != 0           # NPORE_OUT_FULL needs NPORE_OUT_BAM
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 32) != 0
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 16) != 0           # ... and one of EOF / PART: 16 alone stays refused
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 16 | 4) != 0
-    for flags in (17, 18, 16 | 4 | 1, 16 | 12 | 2):                        # ... and combines with EOF, PART, DEFLATE, MATCH
+    assert lib.npore_bam_set_output(nb.handle, 0, None, FULL) != 0         # NPORE_OUT_FULL needs NPORE_OUT_BAM
+    assert lib.npore_bam_set_output(nb.handle, 1, None, MD) != 0
+    assert lib.npore_bam_set_output(nb.handle, 1, None, FULL) != 0         # ... and one of EOF / PART: FULL alone stays refused
+    assert lib.npore_bam_set_output(nb.handle, 1, None, FULL | DEFLATE) != 0
+    for flags in (FULL | EOF, FULL | PART, FULL | DEFLATE | EOF, FULL | DEFLATE | MATCH | PART):      # ... and combines with EOF, PART, DEFLATE, MATCH
         assert lib.npore_bam_set_output(nb.handle, 1, None, flags) == 0
     out = str(tmp_path / "w.bam")
-    fb = [f.encode() for f in finals]
-    fo = np.zeros(len(fb) + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 17) == 0
-    rc = lib.npore_bam_write_file(nb.handle, idx.ctypes.data, len(idx), 5, buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
-                                  status.ctypes.data, 0, os.fsencode(out))
+    _keep, reads = bam.marshal_finals(idx, finals, status)
+    assert lib.npore_bam_set_output(nb.handle, 1, None, FULL | EOF) == 0
+    rc = lib.npore_bam_write_file(nb.handle, *reads[:2], 5, *reads[2:], 0, os.fsencode(out))
     assert rc == -5 and "NM" in _lib.last_error() and not os.path.exists(out)      # NPORE_E_UNSUPPORTED
     # (the setting held for that one run: the reference form again)
     bam.create_bam_header(out, Hdr(nb.references, nb.lengths))

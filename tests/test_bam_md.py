@@ -19,7 +19,9 @@ from test_bam_out import split_records
 import bam_full_cases as fc
 import bam_md_cases as mc
 import long_cigar_cases as lc
+from full_record_driver import host_full
 
+EOF, PART, DEFLATE, MATCH, FULL, MD = bam.OUT_EOF, bam.OUT_PART, bam.OUT_DEFLATE, bam.OUT_MATCH, bam.OUT_FULL, bam.OUT_MD      # npore_bam_set_output's flags
 
 def open_pair(bp, fa):
     nb, nf = bam.NativeBam(bp, stream=False), bam.NativeFasta(fa)
@@ -100,20 +102,9 @@ def test_crafted_reads(crafted):
     assert plain == mc.want_stream(raws, records, refs, finals, status, md=False)
     # flags = 0: the new entry point is the old one
     nb, nf, idx = open_pair(bp, fa)
-    fb = [f.encode() for f in finals]
-    fo = np.zeros(len(fb) + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    fmap = nb.fasta_map(nf)
-    import ctypes as C
-    recs, recs_len = C.c_void_p(), C.c_int64()
-    args = (nb.handle, nf.handle, fmap.ctypes.data, idx.ctypes.data, len(idx), buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
-            status.ctypes.data, 0, C.byref(recs), C.byref(recs_len))
-    assert nb._lib.npore_bam_format_bam_full_md(*args, 0) == 0
-    assert C.string_at(recs.value, recs_len.value) == plain
-    for flags in (1, 16, 33, 64):                                # NPORE_OUT_MD is the only bit it knows
-        assert nb._lib.npore_bam_format_bam_full_md(*args, flags) != 0, flags
+    assert host_full(nb, nf, idx, finals, status, entry="_md", flags=0) == (0, plain)
+    for flags in (EOF, FULL, MD | EOF, 64):      # NPORE_OUT_MD is the only bit it knows
+        assert host_full(nb, nf, idx, finals, status, entry="_md", flags=flags)[0] != 0, flags
     nb.close(); nf.close()
     # the texts pinned by hand, the tag's place and the order of the tags
     out = split_records(got)
@@ -164,20 +155,15 @@ def test_surface(crafted, tmp_path):
     tmp, bp, fa, refs, records, finals, pinned, status, got, plain = crafted
     nb, nf, idx = open_pair(bp, fa)
     lib = nb._lib
-    for fmt, flags in ((1, 32), (1, 32 | 1), (1, 32 | 2), (1, 32 | 4 | 1), (1, 32 | 16), (0, 32 | 16 | 1), (0, 32), (1, 64 | 16 | 1)):
+    for fmt, flags in ((1, MD), (1, MD | EOF), (1, MD | PART), (1, MD | DEFLATE | EOF), (1, MD | FULL), (0, MD | FULL | EOF), (0, MD), (1, 64 | FULL | EOF)):
         assert lib.npore_bam_set_output(nb.handle, fmt, None, flags) != 0, (fmt, flags)      # MD only with FULL (which needs EOF or PART, and BAM)
-    for flags in (32 | 16 | 1, 32 | 16 | 2, 32 | 16 | 4 | 1, 32 | 16 | 12 | 2):
+    for flags in (MD | FULL | EOF, MD | FULL | PART, MD | FULL | DEFLATE | EOF, MD | FULL | DEFLATE | MATCH | PART):
         assert lib.npore_bam_set_output(nb.handle, 1, None, flags) == 0, flags
     # npore_bam_write_file keeps refusing FULL, with MD beside it too
     out = str(tmp_path / "w.bam")
-    fb = [f.encode() for f in finals]
-    fo = np.zeros(len(fb) + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 32 | 16 | 1) == 0
-    rc = lib.npore_bam_write_file(nb.handle, idx.ctypes.data, len(idx), 5, buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
-                                  status.ctypes.data, 0, os.fsencode(out))
+    _keep, reads = bam.marshal_finals(idx, finals, status)
+    assert lib.npore_bam_set_output(nb.handle, 1, None, MD | FULL | EOF) == 0
+    rc = lib.npore_bam_write_file(nb.handle, *reads[:2], 5, *reads[2:], 0, os.fsencode(out))
     assert rc == -5 and not os.path.exists(out)
     with pytest.raises(ValueError):
         nb.set_output("bam", md=True)

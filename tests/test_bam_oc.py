@@ -19,11 +19,13 @@ from conftest import GOLDEN, REPO
 from test_bam_out import split_records
 import bam_full_cases as fc
 import bam_oc_cases as oc
+from full_record_driver import host_full
 
+EOF, PART, DEFLATE, MATCH, FULL, MD = bam.OUT_EOF, bam.OUT_PART, bam.OUT_DEFLATE, bam.OUT_MATCH, bam.OUT_FULL, bam.OUT_MD      # npore_bam_set_output's flags
+CS, CS_LONG, DE = bam.TAG_CS, bam.TAG_CS_LONG, bam.TAG_DE                  # npore_bam_set_output_tags' word
 ALL_TAGS = dict(md=True, cs="long", de=True, eqx=True)
 COMBOS = {"alone": dict(), "tags": ALL_TAGS}
-OC = 256                                                         # NPORE_TAG_OC
-EQX = 32
+OC, EQX = bam.TAG_OC, bam.CIGAR_EQX
 
 
 def open_all(bp, fa):
@@ -52,7 +54,7 @@ def test_statement_on_the_table():
     big = [(0, (1 << 28) - 1)] * 20                              # a merged length beyond 32 bits is no word's length
     assert bam.cigar_changed(big, f"{((1 << 28) - 1) * 20 % (1 << 32)}M")
     # the option's word and the filter
-    assert bam.output_tags(None, False) == 0 and bam.output_tags(None, False, oc=True) == OC and bam.output_tags("long", True, True, True) == OC | EQX | 7
+    assert bam.output_tags(None, False) == 0 and bam.output_tags(None, False, oc=True) == OC and bam.output_tags("long", True, True, True) == OC | EQX | CS | CS_LONG | DE
     aux = b"XAZa\0" + b"OCZ5M\0" + b"NMC\x01" + b"XBC\x02"
     assert bam.filter_aux(aux) == b"XAZa\0" + b"OCZ5M\0" + b"XBC\x02" and bam.filter_aux(aux, oc=True) == b"XAZa\0" + b"XBC\x02"
     assert b"OC" not in bam.STALE_TAGS
@@ -200,7 +202,6 @@ def test_with_a_pass_mask(crafted, mask):
 
 # ---- 4. the surface -----------------------------------------------------------------------------------------------------------------
 def test_surface(crafted):
-    import ctypes as C
     tmp, sets = crafted
     s = sets["oc"]
     nb, nf, idx = open_all(s["bp"], s["fa"])
@@ -214,41 +215,34 @@ def test_surface(crafted):
     assert declared == set(_lib.SIGNATURES)                      # no entry point was added for it
     # the ladder of test_bam_eqx.py::test_surface, for the bit alone and beside every valid word
     assert lib.npore_bam_set_output_tags(nb.handle, OC) != 0       # (a fresh handle writes SAM)
-    for fmt, flags in ((0, 0), (1, 1), (1, 4 | 1), (1, 2)):
+    for fmt, flags in ((0, 0), (1, EOF), (1, DEFLATE | EOF), (1, PART)):
         assert lib.npore_bam_set_output(nb.handle, fmt, None, flags) == 0
-        for tags in (OC, OC | 1, OC | 7, OC | EQX):
+        for tags in (OC, OC | CS, OC | CS | CS_LONG | DE, OC | EQX):
             assert lib.npore_bam_set_output_tags(nb.handle, tags) != 0, (fmt, flags, tags)
-    assert lib.npore_bam_set_output(nb.handle, 0, None, 16 | 1) != 0                  # (FULL in SAM format is refused outright)
-    for full in (16 | 1, 16 | 2, 16 | 32 | 1, 16 | 4 | 1):
+    assert lib.npore_bam_set_output(nb.handle, 0, None, FULL | EOF) != 0                  # (FULL in SAM format is refused outright)
+    for full in (FULL | EOF, FULL | PART, FULL | MD | EOF, FULL | DEFLATE | EOF):
         assert lib.npore_bam_set_output(nb.handle, 1, None, full) == 0
-        for tags in (OC, OC | 1, OC | 3, OC | 4, OC | 7, OC | EQX, OC | EQX | 1, OC | EQX | 3, OC | EQX | 4, OC | EQX | 7):
+        for tags in [OC | eqx | word for eqx in (0, EQX) for word in (0, CS, CS | CS_LONG, DE, CS | CS_LONG | DE)]:
             assert lib.npore_bam_set_output_tags(nb.handle, tags) == 0, tags
-        for tags in (OC | 2, OC | 6, 8, OC | 8, 16, OC | 16, 64, OC | 64, 128, OC | 128, 512, OC | 512, 1 << 30, -1):
+        for tags in (OC | CS_LONG, OC | CS_LONG | DE, 8, OC | 8, 16, OC | 16, 64, OC | 64, 128, OC | 128, 512, OC | 512, 1 << 30, -1):
             assert lib.npore_bam_set_output_tags(nb.handle, tags) != 0, tags
     # set_output sets it back; the pass setter behind the bit keeps it
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 16 | 1) == 0 and lib.npore_bam_set_output_tags(nb.handle, OC) == 0
+    assert lib.npore_bam_set_output(nb.handle, 1, None, FULL | EOF) == 0 and lib.npore_bam_set_output_tags(nb.handle, OC) == 0
     assert lib.npore_bam_set_output_pass(nb.handle, 0x904) == 0
     assert lib.npore_bam_set_output(nb.handle, 0, None, 0) == 0
     assert lib.npore_bam_set_output_tags(nb.handle, OC) != 0 and lib.npore_bam_set_output_tags(nb.handle, 0) != 0
     # npore_bam_write_file keeps refusing FULL, with the bit as without
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 16 | 1) == 0 and lib.npore_bam_set_output_tags(nb.handle, OC) == 0
+    assert lib.npore_bam_set_output(nb.handle, 1, None, FULL | EOF) == 0 and lib.npore_bam_set_output_tags(nb.handle, OC) == 0
     out = tmp / "never.bam"
     assert lib.npore_bam_write_file(nb.handle, None, 0, 1, None, None, None, None, 0, str(out).encode()) != 0
     assert b"FULL records" in lib.npore_last_error() and not out.exists()
     # the host entries: accepted by _tags and _pass, refused beside an undefined bit or with FULL / a writer's bit in `flags`
-    fb = [f.encode() for f in s["finals"]]
-    fo = np.zeros(len(fb) + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    recs, recs_len = C.c_void_p(), C.c_int64()
-    args = (nb.handle, nf.handle, nb.fasta_map(nf).ctypes.data, idx.ctypes.data, len(idx), buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
-            s["status"].ctypes.data, 0, C.byref(recs), C.byref(recs_len))
-    assert lib.npore_bam_format_bam_full_tags(*args, 0, OC) == 0 and C.string_at(recs.value, recs_len.value) == s["got"]["alone"]
-    assert lib.npore_bam_format_bam_full_pass(*args, 32, OC | EQX | 3 | 4, 0) == 0 and C.string_at(recs.value, recs_len.value) == s["got"]["tags"]
-    assert lib.npore_bam_format_bam_full_tags(*args, 0, 0) == 0 and C.string_at(recs.value, recs_len.value) == s["plain"]["alone"]
-    for flags, tags in ((0, OC | 2), (0, OC | 8), (0, OC | 128), (0, OC | 16), (16, OC), (1, OC), (64, OC)):
-        assert lib.npore_bam_format_bam_full_tags(*args, flags, tags) != 0, (flags, tags)
+    host = lambda entry, **words: host_full(nb, nf, idx, s["finals"], s["status"], entry=entry, **words)
+    assert host("_tags", tags=OC) == (0, s["got"]["alone"])
+    assert host("_pass", flags=MD, tags=OC | EQX | CS | CS_LONG | DE) == (0, s["got"]["tags"])
+    assert host("_tags") == (0, s["plain"]["alone"])
+    for flags, tags in ((0, OC | CS_LONG), (0, OC | 8), (0, OC | 128), (0, OC | 16), (FULL, OC), (EOF, OC), (64, OC)):
+        assert host("_tags", flags=flags, tags=tags)[0] != 0, (flags, tags)
     # Python: the option needs records "full"
     for kw in (dict(out_format="bam", oc=True), dict(out_format="sam", oc=True), dict(out_format="bam", records="reference", oc=True)):
         with pytest.raises(ValueError):

@@ -12,8 +12,12 @@ from test_bam_out import split_records
 import bam_full_cases as fc
 import bam_pass_cases as pc
 import long_cigar_cases as lc
+from full_record_driver import host_full
 
 MASKS = (0x904, 0x100, 0x800, 0x4, 0x900, 0x104)
+EOF, PART, DEFLATE, MATCH, FULL, MD = bam.OUT_EOF, bam.OUT_PART, bam.OUT_DEFLATE, bam.OUT_MATCH, bam.OUT_FULL, bam.OUT_MD      # npore_bam_set_output's flags
+ALL_FLAGS = EOF | PART | DEFLATE | MATCH | FULL | MD
+CS, CS_LONG, DE = bam.TAG_CS, bam.TAG_CS_LONG, bam.TAG_DE                  # npore_bam_set_output_tags' word
 
 
 @pytest.fixture(scope="module")
@@ -54,11 +58,11 @@ def test_setter(case):
     nb, lib = case["nb"], case["nb"]._lib
     assert lib.npore_abi_version() == 2
     assert lib.npore_bam_set_output_pass(nb.handle, 0x904) != 0                      # (a fresh handle writes SAM)
-    for fmt, flags in ((0, 0), (1, 1), (1, 2), (1, 1 | 4), (1, 1 | 4 | 8)):            # no FULL set_output in front
+    for fmt, flags in ((0, 0), (1, EOF), (1, PART), (1, EOF | DEFLATE), (1, EOF | DEFLATE | MATCH)):      # no FULL set_output in front
         assert lib.npore_bam_set_output(nb.handle, fmt, None, flags) == 0
         assert lib.npore_bam_set_output_pass(nb.handle, 0x100) != 0, (fmt, flags)
         assert lib.npore_bam_set_output_pass(nb.handle, 0) != 0, (fmt, flags)
-    for flags in (1 | 16, 2 | 16, 1 | 16 | 32, 1 | 4 | 16):
+    for flags in (EOF | FULL, PART | FULL, EOF | FULL | MD, EOF | DEFLATE | FULL):
         assert lib.npore_bam_set_output(nb.handle, 1, None, flags) == 0
         for bit in range(31):
             mask = 1 << bit
@@ -70,9 +74,9 @@ def test_setter(case):
     # every set_output clears the mask: a run behind it passes nothing (the host's view of the mask: npore_bam_pack_sizes)
     idx = np.arange(40, dtype=np.int64)
     sizes = lambda: [np.diff(a) for a in nb.pack(case["nf"], idx)[1::2]]
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 1 | 16) == 0 and lib.npore_bam_set_output_pass(nb.handle, 0x904) == 0
+    assert lib.npore_bam_set_output(nb.handle, 1, None, EOF | FULL) == 0 and lib.npore_bam_set_output_pass(nb.handle, 0x904) == 0
     with_mask = sizes()
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 1 | 16) == 0
+    assert lib.npore_bam_set_output(nb.handle, 1, None, EOF | FULL) == 0
     without = sizes()
     for k in range(40):
         if pc.passes(case["flags"][k], 0x904):
@@ -81,7 +85,7 @@ def test_setter(case):
             assert [int(a[k]) for a in with_mask] == [int(a[k]) for a in without], k
     assert any(int(a[4]) > 0 for a in without)                                      # (without the mask a supplementary is a read like any other)
     # what the other setters refuse stays refused
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 64 | 16 | 1) != 0
+    assert lib.npore_bam_set_output(nb.handle, 1, None, 64 | FULL | EOF) != 0
     assert lib.npore_bam_set_output(nb.handle, 0, None, 0) == 0
     # the ABI lists the four new symbols with the arguments of their parents plus the mask
     for name in ("npore_bam_set_output_pass", "npore_bam_select_pass", "npore_bam_format_bam_full_pass", "npore_debug_format_bam_full_pass_device"):
@@ -135,16 +139,7 @@ def test_record_bytes(case, md, cs, de):
     # mask 0: the bytes of npore_bam_format_bam_full_tags, for the reads npore_bam_select keeps
     reads = np.array(pc.py_select(raws, [(0, 0, 1 << 28), (1, 0, 1 << 28)], 0, 0), np.int64)
     plain = nb.format_bam_full(nf, reads, [finals[k] for k in reads], status[reads], **kw)
-    args = (nb.handle, nf.handle, nb.fasta_map(nf).ctypes.data)
-    import ctypes as C
-    fb = [finals[k].encode() for k in reads]
-    fo = np.zeros(len(reads) + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl, buf, st = np.ascontiguousarray(np.diff(fo)), np.frombuffer(b"".join(fb) + b"\0", np.uint8), np.ascontiguousarray(status[reads])
-    recs, n = C.c_void_p(), C.c_int64()
-    assert nb._lib.npore_bam_format_bam_full_pass(*args, reads.ctypes.data, len(reads), buf.ctypes.data, fo.ctypes.data, fl.ctypes.data, st.ctypes.data, 0,
-                                                  C.byref(recs), C.byref(n), 32 if md else 0, bam.output_tags(cs, de), 0) == 0
-    assert C.string_at(recs.value, n.value) == plain
+    assert host_full(nb, nf, reads, [finals[k] for k in reads], status[reads], flags=MD if md else 0, tags=bam.output_tags(cs, de)) == (0, plain)
     assert len(split_records(plain)) == len(reads) - 1            # the refused read is absent
     for mask in MASKS:
         idx = np.array(pc.py_select(raws, [(0, 0, 1 << 28), (1, 0, 1 << 28)], 0, mask), np.int64)
@@ -166,8 +161,7 @@ def test_record_bytes(case, md, cs, de):
             assert g[14:16] == (k).to_bytes(2, "little")         # (the input's bin, whatever it says)
     assert sum(pc.passes(f, 0x904) for f in flags) == 10
     # a bit outside 0x904 is refused
-    assert nb._lib.npore_bam_format_bam_full_pass(*args, reads.ctypes.data, len(reads), buf.ctypes.data, fo.ctypes.data, fl.ctypes.data, st.ctypes.data, 0,
-                                                  C.byref(recs), C.byref(n), 0, 0, 0x904 | 2) != 0
+    assert host_full(nb, nf, reads, [finals[k] for k in reads], status[reads], mask=0x904 | 2)[0] != 0
 
 
 def test_cli_refuses_pass_through_without_full_records(case, tmp_path):
@@ -193,16 +187,11 @@ def test_cli_refuses_pass_through_without_full_records(case, tmp_path):
 def ladder_args(case, idx):
     """the arguments the four host entries share, and where they leave the records"""
     import ctypes as C
-    nb, finals, status = case["nb"], case["finals"], case["status"]
-    fb = [finals[k].encode() for k in idx]
-    fo = np.zeros(len(idx) + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl, buf, st = np.ascontiguousarray(np.diff(fo)), np.frombuffer(b"".join(fb) + b"\0", np.uint8), np.ascontiguousarray(status[idx])
-    recs, n = C.c_void_p(), C.c_int64()
-    keep = (fo, fl, buf, st, idx)
-    args = (nb.handle, case["nf"].handle, nb.fasta_map(case["nf"]).ctypes.data, idx.ctypes.data, len(idx), buf.ctypes.data, fo.ctypes.data, fl.ctypes.data,
-            st.ctypes.data, 0, C.byref(recs), C.byref(n))
-    return args, (lambda: C.string_at(recs.value, n.value)), keep
+    nb = case["nb"]
+    keep, reads = bam.marshal_finals(idx, [case["finals"][k] for k in idx], case["status"][idx])
+    fmap, recs, n = nb.fasta_map(case["nf"]), C.c_void_p(), C.c_int64()
+    args = (nb.handle, case["nf"].handle, fmap.ctypes.data, *reads, 0, C.byref(recs), C.byref(n))
+    return args, (lambda: C.string_at(recs.value, n.value)), (keep, fmap)
 
 
 @pytest.mark.parametrize("mask", [0, 0x4, 0x100, 0x800, 0x904])
@@ -215,7 +204,7 @@ def test_the_ladder_forwards_agree(case, mask):
     combos = [(md, cs, de) for md in (False, True) for cs in (None, "short", "long") for de in (False, True)]
     assert len(combos) == 12
     for md, cs, de in combos:
-        flags, tags = 32 if md else 0, bam.output_tags(cs, de)
+        flags, tags = MD if md else 0, bam.output_tags(cs, de)
         want = nb.format_bam_full(case["nf"], idx, [case["finals"][k] for k in idx], case["status"][idx], md=md, cs=cs, de=de, pass_mask=mask)
         assert len(split_records(want)) == len(idx) - 1            # (the refused read is absent)
         calls = [lambda: lib.npore_bam_format_bam_full_pass(*args, flags, tags, mask)]
@@ -231,13 +220,14 @@ def test_the_ladder_forwards_agree(case, mask):
 
 def spec_ok(fmt, flags, tags, pas):
     """csrc/hostio.hpp rec_spec_of restated: defined bits only, CS_LONG beside CS, md / tags / pass on FULL records, FULL records in BAM"""
-    full = bool(flags & 16)
-    return not (flags & ~63 or tags & ~7 or pas & ~0x904 or (tags & 2 and not tags & 1) or (not full and (flags & 32 or tags or pas)) or (full and fmt != 1))
+    full = bool(flags & FULL)
+    return not (flags & ~ALL_FLAGS or tags & ~(CS | CS_LONG | DE) or pas & ~0x904 or (tags & CS_LONG and not tags & CS)
+                or (not full and (flags & MD or tags or pas)) or (full and fmt != 1))
 
 
 def set_output_ok(fmt, flags):
     """... and npore_bam_set_output's own: a known format, DEFLATE in BAM, MATCH beside DEFLATE, a FULL run ends a file or writes a part"""
-    return fmt in (0, 1) and not (flags & 4 and fmt != 1) and not (flags & 8 and not flags & 4) and not (flags & 16 and not flags & 3) and spec_ok(fmt, flags, 0, 0)
+    return fmt in (0, 1) and not (flags & DEFLATE and fmt != 1) and not (flags & MATCH and not flags & DEFLATE) and not (flags & FULL and not flags & (EOF | PART)) and spec_ok(fmt, flags, 0, 0)
 
 
 def test_the_rule_table(case):
@@ -245,8 +235,8 @@ def test_the_rule_table(case):
     _tags in that order on a fresh handle: accepted and refused as the rules above say.  And the host entry accepts (flags, tags,
     pass) exactly when the setters accept them for a FULL BAM run."""
     lib = case["nb"]._lib
-    flag_sets = list(range(64)) + [64, 64 | 16 | 1]
-    tag_sets, pass_sets = list(range(8)) + [8], [a | b | c for a in (0, 4) for b in (0, 0x100) for c in (0, 0x800)] + [0x400]
+    flag_sets = list(range(ALL_FLAGS + 1)) + [64, 64 | FULL | EOF]
+    tag_sets, pass_sets = list(range((CS | CS_LONG | DE) + 1)) + [8], [a | b | c for a in (0, 4) for b in (0, 0x100) for c in (0, 0x800)] + [0x400]
     for fmt in (0, 1, 2):
         for flags in flag_sets:
             e1 = set_output_ok(fmt, flags)
@@ -262,7 +252,7 @@ def test_the_rule_table(case):
             for tags in tag_sets:
                 for pas in pass_sets:
                     nb = bam.NativeBam(case["bp"], stream=False)
-                    held = bool(flags & 16)
+                    held = bool(flags & FULL)
                     e2 = held and spec_ok(fmt, flags, 0, pas)
                     e3 = held and spec_ok(fmt, flags, tags, pas if e2 else 0)
                     got = (lib.npore_bam_set_output(nb.handle, fmt, None, flags) == 0, lib.npore_bam_set_output_pass(nb.handle, pas) == 0,
@@ -271,13 +261,13 @@ def test_the_rule_table(case):
                     assert got == (True, e2, e3), (fmt, flags, tags, pas)
     nb = case["nb"]
     args, _got, _keep = ladder_args(case, np.zeros(0, np.int64))
-    for flags in (0, 32, 64, 32 | 64, 16, 1):                    # (the entry's flags know NPORE_OUT_MD alone: FULL and the writer's bits are not its to take)
+    for flags in (0, MD, 64, MD | 64, FULL, EOF):                  # (the entry's flags know NPORE_OUT_MD alone: FULL and the writer's bits are not its to take)
         for tags in tag_sets:
             for pas in pass_sets:
-                assert lib.npore_bam_set_output(nb.handle, 1, None, 16 | 1) == 0
-                setters = flags in (0, 32) and lib.npore_bam_set_output(nb.handle, 1, None, 16 | 1 | flags) == 0 and \
+                assert lib.npore_bam_set_output(nb.handle, 1, None, FULL | EOF) == 0
+                setters = flags in (0, MD) and lib.npore_bam_set_output(nb.handle, 1, None, FULL | EOF | flags) == 0 and \
                     lib.npore_bam_set_output_pass(nb.handle, pas) == 0 and lib.npore_bam_set_output_tags(nb.handle, tags) == 0
-                assert setters == (flags in (0, 32) and spec_ok(1, 16 | 1 | flags, tags, pas))
+                assert setters == (flags in (0, MD) and spec_ok(1, FULL | EOF | flags, tags, pas))
                 assert (lib.npore_bam_format_bam_full_pass(*args, flags, tags, pas) == 0) == setters, (flags, tags, pas)
     assert lib.npore_bam_set_output(nb.handle, 0, None, 0) == 0
 
@@ -289,8 +279,8 @@ def test_the_setting_is_spent_once(case, tmp_path):
     idx = np.arange(40, dtype=np.int64)
     sizes = lambda: [np.diff(a).tolist() for a in nb.pack(case["nf"], idx)[1::2]]
     without = sizes()
-    assert lib.npore_bam_set_output(nb.handle, 1, None, 16 | 32 | 1) == 0
-    assert lib.npore_bam_set_output_pass(nb.handle, 0x904) == 0 and lib.npore_bam_set_output_tags(nb.handle, 1 | 2 | 4) == 0
+    assert lib.npore_bam_set_output(nb.handle, 1, None, FULL | MD | EOF) == 0
+    assert lib.npore_bam_set_output_pass(nb.handle, 0x904) == 0 and lib.npore_bam_set_output_tags(nb.handle, CS | CS_LONG | DE) == 0
     assert sizes() != without
     out = tmp_path / "never.bam"
     assert lib.npore_bam_write_file(nb.handle, None, 0, 1, None, None, None, None, 0, str(out).encode()) != 0
@@ -298,7 +288,7 @@ def test_the_setting_is_spent_once(case, tmp_path):
     assert sizes() == without
     for mask in (0, 0x4, 0x904):
         assert lib.npore_bam_set_output_pass(nb.handle, mask) != 0, mask
-    for tags in (0, 1, 4, 7):
+    for tags in (0, CS, DE, CS | CS_LONG | DE):
         assert lib.npore_bam_set_output_tags(nb.handle, tags) != 0, tags
     assert lib.npore_bam_write_file(nb.handle, None, 0, 1, None, None, None, None, 0, str(out).encode()) != 0      # (SAM again: no BAM run)
     assert b"npore_bam_set_output first" in lib.npore_last_error() and not out.exists()

@@ -5,7 +5,6 @@ BAM through the one-pass file pipeline with stored and with coded members, and o
 buffer has to grow.  The rule is stated in csrc/cs_rec.hpp.
 """
 import argparse
-import ctypes as C
 import os
 import struct
 
@@ -19,6 +18,7 @@ from test_gpu_bam_full import record_stream
 import bam_cs_cases as cc
 import bam_full_cases as fc
 import bam_md_cases as mc
+from full_record_driver import device_full
 
 pytestmark = pytest.mark.gpu
 DATA = os.path.join(GOLDEN, "data")
@@ -31,26 +31,6 @@ def ctx(tables):
     c = aln.Context(sub, nps, max_n=6, max_l=100, device=0)
     yield c
     c.close()
-
-
-def device_full_tags(ctx, nb, nf, idx, finals, status, want_len, md, cs, de):
-    """the record bytes of npore_debug_format_bam_full_tags_device"""
-    idx = np.ascontiguousarray(idx, np.int64)
-    n = len(idx)
-    fb = [f.encode() for f in finals]
-    fo = np.zeros(n + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    st = np.ascontiguousarray(status, np.int32)
-    fmap = nb.fasta_map(nf)
-    cap = want_len + 4096
-    recs, nm, md_len, got = np.zeros(cap, np.uint8), np.full(n, -1, np.int32), np.full(n, -1, np.int32), C.c_int64()
-    nb._check(nb._lib.npore_debug_format_bam_full_tags_device(ctx.handle, nb.handle, nf.handle, fmap.ctypes.data, idx.ctypes.data, n,
-                                                              buf.ctypes.data, fo.ctypes.data, fl.ctypes.data, st.ctypes.data, recs.ctypes.data,
-                                                              cap, C.byref(got), nm.ctypes.data, 32 if md else 0, md_len.ctypes.data,
-                                                              bam.output_tags(cs, de)))
-    return recs[:got.value].tobytes()
 
 
 # ---- 1. the crafted and the random reads through the debug entry, every combination --------------------------------------------
@@ -72,7 +52,7 @@ def test_device_equals_host(ctx, tmp_path, which):
     seen = set()
     for md, cs, de in COMBOS:
         want = nb.format_bam_full(nf, idx, finals, status, md=md, cs=cs, de=de)
-        got = device_full_tags(ctx, nb, nf, idx, finals, status, len(want), md, cs, de)
+        got = device_full(ctx, nb, nf, idx, finals, status, cap=len(want) + 4096, entry="_tags", md=md, cs=cs, de=de)[0]
         if got != want:                                          # the first record that differs, by name
             for (_, a), (_, b) in zip(split_records(got), split_records(want)):
                 assert a == b, (md, cs, de, b[36:36 + b[12] - 1], a[-80:], b[-80:])
@@ -82,7 +62,7 @@ def test_device_equals_host(ctx, tmp_path, which):
     if which == "cs":                                            # the same reads picked in another order, in one call
         pick = np.random.default_rng(2).integers(0, len(records), 200)
         want = nb.format_bam_full(nf, idx[pick], [finals[k] for k in pick], status[pick], md=True, cs="long", de=True)
-        assert device_full_tags(ctx, nb, nf, idx[pick], [finals[k] for k in pick], status[pick], len(want), True, "long", True) == want
+        assert device_full(ctx, nb, nf, idx[pick], [finals[k] for k in pick], status[pick], cap=len(want) + 4096, entry="_tags", md=True, cs="long", de=True)[0] == want
     nb.close(); nf.close()
 
 

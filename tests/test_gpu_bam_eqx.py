@@ -6,7 +6,6 @@ calls between which the engine's eqx_len buffer has to grow and in a batch cut i
 through the tool.  The rule is stated in csrc/eqx_rec.hpp.  Every child process runs under its own time limit.
 """
 import argparse
-import ctypes as C
 import os
 
 import numpy as np
@@ -22,6 +21,7 @@ import bam_full_cases as fc
 import bam_md_cases as mc
 import bam_pass_cases as pc
 import long_cigar_cases as lc
+from full_record_driver import device_full
 
 pytestmark = pytest.mark.gpu
 DATA = os.path.join(GOLDEN, "data")
@@ -34,26 +34,6 @@ def ctx(tables):
     c = aln.Context(sub, nps, max_n=6, max_l=100, device=0)
     yield c
     c.close()
-
-
-def device_eqx(ctx, nb, nf, idx, finals, status, want_len, mask=0, md=False, cs=None, de=False, eqx=True):
-    """the record bytes of npore_debug_format_bam_full_pass_device with NPORE_CIGAR_EQX in its tags"""
-    idx = np.ascontiguousarray(idx, np.int64)
-    n = len(idx)
-    fb = [f.encode() for f in finals]
-    fo = np.zeros(n + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    st = np.ascontiguousarray(status, np.int32)
-    fmap = nb.fasta_map(nf)
-    cap = want_len + 4096
-    recs, nm, md_len, got = np.zeros(cap, np.uint8), np.full(n, -1, np.int32), np.full(n, -1, np.int32), C.c_int64()
-    nb._check(nb._lib.npore_debug_format_bam_full_pass_device(ctx.handle, nb.handle, nf.handle, fmap.ctypes.data, idx.ctypes.data, n,
-                                                              buf.ctypes.data, fo.ctypes.data, fl.ctypes.data, st.ctypes.data, recs.ctypes.data,
-                                                              cap, C.byref(got), nm.ctypes.data, 32 if md else 0, md_len.ctypes.data,
-                                                              bam.output_tags(cs, de, eqx), mask))
-    return recs[:got.value].tobytes()
 
 
 def first_difference(got, want):
@@ -76,7 +56,7 @@ def test_device_equals_host(ctx, tmp_path, which):
     status = np.array([r["_status"] for r in records], np.int32)
     for kw in (dict(), ALL_TAGS):
         want = nb.format_bam_full(nf, idx, finals, status, eqx=True, **kw)
-        got = device_eqx(ctx, nb, nf, idx, finals, status, len(want), **kw)
+        got = device_full(ctx, nb, nf, idx, finals, status, cap=len(want) + 4096, eqx=True, **kw)[0]
         assert got == want, (kw, first_difference(got, want))
         # eqx_len, as the record says it: n_cigar_op (the CG tag's count) is the clip words plus the split words
         kept = [(r, f) for r, f in zip(records, finals) if not r["_status"]]
@@ -89,11 +69,11 @@ def test_device_equals_host(ctx, tmp_path, which):
             assert n_cig == (2 if n_words > 0xFFFF else n_words), r["name"]
         # without the bit the same entry writes the bytes it wrote before
         plain = nb.format_bam_full(nf, idx, finals, status, **kw)
-        assert device_eqx(ctx, nb, nf, idx, finals, status, len(plain), eqx=False, **kw) == plain != want
+        assert device_full(ctx, nb, nf, idx, finals, status, cap=len(plain) + 4096, eqx=False, **kw)[0] == plain != want
     if which == "eqx":                                           # the same reads picked in another order, in one call
         pick = np.random.default_rng(2).integers(0, len(records), 150)
         want = nb.format_bam_full(nf, idx[pick], [finals[k] for k in pick], status[pick], eqx=True, **ALL_TAGS)
-        assert device_eqx(ctx, nb, nf, idx[pick], [finals[k] for k in pick], status[pick], len(want), **ALL_TAGS) == want
+        assert device_full(ctx, nb, nf, idx[pick], [finals[k] for k in pick], status[pick], cap=len(want) + 4096, eqx=True, **ALL_TAGS)[0] == want
     nb.close(); nf.close()
 
 
@@ -109,7 +89,7 @@ def test_device_with_a_pass_mask(ctx, tmp_path, mask):
     idx = np.array(pc.py_select(raws, [(0, 0, 1 << 28), (1, 0, 1 << 28)], 0, mask), np.int64)
     for kw in (dict(), ALL_TAGS):
         want = nb.format_bam_full(nf, idx, [finals[k] for k in idx], status[idx], pass_mask=mask, eqx=True, **kw)
-        got = device_eqx(ctx, nb, nf, idx, [finals[k] for k in idx], status[idx], len(want), mask=mask, **kw)
+        got = device_full(ctx, nb, nf, idx, [finals[k] for k in idx], status[idx], cap=len(want) + 4096, mask=mask, eqx=True, **kw)[0]
         assert got == want, (kw, first_difference(got, want))
     passed = [r for k, (_, r) in zip([k for k in idx if k != 12], split_records(got)) if pc.passes(records[k]["flag"], mask)]
     assert passed and all(r in raws for r in passed)             # as they came
@@ -125,7 +105,7 @@ def test_cg_threshold_on_the_device(ctx, tmp_path):
     st = np.zeros(2, np.int32)
     for kw in (dict(), ALL_TAGS):
         want = nb.format_bam_full(nf, idx, finals, st, eqx=True, **kw)
-        got = device_eqx(ctx, nb, nf, idx, finals, st, len(want), **kw)
+        got = device_full(ctx, nb, nf, idx, finals, st, cap=len(want) + 4096, eqx=True, **kw)[0]
         assert got == want, (kw, first_difference(got, want))
         (_, plain), (_, long) = split_records(got)
         assert ec.record_cigar_text(plain) == ("1S" + "1=1X" * 32766 + "1=" + "2S", 65535) and b"CGBI" not in plain

@@ -5,7 +5,6 @@ the CLI and with two ranks.  The format is stated in csrc/bam_reader.hpp ("FULL 
 Every child process runs under its own time limit.
 """
 import argparse
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -18,6 +17,7 @@ from conftest import GOLDEN, REPO
 from test_bam_out import Hdr, check_index, decoded_lines, header_len, members, split_records
 import bam_full_cases as fc
 import long_cigar_cases as lc
+from full_record_driver import device_full
 
 pytestmark = pytest.mark.gpu
 DATA = os.path.join(GOLDEN, "data")
@@ -36,25 +36,6 @@ def record_stream(path):
     return data[header_len(data):]
 
 
-def device_full(ctx, nb, nf, idx, finals, status):
-    """(record bytes, nm[n]) of npore_debug_format_bam_full_device"""
-    idx = np.ascontiguousarray(idx, np.int64)
-    n = len(idx)
-    fb = [f.encode() for f in finals]
-    fo = np.zeros(n + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    st = np.ascontiguousarray(status, np.int32)
-    fmap = nb.fasta_map(nf)
-    cap = len(nb.format_bam_full(nf, idx, finals, st)) + 4096
-    recs, nm, got = np.zeros(cap, np.uint8), np.full(n, -1, np.int32), C.c_int64()
-    nb._check(nb._lib.npore_debug_format_bam_full_device(ctx.handle, nb.handle, nf.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data,
-                                                         fo.ctypes.data, fl.ctypes.data, st.ctypes.data, recs.ctypes.data, cap, C.byref(got),
-                                                         nm.ctypes.data))
-    return recs[:got.value].tobytes(), nm
-
-
 # ---- 1. NM and records on crafted CIGARs ------------------------------------------------------------------------------------
 def test_crafted_cigars_device_equals_host(ctx, tmp_path):
     references, refs, records, finals = fc.crafted_reads()
@@ -64,7 +45,7 @@ def test_crafted_cigars_device_equals_host(ctx, tmp_path):
     assert len(idx) == len(records)
     status = np.array([r["_status"] for r in records], np.int32)
     want = nb.format_bam_full(nf, idx, finals, status)
-    got, nm = device_full(ctx, nb, nf, idx, finals, status)
+    got, nm, _ = device_full(ctx, nb, nf, idx, finals, status, entry="")
     want_nm = []
     for r, fin in zip(records, finals):
         rc, sc, _ = lc.expected_pack(r, r["cigar"], refs["ctg"])
@@ -76,7 +57,7 @@ def test_crafted_cigars_device_equals_host(ctx, tmp_path):
     # 300 reads in one call (the same records again and again, in another order)
     rng = np.random.default_rng(1)
     pick = rng.integers(0, len(records), 300)
-    got, nm = device_full(ctx, nb, nf, idx[pick], [finals[k] for k in pick], status[pick])
+    got, nm, _ = device_full(ctx, nb, nf, idx[pick], [finals[k] for k in pick], status[pick], entry="")
     assert nm.tolist() == [want_nm[k] for k in pick]
     assert got == nb.format_bam_full(nf, idx[pick], [finals[k] for k in pick], status[pick])
     nb.close(); nf.close()

@@ -11,12 +11,12 @@ import pytest
 
 from npore_amd import aln, bam
 from test_bam_out import split_records
-from test_gpu_bam_oc import device_oc as device_records          # THE helper around the debug entry (every option is a keyword)
 import bam_eqx_cases as ec
 import bam_full_cases as fc
 import bam_fuzz_cases as fz
 import bam_oc_cases as oc
 import long_cigar_cases as lc
+from full_record_driver import device_full
 
 pytestmark = pytest.mark.gpu
 
@@ -48,8 +48,8 @@ class Seed:
 
     def device(self, ctx, kw, mask=0, pick=None, room=None):
         pick = np.arange(len(self.idx)) if pick is None else np.asarray(pick)
-        return device_records(ctx, self.nb, self.nf, self.idx[pick], [self.finals[k] for k in pick], self.status[pick],
-                              len(self.host(kw, mask)) if room is None else room, mask=mask, **kw)
+        return device_full(ctx, self.nb, self.nf, self.idx[pick], [self.finals[k] for k in pick], self.status[pick],
+                           cap=(len(self.host(kw, mask)) if room is None else room) + 4096, mask=mask, **kw)[0]
 
     def describe(self, got, want, kw, mask=0):
         return dict(options=fz.set_name(kw), mask=hex(mask), **fz.describe_difference(got, want, self.records, self.finals, self.status))
@@ -161,7 +161,7 @@ def test_split_long_read_with_oc_and_cg(ctx, tmp_path):
     rc, sc, _ = lc.expected_pack(records[0], records[0]["cigar"], refs["ctg"])
     raw, = fc.input_records(bp)
     want = bam.full_record(raw, rc, sc, finals[0], **fz.FULL_SET)
-    got = device_records(ctx, nb, nf, idx, finals, st, len(want), **fz.FULL_SET)
+    got = device_full(ctx, nb, nf, idx, finals, st, cap=len(want) + 4096, **fz.FULL_SET)[0]
     assert got == want, fz.describe_difference(got, want, records, finals, st)
     assert nb.format_bam_full(nf, idx, finals, st, **fz.FULL_SET) == want
     text, n_cigar_op = ec.record_cigar_text(got)
@@ -170,7 +170,7 @@ def test_split_long_read_with_oc_and_cg(ctx, tmp_path):
     assert texts == ["1S30000M0I35534M2S"] and tags == [b"RG", b"NM", b"MD", b"cs", b"de", b"OC", b"CG"]
     # without the split the same read is a plain record of four words, its OC in the same place
     kw = dict(fz.FULL_SET, eqx=False)
-    plain = device_records(ctx, nb, nf, idx, finals, st, len(want), **kw)
+    plain = device_full(ctx, nb, nf, idx, finals, st, cap=len(want) + 4096, **kw)[0]
     assert plain == bam.full_record(raw, rc, sc, finals[0], **kw) and ec.record_cigar_text(plain) == ("1S65533M1I2S", 4)
     assert oc.oc_of_record(plain) == (texts, tags[:-1])
     nb.close(); nf.close()

@@ -5,7 +5,6 @@ coded members, on a read of more than 65 535 operations, through the CLI and wit
 csrc/md_rec.hpp.  Every child process runs under its own time limit.
 """
 import argparse
-import ctypes as C
 import os
 import sys
 
@@ -15,10 +14,11 @@ import pytest
 from npore_amd import aln, bam, cfg
 from conftest import GOLDEN, REPO
 from test_bam_out import Hdr, check_index, decoded_lines, members, split_records
-from test_gpu_bam_full import device_full, realign_cli, record_stream
+from test_gpu_bam_full import realign_cli, record_stream
 import bam_full_cases as fc
 import bam_md_cases as mc
 import long_cigar_cases as lc
+from full_record_driver import device_full
 
 pytestmark = pytest.mark.gpu
 DATA = os.path.join(GOLDEN, "data")
@@ -30,25 +30,6 @@ def ctx(tables):
     c = aln.Context(sub, nps, max_n=6, max_l=100, device=0)
     yield c
     c.close()
-
-
-def device_full_md(ctx, nb, nf, idx, finals, status, flags=32):
-    """(record bytes, nm[n], md_len[n]) of npore_debug_format_bam_full_md_device"""
-    idx = np.ascontiguousarray(idx, np.int64)
-    n = len(idx)
-    fb = [f.encode() for f in finals]
-    fo = np.zeros(n + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    st = np.ascontiguousarray(status, np.int32)
-    fmap = nb.fasta_map(nf)
-    cap = len(nb.format_bam_full(nf, idx, finals, st, md=bool(flags & 32))) + 4096
-    recs, nm, md_len, got = np.zeros(cap, np.uint8), np.full(n, -1, np.int32), np.full(n, -1, np.int32), C.c_int64()
-    nb._check(nb._lib.npore_debug_format_bam_full_md_device(ctx.handle, nb.handle, nf.handle, fmap.ctypes.data, idx.ctypes.data, n,
-                                                            buf.ctypes.data, fo.ctypes.data, fl.ctypes.data, st.ctypes.data, recs.ctypes.data,
-                                                            cap, C.byref(got), nm.ctypes.data, flags, md_len.ctypes.data))
-    return recs[:got.value].tobytes(), nm, md_len
 
 
 # ---- 1. crafted reads through the debug entry -----------------------------------------------------------------------------------
@@ -66,7 +47,7 @@ def test_crafted_reads_device_equals_host(ctx, tmp_path):
         text = bam.md_of(rc, sc, fin)
         assert pinned.get(r["name"], text) == text, r["name"]
         want_len.append(0 if r["_status"] else len(text))
-    got, nm, md_len = device_full_md(ctx, nb, nf, idx, finals, status)
+    got, nm, md_len = device_full(ctx, nb, nf, idx, finals, status, entry="_md", md=True)
     print("md_len", md_len.tolist())
     assert md_len.tolist() == want_len
     assert got == want
@@ -74,12 +55,12 @@ def test_crafted_reads_device_equals_host(ctx, tmp_path):
     # 300 picks of the same reads in another order, in one call
     rng = np.random.default_rng(1)
     pick = rng.integers(0, len(records), 300)
-    got, nm, md_len = device_full_md(ctx, nb, nf, idx[pick], [finals[k] for k in pick], status[pick])
+    got, nm, md_len = device_full(ctx, nb, nf, idx[pick], [finals[k] for k in pick], status[pick], entry="_md", md=True)
     assert md_len.tolist() == [want_len[k] for k in pick]
     assert got == nb.format_bam_full(nf, idx[pick], [finals[k] for k in pick], status[pick], md=True)
     # flags = 0: the bytes of the entry point without the tag, md_len untouched
-    got0, nm0, md0 = device_full_md(ctx, nb, nf, idx, finals, status, flags=0)
-    old, nm_old = device_full(ctx, nb, nf, idx, finals, status)
+    got0, nm0, md0 = device_full(ctx, nb, nf, idx, finals, status, entry="_md", md=False)
+    old, nm_old, _ = device_full(ctx, nb, nf, idx, finals, status, entry="")
     assert got0 == old == nb.format_bam_full(nf, idx, finals, status) and nm0.tolist() == nm_old.tolist()
     assert (md0 == -1).all()
     nb.close(); nf.close()

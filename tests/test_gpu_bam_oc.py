@@ -6,7 +6,6 @@ with a pass mask, the reads handed in one by one and four at a time, on inputs o
 on a file whose reads the reference changes and does not change.  The rule is stated in csrc/oc_rec.hpp.
 """
 import argparse
-import ctypes as C
 import os
 
 import numpy as np
@@ -19,6 +18,7 @@ from test_gpu_bam_full import realign_cli, record_stream
 import bam_full_cases as fc
 import bam_oc_cases as oc
 import long_cigar_cases as lc
+from full_record_driver import device_full
 
 pytestmark = pytest.mark.gpu
 DATA = os.path.join(GOLDEN, "data")
@@ -31,26 +31,6 @@ def ctx(tables):
     c = aln.Context(sub, nps, max_n=6, max_l=100, device=0)
     yield c
     c.close()
-
-
-def device_oc(ctx, nb, nf, idx, finals, status, want_len, mask=0, md=False, cs=None, de=False, eqx=False, oc=True):
-    """the record bytes of npore_debug_format_bam_full_pass_device with NPORE_TAG_OC in its tags"""
-    idx = np.ascontiguousarray(idx, np.int64)
-    n = len(idx)
-    fb = [f.encode() for f in finals]
-    fo = np.zeros(n + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    st = np.ascontiguousarray(status, np.int32)
-    fmap = nb.fasta_map(nf)
-    cap = want_len + 4096
-    recs, nm, md_len, got = np.zeros(cap, np.uint8), np.full(n, -1, np.int32), np.full(n, -1, np.int32), C.c_int64()
-    nb._check(nb._lib.npore_debug_format_bam_full_pass_device(ctx.handle, nb.handle, nf.handle, fmap.ctypes.data, idx.ctypes.data, n,
-                                                              buf.ctypes.data, fo.ctypes.data, fl.ctypes.data, st.ctypes.data, recs.ctypes.data,
-                                                              cap, C.byref(got), nm.ctypes.data, 32 if md else 0, md_len.ctypes.data,
-                                                              bam.output_tags(cs, de, eqx, oc), mask))
-    return recs[:got.value].tobytes()
 
 
 def first_difference(got, want):
@@ -78,14 +58,14 @@ def test_device_equals_host(ctx, tmp_path, which):
     for kw in (dict(), ALL_TAGS, dict(mask=0x904), dict(mask=0x100, **ALL_TAGS)):
         host_kw = {("pass_mask" if k == "mask" else k): v for k, v in kw.items()}
         want = nb.format_bam_full(nf, idx, finals, status, oc=True, **host_kw)
-        got = device_oc(ctx, nb, nf, idx, finals, status, len(want), **kw)
+        got = device_full(ctx, nb, nf, idx, finals, status, cap=len(want) + 4096, oc=True, **kw)[0]
         assert got == want, (kw, first_difference(got, want))
         # the bit off: the same entry writes the bytes it wrote before
         plain = nb.format_bam_full(nf, idx, finals, status, **host_kw)
-        assert device_oc(ctx, nb, nf, idx, finals, status, len(plain), oc=False, **kw) == plain != want
+        assert device_full(ctx, nb, nf, idx, finals, status, cap=len(plain) + 4096, oc=False, **kw)[0] == plain != want
     # which records carry the tag is the statement's answer (the host twin's bytes say no more than that they agree)
     kept = [r for r in records if not r["_status"]]
-    for (_, rec), r in zip(split_records(device_oc(ctx, nb, nf, idx, finals, status, len(want))), kept):
+    for (_, rec), r in zip(split_records(device_full(ctx, nb, nf, idx, finals, status, cap=len(want) + 4096, oc=True)[0]), kept):
         assert oc.oc_of_record(rec)[0] == ([oc.text_of(r["cigar"])] if changed[r["name"]] else []), r["name"]
     # the reads handed in one by one and four at a time: every call's records are those of the one call
     for kw in (dict(), ALL_TAGS):
@@ -93,13 +73,13 @@ def test_device_equals_host(ctx, tmp_path, which):
         for size in (1, 4):
             got = []
             for lo in range(0, len(idx), size):
-                got += split_records(device_oc(ctx, nb, nf, idx[lo:lo + size], finals[lo:lo + size], status[lo:lo + size],
-                                               sum(len(r) for _, r in want), **kw))
+                got += split_records(device_full(ctx, nb, nf, idx[lo:lo + size], finals[lo:lo + size], status[lo:lo + size],
+                                                 cap=sum(len(r) for _, r in want) + 4096, oc=True, **kw)[0])
             assert [r for _, r in got] == [r for _, r in want], (kw, size)
     if which == "oc":                                            # the same reads picked in another order, in one call
         pick = np.random.default_rng(3).integers(0, len(records), 200)
         want = nb.format_bam_full(nf, idx[pick], [finals[k] for k in pick], status[pick], oc=True, **ALL_TAGS)
-        assert device_oc(ctx, nb, nf, idx[pick], [finals[k] for k in pick], status[pick], len(want), **ALL_TAGS) == want
+        assert device_full(ctx, nb, nf, idx[pick], [finals[k] for k in pick], status[pick], cap=len(want) + 4096, oc=True, **ALL_TAGS)[0] == want
     nb.close(); nf.close()
 
 

@@ -17,6 +17,7 @@ from test_bam_out import Hdr, check_index, header_len, members, split_records
 import bam_full_cases as fc
 import bam_pass_cases as pc
 import long_cigar_cases as lc
+from full_record_driver import device_full
 
 pytestmark = pytest.mark.gpu
 MASK = 0x904
@@ -72,25 +73,6 @@ def case(ctx, tmp_path_factory):
     cfg.args = old
 
 
-def device_pass(ctx, nb, nf, idx, finals, status, mask, md=False, cs=None, de=False):
-    """(record bytes, nm[n], md_len[n]) of npore_debug_format_bam_full_pass_device"""
-    idx = np.ascontiguousarray(idx, np.int64)
-    n = len(idx)
-    fb = [f.encode() for f in finals]
-    fo = np.zeros(n + 1, np.int64)
-    np.cumsum([len(f) for f in fb], out=fo[1:])
-    fl = np.ascontiguousarray(np.diff(fo))
-    buf = np.frombuffer(b"".join(fb) + b"\0", np.uint8)
-    st = np.ascontiguousarray(status, np.int32)
-    fmap = nb.fasta_map(nf)
-    cap = sum(len(r) for r in fc.input_records(nb.path)) * 3 + (1 << 16)
-    recs, nm, mdl, got = np.zeros(cap, np.uint8), np.full(n, -1, np.int32), np.full(n, -1, np.int32), C.c_int64()
-    nb._check(nb._lib.npore_debug_format_bam_full_pass_device(ctx.handle, nb.handle, nf.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data,
-                                                              fo.ctypes.data, fl.ctypes.data, st.ctypes.data, recs.ctypes.data, cap, C.byref(got),
-                                                              nm.ctypes.data, 32 if md else 0, mdl.ctypes.data, bam.output_tags(cs, de), mask))
-    return recs[:got.value].tobytes(), nm, mdl
-
-
 # ---- 1. the device against the host twin -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mask", [0x904, 0x100, 0x800, 0x4, 0])
 def test_device_equals_host_twin(ctx, case, mask):
@@ -102,7 +84,7 @@ def test_device_equals_host_twin(ctx, case, mask):
     status = np.array([st_of.get(int(k), 0) for k in idx], np.int32)
     for kw in (dict(), dict(md=True), TAGS):
         want = nb.format_bam_full(nf, idx, finals, status, pass_mask=mask, **kw)
-        got, nm, mdl = device_pass(ctx, nb, nf, idx, finals, status, mask, **kw)
+        got, nm, mdl = device_full(ctx, nb, nf, idx, finals, status, mask=mask, **kw)
         assert got == want, (mask, kw)
         for k, i in enumerate(idx):
             if pc.passes(flags[i], mask):
@@ -252,19 +234,16 @@ def test_device_ladder_forwards_agree(ctx, case):
         idx = np.array(pc.py_select(case["raws"], [(0, 0, 1 << 28), (1, 0, 1 << 28)], 0, mask), np.int64)
         finals = [final_of.get(int(k), "") for k in idx]
         status = np.array([st_of.get(int(k), 0) for k in idx], np.int32)
-        n, flags, tags = len(idx), 32 if md else 0, bam.output_tags(cs, de)
-        fb = [f.encode() for f in finals]
-        fo = np.zeros(n + 1, np.int64)
-        np.cumsum([len(f) for f in fb], out=fo[1:])
-        fl, buf = np.ascontiguousarray(np.diff(fo)), np.frombuffer(b"".join(fb) + b"\0", np.uint8)
+        n, flags, tags = len(idx), bam.OUT_MD if md else 0, bam.output_tags(cs, de)
+        _keep, reads = bam.marshal_finals(idx, finals, status)
         want = nb.format_bam_full(nf, idx, finals, status, md=md, cs=cs, de=de, pass_mask=mask)
         assert len(split_records(want)) == n - 1
 
         def run(entry, *more):
             recs, nm, mdl, got = np.zeros(cap, np.uint8), np.full(n, -1, np.int32), np.full(n, -1, np.int32), C.c_int64()
             more = tuple(mdl.ctypes.data if m is Ellipsis else m for m in more)
-            nb._check(getattr(lib, entry)(ctx.handle, nb.handle, nf.handle, fmap.ctypes.data, idx.ctypes.data, n, buf.ctypes.data, fo.ctypes.data,
-                                          fl.ctypes.data, status.ctypes.data, recs.ctypes.data, cap, C.byref(got), nm.ctypes.data, *more))
+            nb._check(getattr(lib, entry)(ctx.handle, nb.handle, nf.handle, fmap.ctypes.data, *reads, recs.ctypes.data, cap, C.byref(got),
+                                          nm.ctypes.data, *more))
             return recs[:got.value].tobytes(), nm.tolist(), mdl.tolist() if md else None
 
         wide = run("npore_debug_format_bam_full_pass_device", flags, ..., tags, mask)

@@ -242,13 +242,13 @@ NPORE_HD void shr_small(const Env &env, const Tab &tab, const CellIn &in, int j,
     const float cand0 = cstart0 + s0;
     // (FAST: a lane without a candidate holds an empty descriptor, whose score is +infinity -- np_small -- so its
     // candidate never passes the compare; what the band-edge and out-of-band lanes pick up is never read)
-    const bool take0 = (FAST || (act0 && j - n0 >= 0)) && cand0 < shrv;
+    const bool take0 = (FAST || (act0 && j - n0 >= 0)) && cand0 < shrv; NPORE_SHR2_ENTRY(shrv);
     shrv = take0 ? cand0 : shrv;
     shrrun = take0 ? run0 + n0 : shrrun;                              // :654 / :667
     shrstart = take0 ? cstart0 : shrstart;
     if constexpr (TWO) {
         const float cand1 = cstart1 + s1;
-        const bool take1 = (FAST || (act1 && j - n1 >= 0)) && cand1 < shrv;
+        const bool take1 = (FAST || (act1 && j - n1 >= 0)) && cand1 < shrv; NPORE_SHR2_NOTE(in.c, j, act1, take0, take1, cand0, cand1);
         shrv = take1 ? cand1 : shrv;
         shrrun = take1 ? run1 + n1 : shrrun;
         shrstart = take1 ? cstart1 : shrstart;

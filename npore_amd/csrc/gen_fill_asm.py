@@ -97,7 +97,7 @@ E0, E1 = "v89", "v90"
 CIDX, CRCP, CBASE, CPER = "%[cidx]", "%[crcp]", "%[cbase]", "%[cper]"
 CSF, CTWO, CNONE = "%[csf]", "%[ctwo]", "%[cnone]"
 PAD = {"valu": 0, "salu": 0, "bperm": 0}        # timing-only: --pad KIND:N extra instructions at the head of every step
-ABLATE = {"nopoll": False, "nolen": False}      # timing-only ablations (wrong strings): --nopoll / --nolen with --out FILE
+ABLATE = {"nopoll": False, "nolen": False, "notwo": False}      # timing-only ablations (wrong strings): --nopoll / --nolen / --notwo with --out FILE
 
 
 def col_cache(t, mid, none_test, smr):
@@ -222,8 +222,9 @@ def shr_pass(t, mid, sfx, shadow, shadow2, none_test=True):
         shadow()
         t(f"s_branch {L('shr_done2' + sfx)}")
         t.common()
+    # (--notwo: the second candidate is ignored -- the same two instructions, the branch never taken)
     t(f"""
-        s_cmp_lg_u64 {CTWO}, 0
+        s_cmp_lg_u64 {CTWO}, {CTWO if ABLATE["notwo"] else 0}
         s_cbranch_scc1 {L('shr_two' + sfx)}
     """)
     # ---- one candidate per column
@@ -248,14 +249,17 @@ def shr_pass(t, mid, sfx, shadow, shadow2, none_test=True):
     """)
     t.label("shr_done2" + sfx)
     # ---- two candidates (second in rc1): its lane tables and record now, then both scores, then the compares in
-    # the reference's order
+    # the reference's order.  (The lane-table reads take rc1 as it is, like cell.hpp's shr_small: a lane address is
+    # bits 2 ... 7 of the word, the period lies in bits 2 ... 4, and the lane tables repeat every 8 lanes, so whatever
+    # bits 5 ... 7 hold -- BIGL and MORE can be set in a second descriptor: in a dead or edge lane, whose candidate
+    # does not count; a live lane holds no rare column inside the loop -- the lane read is the period's entry.  The LEN
+    # loop reads lane 33 for a lane without a period on the same ground.  A ds_bpermute cannot fault.)
     t.rare()
     t.label("shr_two" + sfx)
     t(f"""
-        v_and_b32 {X3}, 28, {O('rc1')}
-        ds_bpermute_b32 {X4}, {X3}, {O('tab')}
-        ds_bpermute_b32 {X5}, {X3}, {O('trecip')}
-        v_cmp_gt_i32 {O('sa')}, 0, {O('rc1')}
+        ds_bpermute_b32 {X4}, {O('rc1')}, {O('tab')}
+        ds_bpermute_b32 {P1}, {O('rc1')}, {O('trecip')}
+        v_cmp_gt_i32 vcc, 0, {O('rc1')}
         v_lshrrev_b32 {HP1}, 16, {HP1}
         v_cndmask_b32 {HS}, {HP0}, {HS}, {CSF}
         v_cndmask_b32 {HP1}, {HP1}, 0, {CSF}
@@ -265,17 +269,15 @@ def shr_pass(t, mid, sfx, shadow, shadow2, none_test=True):
         v_lshl_add_u32 {E0}, {E1}, 2, {CBASE}
         s_waitcnt lgkmcnt(0)
         v_add_u32 {X4}, {O('hca')}, {X4}
-        ds_read_b32 {E1}, {X4}
-        ds_read_b64 v[98:99], {X4} offset:8
+        ds_read_b128 v[96:99], {X4}
         ds_read_b32 {E0}, {E0}
     """)
-    shadow2()                # (X4 X5 SE SF E0 E1 SD P0 P1 are in use; leaves X3 = refx & seqw)
+    shadow2()                # (X4 X5 SE SF E0 SD P0 P1 are in use; leaves X3 = refx & seqw)
     t(f"""
         s_waitcnt lgkmcnt(0)
-        v_lshrrev_b32 {SF}, 16, {SF}
-        v_cndmask_b32 {SF}, {SF}, 0, {O('sa')}
-        v_cndmask_b32 {E1}, {SE}, {E1}, {O('sa')}
-        v_mul_u32_u24 {X5}, {SF}, {X5}
+        v_cndmask_b32_sdwa {SF}, {SF}, 0, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD
+        v_cndmask_b32 {E1}, {SE}, {X4}, vcc
+        v_mul_u32_u24 {X5}, {SF}, {P1}
         v_bfe_u32 {X4}, {O('rc1')}, 15, 16
         v_min_u32_sdwa {X5}, {X5}, {O('rc1')} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:BYTE_1
         v_bfe_u32 {SE}, {O('rc1')}, 2, 3
@@ -290,7 +292,6 @@ def shr_pass(t, mid, sfx, shadow, shadow2, none_test=True):
         s_waitcnt lgkmcnt(0)
         v_add_f32 {X4}, {E1}, {X4}
         v_cmp_lt_f32 vcc, {X4}, {SHRV}
-        s_nop 1
         v_cndmask_b32 {SHRV}, {SHRV}, {X4}, vcc
         v_cndmask_b32 {SHRRUN}, {SHRRUN}, {SF}, vcc
         v_cndmask_b32 {SHRST}, {SHRST}, {E1}, vcc
@@ -299,84 +300,78 @@ def shr_pass(t, mid, sfx, shadow, shadow2, none_test=True):
     t.common()
 
 
-def len_pass(t, mid, sfx, mode, first, last, multi):
-    """LEN candidates (cell.hpp, LEN loop; LEN_ARITH form).  On entry X3 = the six "read position i-n in an n-polymer
-    and reference position j starts one" bits.  The loop is out of line (two steps in three have no candidate).
-    Free: X4 X5 SD SE SF P0 P1 E0 E1.  (Lengths of 32 and more -- `big` -- are read from the full table in global memory; the
-    LDS read of that lane then lands somewhere in the LDS and is not used: its index is formed without range masks.)"""
-    if not mid:
-        t(f"v_cndmask_b32 {X3}, 0, {X3}, {O('mhist')}")
-    if ABLATE["nolen"]:
-        t(f"v_mov_b32 {X3}, 0")
-    t(f"""
-        v_cmp_ne_u32 vcc, 0, {X3}
-        s_cbranch_vccnz {L('len_body' + sfx)}
-    """)
-    t.rare()
-    t.label("len_top" + sfx)
-    t(f"""
-        v_cmp_ne_u32 vcc, 0, {X3}
-        s_cbranch_vccz {L('len_done' + sfx)}
-        s_branch {L('len_iter' + sfx)}
-    """)
-    t.label("len_body" + sfx)
-    t(f"""
-        v_mov_b32 {LENV}, {O('ev')}
-        v_mov_b32 {LENRUN}, 0
-    """)
-    t.label("len_iter" + sfx)
+def len_filter(t, fail):
+    """one iteration's filter (vcc = lanes with a period left in X3): the lane's highest period n = k + 1 leaves X3, and
+    the n most recent read bases (the top 3n bits of seqw) are compared with the next n reference bases (refx from bit 14
+    up).  Leaves X4 = k, sa = the lanes that had a period, sb = those of them whose n-mer matches; none: to `fail`.
+    (A lane without a period has k = 32: whatever it computes here and behind is masked by sa / sb.)"""
     t(f"""
         s_mov_b64 {O('sa')}, vcc
         v_ffbh_u32 {X4}, {X3}
         v_sub_u32 {X4}, 31, {X4}
         v_bfe_u32 {X3}, {X3}, 0, {X4}
         v_mad_i32_i24 {X5}, {X4}, -3, 29
-        v_lshrrev_b32 {SD}, 14, {O('refx')}
+        v_mad_u32_u24 {SD}, {X4}, 3, 3
         v_lshrrev_b32 {SE}, {X5}, {O('seqw')}
-        v_xor_b32 {SE}, {SE}, {SD}
-        v_lshlrev_b32 {SE}, {X5}, {SE}
-        v_cmp_eq_u32 {O('sb')}, 0, {SE}
+        v_bfe_u32 {SD}, {O('refx')}, 14, {SD}
+        v_cmp_eq_u32 {O('sb')}, {SE}, {SD}
         s_and_b64 {O('sb')}, {O('sb')}, {O('sa')}
-        s_cbranch_scc0 {L('len_top' + sfx)}
-        v_add_u32 {SF}, 1, {X4}
-        v_lshlrev_b32 {E0}, 2, {SF}
+        s_cbranch_scc0 {L(fail)}
+    """)
+
+
+def len_eval(t, tag, first_match):
+    """the LEN candidate of the lanes in sb (period n = k + 1, k in X4) against the best so far.  first_match: the step's
+    first evaluation -- nothing has set LENV / LENRUN up, the selects take `ev` / 0 in their place (LENST holds +inf)"""
+    # ---- the candidate of the lanes in sb (period n = k + 1): where its source record lies and the lane's 1/n from the
+    # lane tables, L of reference position j from the window (byte k of its 8), then the record, the score and the
+    # compare.  A lane without a period has k = 32, which no mask takes back: its lane address 4 k + 4 selects lane 33
+    # (the lane tables repeat every 8 lanes: a valid entry, of period 1), and in its window address the 32 is ORed into
+    # the ring index that wmask8 has already masked -- it sets bit 2 of that index, another position INSIDE the window.
+    # Both reads stay in range; the lane drops what they return (sb).
+    t(f"""
+        v_lshl_add_u32 {E0}, {X4}, 2, 4
         ds_bpermute_b32 {E1}, {E0}, {O('tab')}
         ds_bpermute_b32 {X5}, {E0}, {O('trecip')}
         v_bfe_u32 {SD}, {O('seqw')}, {X4}, 1
         v_cmp_ne_u32 {O('sc')}, 0, {SD}
-        v_add_u32 {SD}, {O('sdel')}, {O('lanej')}
-        v_and_b32 {SD}, {O('wmask')}, {SD}
-        v_and_b32 {X4}, 7, {X4}
-        v_lshl_add_u32 {SD}, {SD}, 3, {X4}
+        v_add_lshl_u32 {SD}, {O('sdel')}, {O('lanej')}, 3
+        v_and_or_b32 {SD}, {SD}, {O('wmask8')}, {X4}
         v_add_u32 {SD}, {O('winaddr')}, {SD}
         ds_read_u8 {SD}, {SD}
         s_waitcnt lgkmcnt(0)
         v_lshl_add_u32 {E1}, {E0}, 2, {E1}
         v_add_u32 {E1}, {O('hca')}, {E1}
         ds_read_b64 {PP}, {E1}
-        ds_read_b32 {E0}, {E1} offset:12
+        ds_read_u16 {E0}, {E1} offset:12
         v_cmp_ne_u32 {O('sa')}, 0, {SD}
-        v_cmp_ge_u32 vcc, {O('clamp1')}, {SF}
+        v_cmp_ge_u32 vcc, {O('clampv')}, {X4}
         s_and_b64 {O('sa')}, {O('sa')}, vcc
         s_waitcnt lgkmcnt(0)
+    """)
+    # run = the record's low half (read alone), 0 where the candidate starts a run; q + 1 = (run / n + 65536) >> 16 is
+    # the high half of one multiply-add; call = min(clampv, L + q + 1).  (32-bit arithmetic: exact while run * (1/n) +
+    # 65536 < 2^32, that is for every run below 65535 -- at n = 1, 1/n = 65536, a run of 65535 would wrap to q + 1 = 0.
+    # A run is shorter than the chunk has rows, and the host refuses max_b_rows above 60 000 (align_engine.hpp, where the
+    # 16-bit run fields of the history record set the same limit): whoever raises that limit has to widen this first.)
+    # The score's byte address in the LDS table,
+    # ((k << 5 | L) * 34 + 31 - call) * 4, is formed as (k << 5 | L) * 136 - 4 call, the 124 in the read's offset
+    # field (never negative where it counts: L >= 1 and call <= 31).  `big`: call > 31 (L <= call, both clamped alike,
+    # so L alone is never the reason)
+    t(f"""
         v_cndmask_b32 {P0}, {P1}, {P0}, {O('sc')}
-        v_and_b32 {E0}, 0xffff, {E0}
         v_cndmask_b32 {E0}, {E0}, 0, {O('sc')}
-        v_mul_u32_u24 {P1}, {E0}, {X5}
-        v_lshrrev_b32 {P1}, 16, {P1}
-        v_add3_u32 {P1}, {SD}, {P1}, 1
+        v_mad_u32_u24 {P1}, {E0}, {X5}, {O('c64k')}
+        v_add_u32_sdwa {P1}, {P1}, {SD} dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD
         v_min_u32 {SD}, {O('clampv')}, {SD}
         v_min_u32 {P1}, {O('clampv')}, {P1}
-        v_or_b32 {SE}, {SD}, {P1}
-        v_cmp_lt_u32 vcc, 31, {SE}
+        v_cmp_lt_u32 vcc, 31, {P1}
         v_lshl_or_b32 {SE}, {X4}, 5, {SD}
-        v_mul_u32_u24 {SE}, {NP_CT}, {SE}
-        v_sub_u32 {SE}, {SE}, {P1}
-        v_add_u32 {SE}, 31, {SE}
-        v_lshlrev_b32 {SE}, 2, {SE}
-        ds_read_b32 {SE}, {SE}
+        v_mul_u32_u24 {SE}, {4 * NP_CT}, {SE}
+        v_mad_i32_i24 {SE}, {P1}, -4, {SE}
+        ds_read_b32 {SE}, {SE} offset:124
         s_and_b64 vcc, vcc, {O('sb')}
-        s_cbranch_vccz {L('len_lds' + sfx)}
+        s_cbranch_vccz {L('len_lds' + tag)}
         s_waitcnt lgkmcnt(0)
         s_mov_b64 exec, vcc
         v_mul_lo_u32 {X5}, {X4}, {O('npdim')}
@@ -388,20 +383,59 @@ def len_pass(t, mid, sfx, mode, first, last, multi):
         s_waitcnt vmcnt(0)
         s_mov_b64 exec, -1
     """)
-    t.label("len_lds" + sfx)
+    t.label("len_lds" + tag)
     t(f"""
         s_waitcnt lgkmcnt(0)
-        s_mov_b64 vcc, {O('sa')}
-        v_cndmask_b32 {SE}, {O('c100')}, {SE}, vcc
+        v_cndmask_b32 {SE}, {O('c100')}, {SE}, {O('sa')}
         v_add_f32 {SE}, {P0}, {SE}
-        v_add_u32 {E0}, {E0}, {SF}
-        v_cmp_lt_f32 vcc, {SE}, {LENV}
+        v_add3_u32 {E0}, {E0}, {X4}, 1
+        v_cmp_lt_f32 vcc, {SE}, {O('ev') if first_match else LENV}
         s_and_b64 vcc, vcc, {O('sb')}
-        v_cndmask_b32 {LENV}, {LENV}, {SE}, vcc
-        v_cndmask_b32 {LENRUN}, {LENRUN}, {E0}, vcc
+        v_cndmask_b32 {LENV}, {O('ev') if first_match else LENV}, {SE}, vcc
+        v_cndmask_b32 {LENRUN}, {0 if first_match else LENRUN}, {E0}, vcc
         v_cndmask_b32 {LENST}, {LENST}, {P0}, vcc
-        s_branch {L('len_top' + sfx)}
     """)
+
+
+def len_pass(t, mid, sfx, mode, first, last, multi):
+    """LEN candidates (cell.hpp, LEN loop; LEN_ARITH form).  On entry X3 = the six "read position i-n in an n-polymer
+    and reference position j starts one" bits.  The loop is out of line (two steps in three have no candidate).
+    Free: X4 X5 SD SE SF P0 P1 E0 E1.  (Lengths of 32 and more -- `big` -- are read from the full table in global memory; the
+    LDS read of that lane then lands somewhere in the LDS and is not used: its index is formed without range masks.)
+    Two phases.  Until a lane's n-mer has matched nothing of the step depends on the loop: the filter alone runs
+    (len_body / len_topA), and a step whose flagged lanes all fail it goes back to the common tail (len_none) as if it
+    had had no candidate -- LENV / LENRUN are not set up, LENST is untouched.  The first match's evaluation sets them
+    up in its selects (len_eval, emitted twice); from there on the loop (len_top) ends in the tail that reads them.
+    (The second copy of len_eval is about 50 instructions per step kind, 0.4 KB of a role's text of about 6 KB against an
+    instruction cache of 64 KB; it saves the two v_mov of a set-up and the branch back on a step's first match.  Most
+    of the loop's gain is the other half of the split: the exit of a step without a match through the common tail.)"""
+    if not mid:
+        t(f"v_cndmask_b32 {X3}, 0, {X3}, {O('mhist')}")
+    if ABLATE["nolen"]:
+        t(f"v_mov_b32 {X3}, 0")
+    t(f"""
+        v_cmp_ne_u32 vcc, 0, {X3}
+        s_cbranch_vccnz {L('len_body' + sfx)}
+    """)
+    t.label("len_none" + sfx)
+    t.rare()
+    t.label("len_topA" + sfx)
+    t(f"""
+        v_cmp_ne_u32 vcc, 0, {X3}
+        s_cbranch_vccz {L('len_none' + sfx)}
+    """)
+    t.label("len_body" + sfx)
+    len_filter(t, "len_topA" + sfx)
+    len_eval(t, sfx + "a", True)
+    # (falls into the loop's test: the periods that are left, highest first)
+    t.label("len_top" + sfx)
+    t(f"""
+        v_cmp_ne_u32 vcc, 0, {X3}
+        s_cbranch_vccz {L('len_done' + sfx)}
+    """)
+    len_filter(t, "len_top" + sfx)
+    len_eval(t, sfx + "b", False)
+    t(f"s_branch {L('len_top' + sfx)}")
     t.label("len_done" + sfx)
     mat_part(t, mode, True, mid, first, last)
     # The record's ds_write_b128 has just been issued, and LENST is one of its four data registers: an LDS write of
@@ -1116,7 +1150,7 @@ def operands(role):
     ins = [("stepsg", "s", "steps_g"), ("laneid", "v", "a_laneid"), ("b1", "s", "a_b1"), ("hw16", "s", "a_hw16"), ("ringb", "s", "ring_bytes"),
            ("tbs4", "s", "tbstride4"), ("n0", "s", "env.n0_lanes"), ("tbg", "s", "tb_g"), ("istart", "s", "a_istart"),
            ("iext", "s", "a_iext"), ("winaddr", "s", "a_winaddr"), ("wmask", "s", "a_wmask"), ("clampv", "s", "a_clampv"),
-           ("clamp1", "s", "a_clamp1"), ("npdim", "s", "a_npdim"), ("gnp", "s", "env.g_np"),
+           ("c64k", "s", "a_c64k"), ("wmask8", "s", "a_wmask8"), ("npdim", "s", "a_npdim"), ("gnp", "s", "env.g_np"),
            ("hca", "v", "hist_c_addr"), ("trecip", "v", "env.t_recip"), ("one", "v", "a_one"), ("lanej", "v", "a_lanej"),
            ("inf", "v", "a_inf"), ("c100", "v", "a_c100"),
            ("oneI", "v", "a_oneI"), ("oneD", "v", "a_oneD"), ("tagS", "v", "a_tagS"), ("livebc", "v", "a_livebc")]
@@ -1142,9 +1176,9 @@ def main():
     here = os.path.dirname(os.path.abspath(__file__))
     out_path = os.path.join(here, "fill_step_asm.inc")
     args = sys.argv[1:]
-    while args:                      # timing-only variants: --nopoll / --nolen / --pad KIND:N, with --out FILE
+    while args:                      # timing-only variants: --nopoll / --nolen / --notwo / --pad KIND:N, with --out FILE
         a = args.pop(0)
-        if a in ("--nopoll", "--nolen"):
+        if a in ("--nopoll", "--nolen", "--notwo"):
             ABLATE[a[2:]] = True
         elif a == "--pad":               # timing-only: KIND:N, KIND in valu / salu / bperm
             kind, n = args.pop(0).split(":")

@@ -863,7 +863,9 @@ __global__ __launch_bounds__(MAXT) __attribute__((amdgpu_waves_per_eu(4, 4), amd
             int a_bl = b0, a_sdel = uni(st.del_l);      // (uni: the compiler does not always see that these are wave-uniform)
             const int a_b1 = b1;
             const uint32_t a_hw16 = (uint32_t)env.hw16, a_wmask = (uint32_t)env.wmask, a_clampv = (uint32_t)env.clampv,
-                           a_clamp1 = (uint32_t)env.clampv + 1u, a_npdim = (uint32_t)env.np_dim;
+                           a_npdim = (uint32_t)env.np_dim,
+                           a_wmask8 = (uint32_t)env.wmask << 3;      // (the L window's ring mask over byte addresses)
+            const uint32_t a_c64k = 0x10000u;               // (the text's LEN pass: q + 1 from one multiply-add)
             const float a_istart = st.indel_start, a_iext = st.indel_extend;
             const uint32_t a_winaddr = (uint32_t)(reinterpret_cast<const char *>(win) - reinterpret_cast<const char *>(lds));
             const unsigned long long a_mhist = __builtin_amdgcn_ballot_w64(hist_lane), a_ml0 = 1ull, a_ml63 = 1ull << 63,

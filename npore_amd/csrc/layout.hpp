@@ -135,3 +135,10 @@ struct alignas(16) ChunkDesc {
 static inline int tb_stride(int r) { return ((2 * r + 1) + 3) & ~3; }
 
 }  // namespace npore
+
+// Test twins only (tests/model/shr2_twin.cpp defines them before this header): what the two-candidate block of
+// cell.hpp's shr_small saw and decided for one cell.  Nothing in the product: both expand to nothing.
+#if !defined(NPORE_SHR2_ENTRY)
+#define NPORE_SHR2_ENTRY(shrv_in) ((void)0)
+#define NPORE_SHR2_NOTE(c, j, act1, take0, take1, cand0, cand1) ((void)0)
+#endif

@@ -366,6 +366,11 @@ int plan_group(const AlignArgs &a, int64_t g0, int64_t g1, GroupPlan &p)
     return NPORE_OK;
 }
 
+// A staged group's offset block (h_off here, in_off on the device): five arrays of nr + 1 offsets behind each other, in this
+// order -- of the refs, the seqs, the CIGARs, the output slots (BAM records: the final's words) and the record heads
+enum GroupOff : int { OFF_REF = 0, OFF_SEQ, OFF_CIG, OFF_OUT, OFF_RAW, OFF_ARRAYS };
+template <class T> T *group_off(T *block, int which, int64_t nr) { return block + which * (nr + 1); }
+
 // Every buffer of the work set the group's stages use, each under the condition of its use, before the first enqueue
 // (a buffer that grows is a hipFree, which synchronises the device)
 int reserve_group(WorkSet *w, const GroupPlan &p, const AlignArgs &a)
@@ -394,11 +399,11 @@ int reserve_group(WorkSet *w, const GroupPlan &p, const AlignArgs &a)
         if (int rc = b->ensure(mc * 4 + 64)) return rc;
     if (int rc = w->h_cnt.ensure(64)) return rc;
     if (!p.staged) return NPORE_OK;
-    if (int rc = w->h_off.ensure(5 * (nr + 1) * 8)) return rc;
+    if (int rc = w->h_off.ensure(OFF_ARRAYS * (nr + 1) * 8)) return rc;
     if (int rc = w->in_refs.ensure((size_t)p.R_tot + 64)) return rc;
     if (int rc = w->in_seqs.ensure((size_t)p.S_tot + 64)) return rc;
     if (int rc = w->in_cigs.ensure((size_t)p.cig_bytes + 64)) return rc;
-    if (int rc = w->in_off.ensure(5 * (nr + 1) * 8)) return rc;
+    if (int rc = w->in_off.ensure(OFF_ARRAYS * (nr + 1) * 8)) return rc;
     if (int rc = w->out.ensure((size_t)p.out_bytes + 64)) return rc;
     if (int rc = w->out_len.ensure(nr * 8)) return rc;
     if (int rc = w->status.ensure(nr * 4)) return rc;
@@ -413,7 +418,7 @@ int reserve_group(WorkSet *w, const GroupPlan &p, const AlignArgs &a)
 
 // The device addresses of a group whose buffers are reserved: the preparation's arrays (the later stages read them from
 // here) and, in `out` (on entry the caller's device arrays), where the output tail writes.  A staged group has its own slice
-// in the work set (in_off: offsets of refs, seqs, CIGARs, output slots, record heads, nr + 1 each), any other the caller's arrays.
+// in the work set (in_off: GroupOff), any other the caller's arrays.
 PrepParams wire_group(const npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs &a, OutTarget &out)
 {
     const int64_t nr = p.nr;
@@ -421,10 +426,10 @@ PrepParams wire_group(const npore_ctx *ctx, WorkSet *w, const GroupPlan &p, cons
     pp.n_reads = nr;
     if (p.staged) {
         const int64_t *d_off = w->in_off.as<int64_t>();
-        pp.refs = w->in_refs.as<uint8_t>(); pp.ref_off = d_off;
-        pp.seqs = w->in_seqs.as<uint8_t>(); pp.seq_off = d_off + (nr + 1);
-        pp.cigs = w->in_cigs.as<char>(); pp.cig_off = d_off + 2 * (nr + 1);
-        out = OutTarget{w->out.as<uint8_t>(), d_off + 3 * (nr + 1), w->out_len.as<int64_t>(), w->status.as<int32_t>(), 0};
+        pp.refs = w->in_refs.as<uint8_t>(); pp.ref_off = group_off(d_off, OFF_REF, nr);
+        pp.seqs = w->in_seqs.as<uint8_t>(); pp.seq_off = group_off(d_off, OFF_SEQ, nr);
+        pp.cigs = w->in_cigs.as<char>(); pp.cig_off = group_off(d_off, OFF_CIG, nr);
+        out = OutTarget{w->out.as<uint8_t>(), group_off(d_off, OFF_OUT, nr), w->out_len.as<int64_t>(), w->status.as<int32_t>(), 0};
     } else {
         pp.refs = a.d_refs; pp.ref_off = a.d_ref_off + p.g0;
         pp.seqs = a.d_seqs; pp.seq_off = a.d_seq_off + p.g0;
@@ -452,11 +457,11 @@ UnpackParams wire_unpack(WorkSet *w, int64_t nr, const CtgEntry *ctg, int n_ctg,
 {
     const int64_t *d_off = w->in_off.as<int64_t>();
     UnpackParams up;
-    up.raw = w->in_raw.as<uint8_t>(); up.raw_off = d_off + 4 * (nr + 1);
+    up.raw = w->in_raw.as<uint8_t>(); up.raw_off = group_off(d_off, OFF_RAW, nr);
     up.ctg = ctg; up.n_ctg = n_ctg;
-    up.refs = w->in_refs.as<uint8_t>(); up.ref_off = d_off;
-    up.seqs = w->in_seqs.as<uint8_t>(); up.seq_off = d_off + (nr + 1);
-    up.cigs = w->in_cigs.as<char>(); up.cig_off = d_off + 2 * (nr + 1);
+    up.refs = w->in_refs.as<uint8_t>(); up.ref_off = group_off(d_off, OFF_REF, nr);
+    up.seqs = w->in_seqs.as<uint8_t>(); up.seq_off = group_off(d_off, OFF_SEQ, nr);
+    up.cigs = w->in_cigs.as<char>(); up.cig_off = group_off(d_off, OFF_CIG, nr);
     up.n_reads = nr;
     up.pass_mask = pass_mask;
     return up;
@@ -465,12 +470,12 @@ UnpackParams wire_unpack(WorkSet *w, int64_t nr, const CtgEntry *ctg, int n_ctg,
 // own slice: read_base 0), for the records `rec` names, into the record buffer recs / cap / cursor
 BamEmitParams wire_bam_emit(WorkSet *w, int64_t nr, uint8_t *recs, int64_t cap, unsigned long long *cursor, const RecSpec &rec)
 {
-    const int64_t *d_off = w->in_off.as<int64_t>();      // (offsets of refs, seqs, CIGARs, output slots, record heads, nr + 1 each)
+    const int64_t *d_off = w->in_off.as<int64_t>();
     BamEmitParams bp;
-    bp.raw = w->in_raw.as<uint8_t>(); bp.raw_off = d_off + 4 * (nr + 1);
-    bp.ref_off = d_off; bp.seq_off = d_off + (nr + 1);
+    bp.raw = w->in_raw.as<uint8_t>(); bp.raw_off = group_off(d_off, OFF_RAW, nr);
+    bp.ref_off = group_off(d_off, OFF_REF, nr); bp.seq_off = group_off(d_off, OFF_SEQ, nr);
     bp.hp = w->in_hp.as<int64_t>();
-    bp.words = w->out.as<uint8_t>(); bp.words_off = d_off + 3 * (nr + 1); bp.words_len = w->out_len.as<int64_t>(); bp.status = w->status.as<int32_t>();
+    bp.words = w->out.as<uint8_t>(); bp.words_off = group_off(d_off, OFF_OUT, nr); bp.words_len = w->out_len.as<int64_t>(); bp.status = w->status.as<int32_t>();
     bp.read_base = 0; bp.n_reads = nr;
     bp.recs = recs; bp.cap = cap; bp.cursor = cursor;
     bp.rec_off = w->rec_off.as<int64_t>(); bp.rec_len = w->rec_len.as<int64_t>();
@@ -493,12 +498,13 @@ int upload_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs
 {
     hipStream_t s = ctx->stream;
     const int64_t nr = p.nr, g0 = p.g0;
-    int64_t *ho = w->h_off.as<int64_t>(), *hro = ho, *hso = ho + (nr + 1), *hco = ho + 2 * (nr + 1), *hoo = ho + 3 * (nr + 1);
+    int64_t *ho = w->h_off.as<int64_t>(), *hro = group_off(ho, OFF_REF, nr), *hso = group_off(ho, OFF_SEQ, nr), *hco = group_off(ho, OFF_CIG, nr),
+            *hoo = group_off(ho, OFF_OUT, nr), *hraw = group_off(ho, OFF_RAW, nr);
     for (int64_t i = 0; i <= nr; i++) {
         hro[i] = a.h_ref_off[g0 + i] - a.h_ref_off[g0]; hso[i] = a.h_seq_off[g0 + i] - a.h_seq_off[g0];
         hco[i] = a.h_cig_off[g0 + i] - a.h_cig_off[g0]; hoo[i] = a.h_out_off[g0 + i] - a.h_out_off[g0];
     }
-    for (int64_t i = 0; p.raw && i <= nr; i++) ho[4 * (nr + 1) + i] = a.h_raw_off[g0 + i] - a.h_raw_off[g0];
+    for (int64_t i = 0; p.raw && i <= nr; i++) hraw[i] = a.h_raw_off[g0 + i] - a.h_raw_off[g0];
     HIP_TRY(hipEventRecord(w->evc[0], s));
     if (p.raw) {
         HIP_TRY(hipMemcpyAsync(w->in_raw.p, a.h_raw + a.h_raw_off[g0], (size_t)p.raw_bytes, hipMemcpyHostToDevice, s));
@@ -507,7 +513,7 @@ int upload_group(npore_ctx *ctx, WorkSet *w, const GroupPlan &p, const AlignArgs
         HIP_TRY(hipMemcpyAsync(w->in_seqs.p, a.h_seqs + a.h_seq_off[g0], (size_t)p.S_tot, hipMemcpyHostToDevice, s));
         HIP_TRY(hipMemcpyAsync(w->in_cigs.p, a.h_cigs + a.h_cig_off[g0], (size_t)p.cig_bytes, hipMemcpyHostToDevice, s));
     }
-    HIP_TRY(hipMemcpyAsync(w->in_off.p, ho, (size_t)5 * (nr + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(w->in_off.p, ho, (size_t)(group_off(ho, OFF_ARRAYS, nr) - ho) * 8, hipMemcpyHostToDevice, s));
     if (p.mode == OutMode::BamRecords)
         HIP_TRY(hipMemcpyAsync(w->in_hp.p, a.bam->h_hp + g0, (size_t)nr * 8, hipMemcpyHostToDevice, s));
     HIP_TRY(hipEventRecord(w->evc[1], s));

@@ -208,6 +208,39 @@ int slot_pack_arrays(const npore_bam *b, const npore_fasta *fa, const int32_t *f
 // batch's record bytes, s.rec_cap (its terms: hostio.hpp).
 // FULL records: the kept aux bytes behind the qualities (STAGE_FULL) and their number in the HP values' place.
 // A record that passes (RecSpec::pass_mask, staged_head.hpp): the block_size word and the whole record are staged.
+// THE plan of the staged heads of the n records in rf, whoever stages them (the file pipeline below, the debug entry of
+// npore_api.cpp): a read on a contig that is not in the FASTA is refused; raw_off[n + 1]: the heads one after the other, each
+// as long as stage_record(form) makes it, no padding between them; BAM out (form above STAGE_HEAD) also hp[n]: the read's HP
+// value, the kept aux bytes of a FULL record, 0 for a record that passes -- and the sum of record_bound (hostio.hpp) over the
+// records, read k's final as long as extent_of(k) says.  seq_off: the reads' slices of unclipped bases (pack_sizes_of).
+template <class ExtentOf>
+int plan_staged_heads(const npore_bam *b, const RecFetch &rf, int64_t n, const int32_t *fasta_of_ref, int n_fasta, const RecSpec &rec, int form,
+                      const int64_t *seq_off, int64_t *raw_off, int64_t *hp, int64_t *bound, ExtentOf extent_of)
+{
+    const bool records = form != STAGE_HEAD;
+    raw_off[0] = 0;
+    if (records) *bound = 0;
+    for (int64_t k = 0; k < n; k++) {
+        const RecView r = rec_of(rf, k);
+        const int32_t rid = r.ref_id();
+        const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
+        if (fi < 0 || fi >= n_fasta) return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
+        RecMeasures m{r.l_read_name(), r.l_seq(), seq_off[k + 1] - seq_off[k], 0, 0, staged_passes(r.p, rec.pass_mask) ? staged_pass_bytes(r.p) : 0};
+        int64_t head = m.pass_bytes, hp_k = 0;
+        if (!m.pass_bytes) {
+            const RecCigar cg = rec_cigar(r);
+            m.in_words = cg.n;
+            m.aux = form == STAGE_FULL ? filter_aux(r.aux(), r.end(), nullptr, rec.oc()) : 0;
+            head = staged_head_bytes(r, cg, records ? STAGE_QUALS : STAGE_HEAD, false) + m.aux;
+            hp_k = !records ? 0 : form == STAGE_FULL ? m.aux : rec_hp(r);
+        }
+        raw_off[k + 1] = raw_off[k] + head;
+        if (!records) continue;
+        hp[k] = hp_k;
+        *bound += record_bound(rec, m, extent_of(k));
+    }
+    return NPORE_OK;
+}
 int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta, int threads, npore_batch_slot &s, const PipeMode &pm)
 {
     const int64_t n = s.m;
@@ -215,29 +248,11 @@ int slot_pack_heads(const npore_bam *b, const int32_t *fasta_of_ref, int n_fasta
     s.rec_cap = 0;
     slot_pack_sizes(s, threads, pm);
     s.rawo.assign((size_t)n + 1, 0);
-    for (int64_t k = 0; k < n; k++) {
-        const RecView r = rec_of(s.rf, k);
-        const int32_t rid = r.ref_id();
-        const int fi = (rid >= 0 && rid < (int32_t)b->ref_names.size()) ? fasta_of_ref[rid] : -1;
-        if (fi < 0 || fi >= n_fasta) return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
-        if (staged_passes(r.p, pm.rec.pass_mask)) {
-            s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_pass_bytes(r.p);
-            reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = 0;
-            s.rec_cap += staged_pass_bytes(r.p);
-            continue;
-        }
-        const RecCigar cg = rec_cigar(r);
-        const int64_t aux = pm.rec.full ? filter_aux(r.aux(), r.end(), nullptr, pm.rec.oc()) : 0;
-        s.rawo[(size_t)k + 1] = s.rawo[(size_t)k] + staged_head_bytes(r, cg, pm.bam ? STAGE_QUALS : STAGE_HEAD, false) + aux;
-        if (pm.bam) {          // (a final CIGAR has no more words than the read's reference positions and bases: the slot's size too)
-            const int64_t rl = s.ro[(size_t)k + 1] - s.ro[(size_t)k], sl = s.so[(size_t)k + 1] - s.so[(size_t)k];
-            reinterpret_cast<int64_t *>(s.hp_pin.p)[k] = pm.rec.full ? aux : rec_hp(r);
-            s.rec_cap += pm.rec.full ? full_record_bound(r.l_read_name(), rl + sl, r.l_seq(), aux) : ref_record_bound(r.l_read_name(), rl + sl, sl);
-            if (pm.rec.md) s.rec_cap += md_tag_bound(rl, 1);
-            if (pm.rec.cs_de()) s.rec_cap += cs_de_tags_bound(rl + sl);      // (NPORE_CIGAR_EQX adds nothing: eqx_rec.hpp, Size)
-            if (pm.rec.oc()) s.rec_cap += oc_tag_bound(cg.n);
-        }
-    }
+    // (a batch's own final covers the read's reference positions and bases, no more: the size of its slot too)
+    if (int rc = plan_staged_heads(b, s.rf, n, fasta_of_ref, n_fasta, pm.rec, pm.stage_form(), s.so.data(), s.rawo.data(),
+                                   reinterpret_cast<int64_t *>(s.hp_pin.p), &s.rec_cap,
+                                   [&](int64_t k) { return own_final_extent(s.ro[(size_t)k + 1] - s.ro[(size_t)k], s.so[(size_t)k + 1] - s.so[(size_t)k]); }))
+        return rc;
     if (int rc = s.raw.ensure((size_t)s.rawo[(size_t)n] + 64)) return rc;
     const int64_t per = 16;
     parallel_for((n + per - 1) / per, threads, [&](int64_t t) {
@@ -307,24 +322,32 @@ int slot_enqueue(npore_ctx *ctx, npore_batch_slot &s, const PipeMode &pm, const 
 // ---- collect: what the device left of the batch (s.olen, status) into what the writer takes (s.sam / s.recs_pin, s.meta) ------
 // BAM mode, records built on the device: nothing is formatted here -- the batch's bytes as they lie there, into page-locked
 // memory, and from the records' lengths what the writer's index needs (reference, position and span are the input record's)
+// What the emit kernels left of n records, wherever it is fetched (below, the debug entry): no length negative (a record that
+// did not fit), the lengths add up to the cursor, the cursor within the buffer's bound
+int check_record_sizes(const int64_t *len, int64_t n, int64_t total, int64_t bound)
+{
+    if (total < 0 || total > bound) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
+    int64_t sum = 0;
+    for (int64_t k = 0; k < n; k++) {
+        if (len[k] < 0) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
+        sum += len[k];
+    }
+    return sum == total ? NPORE_OK : fail(NPORE_E_HIP, "internal: BAM record sizes do not add up");
+}
 int slot_fetch_records(const int32_t *status, npore_batch_slot &s, const PipeMode &pm)
 {
     const int64_t total = (int64_t)*reinterpret_cast<const unsigned long long *>(s.total_pin.p);
     const int64_t *len = reinterpret_cast<const int64_t *>(s.reclen_pin.p);
-    if (total < 0 || total > s.rec_cap) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
-    int64_t sum = 0;
+    if (int rc = check_record_sizes(len, s.m, total, s.rec_cap)) return rc;
     s.meta.clear();
     for (int64_t k = 0; k < s.m; k++) {
-        if (len[k] < 0) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
         if ((len[k] == 0) != ((status[k] & NPORE_ST_BAD_INPUT) != 0)) return fail(NPORE_E_HIP, "internal: BAM records and status bits disagree");
         if (len[k] == 0) continue;
         const RecView r = rec_of(s.rf, k);
         // (a record that passed gave align() no reference slice: the index takes the input record's own reference length)
         const int64_t span = staged_passes(r.p, pm.rec.pass_mask) ? rec_ref_len(r) : s.ro[(size_t)k + 1] - s.ro[(size_t)k];
         s.meta.push_back(BamRecMeta{r.ref_id(), r.pos(), span, len[k]});
-        sum += len[k];
     }
-    if (sum != total) return fail(NPORE_E_HIP, "internal: BAM record sizes do not add up");
     const char *src = s.d_recs.p;
     int64_t bytes = total;
     if (pm.dev_deflate()) {          // exactly the coded members and the two raw fragments around them

@@ -42,6 +42,7 @@
 #include "../../include/npore_amd.h"
 #include "glue.hpp"
 #include "staged_head.hpp"
+#include "nm_rec.hpp"
 
 namespace npore {
 
@@ -855,11 +856,8 @@ inline int64_t staged_head_bytes(const uint8_t *rec, int form) { return staged_h
 inline void stage_record_head(const uint8_t *rec, int form, uint8_t *dst) { stage_record_head(rec, form, dst, false); }
 // A RUN's record under its spec (there is no default: a run names what it writes).  A record that passes (staged_head.hpp
 // record_passes; STAGE_FULL only) is staged verbatim -- the block_size word and the whole record as it lies in the stream, every
-// tag, a long CIGAR still placeholder + CG tag, n_cigar_op and bin untouched; every other record is a read: its head
-inline int64_t staged_record_bytes(const uint8_t *rec, int form, const RecSpec &spec)
-{
-    return form == STAGE_FULL && staged_passes(rec + 4, spec.pass_mask) ? staged_pass_bytes(rec + 4) : staged_head_bytes(rec, form, spec.oc());
-}
+// tag, a long CIGAR still placeholder + CG tag, n_cigar_op and bin untouched; every other record is a read: its head.  How
+// many bytes either takes, and where in a batch it starts: file_pipeline.hpp plan_staged_heads
 inline void stage_record(const uint8_t *rec, int form, uint8_t *dst, const RecSpec &spec)
 {
     if (form == STAGE_FULL && staged_passes(rec + 4, spec.pass_mask)) std::memcpy(dst, rec, (size_t)staged_pass_bytes(rec + 4));
@@ -876,11 +874,51 @@ inline void stage_record(const uint8_t *rec, int form, uint8_t *dst, const RecSp
 // takes exactly its staged_pass_bytes (staged_head.hpp) -- an ML-like array of tens of kilobytes included.
 // OC (oc_rec.hpp): the tag's four bytes and, for each of the input's `words` real CIGAR words, its letter and a length of at most
 // 28 bits, which has at most 9 digits -- ten bytes a word; only a changed read has the tag, the bound is taken for every read.
+// =/X form (eqx_rec.hpp, Size): a word per compared position more than the final has at the most, four bytes each.
 inline int64_t ref_record_bound(int64_t name, int64_t words, int64_t sl) { return 36 + name + 4 * words + 16 + (sl + 1) / 2 + sl + 7 + 16; }
 inline int64_t full_record_bound(int64_t name, int64_t words, int64_t l_seq, int64_t aux) { return 36 + name + 4 * words + 32 + (l_seq + 1) / 2 + l_seq + aux + 7 + 16; }
 inline int64_t md_tag_bound(int64_t ref_covered, int64_t counts) { return 4 + 3 * ref_covered + 11 * counts; }
 inline int64_t cs_de_tags_bound(int64_t bases_covered) { return 4 + 3 * bases_covered + 7; }
 inline int64_t oc_tag_bound(int64_t words) { return 4 + 10 * words; }
+
+// The bound is record_bound() and nothing else: the named terms above have no other caller.  Its inputs are a record's own
+// measures and the EXTENT of its final CIGAR -- what the final's words number and cover, which is all the terms ask of them.
+struct RecMeasures {
+    int64_t name, l_seq, sl;              // l_read_name (the NUL counted), all bases, the unclipped ones
+    int64_t aux, in_words;                // the kept aux bytes (filter_aux under the run's spec), the words of the input's real CIGAR
+    int64_t pass_bytes;                   // > 0: the record passes and takes these bytes (staged_pass_bytes), whatever else says
+};
+struct FinalExtent {
+    int64_t words, ref_covered, md_counts, bases_covered;      // bases_covered: reference positions + read bases, as cs_de_tags_bound takes them
+    int64_t eqx_extra;                    // words the =/X form may have beyond `words`
+};
+// ... of a batch's own final: it covers the read's rl reference positions and sl bases exactly, so it has no more words than
+// rl + sl, closes one MD count, and its =/X form has no more than one word per position and base either (eqx_rec.hpp, Size)
+inline FinalExtent own_final_extent(int64_t rl, int64_t sl) { return FinalExtent{rl + sl, rl, 1, rl + sl, 0}; }
+// ... of a caller's n final words at w (little-endian, unaligned): they may run past the reference or the read and close a count
+// at every word; the =/X form has at most a word per compared position more
+inline FinalExtent words_final_extent(const uint8_t *w, int64_t n)
+{
+    FinalExtent e{n, 0, n + 1, 0, 0};
+    for (int64_t q = 0; q < n; q++) {
+        const uint32_t v = rd32(w + 4 * q), use = nm_consumes(v & 15u);
+        if (use & 1u) e.ref_covered += v >> 4;
+        if (use) e.bases_covered += v >> 4;
+        if (nm_compares(v & 15u)) e.eqx_extra += v >> 4;
+    }
+    return e;
+}
+inline int64_t record_bound(const RecSpec &rec, const RecMeasures &m, const FinalExtent &e)
+{
+    if (m.pass_bytes > 0) return m.pass_bytes;
+    if (!rec.full) return ref_record_bound(m.name, e.words, m.sl);
+    int64_t bound = full_record_bound(m.name, e.words, m.l_seq, m.aux);
+    if (rec.md) bound += md_tag_bound(e.ref_covered, e.md_counts);
+    if (rec.cs_de()) bound += cs_de_tags_bound(e.bases_covered);
+    if (rec.eqx()) bound += 4 * e.eqx_extra;
+    if (rec.oc()) bound += oc_tag_bound(m.in_words);
+    return bound;
+}
 
 // integer HP tag or 0 (src/bam.pyx:46)
 inline int64_t rec_hp(const RecView &r)

@@ -1591,40 +1591,26 @@ try {
     if (int rc = device_fasta(ctx, b, fa, fasta_of_ref)) return rc;
     RecFetch &rf = b->api_fetch;
     if (int rc = fetch_records(b, idx, n, 0, rf)) return rc;
-    // stage: sizes, staged heads, the finals as words in slots at multiples of 4, the record buffer's bound (hostio.hpp)
+    // stage: sizes, the finals as words in slots at multiples of 4, and the file pipeline's plan of the staged heads with the
+    // bound of a caller's final (plan_staged_heads; hostio.hpp words_final_extent)
     const size_t N = (size_t)n;
-    std::vector<int64_t> off(5 * (N + 1), 0), aux(N, 0), wlen(N, 0);       // ref, seq, cig, words, raw offsets
-    int64_t *ro = off.data(), *so = ro + (N + 1), *co = so + (N + 1), *wo = co + (N + 1), *rawo = wo + (N + 1);
+    std::vector<int64_t> off(OFF_ARRAYS * (N + 1), 0), aux(N, 0), wlen(N, 0);
+    int64_t *ro = group_off(off.data(), OFF_REF, n), *so = group_off(off.data(), OFF_SEQ, n), *co = group_off(off.data(), OFF_CIG, n),
+            *wo = group_off(off.data(), OFF_OUT, n), *rawo = group_off(off.data(), OFF_RAW, n);
     pack_sizes_of(rf, n, ro, so, co, 0, rec.pass_mask);
     std::vector<std::vector<uint8_t>> fin(N);
-    int64_t bound = 0;
     for (size_t k = 0; k < N; k++) {
-        const RecView r = rec_of(rf, (int64_t)k);
-        const int32_t rid = r.ref_id();
-        if (rid < 0 || rid >= (int32_t)b->ref_names.size() || fasta_of_ref[rid] < 0 || fasta_of_ref[rid] >= (int)fa->names.size())
-            return fail(NPORE_E_INVALID, "a selected read lies on a contig that is not in the FASTA");
-        const bool pass = staged_passes(r.p, rec.pass_mask), bad = (status[k] & NPORE_ST_BAD_INPUT) != 0;
-        const int64_t ops = (bad || pass) ? 0 : cigar_text_ops(finals + final_off[k], final_len[k]);
+        const bool skip = (status[k] & NPORE_ST_BAD_INPUT) || staged_passes(rec_of(rf, (int64_t)k).p, rec.pass_mask);
+        const int64_t ops = skip ? 0 : cigar_text_ops(finals + final_off[k], final_len[k]);
         if (ops < 0) return fail(NPORE_E_UNSUPPORTED, "a final CIGAR is no CIGAR text (BAM output)");
-        aux[k] = pass ? 0 : filter_aux(r.aux(), r.end(), nullptr, rec.oc());
+        if (!skip) fin[k] = cigar_text_words(finals + final_off[k], final_len[k], ops);
         wlen[k] = 4 * ops;
         wo[k + 1] = wo[k] + 4 * ops + 16;
-        rawo[k + 1] = rawo[k] + ((staged_record_bytes(rf.ptr[k], STAGE_FULL, rec) + 7) & ~7ll);
-        bound += pass ? staged_pass_bytes(r.p) : full_record_bound(r.l_read_name(), ops, r.l_seq(), aux[k]);
-        if (bad || pass) continue;
-        if (rec.oc()) bound += oc_tag_bound(rec_cigar(r).n);
-        fin[k] = cigar_text_words(finals + final_off[k], final_len[k], ops);
-        int64_t ref_covered = 0, covered = 0, compared = 0;      // (a caller's final may cover more reference than the read has, and close a count at every word)
-        for (int64_t q = 0; q < ops; q++) {
-            const uint32_t w = rd32(fin[k].data() + 4 * q), use = nm_consumes(w & 15u);
-            if (use & 1u) ref_covered += w >> 4;
-            if (use) covered += w >> 4;
-            if (nm_compares(w & 15u)) compared += w >> 4;
-        }
-        if (rec.md) bound += md_tag_bound(ref_covered, ops + 1);
-        if (rec.cs_de()) bound += cs_de_tags_bound(covered);
-        if (rec.eqx()) bound += 4 * compared;      // (=/X form: at most a word per compared position more, eqx_rec.hpp)
     }
+    int64_t bound = 0;
+    if (int rc = plan_staged_heads(b, rf, n, fasta_of_ref, (int)fa->names.size(), rec, STAGE_FULL, so, rawo, aux.data(), &bound,
+                                   [&](int64_t k) { return words_final_extent(fin[(size_t)k].data(), wlen[(size_t)k] / 4); }))
+        return rc;
     std::vector<uint8_t> raw((size_t)rawo[N] + 64, 0), words((size_t)wo[N] + 64, 0);
     for (size_t k = 0; k < N; k++) {
         stage_record(rf.ptr[k], STAGE_FULL, raw.data() + rawo[k], rec);
@@ -1659,12 +1645,7 @@ try {
     HIP_TRY(hipMemcpy(rlen.data(), w.rec_len.p, N * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(nm, w.nm.p, N * 4, hipMemcpyDeviceToHost));
     if (rec.md) HIP_TRY(hipMemcpy(md_len, w.md_len.p, N * 4, hipMemcpyDeviceToHost));
-    int64_t sum = 0;
-    for (size_t k = 0; k < N; k++) {
-        if (rlen[k] < 0) return fail(NPORE_E_HIP, "internal: BAM record buffer overflow");
-        sum += rlen[k];
-    }
-    if ((int64_t)total > bound || sum != (int64_t)total) return fail(NPORE_E_HIP, "internal: BAM record sizes do not add up");
+    if (int rc = check_record_sizes(rlen.data(), n, (int64_t)total, bound)) return rc;
     if ((int64_t)total > cap) return fail(NPORE_E_INVALID, "the records need more room than the caller gave");
     if (total > 0) HIP_TRY(hipMemcpy(recs, d_recs.p, (size_t)total, hipMemcpyDeviceToHost));
     *recs_len = (int64_t)total;

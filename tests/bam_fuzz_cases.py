@@ -207,7 +207,7 @@ SITUATIONS = (["compared_run_over_tile_seam"] + [f"tile_first_{o}_behind_open_{c
                "final_fewer_words", "final_more_words", "unchanged", "changed", "md_count_10_over_round_seam", "md_count_100_over_round_seam",
                "cs_count_10_over_round_seam", "cs_count_100_over_round_seam", "nm_one_byte", "nm_two_bytes", "final_past_reference",
                "final_past_read", "final_short_of_reference", "final_short_of_read", "empty_final", "refused", "passes_under_0x904",
-               "own_oc_tag", "no_qualities"] + [f"clip_shape_{j}" for j in range(len(fc.CLIPS))])
+               "own_oc_tag", "no_qualities"] + [f"clip_shape_{j}" for j in range(len(fc.CLIPS))] + [f"head_offset_mod8_{j}" for j in range(8)])
 
 
 def _differs(rc, sc, a, b, n):
@@ -253,13 +253,26 @@ def _count_seams(fin, rc, sc, closers):
     return hit
 
 
+def staged_full_head_bytes(rec):
+    """the bytes of a read's staged FULL head (csrc/hostio.hpp staged heads: block_size word, fixed fields, name with its NUL, CIGAR
+    words, 4-bit bases, qualities, the kept aux bytes) under no option oc; a CIGAR of more than 65 535 words is not modelled"""
+    l_seq = sum(n for op, n in rec["cigar"] if op in lc.CONSUMES_QUERY)      # (the bases the CIGAR consumes: a record's l_seq)
+    return 4 + 32 + len(rec["name"]) + 1 + 4 * len(rec["cigar"]) + (l_seq + 1) // 2 + l_seq + len(bam.filter_aux(rec["tags"]))
+
+
 def situations(records, finals, packs):
-    """{situation: how many reads hit it} of reads, their final CIGARs and their code arrays [(reference codes, read codes)]"""
+    """{situation: how many reads hit it} of reads, their final CIGARs and their code arrays [(reference codes, read codes)].
+    head_offset_mod8_j: the reads, refused ones too, whose staged FULL head starts at j modulo 8 where the heads of the whole
+    batch lie one after the other in this order, as the file pipeline and the debug entry stage them
+    (csrc/file_pipeline.hpp plan_staged_heads): the unpack and emit kernels read a head from any alignment."""
     count = {s: 0 for s in SITUATIONS}
 
     def seen(name, yes=True):
         count[name] += bool(yes)
+    head = 0                                                     # where the read's staged head starts (below)
     for rec, final, (rc, sc) in zip(records, finals, packs):
+        seen(f"head_offset_mod8_{head % 8}")                     # (a refused read's head is staged and unpacked like any other)
+        head += staged_full_head_bytes(rec)
         if rec["_status"] & 32:
             seen("refused")
             continue

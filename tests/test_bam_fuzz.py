@@ -2,8 +2,8 @@
 seed; inputs over M I D = X P with words of length 0 and clips, finals that are the input's canonical form, a near miss of it, the
 input's words as they stand, or unrelated words over all nine ops) under all 48 option sets md x cs {none, short, long} x de x eqx
 x oc -- the host twin npore_bam_format_bam_full_pass against the Python statement, byte for byte, without and with a pass mask;
-the report of which seam of the device walks each seed hits; and the record buffer's bound as the file pipeline sums it
-(tests/model/record_bounds.cpp over csrc/hostio.hpp's terms) against the statement's record sizes.  No GPU here: the device side
+the report of which seam of the device walks each seed hits; and the record buffer's bound as the file pipeline and the debug
+entry sum it (tests/model/record_bounds.cpp over csrc/hostio.hpp's record_bound) against the statement's record sizes.  No GPU here: the device side
 of the same reads is tests/test_gpu_bam_fuzz.py.
 
 The statement is assembled from each read's tag texts, computed once (bam_fuzz_cases.read_texts / assemble); one seed goes
@@ -173,10 +173,14 @@ def terms_of(l_rn, rl, sl, l_seq, aux, words, kw):
 
 
 def test_record_bound_holds(tmp_path, seeds):
-    """The file pipeline's bound of a batch's record bytes is a sum over its reads (csrc/file_pipeline.hpp slot_pack_heads); a
-    term that is too small fails a run with "BAM record buffer overflow" on the one read dense enough.  Per read and option set:
-    the statement's record is no longer than the sum, and the sum is what the terms' own statement gives -- no more.  The reads:
-    those of every seed whose final is the input's canonical form or a near miss of it, and bam_fuzz_cases.dense_reads.
+    """The file pipeline's bound of a batch's record bytes is a sum over its reads of csrc/hostio.hpp's record_bound
+    (csrc/file_pipeline.hpp plan_staged_heads, which slot_pack_heads and the debug entry both are); a term that is too small
+    fails a run with "BAM record buffer overflow" on the one read dense enough.  Per read and option set: the statement's
+    record is no longer than the sum, and the sum is what the terms' own statement gives -- no more.  The reads: those of
+    every seed whose final is the input's canonical form or a near miss of it, and bam_fuzz_cases.dense_reads.
+    The bound of a CALLER's final words (the debug entry's: words_final_extent) is held to the statement's record on every
+    read of every seed that is not refused -- finals past or short of the reference or the read and empty finals included --
+    and on the dense reads.
     Measured (printed, not asserted): the largest bound / size is 12.83 -- 1078 bytes for a record of 84 -- on seed 108's read
     `qqqq40`, 5H 127D 2M under de + oc: de alone takes the whole cs term, three bytes per covered position, for a tag of seven.
     Among the dense reads the bound is closest on `md` ((1M 1D) x 300, all differing) under md alone, 1.35, and on `mi`
@@ -186,16 +190,19 @@ def test_record_bound_holds(tmp_path, seeds):
         pytest.skip("no g++")
     exe = str(tmp_path / "record_bounds")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-o", exe, os.path.join(REPO, "tests", "model", "record_bounds.cpp"), "-lz", "-pthread"])
-    reads = []                                                   # (name, raw, rc, sc, final, texts or None)
+    reads, own = [], []                                          # (name, raw, rc, sc, final, texts); whether the final is a batch's own
     for seed, s in seeds.items():
-        reads += [(f"{seed}:{r['name']}", raw, rc, sc, fin, t) for k, (r, raw, (rc, sc), fin, t) in
-                  enumerate(zip(s["records"], s["raws"], s["packs"], s["finals"], s["texts"])) if k % 4 < 2 and not r["_status"] & 32]
+        for k, (r, raw, (rc, sc), fin, t) in enumerate(zip(s["records"], s["raws"], s["packs"], s["finals"], s["texts"])):
+            if not r["_status"] & 32:
+                reads.append((f"{seed}:{r['name']}", raw, rc, sc, fin, t))
+                own.append(k % 4 < 2)
     references, refs, records, finals = fz.dense_reads()
     bp, _ = fc.write_inputs(tmp_path, references, refs, records, "dense")
     for r, raw, fin in zip(records, fc.input_records(bp), finals):
         rc, sc, _ = lc.expected_pack(r, r["cigar"], refs["ctg"])
         reads.append((r["name"], raw, rc, sc, fin, fz.read_texts(raw, rc, sc, fin)))
-    assert len(reads) > 120
+        own.append(True)
+    assert sum(own) > 120 and len(own) - sum(own) > 120
     rows = []
     for name, raw, rc, sc, fin, t in reads:
         aux = t["aux"]
@@ -204,14 +211,25 @@ def test_record_bound_holds(tmp_path, seeds):
     cases = str(tmp_path / "reads.bin")
     with open(cases, "wb") as fh:
         fh.write(b"".join(struct.pack("<7q", *row) for row in rows))
-    out = subprocess.run([exe, cases], capture_output=True, text=True, timeout=120)
+    callers = str(tmp_path / "finals.bin")                       # per read: the count and the words of its final, as a caller gives them
+    with open(callers, "wb") as fh:
+        for name, raw, rc, sc, fin, t in reads:
+            words = [(n << 4) | op for op, n in oc.runs_of(fin)]
+            fh.write(struct.pack(f"<q{len(words)}I", len(words), *words))
+    out = subprocess.run([exe, cases, callers], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr[-2000:]
     bounds = [[int(x) for x in line.split()] for line in out.stdout.splitlines()]
-    assert len(bounds) == len(reads) and all(len(b) == 48 for b in bounds)
+    assert len(bounds) == 2 * len(reads) and all(len(b) == 48 for b in bounds)
+    bounds, caller_bounds = bounds[:len(reads)], bounds[len(reads):]
+    sizes = [[len(fz.assemble(t, **kw)) for kw in fz.OPTION_SETS] for name, raw, rc, sc, fin, t in reads]
+    for (name, *_), size, bound in zip(reads, sizes, caller_bounds):
+        for kw, sz, cap in zip(fz.OPTION_SETS, size, bound):
+            assert sz <= cap, ("a caller's final", name, fz.set_name(kw), sz, cap)
+    keep = [k for k, o in enumerate(own) if o]                   # from here on: the file pipeline's bound, of a batch's own finals
+    reads, rows, bounds, sizes = ([v[k] for k in keep] for v in (reads, rows, bounds, sizes))
     worst, best = (0.0, None), (1e9, None)
-    for (name, raw, rc, sc, fin, t), row, bound in zip(reads, rows, bounds):
-        for kw, cap in zip(fz.OPTION_SETS, bound):
-            size = len(fz.assemble(t, **kw))
+    for (name, raw, rc, sc, fin, t), row, bound, size_row in zip(reads, rows, bounds, sizes):
+        for kw, cap, size in zip(fz.OPTION_SETS, bound, size_row):
             fixed, allowed = terms_of(row[0], row[1], row[2], row[3], row[5] if kw["oc"] else row[4], row[6], kw)
             assert size <= cap, (name, fz.set_name(kw), size, cap)
             assert cap == fixed + allowed and size >= fixed, (name, fz.set_name(kw), size, cap, fixed, allowed)
